@@ -66,6 +66,20 @@ def grad_report(items, factor=4.0, floor_l1=3e-3, floor_max=2.5e-2):
     return bad
 
 
+def bn_fed_biases(net):
+    """{conv bias: bias of the BatchNorm right behind it} for every such pair inside one nn.Sequential of `net`.  In train mode the
+    BatchNorm subtracts the batch mean, so the conv bias's gradient is analytically zero and what any implementation computes for it
+    is rounding noise (the CPU oracle's fp32 value moves across 1e-8 with the host's thread count)."""
+    out = {}
+    for name, m in net.named_modules():
+        if isinstance(m, torch.nn.Sequential):
+            for i in range(len(m) - 1):
+                if isinstance(m[i], torch.nn.modules.conv._ConvNd) and m[i].bias is not None and \
+                        isinstance(m[i + 1], torch.nn.modules.batchnorm._BatchNorm):
+                    out[f"{name}.{i}.bias"] = f"{name}.{i + 1}.bias"
+    return out
+
+
 def no_stochastic(nets):
     for n in nets:
         for m in n.modules():
@@ -357,8 +371,14 @@ def test_bf16_math(dev, nets, storage):
         assert bool(torch.isfinite(a.grad).all()), k
     assert float((featd.grad.cpu() - feat.grad).abs().sum() / feat.grad.abs().sum()) < 0.3
     for p, o in ((pn[1], ocp[1]), (pn[2], ocp[2]), (pn[3], ocp[3])):
+        zero, og = bn_fed_biases(o), dict(o.named_parameters())
         for (k, a), (_, b) in zip(p.named_parameters(), o.named_parameters()):
-            if float(b.grad.abs().max()) > 1e-8:
+            if k in zero:
+                # analytically zero: an L1 ratio of two rounding noises means nothing; the HIP value stays at rounding level,
+                # far below the gradient of the BatchNorm shift behind the conv
+                hz, bn = float(a.grad.abs().max()), float(og[zero[k]].grad.abs().max())
+                assert hz < 0.1 * bn, (type(p).__name__, k, hz, bn)
+            elif float(b.grad.abs().max()) > 1e-8:
                 l1 = float((a.grad.cpu() - b.grad).abs().sum() / b.grad.abs().sum())
                 assert l1 < 0.3, (type(p).__name__, k, l1)
 
