@@ -275,6 +275,12 @@ int sv_dwconv2x2_fwd(const void* x, const float* w, const float* b, void* y, int
 int sv_dwconv2x2_bwd(const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int I, int C, int act_dtype, void* stream);
 int sv_upsample3to7_add_fwd(const void* small, const void* x, int ldx, void* y, int I, int C, int act_dtype, void* stream); /* cross_view_attention.py:110-120 */
 int sv_upsample3to7_bwd(const void* dy, void* dsmall, int I, int C, int act_dtype, void* stream);
+/* the same four at ATT_SPATIAL_DOWNSAMPLE_RATIO r in {2, 4, 5, 6, 7}: grid g = (7-r)/r+1 (3x3 at r = 2, 1x1 at r >= 4); weight [C,1,r,r];
+ * small / dy of the conv are [I*g*g, C]; every other r (3, <= 1, >= 8) is refused (SV_ERR_INVALID).  The 2x2 / 3to7 entries above are r = 2. */
+int sv_cva_downsample_fwd(const void* x, const float* w, const float* b, void* y, int I, int C, int r, int act_dtype, void* stream); /* cross_view_attention.py:26-32,68 */
+int sv_cva_downsample_bwd(const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int I, int C, int r, int act_dtype, void* stream);
+int sv_cva_upsample_add_fwd(const void* small, const void* x, int ldx, void* y, int I, int C, int r, int act_dtype, void* stream); /* cross_view_attention.py:110-120 */
+int sv_cva_upsample_bwd(const void* dy, void* dsmall, int I, int C, int r, int act_dtype, void* stream);
 int sv_decoder_head_fwd(const void* x8, const float* w, const float* bias, void* raw12, void* vol, long long M, int act_dtype, void* stream); /* decoder.py:83-94 */
 int sv_decoder_head_bwd(const void* draw12, const void* dvol, const void* x8, const float* w, void* dx8, float* dw, float* dbias,
                         long long M, int act_dtype, void* stream);

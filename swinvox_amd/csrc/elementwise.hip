@@ -275,62 +275,70 @@ __global__ __launch_bounds__(256) void rowscale_vec_kernel(const AT* __restrict_
 }
 
 // ---- cross-view attention spatial path (cross_view_attention.py:26-32,68 and :110-120)
-// depthwise 2x2 stride-2 conv 7->3 (native weight [C,1,2,2])
-template <typename AT>
+// depthwise R x R stride-R conv 7 -> G = (7 - R) / R + 1 (native weight [C,1,R,R]): R = 2 is the 7 -> 3 default, R = 4 ... 7 a 1 x 1 grid
+// that reads the top-left R x R positions of each map.  R (and G) are template arguments: the R = 2 instances compile to the code of the
+// 2x2 kernels they replaced, so ratio 2 keeps its results bit for bit.
+__host__ __device__ constexpr int cva_grid(int r) { return (7 - r) / r + 1; }
+template <typename AT, int R>
 __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const AT* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                          AT* __restrict__ y, int I, int C) {
-  const long long total = (long long)I * 9 * C;
+  constexpr int G = cva_grid(R);
+  const long long total = (long long)I * G * G * C;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C); long long t = i / C;
-    const int ox = (int)(t % 3); t /= 3; const int oy = (int)(t % 3); const int n = (int)(t / 3);
+    const int ox = (int)(t % G); t /= G; const int oy = (int)(t % G); const int n = (int)(t / G);
     float s = b ? b[c] : 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) s += ldf(x + (((size_t)n * 7 + oy * 2 + (k >> 1)) * 7 + ox * 2 + (k & 1)) * C + c) * w[c * 4 + k];
+    for (int k = 0; k < R * R; ++k) s += ldf(x + (((size_t)n * 7 + oy * R + k / R) * 7 + ox * R + k % R) * C + c) * w[c * R * R + k];
     stf(y + i, s);
   }
 }
-// dx (all 49 positions; row/col 6 receive 0)
-template <typename AT>
+// dx (all 49 positions; rows / columns >= G*R are not read by the conv and receive 0)
+template <typename AT, int R>
 __global__ __launch_bounds__(256) void dwconv_bwd_dx_kernel(const AT* __restrict__ dy, const float* __restrict__ w, AT* __restrict__ dx,
                                                             int I, int C) {
+  constexpr int G = cva_grid(R);
   const long long total = (long long)I * 49 * C;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C); long long t = i / C;
     const int xq = (int)(t % 7); t /= 7; const int yq = (int)(t % 7); const int n = (int)(t / 7);
     float v = 0.f;
-    if (yq < 6 && xq < 6) v = ldf(dy + (((size_t)n * 3 + yq / 2) * 3 + xq / 2) * C + c) * w[c * 4 + (yq & 1) * 2 + (xq & 1)];
+    if (yq < G * R && xq < G * R) v = ldf(dy + (((size_t)n * G + yq / R) * G + xq / R) * C + c) * w[c * R * R + (yq % R) * R + (xq % R)];
     stf(dx + i, v);
   }
 }
-// dw[c][k], db[c]: one thread per (c,k) walks a slice of the images (grid.y slices, one atomic per slice)
-template <typename AT>
+// dw[c][k], db[c]: one thread per (c, tap k < R*R) walks a slice of the images (grid.y slices, one atomic per slice)
+template <typename AT, int R>
 __global__ __launch_bounds__(256) void dwconv_bwd_w_kernel(const AT* __restrict__ dy, const AT* __restrict__ x, float* __restrict__ dw,
                                                            float* __restrict__ db, int I, int C) {
+  constexpr int G = cva_grid(R);
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= C * 4) return;
-  const int c = i >> 2, k = i & 3;
+  if (i >= C * R * R) return;
+  const int c = i / (R * R), k = i % (R * R);
   float s = 0.f, sb = 0.f;
   const int per = (I + gridDim.y - 1) / gridDim.y;
   const int n0 = blockIdx.y * per, n1 = n0 + per < I ? n0 + per : I;
   for (int n = n0; n < n1; ++n)
-    for (int o = 0; o < 9; ++o) {
-      const int oy = o / 3, ox = o % 3;
-      const float g = ldf(dy + ((size_t)n * 9 + o) * C + c);
-      s += g * ldf(x + (((size_t)n * 7 + oy * 2 + (k >> 1)) * 7 + ox * 2 + (k & 1)) * C + c);
+    for (int o = 0; o < G * G; ++o) {
+      const int oy = o / G, ox = o % G;
+      const float g = ldf(dy + ((size_t)n * G * G + o) * C + c);
+      s += g * ldf(x + (((size_t)n * 7 + oy * R + k / R) * 7 + ox * R + k % R) * C + c);
       sb += g;
     }
   atomicAdd(dw + i, s);
   if (k == 0 && db) atomicAdd(db + c, sb);
 }
-// bilinear 3->7 (align_corners=False) + residual: y = up(small) + x.  Separable taps per output index:
-// src = (dst+0.5)*3/7-0.5 clamped at 0 -> i0 = floor, frac; taps {1,0,0},{6/7,1/7,0},{3/7,4/7,0},{0,1,0},{0,4/7,3/7},{0,1/7,6/7},{0,0,1}
+// bilinear G -> 7 (align_corners=False) + residual: y = up(small) + x.  Separable taps per output index:
+// src = (dst+0.5)*G/7-0.5 clamped at 0 -> i0 = floor, frac, i1 = min(i0+1, G-1).  G = 3: taps {1,0,0},{6/7,1/7,0},{3/7,4/7,0},{0,1,0},
+// {0,4/7,3/7},{0,1/7,6/7},{0,0,1}; G = 1: a broadcast
+template <int G>
 __device__ __forceinline__ void up_taps(int o, int& i0, int& i1, float& w0, float& w1) {
-  float src = (o + 0.5f) * (3.0f / 7.0f) - 0.5f;
+  float src = (o + 0.5f) * ((float)G / 7.0f) - 0.5f;
   if (src < 0.f) src = 0.f;
-  i0 = (int)src; i1 = i0 < 2 ? i0 + 1 : 2;
+  i0 = (int)src; i1 = i0 < G - 1 ? i0 + 1 : G - 1;
   w1 = src - (float)i0; w0 = 1.f - w1;
 }
-template <typename AT>
+template <typename AT, int G>
 __global__ __launch_bounds__(256) void upsample_add_fwd_kernel(const AT* __restrict__ small, const AT* __restrict__ x, int ldx,
                                                                AT* __restrict__ y, int I, int C) {
   const long long total = (long long)I * 49 * C;
@@ -338,26 +346,26 @@ __global__ __launch_bounds__(256) void upsample_add_fwd_kernel(const AT* __restr
     const int c = (int)(i % C); long long t = i / C;
     const int xq = (int)(t % 7); t /= 7; const int yq = (int)(t % 7); const int n = (int)(t / 7);
     int y0, y1, x0, x1; float wy0, wy1, wx0, wx1;
-    up_taps(yq, y0, y1, wy0, wy1); up_taps(xq, x0, x1, wx0, wx1);
-    const AT* s = small + (size_t)n * 9 * C + c;
-    const float v = wy0 * (wx0 * ldf(s + (y0 * 3 + x0) * C) + wx1 * ldf(s + (y0 * 3 + x1) * C)) +
-                    wy1 * (wx0 * ldf(s + (y1 * 3 + x0) * C) + wx1 * ldf(s + (y1 * 3 + x1) * C));
+    up_taps<G>(yq, y0, y1, wy0, wy1); up_taps<G>(xq, x0, x1, wx0, wx1);
+    const AT* s = small + (size_t)n * G * G * C + c;
+    const float v = wy0 * (wx0 * ldf(s + (y0 * G + x0) * C) + wx1 * ldf(s + (y0 * G + x1) * C)) +
+                    wy1 * (wx0 * ldf(s + (y1 * G + x0) * C) + wx1 * ldf(s + (y1 * G + x1) * C));
     stf(y + i, v + ldf(x + (((size_t)n * 7 + yq) * 7 + xq) * ldx + c));
   }
 }
-template <typename AT>
+template <typename AT, int G>
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const AT* __restrict__ dy, AT* __restrict__ dsmall, int I, int C) {
-  const long long total = (long long)I * 9 * C;
+  const long long total = (long long)I * G * G * C;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C); long long t = i / C;
-    const int sx = (int)(t % 3); t /= 3; const int sy = (int)(t % 3); const int n = (int)(t / 3);
+    const int sx = (int)(t % G); t /= G; const int sy = (int)(t % G); const int n = (int)(t / G);
     float acc = 0.f;
     for (int yq = 0; yq < 7; ++yq) {
-      int y0, y1; float wy0, wy1; up_taps(yq, y0, y1, wy0, wy1);
+      int y0, y1; float wy0, wy1; up_taps<G>(yq, y0, y1, wy0, wy1);
       const float wy = (y0 == sy ? wy0 : 0.f) + (y1 == sy ? wy1 : 0.f);
       if (wy == 0.f) continue;
       for (int xq = 0; xq < 7; ++xq) {
-        int x0, x1; float wx0, wx1; up_taps(xq, x0, x1, wx0, wx1);
+        int x0, x1; float wx0, wx1; up_taps<G>(xq, x0, x1, wx0, wx1);
         const float wx = (x0 == sx ? wx0 : 0.f) + (x1 == sx ? wx1 : 0.f);
         if (wx != 0.f) acc += wy * wx * ldf(dy + (((size_t)n * 7 + yq) * 7 + xq) * C + c);
       }
@@ -824,31 +832,72 @@ extern "C" int sv_rowscale(const void* x, const float* scale, void* y, long long
     else hipLaunchKernelGGL(rowscale_kernel<AT>, dim3(grid_for(rows * C)), dim3(256), 0, STREAM, CA(x), scale, MA(y), rows, C, rows_per_scale););
   return check_launch("sv_rowscale");
 }
-extern "C" int sv_dwconv2x2_fwd(const void* x, const float* w, const float* b, void* y, int I, int C, int act_dtype, void* stream) {
-  SV_REQUIRE(x && w && y && I > 0 && C > 0, "dwconv2x2_fwd: bad arguments");
+// ATT_SPATIAL_DOWNSAMPLE_RATIO r in {2, 4, 5, 6, 7}: the ratios the module runs (3, a 2 x 2 grid, is refused there; r >= 8 exceeds the map)
+static int cva_ratio_check(int r, const char* what) {
+  SV_REQUIRE(r == 2 || (r >= 4 && r <= 7), "%s: ATT_SPATIAL_DOWNSAMPLE_RATIO %d unsupported (2, 4, 5, 6 or 7; a kernel of 8 or more "
+             "exceeds the 7x7 map)", what, r);
+  return SV_OK;
+}
+// runs the statement with `constexpr int R` = r (checked by cva_ratio_check)
+#define SV_DISPATCH_RATIO(r, ...)                                          \
+  switch (r) {                                                             \
+    case 2: { constexpr int R = 2; __VA_ARGS__ } break;                    \
+    case 4: { constexpr int R = 4; __VA_ARGS__ } break;                    \
+    case 5: { constexpr int R = 5; __VA_ARGS__ } break;                    \
+    case 6: { constexpr int R = 6; __VA_ARGS__ } break;                    \
+    default: { constexpr int R = 7; __VA_ARGS__ } break;                   \
+  }
+// runs the statement with `constexpr int G` = grid of ratio r: 3 (r = 2) or 1 (r = 4 ... 7)
+#define SV_DISPATCH_GRID(r, ...)                                           \
+  if (cva_grid(r) == 3) { constexpr int G = 3; __VA_ARGS__ }               \
+  else { constexpr int G = 1; __VA_ARGS__ }
+extern "C" int sv_cva_downsample_fwd(const void* x, const float* w, const float* b, void* y, int I, int C, int r, int act_dtype, void* stream) {
+  SV_REQUIRE(x && w && y && I > 0 && C > 0, "cva_downsample_fwd: bad arguments");
+  if (int rc = cva_ratio_check(r, "cva_downsample_fwd")) return rc;
   SV_REQUIRE_ACT(act_dtype);
-  SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(dwconv_fwd_kernel<AT>, dim3(grid_for((long long)I * 9 * C)), dim3(256), 0, STREAM, CA(x), w, b, MA(y), I, C););
-  return check_launch("sv_dwconv2x2_fwd");
+  const int g = cva_grid(r);
+  SV_DISPATCH_ACT(act_dtype, SV_DISPATCH_RATIO(r,
+    hipLaunchKernelGGL((dwconv_fwd_kernel<AT, R>), dim3(grid_for((long long)I * g * g * C)), dim3(256), 0, STREAM, CA(x), w, b, MA(y), I, C);));
+  return check_launch("sv_cva_downsample_fwd");
+}
+extern "C" int sv_cva_downsample_bwd(const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int I, int C, int r,
+                                     int act_dtype, void* stream) {
+  SV_REQUIRE(dy && x && w && dx && dw && I > 0 && C > 0, "cva_downsample_bwd: bad arguments");
+  if (int rc = cva_ratio_check(r, "cva_downsample_bwd")) return rc;
+  SV_REQUIRE_ACT(act_dtype);
+  SV_DISPATCH_ACT(act_dtype, SV_DISPATCH_RATIO(r,
+    hipLaunchKernelGGL((dwconv_bwd_dx_kernel<AT, R>), dim3(grid_for((long long)I * 49 * C)), dim3(256), 0, STREAM, CA(dy), w, MA(dx), I, C);
+    hipLaunchKernelGGL((dwconv_bwd_w_kernel<AT, R>), dim3(cdiv((long long)C * R * R, 256), I < 32 ? I : 32), dim3(256), 0, STREAM, CA(dy), CA(x), dw, db, I, C);));
+  return check_launch("sv_cva_downsample_bwd");
+}
+extern "C" int sv_cva_upsample_add_fwd(const void* small, const void* x, int ldx, void* y, int I, int C, int r, int act_dtype, void* stream) {
+  SV_REQUIRE(small && x && y && I > 0 && C > 0 && ldx >= C, "cva_upsample_add_fwd: bad arguments");
+  if (int rc = cva_ratio_check(r, "cva_upsample_add_fwd")) return rc;
+  SV_REQUIRE_ACT(act_dtype);
+  SV_DISPATCH_ACT(act_dtype, SV_DISPATCH_GRID(r,
+    hipLaunchKernelGGL((upsample_add_fwd_kernel<AT, G>), dim3(grid_for((long long)I * 49 * C)), dim3(256), 0, STREAM, CA(small), CA(x), ldx, MA(y), I, C);));
+  return check_launch("sv_cva_upsample_add_fwd");
+}
+extern "C" int sv_cva_upsample_bwd(const void* dy, void* dsmall, int I, int C, int r, int act_dtype, void* stream) {
+  SV_REQUIRE(dy && dsmall && I > 0 && C > 0, "cva_upsample_bwd: bad arguments");
+  if (int rc = cva_ratio_check(r, "cva_upsample_bwd")) return rc;
+  SV_REQUIRE_ACT(act_dtype);
+  SV_DISPATCH_ACT(act_dtype, SV_DISPATCH_GRID(r,
+    hipLaunchKernelGGL((upsample_bwd_kernel<AT, G>), dim3(grid_for((long long)I * G * G * C)), dim3(256), 0, STREAM, CA(dy), MA(dsmall), I, C);));
+  return check_launch("sv_cva_upsample_bwd");
+}
+// the ratio-2 entry points of the first ABI: the same kernels at r = 2
+extern "C" int sv_dwconv2x2_fwd(const void* x, const float* w, const float* b, void* y, int I, int C, int act_dtype, void* stream) {
+  return sv_cva_downsample_fwd(x, w, b, y, I, C, 2, act_dtype, stream);
 }
 extern "C" int sv_dwconv2x2_bwd(const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int I, int C, int act_dtype, void* stream) {
-  SV_REQUIRE(dy && x && w && dx && dw && I > 0 && C > 0, "dwconv2x2_bwd: bad arguments");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_DISPATCH_ACT(act_dtype,
-    hipLaunchKernelGGL(dwconv_bwd_dx_kernel<AT>, dim3(grid_for((long long)I * 49 * C)), dim3(256), 0, STREAM, CA(dy), w, MA(dx), I, C);
-    hipLaunchKernelGGL(dwconv_bwd_w_kernel<AT>, dim3(cdiv(C * 4, 256), I < 32 ? I : 32), dim3(256), 0, STREAM, CA(dy), CA(x), dw, db, I, C););
-  return check_launch("sv_dwconv2x2_bwd");
+  return sv_cva_downsample_bwd(dy, x, w, dx, dw, db, I, C, 2, act_dtype, stream);
 }
 extern "C" int sv_upsample3to7_add_fwd(const void* small, const void* x, int ldx, void* y, int I, int C, int act_dtype, void* stream) {
-  SV_REQUIRE(small && x && y && I > 0 && C > 0 && ldx >= C, "upsample3to7_add_fwd: bad arguments");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(upsample_add_fwd_kernel<AT>, dim3(grid_for((long long)I * 49 * C)), dim3(256), 0, STREAM, CA(small), CA(x), ldx, MA(y), I, C););
-  return check_launch("sv_upsample3to7_add_fwd");
+  return sv_cva_upsample_add_fwd(small, x, ldx, y, I, C, 2, act_dtype, stream);
 }
 extern "C" int sv_upsample3to7_bwd(const void* dy, void* dsmall, int I, int C, int act_dtype, void* stream) {
-  SV_REQUIRE(dy && dsmall && I > 0 && C > 0, "upsample3to7_bwd: bad arguments");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(upsample_bwd_kernel<AT>, dim3(grid_for((long long)I * 9 * C)), dim3(256), 0, STREAM, CA(dy), MA(dsmall), I, C););
-  return check_launch("sv_upsample3to7_bwd");
+  return sv_cva_upsample_bwd(dy, dsmall, I, C, 2, act_dtype, stream);
 }
 extern "C" int sv_decoder_head_fwd(const void* x8, const float* w, const float* bias, void* raw12, void* vol, long long M, int act_dtype, void* stream) {
   SV_REQUIRE(x8 && w && raw12 && vol && M > 0, "decoder_head_fwd: bad arguments");

@@ -38,20 +38,30 @@ class CrossViewAttention(nn.Module):
     def forward(self, x):  # pragma: no cover - the Encoder drives the kernel chain
         raise RuntimeError("CrossViewAttention runs inside swinvox_amd.models.Encoder (kernel chain cva_forward)")
 
+    def _positions(self):
+        """Positions of the grid the attention runs on: 7x7 at ratio 1, else the g x g output of the stride-r conv,
+        g = (7 - r) // r + 1 (3x3 at ratio 2, 1x1 at ratios 4 ... 7)."""
+        r = self.attention_spatial_downsample_ratio
+        g = 7 if r == 1 else (7 - r) // r + 1
+        return g * g
+
     # ------------------------------------------------------------------------------------------------
     def cva_forward(self, x, B, V, training, stochastic, seeds):
         """x [B*V*49, C] (7x7 maps, channels last) -> same shape."""
         r = self.attention_spatial_downsample_ratio
-        if r not in (1, 2):
-            raise NotImplementedError("swinvox_amd: ATT_SPATIAL_DOWNSAMPLE_RATIO must be 1 (attention on the 7x7 grid) or 2 (7x7 -> 3x3, "
-                                      "the reference default); got %r" % (r,))
+        if r >= 8:
+            raise RuntimeError("swinvox_amd: ATT_SPATIAL_DOWNSAMPLE_RATIO %d: the %dx%d depth-wise kernel exceeds the 7x7 map "
+                               "(the reference's Conv2d fails there as well)" % (r, r, r))
+        if r not in (1, 2, 4, 5, 6, 7):
+            raise NotImplementedError("swinvox_amd: ATT_SPATIAL_DOWNSAMPLE_RATIO must be 1 (attention on the 7x7 grid), 2 (7x7 -> 3x3, "
+                                      "the reference default) or 4 ... 7 (7x7 -> 1x1); got %r" % (r,))
         C, R, I = self.in_channels, self.reduced_channels, B * V
-        P = 49 if r == 1 else 9                      # positions of the grid the attention runs on
+        P = self._positions()                        # positions of the grid the attention runs on
         if r == 1:                                   # reference cross_view_attention.py:67-73: no depth-wise down-sampling
             dw = x
         else:
-            dw = empty(I * 9, C, like=x)
-            call("sv_dwconv2x2_fwd", ptr(x), ptr(self.downsample_qkv.weight), ptr(self.downsample_qkv.bias), ptr(dw), I, C)
+            dw = empty(I * P, C, like=x)
+            call("sv_cva_downsample_fwd", ptr(x), ptr(self.downsample_qkv.weight), ptr(self.downsample_qkv.bias), ptr(dw), I, C, r)
         qkv = empty(I * P, 3 * R, like=x)
         ops.linear_fwd(dw, I * P, self._s_qkv, self.qkv_conv.weight, qkv, bias=self.qkv_conv.bias)
         att = empty(I * P, R, like=x)
@@ -60,9 +70,9 @@ class CrossViewAttention(nn.Module):
         if r == 1:                                   # :110-120 without the interpolation: proj + x in the projection's epilogue
             ops.linear_fwd(att, I * 49, self._s_proj, self.proj_conv.weight, up, bias=self.proj_conv.bias, residual=x, ldr=C)
         else:
-            pr = empty(I * 9, C, like=x)
-            ops.linear_fwd(att, I * 9, self._s_proj, self.proj_conv.weight, pr, bias=self.proj_conv.bias)
-            call("sv_upsample3to7_add_fwd", ptr(pr), ptr(x), C, ptr(up), I, C)
+            pr = empty(I * P, C, like=x)
+            ops.linear_fwd(att, I * P, self._s_proj, self.proj_conv.weight, pr, bias=self.proj_conv.bias)
+            call("sv_cva_upsample_add_fwd", ptr(pr), ptr(x), C, ptr(up), I, C, r)
         f1pre, f1 = empty(I * 49, C, like=x), empty(I * 49, C, like=x)
         ops.linear_fwd(up, I * 49, self._s_f0, self.ffn[0].weight, f1, bias=self.ffn[0].bias, act=ACT_GELU, pre_act=f1pre)
         st = BatchNormState(self.batch_norm, I * 49, training)
@@ -96,12 +106,12 @@ class CrossViewAttention(nn.Module):
         dup = empty(I * 49, C, like=x)
         ops.linear_dgrad(df1, I * 49, self._s_f0, self._s_f0.pack_dgrad(self.ffn[0].weight), dup)
         full = self.downsample_qkv is None             # ATT_SPATIAL_DOWNSAMPLE_RATIO = 1: attention on the 7x7 grid itself
-        P = 49 if full else 9
+        r, P = self.attention_spatial_downsample_ratio, self._positions()
         if full:
             dpr = dup
         else:
-            dpr = empty(I * 9, C, like=x)
-            call("sv_upsample3to7_bwd", ptr(dup), ptr(dpr), I, C)
+            dpr = empty(I * P, C, like=x)
+            call("sv_cva_upsample_bwd", ptr(dup), ptr(dpr), I, C, r)
         ops.linear_wgrad(dpr, att, I * P, self._s_proj, grads[self.proj_conv.weight], grads[self.proj_conv.bias])
         datt = empty(I * P, R, like=x)
         ops.linear_dgrad(dpr, I * P, self._s_proj, self._s_proj.pack_dgrad(self.proj_conv.weight), datt)
@@ -112,10 +122,10 @@ class CrossViewAttention(nn.Module):
             dx = empty(I * 49, C, like=x)
             ops.linear_dgrad(dqkv, I * 49, self._s_qkv, self._s_qkv.pack_dgrad(self.qkv_conv.weight), dx, residual=dup, ldr=C)
             return dx
-        ddw = empty(I * 9, C, like=x)
-        ops.linear_dgrad(dqkv, I * 9, self._s_qkv, self._s_qkv.pack_dgrad(self.qkv_conv.weight), ddw)
+        ddw = empty(I * P, C, like=x)
+        ops.linear_dgrad(dqkv, I * P, self._s_qkv, self._s_qkv.pack_dgrad(self.qkv_conv.weight), ddw)
         dx = empty(I * 49, C, like=x)
-        call("sv_dwconv2x2_bwd", ptr(ddw), ptr(x), ptr(self.downsample_qkv.weight), ptr(dx), ptr(grads[self.downsample_qkv.weight]),
-             ptr(grads[self.downsample_qkv.bias]), I, C)
+        call("sv_cva_downsample_bwd", ptr(ddw), ptr(x), ptr(self.downsample_qkv.weight), ptr(dx), ptr(grads[self.downsample_qkv.weight]),
+             ptr(grads[self.downsample_qkv.bias]), I, C, r)
         call("sv_axpby", ptr(dx), ptr(dup), ptr(dx), 1.0, 1.0, dx.numel())   # + residual path
         return dx
