@@ -342,6 +342,12 @@ int sv_swin_attn_block_bwd(const void* dx1, const void* qkv, const void* x, cons
  * PatchEmbed Conv2d(3, C, kernel 4, stride 4) (behind reference models/swin_transformer.py:78) is a Linear(48, C) with the weight re-indexed
  * [co][c][ky][kx] -> [co][(ky, kx, c)].  Replaces the fp32 -> storage cast, the NCHW -> NHWC transpose and sv_stem_space_to_depth. */
 int sv_encoder_prep(const void* images, int images_f32, void* x16, void* xp, int I, int S, int act_dtype, void* stream);
+/* Adjoint of sv_encoder_prep, the gradient wrt the renderings: dimages [I, 3, S, S] (fp32 when out_f32, else act_dtype) with
+ *   dimages[i][c][y][x] = dx16[i][y/2][x/2][(y%2) 8 + (x%2) 4 + c] + dxp[i][y/4][x/4][(y%4) 12 + (x%4) 3 + c],
+ * dx16 [I, S/2, S/2, 16] being the data gradient of the torchvision ResNet-50 stem Conv2d(3, 64, 7, stride 2, pad 3) (behind reference
+ * models/encoder.py:22) on the space-to-depth image and dxp [I, S/4, S/4, 48] that of timm's PatchEmbed Conv2d(3, C, 4, 4) (behind reference
+ * models/swin_transformer.py:78) on the patch rows.  Every element of dimages is written. */
+int sv_encoder_prep_bwd(const void* dx16, const void* dxp, void* dimages, int out_f32, int I, int S, int act_dtype, void* stream);
 /* Refiner head Conv3d(1, Co, k = 4, p = 2) on a D^3 grid (reference models/refiner.py:21-26) as a (4, 1, 1)-tap convolution over 16 channels (the stem's
  * trick): xc [N, D, D+1, D+1, 16] with xc[.., Y, X, 4 cy + cx] = x[.., Y + cy - 2, X + cx - 2] (zero outside); sv_head_unpack_dx folds the
  * 16-channel data gradient of that convolution back into dx [N, D, D, D]. */
@@ -350,6 +356,10 @@ int sv_head_unpack_dx(const void* dxc, void* dx, int N, int D, int act_dtype, vo
 int sv_stem_space_to_depth(const void* images, void* x16, int I, int act_dtype, void* stream);
 int sv_stem_pack(const float* w, void* wp, int out_dtype, void* stream);
 int sv_stem_unpack_grad(const float* dw16, float* dw, void* stream);
+/* sv_stem_native: w [64,3,7,7] fp32 -> w16 [64][16 = (sy, sx, c)][4][4] fp32, the stem weight in the native [Co][Ci][kh][kw] layout of its
+ * 4x4 formulation (the inverse of sv_stem_unpack_grad; zero for c = 3 and for taps outside the 7x7 kernel): the source of the data-gradient
+ * pack of the stem on the space-to-depth image (torchvision ResNet-50 conv1, behind reference models/encoder.py:22). */
+int sv_stem_native(const float* w, float* w16, void* stream);
 int sv_merger_pack(const float* w, void* wp_bf16, int cout, int cin, int dgrad, int concat, void* stream);
 
 /* harness-side kernels on fp32 module outputs */

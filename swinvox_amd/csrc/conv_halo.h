@@ -14,7 +14,8 @@ struct HaloConvArgs {
 };
 
 // 1 when the call was taken (launched on `stream`), 0 when the shape is not one of the kernel's (the caller goes on with the engine).
-// kind: 0 = 3 x 3, padding 1, CI = 64;  1 = 4 x 4, padding (2, 1), CI = 16 (the ResNet stem on the space-to-depth image)
+// kind: 0 = 3 x 3, padding 1, CI = 64;  1 = 4 x 4, padding (2, 1), CI = 16 (the ResNet stem on the space-to-depth image);
+//       2 = kind 1's data gradient: x = dy [N][H][W][64], w = its data-gradient pack [16][16 taps][64], y = [N][H][W][16] (flip = 1)
 int conv_halo_launch(const HaloConvArgs& a, int kind, hipStream_t stream);
 bool conv_halo_enabled();
 // the same convolution (3 x 3 / stride 1 / padding 1, plain store + optional statistics) with Ci, Co multiples of 64 up to 512: work items of 256

@@ -2,7 +2,8 @@
 // resnet50 behind it):
 //   kind 0: 3 x 3 / stride 1 / padding 1, 64 -> 64 channels on the 56 x 56 grid (conv2 of the three layer1 bottlenecks) - forward, and with
 //           flip = 1 the data gradient (the same convolution with mirrored taps on the data-gradient weight pack);
-//   kind 1: 4 x 4 / stride 1 / pads (2, 1), 16 -> 64 channels on the 112 x 112 space-to-depth image (the 7 x 7 / stride-2 stem).
+//   kind 1: 4 x 4 / stride 1 / pads (2, 1), 16 -> 64 channels on the 112 x 112 space-to-depth image (the 7 x 7 / stride-2 stem);
+//   kind 2: the data gradient of kind 1 (64 -> 16 channels, mirrored taps): the gradient wrt the renderings (conv_halo_dgrad16_kernel below).
 // The gather engine (igemm_kernel) fetches the activation tile once PER TAP: 9 x 16 KB (+ 9 x 8 KB of weights) from L2 into LDS for 128 x 64
 // outputs, and the L2 -> LDS fill (60-80 GB/s per CU) is what bounds it: 338 TFLOP/s on kind 0, 230 on kind 1.  Here
 //   * the whole weight tensor (9 x 64 x 64 bf16 = 72 KB / 16 x 64 x 16 = 32 KB) sits in LDS for the life of the workgroup,
@@ -299,6 +300,158 @@ __global__ __launch_bounds__(256, MINB) void conv_halo_kernel(const HaloConvArgs
   if (tid == 0) { hc_wg[blockIdx.x][0] = wall_begin; hc_wg[blockIdx.x][1] = wall_loop; hc_wg[blockIdx.x][2] = wall_clock64(); hc_wg[blockIdx.x][3] = hc_tiles; }
   if (blockIdx.x == 0 && tid == 0) { hc_prof[6] += wall_clock64() - wall_begin; hc_prof[7] += clock64() - t_begin; hc_prof[1] += clock64() - t_post; hc_prof[5] = t_post - t_loop; }   // 100 MHz ticks / shader cycles
 #endif
+  if (tid == 0) finish();
+}
+
+// ------------------------------------------------------------------------------------------------
+// kind 2: data gradient of the stem on the space-to-depth image (kind 1's convolution, 4 x 4 taps, pads (2, 1)):
+//   dx16[n][h][w][ci] = sum over (kh, kw, co) of dy[n][h - 1 + kh][w - 1 + kw][co] * pack[ci][15 - (4 kh + kw)][co]
+// i.e. a stride-1 correlation with mirrored taps whose patch starts one position above / left of the tile.  64 -> 16 channels: the gather
+// engine runs it on its 128 x 16 tile and stages every dy element from L2 once PER TAP (16 x 822 MB at 512 images).  Here the 32 KB weight
+// image stays in LDS and a tile of 16 x 32 positions reads its 19 x 35 x 64 dy patch once (1.3 x the tile).  v_mfma_f32_16x16x32_bf16 with
+// the weights as A (16 output channels = the MFMA's M) and 16 consecutive positions of a tile row as B.  Wave w owns the 16-position column
+// block w & 1 of tile rows 8 (w >> 1) .. + 7: per (kw, 32-channel slice) it reads 4 weight fragments and the 11 patch rows its 8 tile rows
+// meet, and each patch fragment feeds up to 4 MFMAs (tile row r meets patch row r + kh under tap row kh): 15 fragment reads per 32 MFMAs.
+// A lane ends up with 4 consecutive channels of one position: one 8-byte store per tile row, a wave's store covering 512 contiguous bytes.
+// Tiles are drawn at run time (conv_halo_kernel's scheduler); a tile cut by the image edge stores nothing outside (buffer range check).
+// ------------------------------------------------------------------------------------------------
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(256, 1) void conv_halo_dgrad16_kernel(const HaloConvArgs p, int tiles_h, int tiles_w, int ntiles, int* __restrict__ ctr) {
+  constexpr int TH = 16, TW = 32, RW = TH / 2, KH = 4, KW = 4, T = KH * KW, PLO = 1;
+  constexpr int PH = TH + KH - 1, PW = TW + KW - 1, NPOS = PH * PW, PROWB = 144;    // 128-byte dy rows padded by 16 (odd slot pitch)
+  constexpr int NCH = NPOS * 8, NLD = (NCH + 255) / 256, WCH = 16 * T * 8, NWL = WCH / 256;
+  constexpr int W_BYTES = T * 16 * 128, PATCH_BYTES = (NPOS * PROWB + 127) / 128 * 128;
+  __shared__ __attribute__((aligned(1024))) char smem[W_BYTES + PATCH_BYTES + 16];
+  const __bf16* __restrict__ Wt = static_cast<const __bf16*>(p.w);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, lg = lane >> 4;
+  const int H = p.H, Wd = p.W;
+  char* Wl = smem;
+  char* Pl = smem + W_BYTES;
+  int* mbox = reinterpret_cast<int*>(smem + W_BYTES + PATCH_BYTES);
+
+  const int xcd = blockIdx.x & 7, cq = ntiles >> 3, cr = ntiles & 7;
+  const int cbase = xcd * cq + (xcd < cr ? xcd : cr), csize = cq + (xcd < cr ? 1 : 0);
+  if (tid == 0) {
+    const int v0 = atomicAdd(ctr + xcd, 1), v1 = atomicAdd(ctr + xcd, 1);
+    mbox[0] = v0 < csize ? cbase + v0 : -1;
+    mbox[1] = v1 < csize ? cbase + v1 : -1;
+  }
+  // ---- weights -> LDS once: pack row r = output channel (0..15), [tap][64]; LDS image [mirrored tap][r][64], 16-byte slots XOR (r / 2) % 8
+  {
+    u32x4 wr[NWL];
+#pragma unroll
+    for (int j = 0; j < NWL; ++j) wr[j] = *reinterpret_cast<const u32x4*>(Wt + (size_t)(tid + 256 * j) * 8);
+#pragma unroll
+    for (int j = 0; j < NWL; ++j) {
+      const int id = tid + 256 * j, c = id & 7, t = (id >> 3) & 15, r = id >> 7;
+      *reinterpret_cast<u32x4*>(Wl + ((T - 1 - t) * 16 + r) * 128 + ((c ^ hc_swz<64>(r)) << 4)) = wr[j];
+    }
+  }
+  __syncthreads();
+  int cur = __builtin_amdgcn_readfirstlane(mbox[0]), nxt = __builtin_amdgcn_readfirstlane(mbox[1]);
+  auto finish = [&]() {
+    if (atomicAdd(ctr + 8, 1) == (int)gridDim.x - 1) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) ctr[i] = 0;
+    }
+  };
+  if (cur < 0) { if (tid == 0) finish(); return; }
+
+  const int tpi = tiles_h * tiles_w;
+  auto origin = [&](int t, int& n, int& h0, int& w0) {
+    n = t / tpi;
+    const int r = t - n * tpi, th = r / tiles_w;
+    h0 = th * TH; w0 = (r - th * tiles_w) * TW;
+  };
+  // buffer descriptors over the whole tensors (< 2 GB, checked by the launcher): bit 31 of an offset = outside = zeros / dropped store
+  const unsigned xbytes = (unsigned)p.N * H * Wd * 128, ybytes = (unsigned)p.N * H * Wd * 32;
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, xbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, ybytes, 0x00020000);
+  u32x4 pre[NLD];
+  int cpr[NLD], cpc[NLD];
+  unsigned crel[NLD];
+#pragma unroll
+  for (int j = 0; j < NLD; ++j) {
+    const int c = tid + 256 * j, pp = c >> 3, sl = c & 7;
+    cpr[j] = pp / PW - PLO; cpc[j] = pp % PW - PLO;
+    crel[j] = (unsigned)((cpr[j] * Wd + cpc[j]) * 128 + (sl << 4));
+  }
+  auto load_patch = [&](int t) {
+    int n, h0, w0;
+    origin(t, n, h0, w0);
+    const unsigned base = (unsigned)((n * H + h0) * Wd + w0) * 128;
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const bool ok = (unsigned)(h0 + cpr[j]) < (unsigned)H && (unsigned)(w0 + cpc[j]) < (unsigned)Wd;
+      pre[j] = __builtin_amdgcn_raw_buffer_load_b128(xr, (base + crel[j]) | ((unsigned)!ok << 31), 0, 0);
+    }
+  };
+  auto store_patch = [&]() {
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const int c = tid + 256 * j;
+      if (NCH % 256 == 0 || c < NCH) *reinterpret_cast<u32x4*>(Pl + (c >> 3) * PROWB + (c & 7) * 16) = pre[j];
+    }
+  };
+  load_patch(cur);
+  store_patch();
+  __syncthreads();
+
+  const int cb = wave & 1, rh = wave >> 1;
+  // A (weights): lane = output channel l16, k = 8 lg .. of the slice; B (patch): lane = position l16 of the block, the same k
+  const char* pa = Wl + l16 * 128;
+  int aoff[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) aoff[ks] = ((4 * ks + lg) ^ hc_swz<64>(l16)) << 4;
+  const char* pb = Pl + ((RW * rh) * PW + 16 * cb + l16) * PROWB + lg * 16;
+
+  while (true) {
+    int drawn;
+    if (tid == 0) drawn = atomicAdd(ctr + xcd, nxt >= 0 ? 1 : 0);
+    load_patch(nxt >= 0 ? nxt : cur);    // the next patch is in flight while this tile is contracted (the last tile re-reads its own)
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4v acc[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) acc[r] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kw = 0; kw < KW; ++kw)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8 a[KH];
+#pragma unroll
+        for (int kh = 0; kh < KH; ++kh) a[kh] = *reinterpret_cast<const bf16x8*>(pa + (kh * KW + kw) * 16 * 128 + aoff[ks]);
+#pragma unroll
+        for (int pr = 0; pr < RW + KH - 1; ++pr) {
+          const bf16x8 b = *reinterpret_cast<const bf16x8*>(pb + (pr * PW + kw) * PROWB + ks * 64);
+#pragma unroll
+          for (int kh = 0; kh < KH; ++kh)
+            if (pr - kh >= 0 && pr - kh < RW) acc[pr - kh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kh], b, acc[pr - kh], 0, 0, 0);
+        }
+      }
+    __syncthreads();                     // every wave is done reading the patch
+    if (nxt >= 0) store_patch();
+    if (tid == 0) mbox[0] = (nxt >= 0 && drawn < csize) ? cbase + drawn : -1;
+
+    // ---- epilogue of `cur`: lane (l16, lg) holds channels 4 lg .. 4 lg + 3 of position l16 of the block, per tile row
+    int n, h0, w0;
+    origin(cur, n, h0, w0);
+    const int col = w0 + 16 * cb + l16;
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+      const int row = h0 + RW * rh + r;
+      bf16x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = (__bf16)acc[r][i];
+      const unsigned off = ((unsigned)((n * H + row) * Wd + col) * 32 + lg * 8) | ((unsigned)!(row < H && col < Wd) << 31);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), yr, off, 0, 0);
+    }
+    __syncthreads();                     // the next patch and the mailbox are complete
+    if (nxt < 0) break;
+    cur = nxt;
+    nxt = __builtin_amdgcn_readfirstlane(mbox[0]);
+  }
   if (tid == 0) finish();
 }
 
@@ -691,7 +844,7 @@ bool conv_halo_enabled() { return halo_mode().load(std::memory_order_relaxed) !=
 
 int conv_halo_launch(const HaloConvArgs& a, int kind, hipStream_t stream) {
   if (!conv_halo_enabled()) return 0;
-  const int tiles_h = cdiv(a.H, 8), tiles_w = cdiv(a.W, 32);
+  const int tiles_h = cdiv(a.H, kind == 2 ? 16 : 8), tiles_w = cdiv(a.W, 32);
   const long long nt = (long long)a.N * tiles_h * tiles_w;
   const int mode = halo_mode().load(std::memory_order_relaxed);
   if ((long long)a.N * a.H * a.W * 128 >= (1ll << 31)) return 0;          // buffer descriptors: 32-bit byte offsets, bit 31 = "outside"
@@ -701,8 +854,10 @@ int conv_halo_launch(const HaloConvArgs& a, int kind, hipStream_t stream) {
   const int ntiles = (int)nt;
   if (kind == 0)
     hipLaunchKernelGGL((conv_halo_kernel<64, 3, 3, 1, 1>), dim3(256), dim3(256), 0, stream, a, tiles_h, tiles_w, ntiles, ctr);
-  else   // 32 KB of weights + 18 KB patch + 16 KB staging: two workgroups per CU - one's epilogue runs under the other's MFMAs
+  else if (kind == 1)   // 32 KB of weights + 18 KB patch + 16 KB staging: two workgroups per CU - one's epilogue runs under the other's MFMAs
     hipLaunchKernelGGL((conv_halo_kernel<16, 4, 4, 2, 2>), dim3(512), dim3(256), 0, stream, a, tiles_h, tiles_w, ntiles, ctr);
+  else                  // 32 KB of weights + 94 KB patch: one workgroup per CU
+    hipLaunchKernelGGL(conv_halo_dgrad16_kernel, dim3(256), dim3(256), 0, stream, a, tiles_h, tiles_w, ntiles, ctr);
   halo_launches.fetch_add(1, std::memory_order_relaxed);
   return 1;
 }

@@ -634,6 +634,47 @@ __global__ __launch_bounds__(256) void encoder_prep_kernel(const IT* __restrict_
       }
   }
 }
+// ---- adjoint of encoder_prep_kernel: the gradient wrt the renderings from the gradients of both rearrangements
+//   dimg[i][c][y][x] = dx16[i][y >> 1][x >> 1][(y & 1) 8 + (x & 1) 4 + c] + dxp[i][y >> 2][x >> 2][(y & 3) 12 + (x & 3) 3 + c]
+// Every pixel is read by exactly one x16 entry and one xp entry (channel 3 of the x16 groups is padding and receives nothing), so this is the
+// exact transpose of the two forward layouts.  One thread per 4 x 4 x 3 pixel block, as the forward: 12 row pieces of dxp, the four 16-value
+// dx16 rows, 12 16-byte stores of 4 pixels; every output element is written (no zero-fill).  OT: fp32, or the storage type.
+template <typename AT, typename OT>
+__global__ __launch_bounds__(256) void encoder_prep_bwd_kernel(const AT* __restrict__ dx16, const AT* __restrict__ dxp, OT* __restrict__ dimg, int S,
+                                                               long long n) {
+  const int P = S >> 2, Q = S >> 1;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
+    const int px = (int)(t % P); long long r = t / P;
+    const int py = (int)(r % P); const long long i = r / P;
+    float v[3][4][4];
+    const AT* sp = dxp + ((i * P + py) * P + px) * 48;
+#pragma unroll
+    for (int g = 0; g < 12; ++g) {                     // 4 consecutive entries (ky, kx, c) = 4 g .. 4 g + 3
+      const float4 q = ld4f(sp + 4 * g);
+      const float o[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const int e = 4 * g + j, ky = e / 12, kx = (e / 3) % 4, c = e % 3; v[c][ky][kx] = o[j]; }
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const AT* ss = dx16 + ((i * Q + 2 * py + a) * Q + 2 * px + b) * 16;
+#pragma unroll
+        for (int sy = 0; sy < 2; ++sy)
+#pragma unroll
+          for (int sx = 0; sx < 2; ++sx) {
+            const float4 q = ld4f(ss + (sy * 2 + sx) * 4);
+            v[0][2 * a + sy][2 * b + sx] += q.x; v[1][2 * a + sy][2 * b + sx] += q.y; v[2][2 * a + sy][2 * b + sx] += q.z;
+          }
+      }
+    OT* dst = dimg + (i * 3) * S * S + (size_t)(4 * py) * S + 4 * px;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int ky = 0; ky < 4; ++ky) st4f(dst + ((size_t)c * S + ky) * S, make_float4(v[c][ky][0], v[c][ky][1], v[c][ky][2], v[c][ky][3]));
+  }
+}
 // wp[co][(ty, tx)][(sy, sx, c)] = w[co][c][2 ty + sy - 1][2 tx + sx - 1] inside the 7x7 kernel and c < 3, else 0
 template <typename WT>
 __global__ void stem_pack_kernel(const float* __restrict__ w, WT* __restrict__ wp) {
@@ -652,6 +693,17 @@ __global__ void stem_unpack_grad_kernel(const float* __restrict__ dw16, float* _
   const int kx = idx % 7, ky = (idx / 7) % 7, c = (idx / 49) % 3, co = idx / 147;
   const int ty = (ky + 1) >> 1, sy = (ky + 1) & 1, tx = (kx + 1) >> 1, sx = (kx + 1) & 1;
   dw[idx] += dw16[((co * 16 + (sy * 8 + sx * 4 + c)) * 4 + ty) * 4 + tx];
+}
+// w16[co][(sy, sx, c)][ty][tx] = w[co][c][2 ty + sy - 1][2 tx + sx - 1] inside the 7x7 kernel and c < 3, else 0: the stem weight in the NATIVE
+// [Co][Ci][kh][kw] layout of the 4x4 formulation (the inverse of stem_unpack_grad_kernel), from which ConvSpec packs the data-gradient operand
+__global__ void stem_native_kernel(const float* __restrict__ w, float* __restrict__ w16) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 64 * 256) return;
+  const int co = idx >> 8, s = (idx >> 4) & 15, ty = (idx >> 2) & 3, tx = idx & 3;
+  const int sy = s >> 3, sx = (s >> 2) & 1, c = s & 3;
+  const int ky = 2 * ty + sy - 1, kx = 2 * tx + sx - 1;
+  const bool ok = c < 3 && ky >= 0 && ky < 7 && kx >= 0 && kx < 7;
+  w16[idx] = ok ? w[((co * 3 + c) * 7 + ky) * 7 + kx] : 0.f;
 }
 // merger.py:20-54 weights [cout][cin][27] -> bf16 stencil packs: forward [16][27][ncols] with wp[co][tap][col(ci)] = w[co][ci][tap];
 // data-gradient [ncols][27][16] with wp[col(ci)][26 - tap][co] = w[co][ci][tap]; col(ci) = 12 (ci / 9) + ci % 9 for the 36-channel concat
@@ -688,6 +740,18 @@ extern "C" int sv_encoder_prep(const void* images, int images_f32, void* x16, vo
   }
   return check_launch("sv_encoder_prep");
 }
+extern "C" int sv_encoder_prep_bwd(const void* dx16, const void* dxp, void* dimages, int out_f32, int I, int S, int act_dtype, void* stream) {
+  SV_REQUIRE(dx16 && dxp && dimages && I > 0 && S >= 4 && S % 4 == 0, "encoder_prep_bwd: bad arguments (I=%d S=%d)", I, S);
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE((((uintptr_t)dimages | (uintptr_t)dx16 | (uintptr_t)dxp) & 15) == 0, "encoder_prep_bwd: buffers must be 16-byte aligned");
+  const long long n = (long long)I * (S / 4) * (S / 4);
+  if (out_f32) {
+    SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL((encoder_prep_bwd_kernel<AT, float>), dim3(grid_for(n)), dim3(256), 0, STREAM, CA(dx16), CA(dxp), static_cast<float*>(dimages), S, n););
+  } else {
+    SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL((encoder_prep_bwd_kernel<AT, AT>), dim3(grid_for(n)), dim3(256), 0, STREAM, CA(dx16), CA(dxp), MA(dimages), S, n););
+  }
+  return check_launch("sv_encoder_prep_bwd");
+}
 extern "C" int sv_head_pack_x(const void* x, void* xc, int N, int D, int act_dtype, void* stream) {
   SV_REQUIRE(x && xc && N > 0 && D > 0, "head_pack_x: bad arguments");
   SV_REQUIRE_ACT(act_dtype);
@@ -708,6 +772,11 @@ extern "C" int sv_stem_pack(const float* w, void* wp, int out_dtype, void* strea
   if (out_dtype == SV_BF16) hipLaunchKernelGGL(stem_pack_kernel<__bf16>, dim3(64), dim3(256), 0, STREAM, w, static_cast<__bf16*>(wp));
   else hipLaunchKernelGGL(stem_pack_kernel<float>, dim3(64), dim3(256), 0, STREAM, w, static_cast<float*>(wp));
   return check_launch("sv_stem_pack");
+}
+extern "C" int sv_stem_native(const float* w, float* w16, void* stream) {
+  SV_REQUIRE(w && w16, "stem_native: bad arguments");
+  hipLaunchKernelGGL(stem_native_kernel, dim3(64), dim3(256), 0, STREAM, w, w16);
+  return check_launch("sv_stem_native");
 }
 extern "C" int sv_stem_unpack_grad(const float* dw16, float* dw, void* stream) {
   SV_REQUIRE(dw16 && dw, "stem_unpack_grad: bad arguments");

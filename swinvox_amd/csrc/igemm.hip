@@ -1549,15 +1549,23 @@ static int* gemm_wide_counters() {     // next launch slot of the current device
 
 int* tile_draw_counters() { return gemm_wide_counters(); }
 
-// Halo-tile kernels (conv_halo.hip) take the two shapes they are built for - 3 x 3 / stride 1 / 64 -> 64 (forward and data gradient) and
-// the 4 x 4 stem on the space-to-depth image - when the call is a plain store (+ BatchNorm statistics); 0 = not taken
+// Halo-tile kernels (conv_halo.hip) take the shapes they are built for - 3 x 3 / stride 1 / 64 -> 64 (forward and data gradient) and
+// the 4 x 4 stem on the space-to-depth image (forward, and its 64 -> 16 data gradient) - when the call is a plain store (+ BatchNorm
+// statistics); 0 = not taken
 static int try_halo(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype, bool dgrad,
                     hipStream_t s) {
   if (math != SV_MATH_BF16 || act_dtype != SV_BF16 || !conv_halo_enabled()) return 0;
+  if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)out) & 15) return 0;
+  // the stem's data gradient (kind 1 backwards: 64 -> 16 channels, a plain store) on the tile that reads each dy patch once
+  if (dgrad && g->kh == 4 && g->kw == 4 && g->ph == 2 && g->pw == 2 && g->Ci == 64 && g->Co == 16 && g->kd == 1 && g->Di == 1 && g->Do == 1 &&
+      g->sd == 1 && g->sh == 1 && g->sw == 1 && g->pd == 0 && g->Hi == g->Ho && g->Wi == g->Wo && g->ldi == 64 && !e->bias && !e->residual &&
+      !e->row_scale && !e->pre_act && !e->stats && e->act == SV_ACT_NONE && !e->act_grad_src && e->ldc == 16 && e->col_off == 0) {
+    HaloConvArgs a{in, w, out, nullptr, g->N, g->Hi, g->Wi, 1};
+    return conv_halo_launch(a, 2, s);
+  }
   if ((g->Co & 63) || g->kd != 1 || g->Di != 1 || g->Do != 1 || g->sd != 1 || g->sh != 1 || g->sw != 1 || g->pd != 0) return 0;
   if (g->Hi != g->Ho || g->Wi != g->Wo || g->ldi != g->Ci) return 0;
   if (e->bias || e->residual || e->row_scale || e->pre_act || e->act != SV_ACT_NONE || e->act_grad_src || e->ldc != g->Co || e->col_off != 0) return 0;
-  if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)out) & 15) return 0;
   int kind;
   if (g->kh == 3 && g->kw == 3 && g->ph == 1 && g->pw == 1 && g->Ci == 64 && g->Co == 64) kind = 0;
   else if (g->kh == 3 && g->kw == 3 && g->ph == 1 && g->pw == 1 && !(dgrad && e->stats))      // more channels: blocks of 64 x 64 (conv_halo.hip)

@@ -153,8 +153,8 @@ class Encoder(HipModule):
             call("sv_maxpool2d_fwd", ptr(z), ptr(mp), ptr(idx), I, 112, 112, 64)
         return mp, (1, 56, 56), (x16, y, st, M, I, idx, fused)
 
-    def _stem_bwd(self, ctx, dmp, grads):
-        """dmp: gradient of the pooled 56 x 56 x 64 map"""
+    def _stem_bwd(self, ctx, dmp, grads, need_dx=False):
+        """dmp: gradient of the pooled 56 x 56 x 64 map; need_dx: also return the data gradient on the space-to-depth image [I*112*112, 16]"""
         x16, y, st, M, I, idx, fused = ctx
         conv, bn = self.resnet[0], self.resnet[1]
         dy = empty(M, 64, like=dmp)
@@ -169,11 +169,19 @@ class Encoder(HipModule):
         dw16 = ops.fzeros(64, 16, 4, 4, like=dy)                         # native layout of the 4x4 formulation: [co][(sy,sx,c)][ty][tx]
         self._stem_spec.wgrad(dy, x16, I, (1, 112, 112), dw16, async_ok=False)   # read back right below
         call("sv_stem_unpack_grad", ptr(dw16), ptr(grads[conv.weight]))  # dw[co][c][ky][kx] += dw16[co][(sy,sx,c)][ty][tx]
+        if not need_dx:
+            return None
+        w16 = ops.fempty(64, 16, 4, 4, like=dy)                           # the weight in the 4x4 formulation's native layout -> data-gradient pack
+        call("sv_stem_native", ptr(conv.weight), ptr(w16))
+        dx16 = empty(M, 16, like=dy)                                        # every element is written
+        self._stem_spec.dgrad(dy, I, (1, 112, 112), ops.pack_one(self._stem_spec, w16, "d"), dx16)
+        return dx16
 
     # ------------------------------------------------------------------------------------------------
     def _fwd(self, images, save):
         B, V = images.shape[:2]
         I = B * V
+        in_dtype = images.dtype
         prep = ops.input_prep_enabled() and self.swin_transformer.model.embed_lin.cin == 48
         if not prep:
             images = ops.to_store(images)                                  # fp32 module input -> storage dtype
@@ -223,7 +231,7 @@ class Encoder(HipModule):
             c_post.append(c)
         out = empty(B, V, 256, 7, 7, like=x)
         ops.transpose(y, out, I, 49, 256)                                  # [I][49][256] -> [I][256][49]
-        tape = (B, V, c_stem, c_blocks, res_feat, rr, swin_tape, neck, c_cva, c_post) if save else None
+        tape = (B, V, c_stem, c_blocks, res_feat, rr, swin_tape, neck, c_cva, c_post, in_dtype) if save else None
         return ops.to_f32(out), tape
 
     def _swin_neck_fwd(self, feats, ready, cat, I, tr, multi, stream):
@@ -258,8 +266,9 @@ class Encoder(HipModule):
         return neck
 
     def _bwd(self, tape, grads, in_needs, dout):
-        B, V, c_stem, c_blocks, res_feat, rr, swin_tape, neck, c_cva, c_post = tape
+        B, V, c_stem, c_blocks, res_feat, rr, swin_tape, neck, c_cva, c_post, in_dtype = tape
         I = B * V
+        need_img = bool(in_needs[0])                                       # images.requires_grad: the gradient wrt the renderings
         multi = self.cfg.NETWORK.USE_SWIN_T_MULTI_STAGE
         dout = ops.to_store(dout)
         dy = empty(I * 49, 256, like=dout)
@@ -308,7 +317,7 @@ class Encoder(HipModule):
                 for i in range(len(dfeats) - 1):   # unused heads of the single-stage path receive zero gradient
                     hw, ch = self.swin_transformer.out_spatial[i], self.swin_transformer.out_channels[i]
                     dfeats[i] = zeros(I * hw * hw, ch, like=dout)
-            swin_backward(self.swin_transformer, swin_tape, dfeats, I, grads, dready)
+            dxp = swin_backward(self.swin_transformer, swin_tape, dfeats, I, grads, dready, need_dx=need_img)   # patch rows [I*3136, 48]
             self._announce(grads, 1)                                       # Swin backbone + stage heads are enqueued
         # ---- ResNet branch
         drr = empty(I * 196, 256, like=dout)
@@ -321,9 +330,18 @@ class Encoder(HipModule):
         self._s_rr.dgrad(drr, I * 196, (1, 1, 1), self._s_rr.pack_dgrad(self.resnet_reduce.weight), d)
         for blk, c in reversed(c_blocks):
             d = blk.bwd(c, d, grads)
-        self._stem_bwd(c_stem, d, grads)                                   # max-pool + BatchNorm + stem conv
+        dx16 = self._stem_bwd(c_stem, d, grads, need_img)                  # max-pool + BatchNorm + stem conv (+ its data gradient)
         self._announce(grads, 2)                                           # ResNet trunk
         main.wait_stream(side)                                             # join: every parameter gradient is complete
         if not tail_on_main:
             self._announce(grads, 0)
-        return (None,)
+        if not need_img:
+            return (None,)
+        # both backbones read the renderings through sv_encoder_prep's two rearrangements: its adjoint sums the two data gradients
+        dxp.record_stream(main)                                            # made on the side stream, read here on the main stream
+        # the kernel writes fp32 or the storage type: images that arrived in the storage type get it, any other dtype gets fp32 (autograd
+        # casts a returned gradient to the input's dtype); the allocation always has the element size the kernel writes
+        to_store = in_dtype == dx16.dtype and in_dtype != torch.float32
+        dimg = torch.empty(B, V, 3, 224, 224, dtype=dx16.dtype if to_store else torch.float32, device=dout.device)
+        call("sv_encoder_prep_bwd", ptr(dx16), ptr(dxp), ptr(dimg), 0 if to_store else 1, I, 224)
+        return (dimg,)

@@ -376,10 +376,12 @@ def hipws(I, L):
     return hip.load().sv_ln_image_workspace_floats(I, L)
 
 
-def swin_backward(st: SwinTransformer, tape, dfeats, I, grads, ready=None):
-    """dfeats: list of gradients wrt the stage-head outputs ([I*HW, C]).  No gradient wrt the image is produced.
+def swin_backward(st: SwinTransformer, tape, dfeats, I, grads, ready=None, need_dx=False):
+    """dfeats: list of gradients wrt the stage-head outputs ([I*HW, C]).
     `ready` (optional): one event per entry of dfeats, awaited right before that gradient is first read (the producer may
-    still be working on the earlier stages' gradients on another stream)."""
+    still be working on the earlier stages' gradients on another stream).
+    need_dx: also return the gradient wrt the patch rows, [I*(S/4)^2, 48] with columns (ky, kx, c) (sv_encoder_prep's xp layout; the
+    same in both forward paths); else None."""
     bb = st.model
     stages = bb.stages()
     head_of = {si: (hi, xs, wt, mr, p, seed, L) for (si, hi, xs, wt, mr, p, seed, L) in tape["heads"]}
@@ -403,7 +405,7 @@ def swin_backward(st: SwinTransformer, tape, dfeats, I, grads, ready=None):
             else:
                 call("sv_axpby", ptr(dx), ptr(dxe), ptr(dx), 1.0, 1.0, dx.numel())
         dx = stage_backward(stage, tape["stages"][si], dx, grads, I)
-    # patch embed: LN backward, then conv weight/bias gradient (the image itself needs no gradient)
+    # patch embed: LN backward, then conv weight/bias gradient (+ the data gradient on the patch rows when asked)
     img, emb, pm, pr, as_patches = tape["embed"]
     pe = bb.patch_embed
     M, Ce = emb.shape
@@ -422,3 +424,11 @@ def swin_backward(st: SwinTransformer, tape, dfeats, I, grads, ready=None):
             ops.transpose(dw48, grads[pe.proj.weight], Ce, 16, 3)
     else:
         bb.embed_spec.wgrad(demb, img, I, (1, S, S), grads[pe.proj.weight], db=grads[pe.proj.bias])
+    if not need_dx:
+        return None
+    # PatchEmbed's Conv2d(3, C, 4, 4) has stride = kernel: its data gradient is the Linear(48, C)'s on the patch rows, dxp = demb . w48
+    w48 = torch.empty(Ce, 48, dtype=torch.float32, device=dx.device)
+    ops.transpose(pe.proj.weight, w48, Ce, 3, 16)                         # [co][c][(ky, kx)] -> [co][(ky, kx)][c]
+    dxp = empty(M, 48, like=dx)
+    bb.embed_lin.dgrad(demb, M, (1, 1, 1), ops.pack_one(bb.embed_lin, w48, "d"), dxp)
+    return dxp
