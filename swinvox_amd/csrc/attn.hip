@@ -865,7 +865,8 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_kernel(const WinArgsT<
 // fp32 accumulate).  Scales are per (window, head) TILE - finer than per tensor and free of an extra pass over HBM: the workgroup takes
 // the absolute maximum of its q / k / v tile while the rows travel through registers and maps it to 224 (half of e4m3's 448, head room
 // for the rounding); probabilities (<= 1) are scaled by 256, so that everything above 2^-17 survives as a subnormal.  Scores and
-// outputs are rescaled in fp32; bias, mask and softmax stay fp32.  The backward keeps bf16 operands and recomputes P from bf16 q / k.
+// outputs are rescaled in fp32; bias, mask and softmax stay fp32.  The backward of SV_MATH_FP8 keeps bf16 operands and recomputes P from
+// bf16 q / k; SV_MATH_FP8_FULL differentiates this very function on e4m3 operands (win_attn_bwd_wg_fp8_kernel).
 constexpr int LDQ_8 = 40;    // byte row stride of the fp8 q / k tiles (32 + 8: 8-byte fragment reads, rows 10 banks apart)
 constexpr int LDP_8 = 72;    // byte row stride of the fp8 P and V^T tiles
 __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d) {
@@ -1183,6 +1184,213 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_kernel(const WinArgsT<
     if (v != 0.f) atomicAdd(dst + i * p.heads + head, v);
   }
 }
+// ---- fp8 (OCP e4m3) backward of the window-attention core (SV_MATH_FP8_FULL) ----------------------------------------------------------
+// The gradient of exactly the function win_attn_fwd_wg_fp8_kernel evaluates, every quantiser taken as the identity (straight-through).
+// Per (window, head) tile: q' = scale q; sq, sk, sv, so = 224 / amax of q', k, v, dO (1 for an all-zero tile); Qq, Kq, Vq, dOq = e4m3 of
+// the scaled tiles (pack4_fp8, the forward's conversions in the forward's order).  S = Qq Kq^T / (sq sk) (+ bias, + mask) and P = softmax(S)
+// are recomputed exactly as the forward computes them (same MFMA operands and strip layout, bias_mask_softmax_strip), Pq = e4m3(256 P).
+//   dV = Pq^T dOq / (256 so),  dP = dOq Vq^T / (so sv),  dS = P o (dP - rowsum(dP o P)) (fp32; the bias-table gradient sums this dS),
+//   ss = 224 / amax(dS) over the tile (one scale: dK contracts over the queries), dSq = e4m3(ss dS),
+//   dQ = scale dSq Kq / (ss sk),  dK = dSq^T Qq / (ss sq).
+// All five contractions are v_mfma_f32_16x16x32_fp8_fp8.  Both operands of that MFMA take 8 consecutive bytes along the contraction
+// index.  The q / k / v / dO tiles stay row-major [token][d] in LDS; the contractions over tokens (dQ, dK, dV) take them through
+// ds_read_b64_tr_b8 (tr8_frag).  P and dS go to LDS as [key][query] (four consecutive queries of one key per lane: one 32-bit write); dK / dV
+// read them as they are, dQ reads dS transposed.
+// Phase 1: wave w owns queries 16 w .. 16 w + 15 (strip layout: lane -> queries 16 w + 4 lg + j, key 16 nt + lr).  Phase 2: wave w owns
+// queries 16 w + lr for dQ and keys 16 w + lr for dK / dV; the transposed products leave 4 consecutive channels per lane (8 / 16-byte stores).
+constexpr int LDT_8 = 72;    // byte row stride of the [key][query] fp8 tiles (64 + 8)
+// a thread's piece of a window's q / k / v / dO head tiles: 4 channels (ch .. ch + 3) of rows r0 and r0 + 32, zeros for rows >= 49
+template <typename AT>
+__device__ __forceinline__ void fetch_rows(const WinArgsT<AT>& p, const TokMap& tn, int colq, int r0, int ch, float4 (&rq)[2], float4 (&rk)[2],
+                                           float4 (&rv)[2], float4 (&rd)[2]) {
+  const int ld = 3 * p.C;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int r = r0 + 32 * it;
+    rq[it] = make_float4(0.f, 0.f, 0.f, 0.f); rk[it] = rq[it]; rv[it] = rq[it]; rd[it] = rq[it];
+    if (r < WT) {
+      const size_t row = tn.row(r);
+      const AT* src = p.qkv + row * ld + colq + ch;
+      rq[it] = ld4f(src); rk[it] = ld4f(src + p.C); rv[it] = ld4f(src + 2 * p.C);
+      rd[it] = ld4f(p.dout + row * p.C + colq + ch);
+    }
+  }
+}
+// e4m3(s v) as 4 row-major bytes at [r][ch]
+__device__ __forceinline__ void put_fp8(uint8_t* rowm, int r, int ch, const float4& v, float s) {
+  *reinterpret_cast<uint32_t*>(rowm + r * LDQ_8 + ch) = pack4_fp8(v.x * s, v.y * s, v.z * s, v.w * s);
+}
+// fp8 MFMA operand along a tile's ROWS: lane -> column col0 + (lane & 15), rows row0 + 8 (lane >> 4) + j (j = 0..7, one byte each).
+// ds_read_b64_tr_b8 transposes an 8 x 16-byte block among 16 lanes: lanes 2 j and 2 j + 1 fetch the two 8-byte halves of row j, lane i
+// receives column i.
+typedef int i32x2_tr __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) i32x2_tr lds_i32x2_a;
+__device__ __forceinline__ long tr8_frag(const uint8_t* tile, int ld, int row0, int col0, int lane) {
+  const int lr = lane & 15, lg = lane >> 4;
+  const uint8_t* src = tile + (row0 + lg * 8 + (lr >> 1)) * ld + col0 + (lr & 1) * 8;
+  return __builtin_bit_cast(long, __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2_a*)(src)));
+}
+template <typename AT>
+__global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_fp8_kernel(const WinArgsT<AT> p, float* __restrict__ dt_ws) {
+  __shared__ __attribute__((aligned(16))) uint8_t Qs[64 * LDQ_8], Ks[64 * LDQ_8], Vs[64 * LDQ_8], Ds[64 * LDQ_8];   // [token][d]
+  __shared__ __attribute__((aligned(16))) uint8_t Pt[64 * LDT_8], St[64 * LDT_8];                                   // Pq, dSq [key][q]
+  __shared__ float bt[176], dbt[176];
+  __shared__ float amax[2][4][4], amaxs[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+  int chunk, head;
+  if (!wg_chunk_head((p.ntasks + p.tasks_per_wave - 1) / p.tasks_per_wave, p.heads, chunk, head)) return;   // uniform over the workgroup
+  const int nWx = p.W / 7, nW = (p.H / 7) * nWx;
+  const int ld = 3 * p.C, colq = head * HD;
+  for (int i = tid; i < 176; i += 256) { bt[i] = i < 169 ? p.table[i * p.heads + head] : 0.f; dbt[i] = 0.f; }
+  __syncthreads();
+  float bias[4][4];                                // strip_bias's values; the table read is unconditional (clamped index) - branches here made
+#pragma unroll                                     // the register allocator spill whole 16-register tuples
+  for (int nt = 0; nt < 4; ++nt) {
+    const int key = nt * 16 + lr, ky = key / 7, kx = key - ky * 7;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int q = wave * 16 + lg * 4 + j, qy = q / 7, qx = q - qy * 7;
+      const bool ok = q < WT && key < WT;
+      const float b = bt[ok ? (qy - ky + 6) * 13 + (qx - kx + 6) : 0];
+      bias[nt][j] = key >= WT ? -1.0e30f : (ok ? b : 0.f);
+    }
+  }
+  f32x4 dsum[4];                                   // sum over this workgroup's windows of dS at this lane's (query, key) slots
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) dsum[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // the next window's rows travel in registers while this window is contracted
+  const int r0 = tid >> 3, ch = (tid & 7) * 4;
+  float4 rq[2], rk[2], rv[2], rd[2];
+  const auto amax4 = [](float m, const float4& v) { return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)))); };
+  const long long task0 = (long long)chunk * p.tasks_per_wave;
+  if (task0 < p.ntasks) fetch_rows(p, task_map(task0, nW, nWx, p.H, p.W, p.shift), colq, r0, ch, rq, rk, rv, rd);
+  for (int tt = 0; tt < p.tasks_per_wave; ++tt) {
+    const long long task = task0 + tt;
+    if (task >= p.ntasks) break;                                         // uniform over the workgroup
+    const TokMap tm = task_map(task, nW, nWx, p.H, p.W, p.shift);
+    // ---- per-tile scales: q' = scale q first (the forward's order), then the workgroup maximum of |q'|, |k|, |v|, |dO|
+    float mq = 0.f, mk = 0.f, mv = 0.f, md = 0.f;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      rq[it].x *= p.scale; rq[it].y *= p.scale; rq[it].z *= p.scale; rq[it].w *= p.scale;
+      mq = amax4(mq, rq[it]); mk = amax4(mk, rk[it]); mv = amax4(mv, rv[it]); md = amax4(md, rd[it]);
+    }
+    mq = wave_max(mq); mk = wave_max(mk); mv = wave_max(mv); md = wave_max(md);
+    float (&am)[4][4] = amax[tt & 1];                                     // double-buffered: no barrier between two windows' maxima
+    if (lane == 0) { am[wave][0] = mq; am[wave][1] = mk; am[wave][2] = mv; am[wave][3] = md; }
+    __syncthreads();                                                     // maxima are in; the previous window's tiles are consumed
+    mq = fmaxf(fmaxf(am[0][0], am[1][0]), fmaxf(am[2][0], am[3][0]));
+    mk = fmaxf(fmaxf(am[0][1], am[1][1]), fmaxf(am[2][1], am[3][1]));
+    mv = fmaxf(fmaxf(am[0][2], am[1][2]), fmaxf(am[2][2], am[3][2]));
+    md = fmaxf(fmaxf(am[0][3], am[1][3]), fmaxf(am[2][3], am[3][3]));
+    const float sq = mq > 0.f ? 224.f / mq : 1.f, sk = mk > 0.f ? 224.f / mk : 1.f, sv = mv > 0.f ? 224.f / mv : 1.f;
+    const float so = md > 0.f ? 224.f / md : 1.f;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int r = r0 + 32 * it;                                        // rows >= 49 hold zeros (registers were zeroed)
+      put_fp8(Qs, r, ch, rq[it], sq); put_fp8(Ks, r, ch, rk[it], sk); put_fp8(Vs, r, ch, rv[it], sv); put_fp8(Ds, r, ch, rd[it], so);
+    }
+    __syncthreads();
+    if (tt + 1 < p.tasks_per_wave && task + 1 < p.ntasks)
+      fetch_rows(p, task_map(task + 1, nW, nWx, p.H, p.W, p.shift), colq, r0, ch, rq, rk, rv, rd);
+    // ---- phase 1, this wave's 16 queries: S and dP in the forward's strip layout (element (q = 16 wave + 4 lg + j, key = 16 nt + lr))
+    f32x4 s[4], dp[4];
+    {
+      const int off = (wave * 16 + lr) * LDQ_8 + lg * 8;
+      const long a = *reinterpret_cast<const long*>(Qs + off), c = *reinterpret_cast<const long*>(Ds + off);
+      const float un = 1.f / (sq * sk), unp = 1.f / (so * sv);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const int offb = (nt * 16 + lr) * LDQ_8 + lg * 8;
+        const long b = *reinterpret_cast<const long*>(Ks + offb), d = *reinterpret_cast<const long*>(Vs + offb);
+        s[nt] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        dp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(c, d, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s[nt][j] *= un; dp[nt][j] *= unp; }
+      }
+    }
+    bias_mask_softmax_strip(s, bias, tm, lane, p.shift > 0 && (tm.wy == p.H / 7 - 1 || tm.wx == nWx - 1), wave);
+    float ms = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int q = wave * 16 + lg * 4 + j;
+      float r = 0.f;
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) r += dp[nt][j] * s[nt][j];
+      r = group16_sum(r);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const float dsv = s[nt][j] * (dp[nt][j] - r);
+        dp[nt][j] = dsv;
+        ms = fmaxf(ms, fabsf(dsv));
+        if (q < WT && nt * 16 + lr < WT) dsum[nt][j] += dsv;
+      }
+    }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)     // Pq as [key][query]: the four queries of this lane are consecutive
+      *reinterpret_cast<uint32_t*>(Pt + (nt * 16 + lr) * LDT_8 + wave * 16 + lg * 4) =
+          pack4_fp8(s[nt][0] * 256.f, s[nt][1] * 256.f, s[nt][2] * 256.f, s[nt][3] * 256.f);
+    ms = wave_max(ms);
+    if (lane == 0) amaxs[wave] = ms;
+    __syncthreads();
+    ms = fmaxf(fmaxf(amaxs[0], amaxs[1]), fmaxf(amaxs[2], amaxs[3]));
+    const float ss = ms > 0.f ? 224.f / ms : 1.f;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+      *reinterpret_cast<uint32_t*>(St + (nt * 16 + lr) * LDT_8 + wave * 16 + lg * 4) =
+          pack4_fp8(dp[nt][0] * ss, dp[nt][1] * ss, dp[nt][2] * ss, dp[nt][3] * ss);
+    __syncthreads();
+    // ---- phase 2: transposed products X^T[d = 16 nt + 4 lg + j][token = 16 wave + lr], contraction over 64 keys (dQ) or queries (dK, dV)
+    f32x4 aq[2], ak[2], av[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) { aq[nt] = (f32x4){0.f, 0.f, 0.f, 0.f}; ak[nt] = aq[nt]; av[nt] = aq[nt]; }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int off = (wave * 16 + lr) * LDT_8 + ks * 32 + lg * 8;
+      const long bs = tr8_frag(St, LDT_8, ks * 32, wave * 16, lane);    // dSq[q = 16 wave + lr][keys 32 ks + 8 lg ..]
+      const long bst = *reinterpret_cast<const long*>(St + off);         // dSq[queries 32 ks + 8 lg ..][key = 16 wave + lr]
+      const long bpt = *reinterpret_cast<const long*>(Pt + off);         // Pq [queries ..][key]
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {                                   // K^T, Q^T, dO^T fragments: [d = 16 nt + lr][tokens 32 ks + 8 lg ..]
+        aq[nt] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(tr8_frag(Ks, LDQ_8, ks * 32, nt * 16, lane), bs, aq[nt], 0, 0, 0);
+        ak[nt] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(tr8_frag(Qs, LDQ_8, ks * 32, nt * 16, lane), bst, ak[nt], 0, 0, 0);
+        av[nt] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(tr8_frag(Ds, LDQ_8, ks * 32, nt * 16, lane), bpt, av[nt], 0, 0, 0);
+      }
+    }
+    {
+      const int t = wave * 16 + lr;                // the query of dQ and the key of dK / dV
+      if (t < WT) {
+        const float uq = p.scale / (ss * sk), uk = 1.f / (ss * sq), uv = 1.f / (256.f * so);
+        AT* dst = p.dqkv + (size_t)tm.row(t) * ld + colq + lg * 4;
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+          st4f(dst + nt * 16, make_float4(aq[nt][0] * uq, aq[nt][1] * uq, aq[nt][2] * uq, aq[nt][3] * uq));
+          st4f(dst + p.C + nt * 16, make_float4(ak[nt][0] * uk, ak[nt][1] * uk, ak[nt][2] * uk, ak[nt][3] * uk));
+          st4f(dst + 2 * p.C + nt * 16, make_float4(av[nt][0] * uv, av[nt][1] * uv, av[nt][2] * uv, av[nt][3] * uv));
+        }
+      }
+    }
+  }
+  // ---- relative-position-bias gradient: registers -> LDS (once per workgroup) -> slot image or table (as win_attn_bwd_wg_kernel)
+  __syncthreads();
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    const int key = nt * 16 + lr, ky = key / 7, kx = key - ky * 7;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int q = wave * 16 + lg * 4 + j, qy = q / 7, qx = q - qy * 7;
+      if (q < WT && key < WT) atomicAdd(dbt + (qy - ky + 6) * 13 + (qx - kx + 6), dsum[nt][j]);
+    }
+  }
+  __syncthreads();
+  float* dst = dt_ws ? dt_ws + (size_t)(chunk % ATTN_DT_SLOTS) * 169 * p.heads : p.dtable;
+  for (int i = tid; i < 169; i += 256) {
+    const float v = dbt[i];
+    if (v != 0.f) atomicAdd(dst + i * p.heads + head, v);
+  }
+}
+
 __global__ __launch_bounds__(256) void attn_dtable_fold_kernel(const float* __restrict__ ws, float* __restrict__ dtable, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -1844,7 +2052,8 @@ static int win_check(const void* qkv, const float* table, int I, int H, int W, i
   SV_REQUIRE(shift >= 0 && shift < 7 && (shift == 0 || (H > 7 && W > 7)), "window_attention: bad shift %d for map %dx%d", shift, H, W);
   SV_REQUIRE(((uintptr_t)qkv & 15) == 0, "window_attention: qkv must be 16-byte aligned");
   SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(act_dtype == SV_F32 || math == SV_MATH_BF16 || math == SV_MATH_FP8, "window_attention: bf16 activations require SV_MATH_BF16 / SV_MATH_FP8");
+  SV_REQUIRE(act_dtype == SV_F32 || math == SV_MATH_BF16 || math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL,
+             "window_attention: bf16 activations require SV_MATH_BF16 / SV_MATH_FP8 / SV_MATH_FP8_FULL");
   return SV_OK;
 }
 
@@ -1866,7 +2075,7 @@ extern "C" int sv_window_attention_fwd(const void* qkv, const float* table, void
   SV_REQUIRE(out, "window_attention_fwd: null out");
   const int ntasks = I * (H / 7) * (W / 7);
   hipStream_t s = (hipStream_t)stream;
-  if (math == SV_MATH_FP8) {    // e4m3 operands for QK^T and PV (forward only; the backward entry point treats SV_MATH_FP8 as bf16)
+  if (math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL) {   // e4m3 operands for QK^T and PV (the backward of SV_MATH_FP8 is bf16)
     int tpb = (int)((long long)ntasks * heads / 2048); if (tpb < 1) tpb = 1; if (tpb > 8) tpb = 8;
     dim3 grid(wg_grid(cdiv(ntasks, tpb), heads));
     if (act_dtype == SV_BF16) {
@@ -1908,7 +2117,20 @@ extern "C" int sv_window_attention_bwd(const void* qkv, const float* table, cons
   SV_REQUIRE(dout && dqkv && dtable && ((uintptr_t)dout & 15) == 0, "window_attention_bwd: null/unaligned argument");
   const int ntasks = I * (H / 7) * (W / 7);
   hipStream_t s = (hipStream_t)stream;
-  if (math == SV_MATH_BF16 || math == SV_MATH_FP8) {   // workgroup per window, tpb windows of one head per workgroup
+  if (math == SV_MATH_FP8_FULL) {   // e4m3 operands for all five contractions: the gradient of the SV_MATH_FP8 forward
+    const int tpb = wg_tasks_per_block(ntasks, heads, 3);
+    dim3 grid(wg_grid(cdiv(ntasks, tpb), heads));
+    if (act_dtype == SV_BF16) {
+      WinArgsT<__bf16> a = win_args<__bf16>(qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift);
+      a.tasks_per_wave = tpb;
+      hipLaunchKernelGGL(win_attn_bwd_wg_fp8_kernel<__bf16>, grid, dim3(256), 0, s, a, workspace);
+    } else {
+      WinArgs a = win_args<float>(qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift);
+      a.tasks_per_wave = tpb;
+      hipLaunchKernelGGL(win_attn_bwd_wg_fp8_kernel<float>, grid, dim3(256), 0, s, a, workspace);
+    }
+    if (workspace) hipLaunchKernelGGL(attn_dtable_fold_kernel, dim3(cdiv(169 * heads, 256)), dim3(256), 0, s, workspace, dtable, 169 * heads);
+  } else if (math == SV_MATH_BF16 || math == SV_MATH_FP8) {   // workgroup per window, tpb windows of one head per workgroup
     const int tpb = wg_tasks_per_block(ntasks, heads, 3);
     dim3 grid(wg_grid(cdiv(ntasks, tpb), heads));
     if (act_dtype == SV_BF16) {

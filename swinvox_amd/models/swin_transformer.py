@@ -276,7 +276,7 @@ def _attention_backward(blk, x, m1, r1, ln1, qkv, att, sc1, dx1, grads, I, H, W,
     # backward = 2.5 x the forward products (recomputed P, dP, dQ, dK, dV); bytes: qkv + dout in, dqkv out
     ops.traced_call("sv_window_attention_bwd", 10.0 * 49 * 32 * M * blk.heads, esz * 7 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
                     ptr(datt), ptr(dqkv), ptr(grads[blk.attn.relative_position_bias_table]), ptr(ws), I, H, W, Cd, blk.heads, blk.shift,
-                    ops._STATE["math"], tag=f"M={M} C={Cd}")
+                    ops.attention_bwd_math(), tag=f"M={M} C={Cd}")
     ops.linear_wgrad(dqkv, ln1, M, blk.s_qkv, grads[blk.attn.qkv.weight], grads[blk.attn.qkv.bias])
     dln1 = empty(M, Cd, like=x)
     ops.linear_dgrad(dqkv, M, blk.s_qkv, blk.s_qkv.pack_dgrad(blk.attn.qkv.weight), dln1)

@@ -492,9 +492,12 @@ def fused_attn_block_enabled(C: int, heads: int) -> bool:
 def fused_attn_block_bwd_enabled(C: int, heads: int) -> bool:
     """The fused BACKWARD of the attention branch (csrc/attn.hip swin_attn_block_bwd_kernel) serves the same blocks as the fused forward; it
     reads what either forward stores (qkv, LayerNorm statistics), so fp8 attention in the forward does not switch it off.
-    A/B: SV_FUSED_ATTN_BWD=0 or set_fused_attn_block_bwd(False) route the branch through the unfused four-kernel chain."""
+    A/B: SV_FUSED_ATTN_BWD=0 or set_fused_attn_block_bwd(False) route the branch through the unfused four-kernel chain.  The fp8
+    backward (set_attention_fp8(True, backward=True)) switches it off: its core kernel is a separate build."""
     import os
     if os.environ.get("SV_FUSED_ATTN_BWD", "1") == "0" or not _STATE.get("fused_attn_block_bwd", True):
+        return False
+    if _STATE.get("attn_fp8") and _STATE.get("attn_fp8_bwd"):
         return False
     return (_STATE["math"] == hip.MATH_BF16 and _STATE["store"] == torch.bfloat16
             and hip.load().sv_swin_attn_block_supported(C, heads, hip.BF16, hip.MATH_BF16) == 1)
@@ -509,15 +512,25 @@ def set_fused_attn_block(on: bool) -> None:
     _STATE["fused_attn_block"] = bool(on)
 
 
-def set_attention_fp8(on: bool) -> None:
+def set_attention_fp8(on: bool, backward: bool = False) -> None:
     """BASELINE configuration 5: QK^T and PV of the Swin window attention FORWARD on fp8 (OCP e4m3) MFMA operands with per-(window, head)
-    scales; everything else (and the whole backward) keeps bf16 operands.  Needs set_math('bf16')."""
+    scales; everything else keeps bf16 operands.  With backward=True the window-attention backward differentiates that fp8 forward
+    (quantisers straight-through) with all five of its contractions on e4m3 operands; otherwise it is the bf16 backward.
+    Needs set_math('bf16')."""
     _STATE["attn_fp8"] = bool(on)
+    _STATE["attn_fp8_bwd"] = bool(on) and bool(backward)
 
 
 def attention_math() -> int:
     """math code of the window-attention forward call"""
     return hip.MATH_FP8 if (_STATE.get("attn_fp8") and _STATE["math"] == hip.MATH_BF16) else _STATE["math"]
+
+
+def attention_bwd_math() -> int:
+    """math code of the window-attention backward call"""
+    if _STATE.get("attn_fp8") and _STATE.get("attn_fp8_bwd") and _STATE["math"] == hip.MATH_BF16:
+        return hip.MATH_FP8_FULL
+    return _STATE["math"]
 
 
 def set_fused_mlp(on: bool) -> None:
