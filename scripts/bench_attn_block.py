@@ -8,8 +8,6 @@ import swinvox_amd as S
 from swinvox_amd import hip, ops
 from swinvox_amd.hip import call, ptr
 from swinvox_amd.ops import ConvSpec
-if os.environ.get("SV_LIB"):
-    hip.LIB_PATH = os.environ["SV_LIB"]      # A/B builds of the library
 dev = torch.device("cuda", 0); hip.load(); S.set_math("bf16"); S.set_storage("bf16")
 def timeit(fn, iters=10):
     for _ in range(2): fn()

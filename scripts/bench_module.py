@@ -1,11 +1,9 @@
 """One module's forward + backward at the default bench shape (B=32, V=8), for kernel traces of a single module.
-python scripts/bench_module.py {encoder,decoder,merger,refiner}   (SV_LIB=<path> for A/B builds, SV_B=<samples>)"""
+python scripts/bench_module.py {encoder,decoder,merger,refiner}   (SV_HIP_LIB=<path> for A/B builds, SV_B=<samples>)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import swinvox_amd as S
 from swinvox_amd import hip
-if os.environ.get("SV_LIB"):
-    hip.LIB_PATH = os.environ["SV_LIB"]
 from swinvox_amd.models import Decoder, Encoder, Merger, Refiner
 dev = torch.device("cuda", 0); hip.load(); S.set_math("bf16"); S.set_storage("bf16")
 which = sys.argv[1] if len(sys.argv) > 1 else "merger"

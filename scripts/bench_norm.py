@@ -6,8 +6,6 @@ import swinvox_amd as S
 from swinvox_amd import hip, ops
 from swinvox_amd.hip import call, ptr
 from swinvox_amd.ops import ACT_RELU, BatchNormState
-if os.environ.get("SV_LIB"):
-    hip.LIB_PATH = os.environ["SV_LIB"]
 dev = torch.device("cuda", 0); hip.load(); S.set_math("bf16"); S.set_storage("bf16")
 def timeit(fn, iters=20):
     for _ in range(3): fn()

@@ -1,8 +1,13 @@
 // Attention kernels.
-//  * Swin window / shifted-window attention core (timm WindowAttention behind models/swin_transformer.py:78):
-//    one wave per (image, window, head); the cyclic shift, the 7x7 window partition/reverse and the 9-region
-//    shift mask are folded into the token index math (no materialised roll); q/k/v tiles of the window are
-//    staged in LDS, QK^T and PV run on MFMA, the softmax runs on the accumulator layout with 16-lane shuffles.
+//  * Swin window / shifted-window attention core (timm WindowAttention behind models/swin_transformer.py:78).  The cyclic shift, the
+//    7x7 window partition/reverse and the 9-region shift mask are folded into the token index math (no materialised roll); the q/k/v
+//    tiles of a window are staged in LDS, every product runs on MFMA, the softmax runs on the accumulator registers.
+//      - exact fp32: one WAVE per (image, window, head), the whole 64 x 64 score matrix in registers (win_attn_fwd_kernel / _bwd_kernel);
+//      - bf16 and fp8 (e4m3) MFMA: one WORKGROUP per (window, head), each of its 4 waves owns 16 queries (win_attn_*_wg_*kernel);
+//      - stage-0 blocks (C = 96): LayerNorm, qkv, attention, projection and residual in one kernel each way (swin_attn_block_*_kernel).
+//    A wave's 16 x 64 score strip comes in two layouts.  STRIP (queries 4 lg + j, key 16 nt + lr; fp32 and fp8 kernels) is owned by
+//    strip_bias / bias_mask_softmax_strip; QUERY-IN-LANE (query lr, keys 16 nt + 4 lg + j; bf16 and fused kernels) by lane_bias /
+//    seam_kdiff / softmax_lane.  dbias_flush takes the bias-table gradient of either layout to HBM.
 //  * Cross-view attention core (models/cross_view_attention.py:81-105): one workgroup per (sample, head),
 //    V x V scores over 288-long features -- tiny, plain FMA.
 #include "common.h"
@@ -39,7 +44,20 @@ struct TokMap {  // window -> token rows of the un-shifted [I,H,W] map
     const int b = rx < W - 7 ? 0 : (rx < W - shift ? 1 : 2);
     return a * 3 + b;
   }
+  // a window touching the rolled seam (last window row / column of a shifted block): tokens of different regions must not attend to each other
+  __device__ __forceinline__ bool seam() const { return shift > 0 && (wy == H / 7 - 1 || wx == W / 7 - 1); }
 };
+__device__ __forceinline__ TokMap task_map(long long task, int nW, int nWx, int H, int W, int shift) {
+  TokMap tm;
+  tm.img = (int)(task / nW); const int win = (int)(task - (long long)tm.img * nW);
+  tm.wy = win / nWx; tm.wx = win - tm.wy * nWx; tm.H = H; tm.W = W; tm.shift = shift;
+  return tm;
+}
+// row of the [169] relative-position-bias table of a head for (query, key) tokens of a window
+__device__ __forceinline__ int rel_index(int q, int key) {
+  const int qy = q / 7, qx = q - qy * 7, ky = key / 7, kx = key - ky * 7;
+  return (qy - ky + 6) * 13 + (qx - kx + 6);
+}
 
 // all-reduce over the 16 lanes of a DPP row, every lane gets the result: quad_perm xor 1, xor 2, row_half_mirror (i <-> 7 - i: the two quads
 // of a half), row_mirror (i <-> 15 - i: the two halves).  Four VALU DPP moves instead of four ds_bpermute round trips through the LDS crossbar.
@@ -72,11 +90,10 @@ template <typename OP> __device__ __forceinline__ float lanegroup_allreduce(floa
 // element (q = mt*16 + lg*4 + j, key = nt*16 + lr)
 __device__ __forceinline__ void bias_mask_softmax(f32x4 (&s)[4][4], const float* bt, const TokMap& tm, int lane, bool shifted) {
   const int lr = lane & 15, lg = lane >> 4;
-  int ky[4], kx[4], kreg[4];
+  int kreg[4];
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) {
     const int key = nt * 16 + lr;
-    ky[nt] = key / 7; kx[nt] = key - ky[nt] * 7;
     kreg[nt] = (shifted && key < WT) ? tm.region(key) : 0;
   }
 #pragma unroll
@@ -84,7 +101,6 @@ __device__ __forceinline__ void bias_mask_softmax(f32x4 (&s)[4][4], const float*
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int q = mt * 16 + lg * 4 + j;
-      const int qy = q / 7, qx = q - qy * 7;
       const int qreg = (shifted && q < WT) ? tm.region(q) : 0;
       float mx = -3.0e38f;
 #pragma unroll
@@ -93,7 +109,7 @@ __device__ __forceinline__ void bias_mask_softmax(f32x4 (&s)[4][4], const float*
         float v = s[mt][nt][j];
         if (key >= WT) v = -1.0e30f;
         else if (q < WT) {
-          v += bt[(qy - ky[nt] + 6) * 13 + (qx - kx[nt] + 6)];
+          v += bt[rel_index(q, key)];
           if (shifted && qreg != kreg[nt]) v += -100.0f;
         }
         s[mt][nt][j] = v;
@@ -124,9 +140,9 @@ __device__ __forceinline__ void load_tile_f32(float* dst, const AT* src, int ld,
   }
 }
 
-template <bool BF16, typename AT>
-__global__ __launch_bounds__(256) void win_attn_fwd_kernel(const WinArgsT<AT> p) {
-  constexpr int WAVE_BYTES = BF16 ? (2 * 64 * LDQ_H + HD * LDP_H) * 2 + 176 * 4 : 3 * 64 * LDQ_F * 4 + 176 * 4;
+// forward (exact fp32 MFMA): one wave per (image, window, head), four waves per workgroup
+__global__ __launch_bounds__(256) void win_attn_fwd_kernel(const WinArgs p) {
+  constexpr int WAVE_BYTES = 3 * 64 * LDQ_F * 4 + 176 * 4;
   __shared__ __attribute__((aligned(16))) char smem[4 * WAVE_BYTES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lg = lane >> 4;
@@ -135,9 +151,7 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const WinArgsT<AT> p)
   long long task = (long long)blockIdx.x * 4 + wave;
   const bool active = task < p.ntasks;
   if (!active) task = p.ntasks - 1;
-  TokMap tm;
-  tm.img = (int)(task / nW); const int win = (int)(task - (long long)tm.img * nW);
-  tm.wy = win / nWx; tm.wx = win - tm.wy * nWx; tm.H = p.H; tm.W = p.W; tm.shift = p.shift;
+  const TokMap tm = task_map(task, nW, nWx, p.H, p.W, p.shift);
   const int ld = 3 * p.C, colq = head * HD;
   char* base = smem + wave * WAVE_BYTES;
   float* bt = reinterpret_cast<float*>(base + WAVE_BYTES - 176 * 4);
@@ -152,103 +166,44 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const WinArgsT<AT> p)
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) { o[mt][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; o[mt][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 
-  if constexpr (!BF16) {
-    float* Qs = reinterpret_cast<float*>(base);
-    float* Ks = Qs + 64 * LDQ_F;
-    float* Vs = Ks + 64 * LDQ_F;
-    float* Ps = Qs;  // aliases Q,K once the scores are in registers
-    load_tile_f32(Qs, p.qkv, ld, colq, tm, lane, p.scale);
-    load_tile_f32(Ks, p.qkv, ld, p.C + colq, tm, lane, 1.f);
-    load_tile_f32(Vs, p.qkv, ld, 2 * p.C + colq, tm, lane, 1.f);
-    __syncthreads();
+  float* Qs = reinterpret_cast<float*>(base);
+  float* Ks = Qs + 64 * LDQ_F;
+  float* Vs = Ks + 64 * LDQ_F;
+  float* Ps = Qs;  // aliases Q,K once the scores are in registers
+  load_tile_f32(Qs, p.qkv, ld, colq, tm, lane, p.scale);
+  load_tile_f32(Ks, p.qkv, ld, p.C + colq, tm, lane, 1.f);
+  load_tile_f32(Vs, p.qkv, ld, 2 * p.C + colq, tm, lane, 1.f);
+  __syncthreads();
 #pragma unroll
-    for (int kk = 0; kk < HD / 4; ++kk) {
-      float a[4], b[4];
+  for (int kk = 0; kk < HD / 4; ++kk) {
+    float a[4], b[4];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) { a[t] = Qs[(t * 16 + lr) * LDQ_F + kk * 4 + lg]; b[t] = Ks[(t * 16 + lr) * LDQ_F + kk * 4 + lg]; }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) s[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], b[nt], s[mt][nt], 0, 0, 0);
-    }
-    bias_mask_softmax(s, bt, tm, lane, p.shift > 0);
-    __syncthreads();
+    for (int t = 0; t < 4; ++t) { a[t] = Qs[(t * 16 + lr) * LDQ_F + kk * 4 + lg]; b[t] = Ks[(t * 16 + lr) * LDQ_F + kk * 4 + lg]; }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
+      for (int nt = 0; nt < 4; ++nt) s[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], b[nt], s[mt][nt], 0, 0, 0);
+  }
+  bias_mask_softmax(s, bt, tm, lane, p.shift > 0);
+  __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 4; ++j) Ps[(mt * 16 + lg * 4 + j) * LDP_F + nt * 16 + lr] = s[mt][nt][j];
-    __syncthreads();
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Ps[(mt * 16 + lg * 4 + j) * LDP_F + nt * 16 + lr] = s[mt][nt][j];
+  __syncthreads();
 #pragma unroll 4
-    for (int kk = 0; kk < 16; ++kk) {
-      float a[4], b[2];
+  for (int kk = 0; kk < 16; ++kk) {
+    float a[4], b[2];
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt) a[mt] = Ps[(mt * 16 + lr) * LDP_F + kk * 4 + lg];
+    for (int mt = 0; mt < 4; ++mt) a[mt] = Ps[(mt * 16 + lr) * LDP_F + kk * 4 + lg];
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt) b[nt] = Vs[(kk * 4 + lg) * LDQ_F + nt * 16 + lr];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) o[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], b[nt], o[mt][nt], 0, 0, 0);
-    }
-  } else {
-    __bf16* Qs = reinterpret_cast<__bf16*>(base);
-    __bf16* Ks = Qs + 64 * LDQ_H;
-    __bf16* Vt = Ks + 64 * LDQ_H;   // [d][key]
-    __bf16* Ps = Qs;                // [q][key], aliases Q,K
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int r = (lane >> 3) + 8 * it, ch = (lane & 7) * 4;
-      float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f), k4 = q4, v4 = q4;
-      if (r < WT) {
-        const AT* src = p.qkv + (size_t)tm.row(r) * ld + colq + ch;
-        q4 = ld4f(src);
-        k4 = ld4f(src + p.C);
-        v4 = ld4f(src + 2 * p.C);
-      }
-      bf16x4 qb, kb;
-      qb[0] = (__bf16)(q4.x * p.scale); qb[1] = (__bf16)(q4.y * p.scale); qb[2] = (__bf16)(q4.z * p.scale); qb[3] = (__bf16)(q4.w * p.scale);
-      kb[0] = (__bf16)k4.x; kb[1] = (__bf16)k4.y; kb[2] = (__bf16)k4.z; kb[3] = (__bf16)k4.w;
-      *reinterpret_cast<bf16x4*>(Qs + r * LDQ_H + ch) = qb;
-      *reinterpret_cast<bf16x4*>(Ks + r * LDQ_H + ch) = kb;
-      Vt[(ch + 0) * LDP_H + r] = (__bf16)v4.x; Vt[(ch + 1) * LDP_H + r] = (__bf16)v4.y;
-      Vt[(ch + 2) * LDP_H + r] = (__bf16)v4.z; Vt[(ch + 3) * LDP_H + r] = (__bf16)v4.w;
-    }
-    __syncthreads();
-    {
-      bf16x8 a[4], b[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        a[t] = *reinterpret_cast<const bf16x8*>(Qs + (t * 16 + lr) * LDQ_H + lg * 8);
-        b[t] = *reinterpret_cast<const bf16x8*>(Ks + (t * 16 + lr) * LDQ_H + lg * 8);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) s[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt], b[nt], s[mt][nt], 0, 0, 0);
-    }
-    bias_mask_softmax(s, bt, tm, lane, p.shift > 0);
-    __syncthreads();
+    for (int nt = 0; nt < 2; ++nt) b[nt] = Vs[(kk * 4 + lg) * LDQ_F + nt * 16 + lr];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) Ps[(mt * 16 + lg * 4 + j) * LDP_H + nt * 16 + lr] = (__bf16)s[mt][nt][j];
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 a[4], b[2];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) a[mt] = *reinterpret_cast<const bf16x8*>(Ps + (mt * 16 + lr) * LDP_H + ks * 32 + lg * 8);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const bf16x8*>(Vt + (nt * 16 + lr) * LDP_H + ks * 32 + lg * 8);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) o[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt], b[nt], o[mt][nt], 0, 0, 0);
-    }
+      for (int nt = 0; nt < 2; ++nt) o[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], b[nt], o[mt][nt], 0, 0, 0);
   }
   if (active) {
 #pragma unroll
@@ -257,9 +212,8 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const WinArgsT<AT> p)
       for (int j = 0; j < 4; ++j) {
         const int q = mt * 16 + lg * 4 + j;
         if (q < WT) {
-          AT* dst = p.out + (size_t)tm.row(q) * p.C + colq;
-          stf(dst + lr, o[mt][0][j]);
-          stf(dst + 16 + lr, o[mt][1][j]);
+          float* dst = p.out + (size_t)tm.row(q) * p.C + colq;
+          dst[lr] = o[mt][0][j]; dst[16 + lr] = o[mt][1][j];
         }
       }
   }
@@ -291,9 +245,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     long long task = task0 + tt;
     const bool active = task < p.ntasks;   // inactive waves keep running (barriers) on a clamped task, stores suppressed
     if (!active) task = p.ntasks - 1;
-    TokMap tm;
-    tm.img = (int)(task / nW); const int win = (int)(task - (long long)tm.img * nW);
-    tm.wy = win / nWx; tm.wx = win - tm.wy * nWx; tm.H = p.H; tm.W = p.W; tm.shift = p.shift;
+    const TokMap tm = task_map(task, nW, nWx, p.H, p.W, p.shift);
 
     __syncthreads();  // previous task's LDS reads done
     load_tile_f32(Qs, p.qkv, ld, colq, tm, lane, p.scale);
@@ -344,14 +296,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int j = 0; j < 4; ++j) {
           const int q = mt * 16 + lg * 4 + j;
           if (q < WT) {
-            const int qy = q / 7, qx = q - qy * 7;
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
               const int key = nt * 16 + lr;
-              if (key < WT) {
-                const int ky = key / 7, kx = key - ky * 7;
-                atomicAdd(dbt + (qy - ky + 6) * 13 + (qx - kx + 6), dp[mt][nt][j]);
-              }
+              if (key < WT) atomicAdd(dbt + rel_index(q, key), dp[mt][nt][j]);
             }
           }
         }
@@ -626,18 +574,52 @@ __global__ __launch_bounds__(256) void cva_attn_bwd_kernel(const CvaArgsT<AT> p)
 // bias + mask + softmax over the keys for ONE 16-row strip (query rows mt*16 + lg*4 + j, keys nt*16 + lr).
 // The relative-position bias of this lane's 16 (query, key) slots is the same for every window of a head: it is gathered
 // once per workgroup into registers (strip_bias); the shifted-window mask only exists in the last window row / column.
-__device__ __forceinline__ void strip_bias(float (&bias)[4][4], const float* bt, int lane, int mt, float mul = 1.f) {
+__device__ __forceinline__ void strip_bias(float (&bias)[4][4], const float* bt, int lane, int mt) {
   const int lr = lane & 15, lg = lane >> 4;
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) {
-    const int key = nt * 16 + lr, ky = key / 7, kx = key - ky * 7;
+    const int key = nt * 16 + lr;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int q = mt * 16 + lg * 4 + j, qy = q / 7, qx = q - qy * 7;
-      bias[nt][j] = key >= WT ? -1.0e30f : (q < WT ? mul * bt[(qy - ky + 6) * 13 + (qx - kx + 6)] : 0.f);   // key padding: excluded
+      const int q = mt * 16 + lg * 4 + j;
+      bias[nt][j] = key >= WT ? -1.0e30f : (q < WT ? bt[rel_index(q, key)] : 0.f);   // key padding: excluded
     }
   }
 }
+// The same registers in the QUERY-IN-LANE layout of the transposed score blocks S^T = K Q^T (keys as the first MFMA operand): lane -> query q
+// (= 16 wave + lr), keys 16 nt + 4 lg + j.  mul: log2(e) where bt holds the plain table and the softmax runs in the exp2 domain.
+__device__ __forceinline__ void lane_bias(float (&bias)[4][4], const float* bt, int q, int lg, float mul = 1.f) {
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = nt * 16 + lg * 4 + j;
+      bias[nt][j] = key >= WT ? -1.0e30f : (q < WT ? bt[rel_index(q, key)] * mul : 0.f);   // key padding: excluded
+    }
+}
+// seam mask of query q in that layout: bit (4 nt + j) is set where key 16 nt + 4 lg + j lies in another region of the rolled map (TokMap::region)
+// than q.  Inside one window the regions split at token row 7 - shift of the last window row and at token column 7 - shift of the last window
+// column, so the mask is two window-independent bit sets (key row / column below the split) picked by the window's position.
+__device__ __forceinline__ unsigned seam_kdiff(const TokMap& tm, int q, int lg) {
+  const int split = 7 - tm.shift, qy = q / 7, qx = q - qy * 7;
+  unsigned ylow = 0, xlow = 0, valid = 0;
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = nt * 16 + lg * 4 + j, ky = key / 7, kx = key - ky * 7;
+      const unsigned bit = 1u << (nt * 4 + j);
+      if (key < WT) valid |= bit;
+      if (ky < split) ylow |= bit;
+      if (kx < split) xlow |= bit;
+    }
+  unsigned kdiff = 0;
+  if (tm.wy == tm.H / 7 - 1) kdiff |= qy < split ? ~ylow : ylow;
+  if (tm.wx == tm.W / 7 - 1) kdiff |= qx < split ? ~xlow : xlow;
+  return q < WT ? kdiff & valid : 0u;
+}
+struct FMax2 { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+struct FAdd2 { __device__ __forceinline__ float operator()(float a, float b) const { return a + b; } };
 // LOG2: scores and bias arrive multiplied by log2(e) (the forward folds the factor into the scale of Q and into the bias strip), so the
 // exponential is one v_exp_f32 without the multiply __expf carries
 constexpr float ATTN_LOG2E = 1.4426950408889634f;
@@ -676,29 +658,88 @@ __device__ __forceinline__ void bias_mask_softmax_strip(f32x4 (&s)[4], const flo
   }
 }
 
-__device__ __forceinline__ float4 to_f4(float4 v) { return v; }
-__device__ __forceinline__ float4 to_f4(bf16x4 b) { return make_float4((float)b[0], (float)b[1], (float)b[2], (float)b[3]); }
-
-// cooperative (256 threads) load of one [49(64) x 32] head slice into a bf16 LDS tile [64][LDQ_H]; rows >= 49 zeroed
-template <typename AT>
-__device__ __forceinline__ void load_tile_wg(__bf16* dst, const AT* src, int ld, int col, const TokMap& tm, int tid, float mul) {
+// The QUERY-IN-LANE softmax of one query: s = smul * s + bias (smul: what the raw product still owes - 1, or log2(e) where the q tile carries
+// the plain softmax scale), seam mask from seam_kdiff (`masked` is uniform over the window), then 16 in-lane values + two lane-group exchanges
+// per reduction.  Returns 1 / sum; NORMALISE = false leaves the exponentials unnormalised for a caller that folds the factor into its bf16 pack.
+template <bool LOG2, bool NORMALISE>
+__device__ __forceinline__ float softmax_lane(f32x4 (&s)[4], const float (&bias)[4][4], float smul, bool masked, unsigned kdiff) {
+  float mx = -3.0e38f;
 #pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int r = (tid >> 3) + 32 * it, ch = (tid & 7) * 4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < WT) v = ld4f(src + (size_t)tm.row(r) * ld + col + ch);
-    bf16x4 b;
-    b[0] = (__bf16)(v.x * mul); b[1] = (__bf16)(v.y * mul); b[2] = (__bf16)(v.z * mul); b[3] = (__bf16)(v.w * mul);
-    *reinterpret_cast<bf16x4*>(dst + r * LDQ_H + ch) = b;
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float v = __builtin_fmaf(s[nt][j], smul, bias[nt][j]);   // key padding: bias = -1e30 under finite scores
+      s[nt][j] = v;
+      mx = fmaxf(mx, v);
+    }
+  if (masked) {
+    mx = -3.0e38f;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (kdiff & (1u << (nt * 4 + j))) s[nt][j] += LOG2 ? -100.0f * ATTN_LOG2E : -100.0f;
+        mx = fmaxf(mx, s[nt][j]);
+      }
+  }
+  mx = lanegroup_allreduce(mx, FMax2());
+  float sum = 0.f;
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float e = LOG2 ? __builtin_amdgcn_exp2f(s[nt][j] - mx) : __expf(s[nt][j] - mx); s[nt][j] = e; sum += e; }
+  const float inv = __builtin_amdgcn_rcpf(lanegroup_allreduce(sum, FAdd2()));   // 1 ulp: the quotient is rounded to bf16 right after
+  if (NORMALISE) {
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[nt][j] *= inv;
+  }
+  return inv;
+}
+
+// Relative-position-bias gradient of a workgroup (256 threads): dsum = the sum of dS over the workgroup's windows at each lane's 16 (query,
+// key) slots of NH heads, in the STRIP or the query-in-lane layout -> dbt (LDS, [NH][176], zero so far) -> one atomic per non-zero table
+// entry into dst[entry * heads + head0 + h] (a slot image of the table, or the table).  Call behind a barrier.
+template <bool STRIP, int NH>
+__device__ __forceinline__ void dbias_flush(const f32x4 (*dsum)[4], float* dbt, float* dst, int head0, int heads, int lane, int wave) {
+  const int lr = lane & 15, lg = lane >> 4;
+#pragma unroll
+  for (int h = 0; h < NH; ++h)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int q = wave * 16 + (STRIP ? lg * 4 + j : lr), key = nt * 16 + (STRIP ? lr : lg * 4 + j);
+        if (q < WT && key < WT) atomicAdd(dbt + h * 176 + rel_index(q, key), dsum[h][nt][j]);
+      }
+  __syncthreads();
+  for (int i = threadIdx.x; i < NH * 169; i += 256) {
+    const int h = NH == 1 ? 0 : i / 169, e = i - h * 169;
+    const float v = dbt[h * 176 + e];
+    if (v != 0.f) atomicAdd(dst + e * heads + head0 + h, v);
   }
 }
 
-__device__ __forceinline__ TokMap task_map(long long task, int nW, int nWx, int H, int W, int shift) {
-  TokMap tm;
-  tm.img = (int)(task / nW); const int win = (int)(task - (long long)tm.img * nW);
-  tm.wy = win / nWx; tm.wx = win - tm.wy * nWx; tm.H = H; tm.W = W; tm.shift = shift;
-  return tm;
+// fp8 tile scales: m[n] = this thread's maximum of |x| over its piece of N tiles -> 224 / (the workgroup's maximum) (half of e4m3's 448: head
+// room for the rounding; 1 for an all-zero tile).  The 4 waves meet in `am` (LDS).  SYNC_FIRST: `am` is single-buffered and may still be
+// read for the previous window, so a barrier goes before the write as well.
+template <int N, bool SYNC_FIRST>
+__device__ __forceinline__ void wg_amax_scale(float (&m)[N], float (*am)[N], int lane, int wave) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) m[n] = wave_max(m[n]);
+  if (SYNC_FIRST) __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) am[wave][n] = m[n];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int n = 0; n < N; ++n) m[n] = fmaxf(fmaxf(am[0][n], am[1][n]), fmaxf(am[2][n], am[3][n]));
+#pragma unroll
+  for (int n = 0; n < N; ++n) m[n] = m[n] > 0.f ? 224.f / m[n] : 1.f;
 }
+__device__ __forceinline__ float amax4(float m, const float4& v) { return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)))); }
 
 // (window chunk, head) of a workgroup in the 1-D grids of the workgroup-per-window kernels.  A head's slice of a token row is
 // 64 bytes - half a cache line - so the `heads` workgroups that walk the same windows must meet in one L2: consecutive
@@ -769,19 +810,8 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_kernel(const WinArgsT<
   const int q = wave * 16 + lr;                      // the query of this lane
   const bool qok = q < WT;
   float bias[4][4];                                  // relative-position bias of this lane's 16 (query, key) slots: the same for every window
-  {
-    const int qy = q / 7, qx = q - qy * 7;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = nt * 16 + lg * 4 + j, ky = key / 7, kx = key - ky * 7;
-        bias[nt][j] = key >= WT ? -1.0e30f : (qok ? bt[(qy - ky + 6) * 13 + (qx - kx + 6)] : 0.f);   // key padding: excluded
-      }
-  }
+  lane_bias(bias, bt, q, lg);
   const float qscale = p.scale * ATTN_LOG2E;      // scores come out of the MFMA in log2 units
-  const auto fmax2 = [](float a, float b) { return fmaxf(a, b); };
-  const auto fadd2 = [](float a, float b) { return a + b; };
   const long long task0 = (long long)chunk * p.tasks_per_wave;
   for (int tt = 0; tt < p.tasks_per_wave; ++tt) {
     const long long task = task0 + tt;
@@ -811,30 +841,8 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_kernel(const WinArgsT<
         s[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);   // lane: query lr, keys 16 nt + 4 lg + j
       }
     }
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[nt][j] += bias[nt][j]; mx = fmaxf(mx, s[nt][j]); }
-    if (p.shift > 0 && (tm.wy == p.H / 7 - 1 || tm.wx == nWx - 1)) {    // a window touching the rolled seam: regions must not attend to each other
-      const int qreg = qok ? tm.region(q) : 0;
-      mx = -3.0e38f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int key = nt * 16 + lg * 4 + j;
-          if (qok && key < WT && tm.region(key) != qreg) s[nt][j] += -100.0f * ATTN_LOG2E;
-          mx = fmaxf(mx, s[nt][j]);
-        }
-    }
-    mx = lanegroup_allreduce(mx, fmax2);
-    float sum = 0.f;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { const float e = __builtin_amdgcn_exp2f(s[nt][j] - mx); s[nt][j] = e; sum += e; }
-    const float inv = __builtin_amdgcn_rcpf(lanegroup_allreduce(sum, fadd2));   // 1 ulp: the quotient is rounded to bf16 right after
+    const bool masked = tm.seam();
+    const float inv = softmax_lane<true, false>(s, bias, 1.f, masked, masked ? seam_kdiff(tm, q, lg) : 0u);
     bf16x8 pf[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -898,7 +906,7 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_fp8_kernel(const WinAr
     if (task >= p.ntasks) break;                                         // uniform over the workgroup
     const TokMap tm = task_map(task, nW, nWx, p.H, p.W, p.shift);
     float4 q4[2], k4[2], v4[2];
-    float mq = 0.f, mk = 0.f, mv = 0.f;
+    float sc[3] = {0.f, 0.f, 0.f};                                       // maxima, then scales, of the q' / k / v tile
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const int r = (tid >> 3) + 32 * it, ch = (tid & 7) * 4;
@@ -908,18 +916,10 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_fp8_kernel(const WinAr
         q4[it] = ld4f(src); k4[it] = ld4f(src + p.C); v4[it] = ld4f(src + 2 * p.C);
       }
       q4[it].x *= p.scale; q4[it].y *= p.scale; q4[it].z *= p.scale; q4[it].w *= p.scale;
-      mq = fmaxf(mq, fmaxf(fmaxf(fabsf(q4[it].x), fabsf(q4[it].y)), fmaxf(fabsf(q4[it].z), fabsf(q4[it].w))));
-      mk = fmaxf(mk, fmaxf(fmaxf(fabsf(k4[it].x), fabsf(k4[it].y)), fmaxf(fabsf(k4[it].z), fabsf(k4[it].w))));
-      mv = fmaxf(mv, fmaxf(fmaxf(fabsf(v4[it].x), fabsf(v4[it].y)), fmaxf(fabsf(v4[it].z), fabsf(v4[it].w))));
+      sc[0] = amax4(sc[0], q4[it]); sc[1] = amax4(sc[1], k4[it]); sc[2] = amax4(sc[2], v4[it]);
     }
-    mq = wave_max(mq); mk = wave_max(mk); mv = wave_max(mv);
-    __syncthreads();                                                     // previous window's tiles (and maxima) are consumed
-    if (lane == 0) { amax[wave][0] = mq; amax[wave][1] = mk; amax[wave][2] = mv; }
-    __syncthreads();
-    mq = fmaxf(fmaxf(amax[0][0], amax[1][0]), fmaxf(amax[2][0], amax[3][0]));
-    mk = fmaxf(fmaxf(amax[0][1], amax[1][1]), fmaxf(amax[2][1], amax[3][1]));
-    mv = fmaxf(fmaxf(amax[0][2], amax[1][2]), fmaxf(amax[2][2], amax[3][2]));
-    const float sq = mq > 0.f ? 224.f / mq : 1.f, sk = mk > 0.f ? 224.f / mk : 1.f, sv = mv > 0.f ? 224.f / mv : 1.f;
+    wg_amax_scale<3, true>(sc, amax, lane, wave);                        // its first barrier: the previous window's tiles (and maxima) are consumed
+    const float sq = sc[0], sk = sc[1], sv = sc[2];
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const int r = (tid >> 3) + 32 * it, ch = (tid & 7) * 4;
@@ -944,7 +944,7 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_fp8_kernel(const WinAr
         for (int j = 0; j < 4; ++j) s[nt][j] *= un;
       }
     }
-    bias_mask_softmax_strip(s, bias, tm, lane, p.shift > 0 && (tm.wy == p.H / 7 - 1 || tm.wx == nWx - 1), wave);
+    bias_mask_softmax_strip(s, bias, tm, lane, tm.seam(), wave);
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -994,19 +994,8 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_kernel(const WinArgsT<
   const int qrow = wave * 16 + lr;
   const bool qrow_ok = qrow < WT;
   float bias[4][4];
-  {
-    const int qy = qrow / 7, qx = qrow - qy * 7;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = nt * 16 + lg * 4 + j, ky = key / 7, kx = key - ky * 7;
-        bias[nt][j] = key >= WT ? -1.0e30f : (qrow_ok ? bt[(qy - ky + 6) * 13 + (qx - kx + 6)] : 0.f);   // key padding: excluded
-      }
-  }
-  const auto fmax2 = [](float a, float b) { return fmaxf(a, b); };
-  const auto fadd2 = [](float a, float b) { return a + b; };
-  f32x4 dsum[4];                                   // sum over this workgroup's windows of dS at this lane's (query, key) slots
+  lane_bias(bias, bt, qrow, lg);
+  f32x4 dsum[4];                                  // sum over this workgroup's windows of dS at this lane's (query, key) slots
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) dsum[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const long long task0 = (long long)chunk * p.tasks_per_wave;
@@ -1021,11 +1010,7 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_kernel(const WinArgsT<
     for (int it = 0; it < HC::NIT; ++it) {
       const int r = HC::row(tid, it), ch = HC::ch(tid);
       rq[it] = VecN<AT, HC::CV>::zero(); rk[it] = rq[it]; rv[it] = rq[it]; rd[it] = rq[it];
-#ifdef SV_AT_PROBE_NOFETCH
-      if (r < 0) {
-#else
       if (r < WT) {
-#endif
         const size_t row = tn.row(r);
         const AT* src = p.qkv + row * ld + colq + ch;
         rq[it] = VecN<AT, HC::CV>::load(src); rk[it] = VecN<AT, HC::CV>::load(src + p.C); rv[it] = VecN<AT, HC::CV>::load(src + 2 * p.C);
@@ -1057,45 +1042,15 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_kernel(const WinArgsT<
         dp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d, c, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
       }
     }
-#ifndef SV_AT_PROBE_NOSOFTMAX
-    {
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s[nt][j] += bias[nt][j]; mx = fmaxf(mx, s[nt][j]); }
-      if (p.shift > 0 && (tm.wy == p.H / 7 - 1 || tm.wx == nWx - 1)) {    // a window touching the rolled seam
-        const int qreg = qrow_ok ? tm.region(qrow) : 0;
-        mx = -3.0e38f;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int key = nt * 16 + lg * 4 + j;
-            if (qrow_ok && key < WT && tm.region(key) != qreg) s[nt][j] += -100.0f;
-            mx = fmaxf(mx, s[nt][j]);
-          }
-      }
-      mx = lanegroup_allreduce(mx, fmax2);
-      float sum = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const float e = __expf(s[nt][j] - mx); s[nt][j] = e; sum += e; }
-      const float inv = __builtin_amdgcn_rcpf(lanegroup_allreduce(sum, fadd2));
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[nt][j] *= inv;
-    }
-#endif
+    const bool masked = tm.seam();
+    softmax_lane<false, true>(s, bias, 1.f, masked, masked ? seam_kdiff(tm, qrow, lg) : 0u);
     {
       float r = 0.f;
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) r += dp[nt][j] * s[nt][j];
-      r = lanegroup_allreduce(r, fadd2);
+      r = lanegroup_allreduce(r, FAdd2());
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -1111,10 +1066,8 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_kernel(const WinArgsT<
       bf16x4 pb, sb;
 #pragma unroll
       for (int j = 0; j < 4; ++j) { pb[j] = (__bf16)s[nt][j]; sb[j] = (__bf16)dp[nt][j]; dsf[nt >> 1][(nt & 1) * 4 + j] = sb[j]; }
-#ifndef SV_AT_PROBE_NOPS
       *reinterpret_cast<bf16x4*>(Ps + qrow * LDP_H + nt * 16 + lg * 4) = pb;     // [query][key] rows: four consecutive keys per lane
       *reinterpret_cast<bf16x4*>(Ss + qrow * LDP_H + nt * 16 + lg * 4) = sb;
-#endif
     }
     // ---- dQ = scale dS K for this wave's queries, from the registers: lane -> query lr, head channels 8 lg + 4 nt + j
     f32x4 aq[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
@@ -1164,25 +1117,7 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_kernel(const WinArgsT<
   }
   // ---- relative-position-bias gradient: registers -> LDS (once per workgroup) -> one atomic per table entry
   __syncthreads();
-  if (qrow_ok) {
-    const int qy = qrow / 7, qx = qrow - qy * 7;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = nt * 16 + lg * 4 + j;
-        if (key < WT) {
-          const int ky = key / 7, kx = key - ky * 7;
-          atomicAdd(dbt + (qy - ky + 6) * 13 + (qx - kx + 6), dsum[nt][j]);
-        }
-      }
-  }
-  __syncthreads();
-  float* dst = dt_ws ? dt_ws + (size_t)(chunk % ATTN_DT_SLOTS) * 169 * p.heads : p.dtable;
-  for (int i = tid; i < 169; i += 256) {
-    const float v = dbt[i];
-    if (v != 0.f) atomicAdd(dst + i * p.heads + head, v);
-  }
+  dbias_flush<false, 1>(&dsum, dbt, dt_ws ? dt_ws + (size_t)(chunk % ATTN_DT_SLOTS) * 169 * p.heads : p.dtable, head, p.heads, lane, wave);
 }
 // ---- fp8 (OCP e4m3) backward of the window-attention core (SV_MATH_FP8_FULL) ----------------------------------------------------------
 // The gradient of exactly the function win_attn_fwd_wg_fp8_kernel evaluates, every quantiser taken as the identity (straight-through).
@@ -1235,7 +1170,7 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_fp8_kernel(const WinAr
   __shared__ __attribute__((aligned(16))) uint8_t Qs[64 * LDQ_8], Ks[64 * LDQ_8], Vs[64 * LDQ_8], Ds[64 * LDQ_8];   // [token][d]
   __shared__ __attribute__((aligned(16))) uint8_t Pt[64 * LDT_8], St[64 * LDT_8];                                   // Pq, dSq [key][q]
   __shared__ float bt[176], dbt[176];
-  __shared__ float amax[2][4][4], amaxs[4];
+  __shared__ float amax[2][4][4], amaxs[4][1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, lg = lane >> 4;
   int chunk, head;
@@ -1244,25 +1179,14 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_fp8_kernel(const WinAr
   const int ld = 3 * p.C, colq = head * HD;
   for (int i = tid; i < 176; i += 256) { bt[i] = i < 169 ? p.table[i * p.heads + head] : 0.f; dbt[i] = 0.f; }
   __syncthreads();
-  float bias[4][4];                                // strip_bias's values; the table read is unconditional (clamped index) - branches here made
-#pragma unroll                                     // the register allocator spill whole 16-register tuples
-  for (int nt = 0; nt < 4; ++nt) {
-    const int key = nt * 16 + lr, ky = key / 7, kx = key - ky * 7;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int q = wave * 16 + lg * 4 + j, qy = q / 7, qx = q - qy * 7;
-      const bool ok = q < WT && key < WT;
-      const float b = bt[ok ? (qy - ky + 6) * 13 + (qx - kx + 6) : 0];
-      bias[nt][j] = key >= WT ? -1.0e30f : (ok ? b : 0.f);
-    }
-  }
-  f32x4 dsum[4];                                   // sum over this workgroup's windows of dS at this lane's (query, key) slots
+  float bias[4][4];
+  strip_bias(bias, bt, lane, wave);
+  f32x4 dsum[4];                                  // sum over this workgroup's windows of dS at this lane's (query, key) slots
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) dsum[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   // the next window's rows travel in registers while this window is contracted
   const int r0 = tid >> 3, ch = (tid & 7) * 4;
   float4 rq[2], rk[2], rv[2], rd[2];
-  const auto amax4 = [](float m, const float4& v) { return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)))); };
   const long long task0 = (long long)chunk * p.tasks_per_wave;
   if (task0 < p.ntasks) fetch_rows(p, task_map(task0, nW, nWx, p.H, p.W, p.shift), colq, r0, ch, rq, rk, rv, rd);
   for (int tt = 0; tt < p.tasks_per_wave; ++tt) {
@@ -1270,22 +1194,15 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_fp8_kernel(const WinAr
     if (task >= p.ntasks) break;                                         // uniform over the workgroup
     const TokMap tm = task_map(task, nW, nWx, p.H, p.W, p.shift);
     // ---- per-tile scales: q' = scale q first (the forward's order), then the workgroup maximum of |q'|, |k|, |v|, |dO|
-    float mq = 0.f, mk = 0.f, mv = 0.f, md = 0.f;
+    float sc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       rq[it].x *= p.scale; rq[it].y *= p.scale; rq[it].z *= p.scale; rq[it].w *= p.scale;
-      mq = amax4(mq, rq[it]); mk = amax4(mk, rk[it]); mv = amax4(mv, rv[it]); md = amax4(md, rd[it]);
+      sc[0] = amax4(sc[0], rq[it]); sc[1] = amax4(sc[1], rk[it]); sc[2] = amax4(sc[2], rv[it]); sc[3] = amax4(sc[3], rd[it]);
     }
-    mq = wave_max(mq); mk = wave_max(mk); mv = wave_max(mv); md = wave_max(md);
-    float (&am)[4][4] = amax[tt & 1];                                     // double-buffered: no barrier between two windows' maxima
-    if (lane == 0) { am[wave][0] = mq; am[wave][1] = mk; am[wave][2] = mv; am[wave][3] = md; }
-    __syncthreads();                                                     // maxima are in; the previous window's tiles are consumed
-    mq = fmaxf(fmaxf(am[0][0], am[1][0]), fmaxf(am[2][0], am[3][0]));
-    mk = fmaxf(fmaxf(am[0][1], am[1][1]), fmaxf(am[2][1], am[3][1]));
-    mv = fmaxf(fmaxf(am[0][2], am[1][2]), fmaxf(am[2][2], am[3][2]));
-    md = fmaxf(fmaxf(am[0][3], am[1][3]), fmaxf(am[2][3], am[3][3]));
-    const float sq = mq > 0.f ? 224.f / mq : 1.f, sk = mk > 0.f ? 224.f / mk : 1.f, sv = mv > 0.f ? 224.f / mv : 1.f;
-    const float so = md > 0.f ? 224.f / md : 1.f;
+    // double-buffered maxima: no barrier between two windows' maxima; the helper's barrier also ends the reads of the previous window's tiles
+    wg_amax_scale<4, false>(sc, amax[tt & 1], lane, wave);
+    const float sq = sc[0], sk = sc[1], sv = sc[2], so = sc[3];
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const int r = r0 + 32 * it;                                        // rows >= 49 hold zeros (registers were zeroed)
@@ -1310,7 +1227,7 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_fp8_kernel(const WinAr
         for (int j = 0; j < 4; ++j) { s[nt][j] *= un; dp[nt][j] *= unp; }
       }
     }
-    bias_mask_softmax_strip(s, bias, tm, lane, p.shift > 0 && (tm.wy == p.H / 7 - 1 || tm.wx == nWx - 1), wave);
+    bias_mask_softmax_strip(s, bias, tm, lane, tm.seam(), wave);
     float ms = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1331,11 +1248,9 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_fp8_kernel(const WinAr
     for (int nt = 0; nt < 4; ++nt)     // Pq as [key][query]: the four queries of this lane are consecutive
       *reinterpret_cast<uint32_t*>(Pt + (nt * 16 + lr) * LDT_8 + wave * 16 + lg * 4) =
           pack4_fp8(s[nt][0] * 256.f, s[nt][1] * 256.f, s[nt][2] * 256.f, s[nt][3] * 256.f);
-    ms = wave_max(ms);
-    if (lane == 0) amaxs[wave] = ms;
-    __syncthreads();
-    ms = fmaxf(fmaxf(amaxs[0], amaxs[1]), fmaxf(amaxs[2], amaxs[3]));
-    const float ss = ms > 0.f ? 224.f / ms : 1.f;
+    float ssc[1] = {ms};
+    wg_amax_scale<1, false>(ssc, amaxs, lane, wave);   // amaxs was last read before this window's two barriers
+    const float ss = ssc[0];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
       *reinterpret_cast<uint32_t*>(St + (nt * 16 + lr) * LDT_8 + wave * 16 + lg * 4) =
@@ -1374,21 +1289,7 @@ __global__ __launch_bounds__(256, 3) void win_attn_bwd_wg_fp8_kernel(const WinAr
   }
   // ---- relative-position-bias gradient: registers -> LDS (once per workgroup) -> slot image or table (as win_attn_bwd_wg_kernel)
   __syncthreads();
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    const int key = nt * 16 + lr, ky = key / 7, kx = key - ky * 7;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int q = wave * 16 + lg * 4 + j, qy = q / 7, qx = q - qy * 7;
-      if (q < WT && key < WT) atomicAdd(dbt + (qy - ky + 6) * 13 + (qx - kx + 6), dsum[nt][j]);
-    }
-  }
-  __syncthreads();
-  float* dst = dt_ws ? dt_ws + (size_t)(chunk % ATTN_DT_SLOTS) * 169 * p.heads : p.dtable;
-  for (int i = tid; i < 169; i += 256) {
-    const float v = dbt[i];
-    if (v != 0.f) atomicAdd(dst + i * p.heads + head, v);
-  }
+  dbias_flush<true, 1>(&dsum, dbt, dt_ws ? dt_ws + (size_t)(chunk % ATTN_DT_SLOTS) * 169 * p.heads : p.dtable, head, p.heads, lane, wave);
 }
 
 __global__ __launch_bounds__(256) void attn_dtable_fold_kernel(const float* __restrict__ ws, float* __restrict__ dtable, int n) {
@@ -1463,25 +1364,13 @@ __global__ __launch_bounds__(512, 1) void swin_attn_block_fwd_kernel(const Block
   const bool qok = q < WT;
   // relative-position bias of this lane's 16 (query, key) slots per head: the same for every window
   float bias[FB_HEADS][4][4];
-  {
-    const int qy = q / 7, qx = q - qy * 7;
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = nt * 16 + lg * 4 + j, ky = key / 7, kx = key - ky * 7;
-#pragma unroll
-        for (int h = 0; h < FB_HEADS; ++h)
-          bias[h][nt][j] = key >= WT ? -1.0e30f : (qok ? bt[h * 176 + (qy - ky + 6) * 13 + (qx - kx + 6)] : 0.f);
-      }
-  }
+  for (int h = 0; h < FB_HEADS; ++h) lane_bias(bias[h], bt + h * 176, q, lg);
   __bf16* T = Tb + grp * 64 * FB_LDT;
   const int nWx = p.W / 7, nW = (p.H / 7) * nWx;
   const long long task0 = ((long long)blockIdx.x * 2 + grp) * p.tasks_per_group;
   const float qscale = p.scale * ATTN_LOG2E;
   const bf16x8 zero8 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-  const auto fmax2 = [](float a, float b) { return fmaxf(a, b); };
-  const auto fadd2 = [](float a, float b) { return a + b; };
 
   // the windows of a group are consecutive: (image, window row, window column) advance by increments, one division at the start
   TokMap tnext = task_map(task0 < p.ntasks ? task0 : 0, nW, nWx, p.H, p.W, p.shift);
@@ -1518,13 +1407,13 @@ __global__ __launch_bounds__(512, 1) void swin_attn_block_fwd_kernel(const Block
       for (int ks = 0; ks < 3; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { xv[ks][e] = (float)xr[ks][e]; s += xv[ks][e]; }
-      const float mean = lanegroup_allreduce(s, fadd2) * (1.f / FB_C);
+      const float mean = lanegroup_allreduce(s, FAdd2()) * (1.f / FB_C);
       float v2 = 0.f;
 #pragma unroll
       for (int ks = 0; ks < 3; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float a = xv[ks][e] - mean; v2 += a * a; }
-      const float rstd = rsqrtf(lanegroup_allreduce(v2, fadd2) * (1.f / FB_C) + p.eps);
+      const float rstd = rsqrtf(lanegroup_allreduce(v2, FAdd2()) * (1.f / FB_C) + p.eps);
 #pragma unroll
       for (int ks = 0; ks < 3; ++ks) {
         const float4 g0 = *reinterpret_cast<const float4*>(lng + ks * 32 + lg * 8), g1 = *reinterpret_cast<const float4*>(lng + ks * 32 + lg * 8 + 4);
@@ -1564,18 +1453,8 @@ __global__ __launch_bounds__(512, 1) void swin_attn_block_fwd_kernel(const Block
     }
     __syncthreads();                                                     // all key / value rows of both windows are in LDS
     // ---- attention, one head at a time; lane -> query lr, keys nt*16 + lg*4 + j
-    const bool masked = p.shift > 0 && (tm.wy == p.H / 7 - 1 || tm.wx == nWx - 1);
-    unsigned kdiff = 0;                                                  // bit (nt*4 + j): key in another region than the query
-    if (masked) {
-      const int qreg = qok ? tm.region(q) : 0;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int key = nt * 16 + lg * 4 + j;
-          if (qok && key < WT && tm.region(key) != qreg) kdiff |= 1u << (nt * 4 + j);
-        }
-    }
+    const bool masked = tm.seam();                                       // uniform over the window
+    const unsigned kdiff = masked ? seam_kdiff(tm, q, lg) : 0u;
 #pragma unroll
     for (int h = 0; h < FB_HEADS; ++h) {
       f32x4 s[4];
@@ -1587,32 +1466,8 @@ __global__ __launch_bounds__(512, 1) void swin_attn_block_fwd_kernel(const Block
           s[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         }
       }
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float v = s[nt][j] + bias[h][nt][j];      // key padding: bias = -1e30 and the padded K rows are finite (LayerNorm of a zero row = beta)
-          s[nt][j] = v;
-          mx = fmaxf(mx, v);
-        }
-      if (masked) {                                        // uniform over the window: only the last window row / column of a shifted block
-        mx = -3.0e38f;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (kdiff & (1u << (nt * 4 + j))) s[nt][j] += -100.0f * ATTN_LOG2E;
-            mx = fmaxf(mx, s[nt][j]);
-          }
-      }
-      mx = lanegroup_allreduce(mx, fmax2);
-      float sum = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const float e = __builtin_amdgcn_exp2f(s[nt][j] - mx); s[nt][j] = e; sum += e; }
-      const float inv = __builtin_amdgcn_rcpf(lanegroup_allreduce(sum, fadd2));
+      // key padding: bias = -1e30 and the padded K rows are finite (LayerNorm of a zero row = beta)
+      const float inv = softmax_lane<true, false>(s, bias[h], 1.f, masked, kdiff);
       bf16x8 pf[2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -1725,20 +1580,8 @@ __global__ __launch_bounds__(256, 1) void swin_attn_block_bwd_kernel(const Block
   const int q = wave * 16 + lr;                      // the token of this lane wherever rows are owned (queries of P2, keys of its second half)
   const bool qok = q < WT;
   float bias[FB_HEADS][4][4];
-  {
-    const int qy = q / 7, qx = q - qy * 7;
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = nt * 16 + lg * 4 + j, ky = key / 7, kx = key - ky * 7;
-#pragma unroll
-        for (int h = 0; h < FB_HEADS; ++h)
-          bias[h][nt][j] = key >= WT ? -1.0e30f : (qok ? bt[h * 176 + (qy - ky + 6) * 13 + (qx - kx + 6)] * ATTN_LOG2E : 0.f);   // exp2 domain
-      }
-  }
-  const auto fmax2 = [](float a, float b) { return fmaxf(a, b); };
-  const auto fadd2 = [](float a, float b) { return a + b; };
+  for (int h = 0; h < FB_HEADS; ++h) lane_bias(bias[h], bt + h * 176, q, lg, ATTN_LOG2E);   // exp2 domain
   const bf16x8 zero8 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
   f32x4 dsum[FB_HEADS][4];                           // bias-table gradient at this lane's (query, key) slots, over all windows
 #pragma unroll
@@ -1837,18 +1680,8 @@ __global__ __launch_bounds__(256, 1) void swin_attn_block_bwd_kernel(const Block
       }
     }
     __syncthreads();                                 // every row of T and of D (= datt) is in LDS
-    const bool masked = p.shift > 0 && (tm.wy == p.H / 7 - 1 || tm.wx == nWx - 1);
-    unsigned kdiff = 0;                              // bit (nt * 4 + j): key in another region of the rolled map than the query
-    if (masked) {
-      const int qreg = qok ? tm.region(q) : 0;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int key = nt * 16 + lg * 4 + j;
-          if (qok && key < WT && tm.region(key) != qreg) kdiff |= 1u << (nt * 4 + j);
-        }
-    }
+    const bool masked = tm.seam();                   // uniform over the workgroup
+    const unsigned kdiff = masked ? seam_kdiff(tm, q, lg) : 0u;
     // ---- P2: attention backward, one head at a time (win_attn_bwd_wg_kernel's body on the tile columns of the head)
 #pragma unroll
     for (int h = 0; h < FB_HEADS; ++h) {
@@ -1870,38 +1703,13 @@ __global__ __launch_bounds__(256, 1) void swin_attn_block_bwd_kernel(const Block
       {
         // scores in the exp2 domain: log2 e rides on the bias (above) and on the raw product here (Q carries the plain softmax scale, as the
         // dK product needs it)
-        float mx = -3.0e38f;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float v = __builtin_fmaf(s[nt][j], ATTN_LOG2E, bias[h][nt][j]);
-            s[nt][j] = v;
-            mx = fmaxf(mx, v);
-          }
-        if (masked) {                                // uniform over the workgroup: only windows on the rolled seam
-          mx = -3.0e38f;
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if (kdiff & (1u << (nt * 4 + j))) s[nt][j] += -100.0f * ATTN_LOG2E;
-              mx = fmaxf(mx, s[nt][j]);
-            }
-        }
-        mx = lanegroup_allreduce(mx, fmax2);
-        float sum = 0.f;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { const float e = __builtin_amdgcn_exp2f(s[nt][j] - mx); s[nt][j] = e; sum += e; }
-        const float inv = __builtin_amdgcn_rcpf(lanegroup_allreduce(sum, fadd2));
+        softmax_lane<true, true>(s, bias[h], ATTN_LOG2E, masked, kdiff);
         float r = 0.f;
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { s[nt][j] *= inv; r += dp[nt][j] * s[nt][j]; }
-        r = lanegroup_allreduce(r, fadd2);
+          for (int j = 0; j < 4; ++j) r += dp[nt][j] * s[nt][j];
+        r = lanegroup_allreduce(r, FAdd2());
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -1991,11 +1799,17 @@ __global__ __launch_bounds__(256, 1) void swin_attn_block_bwd_kernel(const Block
           dbet[ck][e] += d; dgam[ck][e] += d * xv;
           const float g = d * gm[e];
           dl[ck][e] = g; xh[ck][e] = xv;
-          s1 += g; s2 += g * xv;
+          s1 += g;
+          // g xhat is rounded before it is summed: left to the compiler, whether the product is fused into the sum follows from how the loop
+          // happens to be vectorised, and dx changes in its last bit with unrelated edits of this kernel
+          {
+#pragma clang fp contract(off)
+            s2 += g * xv;
+          }
         }
       }
-      s1 = lanegroup_allreduce(s1, fadd2) * (1.f / FB_C);
-      s2 = lanegroup_allreduce(s2, fadd2) * (1.f / FB_C);
+      s1 = lanegroup_allreduce(s1, FAdd2()) * (1.f / FB_C);
+      s2 = lanegroup_allreduce(s2, FAdd2()) * (1.f / FB_C);
       if (valid) {
 #pragma unroll
         for (int ck = 0; ck < 3; ++ck) {
@@ -2016,40 +1830,25 @@ __global__ __launch_bounds__(256, 1) void swin_attn_block_bwd_kernel(const Block
       const float a = group16_sum(dgam[ck][e]), b = group16_sum(dbet[ck][e]);      // the 16 tokens of a lane group
       if (lr == 0) { atomicAdd(red + ck * 32 + lg * 8 + e, a); atomicAdd(red + 96 + ck * 32 + lg * 8 + e, b); }
     }
-  if (qok) {
-    const int qy = q / 7, qx = q - qy * 7;
-#pragma unroll
-    for (int h = 0; h < FB_HEADS; ++h)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int key = nt * 16 + lg * 4 + j;
-          if (key < WT) {
-            const int ky = key / 7, kx = key - ky * 7;
-            atomicAdd(dbt + h * 176 + (qy - ky + 6) * 13 + (qx - kx + 6), dsum[h][nt][j]);
-          }
-        }
-  }
-  __syncthreads();
-  if (tid < 96) { atomicAdd(p.dgamma + tid, red[tid]); atomicAdd(p.dbeta + tid, red[96 + tid]); }
-  float* dst = p.dt_ws + (size_t)(blockIdx.x % ATTN_DT_SLOTS) * 169 * FB_HEADS;
-  for (int i = tid; i < 3 * 169; i += 256) {
-    const int h = i / 169, e = i - h * 169;
-    const float v = dbt[h * 176 + e];
-    if (v != 0.f) atomicAdd(dst + e * FB_HEADS + h, v);
-  }
+  dbias_flush<false, FB_HEADS>(dsum, dbt, p.dt_ws + (size_t)(blockIdx.x % ATTN_DT_SLOTS) * 169 * FB_HEADS, 0, FB_HEADS, lane, wave);
+  if (tid < 96) { atomicAdd(p.dgamma + tid, red[tid]); atomicAdd(p.dbeta + tid, red[96 + tid]); }   // behind the barrier of the flush
 }
 
 }  // namespace sv
 
 using namespace sv;
 
+// the window geometry every entry point of the window kernels requires; `who` names the entry point in the message
+static int win_geom_check(const char* who, int H, int W, int shift) {
+  SV_REQUIRE(H % 7 == 0 && W % 7 == 0 && H >= 7 && W >= 7, "%s: map %dx%d is not a multiple of the 7x7 window", who, H, W);
+  SV_REQUIRE(shift >= 0 && shift < 7 && (shift == 0 || (H > 7 && W > 7)), "%s: bad shift %d for map %dx%d", who, shift, H, W);
+  return SV_OK;
+}
+
 static int win_check(const void* qkv, const float* table, int I, int H, int W, int C, int heads, int shift, int math, int act_dtype) {
   SV_REQUIRE(qkv && table && I > 0, "window_attention: null/empty argument");
-  SV_REQUIRE(H % 7 == 0 && W % 7 == 0 && H >= 7 && W >= 7, "window_attention: map %dx%d is not a multiple of the 7x7 window", H, W);
+  if (int rc = win_geom_check("window_attention", H, W, shift)) return rc;
   SV_REQUIRE(C == heads * HD, "window_attention: C (%d) must equal heads (%d) * 32", C, heads);
-  SV_REQUIRE(shift >= 0 && shift < 7 && (shift == 0 || (H > 7 && W > 7)), "window_attention: bad shift %d for map %dx%d", shift, H, W);
   SV_REQUIRE(((uintptr_t)qkv & 15) == 0, "window_attention: qkv must be 16-byte aligned");
   SV_REQUIRE_ACT(act_dtype);
   SV_REQUIRE(act_dtype == SV_F32 || math == SV_MATH_BF16 || math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL,
@@ -2057,55 +1856,57 @@ static int win_check(const void* qkv, const float* table, int I, int H, int W, i
   return SV_OK;
 }
 
+// the arguments of sv_window_attention_fwd / _bwd, as they arrive
+struct WinCall {
+  const void* qkv; const float* table; void* out; const void* dout; void* dqkv; float* dtable;
+  int I, H, W, C, heads, shift;
+  int ntasks() const { return I * (H / 7) * (W / 7); }
+};
 template <typename AT>
-static WinArgsT<AT> win_args(const void* qkv, const float* table, void* out, const void* dout, void* dqkv, float* dtable, int I, int H, int W,
-                             int C, int heads, int shift) {
+static WinArgsT<AT> win_args(const WinCall& c, int tasks_per_wave) {
   WinArgsT<AT> a{};
-  a.qkv = static_cast<const AT*>(qkv); a.table = table; a.out = static_cast<AT*>(out);
-  a.dout = static_cast<const AT*>(dout); a.dqkv = static_cast<AT*>(dqkv); a.dtable = dtable;
-  a.I = I; a.H = H; a.W = W; a.C = C; a.heads = heads; a.shift = shift;
+  a.qkv = static_cast<const AT*>(c.qkv); a.table = c.table; a.out = static_cast<AT*>(c.out);
+  a.dout = static_cast<const AT*>(c.dout); a.dqkv = static_cast<AT*>(c.dqkv); a.dtable = c.dtable;
+  a.I = c.I; a.H = c.H; a.W = c.W; a.C = c.C; a.heads = c.heads; a.shift = c.shift;
   a.scale = 1.0f / sqrtf((float)HD);
-  a.ntasks = I * (H / 7) * (W / 7);
+  a.ntasks = c.ntasks();
+  a.tasks_per_wave = tasks_per_wave;
   return a;
+}
+
+static void launch_dtable_fold(float* workspace, float* dtable, int heads, hipStream_t s) {
+  hipLaunchKernelGGL(attn_dtable_fold_kernel, dim3(cdiv(169 * heads, 256)), dim3(256), 0, s, workspace, dtable, 169 * heads);
+}
+
+// The four workgroup-per-window kernels: a workgroup walks tpb windows of one head.
+//  * forward: >= ~2048 short workgroups (the forward task is brief, oversubscribing the CUs balances better than one exact wave - measured);
+//  * backward: one resident wave of workgroups, 3 per CU; the bias-table gradient goes to the slot images of `workspace` (folded into
+//    dtable by a second launch) or, without a workspace, straight to dtable.
+static void launch_win_wg(bool bwd, bool fp8, int act_dtype, const WinCall& c, float* workspace, hipStream_t s) {
+  const int ntasks = c.ntasks();
+  int tpb;
+  if (bwd) tpb = wg_tasks_per_block(ntasks, c.heads, 3);
+  else { tpb = (int)((long long)ntasks * c.heads / 2048); if (tpb < 1) tpb = 1; if (tpb > 8) tpb = 8; }
+  const dim3 grid(wg_grid(cdiv(ntasks, tpb), c.heads));
+  SV_DISPATCH_ACT(act_dtype,
+    const WinArgsT<AT> a = win_args<AT>(c, tpb);
+    if (!bwd && !fp8) hipLaunchKernelGGL(win_attn_fwd_wg_kernel<AT>, grid, dim3(256), 0, s, a);
+    else if (!bwd) hipLaunchKernelGGL(win_attn_fwd_wg_fp8_kernel<AT>, grid, dim3(256), 0, s, a);
+    else if (!fp8) hipLaunchKernelGGL(win_attn_bwd_wg_kernel<AT>, grid, dim3(256), 0, s, a, workspace);
+    else hipLaunchKernelGGL(win_attn_bwd_wg_fp8_kernel<AT>, grid, dim3(256), 0, s, a, workspace););
+  if (bwd && workspace) launch_dtable_fold(workspace, c.dtable, c.heads, s);
 }
 
 extern "C" int sv_window_attention_fwd(const void* qkv, const float* table, void* out, int I, int H, int W, int C, int heads,
                                        int shift, int math, int act_dtype, void* stream) {
   if (int rc = win_check(qkv, table, I, H, W, C, heads, shift, math, act_dtype)) return rc;
   SV_REQUIRE(out, "window_attention_fwd: null out");
-  const int ntasks = I * (H / 7) * (W / 7);
+  const WinCall c{qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift};
   hipStream_t s = (hipStream_t)stream;
-  if (math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL) {   // e4m3 operands for QK^T and PV (the backward of SV_MATH_FP8 is bf16)
-    int tpb = (int)((long long)ntasks * heads / 2048); if (tpb < 1) tpb = 1; if (tpb > 8) tpb = 8;
-    dim3 grid(wg_grid(cdiv(ntasks, tpb), heads));
-    if (act_dtype == SV_BF16) {
-      WinArgsT<__bf16> a = win_args<__bf16>(qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_fwd_wg_fp8_kernel<__bf16>, grid, dim3(256), 0, s, a);
-    } else {
-      WinArgs a = win_args<float>(qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_fwd_wg_fp8_kernel<float>, grid, dim3(256), 0, s, a);
-    }
-    return check_launch("sv_window_attention_fwd");
-  }
-  if (math == SV_MATH_BF16) {   // workgroup per window; a workgroup walks tpb windows of one head (>= ~2048 short workgroups:
-    // the forward task is brief, oversubscribing the CUs balances better than one exact wave - measured)
-    int tpb = (int)((long long)ntasks * heads / 2048); if (tpb < 1) tpb = 1; if (tpb > 8) tpb = 8;
-    dim3 grid(wg_grid(cdiv(ntasks, tpb), heads));
-    if (act_dtype == SV_BF16) {
-      WinArgsT<__bf16> a = win_args<__bf16>(qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_fwd_wg_kernel<__bf16>, grid, dim3(256), 0, s, a);
-    } else {
-      WinArgs a = win_args<float>(qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_fwd_wg_kernel<float>, grid, dim3(256), 0, s, a);
-    }
-  } else {
-    dim3 grid(cdiv(ntasks, 4), heads);
-    hipLaunchKernelGGL((win_attn_fwd_kernel<false, float>), grid, dim3(256), 0, s, win_args<float>(qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift));
-  }
+  const bool fp8 = math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL;   // e4m3 operands for QK^T and PV (the backward of SV_MATH_FP8 is bf16)
+  if (fp8 || math == SV_MATH_BF16) launch_win_wg(false, fp8, act_dtype, c, nullptr, s);
+  else   // exact-fp32 MFMA: wave per window
+    hipLaunchKernelGGL(win_attn_fwd_kernel, dim3(cdiv(c.ntasks(), 4), heads), dim3(256), 0, s, win_args<float>(c, 1));
   return check_launch("sv_window_attention_fwd");
 }
 
@@ -2115,42 +1916,16 @@ extern "C" int sv_window_attention_bwd(const void* qkv, const float* table, cons
                                        int I, int H, int W, int C, int heads, int shift, int math, int act_dtype, void* stream) {
   if (int rc = win_check(qkv, table, I, H, W, C, heads, shift, math, act_dtype)) return rc;
   SV_REQUIRE(dout && dqkv && dtable && ((uintptr_t)dout & 15) == 0, "window_attention_bwd: null/unaligned argument");
-  const int ntasks = I * (H / 7) * (W / 7);
+  const WinCall c{qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift};
   hipStream_t s = (hipStream_t)stream;
-  if (math == SV_MATH_FP8_FULL) {   // e4m3 operands for all five contractions: the gradient of the SV_MATH_FP8 forward
-    const int tpb = wg_tasks_per_block(ntasks, heads, 3);
-    dim3 grid(wg_grid(cdiv(ntasks, tpb), heads));
-    if (act_dtype == SV_BF16) {
-      WinArgsT<__bf16> a = win_args<__bf16>(qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_bwd_wg_fp8_kernel<__bf16>, grid, dim3(256), 0, s, a, workspace);
-    } else {
-      WinArgs a = win_args<float>(qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_bwd_wg_fp8_kernel<float>, grid, dim3(256), 0, s, a, workspace);
-    }
-    if (workspace) hipLaunchKernelGGL(attn_dtable_fold_kernel, dim3(cdiv(169 * heads, 256)), dim3(256), 0, s, workspace, dtable, 169 * heads);
-  } else if (math == SV_MATH_BF16 || math == SV_MATH_FP8) {   // workgroup per window, tpb windows of one head per workgroup
-    const int tpb = wg_tasks_per_block(ntasks, heads, 3);
-    dim3 grid(wg_grid(cdiv(ntasks, tpb), heads));
-    if (act_dtype == SV_BF16) {
-      WinArgsT<__bf16> a = win_args<__bf16>(qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_bwd_wg_kernel<__bf16>, grid, dim3(256), 0, s, a, workspace);
-    } else {
-      WinArgs a = win_args<float>(qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift);
-      a.tasks_per_wave = tpb;
-      hipLaunchKernelGGL(win_attn_bwd_wg_kernel<float>, grid, dim3(256), 0, s, a, workspace);
-    }
-    if (workspace) hipLaunchKernelGGL(attn_dtable_fold_kernel, dim3(cdiv(169 * heads, 256)), dim3(256), 0, s, workspace, dtable, 169 * heads);
+  if (math == SV_MATH_BF16 || math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL) {
+    // SV_MATH_FP8_FULL: e4m3 operands for all five contractions, the gradient of the SV_MATH_FP8 forward; SV_MATH_FP8: the bf16 backward
+    launch_win_wg(true, math == SV_MATH_FP8_FULL, act_dtype, c, workspace, s);
   } else {
     // exact-fp32 MFMA: wave per window, several windows per wave (same head) so the bias gradient is reduced on chip
     int tpw = 1;
-    while (tpw < 8 && (long long)ntasks * heads / (tpw * 2) > 2048) tpw *= 2;
-    dim3 grid(cdiv(ntasks, 2 * tpw), heads);
-    WinArgs a = win_args<float>(qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift);
-    a.tasks_per_wave = tpw;
-    hipLaunchKernelGGL(win_attn_bwd_kernel, grid, dim3(128), 0, s, a);
+    while (tpw < 8 && (long long)c.ntasks() * heads / (tpw * 2) > 2048) tpw *= 2;
+    hipLaunchKernelGGL(win_attn_bwd_kernel, dim3(cdiv(c.ntasks(), 2 * tpw), heads), dim3(128), 0, s, win_args<float>(c, tpw));
   }
   return check_launch("sv_window_attention_bwd");
 }
@@ -2198,8 +1973,7 @@ extern "C" int sv_swin_attn_block_fwd(const void* x, const float* ln_g, const fl
   SV_REQUIRE(x && ln_g && ln_b && wqkv && bqkv && table && wproj && bproj && x1 && I > 0, "swin_attn_block_fwd: null/empty argument");
   SV_REQUIRE(C == FB_C && heads == FB_HEADS && act_dtype == SV_BF16, "swin_attn_block_fwd: built for C = 96, 3 heads, bf16 token rows (got C=%d heads=%d dtype=%d)",
              C, heads, act_dtype);
-  SV_REQUIRE(H % 7 == 0 && W % 7 == 0 && H >= 7 && W >= 7, "swin_attn_block_fwd: map %dx%d is not a multiple of the 7x7 window", H, W);
-  SV_REQUIRE(shift >= 0 && shift < 7 && (shift == 0 || (H > 7 && W > 7)), "swin_attn_block_fwd: bad shift %d for map %dx%d", shift, H, W);
+  if (int rc = win_geom_check("swin_attn_block_fwd", H, W, shift)) return rc;
   const bool side = ln1 || mean || rstd || qkv || att;
   SV_REQUIRE(!side || (ln1 && mean && rstd && qkv && att), "swin_attn_block_fwd: the side outputs (ln1, mean, rstd, qkv, att) come all or none");
   SV_REQUIRE((((uintptr_t)x | (uintptr_t)x1 | (uintptr_t)ln1 | (uintptr_t)qkv | (uintptr_t)att | (uintptr_t)wqkv | (uintptr_t)wproj) & 15) == 0,
@@ -2226,8 +2000,7 @@ extern "C" int sv_swin_attn_block_bwd(const void* dx1, const void* qkv, const vo
              "swin_attn_block_bwd: null/empty argument");
   SV_REQUIRE(C == FB_C && heads == FB_HEADS && act_dtype == SV_BF16, "swin_attn_block_bwd: built for C = 96, 3 heads, bf16 token rows (got C=%d heads=%d dtype=%d)",
              C, heads, act_dtype);
-  SV_REQUIRE(H % 7 == 0 && W % 7 == 0 && H >= 7 && W >= 7, "swin_attn_block_bwd: map %dx%d is not a multiple of the 7x7 window", H, W);
-  SV_REQUIRE(shift >= 0 && shift < 7 && (shift == 0 || (H > 7 && W > 7)), "swin_attn_block_bwd: bad shift %d for map %dx%d", shift, H, W);
+  if (int rc = win_geom_check("swin_attn_block_bwd", H, W, shift)) return rc;
   SV_REQUIRE((((uintptr_t)dx1 | (uintptr_t)qkv | (uintptr_t)x | (uintptr_t)dqkv | (uintptr_t)dx | (uintptr_t)dbr) & 15) == 0,
              "swin_attn_block_bwd: tensors must be 16-byte aligned");
   BlockBwdArgs a{};
@@ -2240,6 +2013,6 @@ extern "C" int sv_swin_attn_block_bwd(const void* dx1, const void* qkv, const vo
   a.tasks_per_group = cdiv(a.ntasks, 256);                  // one workgroup per CU, every workgroup the same share of consecutive windows
   const int nblocks = cdiv(a.ntasks, a.tasks_per_group);
   hipLaunchKernelGGL(swin_attn_block_bwd_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(attn_dtable_fold_kernel, dim3(cdiv(169 * heads, 256)), dim3(256), 0, (hipStream_t)stream, workspace, dtable, 169 * heads);
+  launch_dtable_fold(workspace, dtable, heads, (hipStream_t)stream);
   return check_launch("sv_swin_attn_block_bwd");
 }
