@@ -115,6 +115,22 @@ size_t sv_conv_wgrad_workspace_floats(const sv_geom* g);
 int sv_conv_wgrad(const void* anchor, int lda, const void* gathered, float* dw, const sv_geom* g, int cg_valid,
                   float* workspace, float* dbias /* optional: dbias[ca] += sum_r anchor[r, ca] */, int math, int act_dtype,
                   void* stream);
+/* fp8 forward of the Swin Linear layers (timm Linear behind models/swin_transformer.py:78: qkv, proj, fc1, fc2, patch-merge reduction) on the
+ * block-scaled K = 128 MFMA.  Recipe for y = x W^T, x [M, K], W [N, K]: row scales s = 224 / max|row| in fp32 (all-zero row: 1; clamped to
+ * at most 2^60), operands e4m3_rne(row * s) (OCP e4m3fn) in rows of Kp = roundup(K, 128) bytes with zero padding, fp32 accumulation with both
+ * hardware block scales 1.0, val = acc / (sx[m] * sw[n]) in fp32, then the sv_epilogue arithmetic on val.
+ * The row quantiser (timm Linear behind models/swin_transformer.py:78, operand preparation): src [rows, K] with row stride ld (elements of src_dtype,
+ * SV_F32 or SV_BF16) -> dst_q [rows, Kp] bytes (16-byte aligned, Kp % 128 == 0, bytes K .. Kp-1 zero) and scales [rows]. */
+int sv_quant_rows_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, float* scales, void* stream);
+/* out[m, n] = epilogue(sum_k xq[m, k] wq[n, k] / (sx[m] sw[n])) (timm Linear behind models/swin_transformer.py:78).  xq [M, Kp], wq [N, Kp] from the row
+ * quantiser with Kp = roundup(K, 128); out, e->residual and e->pre_act hold act_dtype elements.  Epilogue forms served: bias, act = SV_ACT_NONE or
+ * SV_ACT_GELU with pre_act, residual / ldr with row_scale / rows_per_scale, ldc.  stats, act_grad_src, other activations and col_off != 0 are
+ * refused with SV_ERR_INVALID.  GELU is the erf form with SV_F32 storage and the engine's fast form with SV_BF16 storage. */
+int sv_linear_fp8(const void* xq, const float* sx, const void* wq, const float* sw, void* out, int M, int K, int N, const sv_epilogue* e,
+                  int act_dtype, void* stream);
+/* 1 when the fp8 linear serves this call (timm Linear behind models/swin_transformer.py:78): math == SV_MATH_BF16 and an epilogue form listed above; else 0 */
+int sv_linear_fp8_supported(int K, int N, const sv_epilogue* e, int math, int act_dtype);
+long long sv_linear_fp8_launches(void); /* fp8 linear launches so far in this process (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise) */
 /* LDS-halo MFMA stencils for 3x3x3 / stride 1 / pad 1 convolutions with <= 16 output channels per tile (merger.py:20-54),
  * bf16 operands.  x: channels-last positions with row stride ldx, cin_load (multiple of 4) elements read per position,
  * zero-extended to 16*groups channels; w_bf16: [16*ntiles16][27][16*groups] bf16 (forward: rows = output channels;

@@ -1,5 +1,6 @@
 """Whole optimisation step (harness.train_step: forward + backward + clip + solver) with the flat-buffer solvers and with
-the stock torch.optim sequence, next to forward+backward alone.  python scripts/bench_train_step.py [--batch 32]"""
+the stock torch.optim sequence, next to forward+backward alone.  python scripts/bench_train_step.py [--batch 32]
+--fp8-linear: forward+backward alone with the fp8 Swin linears (set_linear_fp8) off and on, same process."""
 import argparse
 import os
 import sys
@@ -16,6 +17,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--views", type=int, default=8)
 ap.add_argument("--steps", type=int, default=6)
+ap.add_argument("--fp8-linear", action="store_true", help="time forward+backward only, with set_linear_fp8 off and on")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = S.default_cfg()
@@ -36,15 +38,16 @@ def timed(fn, n):
     return (time.perf_counter() - t) / n * 1e3
 
 
-for fused in (True, False, None):
+for fused in ((None, "fp8") if a.fp8_linear else (True, False, None)):
     torch.manual_seed(0)
     nets = [m(cfg).to(dev).train() for m in (Encoder, Decoder, Merger, Refiner)]
-    if fused is None:
+    S.set_linear_fp8(fused == "fp8")
+    if fused is None or fused == "fp8":
         def step():
             for n in nets:
                 n.zero_grad(set_to_none=True)
             harness.forward_losses(nets, cfg, x, gt)[0].backward()
-        name = "forward+backward only"
+        name = "forward+backward only" + (", fp8 Swin linears" if fused == "fp8" else "")
     else:
         solvers, _ = harness.make_solvers(nets, cfg, fused=fused)
         def step():

@@ -1,0 +1,310 @@
+// fp8 (OCP e4m3fn) forward of the Swin linear layers on the block-scaled K = 128 MFMA (v_mfma_scale_f32_16x16x128_f8f6f4).
+//
+// Recipe, for y = x W^T with x [M, K] (stored activations, bf16 or fp32) and W [N, K] (fp32 parameter):
+//   row scales   sx[m] = 224 / max_k |x[m, k]|, sw[n] = 224 / max_k |W[n, k]|, formed in fp32 (IEEE division).  An all-zero row gets scale 1 (the
+//                constant and the zero rule of the fp8 window attention, attn.hip).  CLAMP: a scale is at most 2^60, so the product
+//                sx[m] sw[n] of the epilogue is finite for every input; a row whose maximum is below 224 / 2^60 = 1.9e-16 quantises to zeros.
+//   quantisers   xq = e4m3_rne(x sx), wq = e4m3_rne(W sw), the product formed in fp32 (v_cvt_pk_fp8_f32: round to nearest even).
+//   operands     rows of Kp = roundup(K, 128) bytes, the padding bytes zero in BOTH operands: the contraction has no K tail.
+//   contraction  acc = sum_k xq wq in fp32 on the 16 x 16 x 128 scaled MFMA, both formats e4m3 (cbsz = blgp = 0), both hardware block scales
+//                1.0 (E8M0 exponent 127 in every byte, op-sel 0); val = acc / (sx[m] sw[n]) in fp32 in the epilogue.
+//   epilogue     sv_epilogue semantics on val, in the engine's order (igemm.hip epilogue_rows): + bias, pre_act copy, activation, residual +
+//                row_scale * val, store rounded to the storage type.  The arithmetic is common.h's (apply_act_t, stf / stnf): GELU is the erf form
+//                with fp32 storage and the fast form with bf16 storage (its error is 1/30 of the bf16 rounding unit of the stored value).
+//                Served: no activation or GELU, bias, pre_act, residual / ldr, row_scale / rows_per_scale, ldc.  Refused with a status code:
+//                stats, act_grad_src, other activations, col_off != 0.
+//
+// Kernels
+//   quant_rows_kernel   one wave per row: amax by a DPP / permlane reduction (wave_max), then Kp bytes and one fp32 scale.  The row is read twice
+//                       (the second time from cache); activations (bf16 / fp32) and weights (fp32) take the same kernel.
+//   linear_fp8_kernel   128 x 128 output tile per 256-thread workgroup, 4 waves as 2 x 2, a wave owns 64 x 64 = 4 x 4 MFMA blocks (64 accumulator
+//                       registers).  One k-step = 128 bytes of every row = ONE MFMA deep: 16 KB per operand tile, staged through registers
+//                       (16-byte global loads of the next step are in flight while the current step's 16 MFMAs per wave run) into two LDS
+//                       buffers, one barrier per step.  LDS rows are 128 bytes = eight 16-byte pieces; a plain image would put every row
+//                       on the same banks, so piece c of row r lives at position c ^ swz(r), swz(r) = bit 1 of r | bit 3 of r << 2: each of
+//                       the four 16-lane groups a ds_read_b128 is served in (lanes 0-3, 12-15, 20-27 / 4-11, 16-19, 28-31 / + 32) then
+//                       covers the 64 banks exactly once, for both halves of a fragment (no pitch from 128 to 256 bytes does: all leave
+//                       2-way conflicts), and a staging write still fills whole rows.  LDS: 2 x 2 x 128 x 128 = 65 536 bytes, two
+//                       workgroups per CU.  Rows and columns past M / N load a clamped (valid) row and are skipped by the epilogue: nothing
+//                       is read or written out of range.
+//   Operand lane map of the K = 128 form: lane l holds row / column l & 15 and the 32 bytes k = 32 (l >> 4) .. + 31 in eight VGPRs.  Both
+//   operands use the same k map, so the sum does not depend on it; the row / column map and the C/D map (the 16 x 16 one) are what the
+//   exact-integer test (tests/test_gpu_linear_fp8.py) establishes.  W is the A operand and x the B operand: a lane then holds output row
+//   l & 15 and four consecutive rows of D = output columns per block; the W rows are permuted on their way into LDS so that the lane's four blocks
+//   together are 16 consecutive output columns - 16-byte stores, 32 (bf16) / 64 (fp32) contiguous bytes per lane and row.
+#include "common.h"
+#include <atomic>
+
+namespace sv {
+
+constexpr float FP8_ROW_TARGET = 224.f;                    // half of e4m3's 448, as the attention recipe
+constexpr float FP8_SCALE_MAX = 1152921504606846976.f;     // 2^60
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  return (uint32_t)w;
+}
+
+// ---- row quantiser -------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ void load4_guarded(const T* row, int k, int K, bool vec, float (&v)[4]) {
+  if (vec && k + 4 <= K) { ldnf<4>(row + k, v); return; }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = (k + j < K) ? ldf(row + k + j) : 0.f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void quant_rows_kernel(const T* __restrict__ src, int rows, int K, long long ld, uint8_t* __restrict__ dst, int Kp,
+                                                         float* __restrict__ scales) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;                                   // whole waves leave: no barrier in this kernel
+  const T* row = src + (size_t)r * ld;
+  const bool vec = (((uintptr_t)row) & (4 * sizeof(T) - 1)) == 0;
+  float m = 0.f;
+  for (int k = lane * 4; k < K; k += 256) {
+    float v[4];
+    load4_guarded(row, k, K, vec, v);
+    m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(m, fmaxf(fabsf(v[2]), fabsf(v[3]))));
+  }
+  m = wave_max(m);
+  const float s = m > 0.f ? fminf(FP8_ROW_TARGET / m, FP8_SCALE_MAX) : 1.f;
+  uint32_t* out = reinterpret_cast<uint32_t*>(dst + (size_t)r * Kp);
+  for (int k = lane * 4; k < Kp; k += 256) {
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (k < K) load4_guarded(row, k, K, vec, v);
+    out[k >> 2] = pack4_e4m3(v[0] * s, v[1] * s, v[2] * s, v[3] * s);
+  }
+  if (lane == 0) scales[r] = s;
+}
+
+// ---- GEMM ----------------------------------------------------------------------------------------------------------------------------
+struct LinFp8Args {
+  const uint8_t* xq; const float* sx; const uint8_t* wq; const float* sw; void* out;
+  int M, N, Kp;
+  const float* bias; const void* residual; int ldr; const float* row_scale; int rows_per_scale; void* pre_act; int act; float slope; int ldc;
+};
+
+constexpr int LF_BM = 128, LF_BN = 128, LF_BK = 128, LF_PITCH = 128, LF_TILE = LF_BM * LF_PITCH;   // bytes
+__device__ __forceinline__ int lf_swz(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 2); }   // position of piece c in row r: c ^ lf_swz(r)
+
+template <typename AT, bool FAST>
+__global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];   // [2 buffers][x tile, w tile][128 rows][128 bytes, swizzled]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;                 // the wave's 64 x 64 quarter of the tile
+  const int lr = lane & 15, lg = lane >> 4;
+  const int tiles_n = (p.N + LF_BN - 1) / LF_BN;
+  const int row0 = (blockIdx.x / tiles_n) * LF_BM, col0 = (blockIdx.x % tiles_n) * LF_BN;   // consecutive workgroups share the x rows
+
+  // staging: a tile is 128 rows x 8 pieces of 16 bytes; thread t moves pieces t, t + 256, t + 512, t + 768 of each operand
+  const uint8_t* gx[4]; const uint8_t* gw[4]; int so[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pc = tid + 256 * i, r = pc >> 3, c = pc & 7;
+    // W rows are permuted on their way into LDS: tile row 64 wn + 16 nt + i (row i of MFMA block nt) holds output column 64 wn + 16 (i >> 2)
+    // + 4 nt + (i & 3), so that a lane's four blocks hold 16 CONSECUTIVE columns (epilogue below).  Fragment reads and banks are unaffected.
+    const int nl = (r & 64) + ((r & 15) >> 2) * 16 + ((r >> 4) & 3) * 4 + (r & 3);
+    const int m = min(row0 + r, p.M - 1), n = min(col0 + nl, p.N - 1);   // past the end: any valid row, the epilogue skips it
+    gx[i] = p.xq + (size_t)m * p.Kp + c * 16;
+    gw[i] = p.wq + (size_t)n * p.Kp + c * 16;
+    so[i] = r * LF_PITCH + (c ^ lf_swz(r)) * 16;
+  }
+  i32x4 rx[4], rw[4];
+  auto load_step = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      rx[i] = *reinterpret_cast<const i32x4*>(gx[i] + k0);
+      rw[i] = *reinterpret_cast<const i32x4*>(gw[i] + k0);
+    }
+  };
+  auto store_step = [&](int buf) {
+    uint8_t* xs = lf_smem + buf * 2 * LF_TILE;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      *reinterpret_cast<i32x4*>(xs + so[i]) = rx[i];
+      *reinterpret_cast<i32x4*>(xs + LF_TILE + so[i]) = rw[i];
+    }
+  };
+
+  f32x4 acc[4][4];   // [column block nt][row block mt]
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int o_lo = ((2 * lg) ^ lf_swz(lr)) * 16, o_hi = ((2 * lg + 1) ^ lf_swz(lr)) * 16;   // the lane's two 16-byte pieces of a row
+  const int nk = p.Kp / LF_BK;
+  load_step(0);
+  store_step(0);
+  __syncthreads();
+  for (int ks = 0; ks < nk; ++ks) {
+    const int buf = ks & 1;
+    if (ks + 1 < nk) load_step((ks + 1) * LF_BK);          // in flight during the MFMAs below
+    const uint8_t* xs = lf_smem + buf * 2 * LF_TILE + (wm * 64 + lr) * LF_PITCH;   // rows + 16 mt share bits 1 and 3 with lr: one swizzle per lane
+    const uint8_t* ws = lf_smem + buf * 2 * LF_TILE + LF_TILE + (wn * 64 + lr) * LF_PITCH;
+    i32x8 fx[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const i32x4 lo = *reinterpret_cast<const i32x4*>(xs + mt * 16 * LF_PITCH + o_lo), hi = *reinterpret_cast<const i32x4*>(xs + mt * 16 * LF_PITCH + o_hi);
+      fx[mt] = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const i32x4 lo = *reinterpret_cast<const i32x4*>(ws + nt * 16 * LF_PITCH + o_lo), hi = *reinterpret_cast<const i32x4*>(ws + nt * 16 * LF_PITCH + o_hi);
+      const i32x8 fw = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)   // A = W (rows of D = output columns), B = x: the lane holds 4 consecutive output columns
+        acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fx[mt], acc[nt][mt], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+    }
+    if (ks + 1 < nk) store_step(buf ^ 1);                  // the other buffer: its readers passed the barrier of the previous step
+    __syncthreads();
+  }
+
+  // ---- epilogue on the registers: with the permuted W rows, lane (lr, lg) holds row 16 mt + lr and, over its four blocks nt, the 16
+  // consecutive columns 16 lg + 4 nt + j of the wave's 64: 16-byte stores (8 bf16 / 4 fp32), 32 / 64 contiguous bytes per lane and row
+  AT* __restrict__ Y = static_cast<AT*>(p.out);
+  AT* __restrict__ PRE = static_cast<AT*>(p.pre_act);
+  const AT* __restrict__ RES = static_cast<const AT*>(p.residual);
+  constexpr int CV = sizeof(AT) == 2 ? 8 : 4;              // elements of a 16-byte piece
+  const bool vec4 = ((p.ldc | p.N) & 3) == 0 && (!RES || (p.ldr & 3) == 0);   // (base pointers: 4 elements, checked on the host)
+  const bool vecw = ((p.ldc | p.N) & (CV - 1)) == 0 && (!RES || (p.ldr & (CV - 1)) == 0) &&
+                    ((((uintptr_t)Y) | ((uintptr_t)PRE) | ((uintptr_t)RES)) & 15) == 0;
+  const int c0 = col0 + wn * 64 + lg * 16;
+  if (c0 < p.N) {
+    float swn[16], bias[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int n = min(c0 + j, p.N - 1);
+      swn[j] = p.sw[n];
+      bias[j] = p.bias ? p.bias[n] : 0.f;
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const int m = row0 + wm * 64 + mt * 16 + lr;
+      if (m >= p.M) continue;
+      const float sxm = p.sx[m];
+      const float sc = (RES && p.row_scale) ? p.row_scale[m / p.rows_per_scale] : 1.f;
+      float v[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sxm * swn[j]) + bias[j];
+      const size_t o = (size_t)m * p.ldc + c0;
+      const size_t orow = (size_t)m * p.ldr + c0;
+      if (vecw) {   // N % CV == 0: a piece is in range as a whole
+#pragma unroll
+        for (int q = 0; q < 16 / CV; ++q) {
+          if (c0 + q * CV >= p.N) break;
+          float t[CV];
+#pragma unroll
+          for (int j = 0; j < CV; ++j) t[j] = v[q * CV + j];
+          if (PRE) stnf<CV>(PRE + o + q * CV, t);
+#pragma unroll
+          for (int j = 0; j < CV; ++j) t[j] = apply_act_t<FAST>(t[j], p.act, p.slope);
+          if (RES) {
+            float r[CV];
+            ldnf<CV>(RES + orow + q * CV, r);
+#pragma unroll
+            for (int j = 0; j < CV; ++j) t[j] = r[j] + sc * t[j];
+          }
+          stnf<CV>(Y + o + q * CV, t);
+        }
+      } else if (vec4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (c0 + q * 4 >= p.N) break;
+          float t[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) t[j] = v[q * 4 + j];
+          if (PRE) stnf<4>(PRE + o + q * 4, t);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) t[j] = apply_act_t<FAST>(t[j], p.act, p.slope);
+          if (RES) {
+            float r[4];
+            ldnf<4>(RES + orow + q * 4, r);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = r[j] + sc * t[j];
+          }
+          stnf<4>(Y + o + q * 4, t);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          if (c0 + j < p.N) {
+            float t = v[j];
+            if (PRE) stf(PRE + o + j, t);
+            t = apply_act_t<FAST>(t, p.act, p.slope);
+            if (RES) t = ldf(RES + orow + j) + sc * t;
+            stf(Y + o + j, t);
+          }
+        }
+      }
+    }
+  }
+}
+
+static std::atomic<long long> linear_fp8_launches{0};
+
+// the epilogue forms the kernel serves; `why` receives the reason of a refusal
+static bool linear_fp8_epilogue_ok(const sv_epilogue* e, int N, const char** why) {
+  *why = nullptr;
+  if (!e) *why = "null epilogue";
+  else if (e->stats) *why = "per-channel statistics (stats) are not served";
+  else if (e->act_grad_src) *why = "an activation-gradient source (act_grad_src) is not served";
+  else if (e->act != SV_ACT_NONE && e->act != SV_ACT_GELU) *why = "only SV_ACT_NONE and SV_ACT_GELU are served";
+  else if (e->col_off != 0) *why = "col_off must be 0";
+  else if (e->ldc < N) *why = "ldc < N";
+  else if (e->residual && e->ldr < N) *why = "ldr < N";
+  return *why == nullptr;
+}
+
+}  // namespace sv
+
+using namespace sv;
+
+extern "C" int sv_quant_rows_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, float* scales, void* stream) {
+  SV_REQUIRE(src && dst_q && scales, "sv_quant_rows_e4m3: null argument");
+  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_rows_e4m3: bad source dtype %d", src_dtype);
+  SV_REQUIRE(rows > 0 && K > 0 && ld >= K, "sv_quant_rows_e4m3: rows (%d) and K (%d) must be positive, ld (%d) >= K", rows, K, ld);
+  SV_REQUIRE(Kp >= K && Kp % 128 == 0, "sv_quant_rows_e4m3: Kp (%d) must be a multiple of 128 and >= K (%d)", Kp, K);
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0, "sv_quant_rows_e4m3: dst_q must be 16-byte aligned");
+  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0, "sv_quant_rows_e4m3: src is not aligned to its element");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(cdiv(rows, 4));
+  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_rows_kernel<__bf16>, grid, dim3(256), 0, s, static_cast<const __bf16*>(src), rows, K, (long long)ld, static_cast<uint8_t*>(dst_q), Kp, scales);
+  else hipLaunchKernelGGL(quant_rows_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(src), rows, K, (long long)ld, static_cast<uint8_t*>(dst_q), Kp, scales);
+  return check_launch("sv_quant_rows_e4m3");
+}
+
+extern "C" int sv_linear_fp8_supported(int K, int N, const sv_epilogue* e, int math, int act_dtype) {
+  const char* why;
+  return (K > 0 && N > 0 && math == SV_MATH_BF16 && (act_dtype == SV_F32 || act_dtype == SV_BF16) && linear_fp8_epilogue_ok(e, N, &why)) ? 1 : 0;
+}
+
+extern "C" long long sv_linear_fp8_launches(void) { return linear_fp8_launches.load(std::memory_order_relaxed); }
+
+extern "C" int sv_linear_fp8(const void* xq, const float* sx, const void* wq, const float* sw, void* out, int M, int K, int N, const sv_epilogue* e,
+                             int act_dtype, void* stream) {
+  SV_REQUIRE(xq && sx && wq && sw && out && e, "sv_linear_fp8: null argument");
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE(M > 0 && K > 0 && N > 0, "sv_linear_fp8: M (%d), K (%d), N (%d) must be positive", M, K, N);
+  const char* why;
+  SV_REQUIRE(linear_fp8_epilogue_ok(e, N, &why), "sv_linear_fp8: %s", why);
+  SV_REQUIRE((((uintptr_t)xq | (uintptr_t)wq) & 15) == 0, "sv_linear_fp8: quantised operands must be 16-byte aligned");
+  const uintptr_t amask = act_dtype == SV_BF16 ? 7 : 15;
+  SV_REQUIRE((((uintptr_t)out | (uintptr_t)e->residual | (uintptr_t)e->pre_act) & amask) == 0, "sv_linear_fp8: out / residual / pre_act must be aligned to 4 elements");
+  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(N, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_fp8: too many tiles");
+  LinFp8Args a{static_cast<const uint8_t*>(xq), sx, static_cast<const uint8_t*>(wq), sw, out, M, N, cdiv(K, LF_BK) * LF_BK,
+               e->bias, e->residual, e->ldr, e->row_scale, e->rows_per_scale > 0 ? e->rows_per_scale : 1, e->pre_act, e->act, e->slope, e->ldc};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)tiles), block(256);
+  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_kernel<__bf16, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((linear_fp8_kernel<float, false>), grid, block, 0, s, a);
+  const int rc = check_launch("sv_linear_fp8");
+  if (rc == SV_OK) linear_fp8_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}

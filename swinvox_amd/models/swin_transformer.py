@@ -165,7 +165,7 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
     else:
         ln1, m1, r1 = ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, M, Cd)
         qkv = empty(M, 3 * Cd, like=x)
-        ops.linear_fwd(ln1, M, blk.s_qkv, blk.attn.qkv.weight, qkv, bias=blk.attn.qkv.bias)
+        ops.swin_linear_fwd(ln1, M, blk.s_qkv, blk.attn.qkv.weight, qkv, bias=blk.attn.qkv.bias)
         att = empty(M, Cd, like=x)
         # algorithmic work of the core (49-token windows, no padding): QK^T + PV = 4 * 49 * 32 flop per (token, head); bytes: qkv in, out
         ops.traced_call("sv_window_attention_fwd", 4.0 * 49 * 32 * M * blk.heads, esz * 4 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
@@ -173,8 +173,8 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         sc1 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
         sc2 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
         x1 = empty(M, Cd, like=x)
-        ops.linear_fwd(att, M, blk.s_proj, blk.attn.proj.weight, x1, bias=blk.attn.proj.bias, residual=x, ldr=Cd, row_scale=sc1,
-                       rows_per_scale=H * W)
+        ops.swin_linear_fwd(att, M, blk.s_proj, blk.attn.proj.weight, x1, bias=blk.attn.proj.bias, residual=x, ldr=Cd, row_scale=sc1,
+                            rows_per_scale=H * W)
     if ops.fused_mlp_enabled(Cd):
         # norm2 -> fc1 -> GELU -> fc2 -> drop-path -> +x1 in ONE kernel; the 4C-wide hidden activation never reaches HBM
         packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
@@ -187,10 +187,10 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
     ln2, m2, r2 = ops.layernorm_fwd(x1, blk.norm2.weight, blk.norm2.bias, M, Cd)
     hpre = empty(M, 4 * Cd, like=x)
     h = empty(M, 4 * Cd, like=x)
-    ops.linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
+    ops.swin_linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
     x2 = empty(M, Cd, like=x)
-    ops.linear_fwd(h, M, blk.s_fc2, blk.mlp.fc2.weight, x2, bias=blk.mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2,
-                   rows_per_scale=H * W)
+    ops.swin_linear_fwd(h, M, blk.s_fc2, blk.mlp.fc2.weight, x2, bias=blk.mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2,
+                        rows_per_scale=H * W)
     return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, m2, r2, ln2, hpre, h, I)
 
 
@@ -294,7 +294,7 @@ def stage_forward(stage: SwinStage, x, I, training, stochastic, seeds, save=True
         Mo = I * stage.res * stage.res
         lnm, mm, rm = ops.layernorm_fwd(x, ds.norm.weight, ds.norm.bias, Mo, 2 * stage.dim, merge_hw=(Hin, Hin))
         y = empty(Mo, stage.dim, like=x)
-        ops.linear_fwd(lnm, Mo, ds.spec, ds.reduction.weight, y)
+        ops.swin_linear_fwd(lnm, Mo, ds.spec, ds.reduction.weight, y)
         sctx["merge"] = (x, lnm, mm, rm, Mo, Hin)
         x = y
     for blk in stage.blocks:

@@ -293,6 +293,7 @@ class PackCache:
 
     def __init__(self):
         self.tables = {}   # storage dtype -> dict(entries={key: [spec, w, kind, view]}, dirty, flat, descs, sig, nblocks)
+        self.w8 = {}       # id(parameter) -> (e4m3 rows, row scales) of the running forward (quantize_weight_fp8); dropped by refresh()
 
     def __deepcopy__(self, memo):
         return PackCache()    # keyed by parameter identity: a copied module starts with an empty cache
@@ -313,6 +314,7 @@ class PackCache:
 
     def refresh(self):
         """(Re)build the descriptor table when the set of packs or a parameter's address changed, then pack everything."""
+        self.w8 = {}
         t = self._table()
         ents = list(t["entries"].values())
         if not ents:
@@ -547,6 +549,58 @@ def colsum(x, rows, cols, ld, out, accumulate=True):
 # ---------------------------------------------------------------------------------------------------
 def linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
     spec.forward(x, rows, (1, 1, 1), w, out, **epi)
+
+
+def set_linear_fp8(on: bool) -> None:
+    """BASELINE configuration 5, linear part: the FORWARD of the Swin linears (qkv, proj, fc1, fc2, patch-merge reduction) on e4m3 operands
+    with per-row scales and the block-scaled K = 128 MFMA (csrc/linear_fp8.hip).  The stored tensors and the backward are unchanged (bf16
+    data and weight gradients: the quantisers are straight-through).  Active only under set_math('bf16'); independent of set_attention_fp8.
+    Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them)."""
+    _STATE["linear_fp8"] = bool(on)
+
+
+def linear_fp8_enabled() -> bool:
+    return bool(_STATE.get("linear_fp8")) and _STATE["math"] == hip.MATH_BF16
+
+
+def linear_fp8_launches() -> int:
+    """sv_linear_fp8 launches of this process so far."""
+    return int(hip.load().sv_linear_fp8_launches())
+
+
+def quantize_rows_fp8(t: torch.Tensor, rows: int, K: int, ld: Optional[int] = None):
+    """t [rows, K] (fp32 or bf16, row stride ld) -> (e4m3 bytes [rows, roundup(K, 128)], fp32 row scales [rows]) by sv_quant_rows_e4m3."""
+    Kp = (K + 127) // 128 * 128
+    q = torch.empty(rows, Kp, dtype=torch.uint8, device=t.device)
+    sc = torch.empty(rows, dtype=torch.float32, device=t.device)
+    call("sv_quant_rows_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, K, ld or K, ptr(q), Kp, ptr(sc))
+    return q, sc
+
+
+def quantize_weight_fp8(w: torch.Tensor):
+    """Quantised rows of a Linear weight [N, K]: one small launch, cached for the running forward of the module (weights change only in
+    optimizer.step(), the lifetime of the weight packs)."""
+    cache = _CTX.packs
+    if cache is None or not isinstance(w, torch.nn.Parameter):
+        return quantize_rows_fp8(w, w.shape[0], w.shape[1])
+    hit = cache.w8.get(id(w))
+    if hit is None:
+        hit = cache.w8[id(w)] = quantize_rows_fp8(w, w.shape[0], w.shape[1])
+    return hit
+
+
+def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
+    """linear_fwd of the Swin call sites: with set_linear_fp8(True) (and a form sv_linear_fp8 serves) the activation rows are quantised, the
+    quantised weight fetched and the product runs on the fp8 kernel; otherwise exactly linear_fwd."""
+    if linear_fp8_enabled() and spec.taps == 1 and spec.cin_mem == spec.cin and isinstance(w, torch.nn.Parameter):
+        e = _epilogue(spec.cout, **epi)
+        if hip.load().sv_linear_fp8_supported(spec.cin, spec.cout, C.byref(e), _STATE["math"], hip.ACT) == 1:
+            xq, sx = quantize_rows_fp8(x, rows, spec.cin)
+            wq, sw = quantize_weight_fp8(w)
+            traced_call("sv_linear_fp8", 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + x.element_size() * spec.cout) + wq.numel(),
+                        ptr(xq), ptr(sx), ptr(wq), ptr(sw), ptr(out), rows, spec.cin, spec.cout, C.byref(e), tag=f"M={rows} K={spec.cin} N={spec.cout}")
+            return
+    linear_fwd(x, rows, spec, w, out, **epi)
 
 
 def linear_dgrad(dy, rows, spec: ConvSpec, w_t, dx, **epi):
