@@ -131,6 +131,28 @@ int sv_linear_fp8(const void* xq, const float* sx, const void* wq, const float* 
 /* 1 when the fp8 linear serves this call (timm Linear behind models/swin_transformer.py:78): math == SV_MATH_BF16 and an epilogue form listed above; else 0 */
 int sv_linear_fp8_supported(int K, int N, const sv_epilogue* e, int math, int act_dtype);
 long long sv_linear_fp8_launches(void); /* fp8 linear launches so far in this process (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise) */
+/* fp8 BACKWARD of the same Linear layers (timm Linear behind models/swin_transformer.py:78; autograd of F.linear), constants and rounding of the
+ * forward recipe, all operands e4m3, quantisers straight-through.
+ * The column quantiser (timm Linear behind models/swin_transformer.py:78, operand preparation of the backward): src [M, C] with row stride ld (SV_F32 or
+ * SV_BF16 elements) -> dst_q [C][Mp] bytes (the TRANSPOSE, 16-byte aligned, Mp = roundup(M, 128), bytes M .. Mp-1 of every row zero) and
+ * scales [C] = 224 / max_m |src[m, c]| (all-zero column: 1; at most 2^60).  colsum (optional, [C] fp32): colsum[c] += sum_m src[m, c], the bias
+ * gradient, from the unquantised values.  On the [N, K] fp32 weight it yields the [K][Np] operand of the data gradient. */
+int sv_quant_cols_e4m3(const void* src, int src_dtype, int M, int C, int ld, void* dst_q, int Mp, float* scales, float* colsum, void* stream);
+/* data gradient dx[m, k] = sum_n dq[m, n] wtq[k, n] / (sd[m] swt[k]) (timm Linear behind models/swin_transformer.py:78, gradient with respect to the
+ * input).  dq [M, Np] / sd [M] from the row quantiser on dy, wtq [K, Np] / swt [K] from the column quantiser on W [N, K], Np = roundup(N, 128); dx and
+ * e->act_grad_src hold act_dtype elements with row stride e->ldc.  Epilogue forms served: none, act_grad_src with act_grad_kind = SV_ACT_GELU
+ * (erf form with SV_F32 storage, the engine's fast form with SV_BF16 storage), ldc.  Everything else is refused with SV_ERR_INVALID. */
+int sv_linear_fp8_dgrad(const void* dq, const float* sd, const void* wtq, const float* swt, void* dx, int M, int N, int K, const sv_epilogue* e,
+                        int act_dtype, void* stream);
+/* 1 when sv_linear_fp8_dgrad serves this call (timm Linear behind models/swin_transformer.py:78): math == SV_MATH_BF16 and an epilogue form listed above; else 0 */
+int sv_linear_fp8_dgrad_supported(int N, int K, const sv_epilogue* e, int math, int act_dtype);
+/* weight gradient dw[n * ldw + k] += sum_m dyt[n, m] xt[k, m] / (sdc[n] sxc[k]) (timm Linear behind models/swin_transformer.py:78, gradient with respect
+ * to the weight; fp32 atomics).  dyt [N, Mp] / sdc [N] and xt [K, Mp] / sxc [K] from the column quantiser on dy [M, N] and x [M, K].  The contraction
+ * over the tokens is shared among `splits` workgroups per 128 x 128 tile of dw (at most one per 128 tokens); 0 = as many as give two workgroups
+ * to each of 256 CUs. */
+int sv_linear_fp8_wgrad(const void* dyt, const float* sdc, const void* xt, const float* sxc, float* dw, int M, int N, int K, int ldw, int splits,
+                        void* stream);
+long long sv_linear_fp8_bwd_launches(int which); /* launches so far of sv_linear_fp8_dgrad (which = 0) / sv_linear_fp8_wgrad (1) (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise); sv_linear_fp8_launches counts neither */
 /* LDS-halo MFMA stencils for 3x3x3 / stride 1 / pad 1 convolutions with <= 16 output channels per tile (merger.py:20-54),
  * bf16 operands.  x: channels-last positions with row stride ldx, cin_load (multiple of 4) elements read per position,
  * zero-extended to 16*groups channels; w_bf16: [16*ntiles16][27][16*groups] bf16 (forward: rows = output channels;

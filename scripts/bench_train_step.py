@@ -1,6 +1,7 @@
 """Whole optimisation step (harness.train_step: forward + backward + clip + solver) with the flat-buffer solvers and with
 the stock torch.optim sequence, next to forward+backward alone.  python scripts/bench_train_step.py [--batch 32]
---fp8-linear: forward+backward alone with the fp8 Swin linears (set_linear_fp8) off and on, same process."""
+--fp8-linear: forward+backward alone with the fp8 Swin linears (set_linear_fp8) off and on, same process.
+--fp8-linear-bwd: the same with a third run, set_linear_fp8(True, backward=True): data and weight gradients of the linears in e4m3 too."""
 import argparse
 import os
 import sys
@@ -18,6 +19,7 @@ ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--views", type=int, default=8)
 ap.add_argument("--steps", type=int, default=6)
 ap.add_argument("--fp8-linear", action="store_true", help="time forward+backward only, with set_linear_fp8 off and on")
+ap.add_argument("--fp8-linear-bwd", action="store_true", help="as --fp8-linear, plus a run with the fp8 backward of the linears")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = S.default_cfg()
@@ -38,16 +40,17 @@ def timed(fn, n):
     return (time.perf_counter() - t) / n * 1e3
 
 
-for fused in ((None, "fp8") if a.fp8_linear else (True, False, None)):
+for fused in ((None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
     torch.manual_seed(0)
     nets = [m(cfg).to(dev).train() for m in (Encoder, Decoder, Merger, Refiner)]
-    S.set_linear_fp8(fused == "fp8")
-    if fused is None or fused == "fp8":
+    fp8 = fused in ("fp8", "fp8+bwd")
+    S.set_linear_fp8(fp8, backward=fused == "fp8+bwd")
+    if fused is None or fp8:
         def step():
             for n in nets:
                 n.zero_grad(set_to_none=True)
             harness.forward_losses(nets, cfg, x, gt)[0].backward()
-        name = "forward+backward only" + (", fp8 Swin linears" if fused == "fp8" else "")
+        name = "forward+backward only" + (", fp8 Swin linears" if fused == "fp8" else ", fp8 Swin linears fwd + bwd" if fp8 else "")
     else:
         solvers, _ = harness.make_solvers(nets, cfg, fused=fused)
         def step():

@@ -32,6 +32,30 @@
 //   exact-integer test (tests/test_gpu_linear_fp8.py) establishes.  W is the A operand and x the B operand: a lane then holds output row
 //   l & 15 and four consecutive rows of D = output columns per block; the W rows are permuted on their way into LDS so that the lane's four blocks
 //   together are 16 consecutive output columns - 16-byte stores, 32 (bf16) / 64 (fp32) contiguous bytes per lane and row.
+//
+// Backward (opt-in: set_linear_fp8(True, backward=True)); the constants, the zero rule, the clamp, the rounding, the zero padding to a multiple of 128
+// bytes along the contraction, the unit hardware block scales and the fp32 IEEE division of the epilogue are the forward's.  All operands are
+// e4m3: inside one contraction its range (224 / 2^-9 = 1e5 below the vector's maximum) loses only terms that do not matter to the sum, and its
+// third mantissa bit (e5m2 has two) does matter.  The quantisers are straight-through.
+//   data gradient    dx[M, K] = dy[M, N] W[N, K], contraction over N.  dy is quantised per ROW (scale over N: sd[m], the row quantiser above),
+//                    W^T per row = per COLUMN k of W (scale over N: swt[k], the column quantiser on the [N, K] fp32 weight, whose [K][Np] output is
+//                    the row-major operand the GEMM wants).  val = acc / (sd[m] swt[k]).  Epilogue forms served: none; act_grad_src with
+//                    SV_ACT_GELU (val *= gelu'(act_grad_src), common.h's act_grad_t<FAST>, FAST with bf16 storage as in the engine); ldc.
+//                    Everything else (stats, bias, residual, row_scale, pre_act, act, another act_grad_kind, col_off) is refused.
+//   weight gradient  dw[N, K] += dy^T[N, M] x[M, K], contraction over M.  dy and x are quantised per COLUMN, one scale per column over all M rows of
+//                    the stored tensor (sdc[n], sxc[k]), and written transposed as [N][Mp] and [K][Mp] bytes, Mp = roundup(M, 128), zeros past M.
+//                    val = acc / (sdc[n] sxc[k]) is added into the fp32 dw in its native [N, K] layout.  db[n] += sum_m dy[m, n] is taken in
+//                    fp32 from the stored, unquantised dy by the column quantiser's first pass.
+// Kernels of the backward
+//   quant_cols_*     pass 1: per-workgroup partial column maxima (and fp64 partial column sums), then an integer atomic max on the bit pattern
+//                    of the non-negative float (and one fp32 atomic add per workgroup and column); a C-thread kernel turns the maxima into
+//                    scales in place; pass 2: a 128-row x 64-column tile is scaled, rounded and transposed through LDS, 16-byte stores along M.
+//   lf_contract      the k-loop of linear_fp8_kernel (staging, swizzled LDS image, fragment reads, MFMA block) over a range of k-steps: the one
+//                    copy the forward, the data-gradient and the weight-gradient kernel run.
+//   linear_fp8_dgrad_kernel   lf_contract over the full contraction + the epilogue above.
+//   linear_fp8_wgrad_kernel   grid tiles(N) x tiles(K) x splits, split z contracts the k-steps [z nk / splits, (z + 1) nk / splits); dy^T is the
+//                    row operand, so a lane's 16 consecutive outputs run along k, the contiguous dimension of dw; fp32 atomicAdd into dw
+//                    (a plain read-add-write when splits == 1).  splits = 0 picks enough workgroups for 2 per CU of 256 CUs.
 #include "common.h"
 #include <atomic>
 
@@ -92,14 +116,15 @@ struct LinFp8Args {
 constexpr int LF_BM = 128, LF_BN = 128, LF_BK = 128, LF_PITCH = 128, LF_TILE = LF_BM * LF_PITCH;   // bytes
 __device__ __forceinline__ int lf_swz(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 2); }   // position of piece c in row r: c ^ lf_swz(r)
 
-template <typename AT, bool FAST>
-__global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];   // [2 buffers][x tile, w tile][128 rows][128 bytes, swizzled]
+// The contraction core every fp8 GEMM of this file runs: acc += sum over the k-steps ks0 .. ks1 - 1 (128 bytes each) of the 128 x 128 tile
+// at (row0, col0) of xq [M][pitch] times wq [N][pitch]^T.  Staging, the swizzled LDS image, the fragment reads and the MFMA block have this
+// one copy.  On return lane (lr, lg) of wave (wm, wn) holds, in acc[nt][mt][i], row row0 + 64 wm + 16 mt + lr and column
+// col0 + 64 wn + 16 lg + 4 nt + i: 16 consecutive columns per row.  Rows past M / N read a clamped (valid) row; the caller's epilogue skips them.
+__device__ __forceinline__ void lf_contract(const uint8_t* __restrict__ xq, int M, const uint8_t* __restrict__ wq, int N, size_t pitch, int row0, int col0,
+                                            int ks0, int ks1, uint8_t* __restrict__ lf_smem, f32x4 (&acc)[4][4]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;                 // the wave's 64 x 64 quarter of the tile
   const int lr = lane & 15, lg = lane >> 4;
-  const int tiles_n = (p.N + LF_BN - 1) / LF_BN;
-  const int row0 = (blockIdx.x / tiles_n) * LF_BM, col0 = (blockIdx.x % tiles_n) * LF_BN;   // consecutive workgroups share the x rows
 
   // staging: a tile is 128 rows x 8 pieces of 16 bytes; thread t moves pieces t, t + 256, t + 512, t + 768 of each operand
   const uint8_t* gx[4]; const uint8_t* gw[4]; int so[4];
@@ -107,15 +132,15 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) 
   for (int i = 0; i < 4; ++i) {
     const int pc = tid + 256 * i, r = pc >> 3, c = pc & 7;
     // W rows are permuted on their way into LDS: tile row 64 wn + 16 nt + i (row i of MFMA block nt) holds output column 64 wn + 16 (i >> 2)
-    // + 4 nt + (i & 3), so that a lane's four blocks hold 16 CONSECUTIVE columns (epilogue below).  Fragment reads and banks are unaffected.
+    // + 4 nt + (i & 3), so that a lane's four blocks hold 16 CONSECUTIVE columns (epilogues below).  Fragment reads and banks are unaffected.
     const int nl = (r & 64) + ((r & 15) >> 2) * 16 + ((r >> 4) & 3) * 4 + (r & 3);
-    const int m = min(row0 + r, p.M - 1), n = min(col0 + nl, p.N - 1);   // past the end: any valid row, the epilogue skips it
-    gx[i] = p.xq + (size_t)m * p.Kp + c * 16;
-    gw[i] = p.wq + (size_t)n * p.Kp + c * 16;
+    const int m = min(row0 + r, M - 1), n = min(col0 + nl, N - 1);   // past the end: any valid row, the epilogue skips it
+    gx[i] = xq + (size_t)m * pitch + c * 16;
+    gw[i] = wq + (size_t)n * pitch + c * 16;
     so[i] = r * LF_PITCH + (c ^ lf_swz(r)) * 16;
   }
   i32x4 rx[4], rw[4];
-  auto load_step = [&](int k0) {
+  auto load_step = [&](size_t k0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       rx[i] = *reinterpret_cast<const i32x4*>(gx[i] + k0);
@@ -131,20 +156,13 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) 
     }
   };
 
-  f32x4 acc[4][4];   // [column block nt][row block mt]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
   const int o_lo = ((2 * lg) ^ lf_swz(lr)) * 16, o_hi = ((2 * lg + 1) ^ lf_swz(lr)) * 16;   // the lane's two 16-byte pieces of a row
-  const int nk = p.Kp / LF_BK;
-  load_step(0);
+  load_step((size_t)ks0 * LF_BK);
   store_step(0);
   __syncthreads();
-  for (int ks = 0; ks < nk; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nk) load_step((ks + 1) * LF_BK);          // in flight during the MFMAs below
+  for (int ks = ks0; ks < ks1; ++ks) {
+    const int buf = (ks - ks0) & 1;
+    if (ks + 1 < ks1) load_step((size_t)(ks + 1) * LF_BK);   // in flight during the MFMAs below
     const uint8_t* xs = lf_smem + buf * 2 * LF_TILE + (wm * 64 + lr) * LF_PITCH;   // rows + 16 mt share bits 1 and 3 with lr: one swizzle per lane
     const uint8_t* ws = lf_smem + buf * 2 * LF_TILE + LF_TILE + (wn * 64 + lr) * LF_PITCH;
     i32x8 fx[4];
@@ -161,9 +179,30 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) 
       for (int mt = 0; mt < 4; ++mt)   // A = W (rows of D = output columns), B = x: the lane holds 4 consecutive output columns
         acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fx[mt], acc[nt][mt], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
     }
-    if (ks + 1 < nk) store_step(buf ^ 1);                  // the other buffer: its readers passed the barrier of the previous step
+    if (ks + 1 < ks1) store_step(buf ^ 1);                 // the other buffer: its readers passed the barrier of the previous step
     __syncthreads();
   }
+}
+
+__device__ __forceinline__ void lf_zero(f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+template <typename AT, bool FAST>
+__global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];   // [2 buffers][x tile, w tile][128 rows][128 bytes, swizzled]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int tiles_n = (p.N + LF_BN - 1) / LF_BN;
+  const int row0 = (blockIdx.x / tiles_n) * LF_BM, col0 = (blockIdx.x % tiles_n) * LF_BN;   // consecutive workgroups share the x rows
+
+  f32x4 acc[4][4];   // [column block nt][row block mt]
+  lf_zero(acc);
+  lf_contract(p.xq, p.M, p.wq, p.N, (size_t)p.Kp, row0, col0, 0, p.Kp / LF_BK, lf_smem, acc);
 
   // ---- epilogue on the registers: with the permuted W rows, lane (lr, lg) holds row 16 mt + lr and, over its four blocks nt, the 16
   // consecutive columns 16 lg + 4 nt + j of the wave's 64: 16-byte stores (8 bf16 / 4 fp32), 32 / 64 contiguous bytes per lane and row
@@ -246,7 +285,201 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) 
   }
 }
 
+// ---- data gradient: dx[M, K] = dy[M, N] W[N, K], the contraction runs over N -----------------------------------------------------------------
+struct LinFp8DgradArgs {
+  const uint8_t* dq; const float* sd; const uint8_t* wtq; const float* swt; void* out;
+  int M, K, Np;
+  const void* act_grad_src; int act_grad_kind; float slope; int ldc;
+};
+
+template <typename AT, bool FAST>
+__global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const LinFp8DgradArgs p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int tiles_k = (p.K + LF_BN - 1) / LF_BN;
+  const int row0 = (blockIdx.x / tiles_k) * LF_BM, col0 = (blockIdx.x % tiles_k) * LF_BN;   // consecutive workgroups share the dy rows
+
+  f32x4 acc[4][4];
+  lf_zero(acc);
+  lf_contract(p.dq, p.M, p.wtq, p.K, (size_t)p.Np, row0, col0, 0, p.Np / LF_BK, lf_smem, acc);
+
+  AT* __restrict__ Y = static_cast<AT*>(p.out);
+  const AT* __restrict__ G = static_cast<const AT*>(p.act_grad_src);   // layout of the output
+  constexpr int CV = sizeof(AT) == 2 ? 8 : 4;
+  const bool vecw = ((p.ldc | p.K) & (CV - 1)) == 0 && ((((uintptr_t)Y) | ((uintptr_t)G)) & 15) == 0;
+  const int c0 = col0 + wn * 64 + lg * 16;
+  if (c0 >= p.K) return;
+  float swk[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) swk[j] = p.swt[min(c0 + j, p.K - 1)];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int m = row0 + wm * 64 + mt * 16 + lr;
+    if (m >= p.M) continue;
+    const float sdm = p.sd[m];
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sdm * swk[j]);
+    const size_t o = (size_t)m * p.ldc + c0;
+    if (vecw) {   // K % CV == 0: a piece is in range as a whole
+#pragma unroll
+      for (int q = 0; q < 16 / CV; ++q) {
+        if (c0 + q * CV >= p.K) break;
+        float t[CV];
+#pragma unroll
+        for (int j = 0; j < CV; ++j) t[j] = v[q * CV + j];
+        if (G) {
+          float a[CV];
+          ldnf<CV>(G + o + q * CV, a);
+#pragma unroll
+          for (int j = 0; j < CV; ++j) t[j] *= act_grad_t<FAST>(a[j], p.act_grad_kind, p.slope);
+        }
+        stnf<CV>(Y + o + q * CV, t);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        if (c0 + j < p.K) {
+          float t = v[j];
+          if (G) t *= act_grad_t<FAST>(ldf(G + o + j), p.act_grad_kind, p.slope);
+          stf(Y + o + j, t);
+        }
+      }
+    }
+  }
+}
+
+// ---- weight gradient: dw[N, K] += dy^T[N, M] x[M, K], the contraction runs over M (the tokens) ------------------------------------------------------
+struct LinFp8WgradArgs {
+  const uint8_t* dyt; const float* sdc; const uint8_t* xt; const float* sxc; float* dw;
+  int N, K, Mp, ldw, splits;
+};
+
+__global__ __launch_bounds__(256, 2) void linear_fp8_wgrad_kernel(const LinFp8WgradArgs p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int tiles_k = (p.K + LF_BN - 1) / LF_BN;
+  const int row0 = (blockIdx.x / tiles_k) * LF_BM, col0 = (blockIdx.x % tiles_k) * LF_BN;   // rows of dw = n, columns = k
+  const int nk = p.Mp / LF_BK, z = blockIdx.y;
+  const int ks0 = (int)((long long)z * nk / p.splits), ks1 = (int)((long long)(z + 1) * nk / p.splits);   // splits <= nk: no share is empty
+
+  f32x4 acc[4][4];
+  lf_zero(acc);
+  // dy^T is the row operand and x^T the permuted one: a lane's 16 consecutive outputs run along k, the contiguous dimension of dw
+  lf_contract(p.dyt, p.N, p.xt, p.K, (size_t)p.Mp, row0, col0, ks0, ks1, lf_smem, acc);
+
+  const int c0 = col0 + wn * 64 + lg * 16;
+  if (c0 >= p.K) return;
+  float sxk[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) sxk[j] = p.sxc[min(c0 + j, p.K - 1)];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int n = row0 + wm * 64 + mt * 16 + lr;
+    if (n >= p.N) continue;
+    const float sdn = p.sdc[n];
+    float* __restrict__ d = p.dw + (size_t)n * p.ldw + c0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if (c0 + j < p.K) {
+        const float val = acc[j >> 2][mt][j & 3] / (sdn * sxk[j]);
+        if (p.splits == 1) d[j] += val;                    // the only writer of this element
+        else atomicAdd(d + j, val);
+      }
+    }
+  }
+}
+
+// ---- column quantiser: src [M, C] (row stride ld) -> dst [C][Mp] e4m3 bytes, one scale per column ---------------------------------------------------
+constexpr int QC_COLS = 64, QC_ROWS1 = 256, QC_ROWS2 = 128, QC_PITCH = 33;   // pass-2 LDS rows: 32 dwords + 1, conflict-free on both sides
+
+// pass 1: amax[c] = max over the rows of |src[m, c]| as the bit pattern of the non-negative float (integer max = float max there), into a zeroed
+// buffer; optionally colsum[c] += sum over the rows (fp64 partial per workgroup, one fp32 atomic per workgroup and column)
+template <typename T>
+__global__ __launch_bounds__(256) void quant_cols_amax_kernel(const T* __restrict__ src, int M, int C, long long ld, int* __restrict__ amax_bits,
+                                                              float* __restrict__ colsum) {
+  __shared__ float smax[4][QC_COLS];
+  __shared__ double ssum[4][QC_COLS];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * QC_COLS + tx;
+  const int m0 = blockIdx.y * QC_ROWS1, m1 = min(m0 + QC_ROWS1, M);
+  float mx = 0.f;
+  double sum = 0.0;
+  if (c < C) {
+    for (int m = m0 + ty; m < m1; m += 4) {
+      const float v = ldf(src + (size_t)m * ld + c);
+      mx = fmaxf(mx, fabsf(v));
+      sum += (double)v;
+    }
+  }
+  smax[ty][tx] = mx;
+  ssum[ty][tx] = sum;
+  __syncthreads();
+  if (ty == 0 && c < C) {
+    mx = fmaxf(fmaxf(smax[0][tx], smax[1][tx]), fmaxf(smax[2][tx], smax[3][tx]));
+    atomicMax(amax_bits + c, __float_as_int(mx));
+    if (colsum) atomicAdd(colsum + c, (float)(ssum[0][tx] + ssum[1][tx] + ssum[2][tx] + ssum[3][tx]));
+  }
+}
+
+// between the passes: the bit pattern of amax becomes the scale, in place
+__global__ void quant_cols_scale_kernel(float* __restrict__ scales, int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) {
+    const float m = scales[c];
+    scales[c] = m > 0.f ? fminf(FP8_ROW_TARGET / m, FP8_SCALE_MAX) : 1.f;
+  }
+}
+
+// pass 2: a tile of 128 rows x 64 columns is scaled, rounded to e4m3 and transposed through LDS; 16-byte stores along M.  Rows past M are zero bytes.
+template <typename T>
+__global__ __launch_bounds__(256) void quant_cols_write_kernel(const T* __restrict__ src, int M, int C, long long ld, const float* __restrict__ scales,
+                                                               uint8_t* __restrict__ dst, int Mp) {
+  __shared__ uint32_t tile[QC_COLS * QC_PITCH];            // [column][32 dwords = 128 rows]
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c0 = blockIdx.x * QC_COLS, m0 = blockIdx.y * QC_ROWS2;
+  const int c = c0 + tx;
+  const float s = c < C ? scales[c] : 1.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {                            // thread (tx, ty): rows 32 ty + 4 i .. + 3 of column tx
+    const int m = m0 + ty * 32 + i * 4;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (c < C && m + j < M) ? ldf(src + (size_t)(m + j) * ld + c) : 0.f;
+    tile[tx * QC_PITCH + ty * 8 + i] = pack4_e4m3(v[0] * s, v[1] * s, v[2] * s, v[3] * s);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {                            // 64 columns x 8 pieces of 16 bytes
+    const int pc = threadIdx.x + 256 * i, col = pc >> 3, piece = pc & 7;
+    if (c0 + col < C) {
+      const uint32_t* t = tile + col * QC_PITCH + piece * 4;
+      *reinterpret_cast<uint4*>(dst + (size_t)(c0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
+    }
+  }
+}
+
 static std::atomic<long long> linear_fp8_launches{0};
+static std::atomic<long long> linear_fp8_bwd_launches[2];   // data gradient, weight gradient
+
+// the epilogue forms the data-gradient kernel serves
+static bool linear_fp8_dgrad_epilogue_ok(const sv_epilogue* e, int K, const char** why) {
+  *why = nullptr;
+  if (!e) *why = "null epilogue";
+  else if (e->stats) *why = "per-channel statistics (stats) are not served";
+  else if (e->bias) *why = "a bias is not served";
+  else if (e->residual || e->row_scale) *why = "a residual / row_scale is not served";
+  else if (e->pre_act) *why = "pre_act is not served";
+  else if (e->act != SV_ACT_NONE) *why = "an activation is not served";
+  else if (e->act_grad_src && e->act_grad_kind != SV_ACT_GELU) *why = "only SV_ACT_GELU is served as act_grad_kind";
+  else if (e->col_off != 0) *why = "col_off must be 0";
+  else if (e->ldc < K) *why = "ldc < K";
+  return *why == nullptr;
+}
 
 // the epilogue forms the kernel serves; `why` receives the reason of a refusal
 static bool linear_fp8_epilogue_ok(const sv_epilogue* e, int N, const char** why) {
@@ -306,5 +539,76 @@ extern "C" int sv_linear_fp8(const void* xq, const float* sx, const void* wq, co
   else hipLaunchKernelGGL((linear_fp8_kernel<float, false>), grid, block, 0, s, a);
   const int rc = check_launch("sv_linear_fp8");
   if (rc == SV_OK) linear_fp8_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+extern "C" int sv_quant_cols_e4m3(const void* src, int src_dtype, int M, int C, int ld, void* dst_q, int Mp, float* scales, float* colsum, void* stream) {
+  SV_REQUIRE(src && dst_q && scales, "sv_quant_cols_e4m3: null argument");
+  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_cols_e4m3: bad source dtype %d", src_dtype);
+  SV_REQUIRE(M > 0 && C > 0 && ld >= C, "sv_quant_cols_e4m3: M (%d) and C (%d) must be positive, ld (%d) >= C", M, C, ld);
+  SV_REQUIRE(Mp >= M && Mp % 128 == 0 && Mp - M < 128, "sv_quant_cols_e4m3: Mp (%d) must be M (%d) rounded up to a multiple of 128", Mp, M);
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0, "sv_quant_cols_e4m3: dst_q must be 16-byte aligned");
+  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0, "sv_quant_cols_e4m3: src is not aligned to its element");
+  SV_REQUIRE(cdiv(M, QC_ROWS2) <= 65535, "sv_quant_cols_e4m3: M (%d) is too large", M);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(scales, 0, sizeof(float) * (size_t)C, s) != hipSuccess) return check_launch("sv_quant_cols_e4m3 (clear)");
+  const dim3 g1(cdiv(C, QC_COLS), cdiv(M, QC_ROWS1)), g2(cdiv(C, QC_COLS), Mp / QC_ROWS2);
+  uint8_t* dst = static_cast<uint8_t*>(dst_q);
+  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_cols_amax_kernel<__bf16>, g1, dim3(256), 0, s, static_cast<const __bf16*>(src), M, C, (long long)ld, reinterpret_cast<int*>(scales), colsum);
+  else hipLaunchKernelGGL(quant_cols_amax_kernel<float>, g1, dim3(256), 0, s, static_cast<const float*>(src), M, C, (long long)ld, reinterpret_cast<int*>(scales), colsum);
+  hipLaunchKernelGGL(quant_cols_scale_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, scales, C);
+  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_cols_write_kernel<__bf16>, g2, dim3(256), 0, s, static_cast<const __bf16*>(src), M, C, (long long)ld, scales, dst, Mp);
+  else hipLaunchKernelGGL(quant_cols_write_kernel<float>, g2, dim3(256), 0, s, static_cast<const float*>(src), M, C, (long long)ld, scales, dst, Mp);
+  return check_launch("sv_quant_cols_e4m3");
+}
+
+extern "C" int sv_linear_fp8_dgrad_supported(int N, int K, const sv_epilogue* e, int math, int act_dtype) {
+  const char* why;
+  return (N > 0 && K > 0 && math == SV_MATH_BF16 && (act_dtype == SV_F32 || act_dtype == SV_BF16) && linear_fp8_dgrad_epilogue_ok(e, K, &why)) ? 1 : 0;
+}
+
+extern "C" long long sv_linear_fp8_bwd_launches(int which) {
+  return (which == 0 || which == 1) ? linear_fp8_bwd_launches[which].load(std::memory_order_relaxed) : -1;
+}
+
+extern "C" int sv_linear_fp8_dgrad(const void* dq, const float* sd, const void* wtq, const float* swt, void* dx, int M, int N, int K, const sv_epilogue* e,
+                                   int act_dtype, void* stream) {
+  SV_REQUIRE(dq && sd && wtq && swt && dx && e, "sv_linear_fp8_dgrad: null argument");
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE(M > 0 && N > 0 && K > 0, "sv_linear_fp8_dgrad: M (%d), N (%d), K (%d) must be positive", M, N, K);
+  const char* why;
+  SV_REQUIRE(linear_fp8_dgrad_epilogue_ok(e, K, &why), "sv_linear_fp8_dgrad: %s", why);
+  SV_REQUIRE((((uintptr_t)dq | (uintptr_t)wtq) & 15) == 0, "sv_linear_fp8_dgrad: quantised operands must be 16-byte aligned");
+  const uintptr_t amask = act_dtype == SV_BF16 ? 1 : 3;
+  SV_REQUIRE((((uintptr_t)dx | (uintptr_t)e->act_grad_src) & amask) == 0, "sv_linear_fp8_dgrad: dx / act_grad_src are not aligned to their element");
+  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(K, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_fp8_dgrad: too many tiles");
+  LinFp8DgradArgs a{static_cast<const uint8_t*>(dq), sd, static_cast<const uint8_t*>(wtq), swt, dx, M, K, cdiv(N, LF_BK) * LF_BK,
+                    e->act_grad_src, e->act_grad_kind, e->slope, e->ldc};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)tiles), block(256);
+  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_dgrad_kernel<__bf16, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((linear_fp8_dgrad_kernel<float, false>), grid, block, 0, s, a);
+  const int rc = check_launch("sv_linear_fp8_dgrad");
+  if (rc == SV_OK) linear_fp8_bwd_launches[0].fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+extern "C" int sv_linear_fp8_wgrad(const void* dyt, const float* sdc, const void* xt, const float* sxc, float* dw, int M, int N, int K, int ldw, int splits,
+                                   void* stream) {
+  SV_REQUIRE(dyt && sdc && xt && sxc && dw, "sv_linear_fp8_wgrad: null argument");
+  SV_REQUIRE(M > 0 && N > 0 && K > 0 && ldw >= K, "sv_linear_fp8_wgrad: M (%d), N (%d), K (%d) must be positive, ldw (%d) >= K", M, N, K, ldw);
+  SV_REQUIRE(splits >= 0, "sv_linear_fp8_wgrad: splits (%d) must be >= 0", splits);
+  SV_REQUIRE((((uintptr_t)dyt | (uintptr_t)xt) & 15) == 0 && ((uintptr_t)dw & 3) == 0, "sv_linear_fp8_wgrad: operands are not aligned");
+  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_fp8_wgrad: too many tiles");
+  const int nk = cdiv(M, LF_BK);
+  if (splits == 0) splits = (int)((2 * 256 + tiles - 1) / tiles);   // two workgroups for each of the 256 CUs
+  splits = splits < nk ? splits : nk;
+  if (splits > 65535) splits = 65535;
+  LinFp8WgradArgs a{static_cast<const uint8_t*>(dyt), sdc, static_cast<const uint8_t*>(xt), sxc, dw, N, K, nk * LF_BK, ldw, splits};
+  hipLaunchKernelGGL(linear_fp8_wgrad_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  const int rc = check_launch("sv_linear_fp8_wgrad");
+  if (rc == SV_OK) linear_fp8_bwd_launches[1].fetch_add(1, std::memory_order_relaxed);
   return rc;
 }

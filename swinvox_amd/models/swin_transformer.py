@@ -208,12 +208,12 @@ def block_backward(blk: SwinBlock, ctx, dx2, grads):
         dbr = empty(M, Cd, like=x)
         call("sv_rowscale", ptr(dx2), ptr(sc2), ptr(dbr), M, Cd, H * W)
     # without a drop-path copy dbr IS dx2, which the LayerNorm backward below updates in place -> keep this one in order
-    ops.linear_wgrad(dbr, h, M, blk.s_fc2, grads[blk.mlp.fc2.weight], grads[blk.mlp.fc2.bias], async_ok=sc2 is not None)
+    ops.swin_linear_wgrad(dbr, h, M, blk.s_fc2, blk.mlp.fc2.weight, grads[blk.mlp.fc2.weight], grads[blk.mlp.fc2.bias], async_ok=sc2 is not None)
     dh = empty(M, 4 * Cd, like=x)
-    ops.linear_dgrad(dbr, M, blk.s_fc2, blk.s_fc2.pack_dgrad(blk.mlp.fc2.weight), dh, act_grad_src=hpre, act_grad_kind=ACT_GELU)
-    ops.linear_wgrad(dh, ln2, M, blk.s_fc1, grads[blk.mlp.fc1.weight], grads[blk.mlp.fc1.bias])
+    ops.swin_linear_dgrad(dbr, M, blk.s_fc2, blk.mlp.fc2.weight, dh, act_grad_src=hpre, act_grad_kind=ACT_GELU)
+    ops.swin_linear_wgrad(dh, ln2, M, blk.s_fc1, blk.mlp.fc1.weight, grads[blk.mlp.fc1.weight], grads[blk.mlp.fc1.bias])
     dln2 = empty(M, Cd, like=x)
-    ops.linear_dgrad(dh, M, blk.s_fc1, blk.s_fc1.pack_dgrad(blk.mlp.fc1.weight), dln2)
+    ops.swin_linear_dgrad(dh, M, blk.s_fc1, blk.mlp.fc1.weight, dln2)
     ops.layernorm_bwd(dln2, x1, blk.norm2.weight, m2, r2, dx2, grads[blk.norm2.weight], grads[blk.norm2.bias], M, Cd, accumulate_dx=True)
     dx1 = dx2
     return _attention_backward(blk, x, m1, r1, ln1, qkv, att, sc1, dx1, grads, I, H, W, Cd, M)
@@ -268,18 +268,18 @@ def _attention_backward(blk, x, m1, r1, ln1, qkv, att, sc1, dx1, grads, I, H, W,
     if sc1 is not None:
         dbr = empty(M, Cd, like=x)
         call("sv_rowscale", ptr(dx1), ptr(sc1), ptr(dbr), M, Cd, H * W)
-    ops.linear_wgrad(dbr, att, M, blk.s_proj, grads[blk.attn.proj.weight], grads[blk.attn.proj.bias], async_ok=sc1 is not None)
+    ops.swin_linear_wgrad(dbr, att, M, blk.s_proj, blk.attn.proj.weight, grads[blk.attn.proj.weight], grads[blk.attn.proj.bias], async_ok=sc1 is not None)
     datt = empty(M, Cd, like=x)
-    ops.linear_dgrad(dbr, M, blk.s_proj, blk.s_proj.pack_dgrad(blk.attn.proj.weight), datt)
+    ops.swin_linear_dgrad(dbr, M, blk.s_proj, blk.attn.proj.weight, datt)
     dqkv = empty(M, 3 * Cd, like=x)
     ws = ops.zeros_f64(8 * 169 * blk.heads, x.device)    # sv_window_attention_bwd_workspace_floats(heads) floats, zero on entry
     # backward = 2.5 x the forward products (recomputed P, dP, dQ, dK, dV); bytes: qkv + dout in, dqkv out
     ops.traced_call("sv_window_attention_bwd", 10.0 * 49 * 32 * M * blk.heads, esz * 7 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
                     ptr(datt), ptr(dqkv), ptr(grads[blk.attn.relative_position_bias_table]), ptr(ws), I, H, W, Cd, blk.heads, blk.shift,
                     ops.attention_bwd_math(), tag=f"M={M} C={Cd}")
-    ops.linear_wgrad(dqkv, ln1, M, blk.s_qkv, grads[blk.attn.qkv.weight], grads[blk.attn.qkv.bias])
+    ops.swin_linear_wgrad(dqkv, ln1, M, blk.s_qkv, blk.attn.qkv.weight, grads[blk.attn.qkv.weight], grads[blk.attn.qkv.bias])
     dln1 = empty(M, Cd, like=x)
-    ops.linear_dgrad(dqkv, M, blk.s_qkv, blk.s_qkv.pack_dgrad(blk.attn.qkv.weight), dln1)
+    ops.swin_linear_dgrad(dqkv, M, blk.s_qkv, blk.attn.qkv.weight, dln1)
     ops.layernorm_bwd(dln1, x, blk.norm1.weight, m1, r1, dx1, grads[blk.norm1.weight], grads[blk.norm1.bias], M, Cd, accumulate_dx=True)
     return dx1
 
@@ -310,9 +310,9 @@ def stage_backward(stage: SwinStage, sctx, dx, grads, I):
     if sctx["merge"] is not None:
         ds = stage.downsample
         xin, lnm, mm, rm, Mo, Hin = sctx["merge"]
-        ops.linear_wgrad(dx, lnm, Mo, ds.spec, grads[ds.reduction.weight], None)
+        ops.swin_linear_wgrad(dx, lnm, Mo, ds.spec, ds.reduction.weight, grads[ds.reduction.weight], None)
         dln = empty(Mo, 2 * stage.dim, like=dx)
-        ops.linear_dgrad(dx, Mo, ds.spec, ds.spec.pack_dgrad(ds.reduction.weight), dln)
+        ops.swin_linear_dgrad(dx, Mo, ds.spec, ds.reduction.weight, dln)
         dxin = empty(I * Hin * Hin, stage.dim // 2, like=dx)
         ops.layernorm_bwd(dln, xin, ds.norm.weight, mm, rm, dxin, grads[ds.norm.weight], grads[ds.norm.bias], Mo, 2 * stage.dim,
                           merge_hw=(Hin, Hin))

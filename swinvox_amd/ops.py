@@ -294,6 +294,7 @@ class PackCache:
     def __init__(self):
         self.tables = {}   # storage dtype -> dict(entries={key: [spec, w, kind, view]}, dirty, flat, descs, sig, nblocks)
         self.w8 = {}       # id(parameter) -> (e4m3 rows, row scales) of the running forward (quantize_weight_fp8); dropped by refresh()
+        self.w8t = {}      # id(parameter) -> (e4m3 rows of W^T, their scales) for the fp8 data gradient (quantize_weight_t_fp8); same lifetime
 
     def __deepcopy__(self, memo):
         return PackCache()    # keyed by parameter identity: a copied module starts with an empty cache
@@ -314,7 +315,7 @@ class PackCache:
 
     def refresh(self):
         """(Re)build the descriptor table when the set of packs or a parameter's address changed, then pack everything."""
-        self.w8 = {}
+        self.w8, self.w8t = {}, {}
         t = self._table()
         ents = list(t["entries"].values())
         if not ents:
@@ -551,16 +552,29 @@ def linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
     spec.forward(x, rows, (1, 1, 1), w, out, **epi)
 
 
-def set_linear_fp8(on: bool) -> None:
+def set_linear_fp8(on: bool, backward: bool = False) -> None:
     """BASELINE configuration 5, linear part: the FORWARD of the Swin linears (qkv, proj, fc1, fc2, patch-merge reduction) on e4m3 operands
-    with per-row scales and the block-scaled K = 128 MFMA (csrc/linear_fp8.hip).  The stored tensors and the backward are unchanged (bf16
-    data and weight gradients: the quantisers are straight-through).  Active only under set_math('bf16'); independent of set_attention_fp8.
+    with per-row scales and the block-scaled K = 128 MFMA (csrc/linear_fp8.hip).  The stored tensors are unchanged.  Without `backward` the
+    backward is unchanged too (bf16 data and weight gradients: the quantisers are straight-through); with backward=True (effective only
+    together with `on`) the data and weight gradients of the unfused Swin sites run on e4m3 operands as well (swin_linear_dgrad /
+    swin_linear_wgrad).  Active only under set_math('bf16'); independent of set_attention_fp8.
     Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them)."""
     _STATE["linear_fp8"] = bool(on)
+    _STATE["linear_fp8_bwd"] = bool(on) and bool(backward)
 
 
 def linear_fp8_enabled() -> bool:
     return bool(_STATE.get("linear_fp8")) and _STATE["math"] == hip.MATH_BF16
+
+
+def linear_fp8_bwd_enabled() -> bool:
+    return bool(_STATE.get("linear_fp8_bwd")) and linear_fp8_enabled()
+
+
+def linear_fp8_bwd_launches() -> Tuple[int, int]:
+    """(sv_linear_fp8_dgrad, sv_linear_fp8_wgrad) launches of this process so far; linear_fp8_launches() counts neither."""
+    lib = hip.load()
+    return int(lib.sv_linear_fp8_bwd_launches(0)), int(lib.sv_linear_fp8_bwd_launches(1))
 
 
 def linear_fp8_launches() -> int:
@@ -601,6 +615,74 @@ def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
                         ptr(xq), ptr(sx), ptr(wq), ptr(sw), ptr(out), rows, spec.cin, spec.cout, C.byref(e), tag=f"M={rows} K={spec.cin} N={spec.cout}")
             return
     linear_fwd(x, rows, spec, w, out, **epi)
+
+
+def quantize_cols_fp8(t: torch.Tensor, rows: int, Cc: int, ld: Optional[int] = None, colsum: Optional[torch.Tensor] = None):
+    """t [rows, Cc] (fp32 or bf16, row stride ld) -> (e4m3 bytes of the TRANSPOSE [Cc, roundup(rows, 128)], fp32 column scales [Cc]) by
+    sv_quant_cols_e4m3; colsum (fp32 [Cc]) += the column sums of the unquantised values."""
+    Mp = (rows + 127) // 128 * 128
+    q = torch.empty(Cc, Mp, dtype=torch.uint8, device=t.device)
+    sc = torch.empty(Cc, dtype=torch.float32, device=t.device)
+    call("sv_quant_cols_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, Cc, ld or Cc, ptr(q), Mp, ptr(sc), ptr(colsum))
+    return q, sc
+
+
+def quantize_weight_t_fp8(w: torch.Tensor):
+    """Quantised rows of W^T for a Linear weight W [N, K] (one scale per column k of W): the operand of the fp8 data gradient, cached next to
+    quantize_weight_fp8's rows with the same lifetime."""
+    cache = _CTX.packs
+    if cache is None or not isinstance(w, torch.nn.Parameter):
+        return quantize_cols_fp8(w, w.shape[0], w.shape[1])
+    hit = cache.w8t.get(id(w))
+    if hit is None:
+        hit = cache.w8t[id(w)] = quantize_cols_fp8(w, w.shape[0], w.shape[1])
+    return hit
+
+
+def _fp8_bwd_site(spec: ConvSpec, w) -> bool:
+    return (linear_fp8_bwd_enabled() and spec.taps == 1 and spec.cin_mem == spec.cin and spec.cout_mem == spec.cout
+            and isinstance(w, torch.nn.Parameter))
+
+
+def swin_linear_dgrad(dy, rows, spec: ConvSpec, w, dx, **epi):
+    """linear_dgrad of the unfused Swin call sites (w is the PARAMETER): with set_linear_fp8(True, backward=True) (and a form
+    sv_linear_fp8_dgrad serves) dy is quantised per row, the quantised W^T fetched and the product runs on the fp8 kernel; otherwise exactly
+    linear_dgrad on the data-gradient weight pack."""
+    if _fp8_bwd_site(spec, w):
+        e = _epilogue(spec.cin, **epi)
+        if hip.load().sv_linear_fp8_dgrad_supported(spec.cout, spec.cin, C.byref(e), _STATE["math"], hip.ACT) == 1:
+            dq, sd = quantize_rows_fp8(dy, rows, spec.cout)
+            wtq, swt = quantize_weight_t_fp8(w)
+            traced_call("sv_linear_fp8_dgrad", 2.0 * rows * spec.cin * spec.cout, float(rows) * (dq.shape[1] + dy.element_size() * spec.cin) + wtq.numel(),
+                        ptr(dq), ptr(sd), ptr(wtq), ptr(swt), ptr(dx), rows, spec.cout, spec.cin, C.byref(e), tag=f"M={rows} N={spec.cout} K={spec.cin}")
+            return
+    linear_dgrad(dy, rows, spec, spec.pack_dgrad(w), dx, **epi)
+
+
+def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True):
+    """linear_wgrad of the unfused Swin call sites (w is the PARAMETER dw belongs to): with set_linear_fp8(True, backward=True) dy and x are
+    quantised per column into transposed e4m3 copies (db from the unquantised dy in the same pass) and the product over the tokens runs on
+    the fp8 kernel; otherwise exactly linear_wgrad.  The whole sequence follows linear_wgrad's stream rule: on the weight-gradient stream
+    (temporaries allocated inside that stream context) unless async_ok is False, in which case it stays in order on the caller's stream (the
+    quantised copies are complete before the caller overwrites dy).  The transposed copies, rows x (N + K) bytes, are freed on return either
+    way; only dy and x are held until the join."""
+    if not _fp8_bwd_site(spec, w):
+        return linear_wgrad(dy, x, rows, spec, dw, db, async_ok=async_ok)
+
+    def run():
+        dyt, sdc = quantize_cols_fp8(dy, rows, spec.cout, colsum=db)
+        xt, sxc = quantize_cols_fp8(x, rows, spec.cin)
+        traced_call("sv_linear_fp8_wgrad", 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout,
+                    ptr(dyt), ptr(sdc), ptr(xt), ptr(sxc), ptr(dw), rows, spec.cout, spec.cin, spec.cin, 0, tag=f"M={rows} N={spec.cout} K={spec.cin}")
+
+    aw = _CTX.awg
+    if aw is not None and async_ok:
+        aw.stream.wait_stream(torch.cuda.current_stream())     # dy and x are complete on the producing stream
+        aw.held.append((dy, x))                                # the operands stay alive (and unrecycled) until the join
+        with torch.cuda.stream(aw.stream):
+            run()      # the temporaries are allocated on the weight-gradient stream and dropped here: its allocator recycles them in stream order
+        return
+    run()
 
 
 def linear_dgrad(dy, rows, spec: ConvSpec, w_t, dx, **epi):
