@@ -285,6 +285,12 @@ int sv_window_attention_fwd(const void* qkv, const float* table, void* out, int 
 size_t sv_window_attention_bwd_workspace_floats(int heads);
 int sv_window_attention_bwd(const void* qkv, const float* table, const void* dout, void* dqkv, float* dtable, float* workspace,
                             int I, int H, int W, int C, int heads, int shift, int math, int act_dtype, void* stream);
+/* Consecutive windows one workgroup (bf16 / fp8 kernels) or one wave (exact-fp32 kernels) walks in the launch sv_window_attention_fwd
+ * (backward = 0) / _bwd (backward = 1) makes for these arguments (call site models/swin_transformer.py:78); 1 for the fp32 forward.  A
+ * pure host function - the launches take their share from the same place - for tests that mean to run a kernel at several windows per
+ * workgroup.  Negative SV_ERR_* for a geometry the entry points refuse, for I or heads < 1, and - the query's own rule - for a math
+ * code that is none of SV_MATH_F32 / _BF16 / _FP8 / _FP8_FULL. */
+int sv_window_attention_windows_per_group(int I, int H, int W, int heads, int math, int backward);
 int sv_cross_view_attention_fwd(const void* qkv, void* out, int B, int V, int P, int R, int heads, int act_dtype, void* stream);
 int sv_cross_view_attention_bwd(const void* qkv, const void* dout, void* dqkv, int B, int V, int P, int R, int heads,
                                 int act_dtype, void* stream);
@@ -359,6 +365,10 @@ int sv_swin_attn_block_supported(int C, int heads, int act_dtype, int math);
 int sv_swin_attn_block_fwd(const void* x, const float* ln_g, const float* ln_b, const float* wqkv, const float* bqkv, const float* table,
                            const float* wproj, const float* bproj, const float* row_scale, void* x1, void* ln1, float* mean, float* rstd,
                            void* qkv, void* att, int I, int H, int W, int C, int heads, int shift, float eps, int act_dtype, void* stream);
+/* Consecutive windows per window group (two groups per forward workgroup, one per backward workgroup) of the launch sv_swin_attn_block_fwd
+ * (backward = 0) / _bwd (backward = 1) makes for these arguments (call site models/swin_transformer.py:78); pure host function, negative
+ * SV_ERR_* for a geometry the entry points refuse. */
+int sv_swin_attn_block_windows_per_group(int I, int H, int W, int backward);
 /* Fused BACKWARD of the same branch (data path): reads dx1 [M,96], the qkv rows and LayerNorm statistics the forward stored, and x; writes
  * dqkv [M,288] (the engine's weight-gradient kernels read it: d qkv.weight / bias from (dqkv, ln1), d proj.weight / bias from (s dx1, att)) and
  * dx = dx1 + LayerNormBackward(dqkv Wqkv) [M,96]; accumulates into dgamma / dbeta of norm1 [96] and dtable [169,3].  dbr (optional) receives

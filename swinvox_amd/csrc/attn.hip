@@ -1878,15 +1878,32 @@ static void launch_dtable_fold(float* workspace, float* dtable, int heads, hipSt
   hipLaunchKernelGGL(attn_dtable_fold_kernel, dim3(cdiv(169 * heads, 256)), dim3(256), 0, s, workspace, dtable, 169 * heads);
 }
 
-// The four workgroup-per-window kernels: a workgroup walks tpb windows of one head.
-//  * forward: >= ~2048 short workgroups (the forward task is brief, oversubscribing the CUs balances better than one exact wave - measured);
-//  * backward: one resident wave of workgroups, 3 per CU; the bias-table gradient goes to the slot images of `workspace` (folded into
-//    dtable by a second launch) or, without a workspace, straight to dtable.
-static void launch_win_wg(bool bwd, bool fp8, int act_dtype, const WinCall& c, float* workspace, hipStream_t s) {
+// Consecutive windows of one head per workgroup (per wave in the exact-fp32 kernels) of the launch for these arguments: the launches below
+// and sv_window_attention_windows_per_group both take it from here.
+//  * bf16 / fp8 forward: >= ~2048 short workgroups (the forward task is brief, oversubscribing the CUs balances better than one exact wave
+//    - measured);
+//  * bf16 / fp8 backward: one resident wave of workgroups, 3 per CU;
+//  * exact fp32: wave per window; the backward walks several windows per wave so the bias gradient is reduced on chip.
+static int win_share(int ntasks, int heads, int math, bool bwd) {
+  if (math == SV_MATH_BF16 || math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL) {
+    if (bwd) return wg_tasks_per_block(ntasks, heads, 3);
+    int tpb = (int)((long long)ntasks * heads / 2048);
+    if (tpb < 1) tpb = 1;
+    if (tpb > 8) tpb = 8;
+    return tpb;
+  }
+  int tpw = 1;
+  while (bwd && tpw < 8 && (long long)ntasks * heads / (tpw * 2) > 2048) tpw *= 2;
+  return tpw;
+}
+// Fused stage-0 block, windows per window group.  Forward: one workgroup (two window groups) per CU, every group the same share;
+// backward: one workgroup (one group) per CU, every workgroup the same share of consecutive windows.
+static int block_share(int ntasks, bool bwd) { return cdiv(ntasks, bwd ? 256 : 512); }
+
+// The four workgroup-per-window kernels: a workgroup walks tpb windows of one head.  Backward: the bias-table gradient goes to the slot
+// images of `workspace` (folded into dtable by a second launch) or, without a workspace, straight to dtable.
+static void launch_win_wg(bool bwd, bool fp8, int act_dtype, const WinCall& c, int tpb, float* workspace, hipStream_t s) {
   const int ntasks = c.ntasks();
-  int tpb;
-  if (bwd) tpb = wg_tasks_per_block(ntasks, c.heads, 3);
-  else { tpb = (int)((long long)ntasks * c.heads / 2048); if (tpb < 1) tpb = 1; if (tpb > 8) tpb = 8; }
   const dim3 grid(wg_grid(cdiv(ntasks, tpb), c.heads));
   SV_DISPATCH_ACT(act_dtype,
     const WinArgsT<AT> a = win_args<AT>(c, tpb);
@@ -1904,10 +1921,19 @@ extern "C" int sv_window_attention_fwd(const void* qkv, const float* table, void
   const WinCall c{qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift};
   hipStream_t s = (hipStream_t)stream;
   const bool fp8 = math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL;   // e4m3 operands for QK^T and PV (the backward of SV_MATH_FP8 is bf16)
-  if (fp8 || math == SV_MATH_BF16) launch_win_wg(false, fp8, act_dtype, c, nullptr, s);
+  const int share = win_share(c.ntasks(), heads, math, false);
+  if (fp8 || math == SV_MATH_BF16) launch_win_wg(false, fp8, act_dtype, c, share, nullptr, s);
   else   // exact-fp32 MFMA: wave per window
-    hipLaunchKernelGGL(win_attn_fwd_kernel, dim3(cdiv(c.ntasks(), 4), heads), dim3(256), 0, s, win_args<float>(c, 1));
+    hipLaunchKernelGGL(win_attn_fwd_kernel, dim3(cdiv(c.ntasks(), 4), heads), dim3(256), 0, s, win_args<float>(c, share));
   return check_launch("sv_window_attention_fwd");
+}
+
+extern "C" int sv_window_attention_windows_per_group(int I, int H, int W, int heads, int math, int backward) {
+  SV_REQUIRE(I > 0 && heads > 0, "window_attention_windows_per_group: I (%d) and heads (%d) must be positive", I, heads);
+  SV_REQUIRE(math == SV_MATH_F32 || math == SV_MATH_BF16 || math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL,
+             "window_attention_windows_per_group: unknown math mode %d", math);
+  if (int rc = win_geom_check("window_attention_windows_per_group", H, W, 0)) return rc;
+  return win_share(I * (H / 7) * (W / 7), heads, math, backward != 0);
 }
 
 extern "C" size_t sv_window_attention_bwd_workspace_floats(int heads) { return (size_t)ATTN_DT_SLOTS * 169 * heads; }
@@ -1918,13 +1944,13 @@ extern "C" int sv_window_attention_bwd(const void* qkv, const float* table, cons
   SV_REQUIRE(dout && dqkv && dtable && ((uintptr_t)dout & 15) == 0, "window_attention_bwd: null/unaligned argument");
   const WinCall c{qkv, table, nullptr, dout, dqkv, dtable, I, H, W, C, heads, shift};
   hipStream_t s = (hipStream_t)stream;
+  const int share = win_share(c.ntasks(), heads, math, true);
   if (math == SV_MATH_BF16 || math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL) {
     // SV_MATH_FP8_FULL: e4m3 operands for all five contractions, the gradient of the SV_MATH_FP8 forward; SV_MATH_FP8: the bf16 backward
-    launch_win_wg(true, math == SV_MATH_FP8_FULL, act_dtype, c, workspace, s);
+    launch_win_wg(true, math == SV_MATH_FP8_FULL, act_dtype, c, share, workspace, s);
   } else {
     // exact-fp32 MFMA: wave per window, several windows per wave (same head) so the bias gradient is reduced on chip
-    int tpw = 1;
-    while (tpw < 8 && (long long)c.ntasks() * heads / (tpw * 2) > 2048) tpw *= 2;
+    const int tpw = share;
     hipLaunchKernelGGL(win_attn_bwd_kernel, dim3(cdiv(c.ntasks(), 2 * tpw), heads), dim3(128), 0, s, win_args<float>(c, tpw));
   }
   return check_launch("sv_window_attention_bwd");
@@ -1984,10 +2010,16 @@ extern "C" int sv_swin_attn_block_fwd(const void* x, const float* ln_g, const fl
   a.att = static_cast<__bf16*>(att); a.mean = mean; a.rstd = rstd;
   a.I = I; a.H = H; a.W = W; a.shift = shift; a.eps = eps; a.scale = 1.0f / sqrtf((float)HD);
   a.ntasks = I * (H / 7) * (W / 7);
-  a.tasks_per_group = cdiv(a.ntasks, 512);                  // one workgroup (two window groups) per CU, every group the same share
+  a.tasks_per_group = block_share(a.ntasks, false);
   const int nblocks = cdiv(a.ntasks, 2 * a.tasks_per_group);
   hipLaunchKernelGGL(swin_attn_block_fwd_kernel, dim3(nblocks), dim3(512), 0, (hipStream_t)stream, a);
   return check_launch("sv_swin_attn_block_fwd");
+}
+
+extern "C" int sv_swin_attn_block_windows_per_group(int I, int H, int W, int backward) {
+  SV_REQUIRE(I > 0, "swin_attn_block_windows_per_group: I (%d) must be positive", I);
+  if (int rc = win_geom_check("swin_attn_block_windows_per_group", H, W, 0)) return rc;
+  return block_share(I * (H / 7) * (W / 7), backward != 0);
 }
 
 /* Fused backward of the attention branch of a stage-0 block (see swin_attn_block_bwd_kernel).  dgamma / dbeta / dtable are accumulated into;
@@ -2010,7 +2042,7 @@ extern "C" int sv_swin_attn_block_bwd(const void* dx1, const void* qkv, const vo
   a.dgamma = dgamma; a.dbeta = dbeta; a.dt_ws = workspace;
   a.I = I; a.H = H; a.W = W; a.shift = shift; a.scale = 1.0f / sqrtf((float)HD);
   a.ntasks = I * (H / 7) * (W / 7);
-  a.tasks_per_group = cdiv(a.ntasks, 256);                  // one workgroup per CU, every workgroup the same share of consecutive windows
+  a.tasks_per_group = block_share(a.ntasks, true);
   const int nblocks = cdiv(a.ntasks, a.tasks_per_group);
   hipLaunchKernelGGL(swin_attn_block_bwd_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, a);
   launch_dtable_fold(workspace, dtable, heads, (hipStream_t)stream);

@@ -100,6 +100,7 @@ _PROTOS = {
     "sv_bn_bwd_signs": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _L, _I, _I, _F, _I, _P, _I, _P, _I, _P, _P, _P]),
     "sv_window_attention_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "sv_window_attention_bwd_workspace_floats": (C.c_size_t, None, [_I]),
+    "sv_window_attention_windows_per_group": (_I, None, [_I, _I, _I, _I, _I, _I]),
     "sv_window_attention_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "sv_stem_space_to_depth": (_I, [_P, _P, _I]),
     "sv_bn_act_maxpool_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F]),
@@ -124,6 +125,7 @@ _PROTOS = {
     "sv_swin_mlp_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _I, _F]),
     "sv_swin_mlp_wgrad": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _I, _F]),
     "sv_swin_attn_block_supported": (_I, None, [_I, _I, _I, _I]),
+    "sv_swin_attn_block_windows_per_group": (_I, None, [_I, _I, _I, _I]),
     "sv_swin_attn_block_fwd": (_I, [_P] * 15 + [_I, _I, _I, _I, _I, _I, _F]),
     "sv_swin_attn_block_bwd": (_I, [_P] * 17 + [_I, _I, _I, _I, _I, _I]),
     "sv_cross_view_attention_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I]),

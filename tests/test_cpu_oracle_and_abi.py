@@ -224,6 +224,21 @@ def test_ctypes_prototypes_match_the_header():
     assert lib.sv_pack_weights_block_elems() > 0 and ctypes.sizeof(hip.PackDesc) == 48
 
 
+def test_windows_per_group_queries():
+    """sv_window_attention_windows_per_group / sv_swin_attn_block_windows_per_group are pure host functions: share 1 for a handful of
+    windows and for every exact-fp32 forward, a share above 1 at the benchmark's stage-0 shape, a negative code for what the entry
+    points refuse."""
+    lib = hip.load()
+    q, b = lib.sv_window_attention_windows_per_group, lib.sv_swin_attn_block_windows_per_group
+    for math in (hip.MATH_F32, hip.MATH_BF16, hip.MATH_FP8, hip.MATH_FP8_FULL):
+        assert q(2, 14, 14, 3, math, 0) == 1 and q(2, 14, 14, 3, math, 1) == 1
+        assert (q(512, 56, 56, 3, math, 0) > 1) == (math != hip.MATH_F32) and q(512, 56, 56, 3, math, 1) > 1
+    assert q(2, 20, 21, 3, hip.MATH_BF16, 0) == -1 and q(0, 21, 21, 3, hip.MATH_BF16, 0) == -1
+    assert q(2, 21, 21, 0, hip.MATH_BF16, 1) == -1 and q(2, 21, 21, 3, 9, 0) == -1
+    assert b(2, 14, 14, 0) == 1 and b(2, 14, 14, 1) == 1 and b(512, 56, 56, 0) > 1 and b(512, 56, 56, 1) > 1
+    assert b(2, 15, 14, 0) == -1 and b(0, 14, 14, 1) == -1
+
+
 def test_product_fails_loudly_without_gpu_or_library(monkeypatch):
     m = Refiner(S.default_cfg())
     with pytest.raises(RuntimeError, match="GPU"):

@@ -90,13 +90,42 @@ def _unfused(d, I, H, shift, scd):
     return {"x1": x1, "ln1": ln1, "qkv": qkv, "att": att, "mean": m1, "rstd": r1}
 
 
+# (I, H) of the cases that run the kernels at several windows per window group (sv_swin_attn_block_windows_per_group >= 2): the window loop,
+# its prefetch and the sums carried across windows exist only there.  (58, 21): 522 windows - the forward's last workgroup has an empty
+# second group; (9, 56): 576 windows.
+SEVERAL_WINDOWS = {(9, 56), (58, 21)}
+
+
+def _share(I, H, backward):
+    s = hip.load().sv_swin_attn_block_windows_per_group(I, H, H, int(backward))
+    assert s >= 1, (s, I, H, backward)
+    return s
+
+
+def _image_slices(I, H, backward):
+    """consecutive image ranges (i0, n), each as long as the kernel still runs it at one window per group"""
+    n = next(n for n in range(I, 0, -1) if _share(n, H, backward) == 1)
+    parts = [(i0, min(n, I - i0)) for i0 in range(0, I, n)]
+    assert len(parts) >= 2 and all(_share(m, H, backward) == 1 for _, m in parts), parts
+    return parts
+
+
+def _rows(t, H, i0, n):
+    return None if t is None else t[i0 * H * H:(i0 + n) * H * H]
+
+
 def _rel(a, b):
     a, b = a.detach().float().cpu().double(), b.detach().float().cpu().double()
     return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
-@pytest.mark.parametrize("I,H,shift,with_scale", [(2, 14, 0, False), (3, 14, 3, True), (1, 28, 3, False), (5, 7, 0, True), (40, 14, 3, True)])
+@pytest.mark.parametrize("I,H,shift,with_scale", [(2, 14, 0, False), (3, 14, 3, True), (1, 28, 3, False), (5, 7, 0, True), (40, 14, 3, True),
+                                                   (9, 56, 3, True), (58, 21, 3, True)])
 def test_fused_attention_branch_matches_torch_and_the_unfused_chain(dev, I, H, shift, with_scale):
+    share, windows = _share(I, H, False), I * (H // 7) ** 2
+    assert (share >= 2) == ((I, H) in SEVERAL_WINDOWS), (share, I, H)
+    if (I, H) == (58, 21):
+        assert 0 < windows % (2 * share) <= share            # the second window group of the last workgroup has nothing to do
     assert hip.load().sv_swin_attn_block_supported(C, HEADS, hip.BF16, hip.MATH_BF16) == 1
     assert hip.load().sv_swin_attn_block_supported(192, 6, hip.BF16, hip.MATH_BF16) == 0
     p = _case(I, H, 7 * I + H + shift)
@@ -111,6 +140,13 @@ def test_fused_attention_branch_matches_torch_and_the_unfused_chain(dev, I, H, s
     # the inference form (no side outputs) is the same arithmetic
     lean = _fused(d, I, H, shift, scd, side=False)
     assert torch.equal(lean["x1"], got["x1"])
+    if share >= 2:
+        # the same images at one window per group, bit for bit: a window's rows are written by one group and must not depend on the
+        # iteration of the window loop that computed them
+        for i0, n in _image_slices(I, H, False):
+            one = _fused(dict(d, x=_rows(d["x"], H, i0, n)), n, H, shift, scd[i0:i0 + n] if scd is not None else None, side=True)
+            for k in ("x1", "qkv", "att", "ln1"):
+                assert torch.equal(_rows(got[k], H, i0, n), one[k]), (k, i0, n)
     # (b) against the unfused chain in bf16 math + bf16 storage: every tensor the backward reads
     ops.set_math("bf16")
     ops.set_storage("bf16")
@@ -193,11 +229,14 @@ def _unfused_bwd(d, fw, dx1, I, H, shift, scd):
     return {"dx": dx, "dqkv": dqkv, "dgamma": dg, "dbeta": db, "dtable": dt}
 
 
-@pytest.mark.parametrize("I,H,shift,with_scale", [(2, 14, 0, False), (3, 14, 3, True), (1, 28, 3, False), (5, 7, 0, True), (40, 14, 3, True), (9, 56, 3, True)])
+@pytest.mark.parametrize("I,H,shift,with_scale", [(2, 14, 0, False), (3, 14, 3, True), (1, 28, 3, False), (5, 7, 0, True), (40, 14, 3, True), (9, 56, 3, True),
+                                                   (58, 21, 3, True)])
 def test_fused_attention_branch_backward(dev, I, H, shift, with_scale):
     """sv_swin_attn_block_bwd (dx1 -> projection data gradient -> attention backward -> qkv data gradient -> LayerNorm backward + residual in
     one kernel) against (a) fp64 autograd of the branch and (b) the unfused four-kernel chain on the same stored tensors: dx, dqkv, the
     LayerNorm parameter gradients and the bias-table gradient."""
+    share = _share(I, H, True)
+    assert (share >= 2) == ((I, H) in SEVERAL_WINDOWS), (share, I, H)
     p = _case(I, H, 11 * I + H + shift)
     sc = torch.tensor([0.0 if i % 3 == 1 else 1.0 / 0.9 for i in range(I)]) if with_scale else None
     g = torch.Generator().manual_seed(I + H)
@@ -213,6 +252,13 @@ def test_fused_attention_branch_backward(dev, I, H, shift, with_scale):
         assert _rel(got[k], ref[k]) < tol, (k, _rel(got[k], ref[k]))
     if scd is not None:
         assert torch.equal(got["dbr"].float(), (dx1.float() * scd.repeat_interleave(H * H)[:, None]).to(torch.bfloat16).float())
+    if share >= 2:
+        # the same images at one window per workgroup, bit for bit (dqkv and dx rows are written by one workgroup, no atomics)
+        for i0, n in _image_slices(I, H, True):
+            fw1 = {k: _rows(fw[k], H, i0, n) for k in ("qkv", "mean", "rstd")}
+            one = _fused_bwd(dict(d, x=_rows(d["x"], H, i0, n)), fw1, _rows(dx1, H, i0, n), n, H, shift, scd[i0:i0 + n] if scd is not None else None)
+            for k in ("dqkv", "dx"):
+                assert torch.equal(_rows(got[k], H, i0, n), one[k]), (k, i0, n)
     # (b) the unfused chain in bf16 math + bf16 storage
     ops.set_math("bf16")
     ops.set_storage("bf16")
