@@ -211,6 +211,15 @@ int sv_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long long 
  * ---------------------------------------------------------------------------------------------- */
 int sv_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                      long long rows, int C, float eps, int merge_H, int merge_W, int act_dtype, void* stream);
+/* sv_layernorm_fwd that also emits the operand rows sv_linear_fp8 reads (timm LayerNorm -> Linear behind
+ * models/swin_transformer.py:78): q [rows, Kp] e4m3 bytes (16-byte aligned), Kp = roundup(C, 128), zeros past C; scales [rows] =
+ * sv_quant_rows_e4m3's scale of the STORED row (the row rounded to act_dtype first), so q and scales equal that quantiser's output on y
+ * bit for bit.  y may be NULL (the rows are then not stored: inference); mean and rstd may be NULL together.  Refused with SV_ERR_INVALID:
+ * what sv_layernorm_fwd refuses, q or scales NULL, Kp != roundup(C, 128), exactly one of mean / rstd NULL. */
+int sv_layernorm_quant_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                           void* q, int Kp, float* scales, long long rows, int C, float eps, int merge_H, int merge_W,
+                           int act_dtype, void* stream);
+long long sv_layernorm_quant_launches(void); /* sv_layernorm_quant_fwd launches so far in this process (timm LayerNorm -> Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise) */
 /* workspace: sv_layernorm_bwd_workspace_floats(C) floats, ZERO on entry (slot-spread dgamma/dbeta partial sums + ticket) */
 size_t sv_layernorm_bwd_workspace_floats(int C);
 int sv_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,

@@ -133,6 +133,17 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- fp8 (OCP e4m3fn) row recipe of the Swin linears (linear_fp8.hip; producers: its row / column quantisers and norm.hip's quantising
+// LayerNorm): scale = amax > 0 ? min(FP8_ROW_TARGET / amax, FP8_SCALE_MAX) : 1 in fp32 (IEEE division), bytes = e4m3_rne(value * scale)
+constexpr float FP8_ROW_TARGET = 224.f;                    // half of e4m3's 448, as the attention recipe
+constexpr float FP8_SCALE_MAX = 1152921504606846976.f;     // 2^60
+__device__ __forceinline__ float fp8_row_scale(float amax) { return amax > 0.f ? fminf(FP8_ROW_TARGET / amax, FP8_SCALE_MAX) : 1.f; }
+__device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float d) {   // v_cvt_pk_fp8_f32: round to nearest even; a = byte 0
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  return (uint32_t)w;
+}
+
 // block-wide sum over 256 threads (4 waves); scratch must hold >= 4 floats; all threads get the result
 template <int NW>
 __device__ __forceinline__ float block_sum(float v, float* scratch) {

@@ -17,6 +17,9 @@
 // Kernels
 //   quant_rows_kernel   one wave per row: amax by a DPP / permlane reduction (wave_max), then Kp bytes and one fp32 scale.  The row is read twice
 //                       (the second time from cache); activations (bf16 / fp32) and weights (fp32) take the same kernel.
+//                       SECOND PRODUCER of these operand rows: ln_fwd_kernel with its LnQuantOut argument (norm.hip, sv_layernorm_quant_fwd) writes the same bytes and
+//                       scales for the rows a token LayerNorm stores (norm1 -> qkv, norm2 -> fc1, patch-merge norm -> reduction), from the
+//                       registers that hold the normalised row; att -> proj and h -> fc2 keep this kernel.
 //   linear_fp8_kernel   128 x 128 output tile per 256-thread workgroup, 4 waves as 2 x 2, a wave owns 64 x 64 = 4 x 4 MFMA blocks (64 accumulator
 //                       registers).  One k-step = 128 bytes of every row = ONE MFMA deep: 16 KB per operand tile, staged through registers
 //                       (16-byte global loads of the next step are in flight while the current step's 16 MFMAs per wave run) into two LDS
@@ -61,17 +64,10 @@
 
 namespace sv {
 
-constexpr float FP8_ROW_TARGET = 224.f;                    // half of e4m3's 448, as the attention recipe
-constexpr float FP8_SCALE_MAX = 1152921504606846976.f;     // 2^60
+// FP8_ROW_TARGET, FP8_SCALE_MAX, fp8_row_scale and pack4_e4m3 live in common.h: the quantising LayerNorm (norm.hip) forms the same rows.
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (uint32_t)w;
-}
 
 // ---- row quantiser -------------------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -96,7 +92,7 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const T* __restrict__ s
     m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(m, fmaxf(fabsf(v[2]), fabsf(v[3]))));
   }
   m = wave_max(m);
-  const float s = m > 0.f ? fminf(FP8_ROW_TARGET / m, FP8_SCALE_MAX) : 1.f;
+  const float s = fp8_row_scale(m);
   uint32_t* out = reinterpret_cast<uint32_t*>(dst + (size_t)r * Kp);
   for (int k = lane * 4; k < Kp; k += 256) {
     float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -431,7 +427,7 @@ __global__ void quant_cols_scale_kernel(float* __restrict__ scales, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) {
     const float m = scales[c];
-    scales[c] = m > 0.f ? fminf(FP8_ROW_TARGET / m, FP8_SCALE_MAX) : 1.f;
+    scales[c] = fp8_row_scale(m);
   }
 }
 

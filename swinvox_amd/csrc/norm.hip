@@ -1,6 +1,7 @@
 // Normalisation kernels (HBM-bound): token LayerNorm (+ fused PatchMerging gather), whole-image
 // LayerNorm([C,H,W]) of the Swin stage heads, BatchNorm statistics / apply / backward on channels-last data.
 #include "common.h"
+#include <atomic>
 #include <stdlib.h>
 
 namespace sv {
@@ -10,6 +11,9 @@ namespace sv {
 // (two-pass variance), so a wave normalises 64/LPR rows at once and narrow rows (C = 96 ... 384) keep 75 % of the lanes
 // busy; VEC = 8 (16-byte accesses) with bf16 storage, 4 otherwise.
 // MERGE: the row is the PatchMerging gather of 4 tokens (order h0w0,h1w0,h0w1,h1w1) of a [I,H,W,C0] map.
+// QUANT (sv_layernorm_quant_fwd): the lane group also emits the operand row sv_linear_fp8 reads - the e4m3 bytes and the scale of the row AS
+// STORED (rounded to the storage type first), by the recipe of linear_fp8.hip: one more lane-group reduction (the maximum) and one more
+// store per chunk, no second kernel and no second read.  y / mean / rstd are then optional (inference stores only the bytes).
 // ------------------------------------------------------------------------------------------------
 // Contention-free reductions across workgroups: partial sums go (atomically) into one of NSLOT accumulator images chosen by
 // the workgroup index and a tiny second kernel folds the images.  (A "last workgroup folds" ticket would need a device-scope
@@ -64,11 +68,26 @@ __device__ __forceinline__ float group_sum(float v) {   // sum over the LPR (16 
   return v;
 }
 
-template <bool MERGE, typename AT, int VEC, int LPR, int NV>
+template <int LPR>
+__device__ __forceinline__ float group_max(float v) {   // maximum over the same lanes (values >= 0: the DPP moves read 0 where they have no source)
+  v = fmaxf(v, ln_dpp_mov<0xB1>(v)); v = fmaxf(v, ln_dpp_mov<0x4E>(v)); v = fmaxf(v, ln_dpp_mov<0x141>(v)); v = fmaxf(v, ln_dpp_mov<0x140>(v));
+  if constexpr (LPR > 16) { float w = v; permlane16_pair(v, w); v = fmaxf(v, w); }
+  if constexpr (LPR > 32) { float w = v; permlane32_pair(v, w); v = fmaxf(v, w); }
+  return v;
+}
+
+// the outputs only the quantising form has
+struct LnQuantOut { uint8_t* q; float* scales; int Kp; };   // q [rows][Kp] e4m3 bytes, scales [rows]
+__device__ __forceinline__ const LnQuantOut& ln_quant_out(const LnQuantOut& o) { return o; }
+
+// QO is empty (the plain forward: y, mean_out, rstd_out required; its argument list, and with it its code, is what it was before the
+// quantising form existed) or one LnQuantOut (QUANT: q and scales are written as well, and y / (mean_out, rstd_out) are skipped when null).
+template <bool MERGE, typename AT, int VEC, int LPR, int NV, typename... QO>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const AT* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, AT* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     long long rows, int C, float eps, MergeMap mm) {
+                                                     long long rows, int C, float eps, MergeMap mm, QO... qo_) {
+  constexpr bool QUANT = sizeof...(QO) == 1;
   constexpr int RPW = 64 / LPR;                       // rows per wave
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gl = lane % LPR, gr = lane / LPR;
@@ -88,17 +107,18 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const AT* __restrict__ x, c
   }
   const float invC = 1.f / C;                                   // one division per thread, not two per row
   const float mean = group_sum<LPR>(s) * invC;
-  float q = 0.f;
+  float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int ch = gl + LPR * i;
     if (rok && ch < nchunk) {
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) { const float a = v[i][j] - mean; q += a * a; }
+      for (int j = 0; j < VEC; ++j) { const float a = v[i][j] - mean; sq += a * a; }
     }
   }
-  const float rstd = rsqrtf(group_sum<LPR>(q) * invC + eps);
-  if (rok && gl == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+  const float rstd = rsqrtf(group_sum<LPR>(sq) * invC + eps);
+  if (rok && gl == 0 && (!QUANT || mean_out)) { mean_out[row] = mean; rstd_out[row] = rstd; }
+  float amax = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int ch = gl + LPR * i;
@@ -107,7 +127,39 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const AT* __restrict__ x, c
       ldp(gamma + ch * VEC, g, VEC); ldp(beta + ch * VEC, b, VEC);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
-      LnIO<VEC, AT>::store(y + (size_t)row * C + ch * VEC, o);
+      if constexpr (QUANT) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {   // the STORED value takes the place of x in the registers: it is what the quantiser of the row sees
+          o[j] = (float)(AT)o[j]; v[i][j] = o[j];
+          amax = fmaxf(amax, fabsf(o[j]));
+        }
+        if (y) LnIO<VEC, AT>::store(y + (size_t)row * C + ch * VEC, o);
+      } else {
+        LnIO<VEC, AT>::store(y + (size_t)row * C + ch * VEC, o);
+      }
+    }
+  }
+  if constexpr (QUANT) {
+    const float sc = fp8_row_scale(group_max<LPR>(amax));
+    const LnQuantOut& qo = ln_quant_out(qo_...);
+    if (rok) {
+      uint8_t* __restrict__ qrow = qo.q + (size_t)row * qo.Kp;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int ch = gl + LPR * i;
+        if (ch < nchunk) {   // element k of the row is byte k: VEC bytes per chunk
+          const uint32_t lo = pack4_e4m3(v[i][0] * sc, v[i][1] * sc, v[i][2] * sc, v[i][3] * sc);
+          if constexpr (VEC == 8) {
+            const uint32_t hi = pack4_e4m3(v[i][4] * sc, v[i][5] * sc, v[i][6] * sc, v[i][7] * sc);
+            *reinterpret_cast<uint2*>(qrow + ch * 8) = make_uint2(lo, hi);
+          } else {
+            *reinterpret_cast<uint32_t*>(qrow + ch * 4) = lo;
+          }
+        }
+      }
+      // zero bytes C .. Kp - 1 (C % 4 == 0: whole words; up to 31 of them, the group's registers need not reach Kp)
+      for (int w = (C >> 2) + gl; w < (qo.Kp >> 2); w += LPR) reinterpret_cast<uint32_t*>(qrow)[w] = 0u;
+      if (gl == 0) qo.scales[row] = sc;
     }
   }
 }
@@ -1191,6 +1243,16 @@ static void ln_fwd_launch(const void* x, const float* gamma, const float* beta, 
                                              static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm););
 }
 template <bool MERGE, typename AT, int VEC>
+static void ln_quant_fwd_launch(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* q, int Kp,
+                                float* scales, long long rows, int C, float eps, MergeMap mm, hipStream_t s) {
+  int lpr, nv;
+  ln_shape(C / VEC, lpr, nv);
+  const int rpb = 4 * (64 / lpr);   // rows per workgroup
+  const LnQuantOut qo{static_cast<uint8_t*>(q), scales, Kp};
+  SV_LN_DISPATCH(lpr, nv, hipLaunchKernelGGL((ln_fwd_kernel<MERGE, AT, VEC, LPR, NV, LnQuantOut>), dim3(cdiv(rows, rpb)), dim3(256), 0, s,
+                                             static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm, qo););
+}
+template <bool MERGE, typename AT, int VEC>
 static void ln_bwd_launch(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
                           float* dbeta, long long rows, int C, MergeMap mm, int accumulate_dx, float* ws, hipStream_t s) {
   int lpr, nv;
@@ -1210,15 +1272,23 @@ static inline bool ln_vec8(int act_dtype, int C, int merge_H, const void* a, con
          (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
+// the refusals both forward entries share (everything but the null checks of their outputs); `who` names the entry in the message
+static int ln_fwd_check(const char* who, const void* x, const float* gamma, const float* beta, long long rows, int C, int merge_H, int merge_W,
+                        int act_dtype) {
+  SV_REQUIRE(x && gamma && beta && rows > 0, "%s: null/empty argument", who);
+  SV_REQUIRE(C % 4 == 0 && C <= 3072, "%s: C=%d must be a multiple of 4 and <= 3072", who, C);
+  SV_REQUIRE(act_dtype == SV_F32 || act_dtype == SV_BF16, "%s: bad activation dtype %d", who, act_dtype);
+  SV_REQUIRE((((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, "%s: gamma/beta must be 16-byte aligned", who);
+  if (merge_H > 0) SV_REQUIRE(merge_H % 2 == 0 && merge_W % 2 == 0 && C % 16 == 0, "%s(merge): H,W must be even and C a multiple of 16", who);
+  return SV_OK;
+}
+
 extern "C" int sv_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                 long long rows, int C, float eps, int merge_H, int merge_W, int act_dtype, void* stream) {
-  SV_REQUIRE(x && gamma && beta && y && mean && rstd && rows > 0, "layernorm_fwd: null/empty argument");
-  SV_REQUIRE(C % 4 == 0 && C <= 3072, "layernorm_fwd: C=%d must be a multiple of 4 and <= 3072", C);
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE((((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, "layernorm_fwd: gamma/beta must be 16-byte aligned");
+  SV_REQUIRE(y && mean && rstd, "layernorm_fwd: null/empty argument");
+  if (const int rc = ln_fwd_check("layernorm_fwd", x, gamma, beta, rows, C, merge_H, merge_W, act_dtype)) return rc;
   hipStream_t s = (hipStream_t)stream;
   MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
-  if (merge_H > 0) SV_REQUIRE(merge_H % 2 == 0 && merge_W % 2 == 0 && C % 16 == 0, "layernorm_fwd(merge): H,W must be even and C a multiple of 16");
   const bool v8 = ln_vec8(act_dtype, C, merge_H, x, y);
   if (merge_H > 0) {
     if (v8) ln_fwd_launch<true, __bf16, 8>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
@@ -1230,6 +1300,35 @@ extern "C" int sv_layernorm_fwd(const void* x, const float* gamma, const float* 
     else ln_fwd_launch<false, float, 4>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
   }
   return check_launch("sv_layernorm_fwd");
+}
+
+static std::atomic<long long> layernorm_quant_launches{0};
+
+extern "C" long long sv_layernorm_quant_launches(void) { return layernorm_quant_launches.load(std::memory_order_relaxed); }
+
+extern "C" int sv_layernorm_quant_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                                      void* q, int Kp, float* scales, long long rows, int C, float eps, int merge_H, int merge_W,
+                                      int act_dtype, void* stream) {
+  SV_REQUIRE(q && scales, "sv_layernorm_quant_fwd: q and scales must not be null");
+  SV_REQUIRE((mean == nullptr) == (rstd == nullptr), "sv_layernorm_quant_fwd: mean and rstd must be null together");
+  if (const int rc = ln_fwd_check("sv_layernorm_quant_fwd", x, gamma, beta, rows, C, merge_H, merge_W, act_dtype)) return rc;
+  SV_REQUIRE(C > 0 && Kp == (C + 127) / 128 * 128, "sv_layernorm_quant_fwd: Kp (%d) must be C (%d) rounded up to a multiple of 128", Kp, C);
+  SV_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)scales & 3) == 0, "sv_layernorm_quant_fwd: q must be 16-byte aligned, scales 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
+  const bool v8 = ln_vec8(act_dtype, C, merge_H, x, y);
+  if (merge_H > 0) {
+    if (v8) ln_quant_fwd_launch<true, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
+    else if (act_dtype == SV_BF16) ln_quant_fwd_launch<true, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
+    else ln_quant_fwd_launch<true, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
+  } else {
+    if (v8) ln_quant_fwd_launch<false, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
+    else if (act_dtype == SV_BF16) ln_quant_fwd_launch<false, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
+    else ln_quant_fwd_launch<false, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
+  }
+  const int rc = check_launch("sv_layernorm_quant_fwd");
+  if (rc == SV_OK) layernorm_quant_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
 }
 
 extern "C" size_t sv_layernorm_bwd_workspace_floats(int C) { return (size_t)LN_BWD_SLOTS * 2 * C + 2; }

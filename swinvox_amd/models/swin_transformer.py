@@ -140,6 +140,17 @@ def _drop_scale(I, p, seed, like):
     return sc
 
 
+def _norm_for_linear(x, norm, rows, Cd, spec, w, save, merge_hw=(0, 0), **epi):
+    """The LayerNorm in front of a Swin linear (norm1 -> qkv, norm2 -> fc1, patch-merge norm -> reduction; **epi: that linear's epilogue form)
+    -> (ln, mean, rstd, xq).  When the linear will take the fp8 kernel and the fused quantiser is on, the LayerNorm kernel emits the
+    quantised rows xq = (bytes, scales) itself, and without `save` (no backward follows) stores nothing else (ln, mean, rstd are None);
+    otherwise xq is None and this is ops.layernorm_fwd."""
+    if ops.ln_quant_site(spec, w, **epi):
+        ln, m, r, q, sq = ops.layernorm_quant_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save)
+        return ln, m, r, (q, sq)
+    return ops.layernorm_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw) + (None,)
+
+
 def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
     """x [I*res*res, C] -> same shape; returns (out, ctx).  save=False (no backward will follow): the fused attention branch
     skips the tensors it would store for the backward."""
@@ -163,9 +174,9 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
                         ptr(a.proj.weight), ptr(a.proj.bias), ptr(sc1), ptr(x1), ptr(ln1), ptr(m1), ptr(r1), ptr(qkv), ptr(att),
                         I, H, W, Cd, blk.heads, blk.shift, float(blk.norm1.eps), tag=f"M={M} C={Cd}")
     else:
-        ln1, m1, r1 = ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, M, Cd)
+        ln1, m1, r1, q1 = _norm_for_linear(x, blk.norm1, M, Cd, blk.s_qkv, blk.attn.qkv.weight, save, bias=blk.attn.qkv.bias)
         qkv = empty(M, 3 * Cd, like=x)
-        ops.swin_linear_fwd(ln1, M, blk.s_qkv, blk.attn.qkv.weight, qkv, bias=blk.attn.qkv.bias)
+        ops.swin_linear_fwd(ln1, M, blk.s_qkv, blk.attn.qkv.weight, qkv, xq=q1, bias=blk.attn.qkv.bias)
         att = empty(M, Cd, like=x)
         # algorithmic work of the core (49-token windows, no padding): QK^T + PV = 4 * 49 * 32 flop per (token, head); bytes: qkv in, out
         ops.traced_call("sv_window_attention_fwd", 4.0 * 49 * 32 * M * blk.heads, esz * 4 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
@@ -184,10 +195,10 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         ops.traced_call("sv_swin_mlp_fwd", 2 * unit, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs),
                         ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
         return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, packs, None, I)
-    ln2, m2, r2 = ops.layernorm_fwd(x1, blk.norm2.weight, blk.norm2.bias, M, Cd)
+    ln2, m2, r2, q2 = _norm_for_linear(x1, blk.norm2, M, Cd, blk.s_fc1, blk.mlp.fc1.weight, save, bias=blk.mlp.fc1.bias, act=ACT_GELU)
     hpre = empty(M, 4 * Cd, like=x)
     h = empty(M, 4 * Cd, like=x)
-    ops.swin_linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
+    ops.swin_linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, xq=q2, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
     x2 = empty(M, Cd, like=x)
     ops.swin_linear_fwd(h, M, blk.s_fc2, blk.mlp.fc2.weight, x2, bias=blk.mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2,
                         rows_per_scale=H * W)
@@ -292,9 +303,9 @@ def stage_forward(stage: SwinStage, x, I, training, stochastic, seeds, save=True
         ds = stage.downsample
         Hin = stage.res * 2
         Mo = I * stage.res * stage.res
-        lnm, mm, rm = ops.layernorm_fwd(x, ds.norm.weight, ds.norm.bias, Mo, 2 * stage.dim, merge_hw=(Hin, Hin))
+        lnm, mm, rm, qm = _norm_for_linear(x, ds.norm, Mo, 2 * stage.dim, ds.spec, ds.reduction.weight, save, merge_hw=(Hin, Hin))
         y = empty(Mo, stage.dim, like=x)
-        ops.swin_linear_fwd(lnm, Mo, ds.spec, ds.reduction.weight, y)
+        ops.swin_linear_fwd(lnm, Mo, ds.spec, ds.reduction.weight, y, xq=qm)
         sctx["merge"] = (x, lnm, mm, rm, Mo, Hin)
         x = y
     for blk in stage.blocks:

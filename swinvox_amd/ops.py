@@ -558,7 +558,8 @@ def set_linear_fp8(on: bool, backward: bool = False) -> None:
     backward is unchanged too (bf16 data and weight gradients: the quantisers are straight-through); with backward=True (effective only
     together with `on`) the data and weight gradients of the unfused Swin sites run on e4m3 operands as well (swin_linear_dgrad /
     swin_linear_wgrad).  Active only under set_math('bf16'); independent of set_attention_fp8.
-    Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them)."""
+    Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them).
+    The LayerNorms that feed qkv, fc1 and the reduction emit the quantised rows themselves (set_ln_quant_fused)."""
     _STATE["linear_fp8"] = bool(on)
     _STATE["linear_fp8_bwd"] = bool(on) and bool(backward)
 
@@ -603,17 +604,31 @@ def quantize_weight_fp8(w: torch.Tensor):
     return hit
 
 
-def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
+def swin_linear_fp8_epilogue(spec: ConvSpec, w, **epi):
+    """The sv_epilogue of a Swin linear that takes the fp8 kernel, None when it does not: set_linear_fp8(True) under bf16 math, a plain
+    Linear on an unpadded input whose weight is a Parameter, and an epilogue form sv_linear_fp8 serves.  The one copy of these conditions:
+    swin_linear_fwd runs on it, and the LayerNorm sites ask it BEFORE they normalise (with the epilogue keywords of the linear that follows;
+    the query looks at the form, not at the output pointers) whether to emit the quantised rows from the LayerNorm kernel."""
+    if not (linear_fp8_enabled() and spec.taps == 1 and spec.cin_mem == spec.cin and isinstance(w, torch.nn.Parameter)):
+        return None
+    e = _epilogue(spec.cout, **epi)
+    return e if hip.load().sv_linear_fp8_supported(spec.cin, spec.cout, C.byref(e), _STATE["math"], hip.ACT) == 1 else None
+
+
+def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, xq=None, **epi):
     """linear_fwd of the Swin call sites: with set_linear_fp8(True) (and a form sv_linear_fp8 serves) the activation rows are quantised, the
-    quantised weight fetched and the product runs on the fp8 kernel; otherwise exactly linear_fwd."""
-    if linear_fp8_enabled() and spec.taps == 1 and spec.cin_mem == spec.cin and isinstance(w, torch.nn.Parameter):
-        e = _epilogue(spec.cout, **epi)
-        if hip.load().sv_linear_fp8_supported(spec.cin, spec.cout, C.byref(e), _STATE["math"], hip.ACT) == 1:
-            xq, sx = quantize_rows_fp8(x, rows, spec.cin)
-            wq, sw = quantize_weight_fp8(w)
-            traced_call("sv_linear_fp8", 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + x.element_size() * spec.cout) + wq.numel(),
-                        ptr(xq), ptr(sx), ptr(wq), ptr(sw), ptr(out), rows, spec.cin, spec.cout, C.byref(e), tag=f"M={rows} K={spec.cin} N={spec.cout}")
-            return
+    quantised weight fetched and the product runs on the fp8 kernel; otherwise exactly linear_fwd.  xq = (bytes, scales): the rows of x
+    already quantised by its producer (layernorm_quant_fwd), which the caller obtained because swin_linear_fp8_epilogue said this linear takes
+    the fp8 kernel; the quantiser pass is skipped and x itself is not read (it may be None)."""
+    e = swin_linear_fp8_epilogue(spec, w, **epi)
+    if e is not None:
+        xq, sx = xq if xq is not None else quantize_rows_fp8(x, rows, spec.cin)
+        wq, sw = quantize_weight_fp8(w)
+        traced_call("sv_linear_fp8", 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + out.element_size() * spec.cout) + wq.numel(),
+                    ptr(xq), ptr(sx), ptr(wq), ptr(sw), ptr(out), rows, spec.cin, spec.cout, C.byref(e), tag=f"M={rows} K={spec.cin} N={spec.cout}")
+        return
+    if xq is not None:
+        raise RuntimeError("swin_linear_fwd: pre-quantised rows were passed to a linear that does not take the fp8 kernel")
     linear_fwd(x, rows, spec, w, out, **epi)
 
 
@@ -702,6 +717,46 @@ def layernorm_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5):
     rstd = fempty(rows, like=x)
     call("sv_layernorm_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), rows, Cdim, eps, merge_hw[0], merge_hw[1])
     return y, mean, rstd
+
+
+def set_ln_quant_fused(on: bool) -> None:
+    """A/B switch of the quantising LayerNorm (csrc/norm.hip, sv_layernorm_quant_fwd): True (default) lets norm1 / norm2 / the patch-merge
+    norm emit the e4m3 rows and scales of the fp8 linear they feed; False keeps LayerNorm + the stand-alone row quantiser.  Effective only
+    while linear_fp8_enabled(); SV_LN_QUANT_FUSED=0 in the environment switches it off as well."""
+    _STATE["ln_quant_fused"] = bool(on)
+
+
+def ln_quant_fused_enabled() -> bool:
+    import os
+    return linear_fp8_enabled() and _STATE.get("ln_quant_fused", True) and os.environ.get("SV_LN_QUANT_FUSED", "1") != "0"
+
+
+def ln_quant_site(spec: ConvSpec, w, **epi) -> bool:
+    """Whether the LayerNorm in front of this Swin linear takes the quantising form: the linear will run on the fp8 kernel and the fused
+    quantiser is on.  With set_linear_fp8 off this is one flag test."""
+    return ln_quant_fused_enabled() and swin_linear_fp8_epilogue(spec, w, **epi) is not None
+
+
+def layernorm_quant_launches() -> int:
+    """sv_layernorm_quant_fwd launches of this process so far."""
+    return int(hip.load().sv_layernorm_quant_launches())
+
+
+def layernorm_quant_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5, store=True):
+    """layernorm_fwd that also returns the operand rows of the fp8 linear it feeds: (y, mean, rstd, xq, sx) with xq [rows, roundup(Cdim, 128)]
+    e4m3 bytes and sx [rows] fp32 scales, equal to quantize_rows_fp8(y).  store=False (no backward follows): y, mean and rstd are neither
+    allocated nor written and come back as None."""
+    y = mean = rstd = None
+    if store:
+        y = empty(rows, Cdim, like=x)
+        mean = fempty(rows, like=x)
+        rstd = fempty(rows, like=x)
+    Kp = (Cdim + 127) // 128 * 128
+    xq = torch.empty(rows, Kp, dtype=torch.uint8, device=x.device)
+    sx = torch.empty(rows, dtype=torch.float32, device=x.device)
+    call("sv_layernorm_quant_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), ptr(xq), Kp, ptr(sx), rows, Cdim, eps,
+         merge_hw[0], merge_hw[1])
+    return y, mean, rstd, xq, sx
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, Cdim, merge_hw=(0, 0), accumulate_dx=False):
