@@ -153,6 +153,23 @@ int sv_linear_fp8_dgrad_supported(int N, int K, const sv_epilogue* e, int math, 
 int sv_linear_fp8_wgrad(const void* dyt, const float* sdc, const void* xt, const float* sxc, float* dw, int M, int N, int K, int ldw, int splits,
                         void* stream);
 long long sv_linear_fp8_bwd_launches(int which); /* launches so far of sv_linear_fp8_dgrad (which = 0) / sv_linear_fp8_wgrad (1) (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise); sv_linear_fp8_launches counts neither */
+/* MX form of the fp8 forward of the same Linear layers (timm Linear behind models/swin_transformer.py:78), opt-in.  Operands: rows of
+ * Kp = roundup(K, 128) OCP e4m3fn bytes and one E8M0 byte per 32-byte block, [rows][Kp / 32] uint8.  Block scale: amax of the 32 stored values
+ * = m 2^e, m in [1, 2): E = e - 8 + (m > 1.75) = ceil(log2(amax / 448)) clamped to [-127, 127], byte = E + 127 (all-zero block: 127; 255 never);
+ * elements e4m3_rne(ldexpf(x, -E)), so nothing saturates; bytes K .. Kp-1 zero, blocks wholly in the padding carry 127.  The MFMA applies both
+ * operands' block scales in hardware: val = acc, no division.
+ * The MX row quantiser (timm Linear behind models/swin_transformer.py:78, operand preparation; the definition every producer equals): src [rows, K] with
+ * row stride ld (SV_F32 or SV_BF16) -> dst_q [rows, Kp] (16-byte aligned, Kp == roundup(K, 128)) and scales_u8 [rows, Kp / 32] (4-byte aligned). */
+int sv_quant_rows_mx_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, void* scales_u8, void* stream);
+/* out[m, n] = epilogue(sum_k 2^(xs + ws - 254) xq[m, k] wq[n, k]) (timm Linear behind models/swin_transformer.py:78).  xq / xs, wq / ws from the MX row
+ * quantiser; epilogue forms and refusals are sv_linear_fp8's (sv_linear_fp8_supported answers for both).  q_out [M, N] / qs_out [M, N / 32]
+ * (optional, both or neither): the MX rows of the STORED output (after the activation, rounded to act_dtype), equal to the MX row quantiser on out -
+ * the operand of the next linear.  Refused with SV_ERR_INVALID unless N % 128 == 0, and with a residual.  With q_out given, out (and then
+ * e->pre_act) may be NULL: nothing but the MX rows is written. */
+int sv_linear_mxfp8(const void* xq, const void* xs, const void* wq, const void* ws, void* out, int M, int K, int N, const sv_epilogue* e,
+                    void* q_out, void* qs_out, int act_dtype, void* stream);
+long long sv_linear_mxfp8_launches(void); /* sv_linear_mxfp8 launches so far in this process (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise) */
+long long sv_quant_rows_mx_launches(void); /* sv_quant_rows_mx_e4m3 launches so far in this process (timm Linear behind models/swin_transformer.py:78, operand preparation; tests) */
 /* LDS-halo MFMA stencils for 3x3x3 / stride 1 / pad 1 convolutions with <= 16 output channels per tile (merger.py:20-54),
  * bf16 operands.  x: channels-last positions with row stride ldx, cin_load (multiple of 4) elements read per position,
  * zero-extended to 16*groups channels; w_bf16: [16*ntiles16][27][16*groups] bf16 (forward: rows = output channels;
@@ -294,6 +311,13 @@ int sv_window_attention_fwd(const void* qkv, const float* table, void* out, int 
 size_t sv_window_attention_bwd_workspace_floats(int heads);
 int sv_window_attention_bwd(const void* qkv, const float* table, const void* dout, void* dqkv, float* dtable, float* workspace,
                             int I, int H, int W, int C, int heads, int shift, int math, int act_dtype, void* stream);
+/* sv_window_attention_fwd that also emits the MX operand rows of the Linear that follows (timm WindowAttention -> proj Linear behind
+ * models/swin_transformer.py:78; recipe: sv_quant_rows_mx_e4m3): q_out [tokens, Kp] e4m3 bytes and qs_out [tokens, Kp / 32] E8M0 bytes of the STORED
+ * output, equal to the MX row quantiser on out - one head of one token is one block.  Kp == roundup(C, 128); for Kp > C the kernel writes the
+ * zero padding bytes and the scale 127 of the padding blocks itself.  out may be NULL (no backward follows).  Served by the workgroup kernels
+ * of SV_MATH_BF16 / SV_MATH_FP8 / SV_MATH_FP8_FULL; SV_MATH_F32 is refused with SV_ERR_INVALID. */
+int sv_window_attention_fwd_mxq(const void* qkv, const float* table, void* out, int I, int H, int W, int C, int heads, int shift, int math,
+                                void* q_out, int Kp, void* qs_out, int act_dtype, void* stream);
 /* Consecutive windows one workgroup (bf16 / fp8 kernels) or one wave (exact-fp32 kernels) walks in the launch sv_window_attention_fwd
  * (backward = 0) / _bwd (backward = 1) makes for these arguments (call site models/swin_transformer.py:78); 1 for the fp32 forward.  A
  * pure host function - the launches take their share from the same place - for tests that mean to run a kernel at several windows per

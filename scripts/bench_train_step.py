@@ -1,7 +1,9 @@
 """Whole optimisation step (harness.train_step: forward + backward + clip + solver) with the flat-buffer solvers and with
 the stock torch.optim sequence, next to forward+backward alone.  python scripts/bench_train_step.py [--batch 32]
 --fp8-linear: forward+backward alone with the fp8 Swin linears (set_linear_fp8) off and on, same process.
---fp8-linear-bwd: the same with a third run, set_linear_fp8(True, backward=True): data and weight gradients of the linears in e4m3 too."""
+--fp8-linear-bwd: the same with a third run, set_linear_fp8(True, backward=True): data and weight gradients of the linears in e4m3 too.
+--fp8-linear-mx: forward+backward alone, alternating (two rounds, one process) bf16, the row recipe, the MX recipe with producer emission and
+the MX recipe with the stand-alone quantiser everywhere (set_mx_producer_quant(False))."""
 import argparse
 import os
 import sys
@@ -11,7 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import swinvox_amd as S  # noqa: E402
-from swinvox_amd import harness  # noqa: E402
+from swinvox_amd import harness, ops  # noqa: E402
 from swinvox_amd.models import Decoder, Encoder, Merger, Refiner  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -20,6 +22,7 @@ ap.add_argument("--views", type=int, default=8)
 ap.add_argument("--steps", type=int, default=6)
 ap.add_argument("--fp8-linear", action="store_true", help="time forward+backward only, with set_linear_fp8 off and on")
 ap.add_argument("--fp8-linear-bwd", action="store_true", help="as --fp8-linear, plus a run with the fp8 backward of the linears")
+ap.add_argument("--fp8-linear-mx", action="store_true", help="forward+backward only: bf16, row recipe, MX with and without producer emission, two rounds")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = S.default_cfg()
@@ -40,17 +43,20 @@ def timed(fn, n):
     return (time.perf_counter() - t) / n * 1e3
 
 
-for fused in ((None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
+MX_MODES = (None, "fp8", "mx", "mx-noemit")
+for fused in (MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
     torch.manual_seed(0)
     nets = [m(cfg).to(dev).train() for m in (Encoder, Decoder, Merger, Refiner)]
-    fp8 = fused in ("fp8", "fp8+bwd")
-    S.set_linear_fp8(fp8, backward=fused == "fp8+bwd")
+    fp8 = fused in ("fp8", "fp8+bwd", "mx", "mx-noemit")
+    S.set_linear_fp8(fp8, backward=fused == "fp8+bwd", recipe="mx" if fused in ("mx", "mx-noemit") else "row")
+    ops.set_mx_producer_quant(fused != "mx-noemit")
     if fused is None or fp8:
         def step():
             for n in nets:
                 n.zero_grad(set_to_none=True)
             harness.forward_losses(nets, cfg, x, gt)[0].backward()
-        name = "forward+backward only" + (", fp8 Swin linears" if fused == "fp8" else ", fp8 Swin linears fwd + bwd" if fp8 else "")
+        name = "forward+backward only" + {"fp8": ", fp8 Swin linears", "fp8+bwd": ", fp8 Swin linears fwd + bwd", "mx": ", MX Swin linears, emission",
+                                          "mx-noemit": ", MX Swin linears, quantiser"}.get(fused, "")
     else:
         solvers, _ = harness.make_solvers(nets, cfg, fused=fused)
         def step():

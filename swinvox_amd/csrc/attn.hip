@@ -790,8 +790,38 @@ __device__ __forceinline__ void put_chunk(__bf16* dst, const bf16x8& v, float mu
   *reinterpret_cast<bf16x8*>(dst) = b;
 }
 
+// ---- MX operand rows of the attention output (sv_window_attention_fwd_mxq): the producer side of linear_fp8.hip's MX recipe for att -> proj.
+// One head of one token (32 channels) is exactly one MX block.  A lane holds 8 of the 32 channels of query lr as two groups of 4 consecutive
+// channels (c0, c1: offsets inside the head); the block maximum of the STORED values (rounded to AT first) is a reduction over the four lg
+// groups, lanes lr + 16 lg.  Each lane stores its 2 x 4 bytes, lg == 0 the E8M0 byte at [token][head].  For Kp > C the workgroup of the last
+// head writes the zero bytes C .. Kp - 1 and the scale 127 of the padding blocks of its tokens: nothing relies on a pre-zeroed buffer.
+// All lanes of a query (the four lg groups) must call it together.
+template <typename AT> struct WinMxqArgsT : WinArgsT<AT> { uint8_t* q_out; uint8_t* qs_out; int Kp; };
+template <typename AT, bool MXQ> struct WinFwdArgsOf { typedef WinArgsT<AT> type; };
+template <typename AT> struct WinFwdArgsOf<AT, true> { typedef WinMxqArgsT<AT> type; };
+
 template <typename AT>
-__global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_kernel(const WinArgsT<AT> p) {
+__device__ __forceinline__ void mxq_emit(const WinMxqArgsT<AT>& p, long long row, int head, int lg, const float (&v)[8], int c0, int c1) {
+  float t[8], am = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { t[j] = (float)(AT)v[j]; am = fmaxf(am, fabsf(t[j])); }
+  am = fmaxf(am, __shfl_xor(am, 16));
+  am = fmaxf(am, __shfl_xor(am, 32));
+  const int E = mx_block_exp(am);
+  uint8_t* q = p.q_out + (size_t)row * p.Kp + head * HD;
+  *reinterpret_cast<uint32_t*>(q + c0) = pack4_e4m3_mx(t[0], t[1], t[2], t[3], E);
+  *reinterpret_cast<uint32_t*>(q + c1) = pack4_e4m3_mx(t[4], t[5], t[6], t[7], E);
+  uint8_t* qs = p.qs_out + (size_t)row * (p.Kp >> 5);
+  if (lg == 0) qs[head] = (uint8_t)(E + 127);
+  if (head == p.heads - 1 && p.C + 32 * lg < p.Kp) {       // padding block lg of this token: 32 zero bytes, scale 1.0
+    uint4* z = reinterpret_cast<uint4*>(p.q_out + (size_t)row * p.Kp + p.C + 32 * lg);
+    z[0] = make_uint4(0u, 0u, 0u, 0u); z[1] = make_uint4(0u, 0u, 0u, 0u);
+    qs[(p.C >> 5) + lg] = 127;
+  }
+}
+
+template <typename AT, bool MXQ = false>
+__global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_kernel(const typename WinFwdArgsOf<AT, MXQ>::type p) {
   // q (scaled) | k | v of the window's head, row-major [token][32 (+8)] bf16.  The products are taken with swapped operands (keys / V^T as
   // the first MFMA operand): S^T = K Q^T leaves the 16 keys (16 nt + 4 lg + j) of query lr in one lane, so the softmax of a query is 16
   // in-lane values + two lane-group exchanges, and the probabilities go into P V from the registers they are in (the contraction index of
@@ -863,7 +893,8 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_kernel(const WinArgsT<
       }
     if (qok) {   // lane: query lr, head channels 8 lg .. 8 lg + 7 (block nt holds 8 lg + 4 nt + j): one 16-byte vector of bf16 rows
       const float ov[8] = {o[0][0], o[0][1], o[0][2], o[0][3], o[1][0], o[1][1], o[1][2], o[1][3]};
-      stnf<8>(p.out + (size_t)tm.row(q) * p.C + colq + lg * 8, ov);
+      if (!MXQ || p.out) stnf<8>(p.out + (size_t)tm.row(q) * p.C + colq + lg * 8, ov);
+      if constexpr (MXQ) mxq_emit<AT>(p, tm.row(q), head, lg, ov, lg * 8, lg * 8 + 4);
     }
   }
 }
@@ -884,8 +915,8 @@ __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d
 }
 __device__ __forceinline__ uint8_t one_fp8(float a) { return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(a, 0.f, 0, false) & 0xff); }
 
-template <typename AT>
-__global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_fp8_kernel(const WinArgsT<AT> p) {
+template <typename AT, bool MXQ = false>
+__global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_fp8_kernel(const typename WinFwdArgsOf<AT, MXQ>::type p) {
   __shared__ __attribute__((aligned(16))) uint8_t Qs[64 * LDQ_8], Ks[64 * LDQ_8], Vt[HD * LDP_8], Ps[64 * LDP_8];
   __shared__ float bt[176];
   __shared__ float amax[4][3];
@@ -964,9 +995,15 @@ __global__ __launch_bounds__(256, 4) void win_attn_fwd_wg_fp8_kernel(const WinAr
       const int q = wave * 16 + lr;
       const float un = 1.f / (256.f * sv);
       if (q < WT) {
-        AT* dst = p.out + (size_t)tm.row(q) * p.C + colq + lg * 4;
-        st4f(dst, make_float4(o[0][0] * un, o[0][1] * un, o[0][2] * un, o[0][3] * un));
-        st4f(dst + 16, make_float4(o[1][0] * un, o[1][1] * un, o[1][2] * un, o[1][3] * un));
+        if (!MXQ || p.out) {
+          AT* dst = p.out + (size_t)tm.row(q) * p.C + colq + lg * 4;
+          st4f(dst, make_float4(o[0][0] * un, o[0][1] * un, o[0][2] * un, o[0][3] * un));
+          st4f(dst + 16, make_float4(o[1][0] * un, o[1][1] * un, o[1][2] * un, o[1][3] * un));
+        }
+        if constexpr (MXQ) {   // the lane's channels: 4 lg .. + 3 and 16 + 4 lg .. + 3 of the head
+          const float ov[8] = {o[0][0] * un, o[0][1] * un, o[0][2] * un, o[0][3] * un, o[1][0] * un, o[1][1] * un, o[1][2] * un, o[1][3] * un};
+          mxq_emit<AT>(p, tm.row(q), head, lg, ov, lg * 4, 16 + lg * 4);
+        }
       }
     }
   }
@@ -1926,6 +1963,28 @@ extern "C" int sv_window_attention_fwd(const void* qkv, const float* table, void
   else   // exact-fp32 MFMA: wave per window
     hipLaunchKernelGGL(win_attn_fwd_kernel, dim3(cdiv(c.ntasks(), 4), heads), dim3(256), 0, s, win_args<float>(c, share));
   return check_launch("sv_window_attention_fwd");
+}
+
+extern "C" int sv_window_attention_fwd_mxq(const void* qkv, const float* table, void* out, int I, int H, int W, int C, int heads, int shift, int math,
+                                           void* q_out, int Kp, void* qs_out, int act_dtype, void* stream) {
+  if (int rc = win_check(qkv, table, I, H, W, C, heads, shift, math, act_dtype)) return rc;
+  SV_REQUIRE(math == SV_MATH_BF16 || math == SV_MATH_FP8 || math == SV_MATH_FP8_FULL,
+             "window_attention_fwd_mxq: served by the bf16 and fp8 workgroup kernels only (math %d)", math);
+  SV_REQUIRE(q_out && qs_out, "window_attention_fwd_mxq: null q_out / qs_out");
+  SV_REQUIRE(Kp == cdiv(C, 128) * 128, "window_attention_fwd_mxq: Kp (%d) must be C (%d) rounded up to a multiple of 128", Kp, C);
+  SV_REQUIRE(((uintptr_t)q_out & 15) == 0 && ((uintptr_t)qs_out & 3) == 0, "window_attention_fwd_mxq: q_out must be 16-byte, qs_out 4-byte aligned");
+  const WinCall c{qkv, table, out, nullptr, nullptr, nullptr, I, H, W, C, heads, shift};
+  hipStream_t s = (hipStream_t)stream;
+  const bool fp8 = math != SV_MATH_BF16;
+  const int tpb = win_share(c.ntasks(), heads, math, false);
+  const dim3 grid(wg_grid(cdiv(c.ntasks(), tpb), heads));
+  SV_DISPATCH_ACT(act_dtype,
+    WinMxqArgsT<AT> a{};
+    static_cast<WinArgsT<AT>&>(a) = win_args<AT>(c, tpb);
+    a.q_out = static_cast<uint8_t*>(q_out); a.qs_out = static_cast<uint8_t*>(qs_out); a.Kp = Kp;
+    if (!fp8) hipLaunchKernelGGL((win_attn_fwd_wg_kernel<AT, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((win_attn_fwd_wg_fp8_kernel<AT, true>), grid, dim3(256), 0, s, a););
+  return check_launch("sv_window_attention_fwd_mxq");
 }
 
 extern "C" int sv_window_attention_windows_per_group(int I, int H, int W, int heads, int math, int backward) {

@@ -144,6 +144,19 @@ __device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float 
   return (uint32_t)w;
 }
 
+// ---- MX form of the same operands (linear_fp8.hip, "MX recipe"): one E8M0 power-of-two scale per 32 consecutive elements.  For a block whose
+// maximum is amax = m 2^e, m in [1, 2): E = e - 8 + (m > 1.75) = ceil(log2(amax / 448)), read from the float's bits; E is clamped to
+// [-127, 127] (a subnormal amax clamps to -127), an all-zero block takes E = 0.  Byte = E + 127 (never 255); elements = e4m3_rne(ldexpf(x, -E)).
+__device__ __forceinline__ int mx_block_exp(float amax) {
+  const uint32_t b = __float_as_uint(amax) & 0x7fffffffu;
+  if (b == 0u) return 0;
+  const int E = (int)(b >> 23) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return max(E, -127);                                     // e <= 128: E <= 121, no upper clamp is ever taken
+}
+__device__ __forceinline__ uint32_t pack4_e4m3_mx(float a, float b, float c, float d, int E) {   // the scaling is an exponent add: exact
+  return pack4_e4m3(ldexpf(a, -E), ldexpf(b, -E), ldexpf(c, -E), ldexpf(d, -E));
+}
+
 // block-wide sum over 256 threads (4 waves); scratch must hold >= 4 floats; all threads get the result
 template <int NW>
 __device__ __forceinline__ float block_sum(float v, float* scratch) {

@@ -19,7 +19,8 @@
 //                       (the second time from cache); activations (bf16 / fp32) and weights (fp32) take the same kernel.
 //                       SECOND PRODUCER of these operand rows: ln_fwd_kernel with its LnQuantOut argument (norm.hip, sv_layernorm_quant_fwd) writes the same bytes and
 //                       scales for the rows a token LayerNorm stores (norm1 -> qkv, norm2 -> fc1, patch-merge norm -> reduction), from the
-//                       registers that hold the normalised row; att -> proj and h -> fc2 keep this kernel.
+//                       registers that hold the normalised row.  att -> proj and h -> fc2 keep this kernel under the per-row recipe (neither
+//                       producer sees a full row); under the MX recipe below their producers emit the operand rows themselves.
 //   linear_fp8_kernel   128 x 128 output tile per 256-thread workgroup, 4 waves as 2 x 2, a wave owns 64 x 64 = 4 x 4 MFMA blocks (64 accumulator
 //                       registers).  One k-step = 128 bytes of every row = ONE MFMA deep: 16 KB per operand tile, staged through registers
 //                       (16-byte global loads of the next step are in flight while the current step's 16 MFMAs per wave run) into two LDS
@@ -30,11 +31,37 @@
 //                       2-way conflicts), and a staging write still fills whole rows.  LDS: 2 x 2 x 128 x 128 = 65 536 bytes, two
 //                       workgroups per CU.  Rows and columns past M / N load a clamped (valid) row and are skipped by the epilogue: nothing
 //                       is read or written out of range.
-//   Operand lane map of the K = 128 form: lane l holds row / column l & 15 and the 32 bytes k = 32 (l >> 4) .. + 31 in eight VGPRs.  Both
-//   operands use the same k map, so the sum does not depend on it; the row / column map and the C/D map (the 16 x 16 one) are what the
+//   Operand lane map of the K = 128 form: lane l holds row / column l & 15 and 32 bytes of its row in eight VGPRs.  Both
+//   operands use the same k map, so the unit-scale sum does not depend on it (the MX form does: lf_contract); the row / column map and the C/D map (the 16 x 16 one) are what the
 //   exact-integer test (tests/test_gpu_linear_fp8.py) establishes.  W is the A operand and x the B operand: a lane then holds output row
 //   l & 15 and four consecutive rows of D = output columns per block; the W rows are permuted on their way into LDS so that the lane's four blocks
 //   together are 16 consecutive output columns - 16-byte stores, 32 (bf16) / 64 (fp32) contiguous bytes per lane and row.
+//
+// MX recipe (opt-in: set_linear_fp8(True, recipe="mx")): the same e4m3 operands with one E8M0 power-of-two scale per 32 consecutive elements of
+// the contraction, applied by the MFMA.  A scale depends on 32 neighbouring values only, so producers that never see a full row can emit the
+// operand.  It is a structural feature, not an accuracy feature: e4m3's three mantissa bits set the error.  NORMATIVE:
+//   operand form   rows of Kp = roundup(K, 128) OCP e4m3fn bytes + one E8M0 byte per 32-byte block, [rows][Kp / 32] uint8: four bytes per row and
+//                  k-step, so a row's scales of one k-step are one aligned dword.
+//   block scale    amax over the 32 STORED values (the value rounded to the storage type first).  amax = m 2^e, m in [1, 2):
+//                  E = e - 8 + (m > 1.75) = ceil(log2(amax / 448)), taken from the float's bits (no transcendental), clamped to [-127, 127];
+//                  byte = E + 127; an all-zero block takes byte 127; byte 255 is never produced.  Round-up variant: |x 2^-E| <= 448 always, so
+//                  nothing saturates.  Pins (amax -> byte, q of the maximum): 1 -> 119, 256; 1.75 -> 119, 448; 1.7578125 -> 120, 224;
+//                  224 -> 126, 448; 448 -> 127, 448; 450 -> 128; 0 -> 127, 0; 1e-30 -> 19.
+//   elements       q = e4m3_rne(ldexpf(x, -E)): the scaling is an exponent add, exact.
+//   padding        bytes K .. Kp - 1 are zero; blocks that lie wholly in the padding carry byte 127.
+//   contraction    v_mfma_scale_f32_16x16x128_f8f6f4, cbsz = blgp = 0, the two scale operands from the operands' scale bytes, fp32 accumulation;
+//                  val = acc, no division.  The epilogue (bias, pre_act copy, GELU, residual + row_scale, ldc) is the per-row kernel's, unchanged.
+//   emission       optional q_out / qs_out: the MX rows of the STORED output (after the activation, rounded to the storage type), for the output
+//                  the next linear contracts over (fc1's h): Kp_out = N, so N % 128 == 0, and no residual.  With q_out, out and pre_act may be
+//                  null (no backward follows): fc1 then writes 1 byte per hidden element instead of 4.
+// Kernels of the MX recipe
+//   quant_rows_mx_kernel   the definition every producer equals: one wave per row, 8 lanes per block, three lane exchanges for the block maximum.
+//   linear_fp8_kernel<.., MX = true>   the kernel above with lf_contract<true>: the scale dwords of a k-step (128 + 128, 1 KB per buffer) are
+//                  staged beside the operand tiles - LDS 65 536 + 2 048 = 67 584 bytes, still two workgroups per CU - and the lane maps of the
+//                  scale operands and of the e4m3 data are those documented at lf_contract.  Emission: a 32-column block is the 16 + 16
+//                  columns of lanes lg and lg ^ 1 of one row: one exchange (lane ^ 16) gives its maximum, each lane stores its 16 bytes and
+//                  the even one of the pair the scale byte.  Other producer: win_attn_fwd_wg*_kernel<.., MXQ = true> (attn.hip,
+//                  sv_window_attention_fwd_mxq): one head of one token is one block.
 //
 // Backward (opt-in: set_linear_fp8(True, backward=True)); the constants, the zero rule, the clamp, the rounding, the zero padding to a multiple of 128
 // bytes along the contraction, the unit hardware block scales and the fp32 IEEE division of the epilogue are the forward's.  All operands are
@@ -102,6 +129,29 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const T* __restrict__ s
   if (lane == 0) scales[r] = s;
 }
 
+// MX row quantiser: one wave per row, a lane holds 4 consecutive elements and 8 lanes one 32-element block; the block maximum is three lane
+// exchanges inside the group of 8 (a group is past Kp as a whole or not at all).  Every lane writes its 4 bytes, the group's first lane the E8M0 byte.
+template <typename T>
+__global__ __launch_bounds__(256) void quant_rows_mx_kernel(const T* __restrict__ src, int rows, int K, long long ld, uint8_t* __restrict__ dst, int Kp,
+                                                            uint8_t* __restrict__ scales) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;                                   // whole waves leave: no barrier in this kernel
+  const T* row = src + (size_t)r * ld;
+  const bool vec = (((uintptr_t)row) & (4 * sizeof(T) - 1)) == 0;
+  uint32_t* out = reinterpret_cast<uint32_t*>(dst + (size_t)r * Kp);
+  uint8_t* sc = scales + (size_t)r * (Kp >> 5);
+  for (int k = lane * 4; k < Kp; k += 256) {
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (k < K) load4_guarded(row, k, K, vec, v);
+    float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    m = fmaxf(m, __shfl_xor(m, 1)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 4));
+    const int E = mx_block_exp(m);
+    out[k >> 2] = pack4_e4m3_mx(v[0], v[1], v[2], v[3], E);
+    if ((lane & 7) == 0) sc[k >> 5] = (uint8_t)(E + 127);
+  }
+}
+
 // ---- GEMM ----------------------------------------------------------------------------------------------------------------------------
 struct LinFp8Args {
   const uint8_t* xq; const float* sx; const uint8_t* wq; const float* sw; void* out;
@@ -110,14 +160,27 @@ struct LinFp8Args {
 };
 
 constexpr int LF_BM = 128, LF_BN = 128, LF_BK = 128, LF_PITCH = 128, LF_TILE = LF_BM * LF_PITCH;   // bytes
+constexpr int LF_SCALES = 4 * (LF_BM + LF_BN);             // MX: the scale dwords of one k-step, x rows then W rows
 __device__ __forceinline__ int lf_swz(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 2); }   // position of piece c in row r: c ^ lf_swz(r)
 
 // The contraction core every fp8 GEMM of this file runs: acc += sum over the k-steps ks0 .. ks1 - 1 (128 bytes each) of the 128 x 128 tile
 // at (row0, col0) of xq [M][pitch] times wq [N][pitch]^T.  Staging, the swizzled LDS image, the fragment reads and the MFMA block have this
 // one copy.  On return lane (lr, lg) of wave (wm, wn) holds, in acc[nt][mt][i], row row0 + 64 wm + 16 mt + lr and column
 // col0 + 64 wn + 16 lg + 4 nt + i: 16 consecutive columns per row.  Rows past M / N read a clamped (valid) row; the caller's epilogue skips them.
+// MX (compile time): the operands carry E8M0 block scales, xsc [M][pitch / 32] and wsc [N][pitch / 32] bytes.  The four scale bytes of a row and
+// k-step are one aligned dword; thread t < 128 stages the dword of x tile row t, thread 128 + t that of W tile row t (the W rows' permutation),
+// into LF_SCALES bytes behind the operand tiles of each buffer.  Lane maps of the scaled MFMA with e4m3 operands, as measured
+// (scripts/probes/mfma_scale_lane_probe.hip) and pinned by the exact-integer test with block scales (tests/test_gpu_linear_mxfp8.py):
+//   scales  lane l's selected byte scales row / column l & 15 and the 32 k-values k = 32 (l >> 4) .. + 31 of the k-step;
+//   data    lane l's registers 0-3 hold k = 16 (l >> 4) .. + 15 and its registers 4-7 k = 64 + 16 (l >> 4) .. + 15 - two K = 64 halves, NOT 32
+//           consecutive bytes: a lane's scale byte covers 16 of its own bytes and 16 of a neighbouring lane group's.  The unit-scale form
+//           never notices (both operands permute k alike); here lane (lr, lg) takes pieces lg and 4 + lg of its row, shifts the row's
+//           scale dword by 8 lg and passes byte 0 (op-sel 0).
+// Without MX both scales are the constant 1.0 and nothing is staged.
+template <bool MX = false>
 __device__ __forceinline__ void lf_contract(const uint8_t* __restrict__ xq, int M, const uint8_t* __restrict__ wq, int N, size_t pitch, int row0, int col0,
-                                            int ks0, int ks1, uint8_t* __restrict__ lf_smem, f32x4 (&acc)[4][4]) {
+                                            int ks0, int ks1, uint8_t* __restrict__ lf_smem, f32x4 (&acc)[4][4],
+                                            const uint8_t* __restrict__ xsc = nullptr, const uint8_t* __restrict__ wsc = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;                 // the wave's 64 x 64 quarter of the tile
   const int lr = lane & 15, lg = lane >> 4;
@@ -133,15 +196,26 @@ __device__ __forceinline__ void lf_contract(const uint8_t* __restrict__ xq, int 
     const int m = min(row0 + r, M - 1), n = min(col0 + nl, N - 1);   // past the end: any valid row, the epilogue skips it
     gx[i] = xq + (size_t)m * pitch + c * 16;
     gw[i] = wq + (size_t)n * pitch + c * 16;
-    so[i] = r * LF_PITCH + (c ^ lf_swz(r)) * 16;
+    // MX: the lane's fragment must be the hardware's k order (below), pieces lg and 4 + lg of the row; they are stored where the plain
+    // image keeps pieces 2 lg and 2 lg + 1, so the fragment reads and their bank pattern are the same in both forms
+    const int cp = MX ? (((c & 3) << 1) | (c >> 2)) : c;
+    so[i] = r * LF_PITCH + (cp ^ lf_swz(r)) * 16;
   }
   i32x4 rx[4], rw[4];
+  const uint8_t* gs = nullptr;                             // MX: this thread's row of scale bytes
+  uint32_t rs = 0;
+  if constexpr (MX) {
+    const int r = tid & 127;
+    const int nl = (r & 64) + ((r & 15) >> 2) * 16 + ((r >> 4) & 3) * 4 + (r & 3);
+    gs = tid < 128 ? xsc + (size_t)min(row0 + r, M - 1) * (pitch >> 5) : wsc + (size_t)min(col0 + nl, N - 1) * (pitch >> 5);
+  }
   auto load_step = [&](size_t k0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       rx[i] = *reinterpret_cast<const i32x4*>(gx[i] + k0);
       rw[i] = *reinterpret_cast<const i32x4*>(gw[i] + k0);
     }
+    if constexpr (MX) rs = *reinterpret_cast<const uint32_t*>(gs + (k0 >> 5));
   };
   auto store_step = [&](int buf) {
     uint8_t* xs = lf_smem + buf * 2 * LF_TILE;
@@ -150,6 +224,7 @@ __device__ __forceinline__ void lf_contract(const uint8_t* __restrict__ xq, int 
       *reinterpret_cast<i32x4*>(xs + so[i]) = rx[i];
       *reinterpret_cast<i32x4*>(xs + LF_TILE + so[i]) = rw[i];
     }
+    if constexpr (MX) reinterpret_cast<uint32_t*>(lf_smem + 4 * LF_TILE + buf * LF_SCALES)[tid] = rs;
   };
 
   const int o_lo = ((2 * lg) ^ lf_swz(lr)) * 16, o_hi = ((2 * lg + 1) ^ lf_swz(lr)) * 16;   // the lane's two 16-byte pieces of a row
@@ -162,18 +237,27 @@ __device__ __forceinline__ void lf_contract(const uint8_t* __restrict__ xq, int 
     const uint8_t* xs = lf_smem + buf * 2 * LF_TILE + (wm * 64 + lr) * LF_PITCH;   // rows + 16 mt share bits 1 and 3 with lr: one swizzle per lane
     const uint8_t* ws = lf_smem + buf * 2 * LF_TILE + LF_TILE + (wn * 64 + lr) * LF_PITCH;
     i32x8 fx[4];
+    int sxb[4];                                            // MX: the E8M0 byte of this lane's block of x row 16 mt + lr, in byte 0
+    const uint32_t* ss = reinterpret_cast<const uint32_t*>(lf_smem + 4 * LF_TILE + buf * LF_SCALES);
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
       const i32x4 lo = *reinterpret_cast<const i32x4*>(xs + mt * 16 * LF_PITCH + o_lo), hi = *reinterpret_cast<const i32x4*>(xs + mt * 16 * LF_PITCH + o_hi);
       fx[mt] = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      if constexpr (MX) sxb[mt] = (int)(ss[wm * 64 + mt * 16 + lr] >> (8 * lg));
     }
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       const i32x4 lo = *reinterpret_cast<const i32x4*>(ws + nt * 16 * LF_PITCH + o_lo), hi = *reinterpret_cast<const i32x4*>(ws + nt * 16 * LF_PITCH + o_hi);
       const i32x8 fw = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt)   // A = W (rows of D = output columns), B = x: the lane holds 4 consecutive output columns
-        acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fx[mt], acc[nt][mt], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+      for (int mt = 0; mt < 4; ++mt) {   // A = W (rows of D = output columns), B = x: the lane holds 4 consecutive output columns
+        if constexpr (MX) {
+          const int swb = (int)(ss[128 + wn * 64 + nt * 16 + lr] >> (8 * lg));
+          acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fx[mt], acc[nt][mt], 0, 0, 0, swb, 0, sxb[mt]);
+        } else {
+          acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fx[mt], acc[nt][mt], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+        }
+      }
     }
     if (ks + 1 < ks1) store_step(buf ^ 1);                 // the other buffer: its readers passed the barrier of the previous step
     __syncthreads();
@@ -187,9 +271,22 @@ __device__ __forceinline__ void lf_zero(f32x4 (&acc)[4][4]) {
     for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
 }
 
-template <typename AT, bool FAST>
-__global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];   // [2 buffers][x tile, w tile][128 rows][128 bytes, swizzled]
+// MX form of the call: E8M0 scale bytes [rows][Kp / 32] in place of the fp32 row scales, and the optional emission of the stored output's own MX rows
+struct LinMxArgs {
+  const uint8_t* xq; const uint8_t* xs; const uint8_t* wq; const uint8_t* ws; void* out;
+  int M, N, Kp;
+  const float* bias; const void* residual; int ldr; const float* row_scale; int rows_per_scale; void* pre_act; int act; float slope; int ldc;
+  uint8_t* q_out; uint8_t* qs_out;   // [M][N] e4m3 bytes and [M][N / 32] scale bytes of the stored output (N % 128 == 0, no residual), or both null
+};
+template <bool MX> struct LinArgsOf { typedef LinFp8Args type; };
+template <> struct LinArgsOf<true> { typedef LinMxArgs type; };
+
+// MX = false: the per-row recipe (val = acc / (sx sw)).  MX = true: the MX recipe (block scales applied by the MFMA, val = acc); out may then be
+// null when q_out is given.  Emission: the stored row (after the activation, rounded to AT) is quantised as quant_rows_mx_kernel would quantise
+// it; a 32-column block is the 16 + 16 columns of lanes lg and lg ^ 1 (lane ^ 16) of the same row, so one exchange gives its maximum.
+template <typename AT, bool FAST, bool MX = false>
+__global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const typename LinArgsOf<MX>::type p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE + (MX ? 2 * LF_SCALES : 0)];   // [2 buffers][x tile, w tile][128 rows][128 bytes, swizzled] (+ [2][scale dwords])
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int lr = lane & 15, lg = lane >> 4;
@@ -198,7 +295,8 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) 
 
   f32x4 acc[4][4];   // [column block nt][row block mt]
   lf_zero(acc);
-  lf_contract(p.xq, p.M, p.wq, p.N, (size_t)p.Kp, row0, col0, 0, p.Kp / LF_BK, lf_smem, acc);
+  if constexpr (MX) lf_contract<true>(p.xq, p.M, p.wq, p.N, (size_t)p.Kp, row0, col0, 0, p.Kp / LF_BK, lf_smem, acc, p.xs, p.ws);
+  else lf_contract(p.xq, p.M, p.wq, p.N, (size_t)p.Kp, row0, col0, 0, p.Kp / LF_BK, lf_smem, acc);
 
   // ---- epilogue on the registers: with the permuted W rows, lane (lr, lg) holds row 16 mt + lr and, over its four blocks nt, the 16
   // consecutive columns 16 lg + 4 nt + j of the wave's 64: 16-byte stores (8 bf16 / 4 fp32), 32 / 64 contiguous bytes per lane and row
@@ -215,18 +313,39 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinFp8Args p) 
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int n = min(c0 + j, p.N - 1);
-      swn[j] = p.sw[n];
+      if constexpr (!MX) swn[j] = p.sw[n];
       bias[j] = p.bias ? p.bias[n] : 0.f;
     }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
       const int m = row0 + wm * 64 + mt * 16 + lr;
       if (m >= p.M) continue;
-      const float sxm = p.sx[m];
+      float sxm = 1.f;
+      if constexpr (!MX) sxm = p.sx[m];
       const float sc = (RES && p.row_scale) ? p.row_scale[m / p.rows_per_scale] : 1.f;
       float v[16];
+      if constexpr (MX) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sxm * swn[j]) + bias[j];
+        for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] + bias[j];
+        if (p.q_out) {   // N % 128 == 0 and no residual (host): all 16 columns are in range and the stored value is act(v)
+          float t[16], am = 0.f;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            t[j] = (float)(AT)apply_act_t<FAST>(v[j], p.act, p.slope);
+            am = fmaxf(am, fabsf(t[j]));
+          }
+          am = fmaxf(am, __shfl_xor(am, 16));              // the partner holds the same row: it is here whenever this lane is
+          const int E = mx_block_exp(am);
+          *reinterpret_cast<uint4*>(p.q_out + (size_t)m * p.N + c0) =
+              make_uint4(pack4_e4m3_mx(t[0], t[1], t[2], t[3], E), pack4_e4m3_mx(t[4], t[5], t[6], t[7], E),
+                         pack4_e4m3_mx(t[8], t[9], t[10], t[11], E), pack4_e4m3_mx(t[12], t[13], t[14], t[15], E));
+          if ((lg & 1) == 0) p.qs_out[(size_t)m * (p.N >> 5) + (c0 >> 5)] = (uint8_t)(E + 127);
+          if (!Y) continue;                                // no backward follows: neither out nor pre_act is stored
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sxm * swn[j]) + bias[j];
+      }
       const size_t o = (size_t)m * p.ldc + c0;
       const size_t orow = (size_t)m * p.ldr + c0;
       if (vecw) {   // N % CV == 0: a piece is in range as a whole
@@ -460,6 +579,7 @@ __global__ __launch_bounds__(256) void quant_cols_write_kernel(const T* __restri
 }
 
 static std::atomic<long long> linear_fp8_launches{0};
+static std::atomic<long long> linear_mxfp8_launches{0}, quant_rows_mx_launches{0};
 static std::atomic<long long> linear_fp8_bwd_launches[2];   // data gradient, weight gradient
 
 // the epilogue forms the data-gradient kernel serves
@@ -535,6 +655,57 @@ extern "C" int sv_linear_fp8(const void* xq, const float* sx, const void* wq, co
   else hipLaunchKernelGGL((linear_fp8_kernel<float, false>), grid, block, 0, s, a);
   const int rc = check_launch("sv_linear_fp8");
   if (rc == SV_OK) linear_fp8_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+extern "C" long long sv_linear_mxfp8_launches(void) { return linear_mxfp8_launches.load(std::memory_order_relaxed); }
+extern "C" long long sv_quant_rows_mx_launches(void) { return quant_rows_mx_launches.load(std::memory_order_relaxed); }
+
+extern "C" int sv_quant_rows_mx_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, void* scales_u8, void* stream) {
+  SV_REQUIRE(src && dst_q && scales_u8, "sv_quant_rows_mx_e4m3: null argument");
+  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_rows_mx_e4m3: bad source dtype %d", src_dtype);
+  SV_REQUIRE(rows > 0 && K > 0 && ld >= K, "sv_quant_rows_mx_e4m3: rows (%d) and K (%d) must be positive, ld (%d) >= K", rows, K, ld);
+  SV_REQUIRE(Kp == cdiv(K, 128) * 128, "sv_quant_rows_mx_e4m3: Kp (%d) must be K (%d) rounded up to a multiple of 128", Kp, K);
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0, "sv_quant_rows_mx_e4m3: dst_q must be 16-byte aligned, scales_u8 4-byte aligned");
+  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0, "sv_quant_rows_mx_e4m3: src is not aligned to its element");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(cdiv(rows, 4));
+  uint8_t* q = static_cast<uint8_t*>(dst_q);
+  uint8_t* sc = static_cast<uint8_t*>(scales_u8);
+  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_rows_mx_kernel<__bf16>, grid, dim3(256), 0, s, static_cast<const __bf16*>(src), rows, K, (long long)ld, q, Kp, sc);
+  else hipLaunchKernelGGL(quant_rows_mx_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(src), rows, K, (long long)ld, q, Kp, sc);
+  const int rc = check_launch("sv_quant_rows_mx_e4m3");
+  if (rc == SV_OK) quant_rows_mx_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+extern "C" int sv_linear_mxfp8(const void* xq, const void* xs, const void* wq, const void* ws, void* out, int M, int K, int N, const sv_epilogue* e,
+                               void* q_out, void* qs_out, int act_dtype, void* stream) {
+  SV_REQUIRE(xq && xs && wq && ws && e, "sv_linear_mxfp8: null argument");
+  SV_REQUIRE(out || q_out, "sv_linear_mxfp8: out may be null only when q_out is given");
+  SV_REQUIRE((q_out != nullptr) == (qs_out != nullptr), "sv_linear_mxfp8: q_out and qs_out go together");
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE(M > 0 && K > 0 && N > 0, "sv_linear_mxfp8: M (%d), K (%d), N (%d) must be positive", M, K, N);
+  const char* why;
+  SV_REQUIRE(linear_fp8_epilogue_ok(e, N, &why), "sv_linear_mxfp8: %s", why);
+  SV_REQUIRE(!q_out || (!e->residual && !e->row_scale), "sv_linear_mxfp8: the emission of the output's MX rows is not served with a residual");
+  SV_REQUIRE(!q_out || N % 128 == 0, "sv_linear_mxfp8: the emission of the output's MX rows needs N (%d) %% 128 == 0", N);
+  SV_REQUIRE(out || !e->pre_act, "sv_linear_mxfp8: pre_act without out");
+  SV_REQUIRE((((uintptr_t)xq | (uintptr_t)wq | (uintptr_t)q_out) & 15) == 0, "sv_linear_mxfp8: quantised operands must be 16-byte aligned");
+  SV_REQUIRE((((uintptr_t)xs | (uintptr_t)ws | (uintptr_t)qs_out) & 3) == 0, "sv_linear_mxfp8: scale bytes must be 4-byte aligned");
+  const uintptr_t amask = act_dtype == SV_BF16 ? 7 : 15;
+  SV_REQUIRE((((uintptr_t)out | (uintptr_t)e->residual | (uintptr_t)e->pre_act) & amask) == 0, "sv_linear_mxfp8: out / residual / pre_act must be aligned to 4 elements");
+  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(N, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_mxfp8: too many tiles");
+  LinMxArgs a{static_cast<const uint8_t*>(xq), static_cast<const uint8_t*>(xs), static_cast<const uint8_t*>(wq), static_cast<const uint8_t*>(ws), out,
+              M, N, cdiv(K, LF_BK) * LF_BK, e->bias, e->residual, e->ldr, e->row_scale, e->rows_per_scale > 0 ? e->rows_per_scale : 1, e->pre_act,
+              e->act, e->slope, e->ldc, static_cast<uint8_t*>(q_out), static_cast<uint8_t*>(qs_out)};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)tiles), block(256);
+  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_kernel<__bf16, true, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((linear_fp8_kernel<float, false, true>), grid, block, 0, s, a);
+  const int rc = check_launch("sv_linear_mxfp8");
+  if (rc == SV_OK) linear_mxfp8_launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }
 

@@ -49,13 +49,13 @@ _P, _I, _L, _F, _U, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_uint3
 _ACT_TYPED = {
     "sv_conv_gather", "sv_tconv_gather", "sv_conv_wgrad", "sv_stencil3_fwd", "sv_stencil3_wgrad", "sv_colsum",
     "sv_layernorm_fwd", "sv_layernorm_quant_fwd", "sv_layernorm_bwd", "sv_ln_image_fwd", "sv_ln_image_bwd", "sv_bn_stats", "sv_scale_shift_act", "sv_bn_bwd", "sv_scale_shift_act_signs", "sv_bn_bwd_signs",
-    "sv_window_attention_fwd", "sv_window_attention_bwd", "sv_cross_view_attention_fwd", "sv_cross_view_attention_bwd",
+    "sv_window_attention_fwd", "sv_window_attention_fwd_mxq", "sv_window_attention_bwd", "sv_cross_view_attention_fwd", "sv_cross_view_attention_bwd",
     "sv_transpose", "sv_add_n", "sv_axpby", "sv_relu_bwd", "sv_maxpool2d_fwd", "sv_maxpool2d_bwd", "sv_avgpool2_fwd", "sv_avgpool2_bwd",
     "sv_decoder_seed_fwd", "sv_decoder_seed_bwd", "sv_maxpool3d_fwd", "sv_maxpool3d_bwd", "sv_dropout", "sv_rowscale",
     "sv_dwconv2x2_fwd", "sv_dwconv2x2_bwd", "sv_upsample3to7_add_fwd", "sv_upsample3to7_bwd",
     "sv_cva_downsample_fwd", "sv_cva_downsample_bwd", "sv_cva_upsample_add_fwd", "sv_cva_upsample_bwd", "sv_decoder_head_fwd", "sv_decoder_head_bwd",
     "sv_merge_views_fwd", "sv_merge_views_bwd", "sv_stem_space_to_depth", "sv_encoder_prep", "sv_encoder_prep_bwd", "sv_bn_act_maxpool_fwd", "sv_bn_maxpool_bwd", "sv_bn_act_maxpool3d_fwd", "sv_bn_maxpool3d_bwd", "sv_head_pack_x", "sv_head_unpack_dx", "sv_swin_attn_block_fwd", "sv_swin_attn_block_bwd",
-    "sv_linear_fp8", "sv_linear_fp8_dgrad",
+    "sv_linear_fp8", "sv_linear_fp8_dgrad", "sv_linear_mxfp8",
 }
 # argument lists WITHOUT the act_dtype / stream tail (added in load())
 _PROTOS = {
@@ -75,6 +75,10 @@ _PROTOS = {
     "sv_linear_fp8_dgrad_supported": (_I, None, [_I, _I, C.POINTER(Epilogue), _I, _I]),
     "sv_linear_fp8_wgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "sv_linear_fp8_bwd_launches": (_L, None, [_I]),
+    "sv_quant_rows_mx_e4m3": (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
+    "sv_linear_mxfp8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(Epilogue), _P, _P]),
+    "sv_linear_mxfp8_launches": (_L, None),
+    "sv_quant_rows_mx_launches": (_L, None),
     "sv_stencil3_fwd": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _L, _L]),
     "sv_stencil3_wgrad_workspace_floats": (C.c_size_t, None, [_I, _I]),
     "sv_stencil3_wgrad": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L]),
@@ -101,6 +105,7 @@ _PROTOS = {
     "sv_scale_shift_act_signs": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _L, _I, _I, _F, _P]),
     "sv_bn_bwd_signs": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _L, _I, _I, _F, _I, _P, _I, _P, _I, _P, _P, _P]),
     "sv_window_attention_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "sv_window_attention_fwd_mxq": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sv_window_attention_bwd_workspace_floats": (C.c_size_t, None, [_I]),
     "sv_window_attention_windows_per_group": (_I, None, [_I, _I, _I, _I, _I, _I]),
     "sv_window_attention_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),

@@ -177,15 +177,23 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         ln1, m1, r1, q1 = _norm_for_linear(x, blk.norm1, M, Cd, blk.s_qkv, blk.attn.qkv.weight, save, bias=blk.attn.qkv.bias)
         qkv = empty(M, 3 * Cd, like=x)
         ops.swin_linear_fwd(ln1, M, blk.s_qkv, blk.attn.qkv.weight, qkv, xq=q1, bias=blk.attn.qkv.bias)
-        att = empty(M, Cd, like=x)
-        # algorithmic work of the core (49-token windows, no padding): QK^T + PV = 4 * 49 * 32 flop per (token, head); bytes: qkv in, out
-        ops.traced_call("sv_window_attention_fwd", 4.0 * 49 * 32 * M * blk.heads, esz * 4 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
-                        ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(), tag=f"M={M} C={Cd}")
         sc1 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
         sc2 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
+        proj_epi = dict(bias=blk.attn.proj.bias, residual=x, ldr=Cd, row_scale=sc1, rows_per_scale=H * W)
+        # algorithmic work of the core (49-token windows, no padding): QK^T + PV = 4 * 49 * 32 flop per (token, head); bytes: qkv in, out
+        if ops.mx_emit_site(blk.s_proj, blk.attn.proj.weight, proj_epi):
+            # MX recipe: the core emits the operand rows of proj (one head of a token = one block); without `save` att itself is not stored
+            att, Kp = (empty(M, Cd, like=x) if save else None), (Cd + 127) // 128 * 128
+            qa = (torch.empty(M, Kp, dtype=torch.uint8, device=x.device), torch.empty(M, Kp // 32, dtype=torch.uint8, device=x.device))
+            ops.traced_call("sv_window_attention_fwd_mxq", 4.0 * 49 * 32 * M * blk.heads, (esz * (4 if save else 3) + 1) * M * Cd, ptr(qkv),
+                            ptr(blk.attn.relative_position_bias_table), ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(),
+                            ptr(qa[0]), Kp, ptr(qa[1]), tag=f"M={M} C={Cd}")
+        else:
+            att, qa = empty(M, Cd, like=x), None
+            ops.traced_call("sv_window_attention_fwd", 4.0 * 49 * 32 * M * blk.heads, esz * 4 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
+                            ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(), tag=f"M={M} C={Cd}")
         x1 = empty(M, Cd, like=x)
-        ops.swin_linear_fwd(att, M, blk.s_proj, blk.attn.proj.weight, x1, bias=blk.attn.proj.bias, residual=x, ldr=Cd, row_scale=sc1,
-                            rows_per_scale=H * W)
+        ops.swin_linear_fwd(att, M, blk.s_proj, blk.attn.proj.weight, x1, xq=qa, **proj_epi)
     if ops.fused_mlp_enabled(Cd):
         # norm2 -> fc1 -> GELU -> fc2 -> drop-path -> +x1 in ONE kernel; the 4C-wide hidden activation never reaches HBM
         packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
@@ -196,12 +204,16 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
                         ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
         return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, packs, None, I)
     ln2, m2, r2, q2 = _norm_for_linear(x1, blk.norm2, M, Cd, blk.s_fc1, blk.mlp.fc1.weight, save, bias=blk.mlp.fc1.bias, act=ACT_GELU)
-    hpre = empty(M, 4 * Cd, like=x)
-    h = empty(M, 4 * Cd, like=x)
-    ops.swin_linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, xq=q2, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
+    fc2_epi = dict(bias=blk.mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2, rows_per_scale=H * W)
+    # MX recipe: fc1 emits the operand rows of fc2 from its epilogue; without `save` neither h nor hpre is allocated or written
+    emit = ops.mx_emit_site(blk.s_fc2, blk.mlp.fc2.weight, fc2_epi, blk.s_fc1, blk.mlp.fc1.weight, dict(bias=blk.mlp.fc1.bias, act=ACT_GELU))
+    hpre = h = None
+    if save or not emit:
+        hpre = empty(M, 4 * Cd, like=x)
+        h = empty(M, 4 * Cd, like=x)
+    qh = ops.swin_linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, xq=q2, emit=emit, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
     x2 = empty(M, Cd, like=x)
-    ops.swin_linear_fwd(h, M, blk.s_fc2, blk.mlp.fc2.weight, x2, bias=blk.mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2,
-                        rows_per_scale=H * W)
+    ops.swin_linear_fwd(h, M, blk.s_fc2, blk.mlp.fc2.weight, x2, xq=qh, **fc2_epi)
     return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, m2, r2, ln2, hpre, h, I)
 
 

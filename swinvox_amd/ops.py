@@ -295,6 +295,7 @@ class PackCache:
         self.tables = {}   # storage dtype -> dict(entries={key: [spec, w, kind, view]}, dirty, flat, descs, sig, nblocks)
         self.w8 = {}       # id(parameter) -> (e4m3 rows, row scales) of the running forward (quantize_weight_fp8); dropped by refresh()
         self.w8t = {}      # id(parameter) -> (e4m3 rows of W^T, their scales) for the fp8 data gradient (quantize_weight_t_fp8); same lifetime
+        self.w8mx = {}     # id(parameter) -> (e4m3 rows, E8M0 block scales) of the MX recipe (quantize_weight_mx); same lifetime
 
     def __deepcopy__(self, memo):
         return PackCache()    # keyed by parameter identity: a copied module starts with an empty cache
@@ -315,7 +316,7 @@ class PackCache:
 
     def refresh(self):
         """(Re)build the descriptor table when the set of packs or a parameter's address changed, then pack everything."""
-        self.w8, self.w8t = {}, {}
+        self.w8, self.w8t, self.w8mx = {}, {}, {}
         t = self._table()
         ents = list(t["entries"].values())
         if not ents:
@@ -552,20 +553,97 @@ def linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
     spec.forward(x, rows, (1, 1, 1), w, out, **epi)
 
 
-def set_linear_fp8(on: bool, backward: bool = False) -> None:
+def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row") -> None:
     """BASELINE configuration 5, linear part: the FORWARD of the Swin linears (qkv, proj, fc1, fc2, patch-merge reduction) on e4m3 operands
     with per-row scales and the block-scaled K = 128 MFMA (csrc/linear_fp8.hip).  The stored tensors are unchanged.  Without `backward` the
     backward is unchanged too (bf16 data and weight gradients: the quantisers are straight-through); with backward=True (effective only
     together with `on`) the data and weight gradients of the unfused Swin sites run on e4m3 operands as well (swin_linear_dgrad /
     swin_linear_wgrad).  Active only under set_math('bf16'); independent of set_attention_fp8.
     Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them).
-    The LayerNorms that feed qkv, fc1 and the reduction emit the quantised rows themselves (set_ln_quant_fused)."""
+    The LayerNorms that feed qkv, fc1 and the reduction emit the quantised rows themselves (set_ln_quant_fused).
+    recipe = "row" (default): one fp32 scale per operand row, divided out in the epilogue.  recipe = "mx": the FORWARD of the same call sites
+    on MX operands - one E8M0 power-of-two scale per 32 consecutive elements of the contraction, applied by the MFMA (sv_linear_mxfp8).  A block
+    scale depends on 32 neighbours only, so fc1 emits the operand rows of fc2 and the window attention those of proj (set_mx_producer_quant);
+    the LayerNorm sites take the stand-alone MX quantiser.  `backward` means the same under either recipe: its quantisers read the stored
+    tensors, which do not change."""
+    if recipe not in ("row", "mx"):
+        raise ValueError(f"set_linear_fp8: recipe must be 'row' or 'mx', not {recipe!r}")
     _STATE["linear_fp8"] = bool(on)
     _STATE["linear_fp8_bwd"] = bool(on) and bool(backward)
+    _STATE["linear_fp8_recipe"] = recipe
 
 
 def linear_fp8_enabled() -> bool:
     return bool(_STATE.get("linear_fp8")) and _STATE["math"] == hip.MATH_BF16
+
+
+def linear_fp8_recipe() -> str:
+    """"row" or "mx": the recipe the fp8 forward of the Swin linears runs (meaningful while linear_fp8_enabled())."""
+    return _STATE.get("linear_fp8_recipe", "row")
+
+
+def _mx() -> bool:
+    return linear_fp8_enabled() and linear_fp8_recipe() == "mx"
+
+
+def set_mx_producer_quant(on: bool) -> None:
+    """A/B switch of the MX producers: True (default) lets fc1 emit the MX operand rows of fc2 and the window attention those of proj; False
+    sends every site through the stand-alone quantiser (sv_quant_rows_mx_e4m3), with bit-identical results.  SV_MX_PRODUCER_QUANT=0 in the
+    environment switches it off as well.  Effective only under recipe "mx"."""
+    _STATE["mx_producer_quant"] = bool(on)
+
+
+def mx_producer_quant_enabled() -> bool:
+    import os
+    return _mx() and _STATE.get("mx_producer_quant", True) and os.environ.get("SV_MX_PRODUCER_QUANT", "1") != "0"
+
+
+_MX_ACT_QUANT = [0]
+
+
+def mx_act_quant_launches() -> int:
+    """Stand-alone MX quantiser launches on ACTIVATIONS of this process so far (weights are not counted)."""
+    return _MX_ACT_QUANT[0]
+
+
+def linear_mxfp8_launches() -> int:
+    """sv_linear_mxfp8 launches of this process so far."""
+    return int(hip.load().sv_linear_mxfp8_launches())
+
+
+def quantize_rows_mx(t: torch.Tensor, rows: int, K: int, ld: Optional[int] = None, activation: bool = True):
+    """t [rows, K] (fp32 or bf16, row stride ld) -> (e4m3 bytes [rows, roundup(K, 128)], E8M0 block scales [rows, roundup(K, 128) / 32] uint8)
+    by sv_quant_rows_mx_e4m3."""
+    Kp = (K + 127) // 128 * 128
+    q = torch.empty(rows, Kp, dtype=torch.uint8, device=t.device)
+    sc = torch.empty(rows, Kp // 32, dtype=torch.uint8, device=t.device)
+    call("sv_quant_rows_mx_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, K, ld or K, ptr(q), Kp, ptr(sc))
+    if activation:
+        _MX_ACT_QUANT[0] += 1
+    return q, sc
+
+
+def quantize_weight_mx(w: torch.Tensor):
+    """MX rows of a Linear weight [N, K], cached like quantize_weight_fp8's for the running forward of the module."""
+    cache = _CTX.packs
+    if cache is None or not isinstance(w, torch.nn.Parameter):
+        return quantize_rows_mx(w, w.shape[0], w.shape[1], activation=False)
+    hit = cache.w8mx.get(id(w))
+    if hit is None:
+        hit = cache.w8mx[id(w)] = quantize_rows_mx(w, w.shape[0], w.shape[1], activation=False)
+    return hit
+
+
+def mx_emit_site(cons_spec: ConvSpec, cons_w, cons_epi: dict, prod_spec: Optional[ConvSpec] = None, prod_w=None, prod_epi: Optional[dict] = None) -> bool:
+    """Whether the producer of a Swin linear's input emits that linear's MX operand rows: recipe "mx", the producer switch on, the consuming
+    linear (cons_*) takes the MX kernel, and - when the producer is a linear itself (prod_*: fc1 in front of fc2) - it takes the MX kernel too,
+    carries no residual and has N % 128 == 0.  With set_linear_fp8 off this is one flag test."""
+    if not mx_producer_quant_enabled() or swin_linear_fp8_epilogue(cons_spec, cons_w, **cons_epi) is None:
+        return False
+    if prod_spec is None:
+        return True
+    return (prod_spec.cout % 128 == 0 and prod_epi.get("residual") is None
+            and swin_linear_fp8_epilogue(prod_spec, prod_w, **prod_epi) is not None)
 
 
 def linear_fp8_bwd_enabled() -> bool:
@@ -615,12 +693,28 @@ def swin_linear_fp8_epilogue(spec: ConvSpec, w, **epi):
     return e if hip.load().sv_linear_fp8_supported(spec.cin, spec.cout, C.byref(e), _STATE["math"], hip.ACT) == 1 else None
 
 
-def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, xq=None, **epi):
+def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, xq=None, emit=False, **epi):
     """linear_fwd of the Swin call sites: with set_linear_fp8(True) (and a form sv_linear_fp8 serves) the activation rows are quantised, the
     quantised weight fetched and the product runs on the fp8 kernel; otherwise exactly linear_fwd.  xq = (bytes, scales): the rows of x
-    already quantised by its producer (layernorm_quant_fwd), which the caller obtained because swin_linear_fp8_epilogue said this linear takes
-    the fp8 kernel; the quantiser pass is skipped and x itself is not read (it may be None)."""
+    already quantised by its producer (layernorm_quant_fwd; under recipe "mx" the MX pair of an emitting fc1 or window attention), which the
+    caller obtained because swin_linear_fp8_epilogue said this linear takes the fp8 kernel; the quantiser pass is skipped and x itself is not
+    read (it may be None).  emit=True (recipe "mx" only, the caller asked mx_emit_site): the kernel also writes the MX rows of its stored
+    output, returned as (bytes, scales); `out` (and pre_act) may then be None, and nothing else is written."""
     e = swin_linear_fp8_epilogue(spec, w, **epi)
+    if e is not None and linear_fp8_recipe() == "mx":
+        xq, xs = xq if xq is not None else quantize_rows_mx(x, rows, spec.cin)
+        wq, ws = quantize_weight_mx(w)
+        q_out = qs_out = None
+        if emit:
+            q_out = torch.empty(rows, spec.cout, dtype=torch.uint8, device=xq.device)
+            qs_out = torch.empty(rows, spec.cout // 32, dtype=torch.uint8, device=xq.device)
+        esz = 0 if out is None else out.element_size()
+        traced_call("sv_linear_mxfp8", 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + (esz + (1 if emit else 0)) * spec.cout) + wq.numel(),
+                    ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(out), rows, spec.cin, spec.cout, C.byref(e), ptr(q_out), ptr(qs_out),
+                    tag=f"M={rows} K={spec.cin} N={spec.cout}")
+        return (q_out, qs_out) if emit else None
+    if emit:
+        raise RuntimeError("swin_linear_fwd: emit=True was passed to a linear that does not take the MX kernel")
     if e is not None:
         xq, sx = xq if xq is not None else quantize_rows_fp8(x, rows, spec.cin)
         wq, sw = quantize_weight_fp8(w)
@@ -728,7 +822,8 @@ def set_ln_quant_fused(on: bool) -> None:
 
 def ln_quant_fused_enabled() -> bool:
     import os
-    return linear_fp8_enabled() and _STATE.get("ln_quant_fused", True) and os.environ.get("SV_LN_QUANT_FUSED", "1") != "0"
+    # recipe "mx": the LayerNorm sites take the stand-alone MX quantiser (the quantising LayerNorm writes per-row scales)
+    return linear_fp8_enabled() and linear_fp8_recipe() == "row" and _STATE.get("ln_quant_fused", True) and os.environ.get("SV_LN_QUANT_FUSED", "1") != "0"
 
 
 def ln_quant_site(spec: ConvSpec, w, **epi) -> bool:
