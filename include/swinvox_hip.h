@@ -170,6 +170,33 @@ int sv_linear_mxfp8(const void* xq, const void* xs, const void* wq, const void* 
                     void* q_out, void* qs_out, int act_dtype, void* stream);
 long long sv_linear_mxfp8_launches(void); /* sv_linear_mxfp8 launches so far in this process (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise) */
 long long sv_quant_rows_mx_launches(void); /* sv_quant_rows_mx_e4m3 launches so far in this process (timm Linear behind models/swin_transformer.py:78, operand preparation; tests) */
+/* MX form of the fp8 BACKWARD of the same Linear layers (timm Linear behind models/swin_transformer.py:78; autograd of F.linear), opt-in.  The block
+ * exponent, the rounding, byte 127 for all-zero and padding blocks, val = acc without clamp or division are the MX forward's; the quantisers are
+ * straight-through and read the stored tensors.
+ * The MX column quantiser (timm Linear behind models/swin_transformer.py:78, operand preparation of the MX backward), one launch and one read of src:
+ * src [M, C] with row stride ld (SV_F32 or SV_BF16) -> dst_q [C][Mp] bytes (the TRANSPOSE, 16-byte aligned, Mp == roundup(M, 128), bytes M .. Mp-1 of
+ * every row zero) and scales_u8 [C][Mp / 32] (4-byte aligned; a block = 32 consecutive rows m of one column; blocks wholly past M carry 127), equal
+ * bit for bit to sv_quant_rows_mx_e4m3 on the transposed tensor.  colsum (optional, [C] fp32): colsum[c] += sum_m src[m, c] from the unquantised
+ * values.  On the [N, K] fp32 weight it yields the [K][Np] operand of the data gradient. */
+int sv_quant_cols_mx_e4m3(const void* src, int src_dtype, int M, int C, int ld, void* dst_q, int Mp, void* scales_u8, float* colsum, void* stream);
+/* data gradient dx[m, k] = sum_n 2^(ds + wts - 254) dq[m, n] wtq[k, n] (timm Linear behind models/swin_transformer.py:78, gradient with respect to the
+ * input).  dq [M, Np] / ds [M, Np / 32] from the MX row quantiser on dy, wtq [K, Np] / wts [K, Np / 32] from the MX column quantiser on W [N, K].
+ * Epilogue forms and refusals are exactly sv_linear_fp8_dgrad's (sv_linear_fp8_dgrad_supported answers for both). */
+int sv_linear_mxfp8_dgrad(const void* dq, const void* ds, const void* wtq, const void* wts, void* dx, int M, int N, int K, const sv_epilogue* e,
+                          int act_dtype, void* stream);
+/* floats of the workspace sv_linear_mxfp8_wgrad needs for this call (timm Linear behind models/swin_transformer.py:78): resulting splits * N * K, and 0
+ * when one split results (no workspace is read then). */
+size_t sv_linear_mxfp8_wgrad_workspace_floats(int M, int N, int K, int splits);
+/* weight gradient dw[n * ldw + k] += sum_m 2^(dys + xs - 254) dyt[n, m] xt[k, m] (timm Linear behind models/swin_transformer.py:78, gradient with
+ * respect to the weight), WITHOUT atomics: dw is bit-identical from run to run for a given `splits`.  dyt [N, Mp] / dys [N, Mp / 32] and xt [K, Mp] /
+ * xs [K, Mp / 32] from the MX column quantiser on dy [M, N] and x [M, K].  The contraction over the tokens is shared among `splits` workgroups per
+ * 128 x 128 tile of dw (at most one per 128 tokens; 0 = as many as give two workgroups to each of 256 CUs).  One resulting split adds into dw
+ * directly; more write fp32 partials into `workspace` (16-byte aligned, caller-owned, contents destroyed, stale contents never read) and a second
+ * kernel adds them to dw in ascending order.  SV_ERR_INVALID: more than one resulting split with a NULL workspace. */
+int sv_linear_mxfp8_wgrad(const void* dyt, const void* dys, const void* xt, const void* xs, float* dw, int M, int N, int K, int ldw, int splits,
+                          float* workspace, void* stream);
+long long sv_linear_mxfp8_bwd_launches(int which); /* launches so far of sv_linear_mxfp8_dgrad (which = 0) / sv_linear_mxfp8_wgrad (1) (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise); the row recipe's counters do not move */
+long long sv_quant_cols_mx_launches(void); /* sv_quant_cols_mx_e4m3 launches so far in this process (timm Linear behind models/swin_transformer.py:78, operand preparation; tests) */
 /* LDS-halo MFMA stencils for 3x3x3 / stride 1 / pad 1 convolutions with <= 16 output channels per tile (merger.py:20-54),
  * bf16 operands.  x: channels-last positions with row stride ldx, cin_load (multiple of 4) elements read per position,
  * zero-extended to 16*groups channels; w_bf16: [16*ntiles16][27][16*groups] bf16 (forward: rows = output channels;

@@ -3,7 +3,9 @@ the stock torch.optim sequence, next to forward+backward alone.  python scripts/
 --fp8-linear: forward+backward alone with the fp8 Swin linears (set_linear_fp8) off and on, same process.
 --fp8-linear-bwd: the same with a third run, set_linear_fp8(True, backward=True): data and weight gradients of the linears in e4m3 too.
 --fp8-linear-mx: forward+backward alone, alternating (two rounds, one process) bf16, the row recipe, the MX recipe with producer emission and
-the MX recipe with the stand-alone quantiser everywhere (set_mx_producer_quant(False))."""
+the MX recipe with the stand-alone quantiser everywhere (set_mx_producer_quant(False)).
+--fp8-linear-mx-bwd: forward+backward alone, alternating (two rounds, one process) bf16, the row-recipe forward + backward, the MX forward with
+the row-recipe backward, and the MX forward with the MX backward (backward_recipe="mx")."""
 import argparse
 import os
 import sys
@@ -23,6 +25,7 @@ ap.add_argument("--steps", type=int, default=6)
 ap.add_argument("--fp8-linear", action="store_true", help="time forward+backward only, with set_linear_fp8 off and on")
 ap.add_argument("--fp8-linear-bwd", action="store_true", help="as --fp8-linear, plus a run with the fp8 backward of the linears")
 ap.add_argument("--fp8-linear-mx", action="store_true", help="forward+backward only: bf16, row recipe, MX with and without producer emission, two rounds")
+ap.add_argument("--fp8-linear-mx-bwd", action="store_true", help="forward+backward only: bf16, row fwd + bwd, MX fwd + row bwd, MX fwd + MX bwd, two rounds")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = S.default_cfg()
@@ -44,11 +47,13 @@ def timed(fn, n):
 
 
 MX_MODES = (None, "fp8", "mx", "mx-noemit")
-for fused in (MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
+MX_BWD_MODES = (None, "fp8+bwd", "mx+bwd", "mx+mxbwd")
+for fused in (MX_BWD_MODES * 2 if a.fp8_linear_mx_bwd else MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
     torch.manual_seed(0)
     nets = [m(cfg).to(dev).train() for m in (Encoder, Decoder, Merger, Refiner)]
-    fp8 = fused in ("fp8", "fp8+bwd", "mx", "mx-noemit")
-    S.set_linear_fp8(fp8, backward=fused == "fp8+bwd", recipe="mx" if fused in ("mx", "mx-noemit") else "row")
+    fp8 = fused in ("fp8", "fp8+bwd", "mx", "mx-noemit", "mx+bwd", "mx+mxbwd")
+    S.set_linear_fp8(fp8, backward=fused in ("fp8+bwd", "mx+bwd", "mx+mxbwd"), recipe="mx" if fused in ("mx", "mx-noemit", "mx+bwd", "mx+mxbwd") else "row",
+                     backward_recipe="mx" if fused == "mx+mxbwd" else "row")
     ops.set_mx_producer_quant(fused != "mx-noemit")
     if fused is None or fp8:
         def step():
@@ -56,7 +61,8 @@ for fused in (MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a
                 n.zero_grad(set_to_none=True)
             harness.forward_losses(nets, cfg, x, gt)[0].backward()
         name = "forward+backward only" + {"fp8": ", fp8 Swin linears", "fp8+bwd": ", fp8 Swin linears fwd + bwd", "mx": ", MX Swin linears, emission",
-                                          "mx-noemit": ", MX Swin linears, quantiser"}.get(fused, "")
+                                          "mx-noemit": ", MX Swin linears, quantiser", "mx+bwd": ", MX Swin linears fwd + row-recipe bwd",
+                                          "mx+mxbwd": ", MX Swin linears fwd + MX bwd"}.get(fused, "")
     else:
         solvers, _ = harness.make_solvers(nets, cfg, fused=fused)
         def step():

@@ -86,6 +86,29 @@
 //   linear_fp8_wgrad_kernel   grid tiles(N) x tiles(K) x splits, split z contracts the k-steps [z nk / splits, (z + 1) nk / splits); dy^T is the
 //                    row operand, so a lane's 16 consecutive outputs run along k, the contiguous dimension of dw; fp32 atomicAdd into dw
 //                    (a plain read-add-write when splits == 1).  splits = 0 picks enough workgroups for 2 per CU of 256 CUs.
+//
+// MX backward (opt-in: set_linear_fp8(True, backward=True, backward_recipe="mx")): both gradients on MX operands.  A block scale over 32 TOKENS of a
+// column needs no global maximum, so the transposing quantiser is one launch and one read, and nothing is left to divide out.  NORMATIVE: everything
+// is the MX forward's - the block exponent, the rounding, "nothing saturates", byte 127 for all-zero and padding blocks, val = acc, no clamp, no
+// division.  The quantisers are straight-through and read the stored bf16 / fp32 tensors.
+//   data gradient    dx[M, K] = dy[M, N] W[N, K], contraction over N.  dy from quant_rows_mx_kernel (blocks along n); W^T as [K][Np] bytes +
+//                    [K][Np / 32] scale bytes, a block = 32 consecutive n of one column k (the column quantiser below on the [N, K] fp32 weight).
+//                    Epilogue forms and refusals are exactly the row recipe's: none, act_grad_src with SV_ACT_GELU, ldc.
+//   weight gradient  dw[N, K] += dy^T[N, M] x[M, K], contraction over M.  dy^T as [N][Mp] bytes + [N][Mp / 32] scale bytes, x^T as [K][Mp] bytes +
+//                    [K][Mp / 32] scale bytes, Mp = roundup(M, 128); a block = 32 consecutive TOKENS of one column.  Bytes past M are zero, blocks
+//                    wholly past M carry 127.  db[n] += sum_m dy[m, n] in fp32 from the unquantised dy in the quantiser's pass.
+//   column quantiser its output EQUALS quant_rows_mx_kernel applied to the transposed stored tensor, bit for bit: a partly filled last block takes
+//                    the maximum of its valid rows.
+// Kernels of the MX backward
+//   quant_cols_mx_kernel   ONE launch, src read once: the 128-row x 64-column tile of quant_cols_write_kernel; thread (tx, ty) owns rows 32 ty .. + 31
+//                    of column tx = exactly one MX block, so the block maximum stays in its registers (32 values held, no exchange).  8 packed dwords
+//                    go through the same LDS transpose (pitch 33 dwords) into 16-byte stores along M; the four scale bytes of a column and tile are
+//                    gathered in LDS into one dword store.  Column sums: fp64 partial per workgroup, one fp32 atomic per workgroup and column.
+//   linear_fp8_dgrad_kernel<.., MX = true>   lf_contract<true> + the epilogue above without its 16 divisions per lane and row; LDS 67 584 bytes.
+//   linear_mxfp8_wgrad_kernel   lf_contract<true> over split z's k-steps; NO atomics into dw.  One split: the only writer of an element does a
+//                    16-byte read-add-write into dw.  More: split z stores its fp32 partial tile into a caller-owned workspace [splits][N][K]
+//                    (16-byte stores) and linear_mxfp8_wgrad_reduce_kernel adds the partials to dw in ascending z: dw is bit-identical from run to
+//                    run for a given `splits`.  splits = 0: enough workgroups for two per CU of 256 CUs, at most one per 128 tokens.
 #include "common.h"
 #include <atomic>
 
@@ -407,9 +430,18 @@ struct LinFp8DgradArgs {
   const void* act_grad_src; int act_grad_kind; float slope; int ldc;
 };
 
-template <typename AT, bool FAST>
-__global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const LinFp8DgradArgs p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];
+// MX form of the call: E8M0 scale bytes [M][Np / 32] of dy and [K][Np / 32] of W^T in place of the fp32 scales
+struct LinMxDgradArgs {
+  const uint8_t* dq; const uint8_t* ds; const uint8_t* wtq; const uint8_t* wts; void* out;
+  int M, K, Np;
+  const void* act_grad_src; int act_grad_kind; float slope; int ldc;
+};
+template <bool MX> struct DgradArgsOf { typedef LinFp8DgradArgs type; };
+template <> struct DgradArgsOf<true> { typedef LinMxDgradArgs type; };
+
+template <typename AT, bool FAST, bool MX = false>
+__global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const typename DgradArgsOf<MX>::type p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE + (MX ? 2 * LF_SCALES : 0)];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int lr = lane & 15, lg = lane >> 4;
@@ -418,7 +450,8 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const LinFp8Dg
 
   f32x4 acc[4][4];
   lf_zero(acc);
-  lf_contract(p.dq, p.M, p.wtq, p.K, (size_t)p.Np, row0, col0, 0, p.Np / LF_BK, lf_smem, acc);
+  if constexpr (MX) lf_contract<true>(p.dq, p.M, p.wtq, p.K, (size_t)p.Np, row0, col0, 0, p.Np / LF_BK, lf_smem, acc, p.ds, p.wts);
+  else lf_contract(p.dq, p.M, p.wtq, p.K, (size_t)p.Np, row0, col0, 0, p.Np / LF_BK, lf_smem, acc);
 
   AT* __restrict__ Y = static_cast<AT*>(p.out);
   const AT* __restrict__ G = static_cast<const AT*>(p.act_grad_src);   // layout of the output
@@ -427,16 +460,23 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const LinFp8Dg
   const int c0 = col0 + wn * 64 + lg * 16;
   if (c0 >= p.K) return;
   float swk[16];
+  if constexpr (!MX) {
 #pragma unroll
-  for (int j = 0; j < 16; ++j) swk[j] = p.swt[min(c0 + j, p.K - 1)];
+    for (int j = 0; j < 16; ++j) swk[j] = p.swt[min(c0 + j, p.K - 1)];
+  }
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
     const int m = row0 + wm * 64 + mt * 16 + lr;
     if (m >= p.M) continue;
-    const float sdm = p.sd[m];
     float v[16];
+    if constexpr (MX) {                                    // the MFMA applied both block scales: val = acc
 #pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sdm * swk[j]);
+      for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3];
+    } else {
+      const float sdm = p.sd[m];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sdm * swk[j]);
+    }
     const size_t o = (size_t)m * p.ldc + c0;
     if (vecw) {   // K % CV == 0: a piece is in range as a whole
 #pragma unroll
@@ -509,6 +549,91 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_wgrad_kernel(const LinFp8Wg
   }
 }
 
+// ---- MX weight gradient: the same contraction on MX operands, no atomics into dw ----------------------------------------------------------------
+struct LinMxWgradArgs {
+  const uint8_t* dyt; const uint8_t* dys; const uint8_t* xt; const uint8_t* xs; float* dw; float* ws;   // ws [splits][N][K] fp32, used when splits > 1
+  int N, K, Mp, ldw, splits;
+};
+
+__global__ __launch_bounds__(256, 2) void linear_mxfp8_wgrad_kernel(const LinMxWgradArgs p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE + 2 * LF_SCALES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int tiles_k = (p.K + LF_BN - 1) / LF_BN;
+  const int row0 = (blockIdx.x / tiles_k) * LF_BM, col0 = (blockIdx.x % tiles_k) * LF_BN;   // rows of dw = n, columns = k
+  const int nk = p.Mp / LF_BK, z = blockIdx.y;
+  const int ks0 = (int)((long long)z * nk / p.splits), ks1 = (int)((long long)(z + 1) * nk / p.splits);   // splits <= nk: no share is empty
+
+  f32x4 acc[4][4];
+  lf_zero(acc);
+  // dy^T is the row operand and x^T the permuted one: a lane's 16 consecutive outputs run along k, the contiguous dimension of dw
+  lf_contract<true>(p.dyt, p.N, p.xt, p.K, (size_t)p.Mp, row0, col0, ks0, ks1, lf_smem, acc, p.dys, p.xs);
+
+  const int c0 = col0 + wn * 64 + lg * 16;
+  if (c0 >= p.K) return;
+  // one split: read-add-write into dw (row stride ldw), this lane is the only writer of its elements; more: a plain store of the partial
+  // into slice z of the workspace (row stride K), which the reduce kernel folds into dw
+  const bool one = p.splits == 1;
+  float* __restrict__ base = one ? p.dw : p.ws + (size_t)z * p.N * p.K;
+  const int ldo = one ? p.ldw : p.K;
+  const bool vec = ((ldo | p.K) & 3) == 0 && (((uintptr_t)base) & 15) == 0;   // K % 4 == 0: a 16-byte piece is in range as a whole
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int n = row0 + wm * 64 + mt * 16 + lr;
+    if (n >= p.N) continue;
+    float* __restrict__ d = base + (size_t)n * ldo + c0;
+    if (vec) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (c0 + q * 4 >= p.K) break;
+        float4 t = make_float4(acc[q][mt][0], acc[q][mt][1], acc[q][mt][2], acc[q][mt][3]);
+        if (one) {
+          const float4 o = *reinterpret_cast<const float4*>(d + q * 4);
+          t = make_float4(o.x + t.x, o.y + t.y, o.z + t.z, o.w + t.w);
+        }
+        *reinterpret_cast<float4*>(d + q * 4) = t;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        if (c0 + j < p.K) {
+          const float val = acc[j >> 2][mt][j & 3];
+          d[j] = one ? d[j] + val : val;
+        }
+      }
+    }
+  }
+}
+
+// dw[n, k] += ws[0][n, k] + ws[1][n, k] + ...: the partials are added in ascending z, one after the other, so the sum does not depend on the run
+__global__ __launch_bounds__(256) void linear_mxfp8_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int N, int K, int ldw, int splits,
+                                                                        int vec) {
+  const size_t slice = (size_t)N * K;
+  if (vec) {                                               // K % 4 == 0, ldw % 4 == 0, both bases 16-byte aligned
+    const int kq = K >> 2;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)N * kq) return;
+    const int n = (int)(i / kq), k = (int)(i % kq) * 4;
+    float4* d = reinterpret_cast<float4*>(dw + (size_t)n * ldw + k);
+    float4 s = *d;
+    const float* w = ws + (size_t)n * K + k;
+#pragma unroll 4
+    for (int z = 0; z < splits; ++z) {
+      const float4 t = *reinterpret_cast<const float4*>(w + z * slice);
+      s = make_float4(s.x + t.x, s.y + t.y, s.z + t.z, s.w + t.w);
+    }
+    *d = s;
+  } else {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= slice) return;
+    const int n = (int)(i / K), k = (int)(i % K);
+    float s = dw[(size_t)n * ldw + k];
+    for (int z = 0; z < splits; ++z) s += ws[z * slice + i];
+    dw[(size_t)n * ldw + k] = s;
+  }
+}
+
 // ---- column quantiser: src [M, C] (row stride ld) -> dst [C][Mp] e4m3 bytes, one scale per column ---------------------------------------------------
 constexpr int QC_COLS = 64, QC_ROWS1 = 256, QC_ROWS2 = 128, QC_PITCH = 33;   // pass-2 LDS rows: 32 dwords + 1, conflict-free on both sides
 
@@ -578,7 +703,53 @@ __global__ __launch_bounds__(256) void quant_cols_write_kernel(const T* __restri
   }
 }
 
+// MX column quantiser: src [M, C] -> dst [C][Mp] e4m3 bytes + scales [C][Mp / 32] E8M0 bytes, equal to quant_rows_mx_kernel on the transposed tensor.
+// The tile of quant_cols_write_kernel; thread (tx, ty) owns rows 32 ty .. + 31 of column tx, which is exactly one MX block: its 32 values stay in
+// registers between the maximum and the packing, and src is read once.  Rows past M are zeros: a partly filled block takes the maximum of its valid
+// rows, a block wholly past M is an all-zero block (byte 127).  colsum as in quant_cols_amax_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void quant_cols_mx_kernel(const T* __restrict__ src, int M, int C, long long ld, uint8_t* __restrict__ dst, int Mp,
+                                                            uint8_t* __restrict__ scales, float* __restrict__ colsum) {
+  __shared__ uint32_t tile[QC_COLS * QC_PITCH];            // [column][32 dwords = 128 rows]
+  __shared__ uint32_t sbytes[QC_COLS];                     // [column][4 blocks of the tile]: one dword per column
+  __shared__ double ssum[4][QC_COLS];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c0 = blockIdx.x * QC_COLS, m0 = blockIdx.y * QC_ROWS2;
+  const int c = c0 + tx, mb = m0 + ty * 32;
+  float v[32];
+  float am = 0.f;
+  double sum = 0.0;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    v[j] = (c < C && mb + j < M) ? ldf(src + (size_t)(mb + j) * ld + c) : 0.f;
+    am = fmaxf(am, fabsf(v[j]));
+  }
+  if (colsum) {
+#pragma unroll
+    for (int j = 0; j < 32; ++j) sum += (double)v[j];
+    ssum[ty][tx] = sum;
+  }
+  const int E = mx_block_exp(am);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) tile[tx * QC_PITCH + ty * 8 + i] = pack4_e4m3_mx(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], E);
+  reinterpret_cast<uint8_t*>(sbytes)[tx * 4 + ty] = (uint8_t)(E + 127);
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {                            // 64 columns x 8 pieces of 16 bytes
+    const int pc = threadIdx.x + 256 * i, col = pc >> 3, piece = pc & 7;
+    if (c0 + col < C) {
+      const uint32_t* t = tile + col * QC_PITCH + piece * 4;
+      *reinterpret_cast<uint4*>(dst + (size_t)(c0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
+    }
+  }
+  if (ty == 0 && c < C) {
+    reinterpret_cast<uint32_t*>(scales + (size_t)c * (Mp >> 5))[m0 >> 7] = sbytes[tx];   // the tile's four blocks of column c: one aligned dword
+    if (colsum) atomicAdd(colsum + c, (float)(ssum[0][tx] + ssum[1][tx] + ssum[2][tx] + ssum[3][tx]));
+  }
+}
+
 static std::atomic<long long> linear_fp8_launches{0};
+static std::atomic<long long> linear_mxfp8_bwd_launches[2], quant_cols_mx_launches{0};   // MX data gradient, MX weight gradient; the MX column quantiser
 static std::atomic<long long> linear_mxfp8_launches{0}, quant_rows_mx_launches{0};
 static std::atomic<long long> linear_fp8_bwd_launches[2];   // data gradient, weight gradient
 
@@ -777,5 +948,96 @@ extern "C" int sv_linear_fp8_wgrad(const void* dyt, const float* sdc, const void
   hipLaunchKernelGGL(linear_fp8_wgrad_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   const int rc = check_launch("sv_linear_fp8_wgrad");
   if (rc == SV_OK) linear_fp8_bwd_launches[1].fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+// ---- MX backward --------------------------------------------------------------------------------------------------------------------------------
+extern "C" long long sv_linear_mxfp8_bwd_launches(int which) {
+  return (which == 0 || which == 1) ? linear_mxfp8_bwd_launches[which].load(std::memory_order_relaxed) : -1;
+}
+extern "C" long long sv_quant_cols_mx_launches(void) { return quant_cols_mx_launches.load(std::memory_order_relaxed); }
+
+extern "C" int sv_quant_cols_mx_e4m3(const void* src, int src_dtype, int M, int C, int ld, void* dst_q, int Mp, void* scales_u8, float* colsum, void* stream) {
+  SV_REQUIRE(src && dst_q && scales_u8, "sv_quant_cols_mx_e4m3: null argument");
+  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_cols_mx_e4m3: bad source dtype %d", src_dtype);
+  SV_REQUIRE(M > 0 && C > 0 && ld >= C, "sv_quant_cols_mx_e4m3: M (%d) and C (%d) must be positive, ld (%d) >= C", M, C, ld);
+  SV_REQUIRE(Mp >= M && Mp % 128 == 0 && Mp - M < 128, "sv_quant_cols_mx_e4m3: Mp (%d) must be M (%d) rounded up to a multiple of 128", Mp, M);
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0, "sv_quant_cols_mx_e4m3: dst_q must be 16-byte aligned, scales_u8 4-byte aligned");
+  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0 && ((uintptr_t)colsum & 3) == 0, "sv_quant_cols_mx_e4m3: src / colsum are not aligned to their element");
+  SV_REQUIRE(cdiv(M, QC_ROWS2) <= 65535, "sv_quant_cols_mx_e4m3: M (%d) is too large", M);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(cdiv(C, QC_COLS), Mp / QC_ROWS2);
+  uint8_t* q = static_cast<uint8_t*>(dst_q);
+  uint8_t* sc = static_cast<uint8_t*>(scales_u8);
+  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_cols_mx_kernel<__bf16>, grid, dim3(256), 0, s, static_cast<const __bf16*>(src), M, C, (long long)ld, q, Mp, sc, colsum);
+  else hipLaunchKernelGGL(quant_cols_mx_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(src), M, C, (long long)ld, q, Mp, sc, colsum);
+  const int rc = check_launch("sv_quant_cols_mx_e4m3");
+  if (rc == SV_OK) quant_cols_mx_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+extern "C" int sv_linear_mxfp8_dgrad(const void* dq, const void* ds, const void* wtq, const void* wts, void* dx, int M, int N, int K, const sv_epilogue* e,
+                                     int act_dtype, void* stream) {
+  SV_REQUIRE(dq && ds && wtq && wts && dx && e, "sv_linear_mxfp8_dgrad: null argument");
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE(M > 0 && N > 0 && K > 0, "sv_linear_mxfp8_dgrad: M (%d), N (%d), K (%d) must be positive", M, N, K);
+  const char* why;
+  SV_REQUIRE(linear_fp8_dgrad_epilogue_ok(e, K, &why), "sv_linear_mxfp8_dgrad: %s", why);
+  SV_REQUIRE((((uintptr_t)dq | (uintptr_t)wtq) & 15) == 0, "sv_linear_mxfp8_dgrad: quantised operands must be 16-byte aligned");
+  SV_REQUIRE((((uintptr_t)ds | (uintptr_t)wts) & 3) == 0, "sv_linear_mxfp8_dgrad: scale bytes must be 4-byte aligned");
+  const uintptr_t amask = act_dtype == SV_BF16 ? 1 : 3;
+  SV_REQUIRE((((uintptr_t)dx | (uintptr_t)e->act_grad_src) & amask) == 0, "sv_linear_mxfp8_dgrad: dx / act_grad_src are not aligned to their element");
+  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(K, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_mxfp8_dgrad: too many tiles");
+  LinMxDgradArgs a{static_cast<const uint8_t*>(dq), static_cast<const uint8_t*>(ds), static_cast<const uint8_t*>(wtq), static_cast<const uint8_t*>(wts), dx,
+                   M, K, cdiv(N, LF_BK) * LF_BK, e->act_grad_src, e->act_grad_kind, e->slope, e->ldc};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)tiles), block(256);
+  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_dgrad_kernel<__bf16, true, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((linear_fp8_dgrad_kernel<float, false, true>), grid, block, 0, s, a);
+  const int rc = check_launch("sv_linear_mxfp8_dgrad");
+  if (rc == SV_OK) linear_mxfp8_bwd_launches[0].fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+// the number of splits a call resolves to: the request (0 = two workgroups for each of 256 CUs), at most one per 128 tokens and the grid's y limit
+static int mxfp8_wgrad_splits(int M, int N, int K, int splits) {
+  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
+  const int nk = cdiv(M, LF_BK);
+  if (splits == 0) splits = (int)((2 * 256 + tiles - 1) / tiles);
+  splits = splits < nk ? splits : nk;
+  return splits > 65535 ? 65535 : splits;
+}
+
+extern "C" size_t sv_linear_mxfp8_wgrad_workspace_floats(int M, int N, int K, int splits) {
+  if (M <= 0 || N <= 0 || K <= 0 || splits < 0) return 0;
+  const int sp = mxfp8_wgrad_splits(M, N, K, splits);
+  return sp > 1 ? (size_t)sp * (size_t)N * (size_t)K : 0;
+}
+
+extern "C" int sv_linear_mxfp8_wgrad(const void* dyt, const void* dys, const void* xt, const void* xs, float* dw, int M, int N, int K, int ldw, int splits,
+                                     float* workspace, void* stream) {
+  SV_REQUIRE(dyt && dys && xt && xs && dw, "sv_linear_mxfp8_wgrad: null argument");
+  SV_REQUIRE(M > 0 && N > 0 && K > 0 && ldw >= K, "sv_linear_mxfp8_wgrad: M (%d), N (%d), K (%d) must be positive, ldw (%d) >= K", M, N, K, ldw);
+  SV_REQUIRE(splits >= 0, "sv_linear_mxfp8_wgrad: splits (%d) must be >= 0", splits);
+  SV_REQUIRE((((uintptr_t)dyt | (uintptr_t)xt) & 15) == 0 && (((uintptr_t)dys | (uintptr_t)xs | (uintptr_t)dw) & 3) == 0, "sv_linear_mxfp8_wgrad: operands are not aligned");
+  SV_REQUIRE(((uintptr_t)workspace & 15) == 0, "sv_linear_mxfp8_wgrad: workspace must be 16-byte aligned");
+  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_mxfp8_wgrad: too many tiles");
+  const int nk = cdiv(M, LF_BK);
+  splits = mxfp8_wgrad_splits(M, N, K, splits);
+  SV_REQUIRE(splits == 1 || workspace, "sv_linear_mxfp8_wgrad: %d splits need a workspace of sv_linear_mxfp8_wgrad_workspace_floats floats", splits);
+  LinMxWgradArgs a{static_cast<const uint8_t*>(dyt), static_cast<const uint8_t*>(dys), static_cast<const uint8_t*>(xt), static_cast<const uint8_t*>(xs), dw,
+                   workspace, N, K, nk * LF_BK, ldw, splits};
+  const int vec = ((K | ldw) & 3) == 0 && ((uintptr_t)dw & 15) == 0;   // the reduce kernel's 16-byte form
+  const size_t items = vec ? (size_t)N * (K >> 2) : (size_t)N * K;
+  SV_REQUIRE(items / 256 + 1 < (1ull << 31), "sv_linear_mxfp8_wgrad: dw is too large");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(linear_mxfp8_wgrad_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, s, a);
+  if (splits > 1) {
+    hipLaunchKernelGGL(linear_mxfp8_wgrad_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, workspace, dw, N, K, ldw, splits, vec);
+  }
+  const int rc = check_launch("sv_linear_mxfp8_wgrad");
+  if (rc == SV_OK) linear_mxfp8_bwd_launches[1].fetch_add(1, std::memory_order_relaxed);
   return rc;
 }

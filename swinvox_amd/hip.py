@@ -55,7 +55,7 @@ _ACT_TYPED = {
     "sv_dwconv2x2_fwd", "sv_dwconv2x2_bwd", "sv_upsample3to7_add_fwd", "sv_upsample3to7_bwd",
     "sv_cva_downsample_fwd", "sv_cva_downsample_bwd", "sv_cva_upsample_add_fwd", "sv_cva_upsample_bwd", "sv_decoder_head_fwd", "sv_decoder_head_bwd",
     "sv_merge_views_fwd", "sv_merge_views_bwd", "sv_stem_space_to_depth", "sv_encoder_prep", "sv_encoder_prep_bwd", "sv_bn_act_maxpool_fwd", "sv_bn_maxpool_bwd", "sv_bn_act_maxpool3d_fwd", "sv_bn_maxpool3d_bwd", "sv_head_pack_x", "sv_head_unpack_dx", "sv_swin_attn_block_fwd", "sv_swin_attn_block_bwd",
-    "sv_linear_fp8", "sv_linear_fp8_dgrad", "sv_linear_mxfp8",
+    "sv_linear_fp8", "sv_linear_fp8_dgrad", "sv_linear_mxfp8", "sv_linear_mxfp8_dgrad",
 }
 # argument lists WITHOUT the act_dtype / stream tail (added in load())
 _PROTOS = {
@@ -79,6 +79,12 @@ _PROTOS = {
     "sv_linear_mxfp8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(Epilogue), _P, _P]),
     "sv_linear_mxfp8_launches": (_L, None),
     "sv_quant_rows_mx_launches": (_L, None),
+    "sv_quant_cols_mx_e4m3": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "sv_linear_mxfp8_dgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(Epilogue)]),
+    "sv_linear_mxfp8_wgrad_workspace_floats": (C.c_size_t, None, [_I, _I, _I, _I]),
+    "sv_linear_mxfp8_wgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "sv_linear_mxfp8_bwd_launches": (_L, None, [_I]),
+    "sv_quant_cols_mx_launches": (_L, None),
     "sv_stencil3_fwd": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _L, _L]),
     "sv_stencil3_wgrad_workspace_floats": (C.c_size_t, None, [_I, _I]),
     "sv_stencil3_wgrad": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L]),

@@ -296,6 +296,7 @@ class PackCache:
         self.w8 = {}       # id(parameter) -> (e4m3 rows, row scales) of the running forward (quantize_weight_fp8); dropped by refresh()
         self.w8t = {}      # id(parameter) -> (e4m3 rows of W^T, their scales) for the fp8 data gradient (quantize_weight_t_fp8); same lifetime
         self.w8mx = {}     # id(parameter) -> (e4m3 rows, E8M0 block scales) of the MX recipe (quantize_weight_mx); same lifetime
+        self.w8mxt = {}    # id(parameter) -> (e4m3 rows of W^T, their E8M0 block scales) for the MX data gradient (quantize_weight_t_mx); same lifetime
 
     def __deepcopy__(self, memo):
         return PackCache()    # keyed by parameter identity: a copied module starts with an empty cache
@@ -316,7 +317,7 @@ class PackCache:
 
     def refresh(self):
         """(Re)build the descriptor table when the set of packs or a parameter's address changed, then pack everything."""
-        self.w8, self.w8t, self.w8mx = {}, {}, {}
+        self.w8, self.w8t, self.w8mx, self.w8mxt = {}, {}, {}, {}
         t = self._table()
         ents = list(t["entries"].values())
         if not ents:
@@ -553,7 +554,7 @@ def linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
     spec.forward(x, rows, (1, 1, 1), w, out, **epi)
 
 
-def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row") -> None:
+def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backward_recipe: str = "row") -> None:
     """BASELINE configuration 5, linear part: the FORWARD of the Swin linears (qkv, proj, fc1, fc2, patch-merge reduction) on e4m3 operands
     with per-row scales and the block-scaled K = 128 MFMA (csrc/linear_fp8.hip).  The stored tensors are unchanged.  Without `backward` the
     backward is unchanged too (bf16 data and weight gradients: the quantisers are straight-through); with backward=True (effective only
@@ -565,12 +566,19 @@ def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row") -> Non
     on MX operands - one E8M0 power-of-two scale per 32 consecutive elements of the contraction, applied by the MFMA (sv_linear_mxfp8).  A block
     scale depends on 32 neighbours only, so fc1 emits the operand rows of fc2 and the window attention those of proj (set_mx_producer_quant);
     the LayerNorm sites take the stand-alone MX quantiser.  `backward` means the same under either recipe: its quantisers read the stored
-    tensors, which do not change."""
+    tensors, which do not change.
+    backward_recipe = "row" (default): the backward above, whatever the forward recipe.  backward_recipe = "mx" (effective only with `on` and
+    `backward`; combines with either forward recipe; inert under f32 math): both gradients on MX operands - dy per row and W^T, dy^T, x^T by the
+    one-launch MX column quantiser (a block = 32 tokens of a column), sv_linear_mxfp8_dgrad and the atomic-free, deterministic
+    sv_linear_mxfp8_wgrad."""
     if recipe not in ("row", "mx"):
         raise ValueError(f"set_linear_fp8: recipe must be 'row' or 'mx', not {recipe!r}")
+    if backward_recipe not in ("row", "mx"):
+        raise ValueError(f"set_linear_fp8: backward_recipe must be 'row' or 'mx', not {backward_recipe!r}")
     _STATE["linear_fp8"] = bool(on)
     _STATE["linear_fp8_bwd"] = bool(on) and bool(backward)
     _STATE["linear_fp8_recipe"] = recipe
+    _STATE["linear_fp8_bwd_recipe"] = backward_recipe if (on and backward) else "row"
 
 
 def linear_fp8_enabled() -> bool:
@@ -648,6 +656,17 @@ def mx_emit_site(cons_spec: ConvSpec, cons_w, cons_epi: dict, prod_spec: Optiona
 
 def linear_fp8_bwd_enabled() -> bool:
     return bool(_STATE.get("linear_fp8_bwd")) and linear_fp8_enabled()
+
+
+def linear_fp8_bwd_recipe() -> str:
+    """"row" or "mx": the recipe the fp8 backward of the Swin linears runs (meaningful while linear_fp8_bwd_enabled())."""
+    return _STATE.get("linear_fp8_bwd_recipe", "row")
+
+
+def linear_mxfp8_bwd_launches() -> Tuple[int, int]:
+    """(sv_linear_mxfp8_dgrad, sv_linear_mxfp8_wgrad) launches of this process so far; linear_fp8_bwd_launches() counts neither."""
+    lib = hip.load()
+    return int(lib.sv_linear_mxfp8_bwd_launches(0)), int(lib.sv_linear_mxfp8_bwd_launches(1))
 
 
 def linear_fp8_bwd_launches() -> Tuple[int, int]:
@@ -748,6 +767,29 @@ def quantize_weight_t_fp8(w: torch.Tensor):
     return hit
 
 
+def quantize_cols_mx(t: torch.Tensor, rows: int, Cc: int, ld: Optional[int] = None, colsum: Optional[torch.Tensor] = None):
+    """t [rows, Cc] (fp32 or bf16, row stride ld) -> (e4m3 bytes of the TRANSPOSE [Cc, roundup(rows, 128)], E8M0 block scales
+    [Cc, roundup(rows, 128) / 32] uint8, a block = 32 consecutive rows of one column) by sv_quant_cols_mx_e4m3: one launch, t read once;
+    colsum (fp32 [Cc]) += the column sums of the unquantised values."""
+    Mp = (rows + 127) // 128 * 128
+    q = torch.empty(Cc, Mp, dtype=torch.uint8, device=t.device)
+    sc = torch.empty(Cc, Mp // 32, dtype=torch.uint8, device=t.device)
+    call("sv_quant_cols_mx_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, Cc, ld or Cc, ptr(q), Mp, ptr(sc), ptr(colsum))
+    return q, sc
+
+
+def quantize_weight_t_mx(w: torch.Tensor):
+    """MX rows of W^T for a Linear weight W [N, K] ([K][Np] bytes, a block = 32 consecutive n of one column k): the operand of the MX data
+    gradient, cached next to quantize_weight_t_fp8's rows with the same lifetime."""
+    cache = _CTX.packs
+    if cache is None or not isinstance(w, torch.nn.Parameter):
+        return quantize_cols_mx(w, w.shape[0], w.shape[1])
+    hit = cache.w8mxt.get(id(w))
+    if hit is None:
+        hit = cache.w8mxt[id(w)] = quantize_cols_mx(w, w.shape[0], w.shape[1])
+    return hit
+
+
 def _fp8_bwd_site(spec: ConvSpec, w) -> bool:
     return (linear_fp8_bwd_enabled() and spec.taps == 1 and spec.cin_mem == spec.cin and spec.cout_mem == spec.cout
             and isinstance(w, torch.nn.Parameter))
@@ -760,6 +802,12 @@ def swin_linear_dgrad(dy, rows, spec: ConvSpec, w, dx, **epi):
     if _fp8_bwd_site(spec, w):
         e = _epilogue(spec.cin, **epi)
         if hip.load().sv_linear_fp8_dgrad_supported(spec.cout, spec.cin, C.byref(e), _STATE["math"], hip.ACT) == 1:
+            if linear_fp8_bwd_recipe() == "mx":
+                dq, ds = quantize_rows_mx(dy, rows, spec.cout, activation=False)
+                wtq, wts = quantize_weight_t_mx(w)
+                traced_call("sv_linear_mxfp8_dgrad", 2.0 * rows * spec.cin * spec.cout, float(rows) * (dq.shape[1] + dy.element_size() * spec.cin) + wtq.numel(),
+                            ptr(dq), ptr(ds), ptr(wtq), ptr(wts), ptr(dx), rows, spec.cout, spec.cin, C.byref(e), tag=f"M={rows} N={spec.cout} K={spec.cin}")
+                return
             dq, sd = quantize_rows_fp8(dy, rows, spec.cout)
             wtq, swt = quantize_weight_t_fp8(w)
             traced_call("sv_linear_fp8_dgrad", 2.0 * rows * spec.cin * spec.cout, float(rows) * (dq.shape[1] + dy.element_size() * spec.cin) + wtq.numel(),
@@ -774,16 +822,26 @@ def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True
     the fp8 kernel; otherwise exactly linear_wgrad.  The whole sequence follows linear_wgrad's stream rule: on the weight-gradient stream
     (temporaries allocated inside that stream context) unless async_ok is False, in which case it stays in order on the caller's stream (the
     quantised copies are complete before the caller overwrites dy).  The transposed copies, rows x (N + K) bytes, are freed on return either
-    way; only dy and x are held until the join."""
+    way; only dy and x are held until the join.  backward_recipe "mx": the same sequence on the MX column quantiser and sv_linear_mxfp8_wgrad,
+    whose workspace of fp32 partials is one more temporary of that stream context."""
     if not _fp8_bwd_site(spec, w):
         return linear_wgrad(dy, x, rows, spec, dw, db, async_ok=async_ok)
 
-    def run():
+    def run_mx():
+        dyt, dys = quantize_cols_mx(dy, rows, spec.cout, colsum=db)
+        xt, xs = quantize_cols_mx(x, rows, spec.cin)
+        nws = int(hip.load().sv_linear_mxfp8_wgrad_workspace_floats(rows, spec.cout, spec.cin, 0))
+        ws = fempty(nws, like=dw) if nws else None         # the splits' fp32 partials: written before they are read, dropped once enqueued
+        traced_call("sv_linear_mxfp8_wgrad", 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout + 8.0 * nws,
+                    ptr(dyt), ptr(dys), ptr(xt), ptr(xs), ptr(dw), rows, spec.cout, spec.cin, spec.cin, 0, ptr(ws), tag=f"M={rows} N={spec.cout} K={spec.cin}")
+
+    def run_row():
         dyt, sdc = quantize_cols_fp8(dy, rows, spec.cout, colsum=db)
         xt, sxc = quantize_cols_fp8(x, rows, spec.cin)
         traced_call("sv_linear_fp8_wgrad", 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout,
                     ptr(dyt), ptr(sdc), ptr(xt), ptr(sxc), ptr(dw), rows, spec.cout, spec.cin, spec.cin, 0, tag=f"M={rows} N={spec.cout} K={spec.cin}")
 
+    run = run_mx if linear_fp8_bwd_recipe() == "mx" else run_row
     aw = _CTX.awg
     if aw is not None and async_ok:
         aw.stream.wait_stream(torch.cuda.current_stream())     # dy and x are complete on the producing stream
