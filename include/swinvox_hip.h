@@ -264,6 +264,16 @@ int sv_layernorm_quant_fwd(const void* x, const float* gamma, const float* beta,
                            void* q, int Kp, float* scales, long long rows, int C, float eps, int merge_H, int merge_W,
                            int act_dtype, void* stream);
 long long sv_layernorm_quant_launches(void); /* sv_layernorm_quant_fwd launches so far in this process (timm LayerNorm -> Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise) */
+/* sv_layernorm_fwd that also emits the MX operand rows sv_linear_mxfp8 reads (timm LayerNorm -> Linear behind
+ * models/swin_transformer.py:78): q [rows, Kp] e4m3 bytes (16-byte aligned), Kp = roundup(C, 128), zeros past C; scales_u8 [rows, Kp / 32]
+ * E8M0 bytes (4-byte aligned), 127 for a block that is all zero or lies in the padding.  Both equal sv_quant_rows_mx_e4m3's output on the
+ * STORED y (the row rounded to act_dtype first) bit for bit.  y may be NULL (the rows are then not stored: inference); mean and rstd may be
+ * NULL together.  Refused with SV_ERR_INVALID before any GPU call: what sv_layernorm_fwd refuses, q or scales_u8 NULL, Kp != roundup(C, 128),
+ * exactly one of mean / rstd NULL, q not 16-byte or scales_u8 not 4-byte aligned. */
+int sv_layernorm_quant_mx_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                              void* q, int Kp, void* scales_u8, long long rows, int C, float eps,
+                              int merge_H, int merge_W, int act_dtype, void* stream);
+long long sv_layernorm_quant_mx_launches(void); /* sv_layernorm_quant_mx_fwd launches so far in this process (timm LayerNorm -> Linear behind models/swin_transformer.py:78; sv_layernorm_quant_launches does not count them) */
 /* workspace: sv_layernorm_bwd_workspace_floats(C) floats, ZERO on entry (slot-spread dgamma/dbeta partial sums + ticket) */
 size_t sv_layernorm_bwd_workspace_floats(int C);
 int sv_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,

@@ -14,6 +14,9 @@ namespace sv {
 // QUANT (sv_layernorm_quant_fwd): the lane group also emits the operand row sv_linear_fp8 reads - the e4m3 bytes and the scale of the row AS
 // STORED (rounded to the storage type first), by the recipe of linear_fp8.hip: one more lane-group reduction (the maximum) and one more
 // store per chunk, no second kernel and no second read.  y / mean / rstd are then optional (inference stores only the bytes).
+// MX (sv_layernorm_quant_mx_fwd): the same for the operand rows sv_linear_mxfp8 reads - one E8M0 scale per 32 columns.  The 32 columns of a
+// block are the chunks of 32 / VEC adjacent lanes (8 at VEC 4, 4 at VEC 8; LPR is a multiple of 8, so chunk gl + LPR i sits in an aligned lane
+// group for every i): the block maximum is the first three (two) DPP steps of group_max, and nothing is divided out.
 // ------------------------------------------------------------------------------------------------
 // Contention-free reductions across workgroups: partial sums go (atomically) into one of NSLOT accumulator images chosen by
 // the workgroup index and a tiny second kernel folds the images.  (A "last workgroup folds" ticket would need a device-scope
@@ -76,18 +79,34 @@ __device__ __forceinline__ float group_max(float v) {   // maximum over the same
   return v;
 }
 
-// the outputs only the quantising form has
+template <int VEC>
+__device__ __forceinline__ float block32_max(float v) {   // maximum over the 32 / VEC adjacent lanes that hold one 32-column block (values >= 0)
+  v = fmaxf(v, ln_dpp_mov<0xB1>(v)); v = fmaxf(v, ln_dpp_mov<0x4E>(v));
+  if constexpr (VEC == 4) v = fmaxf(v, ln_dpp_mov<0x141>(v));
+  return v;
+}
+
+// the outputs only the quantising forms have
 struct LnQuantOut { uint8_t* q; float* scales; int Kp; };   // q [rows][Kp] e4m3 bytes, scales [rows]
+struct LnQuantMxOut { uint8_t* q; uint8_t* scales; int Kp; };   // q [rows][Kp] e4m3 bytes, scales [rows][Kp / 32] E8M0 bytes
 __device__ __forceinline__ const LnQuantOut& ln_quant_out(const LnQuantOut& o) { return o; }
+__device__ __forceinline__ const LnQuantMxOut& ln_quant_out(const LnQuantMxOut& o) { return o; }
+template <typename... QO> struct LnIsMx { static constexpr bool value = false; };
+template <> struct LnIsMx<LnQuantMxOut> { static constexpr bool value = true; };
 
 // QO is empty (the plain forward: y, mean_out, rstd_out required; its argument list, and with it its code, is what it was before the
-// quantising form existed) or one LnQuantOut (QUANT: q and scales are written as well, and y / (mean_out, rstd_out) are skipped when null).
+// quantising form existed), one LnQuantOut (QUANT: q and scales are written as well, and y / (mean_out, rstd_out) are skipped when null) or
+// one LnQuantMxOut (QUANT and MX: the same with one scale byte per 32 columns).
 template <bool MERGE, typename AT, int VEC, int LPR, int NV, typename... QO>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const AT* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, AT* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                      long long rows, int C, float eps, MergeMap mm, QO... qo_) {
   constexpr bool QUANT = sizeof...(QO) == 1;
+  constexpr bool MX = LnIsMx<QO...>::value;
+  // MX: a 32-column block must be an aligned group of 32 / VEC lanes inside the row's lane group for every i, and one pass of the lane group
+  // must cover the (at most 3) scale bytes of the blocks that lie wholly in the padding
+  static_assert(!MX || (LPR % 8 == 0 && LPR >= 4 && (VEC == 4 || VEC == 8)), "MX form: LPR must be a multiple of 8, VEC 4 or 8");
   constexpr int RPW = 64 / LPR;                       // rows per wave
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gl = lane % LPR, gr = lane / LPR;
@@ -119,9 +138,11 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const AT* __restrict__ x, c
   const float rstd = rsqrtf(group_sum<LPR>(sq) * invC + eps);
   if (rok && gl == 0 && (!QUANT || mean_out)) { mean_out[row] = mean; rstd_out[row] = rstd; }
   float amax = 0.f;
+  int bexp[MX ? NV : 1];                                        // MX: the exponent of the block chunk i of this lane lies in
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int ch = gl + LPR * i;
+    if constexpr (MX) amax = 0.f;                               // per block, not per row; lanes without a chunk contribute 0
     if (rok && ch < nchunk) {
       float g[VEC], b[VEC], o[VEC];
       ldp(gamma + ch * VEC, g, VEC); ldp(beta + ch * VEC, b, VEC);
@@ -138,8 +159,33 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const AT* __restrict__ x, c
         LnIO<VEC, AT>::store(y + (size_t)row * C + ch * VEC, o);
       }
     }
+    if constexpr (MX) bexp[i] = mx_block_exp(block32_max<VEC>(amax));   // outside the branch: every lane of the wave takes the DPP steps
   }
-  if constexpr (QUANT) {
+  if constexpr (MX) {
+    const LnQuantMxOut& qo = ln_quant_out(qo_...);
+    if (rok) {
+      uint8_t* __restrict__ qrow = qo.q + (size_t)row * qo.Kp;
+      uint8_t* __restrict__ srow = qo.scales + (size_t)row * (qo.Kp >> 5);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int ch = gl + LPR * i;
+        if (ch < nchunk) {   // element k of the row is byte k: VEC bytes per chunk
+          const uint32_t lo = pack4_e4m3_mx(v[i][0], v[i][1], v[i][2], v[i][3], bexp[i]);
+          if constexpr (VEC == 8) {
+            const uint32_t hi = pack4_e4m3_mx(v[i][4], v[i][5], v[i][6], v[i][7], bexp[i]);
+            *reinterpret_cast<uint2*>(qrow + ch * 8) = make_uint2(lo, hi);
+          } else {
+            *reinterpret_cast<uint32_t*>(qrow + ch * 4) = lo;
+          }
+          // the block's first lane (its chunk starts the block, so it exists whenever any chunk of the block does) writes the scale byte
+          if (gl % (32 / VEC) == 0) srow[ch * VEC >> 5] = (uint8_t)(bexp[i] + 127);
+        }
+      }
+      // zero bytes C .. Kp - 1 as the row form does, and byte 127 (E = 0) for the blocks that lie wholly in the padding (at most 3 < LPR)
+      for (int w = (C >> 2) + gl; w < (qo.Kp >> 2); w += LPR) reinterpret_cast<uint32_t*>(qrow)[w] = 0u;
+      if (((C + 31) >> 5) + gl < (qo.Kp >> 5)) srow[((C + 31) >> 5) + gl] = 127;
+    }
+  } else if constexpr (QUANT) {
     const float sc = fp8_row_scale(group_max<LPR>(amax));
     const LnQuantOut& qo = ln_quant_out(qo_...);
     if (rok) {
@@ -1253,6 +1299,16 @@ static void ln_quant_fwd_launch(const void* x, const float* gamma, const float* 
                                              static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm, qo););
 }
 template <bool MERGE, typename AT, int VEC>
+static void ln_quant_mx_fwd_launch(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* q, int Kp,
+                                   void* scales, long long rows, int C, float eps, MergeMap mm, hipStream_t s) {
+  int lpr, nv;
+  ln_shape(C / VEC, lpr, nv);
+  const int rpb = 4 * (64 / lpr);   // rows per workgroup
+  const LnQuantMxOut qo{static_cast<uint8_t*>(q), static_cast<uint8_t*>(scales), Kp};
+  SV_LN_DISPATCH(lpr, nv, hipLaunchKernelGGL((ln_fwd_kernel<MERGE, AT, VEC, LPR, NV, LnQuantMxOut>), dim3(cdiv(rows, rpb)), dim3(256), 0, s,
+                                             static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm, qo););
+}
+template <bool MERGE, typename AT, int VEC>
 static void ln_bwd_launch(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
                           float* dbeta, long long rows, int C, MergeMap mm, int accumulate_dx, float* ws, hipStream_t s) {
   int lpr, nv;
@@ -1328,6 +1384,36 @@ extern "C" int sv_layernorm_quant_fwd(const void* x, const float* gamma, const f
   }
   const int rc = check_launch("sv_layernorm_quant_fwd");
   if (rc == SV_OK) layernorm_quant_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+static std::atomic<long long> layernorm_quant_mx_launches{0};
+
+extern "C" long long sv_layernorm_quant_mx_launches(void) { return layernorm_quant_mx_launches.load(std::memory_order_relaxed); }
+
+extern "C" int sv_layernorm_quant_mx_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                                         void* q, int Kp, void* scales_u8, long long rows, int C, float eps, int merge_H, int merge_W,
+                                         int act_dtype, void* stream) {
+  SV_REQUIRE(q && scales_u8, "sv_layernorm_quant_mx_fwd: q and scales_u8 must not be null");
+  SV_REQUIRE((mean == nullptr) == (rstd == nullptr), "sv_layernorm_quant_mx_fwd: mean and rstd must be null together");
+  if (const int rc = ln_fwd_check("sv_layernorm_quant_mx_fwd", x, gamma, beta, rows, C, merge_H, merge_W, act_dtype)) return rc;
+  SV_REQUIRE(C > 0 && Kp == (C + 127) / 128 * 128, "sv_layernorm_quant_mx_fwd: Kp (%d) must be C (%d) rounded up to a multiple of 128", Kp, C);
+  SV_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0,
+             "sv_layernorm_quant_mx_fwd: q must be 16-byte aligned, scales_u8 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
+  const bool v8 = ln_vec8(act_dtype, C, merge_H, x, y);
+  if (merge_H > 0) {
+    if (v8) ln_quant_mx_fwd_launch<true, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
+    else if (act_dtype == SV_BF16) ln_quant_mx_fwd_launch<true, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
+    else ln_quant_mx_fwd_launch<true, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
+  } else {
+    if (v8) ln_quant_mx_fwd_launch<false, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
+    else if (act_dtype == SV_BF16) ln_quant_mx_fwd_launch<false, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
+    else ln_quant_mx_fwd_launch<false, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
+  }
+  const int rc = check_launch("sv_layernorm_quant_mx_fwd");
+  if (rc == SV_OK) layernorm_quant_mx_launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }
 

@@ -142,11 +142,14 @@ def _drop_scale(I, p, seed, like):
 
 def _norm_for_linear(x, norm, rows, Cd, spec, w, save, merge_hw=(0, 0), **epi):
     """The LayerNorm in front of a Swin linear (norm1 -> qkv, norm2 -> fc1, patch-merge norm -> reduction; **epi: that linear's epilogue form)
-    -> (ln, mean, rstd, xq).  When the linear will take the fp8 kernel and the fused quantiser is on, the LayerNorm kernel emits the
-    quantised rows xq = (bytes, scales) itself, and without `save` (no backward follows) stores nothing else (ln, mean, rstd are None);
-    otherwise xq is None and this is ops.layernorm_fwd."""
+    -> (ln, mean, rstd, xq).  When the linear will take the fp8 kernel and the fused quantiser is on (row recipe: ops.ln_quant_site, MX
+    recipe: ops.ln_quant_mx_site), the LayerNorm kernel emits the quantised rows xq = (bytes, scales) itself, and without `save` (no backward
+    follows) stores nothing else (ln, mean, rstd are None); otherwise xq is None and this is ops.layernorm_fwd."""
     if ops.ln_quant_site(spec, w, **epi):
         ln, m, r, q, sq = ops.layernorm_quant_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save)
+        return ln, m, r, (q, sq)
+    if ops.ln_quant_mx_site(spec, w, **epi):
+        ln, m, r, q, sq = ops.layernorm_quant_mx_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save)
         return ln, m, r, (q, sq)
     return ops.layernorm_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw) + (None,)
 

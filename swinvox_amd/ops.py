@@ -565,7 +565,9 @@ def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backwa
     recipe = "row" (default): one fp32 scale per operand row, divided out in the epilogue.  recipe = "mx": the FORWARD of the same call sites
     on MX operands - one E8M0 power-of-two scale per 32 consecutive elements of the contraction, applied by the MFMA (sv_linear_mxfp8).  A block
     scale depends on 32 neighbours only, so fc1 emits the operand rows of fc2 and the window attention those of proj (set_mx_producer_quant);
-    the LayerNorm sites take the stand-alone MX quantiser.  `backward` means the same under either recipe: its quantisers read the stored
+    the LayerNorm sites take the stand-alone MX quantiser unless set_ln_quant_mx(True) (off by default) lets norm1 / norm2 / the patch-merge
+    norm emit the MX rows and block scales themselves (sv_layernorm_quant_mx_fwd), which leaves the unfused Swin forward without a stand-alone
+    activation quantiser.  `backward` means the same under either recipe: its quantisers read the stored
     tensors, which do not change.
     backward_recipe = "row" (default): the backward above, whatever the forward recipe.  backward_recipe = "mx" (effective only with `on` and
     `backward`; combines with either forward recipe; inert under f32 math): both gradients on MX operands - dy per row and W^T, dy^T, x^T by the
@@ -880,7 +882,7 @@ def set_ln_quant_fused(on: bool) -> None:
 
 def ln_quant_fused_enabled() -> bool:
     import os
-    # recipe "mx": the LayerNorm sites take the stand-alone MX quantiser (the quantising LayerNorm writes per-row scales)
+    # recipe "mx": this form writes per-row scales; the MX form has a switch of its own (ln_quant_mx_enabled)
     return linear_fp8_enabled() and linear_fp8_recipe() == "row" and _STATE.get("ln_quant_fused", True) and os.environ.get("SV_LN_QUANT_FUSED", "1") != "0"
 
 
@@ -910,6 +912,48 @@ def layernorm_quant_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5, s
     call("sv_layernorm_quant_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), ptr(xq), Kp, ptr(sx), rows, Cdim, eps,
          merge_hw[0], merge_hw[1])
     return y, mean, rstd, xq, sx
+
+
+def set_ln_quant_mx(on: bool) -> None:
+    """A/B switch of the MX quantising LayerNorm (csrc/norm.hip, sv_layernorm_quant_mx_fwd): True lets norm1 / norm2 / the patch-merge norm
+    emit the MX rows and E8M0 block scales of the MXFP8 linear they feed; False (default) keeps LayerNorm + the stand-alone MX quantiser, with
+    bit-identical results.  Effective only under recipe "mx" with bf16 math; SV_LN_QUANT_MX=1 in the environment switches it on as well.
+    Independent of set_mx_producer_quant (the proj / fc2 sites) and of set_ln_quant_fused (the row recipe)."""
+    _STATE["ln_quant_mx"] = bool(on)
+
+
+def ln_quant_mx_enabled() -> bool:
+    import os
+    return _mx() and (_STATE.get("ln_quant_mx", False) or os.environ.get("SV_LN_QUANT_MX", "0") == "1")
+
+
+def ln_quant_mx_site(spec: ConvSpec, w, **epi) -> bool:
+    """MX counterpart of ln_quant_site: the linear behind this LayerNorm will run on the MX kernel and the MX quantising LayerNorm is on.
+    With set_linear_fp8 off this is one flag test."""
+    return ln_quant_mx_enabled() and swin_linear_fp8_epilogue(spec, w, **epi) is not None
+
+
+def layernorm_quant_mx_launches() -> int:
+    """sv_layernorm_quant_mx_fwd launches of this process so far (layernorm_quant_launches() counts none of them)."""
+    return int(hip.load().sv_layernorm_quant_mx_launches())
+
+
+def layernorm_quant_mx_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5, store=True):
+    """layernorm_fwd that also returns the MX operand rows of the MXFP8 linear it feeds: (y, mean, rstd, xq, xs) with xq [rows,
+    roundup(Cdim, 128)] e4m3 bytes and xs [rows, roundup(Cdim, 128) / 32] E8M0 bytes, equal to quantize_rows_mx(y) (which is not launched:
+    mx_act_quant_launches() does not move).  store=False (no backward follows): y, mean and rstd are neither allocated nor written and come
+    back as None."""
+    y = mean = rstd = None
+    if store:
+        y = empty(rows, Cdim, like=x)
+        mean = fempty(rows, like=x)
+        rstd = fempty(rows, like=x)
+    Kp = (Cdim + 127) // 128 * 128
+    xq = torch.empty(rows, Kp, dtype=torch.uint8, device=x.device)
+    xs = torch.empty(rows, Kp // 32, dtype=torch.uint8, device=x.device)
+    call("sv_layernorm_quant_mx_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), ptr(xq), Kp, ptr(xs), rows, Cdim, eps,
+         merge_hw[0], merge_hw[1])
+    return y, mean, rstd, xq, xs
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, Cdim, merge_hw=(0, 0), accumulate_dx=False):
