@@ -164,8 +164,9 @@ int sv_quant_rows_mx_e4m3(const void* src, int src_dtype, int rows, int K, int l
 /* out[m, n] = epilogue(sum_k 2^(xs + ws - 254) xq[m, k] wq[n, k]) (timm Linear behind models/swin_transformer.py:78).  xq / xs, wq / ws from the MX row
  * quantiser; epilogue forms and refusals are sv_linear_fp8's (sv_linear_fp8_supported answers for both).  q_out [M, N] / qs_out [M, N / 32]
  * (optional, both or neither): the MX rows of the STORED output (after the activation, rounded to act_dtype), equal to the MX row quantiser on out -
- * the operand of the next linear.  Refused with SV_ERR_INVALID unless N % 128 == 0, and with a residual.  With q_out given, out (and then
- * e->pre_act) may be NULL: nothing but the MX rows is written. */
+ * the operand of the next linear.  Refused with SV_ERR_INVALID unless N % 128 == 0, and with a residual.  With q_out given, out may be NULL: the
+ * MX rows are written, and e->pre_act when it is given in front of an activation (bit-identical to the call that also stores out) - what a backward
+ * on stored MX rows reads.  pre_act without out and without an activation (it would be out itself) is refused with SV_ERR_INVALID. */
 int sv_linear_mxfp8(const void* xq, const void* xs, const void* wq, const void* ws, void* out, int M, int K, int N, const sv_epilogue* e,
                     void* q_out, void* qs_out, int act_dtype, void* stream);
 long long sv_linear_mxfp8_launches(void); /* sv_linear_mxfp8 launches so far in this process (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise) */
@@ -197,6 +198,15 @@ int sv_linear_mxfp8_wgrad(const void* dyt, const void* dys, const void* xt, cons
                           float* workspace, void* stream);
 long long sv_linear_mxfp8_bwd_launches(int which); /* launches so far of sv_linear_mxfp8_dgrad (which = 0) / sv_linear_mxfp8_wgrad (1) (timm Linear behind models/swin_transformer.py:78; tests: the path they mean to exercise); the row recipe's counters do not move */
 long long sv_quant_cols_mx_launches(void); /* sv_quant_cols_mx_e4m3 launches so far in this process (timm Linear behind models/swin_transformer.py:78, operand preparation; tests) */
+/* MX re-blocker (timm Linear behind models/swin_transformer.py:78, operand preparation of the MX weight gradient from stored MX rows), one launch, xq
+ * and xs each read once: the MX rows of a stored tensor, xq [M, Kp] e4m3 bytes (16-byte aligned, Kp == roundup(K, 128)) and xs [M, Kp / 32] E8M0 bytes
+ * (4-byte aligned), become the column operand dst_q [K][Mp] (16-byte aligned, Mp == roundup(M, 128), bytes M .. Mp-1 of every row zero) and scales_u8
+ * [K][Mp / 32] (4-byte aligned; a block = 32 consecutive tokens of one column, blocks wholly past M carry 127).  Definition: the output equals the MX
+ * column quantiser applied to the fp32 tensor byte 2^(s - 127) (an exact decode), columns 0 .. K-1, bit for bit; columns K .. Kp-1 of xq do not
+ * influence it.  SV_ERR_INVALID before any GPU call: a NULL pointer, M < 1 or K < 1, Kp != roundup(K, 128), Mp != roundup(M, 128), misalignment,
+ * Mp / 128 > 65535 (the grid's limit: M above 8 388 480 tokens). */
+int sv_mx_rows_to_cols(const void* xq, int Kp, const void* xs, int M, int K, void* dst_q, int Mp, void* scales_u8, void* stream);
+long long sv_mx_rows_to_cols_launches(void); /* sv_mx_rows_to_cols launches so far in this process (timm Linear behind models/swin_transformer.py:78, operand preparation; tests) */
 /* LDS-halo MFMA stencils for 3x3x3 / stride 1 / pad 1 convolutions with <= 16 output channels per tile (merger.py:20-54),
  * bf16 operands.  x: channels-last positions with row stride ldx, cin_load (multiple of 4) elements read per position,
  * zero-extended to 16*groups channels; w_bf16: [16*ntiles16][27][16*groups] bf16 (forward: rows = output channels;

@@ -7,7 +7,9 @@ Per shape: the MX row quantiser on dy, the one-launch MX column quantiser on dy 
 (fc2's call site with its GELU-derivative epilogue), sv_linear_mxfp8_wgrad with the default splits (the workspace is allocated once, outside
 the timed region: the host layer takes it from the caching allocator); the same five for the row recipe, measured TWICE (rowA, rowB: their
 spread is the yardstick a difference has to exceed); and sv_conv_gather / sv_conv_wgrad with bf16 operands.
---sweep: the MX weight-gradient GEMM at splits that give about 128, 256, 512, 1024 and 2048 workgroups (never more than one per 128 tokens).
+"rb x" beside "MX qc x": the re-blocker (sv_mx_rows_to_cols) on the stored MX rows of x, what store="mx" runs in place of the column quantiser of x.
+--sweep: the MX weight-gradient GEMM at splits that give about 128, 256, 512, 1024 and 2048 workgroups (never more than one per 128 tokens), and
+the re-blocker against its yardstick, the MX column quantiser on the bf16 tensor of the same shape, with the achieved read + write TB/s of both.
 Protocol: warm-up launches, one HIP event pair per launch, median over the launches; the operands rotate over up to 4 copies so that one
 rotation touches >= 512 MB where memory allows.  --rows-div shrinks the working set below that: its times are for smoke runs only.
 
@@ -40,17 +42,17 @@ def main():
     lib = hip.load()
     S.set_math("bf16"); S.set_storage("bf16")
     print("all times in us; q = quantisers, g = GEMM; dgrad q+g = row quantiser of dy + GEMM, wgrad q+g = both column quantisers + GEMM (+ reduce)")
-    print(f"{'layer':10s} {'M':>8s} {'K':>5s} {'N':>5s} | {'MX qr dy':>8s} {'qc dy':>7s} {'qc x':>7s} | {'row qr dy':>9s} {'qc dy':>7s} {'qc x':>7s} | "
+    print(f"{'layer':10s} {'M':>8s} {'K':>5s} {'N':>5s} | {'MX qr dy':>8s} {'qc dy':>7s} {'qc x':>7s} {'rb x':>7s} | {'row qr dy':>9s} {'qc dy':>7s} {'qc x':>7s} | "
           f"{'dgrad g MX':>10s} {'row':>7s} {'bf16':>7s} | {'dgrad q+g MX':>12s} {'rowA':>7s} {'rowB':>7s} {'bf16':>7s} | "
           f"{'wgrad g MX':>10s} {'splits':>6s} {'row':>7s} {'bf16':>7s} | {'wgrad q+g MX':>12s} {'rowA':>7s} {'rowB':>7s} {'bf16':>7s} | quant W^T MX / row")
     tot = {}
-    sweep = []
+    sweep, rbs = [], []
     bf = torch.bfloat16
     for name, M, K, N, epi in SHAPES:
         M //= a.rows_div
         sp = ConvSpec.linear(K, N)
         R = max(1, min(4, -(-(512 << 20) // (2 * M * (K + N)))))           # rotating copies of (dy, x)
-        Np, Mp = (N + 127) // 128 * 128, (M + 127) // 128 * 128
+        Np, Mp, Kp = (N + 127) // 128 * 128, (M + 127) // 128 * 128, (K + 127) // 128 * 128
         dys = [torch.randn(M, N, device=dev).to(bf) for _ in range(R)]
         xs = [torch.randn(M, K, device=dev).to(bf) for _ in range(R)]
         dxs = [torch.empty(M, K, device=dev, dtype=bf) for _ in range(R)]
@@ -73,6 +75,7 @@ def main():
         dyss = [torch.empty(N, Mp // 32, **u8) for _ in range(R)]
         xss = [torch.empty(K, Mp // 32, **u8) for _ in range(R)]
         wtqm, wtsm = ops.quantize_cols_mx(w, N, K)
+        xrows = [ops.quantize_rows_mx(t_, M, K, activation=False) for t_ in xs]     # the MX rows of x a store="mx" tape holds
         nws = int(lib.sv_linear_mxfp8_wgrad_workspace_floats(M, N, K, 0))
         splits0 = nws // (N * K) if nws else 1
         ws = torch.empty(max(nws, 4), device=dev)
@@ -101,6 +104,9 @@ def main():
         def mq_cols_x(k):
             call("sv_quant_cols_mx_e4m3", ptr(xs[k % R]), hip.BF16, M, K, K, ptr(xts[k % R]), Mp, ptr(xss[k % R]), None)
 
+        def rb_x(k):
+            call("sv_mx_rows_to_cols", ptr(xrows[k % R][0]), Kp, ptr(xrows[k % R][1]), M, K, ptr(xts[k % R]), Mp, ptr(xss[k % R]))
+
         def mdgrad(k):
             call("sv_linear_mxfp8_dgrad", ptr(dqs[k % R]), ptr(dss[k % R]), ptr(wtqm), ptr(wtsm), ptr(dxs[k % R]), M, N, K, C.byref(e))
 
@@ -127,11 +133,14 @@ def main():
         for key, f in (("mqr", mq_rows), ("mqd", mq_cols_dy), ("mqx", mq_cols_x), ("mdg", mdgrad), ("mwg", mwgrad)):
             t[key] = median_us(f, a.iters)
         t["mwt"] = median_us(lambda k: ops.quantize_cols_mx(w, N, K), a.iters)
+        t["rbx"] = median_us(rb_x, a.iters)                                  # last: it overwrites the column operand of x with (nearly) the same bytes
+        out_b = K * Mp * 33 / 32
+        rbs.append((name, M, K, t["mqx"], (2.0 * M * K + out_b) / t["mqx"] * 1e-6, t["rbx"], (M * Kp * 33 / 32 + out_b) / t["rbx"] * 1e-6))
         dq = dict(mx=t["mqr"] + t["mdg"], rowA=t["qrA"] + t["dgA"], rowB=t["qrB"] + t["dgB"], bf16=t["d16"])
         wq = dict(mx=t["mqd"] + t["mqx"] + t["mwg"], rowA=t["qdA"] + t["qxA"] + t["wgA"], rowB=t["qdB"] + t["qxB"] + t["wgB"], bf16=t["w16"])
         for k, v in list(dq.items()) + [("w_" + k, v) for k, v in wq.items()]:
             tot[k] = tot.get(k, 0.0) + v
-        print(f"{name:10s} {M:8d} {K:5d} {N:5d} | {t['mqr']:8.1f} {t['mqd']:7.1f} {t['mqx']:7.1f} | {t['qrA']:9.1f} {t['qdA']:7.1f} {t['qxA']:7.1f} | "
+        print(f"{name:10s} {M:8d} {K:5d} {N:5d} | {t['mqr']:8.1f} {t['mqd']:7.1f} {t['mqx']:7.1f} {t['rbx']:7.1f} | {t['qrA']:9.1f} {t['qdA']:7.1f} {t['qxA']:7.1f} | "
               f"{t['mdg']:10.1f} {t['dgA']:7.1f} {t['d16']:7.1f} | {dq['mx']:12.1f} {dq['rowA']:7.1f} {dq['rowB']:7.1f} {dq['bf16']:7.1f} | "
               f"{t['mwg']:10.1f} {splits0:6d} {t['wgA']:7.1f} {t['w16']:7.1f} | {wq['mx']:12.1f} {wq['rowA']:7.1f} {wq['rowB']:7.1f} {wq['bf16']:7.1f} | "
               f"{t['mwt']:.1f} / {t['rwt']:.1f}", flush=True)
@@ -145,11 +154,15 @@ def main():
                 row.append((s_, median_us(lambda k: mwgrad(k, s_, wsp), a.iters), n * 4 / 2 ** 20))
                 del wsp
             sweep.append((name, row))
-        del dys, xs, dxs, dqs, sds, dyts, xts, dss, dyss, xss, ws, kw, e
+        del dys, xs, dxs, dqs, sds, dyts, xts, dss, dyss, xss, xrows, ws, kw, e
         torch.cuda.empty_cache()
     print("TOTAL dgrad quantise + gemm: " + ", ".join(f"{k} {tot[k]:.1f}" for k in ("mx", "rowA", "rowB", "bf16")) +
           "; wgrad quantise + gemm: " + ", ".join(f"{k} {tot['w_' + k]:.1f}" for k in ("mx", "rowA", "rowB", "bf16")))
     if sweep:
+        print("column operand of x: MX column quantiser on bf16 x (reads 2 bytes, writes 1 per element) against the re-blocker on the MX rows of x "
+              "(reads 1, writes 1); TB/s = bytes read + written, scale bytes included")
+        for name, M, K, tq, bq, tr, br in rbs:
+            print(f"{name:10s} {M:8d} {K:5d} | qc x {tq:8.1f} us {bq:5.2f} TB/s | rb x {tr:8.1f} us {br:5.2f} TB/s | rb / qc {tr / tq:5.2f}", flush=True)
         print("MX weight-gradient GEMM (+ reduce) over the splits: target workgroups -> splits, us, workspace MB")
         for name, row in sweep:
             print(f"{name:10s} " + " | ".join(f"{tg:4d} -> {s_:4d} {us:7.1f} us {mb:6.1f} MB" for tg, (s_, us, mb) in zip(TARGETS, row)), flush=True)

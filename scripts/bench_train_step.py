@@ -5,7 +5,9 @@ the stock torch.optim sequence, next to forward+backward alone.  python scripts/
 --fp8-linear-mx: forward+backward alone, alternating (two rounds, one process) bf16, the row recipe, the MX recipe with producer emission and
 the MX recipe with the stand-alone quantiser everywhere (set_mx_producer_quant(False)).
 --fp8-linear-mx-bwd: forward+backward alone, alternating (two rounds, one process) bf16, the row-recipe forward + backward, the MX forward with
-the row-recipe backward, and the MX forward with the MX backward (backward_recipe="mx")."""
+the row-recipe backward, and the MX forward with the MX backward (backward_recipe="mx").
+--fp8-linear-mx-store: forward+backward alone, alternating (two rounds, one process) bf16, the MX forward + MX backward, and the same with the
+inputs of the linears stored as MX rows (store="mx"); every line also reports torch.cuda.max_memory_allocated of its run."""
 import argparse
 import os
 import sys
@@ -26,6 +28,7 @@ ap.add_argument("--fp8-linear", action="store_true", help="time forward+backward
 ap.add_argument("--fp8-linear-bwd", action="store_true", help="as --fp8-linear, plus a run with the fp8 backward of the linears")
 ap.add_argument("--fp8-linear-mx", action="store_true", help="forward+backward only: bf16, row recipe, MX with and without producer emission, two rounds")
 ap.add_argument("--fp8-linear-mx-bwd", action="store_true", help="forward+backward only: bf16, row fwd + bwd, MX fwd + row bwd, MX fwd + MX bwd, two rounds")
+ap.add_argument("--fp8-linear-mx-store", action="store_true", help="forward+backward only: bf16, MX fwd + MX bwd, the same with store='mx', two rounds; with peak memory")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = S.default_cfg()
@@ -48,12 +51,14 @@ def timed(fn, n):
 
 MX_MODES = (None, "fp8", "mx", "mx-noemit")
 MX_BWD_MODES = (None, "fp8+bwd", "mx+bwd", "mx+mxbwd")
-for fused in (MX_BWD_MODES * 2 if a.fp8_linear_mx_bwd else MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
+MX_STORE_MODES = (None, "mx+mxbwd", "mx+mxbwd+store")
+for fused in (MX_STORE_MODES * 2 if a.fp8_linear_mx_store else MX_BWD_MODES * 2 if a.fp8_linear_mx_bwd else MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
     torch.manual_seed(0)
     nets = [m(cfg).to(dev).train() for m in (Encoder, Decoder, Merger, Refiner)]
-    fp8 = fused in ("fp8", "fp8+bwd", "mx", "mx-noemit", "mx+bwd", "mx+mxbwd")
-    S.set_linear_fp8(fp8, backward=fused in ("fp8+bwd", "mx+bwd", "mx+mxbwd"), recipe="mx" if fused in ("mx", "mx-noemit", "mx+bwd", "mx+mxbwd") else "row",
-                     backward_recipe="mx" if fused == "mx+mxbwd" else "row")
+    fp8 = fused in ("fp8", "fp8+bwd", "mx", "mx-noemit", "mx+bwd", "mx+mxbwd", "mx+mxbwd+store")
+    S.set_linear_fp8(fp8, backward=fused in ("fp8+bwd", "mx+bwd", "mx+mxbwd", "mx+mxbwd+store"),
+                     recipe="mx" if fused in ("mx", "mx-noemit", "mx+bwd", "mx+mxbwd", "mx+mxbwd+store") else "row",
+                     backward_recipe="mx" if fused in ("mx+mxbwd", "mx+mxbwd+store") else "row", store="mx" if fused == "mx+mxbwd+store" else "bf16")
     ops.set_mx_producer_quant(fused != "mx-noemit")
     if fused is None or fp8:
         def step():
@@ -62,13 +67,16 @@ for fused in (MX_BWD_MODES * 2 if a.fp8_linear_mx_bwd else MX_MODES * 2 if a.fp8
             harness.forward_losses(nets, cfg, x, gt)[0].backward()
         name = "forward+backward only" + {"fp8": ", fp8 Swin linears", "fp8+bwd": ", fp8 Swin linears fwd + bwd", "mx": ", MX Swin linears, emission",
                                           "mx-noemit": ", MX Swin linears, quantiser", "mx+bwd": ", MX Swin linears fwd + row-recipe bwd",
-                                          "mx+mxbwd": ", MX Swin linears fwd + MX bwd"}.get(fused, "")
+                                          "mx+mxbwd": ", MX Swin linears fwd + MX bwd",
+                                          "mx+mxbwd+store": ", MX fwd + MX bwd, inputs stored as MX rows"}.get(fused, "")
     else:
         solvers, _ = harness.make_solvers(nets, cfg, fused=fused)
         def step():
             harness.train_step(nets, solvers, cfg, x, gt)
         name = "train_step, flat solvers" if fused else "train_step, torch.optim + clip_grad_norm_"
+    torch.cuda.reset_peak_memory_stats()
     ms = timed(step, a.steps)
-    print(f"{name:45s} {ms:8.2f} ms/step  {a.batch * a.views / ms * 1e3:8.1f} views/s", flush=True)
+    peak = f"  peak {torch.cuda.max_memory_allocated() / 2 ** 20:9.1f} MiB" if a.fp8_linear_mx_store else ""
+    print(f"{name:45s} {ms:8.2f} ms/step  {a.batch * a.views / ms * 1e3:8.1f} views/s{peak}", flush=True)
     del nets
     torch.cuda.empty_cache()

@@ -53,7 +53,9 @@
 //                  val = acc, no division.  The epilogue (bias, pre_act copy, GELU, residual + row_scale, ldc) is the per-row kernel's, unchanged.
 //   emission       optional q_out / qs_out: the MX rows of the STORED output (after the activation, rounded to the storage type), for the output
 //                  the next linear contracts over (fc1's h): Kp_out = N, so N % 128 == 0, and no residual.  With q_out, out and pre_act may be
-//                  null (no backward follows): fc1 then writes 1 byte per hidden element instead of 4.
+//                  null (no backward follows): fc1 then writes 1 byte per hidden element instead of 4.  With q_out, out may also be null
+//                  while pre_act is given in front of an activation (fc1 under the MX store below): pre_act and the rows are written,
+//                  bit-identical to the call that stores out too.  Without an activation that form stays refused (pre_act would be out itself).
 // Kernels of the MX recipe
 //   quant_rows_mx_kernel   the definition every producer equals: one wave per row, 8 lanes per block, three lane exchanges for the block maximum.
 //   linear_fp8_kernel<.., MX = true>   the kernel above with lf_contract<true>: the scale dwords of a k-step (128 + 128, 1 KB per buffer) are
@@ -109,6 +111,23 @@
 //                    16-byte read-add-write into dw.  More: split z stores its fp32 partial tile into a caller-owned workspace [splits][N][K]
 //                    (16-byte stores) and linear_mxfp8_wgrad_reduce_kernel adds the partials to dw in ascending z: dw is bit-identical from run to
 //                    run for a given `splits`.  splits = 0: enough workgroups for two per CU of 256 CUs, at most one per 128 tokens.
+//
+// MX store (opt-in: set_linear_fp8(True, backward=True, recipe="mx", backward_recipe="mx", store="mx")): the training tape keeps the MX ROWS the
+// forward GEMM consumed in place of the stored tensor, and the weight gradient re-blocks them along the tokens.  NORMATIVE:
+//   sv_mx_rows_to_cols   xq [M][Kp] e4m3 bytes + xs [M][Kp / 32] E8M0 bytes (a block = 32 columns of a row) -> dst_q [K][Mp] bytes + scales_u8
+//                  [K][Mp / 32] (a block = 32 tokens of a column), Mp = roundup(M, 128).  The output EQUALS the MX column quantiser applied to the
+//                  dequantised rows, columns 0 .. K - 1, bit for bit: decode byte 2^(s - 127) in fp32 (exact: at most 4 significant bits, exponent
+//                  >= -136); block maximum over the valid tokens; mx_block_exp and pack4_e4m3_mx of common.h; bytes past M zero; blocks wholly past M
+//                  byte 127.  Columns >= K of xq do not influence the result.  The decode is exact down to the smallest scale byte only with fp32
+//                  denormals PRESERVED (v_ldexp_f32 and v_max_f32 follow the kernel's denormal mode; hipcc's default for gfx9 keeps them, and the
+//                  file must not be built with -fgpu-flush-denormals-to-zero): below 2^-126 the decoded values are fp32 denormals.
+//   why it is today's recipe   a power-of-two block scale makes e4m3 a floating-point format: rounding under the row block's exponent and then
+//                  under the column block's gives the bits of rounding once under the column block's, except for values that are subnormal
+//                  under one of the two (tests/test_cpu_linear_mxfp8_store_recipe.py: the weight gradient moves by <= 2.5e-6, L1-relative; bound 1e-5).
+// Kernel of the MX store
+//   mx_rows_to_cols_kernel   ONE launch, xq and xs read once, no atomics: a 128-token x 128-column tile per workgroup, 16-byte global loads along
+//                  K (8 lanes = the 128 contiguous bytes of a row), a byte transpose through LDS (described at the kernel), 16-byte stores along M,
+//                  the four scale bytes of a column and tile as one aligned dword.
 #include "common.h"
 #include <atomic>
 
@@ -363,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const typename LinAr
               make_uint4(pack4_e4m3_mx(t[0], t[1], t[2], t[3], E), pack4_e4m3_mx(t[4], t[5], t[6], t[7], E),
                          pack4_e4m3_mx(t[8], t[9], t[10], t[11], E), pack4_e4m3_mx(t[12], t[13], t[14], t[15], E));
           if ((lg & 1) == 0) p.qs_out[(size_t)m * (p.N >> 5) + (c0 >> 5)] = (uint8_t)(E + 127);
-          if (!Y) continue;                                // no backward follows: neither out nor pre_act is stored
+          if (!Y && !PRE) continue;                        // no backward follows: neither out nor pre_act is stored
         }
       } else {
 #pragma unroll
@@ -379,6 +398,7 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const typename LinAr
 #pragma unroll
           for (int j = 0; j < CV; ++j) t[j] = v[q * CV + j];
           if (PRE) stnf<CV>(PRE + o + q * CV, t);
+          if constexpr (MX) { if (!Y) continue; }          // MX store: pre_act and the emitted rows are all the backward reads
 #pragma unroll
           for (int j = 0; j < CV; ++j) t[j] = apply_act_t<FAST>(t[j], p.act, p.slope);
           if (RES) {
@@ -397,6 +417,7 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const typename LinAr
 #pragma unroll
           for (int j = 0; j < 4; ++j) t[j] = v[q * 4 + j];
           if (PRE) stnf<4>(PRE + o + q * 4, t);
+          if constexpr (MX) { if (!Y) continue; }
 #pragma unroll
           for (int j = 0; j < 4; ++j) t[j] = apply_act_t<FAST>(t[j], p.act, p.slope);
           if (RES) {
@@ -413,6 +434,7 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const typename LinAr
           if (c0 + j < p.N) {
             float t = v[j];
             if (PRE) stf(PRE + o + j, t);
+            if constexpr (MX) { if (!Y) continue; }
             t = apply_act_t<FAST>(t, p.act, p.slope);
             if (RES) t = ldf(RES + orow + j) + sc * t;
             stf(Y + o + j, t);
@@ -748,8 +770,67 @@ __global__ __launch_bounds__(256) void quant_cols_mx_kernel(const T* __restrict_
   }
 }
 
+// MX re-blocker: the MX ROWS of a stored tensor (xq [M][Kp] bytes + xs [M][Kp / 32] scale bytes, a block = 32 columns of a row) become the MX COLUMN
+// operand of the weight gradient (dst [K][Mp] bytes + scales [K][Mp / 32], a block = 32 tokens of a column) - see "MX store" in the header.
+// One workgroup = 128 tokens x 128 columns, 16 KB in and 16 KB out.
+//   load     thread t moves the 16-byte pieces t, t + 256, t + 512, t + 768 of the tile (8 lanes = the 128 contiguous bytes of one row) into a plain
+//            [128][128]-byte LDS image (eight lanes of a ds_write_b128 cover the 32 banks once); t < 128 also stages the scale dword of row t (the
+//            four k-blocks of the tile).  Rows past M are zero bytes.
+//   compute  wave b owns tokens 32 b .. + 31; lane l owns column 64 u + l, u = 0, 1: one MX block per (lane, u).  It reads its 32 bytes down the
+//            column (the 32 lanes of a group read 8 consecutive dwords of one row: no conflict), decodes byte 2^(s - 127) in fp32 (exact; the row's
+//            scale dword comes from lane j of the wave by v_readlane), takes the maximum and packs 8 dwords under the column block's exponent.
+//   store    the 8 dwords go into the [128][33]-dword image of quant_cols_mx_kernel (conflict-free on both sides: 32 consecutive columns x pitch 33
+//            on the way in, 4 columns x 8 pieces on the way out) and leave as 16-byte stores along M; the four scale bytes of a column are one dword.
+constexpr int RB_ROWS = 128, RB_COLS = 128, RB_PITCH = 33;
+__global__ __launch_bounds__(256) void mx_rows_to_cols_kernel(const uint8_t* __restrict__ xq, int Kp, const uint8_t* __restrict__ xs, int M, int K,
+                                                              uint8_t* __restrict__ dst, int Mp, uint8_t* __restrict__ scales) {
+  __shared__ __attribute__((aligned(16))) uint8_t in[RB_ROWS * RB_COLS];   // [token][column] bytes
+  __shared__ uint32_t srows[RB_ROWS];                        // [token]: the scale bytes of the tile's four k-blocks
+  __shared__ uint32_t tile[RB_COLS * RB_PITCH];            // [column][32 dwords = 128 tokens]
+  __shared__ uint32_t sbytes[RB_COLS];                     // [column][4 token blocks]: one dword per column
+  const int tid = threadIdx.x, lane = tid & 63, b = tid >> 6;
+  const int k0 = blockIdx.x * RB_COLS, m0 = blockIdx.y * RB_ROWS;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pc = tid + 256 * i, r = pc >> 3, c = pc & 7;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (m0 + r < M) v = *reinterpret_cast<const uint4*>(xq + (size_t)(m0 + r) * Kp + k0 + c * 16);   // k0 + 127 < Kp: a whole piece is in range
+    *reinterpret_cast<uint4*>(in + r * RB_COLS + c * 16) = v;
+  }
+  if (tid < RB_ROWS) srows[tid] = (m0 + tid < M) ? *reinterpret_cast<const uint32_t*>(xs + (size_t)(m0 + tid) * (Kp >> 5) + (k0 >> 5)) : 0x7f7f7f7fu;
+  __syncthreads();
+  const int srow = (int)srows[b * 32 + (lane & 31)];         // lane j (and j + 32) holds the scale dword of token 32 b + j
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int col = u * 64 + lane, sh = (col >> 5) * 8;    // the column's k-block inside the tile selects the byte of the scale dword
+    float v[32];
+    float am = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      const int s = (__builtin_amdgcn_readlane(srow, j) >> sh) & 0xff;
+      v[j] = ldexpf(__builtin_amdgcn_cvt_f32_fp8((int)in[(b * 32 + j) * RB_COLS + col], 0), s - 127);
+      am = fmaxf(am, fabsf(v[j]));
+    }
+    const int E = mx_block_exp(am);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) tile[col * RB_PITCH + b * 8 + i] = pack4_e4m3_mx(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], E);
+    reinterpret_cast<uint8_t*>(sbytes)[col * 4 + b] = (uint8_t)(E + 127);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {                            // 128 columns x 8 pieces of 16 bytes
+    const int pc = tid + 256 * i, col = pc >> 3, piece = pc & 7;
+    if (k0 + col < K) {
+      const uint32_t* t = tile + col * RB_PITCH + piece * 4;
+      *reinterpret_cast<uint4*>(dst + (size_t)(k0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
+    }
+  }
+  if (tid < RB_COLS && k0 + tid < K) reinterpret_cast<uint32_t*>(scales + (size_t)(k0 + tid) * (Mp >> 5))[m0 >> 7] = sbytes[tid];   // one aligned dword
+}
+
 static std::atomic<long long> linear_fp8_launches{0};
 static std::atomic<long long> linear_mxfp8_bwd_launches[2], quant_cols_mx_launches{0};   // MX data gradient, MX weight gradient; the MX column quantiser
+static std::atomic<long long> mx_rows_to_cols_launches{0};
 static std::atomic<long long> linear_mxfp8_launches{0}, quant_rows_mx_launches{0};
 static std::atomic<long long> linear_fp8_bwd_launches[2];   // data gradient, weight gradient
 
@@ -861,7 +942,8 @@ extern "C" int sv_linear_mxfp8(const void* xq, const void* xs, const void* wq, c
   SV_REQUIRE(linear_fp8_epilogue_ok(e, N, &why), "sv_linear_mxfp8: %s", why);
   SV_REQUIRE(!q_out || (!e->residual && !e->row_scale), "sv_linear_mxfp8: the emission of the output's MX rows is not served with a residual");
   SV_REQUIRE(!q_out || N % 128 == 0, "sv_linear_mxfp8: the emission of the output's MX rows needs N (%d) %% 128 == 0", N);
-  SV_REQUIRE(out || !e->pre_act, "sv_linear_mxfp8: pre_act without out");
+  // pre_act exists for the derivative of the activation: without an activation it would be the unstored out under another name
+  SV_REQUIRE(out || !e->pre_act || e->act != SV_ACT_NONE, "sv_linear_mxfp8: pre_act without out is served only in front of an activation");
   SV_REQUIRE((((uintptr_t)xq | (uintptr_t)wq | (uintptr_t)q_out) & 15) == 0, "sv_linear_mxfp8: quantised operands must be 16-byte aligned");
   SV_REQUIRE((((uintptr_t)xs | (uintptr_t)ws | (uintptr_t)qs_out) & 3) == 0, "sv_linear_mxfp8: scale bytes must be 4-byte aligned");
   const uintptr_t amask = act_dtype == SV_BF16 ? 7 : 15;
@@ -973,6 +1055,24 @@ extern "C" int sv_quant_cols_mx_e4m3(const void* src, int src_dtype, int M, int 
   else hipLaunchKernelGGL(quant_cols_mx_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(src), M, C, (long long)ld, q, Mp, sc, colsum);
   const int rc = check_launch("sv_quant_cols_mx_e4m3");
   if (rc == SV_OK) quant_cols_mx_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+extern "C" long long sv_mx_rows_to_cols_launches(void) { return mx_rows_to_cols_launches.load(std::memory_order_relaxed); }
+
+extern "C" int sv_mx_rows_to_cols(const void* xq, int Kp, const void* xs, int M, int K, void* dst_q, int Mp, void* scales_u8, void* stream) {
+  SV_REQUIRE(xq && xs && dst_q && scales_u8, "sv_mx_rows_to_cols: null argument");
+  SV_REQUIRE(M > 0 && K > 0, "sv_mx_rows_to_cols: M (%d) and K (%d) must be positive", M, K);
+  SV_REQUIRE(Kp == cdiv(K, 128) * 128, "sv_mx_rows_to_cols: Kp (%d) must be K (%d) rounded up to a multiple of 128", Kp, K);
+  SV_REQUIRE(Mp == cdiv(M, 128) * 128, "sv_mx_rows_to_cols: Mp (%d) must be M (%d) rounded up to a multiple of 128", Mp, M);
+  SV_REQUIRE((((uintptr_t)xq | (uintptr_t)dst_q) & 15) == 0, "sv_mx_rows_to_cols: xq and dst_q must be 16-byte aligned");
+  SV_REQUIRE((((uintptr_t)xs | (uintptr_t)scales_u8) & 3) == 0, "sv_mx_rows_to_cols: xs and scales_u8 must be 4-byte aligned");
+  SV_REQUIRE(Mp / RB_ROWS <= 65535, "sv_mx_rows_to_cols: M (%d) is too large", M);
+  const dim3 grid(Kp / RB_COLS, Mp / RB_ROWS);
+  hipLaunchKernelGGL(mx_rows_to_cols_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const uint8_t*>(xq), Kp,
+                     static_cast<const uint8_t*>(xs), M, K, static_cast<uint8_t*>(dst_q), Mp, static_cast<uint8_t*>(scales_u8));
+  const int rc = check_launch("sv_mx_rows_to_cols");
+  if (rc == SV_OK) mx_rows_to_cols_launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }
 

@@ -140,23 +140,29 @@ def _drop_scale(I, p, seed, like):
     return sc
 
 
-def _norm_for_linear(x, norm, rows, Cd, spec, w, save, merge_hw=(0, 0), **epi):
+def _norm_for_linear(x, norm, rows, Cd, spec, w, save, merge_hw=(0, 0), store_mx=False, **epi):
     """The LayerNorm in front of a Swin linear (norm1 -> qkv, norm2 -> fc1, patch-merge norm -> reduction; **epi: that linear's epilogue form)
     -> (ln, mean, rstd, xq).  When the linear will take the fp8 kernel and the fused quantiser is on (row recipe: ops.ln_quant_site, MX
     recipe: ops.ln_quant_mx_site), the LayerNorm kernel emits the quantised rows xq = (bytes, scales) itself, and without `save` (no backward
-    follows) stores nothing else (ln, mean, rstd are None); otherwise xq is None and this is ops.layernorm_fwd."""
+    follows) stores nothing else (ln, mean, rstd are None); otherwise xq is None and this is ops.layernorm_fwd.
+    store_mx (the caller asked ops.mx_store_site): the tape will keep xq in place of ln, so ln comes back as None and xq always - an emitting
+    LayerNorm does not write ln at all, otherwise ln is quantised here by the stand-alone quantiser and dropped."""
     if ops.ln_quant_site(spec, w, **epi):
         ln, m, r, q, sq = ops.layernorm_quant_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save)
         return ln, m, r, (q, sq)
     if ops.ln_quant_mx_site(spec, w, **epi):
-        ln, m, r, q, sq = ops.layernorm_quant_mx_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save)
+        ln, m, r, q, sq = ops.layernorm_quant_mx_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save, store_y=not store_mx)
         return ln, m, r, (q, sq)
-    return ops.layernorm_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw) + (None,)
+    ln, m, r = ops.layernorm_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw)
+    if store_mx:
+        return None, m, r, ops.quantize_rows_mx(ln, rows, Cd)
+    return ln, m, r, None
 
 
 def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
     """x [I*res*res, C] -> same shape; returns (out, ctx).  save=False (no backward will follow): the fused attention branch
-    skips the tensors it would store for the backward."""
+    skips the tensors it would store for the backward.  Store "mx" (ops.mx_store_site, unfused branches with `save`): the ctx slots of ln1,
+    att, ln2 and h hold the MX rows the forward GEMM consumed, (bytes, scales), in place of the tensor."""
     H = W = blk.res
     Cd, M = blk.dim, I * H * W
     dp = blk.drop_path if (training and stochastic) else 0.0
@@ -177,16 +183,20 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
                         ptr(a.proj.weight), ptr(a.proj.bias), ptr(sc1), ptr(x1), ptr(ln1), ptr(m1), ptr(r1), ptr(qkv), ptr(att),
                         I, H, W, Cd, blk.heads, blk.shift, float(blk.norm1.eps), tag=f"M={M} C={Cd}")
     else:
-        ln1, m1, r1, q1 = _norm_for_linear(x, blk.norm1, M, Cd, blk.s_qkv, blk.attn.qkv.weight, save, bias=blk.attn.qkv.bias)
+        # the fused attention backward reads ln1 and att as tensors: the branch then keeps its bf16 tape
+        store_a = save and ops.linear_fp8_store() == "mx" and not ops.fused_attn_block_bwd_enabled(Cd, blk.heads)
+        st1 = store_a and ops.mx_store_site(blk.s_qkv, blk.attn.qkv.weight, bias=blk.attn.qkv.bias)
+        ln1, m1, r1, q1 = _norm_for_linear(x, blk.norm1, M, Cd, blk.s_qkv, blk.attn.qkv.weight, save, store_mx=st1, bias=blk.attn.qkv.bias)
         qkv = empty(M, 3 * Cd, like=x)
         ops.swin_linear_fwd(ln1, M, blk.s_qkv, blk.attn.qkv.weight, qkv, xq=q1, bias=blk.attn.qkv.bias)
         sc1 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
         sc2 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
         proj_epi = dict(bias=blk.attn.proj.bias, residual=x, ldr=Cd, row_scale=sc1, rows_per_scale=H * W)
+        sta = store_a and ops.mx_store_site(blk.s_proj, blk.attn.proj.weight, **proj_epi)
         # algorithmic work of the core (49-token windows, no padding): QK^T + PV = 4 * 49 * 32 flop per (token, head); bytes: qkv in, out
         if ops.mx_emit_site(blk.s_proj, blk.attn.proj.weight, proj_epi):
             # MX recipe: the core emits the operand rows of proj (one head of a token = one block); without `save` att itself is not stored
-            att, Kp = (empty(M, Cd, like=x) if save else None), (Cd + 127) // 128 * 128
+            att, Kp = (empty(M, Cd, like=x) if (save and not sta) else None), (Cd + 127) // 128 * 128
             qa = (torch.empty(M, Kp, dtype=torch.uint8, device=x.device), torch.empty(M, Kp // 32, dtype=torch.uint8, device=x.device))
             ops.traced_call("sv_window_attention_fwd_mxq", 4.0 * 49 * 32 * M * blk.heads, (esz * (4 if save else 3) + 1) * M * Cd, ptr(qkv),
                             ptr(blk.attn.relative_position_bias_table), ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(),
@@ -195,8 +205,14 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
             att, qa = empty(M, Cd, like=x), None
             ops.traced_call("sv_window_attention_fwd", 4.0 * 49 * 32 * M * blk.heads, esz * 4 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
                             ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(), tag=f"M={M} C={Cd}")
+            if sta:
+                qa = ops.quantize_rows_mx(att, M, Cd)
         x1 = empty(M, Cd, like=x)
         ops.swin_linear_fwd(att, M, blk.s_proj, blk.attn.proj.weight, x1, xq=qa, **proj_epi)
+        if st1:
+            ln1 = q1
+        if sta:
+            att = qa                                       # the tensor, where one was written, is dropped here
     if ops.fused_mlp_enabled(Cd):
         # norm2 -> fc1 -> GELU -> fc2 -> drop-path -> +x1 in ONE kernel; the 4C-wide hidden activation never reaches HBM
         packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
@@ -206,22 +222,31 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         ops.traced_call("sv_swin_mlp_fwd", 2 * unit, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs),
                         ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
         return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, packs, None, I)
-    ln2, m2, r2, q2 = _norm_for_linear(x1, blk.norm2, M, Cd, blk.s_fc1, blk.mlp.fc1.weight, save, bias=blk.mlp.fc1.bias, act=ACT_GELU)
+    st2 = save and ops.mx_store_site(blk.s_fc1, blk.mlp.fc1.weight, bias=blk.mlp.fc1.bias, act=ACT_GELU)
+    ln2, m2, r2, q2 = _norm_for_linear(x1, blk.norm2, M, Cd, blk.s_fc1, blk.mlp.fc1.weight, save, store_mx=st2, bias=blk.mlp.fc1.bias, act=ACT_GELU)
     fc2_epi = dict(bias=blk.mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2, rows_per_scale=H * W)
+    sth = save and ops.mx_store_site(blk.s_fc2, blk.mlp.fc2.weight, **fc2_epi)
     # MX recipe: fc1 emits the operand rows of fc2 from its epilogue; without `save` neither h nor hpre is allocated or written
     emit = ops.mx_emit_site(blk.s_fc2, blk.mlp.fc2.weight, fc2_epi, blk.s_fc1, blk.mlp.fc1.weight, dict(bias=blk.mlp.fc1.bias, act=ACT_GELU))
     hpre = h = None
     if save or not emit:
         hpre = empty(M, 4 * Cd, like=x)
-        h = empty(M, 4 * Cd, like=x)
+        h = empty(M, 4 * Cd, like=x) if not (emit and sth) else None   # store "mx": fc1 writes hpre and the MX rows of h, not h
     qh = ops.swin_linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, xq=q2, emit=emit, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
+    if sth and not emit:
+        qh = ops.quantize_rows_mx(h, M, 4 * Cd)
     x2 = empty(M, Cd, like=x)
     ops.swin_linear_fwd(h, M, blk.s_fc2, blk.mlp.fc2.weight, x2, xq=qh, **fc2_epi)
+    if st2:
+        ln2 = q2
+    if sth:
+        h = qh
     return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, m2, r2, ln2, hpre, h, I)
 
 
 def block_backward(blk: SwinBlock, ctx, dx2, grads):
-    """dx2 is consumed (used as the accumulator of the residual path); returns dx."""
+    """dx2 is consumed (used as the accumulator of the residual path); returns dx.  ln1, att, ln2 and h are tensors or, under store "mx", the MX
+    rows (bytes, scales) the forward kept: ops.swin_linear_wgrad takes either."""
     x, m1, r1, ln1, qkv, att, sc1, sc2, x1, m2, r2, ln2, hpre, h, I = ctx
     H = W = blk.res
     Cd, M = blk.dim, I * H * W
@@ -318,10 +343,11 @@ def stage_forward(stage: SwinStage, x, I, training, stochastic, seeds, save=True
         ds = stage.downsample
         Hin = stage.res * 2
         Mo = I * stage.res * stage.res
-        lnm, mm, rm, qm = _norm_for_linear(x, ds.norm, Mo, 2 * stage.dim, ds.spec, ds.reduction.weight, save, merge_hw=(Hin, Hin))
+        stm = save and ops.mx_store_site(ds.spec, ds.reduction.weight)
+        lnm, mm, rm, qm = _norm_for_linear(x, ds.norm, Mo, 2 * stage.dim, ds.spec, ds.reduction.weight, save, merge_hw=(Hin, Hin), store_mx=stm)
         y = empty(Mo, stage.dim, like=x)
         ops.swin_linear_fwd(lnm, Mo, ds.spec, ds.reduction.weight, y, xq=qm)
-        sctx["merge"] = (x, lnm, mm, rm, Mo, Hin)
+        sctx["merge"] = (x, qm if stm else lnm, mm, rm, Mo, Hin)   # store "mx": the MX rows of the norm's output in place of the tensor
         x = y
     for blk in stage.blocks:
         x, bctx = block_forward(blk, x, I, training, stochastic, seeds, save)

@@ -554,7 +554,7 @@ def linear_fwd(x, rows, spec: ConvSpec, w, out, **epi):
     spec.forward(x, rows, (1, 1, 1), w, out, **epi)
 
 
-def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backward_recipe: str = "row") -> None:
+def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backward_recipe: str = "row", store: str = "bf16") -> None:
     """BASELINE configuration 5, linear part: the FORWARD of the Swin linears (qkv, proj, fc1, fc2, patch-merge reduction) on e4m3 operands
     with per-row scales and the block-scaled K = 128 MFMA (csrc/linear_fp8.hip).  The stored tensors are unchanged.  Without `backward` the
     backward is unchanged too (bf16 data and weight gradients: the quantisers are straight-through); with backward=True (effective only
@@ -572,15 +572,23 @@ def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backwa
     backward_recipe = "row" (default): the backward above, whatever the forward recipe.  backward_recipe = "mx" (effective only with `on` and
     `backward`; combines with either forward recipe; inert under f32 math): both gradients on MX operands - dy per row and W^T, dy^T, x^T by the
     one-launch MX column quantiser (a block = 32 tokens of a column), sv_linear_mxfp8_dgrad and the atomic-free, deterministic
-    sv_linear_mxfp8_wgrad."""
+    sv_linear_mxfp8_wgrad.
+    store = "bf16" (default): the training tape keeps the inputs of the linears (ln1, att, ln2, h, the patch-merge norm's output) in the storage
+    type and the weight gradient quantises them again.  store = "mx" (effective only with `on`, `backward`, recipe "mx" and backward_recipe "mx"
+    under bf16 math; inert otherwise): at the sites mx_store_site names the tape keeps the MX rows the forward GEMM consumed, (bytes, block scales),
+    the tensor itself is not stored (an emitting producer does not write it at all) and the weight gradient re-blocks the rows along the tokens
+    (sv_mx_rows_to_cols).  Outputs, data gradients and the fused stage-0 blocks do not change."""
     if recipe not in ("row", "mx"):
         raise ValueError(f"set_linear_fp8: recipe must be 'row' or 'mx', not {recipe!r}")
     if backward_recipe not in ("row", "mx"):
         raise ValueError(f"set_linear_fp8: backward_recipe must be 'row' or 'mx', not {backward_recipe!r}")
+    if store not in ("bf16", "mx"):
+        raise ValueError(f"set_linear_fp8: store must be 'bf16' or 'mx', not {store!r}")
     _STATE["linear_fp8"] = bool(on)
     _STATE["linear_fp8_bwd"] = bool(on) and bool(backward)
     _STATE["linear_fp8_recipe"] = recipe
     _STATE["linear_fp8_bwd_recipe"] = backward_recipe if (on and backward) else "row"
+    _STATE["linear_fp8_store"] = store if (on and backward and recipe == "mx" and backward_recipe == "mx") else "bf16"
 
 
 def linear_fp8_enabled() -> bool:
@@ -665,6 +673,35 @@ def linear_fp8_bwd_recipe() -> str:
     return _STATE.get("linear_fp8_bwd_recipe", "row")
 
 
+def linear_fp8_store() -> str:
+    """"bf16" or "mx": what the training tape keeps of the inputs of the Swin linears - the EFFECTIVE value ("mx" only while the MX forward and
+    the MX backward both run, which needs bf16 math)."""
+    return "mx" if (_STATE.get("linear_fp8_store", "bf16") == "mx" and linear_fp8_bwd_enabled()) else "bf16"
+
+
+def mx_store_site(spec: ConvSpec, w, **epi) -> bool:
+    """Whether the tape keeps the MX rows of this Swin linear's input in place of the tensor (**epi: the linear's epilogue form): the store
+    switch is effective, the linear takes the MX forward kernel and its weight gradient the MX kernel.  The one copy of the per-site condition;
+    with the switch off this is one flag test."""
+    return linear_fp8_store() == "mx" and _fp8_bwd_site(spec, w) and swin_linear_fp8_epilogue(spec, w, **epi) is not None
+
+
+def mx_rows_to_cols_launches() -> int:
+    """sv_mx_rows_to_cols launches of this process so far."""
+    return int(hip.load().sv_mx_rows_to_cols_launches())
+
+
+def mx_rows_to_cols(xq: torch.Tensor, xs: torch.Tensor, rows: int, K: int):
+    """MX rows (xq [rows, roundup(K, 128)] e4m3 bytes, xs [rows, roundup(K, 128) / 32] E8M0 bytes) -> the MX column operand of the weight
+    gradient (bytes [K, roundup(rows, 128)], block scales [K, roundup(rows, 128) / 32]; a block = 32 tokens of a column) by sv_mx_rows_to_cols:
+    equal to quantize_cols_mx on the dequantised rows."""
+    Mp = (rows + 127) // 128 * 128
+    q = torch.empty(K, Mp, dtype=torch.uint8, device=xq.device)
+    sc = torch.empty(K, Mp // 32, dtype=torch.uint8, device=xq.device)
+    call("sv_mx_rows_to_cols", ptr(xq), xq.shape[1], ptr(xs), rows, K, ptr(q), Mp, ptr(sc))
+    return q, sc
+
+
 def linear_mxfp8_bwd_launches() -> Tuple[int, int]:
     """(sv_linear_mxfp8_dgrad, sv_linear_mxfp8_wgrad) launches of this process so far; linear_fp8_bwd_launches() counts neither."""
     lib = hip.load()
@@ -720,7 +757,8 @@ def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, xq=None, emit=False, **epi)
     already quantised by its producer (layernorm_quant_fwd; under recipe "mx" the MX pair of an emitting fc1 or window attention), which the
     caller obtained because swin_linear_fp8_epilogue said this linear takes the fp8 kernel; the quantiser pass is skipped and x itself is not
     read (it may be None).  emit=True (recipe "mx" only, the caller asked mx_emit_site): the kernel also writes the MX rows of its stored
-    output, returned as (bytes, scales); `out` (and pre_act) may then be None, and nothing else is written."""
+    output, returned as (bytes, scales); `out` may then be None: besides the rows only pre_act is written, when it is given (the library
+    serves that form in front of an activation only: fc1)."""
     e = swin_linear_fp8_epilogue(spec, w, **epi)
     if e is not None and linear_fp8_recipe() == "mx":
         xq, xs = xq if xq is not None else quantize_rows_mx(x, rows, spec.cin)
@@ -730,6 +768,8 @@ def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, xq=None, emit=False, **epi)
             q_out = torch.empty(rows, spec.cout, dtype=torch.uint8, device=xq.device)
             qs_out = torch.empty(rows, spec.cout // 32, dtype=torch.uint8, device=xq.device)
         esz = 0 if out is None else out.element_size()
+        if out is None and epi.get("pre_act") is not None:
+            esz = epi["pre_act"].element_size()            # the form without out (store "mx"): pre_act is the tensor the call writes
         traced_call("sv_linear_mxfp8", 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + (esz + (1 if emit else 0)) * spec.cout) + wq.numel(),
                     ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(out), rows, spec.cin, spec.cout, C.byref(e), ptr(q_out), ptr(qs_out),
                     tag=f"M={rows} K={spec.cin} N={spec.cout}")
@@ -825,13 +865,19 @@ def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True
     (temporaries allocated inside that stream context) unless async_ok is False, in which case it stays in order on the caller's stream (the
     quantised copies are complete before the caller overwrites dy).  The transposed copies, rows x (N + K) bytes, are freed on return either
     way; only dy and x are held until the join.  backward_recipe "mx": the same sequence on the MX column quantiser and sv_linear_mxfp8_wgrad,
-    whose workspace of fp32 partials is one more temporary of that stream context."""
+    whose workspace of fp32 partials is one more temporary of that stream context.
+    x = (bytes, scales): the MX rows of x that the tape kept in place of the tensor (store "mx", the caller asked mx_store_site): the
+    re-blocker (mx_rows_to_cols) takes the place of the column quantiser of x, and the pair's tensors are what is held until the join."""
+    pair = isinstance(x, tuple)
+    mx_site = _fp8_bwd_site(spec, w) and linear_fp8_bwd_recipe() == "mx"
+    if pair and not mx_site:
+        raise RuntimeError("swin_linear_wgrad: stored MX rows were passed to a linear whose weight gradient does not take the MX kernel")
     if not _fp8_bwd_site(spec, w):
         return linear_wgrad(dy, x, rows, spec, dw, db, async_ok=async_ok)
 
     def run_mx():
         dyt, dys = quantize_cols_mx(dy, rows, spec.cout, colsum=db)
-        xt, xs = quantize_cols_mx(x, rows, spec.cin)
+        xt, xs = mx_rows_to_cols(x[0], x[1], rows, spec.cin) if pair else quantize_cols_mx(x, rows, spec.cin)
         nws = int(hip.load().sv_linear_mxfp8_wgrad_workspace_floats(rows, spec.cout, spec.cin, 0))
         ws = fempty(nws, like=dw) if nws else None         # the splits' fp32 partials: written before they are read, dropped once enqueued
         traced_call("sv_linear_mxfp8_wgrad", 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout + 8.0 * nws,
@@ -847,7 +893,7 @@ def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True
     aw = _CTX.awg
     if aw is not None and async_ok:
         aw.stream.wait_stream(torch.cuda.current_stream())     # dy and x are complete on the producing stream
-        aw.held.append((dy, x))                                # the operands stay alive (and unrecycled) until the join
+        aw.held.append((dy,) + x if pair else (dy, x))         # the operands stay alive (and unrecycled) until the join
         with torch.cuda.stream(aw.stream):
             run()      # the temporaries are allocated on the weight-gradient stream and dropped here: its allocator recycles them in stream order
         return
@@ -938,14 +984,15 @@ def layernorm_quant_mx_launches() -> int:
     return int(hip.load().sv_layernorm_quant_mx_launches())
 
 
-def layernorm_quant_mx_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5, store=True):
+def layernorm_quant_mx_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5, store=True, store_y=True):
     """layernorm_fwd that also returns the MX operand rows of the MXFP8 linear it feeds: (y, mean, rstd, xq, xs) with xq [rows,
     roundup(Cdim, 128)] e4m3 bytes and xs [rows, roundup(Cdim, 128) / 32] E8M0 bytes, equal to quantize_rows_mx(y) (which is not launched:
     mx_act_quant_launches() does not move).  store=False (no backward follows): y, mean and rstd are neither allocated nor written and come
-    back as None."""
+    back as None.  store_y=False (the tape keeps the MX rows, store "mx"): the statistics are kept for layernorm_bwd, y is neither allocated
+    nor written."""
     y = mean = rstd = None
     if store:
-        y = empty(rows, Cdim, like=x)
+        y = empty(rows, Cdim, like=x) if store_y else None
         mean = fempty(rows, like=x)
         rstd = fempty(rows, like=x)
     Kp = (Cdim + 127) // 128 * 128
