@@ -207,6 +207,16 @@ long long sv_quant_cols_mx_launches(void); /* sv_quant_cols_mx_e4m3 launches so 
  * Mp / 128 > 65535 (the grid's limit: M above 8 388 480 tokens). */
 int sv_mx_rows_to_cols(const void* xq, int Kp, const void* xs, int M, int K, void* dst_q, int Mp, void* scales_u8, void* stream);
 long long sv_mx_rows_to_cols_launches(void); /* sv_mx_rows_to_cols launches so far in this process (timm Linear behind models/swin_transformer.py:78, operand preparation; tests) */
+/* MX dual quantiser (timm Linear behind models/swin_transformer.py:78, operand preparation of the MX backward: the upstream gradient feeds the data
+ * gradient as MX rows and the weight gradient as MX columns), one launch and one read of src [M, N] (row stride ld, SV_F32 or SV_BF16):
+ * row_q [M, Np] / row_s [M, Np / 32] (Np == roundup(N, 128)) equal sv_quant_rows_mx_e4m3's output and col_q [N][Mp] / col_s [N][Mp / 32]
+ * (Mp == roundup(M, 128)) equal sv_quant_cols_mx_e4m3's, bit for bit for finite inputs, paddings included; colsum (optional, [N] fp32) as in
+ * sv_quant_cols_mx_e4m3.  row_q and row_s may be NULL together: the column form alone.  SV_ERR_INVALID before any GPU call: NULL src, col_q or col_s;
+ * exactly one of row_q / row_s NULL; a bad src_dtype; M < 1, N < 1 or ld < N; Np != roundup(N, 128) (also without the row pair) or
+ * Mp != roundup(M, 128); row_q / col_q not 16-byte or row_s / col_s not 4-byte aligned; Mp / 128 > 65535. */
+int sv_quant_rows_cols_mx_e4m3(const void* src, int src_dtype, int M, int N, int ld, void* row_q, int Np, void* row_s, void* col_q, int Mp,
+                               void* col_s, float* colsum, void* stream);
+long long sv_quant_rows_cols_mx_launches(void); /* sv_quant_rows_cols_mx_e4m3 launches so far in this process (timm Linear behind models/swin_transformer.py:78, operand preparation; tests) */
 /* LDS-halo MFMA stencils for 3x3x3 / stride 1 / pad 1 convolutions with <= 16 output channels per tile (merger.py:20-54),
  * bf16 operands.  x: channels-last positions with row stride ldx, cin_load (multiple of 4) elements read per position,
  * zero-extended to 16*groups channels; w_bf16: [16*ntiles16][27][16*groups] bf16 (forward: rows = output channels;

@@ -7,7 +7,9 @@ the MX recipe with the stand-alone quantiser everywhere (set_mx_producer_quant(F
 --fp8-linear-mx-bwd: forward+backward alone, alternating (two rounds, one process) bf16, the row-recipe forward + backward, the MX forward with
 the row-recipe backward, and the MX forward with the MX backward (backward_recipe="mx").
 --fp8-linear-mx-store: forward+backward alone, alternating (two rounds, one process) bf16, the MX forward + MX backward, and the same with the
-inputs of the linears stored as MX rows (store="mx"); every line also reports torch.cuda.max_memory_allocated of its run."""
+inputs of the linears stored as MX rows (store="mx"); every line also reports torch.cuda.max_memory_allocated of its run.
+--fp8-linear-mx-dual: forward+backward alone, alternating (two rounds, one process) bf16, the MX forward + MX backward with store="mx", and the
+same with the MX dual quantiser (set_mx_dual_quant(True)); with the peak memory of every run."""
 import argparse
 import os
 import sys
@@ -29,6 +31,7 @@ ap.add_argument("--fp8-linear-bwd", action="store_true", help="as --fp8-linear, 
 ap.add_argument("--fp8-linear-mx", action="store_true", help="forward+backward only: bf16, row recipe, MX with and without producer emission, two rounds")
 ap.add_argument("--fp8-linear-mx-bwd", action="store_true", help="forward+backward only: bf16, row fwd + bwd, MX fwd + row bwd, MX fwd + MX bwd, two rounds")
 ap.add_argument("--fp8-linear-mx-store", action="store_true", help="forward+backward only: bf16, MX fwd + MX bwd, the same with store='mx', two rounds; with peak memory")
+ap.add_argument("--fp8-linear-mx-dual", action="store_true", help="forward+backward only: bf16, MX fwd + MX bwd + store='mx', the same with the dual quantiser, two rounds; with peak memory")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = S.default_cfg()
@@ -52,14 +55,19 @@ def timed(fn, n):
 MX_MODES = (None, "fp8", "mx", "mx-noemit")
 MX_BWD_MODES = (None, "fp8+bwd", "mx+bwd", "mx+mxbwd")
 MX_STORE_MODES = (None, "mx+mxbwd", "mx+mxbwd+store")
-for fused in (MX_STORE_MODES * 2 if a.fp8_linear_mx_store else MX_BWD_MODES * 2 if a.fp8_linear_mx_bwd else MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
+MX_DUAL_MODES = (None, "mx+mxbwd+store", "mx+mxbwd+store+dual")
+for fused in (MX_DUAL_MODES * 2 if a.fp8_linear_mx_dual else MX_STORE_MODES * 2 if a.fp8_linear_mx_store else MX_BWD_MODES * 2 if a.fp8_linear_mx_bwd else MX_MODES * 2 if a.fp8_linear_mx else (None, "fp8", "fp8+bwd") if a.fp8_linear_bwd else (None, "fp8") if a.fp8_linear else (True, False, None)):
     torch.manual_seed(0)
     nets = [m(cfg).to(dev).train() for m in (Encoder, Decoder, Merger, Refiner)]
+    dual = fused == "mx+mxbwd+store+dual"
+    if dual:
+        fused = "mx+mxbwd+store"
     fp8 = fused in ("fp8", "fp8+bwd", "mx", "mx-noemit", "mx+bwd", "mx+mxbwd", "mx+mxbwd+store")
     S.set_linear_fp8(fp8, backward=fused in ("fp8+bwd", "mx+bwd", "mx+mxbwd", "mx+mxbwd+store"),
                      recipe="mx" if fused in ("mx", "mx-noemit", "mx+bwd", "mx+mxbwd", "mx+mxbwd+store") else "row",
                      backward_recipe="mx" if fused in ("mx+mxbwd", "mx+mxbwd+store") else "row", store="mx" if fused == "mx+mxbwd+store" else "bf16")
     ops.set_mx_producer_quant(fused != "mx-noemit")
+    ops.set_mx_dual_quant(dual)
     if fused is None or fp8:
         def step():
             for n in nets:
@@ -68,7 +76,7 @@ for fused in (MX_STORE_MODES * 2 if a.fp8_linear_mx_store else MX_BWD_MODES * 2 
         name = "forward+backward only" + {"fp8": ", fp8 Swin linears", "fp8+bwd": ", fp8 Swin linears fwd + bwd", "mx": ", MX Swin linears, emission",
                                           "mx-noemit": ", MX Swin linears, quantiser", "mx+bwd": ", MX Swin linears fwd + row-recipe bwd",
                                           "mx+mxbwd": ", MX Swin linears fwd + MX bwd",
-                                          "mx+mxbwd+store": ", MX fwd + MX bwd, inputs stored as MX rows"}.get(fused, "")
+                                          "mx+mxbwd+store": ", MX fwd + MX bwd, inputs stored as MX rows"}.get(fused, "") + (", dual quantiser" if dual else "")
     else:
         solvers, _ = harness.make_solvers(nets, cfg, fused=fused)
         def step():
@@ -76,7 +84,7 @@ for fused in (MX_STORE_MODES * 2 if a.fp8_linear_mx_store else MX_BWD_MODES * 2 
         name = "train_step, flat solvers" if fused else "train_step, torch.optim + clip_grad_norm_"
     torch.cuda.reset_peak_memory_stats()
     ms = timed(step, a.steps)
-    peak = f"  peak {torch.cuda.max_memory_allocated() / 2 ** 20:9.1f} MiB" if a.fp8_linear_mx_store else ""
+    peak = f"  peak {torch.cuda.max_memory_allocated() / 2 ** 20:9.1f} MiB" if a.fp8_linear_mx_store or a.fp8_linear_mx_dual else ""
     print(f"{name:45s} {ms:8.2f} ms/step  {a.batch * a.views / ms * 1e3:8.1f} views/s{peak}", flush=True)
     del nets
     torch.cuda.empty_cache()

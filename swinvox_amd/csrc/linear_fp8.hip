@@ -128,6 +128,22 @@
 //   mx_rows_to_cols_kernel   ONE launch, xq and xs read once, no atomics: a 128-token x 128-column tile per workgroup, 16-byte global loads along
 //                  K (8 lanes = the 128 contiguous bytes of a row), a byte transpose through LDS (described at the kernel), 16-byte stores along M,
 //                  the four scale bytes of a column and tile as one aligned dword.
+//
+// MX dual quantiser (opt-in on the host: set_mx_dual_quant(True) under the MX backward): the upstream gradient dy feeds the data gradient as MX rows
+// and the weight gradient as MX columns; one launch reads it once and writes both.  NORMATIVE, for finite inputs:
+//   sv_quant_rows_cols_mx_e4m3   src [M, N] (row stride ld, bf16 or fp32) ->
+//                  row_q [M][Np] + row_s [M][Np / 32], Np = roundup(N, 128): EQUAL to sv_quant_rows_mx_e4m3(src, .., Np) bit for bit (bytes N .. Np - 1
+//                  zero, padding blocks byte 127);
+//                  col_q [N][Mp] + col_s [N][Mp / 32], Mp = roundup(M, 128): EQUAL to sv_quant_cols_mx_e4m3(src, .., Mp) bit for bit (bytes M .. Mp - 1
+//                  of every row zero, blocks wholly past M byte 127, a partly filled block takes the maximum of its valid rows);
+//                  colsum[c] += sum_m src[m, c] of the unquantised values: one fp64 partial per workgroup (128 tokens), one fp32 atomicAdd per
+//                  workgroup and column - the column quantiser's scheme.
+//                  row_q = row_s = NULL: the column form alone.  mx_block_exp and pack4_e4m3_mx of common.h are the only copy of the rounding.
+// Kernel of the MX dual quantiser
+//   quant_rows_cols_mx_kernel   ONE launch, src read once, no memset, no atomics but colsum's: the re-blocker's 128-token x 128-column tile with
+//                  16-byte global loads along the row; the row form leaves from the registers of the load (one lane exchange per block maximum,
+//                  16-byte stores), the column form from the values staged in LDS (described at the kernel).  With Np and Mp multiples of 128 the
+//                  four row blocks of a token and the four token blocks of a column lie inside the tile: no maximum crosses workgroups.
 #include "common.h"
 #include <atomic>
 
@@ -828,7 +844,137 @@ __global__ __launch_bounds__(256) void mx_rows_to_cols_kernel(const uint8_t* __r
   if (tid < RB_COLS && k0 + tid < K) reinterpret_cast<uint32_t*>(scales + (size_t)(k0 + tid) * (Mp >> 5))[m0 >> 7] = sbytes[tid];   // one aligned dword
 }
 
+// MX dual quantiser: ONE read of src [M, N] gives the MX ROW operand (row_q [M][Np] + row_s [M][Np / 32], equal to quant_rows_mx_kernel) and the MX
+// COLUMN operand (col_q [N][Mp] + col_s [N][Mp / 32] + colsum, equal to quant_cols_mx_kernel) - see "MX dual quantiser" in the header.  One workgroup =
+// 128 tokens x 128 columns; ROWS_OUT = false compiles the row work out (the column form alone, with this kernel's loader).
+//   load     a chunk = 16 consecutive elements of one tile row (sizeof(T) 16-byte pieces: two for bf16, four for fp32); thread t moves the chunks t,
+//            t + 256, t + 512, t + 768 (8 lanes = the 128 columns of one row).  A row that is not 16-byte aligned, and the chunk that crosses N, take
+//            load4_guarded's per-element path.  Rows past M and columns >= N are zeros.  The chunk goes into a plain [128][128] LDS image of T
+//            as it was loaded (the stored values, no conversion).
+//   rows     from the registers of the load: a 32-element block is the chunks of lanes c and c ^ 1, so its maximum is one lane exchange; a lane packs
+//            its 16 bytes (one 16-byte store) and the even lane writes the E8M0 byte.  Rows past M write nothing; columns N .. Np - 1 are the padding
+//            (zero bytes, byte 127), written like any other chunk.
+//   columns  mx_rows_to_cols_kernel's compute and store on the staged values: wave b owns tokens 32 b .. + 31, lane l columns l and 64 + l, one MX
+//            block per (lane, column) read down the tile (a wave reads 64 consecutive elements of one row: no conflict); fp64 column sums as in
+//            quant_cols_mx_kernel.  The 8 packed dwords, the scale byte and the sum wait in registers for a barrier, after which the [column][33
+//            dwords] image, the scale dwords and the partial sums take the place of the input image: LDS is 32 KB (bf16) / 64 KB (fp32).
+//            Columns >= N write nothing; rows past M were loaded as zeros and leave as the zero bytes of the column rows.
+constexpr int DQ_ROWS = 128, DQ_COLS = 128, DQ_PITCH = 33;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <typename T>
+__device__ __forceinline__ float dq_elem(const u32x4 (&p)[sizeof(T)], int j) {   // element j of a chunk held as raw 16-byte pieces
+  if constexpr (sizeof(T) == 4) return __uint_as_float(p[j >> 2][j & 3]);
+  else return __uint_as_float((j & 1) ? (p[j >> 3][(j >> 1) & 3] & 0xffff0000u) : (p[j >> 3][(j >> 1) & 3] << 16));
+}
+
+template <typename T, bool ROWS_OUT>
+__global__ __launch_bounds__(256) void quant_rows_cols_mx_kernel(const T* __restrict__ src, int M, int N, long long ld, uint8_t* __restrict__ row_q, int Np,
+                                                                 uint8_t* __restrict__ row_s, uint8_t* __restrict__ col_q, int Mp,
+                                                                 uint8_t* __restrict__ col_s, float* __restrict__ colsum) {
+  constexpr int P = sizeof(T);                             // 16-byte pieces per chunk
+  constexpr int IN_BYTES = DQ_ROWS * DQ_COLS * (int)sizeof(T);
+  constexpr int SUM_BYTES = 4 * DQ_COLS * 8, TILE_BYTES = DQ_COLS * DQ_PITCH * 4, OUT_BYTES = SUM_BYTES + TILE_BYTES + DQ_COLS * 4;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[IN_BYTES > OUT_BYTES ? IN_BYTES : OUT_BYTES];
+  const T* in = reinterpret_cast<const T*>(smem);          // [token][column], then (after the second barrier):
+  double* ssum = reinterpret_cast<double*>(smem);          // [4 token blocks][column]
+  uint32_t* tile = reinterpret_cast<uint32_t*>(smem + SUM_BYTES);               // [column][32 dwords = 128 tokens]
+  uint32_t* sbytes = reinterpret_cast<uint32_t*>(smem + SUM_BYTES + TILE_BYTES);   // [column][4 token blocks]: one dword per column
+  const int tid = threadIdx.x, lane = tid & 63, b = tid >> 6;
+  const int k0 = blockIdx.x * DQ_COLS, m0 = blockIdx.y * DQ_ROWS;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int ch = tid + 256 * i, r = ch >> 3, c = ch & 7;
+    const int m = m0 + r, k = k0 + 16 * c;
+    u32x4 raw[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) raw[p] = u32x4{0u, 0u, 0u, 0u};
+    if (m < M && k < N) {
+      const T* row = src + (size_t)m * ld;
+      if ((((uintptr_t)row) & 15) == 0 && k + 16 <= N) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) raw[p] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(row + k) + 16 * p);
+      } else {
+        const bool vec = (((uintptr_t)row) & (4 * sizeof(T) - 1)) == 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float v[4] = {0.f, 0.f, 0.f, 0.f};
+          if (k + 4 * q < N) load4_guarded(row, k + 4 * q, N, vec, v);
+          if constexpr (sizeof(T) == 4) {
+            raw[q] = u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+          } else {                                         // the floats came from bf16: their low halves are zero
+            raw[q >> 1][2 * (q & 1)] = (__float_as_uint(v[0]) >> 16) | __float_as_uint(v[1]);
+            raw[q >> 1][2 * (q & 1) + 1] = (__float_as_uint(v[2]) >> 16) | __float_as_uint(v[3]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) *reinterpret_cast<u32x4*>(smem + ((size_t)r * DQ_COLS + 16 * c) * sizeof(T) + 16 * p) = raw[p];
+    if constexpr (ROWS_OUT) {
+      float v[16];
+      float am = 0.f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { v[j] = dq_elem<T>(raw, j); am = fmaxf(am, fabsf(v[j])); }
+      am = fmaxf(am, __shfl_xor(am, 1));
+      const int E = mx_block_exp(am);
+      u32x4 o;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) o[q] = pack4_e4m3_mx(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3], E);
+      if (m < M) {                                         // k + 15 < Np: the grid covers Np / 128 column tiles
+        *reinterpret_cast<u32x4*>(row_q + (size_t)m * Np + k) = o;
+        if ((c & 1) == 0) row_s[(size_t)m * (Np >> 5) + (k >> 5)] = (uint8_t)(E + 127);
+      }
+    }
+  }
+  __syncthreads();
+  uint32_t pk[2][8];
+  int Eb[2];
+  double sum[2] = {0.0, 0.0};
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int col = u * 64 + lane;
+    float v[32];
+    float am = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      v[j] = ldf(in + (b * 32 + j) * DQ_COLS + col);
+      am = fmaxf(am, fabsf(v[j]));
+    }
+    if (colsum) {
+#pragma unroll
+      for (int j = 0; j < 32; ++j) sum[u] += (double)v[j];
+    }
+    Eb[u] = mx_block_exp(am);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pk[u][i] = pack4_e4m3_mx(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], Eb[u]);
+  }
+  __syncthreads();                                         // every wave has read the input image: the output images take its place
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int col = u * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) tile[col * DQ_PITCH + b * 8 + i] = pk[u][i];
+    reinterpret_cast<uint8_t*>(sbytes)[col * 4 + b] = (uint8_t)(Eb[u] + 127);
+    if (colsum) ssum[b * DQ_COLS + col] = sum[u];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {                            // 128 columns x 8 pieces of 16 bytes
+    const int pc = tid + 256 * i, col = pc >> 3, piece = pc & 7;
+    if (k0 + col < N) {
+      const uint32_t* t = tile + col * DQ_PITCH + piece * 4;
+      *reinterpret_cast<uint4*>(col_q + (size_t)(k0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
+    }
+  }
+  if (tid < DQ_COLS && k0 + tid < N) {
+    reinterpret_cast<uint32_t*>(col_s + (size_t)(k0 + tid) * (Mp >> 5))[m0 >> 7] = sbytes[tid];   // the tile's four blocks of the column: one aligned dword
+    if (colsum) atomicAdd(colsum + k0 + tid, (float)(ssum[tid] + ssum[DQ_COLS + tid] + ssum[2 * DQ_COLS + tid] + ssum[3 * DQ_COLS + tid]));
+  }
+}
+
 static std::atomic<long long> linear_fp8_launches{0};
+static std::atomic<long long> quant_rows_cols_mx_launches{0};
 static std::atomic<long long> linear_mxfp8_bwd_launches[2], quant_cols_mx_launches{0};   // MX data gradient, MX weight gradient; the MX column quantiser
 static std::atomic<long long> mx_rows_to_cols_launches{0};
 static std::atomic<long long> linear_mxfp8_launches{0}, quant_rows_mx_launches{0};
@@ -1073,6 +1219,37 @@ extern "C" int sv_mx_rows_to_cols(const void* xq, int Kp, const void* xs, int M,
                      static_cast<const uint8_t*>(xs), M, K, static_cast<uint8_t*>(dst_q), Mp, static_cast<uint8_t*>(scales_u8));
   const int rc = check_launch("sv_mx_rows_to_cols");
   if (rc == SV_OK) mx_rows_to_cols_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+extern "C" long long sv_quant_rows_cols_mx_launches(void) { return quant_rows_cols_mx_launches.load(std::memory_order_relaxed); }
+
+template <typename T>
+static void launch_quant_rows_cols_mx(dim3 grid, hipStream_t s, const void* src, int M, int N, int ld, uint8_t* rq, int Np, uint8_t* rs, uint8_t* cq, int Mp,
+                                      uint8_t* cs, float* colsum) {
+  if (rq) hipLaunchKernelGGL((quant_rows_cols_mx_kernel<T, true>), grid, dim3(256), 0, s, static_cast<const T*>(src), M, N, (long long)ld, rq, Np, rs, cq, Mp, cs, colsum);
+  else hipLaunchKernelGGL((quant_rows_cols_mx_kernel<T, false>), grid, dim3(256), 0, s, static_cast<const T*>(src), M, N, (long long)ld, rq, Np, rs, cq, Mp, cs, colsum);
+}
+
+extern "C" int sv_quant_rows_cols_mx_e4m3(const void* src, int src_dtype, int M, int N, int ld, void* row_q, int Np, void* row_s, void* col_q, int Mp,
+                                          void* col_s, float* colsum, void* stream) {
+  SV_REQUIRE(src && col_q && col_s, "sv_quant_rows_cols_mx_e4m3: null argument (src, col_q and col_s are required)");
+  SV_REQUIRE((row_q != nullptr) == (row_s != nullptr), "sv_quant_rows_cols_mx_e4m3: row_q and row_s go together");
+  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_rows_cols_mx_e4m3: bad source dtype %d", src_dtype);
+  SV_REQUIRE(M > 0 && N > 0 && ld >= N, "sv_quant_rows_cols_mx_e4m3: M (%d) and N (%d) must be positive, ld (%d) >= N", M, N, ld);
+  SV_REQUIRE(Np == cdiv(N, 128) * 128, "sv_quant_rows_cols_mx_e4m3: Np (%d) must be N (%d) rounded up to a multiple of 128", Np, N);
+  SV_REQUIRE(Mp == cdiv(M, 128) * 128, "sv_quant_rows_cols_mx_e4m3: Mp (%d) must be M (%d) rounded up to a multiple of 128", Mp, M);
+  SV_REQUIRE((((uintptr_t)row_q | (uintptr_t)col_q) & 15) == 0, "sv_quant_rows_cols_mx_e4m3: row_q and col_q must be 16-byte aligned");
+  SV_REQUIRE((((uintptr_t)row_s | (uintptr_t)col_s) & 3) == 0, "sv_quant_rows_cols_mx_e4m3: row_s and col_s must be 4-byte aligned");
+  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0 && ((uintptr_t)colsum & 3) == 0, "sv_quant_rows_cols_mx_e4m3: src / colsum are not aligned to their element");
+  SV_REQUIRE(Mp / DQ_ROWS <= 65535, "sv_quant_rows_cols_mx_e4m3: M (%d) is too large", M);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(Np / DQ_COLS, Mp / DQ_ROWS);
+  uint8_t *rq = static_cast<uint8_t*>(row_q), *rs = static_cast<uint8_t*>(row_s), *cq = static_cast<uint8_t*>(col_q), *cs = static_cast<uint8_t*>(col_s);
+  if (src_dtype == SV_BF16) launch_quant_rows_cols_mx<__bf16>(grid, s, src, M, N, ld, rq, Np, rs, cq, Mp, cs, colsum);
+  else launch_quant_rows_cols_mx<float>(grid, s, src, M, N, ld, rq, Np, rs, cq, Mp, cs, colsum);
+  const int rc = check_launch("sv_quant_rows_cols_mx_e4m3");
+  if (rc == SV_OK) quant_rows_cols_mx_launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }
 

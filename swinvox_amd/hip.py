@@ -87,6 +87,8 @@ _PROTOS = {
     "sv_quant_cols_mx_launches": (_L, None),
     "sv_mx_rows_to_cols": (_I, [_P, _I, _P, _I, _I, _P, _I, _P]),
     "sv_mx_rows_to_cols_launches": (_L, None),
+    "sv_quant_rows_cols_mx_e4m3": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P]),
+    "sv_quant_rows_cols_mx_launches": (_L, None),
     "sv_stencil3_fwd": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _L, _L]),
     "sv_stencil3_wgrad_workspace_floats": (C.c_size_t, None, [_I, _I]),
     "sv_stencil3_wgrad": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L]),

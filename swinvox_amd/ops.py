@@ -29,6 +29,7 @@ class _CallContext(threading.local):
     arena = None
     awg = None
     bn_tick = None
+    dyq = None      # one-slot stash of the MX dual quantiser: (dy, rows, N, row bytes, row scales) between swin_linear_wgrad and swin_linear_dgrad
 
 
 _CTX = _CallContext()
@@ -403,10 +404,12 @@ class AsyncWgrad:
     def join(self):
         torch.cuda.current_stream().wait_stream(self.stream)
         self.held.clear()
+        _CTX.dyq = None
 
 
 def set_async_wgrad(aw) -> None:
     _CTX.awg = aw
+    _CTX.dyq = None
 
 
 _SIDE = {}
@@ -820,6 +823,43 @@ def quantize_cols_mx(t: torch.Tensor, rows: int, Cc: int, ld: Optional[int] = No
     return q, sc
 
 
+def quant_rows_cols_mx_launches() -> int:
+    """sv_quant_rows_cols_mx_e4m3 launches of this process so far."""
+    return int(hip.load().sv_quant_rows_cols_mx_launches())
+
+
+def quantize_rows_cols_mx(t: torch.Tensor, rows: int, N: int, ld: Optional[int] = None, colsum: Optional[torch.Tensor] = None, rows_out: bool = True):
+    """t [rows, N] (fp32 or bf16, row stride ld) -> ((dq, ds), (dyt, dys)) by sv_quant_rows_cols_mx_e4m3, one launch and one read of t: (dq, ds)
+    equals quantize_rows_mx(t) and (dyt, dys) equals quantize_cols_mx(t), bit for bit; colsum (fp32 [N]) += the column sums of the unquantised
+    values.  rows_out=False: the column form alone, (None, (dyt, dys))."""
+    Np, Mp = (N + 127) // 128 * 128, (rows + 127) // 128 * 128
+    dq = ds = None
+    if rows_out:
+        dq = torch.empty(rows, Np, dtype=torch.uint8, device=t.device)
+        ds = torch.empty(rows, Np // 32, dtype=torch.uint8, device=t.device)
+    q = torch.empty(N, Mp, dtype=torch.uint8, device=t.device)
+    sc = torch.empty(N, Mp // 32, dtype=torch.uint8, device=t.device)
+    call("sv_quant_rows_cols_mx_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, N, ld or N, ptr(dq), Np, ptr(ds), ptr(q), Mp,
+         ptr(sc), ptr(colsum))
+    return ((dq, ds) if rows_out else None), (q, sc)
+
+
+def set_mx_dual_quant(on: bool) -> None:
+    """A/B switch of the MX dual quantiser (csrc/linear_fp8.hip, sv_quant_rows_cols_mx_e4m3): True lets swin_linear_wgrad quantise dy ONCE, on the
+    caller's stream, into the column operand of the weight gradient and the row operand the data gradient of the same site takes from a one-slot
+    stash, and gives the column operand of a stored bf16 x the same loader; False (default) keeps the row and the column quantiser, with
+    bit-identical data and weight gradients.  Effective only under backward_recipe "mx" with bf16 math; SV_MX_DUAL_QUANT=1 in the environment
+    switches it on as well."""
+    _STATE["mx_dual_quant"] = bool(on)
+    _CTX.dyq = None
+
+
+def mx_dual_quant_enabled() -> bool:
+    import os
+    return (linear_fp8_bwd_enabled() and linear_fp8_bwd_recipe() == "mx"
+            and (_STATE.get("mx_dual_quant", False) or os.environ.get("SV_MX_DUAL_QUANT", "0") == "1"))
+
+
 def quantize_weight_t_mx(w: torch.Tensor):
     """MX rows of W^T for a Linear weight W [N, K] ([K][Np] bytes, a block = 32 consecutive n of one column k): the operand of the MX data
     gradient, cached next to quantize_weight_t_fp8's rows with the same lifetime."""
@@ -840,12 +880,17 @@ def _fp8_bwd_site(spec: ConvSpec, w) -> bool:
 def swin_linear_dgrad(dy, rows, spec: ConvSpec, w, dx, **epi):
     """linear_dgrad of the unfused Swin call sites (w is the PARAMETER): with set_linear_fp8(True, backward=True) (and a form
     sv_linear_fp8_dgrad serves) dy is quantised per row, the quantised W^T fetched and the product runs on the fp8 kernel; otherwise exactly
-    linear_dgrad on the data-gradient weight pack."""
+    linear_dgrad on the data-gradient weight pack.  Under the MX recipe the rows of dy come from the stash of the dual quantiser when it holds
+    this very tensor (set_mx_dual_quant, swin_linear_wgrad); the slot is emptied by the look either way."""
     if _fp8_bwd_site(spec, w):
         e = _epilogue(spec.cin, **epi)
         if hip.load().sv_linear_fp8_dgrad_supported(spec.cout, spec.cin, C.byref(e), _STATE["math"], hip.ACT) == 1:
             if linear_fp8_bwd_recipe() == "mx":
-                dq, ds = quantize_rows_mx(dy, rows, spec.cout, activation=False)
+                st, _CTX.dyq = _CTX.dyq, None              # the dual quantiser's rows of this very dy (swin_linear_wgrad), taken once
+                if st is not None and st[0] is dy and st[1] == rows and st[2] == spec.cout:
+                    dq, ds = st[3], st[4]
+                else:
+                    dq, ds = quantize_rows_mx(dy, rows, spec.cout, activation=False)
                 wtq, wts = quantize_weight_t_mx(w)
                 traced_call("sv_linear_mxfp8_dgrad", 2.0 * rows * spec.cin * spec.cout, float(rows) * (dq.shape[1] + dy.element_size() * spec.cin) + wtq.numel(),
                             ptr(dq), ptr(ds), ptr(wtq), ptr(wts), ptr(dx), rows, spec.cout, spec.cin, C.byref(e), tag=f"M={rows} N={spec.cout} K={spec.cin}")
@@ -867,17 +912,35 @@ def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True
     way; only dy and x are held until the join.  backward_recipe "mx": the same sequence on the MX column quantiser and sv_linear_mxfp8_wgrad,
     whose workspace of fp32 partials is one more temporary of that stream context.
     x = (bytes, scales): the MX rows of x that the tape kept in place of the tensor (store "mx", the caller asked mx_store_site): the
-    re-blocker (mx_rows_to_cols) takes the place of the column quantiser of x, and the pair's tensors are what is held until the join."""
+    re-blocker (mx_rows_to_cols) takes the place of the column quantiser of x, and the pair's tensors are what is held until the join.
+    set_mx_dual_quant(True) at an MX site: dy is quantised ONCE, on the caller's stream and before anything else (quantize_rows_cols_mx with
+    colsum=db): the column pair feeds the GEMM on the weight-gradient stream (recorded on that stream, not held until the join), the row pair
+    waits in the one-slot stash _CTX.dyq for the swin_linear_dgrad of the same dy, which every call site issues next; it is emitted only when
+    that data gradient (the site's plain form) takes the MX kernel.  A stored bf16 x goes through the same kernel's column-only form.  The slot
+    is cleared here on entry, by AsyncWgrad.join() and by set_async_wgrad()."""
     pair = isinstance(x, tuple)
+    _CTX.dyq = None
     mx_site = _fp8_bwd_site(spec, w) and linear_fp8_bwd_recipe() == "mx"
     if pair and not mx_site:
         raise RuntimeError("swin_linear_wgrad: stored MX rows were passed to a linear whose weight gradient does not take the MX kernel")
     if not _fp8_bwd_site(spec, w):
         return linear_wgrad(dy, x, rows, spec, dw, db, async_ok=async_ok)
 
+    dual = mx_site and mx_dual_quant_enabled()
+    dcols = None
+    if dual:                                               # dy is read once, on the caller's stream: db, the column pair, and the row pair
+        e = _epilogue(spec.cin)                            # when the data gradient of this site (its plain form) takes the MX kernel
+        rows_out = hip.load().sv_linear_fp8_dgrad_supported(spec.cout, spec.cin, C.byref(e), _STATE["math"], hip.ACT) == 1
+        drows, dcols = quantize_rows_cols_mx(dy, rows, spec.cout, colsum=db, rows_out=rows_out)
+        if rows_out:
+            _CTX.dyq = (dy, rows, spec.cout) + drows
+
     def run_mx():
-        dyt, dys = quantize_cols_mx(dy, rows, spec.cout, colsum=db)
-        xt, xs = mx_rows_to_cols(x[0], x[1], rows, spec.cin) if pair else quantize_cols_mx(x, rows, spec.cin)
+        dyt, dys = dcols if dual else quantize_cols_mx(dy, rows, spec.cout, colsum=db)
+        if pair:
+            xt, xs = mx_rows_to_cols(x[0], x[1], rows, spec.cin)
+        else:
+            xt, xs = quantize_rows_cols_mx(x, rows, spec.cin, rows_out=False)[1] if dual else quantize_cols_mx(x, rows, spec.cin)
         nws = int(hip.load().sv_linear_mxfp8_wgrad_workspace_floats(rows, spec.cout, spec.cin, 0))
         ws = fempty(nws, like=dw) if nws else None         # the splits' fp32 partials: written before they are read, dropped once enqueued
         traced_call("sv_linear_mxfp8_wgrad", 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout + 8.0 * nws,
@@ -896,6 +959,9 @@ def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True
         aw.held.append((dy,) + x if pair else (dy, x))         # the operands stay alive (and unrecycled) until the join
         with torch.cuda.stream(aw.stream):
             run()      # the temporaries are allocated on the weight-gradient stream and dropped here: its allocator recycles them in stream order
+        if dual:       # the column pair of dy was allocated on the caller's stream and is read on this one: not held, recorded
+            dcols[0].record_stream(aw.stream)
+            dcols[1].record_stream(aw.stream)
         return
     run()
 
