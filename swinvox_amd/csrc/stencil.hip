@@ -7,7 +7,8 @@
 //       A fragment (voxel rows, 8 consecutive channels of one tap) = ONE 16-byte LDS read; weights [16n][27][16G] in LDS.
 //   weight gradient:          dw[co, tap, c] += sum_vox dy[vox, co] * x[vox + tap, c]
 //       the contraction runs over VOXELS: both fragments (8 consecutive x-positions per lane) come from the
-//       [position][channel] images through ds_read_b64_tr_b16; the four waves split the 27 taps.
+//       [position][channel] images through ds_read_b64_tr_b16; the waves split the (dy, dx) pairs and sweep the halo slices
+//       (stencil3_wgrad_sweep_kernel; the earlier kernel, whose waves split the 27 taps, stays behind SV_STENCIL_WGRAD_SWEEP=0).
 // Both kernels are PERSISTENT over bricks: weights / partial sums are set up once per workgroup, and the next brick's
 // halo is prefetched into registers while the current one is contracted (global latency hidden behind the MFMA loop).
 // The forward accumulators are transposed blocks (weight fragment as the MFMA's first operand): a lane holds four consecutive
@@ -97,6 +98,75 @@ struct HaloRegs {
       const int i = tid + NTHR * k;
       if (i < HPOSV * VPP) *reinterpret_cast<bf16x4*>(Xs + lds[k]) = to_bf16x4(r[k]);
     }
+  }
+};
+
+// HaloRegs for a kernel that needs its registers for accumulators (the weight-gradient sweep): the same prefetch with a table of NP entries
+// instead of N.  The halo box is dealt to the threads in NGRP groups of ZG whole z-slices; a thread takes the SAME vectors of every group
+// (NP passes of NTHR threads over a group's ZG * HY * HX * VPP vectors), so group g differs from group 0 by a wave-uniform step only:
+// g ZG slices in memory and in the LDS image, and the z faces belong to the first / last group.  Two words per table entry: off = 32-bit
+// element offset inside the plane, meta = LDS offset (bits 0-19) | face bits as in HaloRegs (20-26) | plane index (27-30).
+// G = 1: 2 groups of 5 slices, 4 passes (8 vectors per thread as HaloRegs); G = 3: 5 groups of 2 slices, 5 passes (25 vectors; HaloRegs 24).
+template <int G, typename AT, int TZV, int NTHR>
+struct HaloSliceRegs {
+  static constexpr int HZV = TZV + 2, C = 16 * G, VPP = C / 4;
+  static constexpr int ZG = G == 1 ? 5 : 2, NGRP = HZV / ZG, GV = ZG * HY * HX * VPP, NP = (GV + NTHR - 1) / NTHR, N = NGRP * NP;
+  static_assert(HZV % ZG == 0, "groups of whole z-slices");
+  static_assert(HZV * HY * 16 * C < (1 << 20), "LDS offsets (pitch <= 16 positions) take 20 bits");
+  typename V4<AT>::type r[N];       // vector j of group g in r[g * NP + j]
+  int off[NP], meta[NP];
+  long long plane_;
+  int gstep_, lstep_;               // group step in memory (elements) and in the LDS image
+  __device__ __forceinline__ void init(int ldx, long long plane, int cin_load, int H, int W, int tid, int pitch) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int i = tid + NTHR * j;
+      int h = i / VPP, v = i - h * VPP;                // position rows: consecutive lanes walk a position's vectors, then x (memory order)
+      const int nvp = ldx / 4;                         // vectors per position in one plane
+      if (plane && VPP % nvp == 0) {
+        // planar channels: consecutive lanes walk ONE plane's x-row (HX positions x nvp vectors, contiguous in memory) before the next
+        // plane's - in position order a wave's load gathers 3 vectors from each of 4 planes per position (24-byte pieces of many lines)
+        const int row = i / (HX * VPP), rem = i - row * (HX * VPP);
+        const int pq = rem / (HX * nvp), r2 = rem - pq * (HX * nvp), px = r2 / nvp;
+        h = row * HX + px; v = pq * nvp + (r2 - px * nvp);
+      }
+      const int hx = h % HX; const int t2 = h / HX; const int hy = t2 % HY; const int hz = t2 / HY;     // hz < ZG where i < GV
+      const int cv = v * 4, pl = plane ? cv / ldx : 0;                                                  // pl <= 11 (ldx >= 4)
+      const int fc = (hz == 0 ? 1 : 0) | (hz == ZG - 1 ? 2 : 0) | (hy == 0 ? 4 : 0) | (hy == HY - 1 ? 8 : 0) | (hx == 0 ? 16 : 0) | (hx == HX - 1 ? 32 : 0) |
+                     ((i < GV && cv < cin_load) ? 0 : 64);
+      const int lo = i < GV ? ((hz * HY + hy) * pitch + hx) * C + cv : 0;
+      meta[j] = lo | (fc << 20) | (pl << 27);
+      off[j] = ((hz * H + hy) * W + hx) * ldx + (cv - pl * ldx);
+    }
+    plane_ = plane; gstep_ = ZG * H * W * ldx; lstep_ = ZG * HY * pitch * C;
+  }
+  __device__ __forceinline__ void load(const AT* __restrict__ x, int ldx, const TileId& t, int D, int H, int W) {
+    const int zlo = t.z0 == 0 ? 1 : 0, zhi = t.z0 + TZV == D ? 2 : 0;
+    const int yx = (t.y0 == 0 ? 4 : 0) | (t.y0 + TY == H ? 8 : 0) | (t.x0 == 0 ? 16 : 0) | (t.x0 + TX == W ? 32 : 0) | 64;
+    const AT* corner = x + ((((long long)t.img * D + t.z0 - 1) * H + t.y0 - 1) * W + t.x0 - 1) * (long long)ldx;   // may point before the volume: only in-range vectors are read
+#pragma unroll
+    for (int g = 0; g < NGRP; ++g) {
+      const int out = (yx | (g == 0 ? zlo : 0) | (g == NGRP - 1 ? zhi : 0)) << 20;   // only the first / last group touches a z face
+      const AT* cg = corner + (long long)g * gstep_;
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        typename V4<AT>::type q = V4<AT>::zero();
+#ifndef SV_ST_PROBE_NOLOAD
+        if ((meta[j] & out) == 0) {
+          if constexpr (G > 1) q = V4<AT>::load(cg + (long long)((meta[j] >> 27) & 15) * plane_ + off[j]);
+          else q = V4<AT>::load(cg + off[j]);
+        }
+#endif
+        r[g * NP + j] = q;
+      }
+    }
+  }
+  __device__ __forceinline__ void store(__bf16* Xs, int tid) const {
+#pragma unroll
+    for (int g = 0; g < NGRP; ++g)
+#pragma unroll
+      for (int j = 0; j < NP; ++j)
+        if ((j + 1) * NTHR <= GV || tid + NTHR * j < GV) *reinterpret_cast<bf16x4*>(Xs + g * lstep_ + (meta[j] & 0xfffff)) = to_bf16x4(r[g * NP + j]);
   }
 };
 
@@ -426,6 +496,213 @@ __global__ __launch_bounds__(StencilBrick<G>::NTHR, 2) void stencil3_wgrad_kerne
   }
 }
 
+// The weight gradient as a SWEEP over halo slices (the default; SV_STENCIL_WGRAD_SWEEP=0 keeps the kernel above for A/B runs).
+// The x fragment of a (y half, dy, dx) at halo slice s is the operand of tap dz = 0 of output slice s, dz = 1 of slice s - 1 and dz = 2 of
+// slice s - 2.  The kernel above splits the 27 taps over the waves, so three different waves fetch it, and every wave fetches every dy
+// fragment: 2.6 transposing LDS reads per MFMA, LDS-bound.  Here a wave owns one half of the brick's y range (the 4 y-rows of a K = 32
+// chunk) and 3 or 2 of the 9 (dy, dx) pairs of that half (18 units on 8 waves: slot 0 of a half takes pairs 0-2, slots 1-3 two each;
+// wave = 2 slot + half puts the two 3-pair waves on different SIMDs).  It walks the halo slices s = 0 .. TZV + 1, reads each of its x
+// fragments ONCE, keeps the dy fragments of output slices s, s - 1, s - 2 (and s + 1, in flight) in a register ring (one new dy fragment per output
+// slice) and issues the MFMAs of dz = 0, 1, 2 wherever 0 <= s - dz < TZV: 3 accumulator blocks per pair and channel group.
+// Per brick and G = 1: 360 x reads + 192 dy reads (128 + the second passes below) for 432 MFMAs (1.3 per MFMA; 1130 before).
+// LDS banks ((byte / 4) mod 64, the two 32-lane halves of a transposing read are one group each):
+//   x image: a 16-lane group (one y-row lg) reads 4 x-positions of 8 B x 4 lanes.  G = 1 (32 B positions): 128 contiguous bytes = 32 banks;
+//   the group's second y-row must start 128 B (mod 256) further on: pitch * 32 = 128 (mod 256) <=> pitch = 4 (mod 8).  G = 3 (96 B
+//   positions): the four positions take the 8-bank slots {0, 3, 6, 1} (+ channel group), the second y-row those + pitch * 3 (mod 8); the sets
+//   are disjoint for a shift of 4 only, pitch * 3 = 4 (mod 8) <=> pitch = 4 (mod 8) again.  Both take HXP = 12 positions (10 used; the natural
+//   pitch of 10 shifts by 64 B resp. 6 slots: half the banks of the two rows collide).  dx shifts both rows alike.
+//   dy image [voxel][16]: y-rows are 256 B, both rows of a group would sit on the same 32 banks; odd y-rows are stored with their x-halves
+//   swapped (position x ^ 4), the `lo` read of an odd row then takes banks 32-63 while the even row's takes 0-31.
+//   Measured: with ~1 read per MFMA the loop is no longer LDS-bound and neither choice moves the time; they cost no residency.
+// LDS: G = 1 38.4 + 16.4 KB (two workgroups per CU as before), G = 3 115.2 + 16.4 KB (one, as before).
+// The bias gradient is summed from the dy fragments by slot 1 of each half (a 2-pair wave), in a pass of its own.  The two halves' accumulators
+// are added through LDS (the x image is free by then) before the atomics: as many atomics per workgroup as the tap-split kernel issues.
+#ifdef SV_ST_PROBE_WG_PITCH                         // probe builds: another row pitch of the x image / the dy image without the swap
+constexpr int SWEEP_HXP = SV_ST_PROBE_WG_PITCH;
+#else
+constexpr int SWEEP_HXP = 12;
+#endif
+#ifdef SV_ST_PROBE_WG_LA                           // probe builds: x fragments read this many steps (3 MFMAs each) ahead of their use
+constexpr int SWEEP_LA = SV_ST_PROBE_WG_LA;
+#else
+constexpr int SWEEP_LA = 1;                         // 1, 2 and 3 measure the same: the loop is MFMA-paced, not waiting on LDS
+#endif
+#ifdef SV_ST_PROBE_WG_NOSWAP
+constexpr int SWEEP_DYSWAP = 0;
+#else
+constexpr int SWEEP_DYSWAP = 4;
+#endif
+template <int G, typename AT>
+__global__ __launch_bounds__(StencilBrick<G>::NTHR, G == 1 && sizeof(AT) == 2 ? 4 : 2) void stencil3_wgrad_sweep_kernel(const StencilWArgsT<AT> p) {
+  constexpr int C = 16 * G, TZV = StencilBrick<G>::TZV, NTHR = StencilBrick<G>::NTHR, HXP = SWEEP_HXP;
+  constexpr int XELEMS = (TZV + 2) * HY * HXP * C, NVOXV = TZV * TY * TX, LA = SWEEP_LA;
+  static_assert(NTHR == 512 && NTHR * 4 == NVOXV * 4, "8 waves: 2 y-halves x 4 pair slots; dy staging = 4 vectors per thread");
+  static_assert(4 * 9 * G * 64 * 4 * sizeof(float) <= XELEMS * sizeof(__bf16), "the half-1 accumulators are handed over through the x image");
+  __shared__ __attribute__((aligned(16))) __bf16 Xs[XELEMS];
+  __shared__ __attribute__((aligned(16))) __bf16 Ds[NVOXV * 16];
+  __shared__ float bred[2 * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lg = lane >> 4, q = lr >> 2, pp = lr & 3;
+  const int half = wave & 1, slot = wave >> 1;
+  const int p0 = slot ? 1 + 2 * slot : 0;             // this wave's pairs pr = p0 + pi = dy * 3 + dx, pi < (slot ? 2 : 3)
+  const bool three = slot == 0, sums_bias = p.dbias != nullptr && slot == 1;
+  f32x4 acc[3][3][G];                                 // [pair][dz][channel group]
+#pragma unroll
+  for (int pi = 0; pi < 3; ++pi)
+#pragma unroll
+    for (int dz = 0; dz < 3; ++dz)
+#pragma unroll
+      for (int gg = 0; gg < G; ++gg) acc[pi][dz][gg] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;                                   // bias gradient: column lr, the voxels (y = 4 half + lg, all x, all z)
+
+  HaloSliceRegs<G, AT, TZV, NTHR> hr;
+  hr.init(p.ldx, p.x_plane, p.cin_load, p.H, p.W, tid, HXP);
+  // dy brick: NVOXV voxels x 4 vectors = 4 per thread; vector k of a thread is voxel (tid >> 2) + 128 k, i.e. two z-slices further on
+  typename V4<AT>::type dr[4];
+  const int dv0 = tid >> 2, dc4 = (tid & 3) * 4;
+  const int dyoff = (((dv0 / (TY * TX)) * p.H + (dv0 / TX) % TY) * p.W + dv0 % TX) * p.lddy + dc4;    // from the brick's first voxel
+  const int dystep = 2 * p.H * p.W * p.lddy;
+  auto load_dy = [&](const TileId& t) {
+    const AT* d0 = p.dy + ((((size_t)t.img * p.D + t.z0) * p.H + t.y0) * p.W + t.x0) * (size_t)p.lddy + dyoff;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      typename V4<AT>::type qv = V4<AT>::zero();
+      if (dc4 < p.cout_load) qv = V4<AT>::load(d0 + (size_t)k * dystep);
+      dr[k] = qv;
+    }
+  };
+  auto store_dy = [&]() {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = tid + NTHR * k;
+      const int v = i >> 2, vs = v ^ (((v >> 3) & 1) * SWEEP_DYSWAP);                    // odd y-rows: x-halves swapped
+      *reinterpret_cast<bf16x4*>(Ds + vs * 16 + (i & 3) * 4) = to_bf16x4(dr[k]);
+    }
+  };
+  // lane addresses of slice 0: x fragment of pair pi = rows (y = 4 half + lg + dy), positions dx + q (lo) and dx + q + 4 (hi)
+  const int yb = 4 * half + lg;
+  const __bf16* xsrc[3];
+#pragma unroll
+  for (int pi = 0; pi < 3; ++pi) {
+    const int pr = (pi < 2 || three) ? p0 + pi : p0;   // a 2-pair wave never reads its third entry
+    const int dy = pr / 3, dx = pr - dy * 3;
+    xsrc[pi] = Xs + ((yb + dy) * HXP + dx + q) * C + pp * 4;
+  }
+  const __bf16* alo_src = Ds + (yb * TX + q + ((yb & 1) ? SWEEP_DYSWAP : 0)) * 16 + pp * 4;
+  const __bf16* ahi_src = Ds + (yb * TX + q + 4 - ((yb & 1) ? SWEEP_DYSWAP : 0)) * 16 + pp * 4;
+
+  auto read_dy = [&](int z) {
+    const bf16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(alo_src + z * TY * TX * 16));
+    const bf16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(ahi_src + z * TY * TX * 16));
+    return (bf16x8)__builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  auto read_x = [&](int s, int pi, int gg) {
+    const __bf16* bsrc = xsrc[pi] + s * HY * HXP * C + gg * 16;
+    const bf16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(bsrc));
+    const bf16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(bsrc + 4 * C));
+    return (bf16x8)__builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  // one pass over the halo slices for the pairs PI0 .. PI0 + NPI - 1: straight-line code (every index below is a constant after unrolling),
+  // the x fragment of the next step and the dy fragment of the next slice are read before the MFMAs of the current step.  All waves sweep
+  // pairs 0-1; the two 3-pair waves sweep pair 2 in a second pass and the two bias waves sum the dy fragments in a third (wave-uniform
+  // branches around whole passes: the transposing reads need EXEC all ones).  The extra passes re-read dy: 128 + 32 + 32 dy reads per brick.
+  auto sweep = [&](auto PI0, auto NPI) {
+    constexpr int pi0 = decltype(PI0)::value, npi = decltype(NPI)::value, NSTEP = (TZV + 2) * npi * G;   // step n = (s, pi, gg)
+    bf16x8 a[4];                                       // dy fragments of output slices s + 1 (in flight), s, s - 1, s - 2: slice z lives in a[z % 4]
+    bf16x8 b[LA + 1];                                  // x fragment of step n in b[n % (LA + 1)]; step n + LA's is read before step n's MFMAs
+    a[0] = read_dy(0);
+#pragma unroll
+    for (int n = 0; n < LA; ++n) b[n] = read_x(n / (npi * G), pi0 + (n / G) % npi, n % G);
+#pragma unroll
+    for (int n = 0; n < NSTEP; ++n) {
+      const int s = n / (npi * G), pi = pi0 + (n / G) % npi, gg = n % G;
+      if (n % (npi * G) == 0 && s + 1 < TZV) a[(s + 1) % 4] = read_dy(s + 1);
+      if (n + LA < NSTEP) b[(n + LA) % (LA + 1)] = read_x((n + LA) / (npi * G), pi0 + ((n + LA) / G) % npi, (n + LA) % G);
+      __builtin_amdgcn_sched_barrier(0);               // the reads above stay above: they are in flight under this step's MFMAs
+#pragma unroll
+      for (int dz = 0; dz < 3; ++dz)
+        if (s - dz >= 0 && s - dz < TZV) acc[pi][dz][gg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[(s - dz) % 4], b[n % (LA + 1)], acc[pi][dz][gg], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  int tile = xcd_first_tile();
+  if (tile < p.ntiles) {
+    const TileId t = tile_of<TZV>(tile, p.D, p.H, p.W);
+    hr.load(p.x, p.ldx, t, p.D, p.H, p.W); load_dy(t);
+    hr.store(Xs, tid); store_dy();
+  }
+  __syncthreads();
+  for (; tile < p.ntiles; tile += gridDim.x) {
+    const int next = tile + gridDim.x;
+    if (next < p.ntiles) {
+      const TileId t = tile_of<TZV>(next, p.D, p.H, p.W);
+      hr.load(p.x, p.ldx, t, p.D, p.H, p.W); load_dy(t);     // in flight during the MFMA loop
+    }
+#ifndef SV_ST_PROBE_NOMMA
+    sweep(std::integral_constant<int, 0>(), std::integral_constant<int, 2>());
+    if (three) sweep(std::integral_constant<int, 2>(), std::integral_constant<int, 1>());
+    if (sums_bias) {
+#pragma unroll
+      for (int z = 0; z < TZV; ++z) {
+        const bf16x8 a = read_dy(z);
+        float t8 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t8 += (float)a[j];
+        bsum += t8;
+      }
+    }
+#endif
+    __syncthreads();                                   // the brick is consumed
+    if (next < p.ntiles) { hr.store(Xs, tid); store_dy(); }
+    __syncthreads();
+  }
+  // half 1 hands its accumulators to the wave of half 0 with the same pairs (every wave is past its last x read: barrier above)
+  f32x4* hand = reinterpret_cast<f32x4*>(Xs) + (size_t)slot * 9 * G * 64 + lane;
+  if (half == 1) {
+#pragma unroll
+    for (int pi = 0; pi < 3; ++pi)
+#pragma unroll
+      for (int dz = 0; dz < 3; ++dz)
+#pragma unroll
+        for (int gg = 0; gg < G; ++gg) hand[((pi * 3 + dz) * G + gg) * 64] = acc[pi][dz][gg];
+  }
+  if (sums_bias) bred[half * 64 + lane] = bsum;         // [half][lg][column]
+  __syncthreads();
+  if (p.dbias && tid < 16 && tid < p.cout) {
+    float s8 = 0.f;
+#pragma unroll
+    for (int g2 = 0; g2 < 8; ++g2) s8 += bred[g2 * 16 + tid];
+    atomicAdd(p.dbias + tid, s8);
+  }
+  if (half == 1) return;
+  // C element: row = lg*4 + j -> co, col = lr -> memory channel 16*gg + lr
+  float* dst = p.ws ? p.ws + (size_t)(blockIdx.x % WG_SLOTS) * p.cout * p.cin * 27 : p.dw;
+#pragma unroll
+  for (int pi = 0; pi < 3; ++pi) {
+    if (pi < 2 || three) {
+#pragma unroll
+      for (int dz = 0; dz < 3; ++dz) {
+        const int tap = dz * 9 + p0 + pi;
+#pragma unroll
+        for (int gg = 0; gg < G; ++gg) {
+          const f32x4 o = hand[((pi * 3 + dz) * G + gg) * 64];
+          const int cm = gg * 16 + lr;
+          const int grp = cm / p.c_stride, within = cm - grp * p.c_stride;
+          const int ci = grp * p.c_valid + within;
+          if (within < p.c_valid && ci < p.cin) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int co = lg * 4 + j;
+              if (co < p.cout) atomicAdd(dst + ((size_t)co * p.cin + ci) * 27 + tap, acc[pi][dz][gg][j] + o[j]);
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // ConvTranspose3d(k = 4, stride 2, pad 1) with <= 8 output channels on an LDS halo brick (the decoder's last up-sampling layer,
 // models/decoder.py:37-40: 32 -> 8 channels, 16^3 -> 32^3).  The generic engine gathers 8 taps x 64 B from L2 for every 16-byte output row
@@ -628,14 +905,21 @@ extern "C" int sv_stencil3_wgrad(const void* x, int ldx, int cin_load, int group
   SV_REQUIRE(groups == 1 || groups == 3, "stencil3_wgrad: unsupported groups=%d", groups);
     const int ntiles = I * (D / (groups == 3 ? StencilBrick<3>::TZV : StencilBrick<1>::TZV)) * (H / TY) * (W / TX);
   hipStream_t s = (hipStream_t)stream;
+  // SV_STENCIL_WGRAD_SWEEP=0 in the environment selects the tap-split kernel (A/B runs); read at every call, so that one process can
+  // compare the two kernels
+  const char* sweep_env = getenv("SV_STENCIL_WGRAD_SWEEP");
+  const bool sweep = sweep_env ? atoi(sweep_env) != 0 : true;
   SV_DISPATCH_ACT(act_dtype,
-    const int per_cu = groups == 1 ? resident_per_cu((const void*)stencil3_wgrad_kernel<1, AT>, StencilBrick<1>::NTHR)
-                                   : resident_per_cu((const void*)stencil3_wgrad_kernel<3, AT>, StencilBrick<3>::NTHR);
+    const void* k1 = sweep ? (const void*)stencil3_wgrad_sweep_kernel<1, AT> : (const void*)stencil3_wgrad_kernel<1, AT>;
+    const void* k3 = sweep ? (const void*)stencil3_wgrad_sweep_kernel<3, AT> : (const void*)stencil3_wgrad_kernel<3, AT>;
+    const int per_cu = groups == 1 ? resident_per_cu(k1, StencilBrick<1>::NTHR) : resident_per_cu(k3, StencilBrick<3>::NTHR);
     const int resident = 256 * per_cu;
     const int blocks = ntiles < resident ? ntiles : resident;
     StencilWArgsT<AT> a{static_cast<const AT*>(x), ldx, cin_load, x_plane_stride, static_cast<const AT*>(dy), lddy, cout_load, dw, workspace, dbias, cout, cin, c_stride, c_valid,
                         I, D, H, W, ntiles};
-    if (groups == 1) hipLaunchKernelGGL((stencil3_wgrad_kernel<1, AT>), dim3(blocks), dim3(StencilBrick<1>::NTHR), 0, s, a);
+    if (groups == 1 && sweep) hipLaunchKernelGGL((stencil3_wgrad_sweep_kernel<1, AT>), dim3(blocks), dim3(StencilBrick<1>::NTHR), 0, s, a);
+    else if (groups == 1) hipLaunchKernelGGL((stencil3_wgrad_kernel<1, AT>), dim3(blocks), dim3(StencilBrick<1>::NTHR), 0, s, a);
+    else if (sweep) hipLaunchKernelGGL((stencil3_wgrad_sweep_kernel<3, AT>), dim3(blocks), dim3(StencilBrick<3>::NTHR), 0, s, a);
     else hipLaunchKernelGGL((stencil3_wgrad_kernel<3, AT>), dim3(blocks), dim3(StencilBrick<3>::NTHR), 0, s, a););
   if (workspace) hipLaunchKernelGGL(stencil_wgrad_fold_kernel, dim3(cdiv(cout * cin * 27, 256)), dim3(256), 0, s, workspace, dw, cout * cin * 27);
   return check_launch("sv_stencil3_wgrad");
