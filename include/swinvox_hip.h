@@ -345,7 +345,8 @@ int sv_bn_bwd(const void* dz, int lddz, const void* z, int ldz, const void* x, i
  * bottleneck, reference models/encoder.py:22-23): sv_scale_shift_act_signs also writes, per row and per 256 channels, four 64-bit words - bit l of
  * word j = (value of channel 256 b + 4 l + j before the activation) > 0 - i.e. [M][C/64] uint64, 1/16 of the bytes of a bf16 output;
  * sv_bn_bwd_signs takes its mask from them (and always returns the masked gradient dz * act' through dres, which its second pass reads back
- * instead of (dz, z)).  C % 256 == 0 (sv_bn_signs_supported), rows 4-aligned. */
+ * instead of (dz, z) wherever the stored value is the masked gradient exactly - ReLU, or fp32 storage; with LeakyReLU in bf16 storage the second
+ * pass masks dz from the words itself, so that dx does not inherit the rounding of slope * dz).  C % 256 == 0 (sv_bn_signs_supported), rows 4-aligned. */
 int sv_bn_signs_supported(int C);
 int sv_scale_shift_act_signs(const void* x, int ldx, const float* scale, const float* shift, const void* residual, int ldr, void* y, int ldy,
                              long long M, int C, int act, float slope, void* signs, int act_dtype, void* stream);

@@ -577,7 +577,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const AT* __restrict
   double s1 = 0.0, s2 = 0.0;
   if (c < C) {
     const float mu = mean[c], rs = rstd[c];
-    const float msc = z ? 0.f : fsc[c], msh = z ? 0.f : fsh[c];     // no saved output: the mask is recomputed from x
+    const bool remask = !z && act != SV_ACT_NONE;                   // no saved output: the mask is recomputed from x
+    const float msc = remask ? fsc[c] : 0.f, msh = remask ? fsh[c] : 0.f;   // (fsc / fsh may be NULL when there is no activation)
     const float neg = act == SV_ACT_LRELU ? slope : 0.f;
     long long r = r0 + rl;
     for (; r + 3 * RL < r1e; r += 4 * RL) {   // 4 rows in flight per thread (independent loads), then the serial tail
@@ -825,14 +826,16 @@ __global__ __launch_bounds__(256) void scale_shift_act_cg_kernel(const AT* __res
   }
 }
 
-template <typename AT>
+// SIGNS: the mask comes from the forward's sign words (G == 64, C % 256 == 0: lane gq owns bit gq of the row's four words)
+template <typename AT, bool SIGNS = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_cg_kernel(const AT* __restrict__ dz, int lddz, const AT* __restrict__ z, int ldz,
                                                               const AT* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
                                                               const double* __restrict__ sums, long long M, int C, int act, float slope,
                                                               int training, AT* __restrict__ dx, int lddx, AT* __restrict__ dres, int lddres,
                                                               const float* __restrict__ fsc, const float* __restrict__ fsh,
-                                                              long long rows_per_block, int G) {
+                                                              long long rows_per_block, int G,
+                                                              const unsigned long long* __restrict__ signs = nullptr) {
   const int gq = threadIdx.x % G, rl = threadIdx.x / G, RL = 256 / G;
   const int c = (blockIdx.x * G + gq) * 4;
   if (c >= C || rl >= RL) return;
@@ -847,7 +850,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cg_kernel(const AT* __restri
     k1[j] = gm * rs;
     if (training) { const double a = sums[c + j] * invM, b = sums[C + c + j] * invM; k3[j] = gm * rs * b * rs; k2[j] = gm * rs * a - k3[j] * mu; }
     else { k2[j] = 0.0; k3[j] = 0.0; }
-    if (!z && act != SV_ACT_NONE) { msc[j] = fsc[c + j]; msh[j] = fsh[c + j]; }
+    if (!SIGNS && !z && act != SV_ACT_NONE) { msc[j] = fsc[c + j]; msh[j] = fsh[c + j]; }
   }
   const float neg = act == SV_ACT_LRELU ? slope : 0.f;
   const long long r0 = (long long)blockIdx.y * rows_per_block;
@@ -857,7 +860,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cg_kernel(const AT* __restri
     const float4 dv = ld4f(dz + (size_t)r * lddz + c), xv = ld4f(x + (size_t)r * ldx + c);
     float d[4] = {dv.x, dv.y, dv.z, dv.w};
     const float xx[4] = {xv.x, xv.y, xv.z, xv.w};
-    if (act != SV_ACT_NONE) {
+    if constexpr (SIGNS) {
+      if (act != SV_ACT_NONE) {
+        const ulonglong2* w = reinterpret_cast<const ulonglong2*>(signs + ((size_t)r * (C >> 8) + blockIdx.x) * 4);
+        const ulonglong2 p0 = w[0], p1 = w[1];
+        const unsigned long long m[4] = {p0.x, p0.y, p1.x, p1.y};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d[j] *= ((m[j] >> gq) & 1ull) ? 1.f : neg;
+      }
+    } else if (act != SV_ACT_NONE) {
       float zz[4];
       if (z) { const float4 zv = ld4f(z + (size_t)r * ldz + c); zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w; }
       else {
@@ -1673,7 +1684,8 @@ static int bn_bwd_impl(const void* dz, int lddz, const void* z, int ldz, const u
   SV_REQUIRE_ACT(act_dtype);
   hipStream_t s = (hipStream_t)stream;   // sums_ws: sv_bn_bwd_workspace_doubles(C) doubles, ZERO on entry (e.g. a slice of one pre-zeroed arena)
   const bool vec = (C % 4 == 0) && (lddz % 4 == 0) && (ldx % 4 == 0) && (lddx % 4 == 0) && (!z || ldz % 4 == 0) && (!dres || lddres % 4 == 0) &&
-                   aligned4(act_dtype, dz, z, x, dx, dres) && (((uintptr_t)save_mean | (uintptr_t)save_rstd) & 15) == 0;
+                   aligned4(act_dtype, dz, z, x, dx, dres) &&
+                   (((uintptr_t)save_mean | (uintptr_t)save_rstd | (uintptr_t)fwd_scale | (uintptr_t)fwd_shift) & 15) == 0;   // all four are read as float4
   // sign words: the reduce pass takes the mask from them and hands the masked gradient on through dres (premask) - both vector-path features
   SV_REQUIRE(!signs || (vec && bn_signs_ok(C) && dres && act != SV_ACT_NONE && ((uintptr_t)signs & 15) == 0),
              "bn_bwd_signs: needs C %% 256 == 0, 4-aligned rows, an activation and the residual-branch output dres (C=%d)", C);
@@ -1700,16 +1712,23 @@ static int bn_bwd_impl(const void* dz, int lddz, const void* z, int ldz, const u
       const long long rpb = (M + splits - 1) / splits;
       // with a residual-branch gradient to produce (dres) the reduce pass stores the masked gradient there and the apply pass reads IT,
       // mask-free, instead of (dz, z): 7 instead of 8 passes over the tensor.  The sums are of the fp32 values, the stored ones are
-      // rounded to the storage type - as dres always was.
+      // rounded to the storage type - as dres always was.  The hand-off needs the stored value to BE the masked gradient: true for ReLU
+      // (dz or 0) and for fp32 storage, not for LeakyReLU in bf16, where slope * dz rounds and dx would inherit 2^-9 |gamma rstd dz'| -
+      // there the apply pass masks dz itself (from z / x, or from the sign words) and dres only carries the residual branch's gradient.
       static const int premask_on = [] { const char* v = getenv("SV_BN_PREMASK"); return v ? atoi(v) : 1; }();
-      const bool premask = (premask_on || signs) && dres_ && act != SV_ACT_NONE;
+      const bool exact = !(act == SV_ACT_LRELU && act_dtype == SV_BF16);
+      const bool premask = (premask_on || signs) && dres_ && act != SV_ACT_NONE && exact;
+      const bool sign_apply = signs && !premask;       // the reduce pass still delivers dres, the apply pass reads (dz, words)
       hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope,
-                         sums_ws, rpb, G, fsc, fsh, premask ? dres_ : (AT*)nullptr, lddres, signs);
+                         sums_ws, rpb, G, fsc, fsh, (premask || sign_apply) ? dres_ : (AT*)nullptr, lddres, signs);
       hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, sums_ws, C, dgamma, dbeta);
       long long asplits = 4096 / cg; if (asplits < 1) asplits = 1;
       const long long amax = (M + 4 * RL - 1) / (4 * RL); if (asplits > amax) asplits = amax;
       const long long arpb = (M + asplits - 1) / asplits;
-      if (premask)
+      if (sign_apply)
+        hipLaunchKernelGGL((bn_bwd_apply_cg_kernel<AT, true>), dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, dz_, lddz, (const AT*)nullptr, 0, x_, ldx, gamma, save_mean,
+                           save_rstd, sums_ws, M, C, act, slope, training, dx_, lddx, (AT*)nullptr, 0, fsc, fsh, arpb, G, signs);
+      else if (premask)
         hipLaunchKernelGGL(bn_bwd_apply_cg_kernel<AT>, dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, (const AT*)dres_, lddres, (const AT*)nullptr, 0, x_, ldx, gamma, save_mean,
                            save_rstd, sums_ws, M, C, (int)SV_ACT_NONE, 0.f, training, dx_, lddx, (AT*)nullptr, 0, fsc, fsh, arpb, G);
       else
