@@ -443,6 +443,28 @@ int sv_swin_mlp_wgrad(const void* x1, const void* dx2, const float* ln_g, const 
                       const float* b1, const float* row_scale, int rows_per_scale, float* dw1, float* db1, float* dw2, float* db2,
                       long long M, int C, float eps, void* stream);
 
+/* MXFP8 forward of the fused Swin MLP branch (timm Mlp + norm2 + DropPath of a SwinTransformerBlock behind models/swin_transformer.py:78): the
+ * unfused MX chain sv_layernorm_quant_mx_fwd -> sv_linear_mxfp8 (GELU, q_out) -> sv_linear_mxfp8 (residual) composed in ONE kernel, both products
+ * on the block-scaled K = 128 MFMA with E8M0 scales per 32 channels / 32 hidden units; neither the hidden activation nor a quantised activation
+ * reaches HBM.  bf16 token rows, C in {96, 128}.  The backward is sv_swin_mlp_bwd / sv_swin_mlp_wgrad, unchanged (straight-through quantisers).
+ *  sv_swin_mlp_mx_supported:  1 for C = 96 and C = 128, else 0 (timm Mlp behind models/swin_transformer.py:78).
+ *  sv_swin_mlp_mx_pack_bytes: size of `packs` for C (0 when unsupported) (timm Mlp weights behind models/swin_transformer.py:78).
+ *  sv_swin_mlp_mx_pack:       w1q [4C, 128] / w1s [4C, 4] and w2q [C, 4C] / w2s [C, 4C / 32], the MX rows sv_quant_rows_mx_e4m3 makes of fc1.weight and
+ *                             fc2.weight (timm Mlp behind models/swin_transformer.py:78), -> `packs` in the kernel's fragment order; w1q, w2q and packs
+ *                             16-byte aligned.  The bytes are re-ordered, never re-quantised.
+ *  sv_swin_mlp_fwd_mx:        x2 from x1; arguments and alignment rules of sv_swin_mlp_fwd, with packs_mx from sv_swin_mlp_mx_pack (timm Mlp +
+ *                             norm2 + DropPath behind models/swin_transformer.py:78).
+ *  sv_swin_mlp_mx_launches:   sv_swin_mlp_fwd_mx launches so far in this process (timm Mlp behind models/swin_transformer.py:78; tests: the path they mean
+ *                             to exercise).
+ * Refusals (SV_ERR_INVALID before any GPU call, the entry's name in sv_last_error()): null pointers, unsupported C, M <= 0 or >= 2^31, misaligned
+ * operands, rows_per_scale <= 0.                                                                                                              */
+int sv_swin_mlp_mx_supported(int C); /* timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+long long sv_swin_mlp_mx_pack_bytes(int C); /* timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+int sv_swin_mlp_mx_pack(const void* w1q, const void* w1s, const void* w2q, const void* w2s, void* packs, int C, void* stream); /* timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+int sv_swin_mlp_fwd_mx(const void* x1, void* x2, const float* ln_g, const float* ln_b, const void* packs_mx, const float* b1, const float* b2,
+                       const float* row_scale, int rows_per_scale, long long M, int C, float eps, void* stream); /* timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+long long sv_swin_mlp_mx_launches(void); /* timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+
 /* Fused attention branch of a stage-0 Swin block (timm SwinTransformerBlock._attn + the residual of forward(), reached from
  * models/swin_transformer.py:78): x1 = x + row_scale * proj(window_attention(qkv(LayerNorm(x)))) in one kernel, the roll / 7x7 partition /
  * reverse and the shift mask folded into token index math as in sv_window_attention_fwd.  Built for C = 96, 3 heads, bf16 token rows

@@ -16,8 +16,11 @@
 //                         x / dy tiles go to LDS once per 128 tokens and serve every wave; H and dH are recomputed for the wave's chunk
 //                         (MFMA 16x16x32, tokens on the accumulator rows) and contracted over the tokens with the transposed tiles read by
 //                         ds_read_b64_tr_b16: dW2 += dy^T . H, dW1^T += LN(x)^T . dH.  Accumulators stay in registers for the whole range.
+//   swin_mlp_fwd_mx_kernel  opt-in sibling of the forward (sv_swin_mlp_fwd_mx, C = 96, 128): both products on MXFP8 operands quantised in registers,
+//                         described in front of the kernel below.  The three kernels above are not touched by it.
 // bf16 storage + bf16 MFMA only (the exact-fp32 parity mode keeps the unfused chain); C = 96, 128, 192 (Swin-T stages 0-1, Swin-B stage 0).
 #include "common.h"
+#include <atomic>
 
 namespace sv {
 
@@ -685,6 +688,227 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void swin_mlp_wgrad_kernel(c
 
 static inline bool mlp_supported(int C) { return C == 96 || C == 128 || C == 192; }
 
+// ---- MXFP8 forward (opt-in sibling of swin_mlp_fwd_kernel; sv_swin_mlp_fwd_mx) ---------------------------------------------------------
+// The unfused MX chain composed in one kernel: quantising LayerNorm -> fc1 on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 x e4m3,
+// E8M0 block scales) -> + b1, fast GELU, bf16 rounding, MX quantisation of h in blocks of 32 consecutive hidden units -> fc2 on the same MFMA ->
+// the epilogue of swin_mlp_fwd_kernel.  Neither h nor any quantised activation reaches HBM.  NORMATIVE recipe: linear_fp8.hip "MX recipe"
+// (mx_block_exp / pack4_e4m3_mx of common.h are the only copy of the rounding); the weight bytes are sv_quant_rows_mx_e4m3's.
+//   tokens on the columns (B operand): lane l = (t = l & 15, lg = l >> 4) holds token t.  Its data registers 0-3 are k = 16 lg .. + 15 and 4-7 are
+//   k = 64 + 16 lg .. + 15 of a 128-wide k-step, its scale byte covers k = 32 lg .. + 31 (linear_fp8.hip, lf_contract).
+//   LayerNorm     lane (t, lg) loads exactly those 16 + 16 channels of its token; the row sums cross the four lane groups (two permlane exchanges).
+//                 A 32-channel block is the 16 + 16 values of lanes lg and lg ^ 1 (same register half): one permlane16 exchange per maximum.
+//                 C = 96: Kp = 128, the upper half of lane groups 2 and 3 is padding - zero bytes, block 3 carries byte 127.
+//   fc1           A = 16 rows of W1 per MFMA, one k-step (Kp = 128).  The accumulator leaves as column t, rows 4 lg .. + 3.  Eight row tiles make the 128
+//                 hidden units of ONE fc2 k-step; the pack orders W1's rows so that tile j, row r is hidden unit 64 (j >> 2) + 16 (r >> 2) + 4 (j & 3)
+//                 + (r & 3) of the group: a lane's 4 x 4 values of tiles 0-3 are its data registers 0-3 of the fc2 operand (k = 16 lg .. + 15), those of
+//                 tiles 4-7 its registers 4-7 - no lane movement, and a hardware block is 32 consecutive hidden units, again split over lanes
+//                 lg and lg ^ 1.  The scale byte a lane must PASS (block lg) is known to lane group 2 (lg & 1): one ds_bpermute of the two packed bytes.
+//   fc2           A = 16 rows of W2 (output channels 16 jc + r), k-step g = hidden units 128 g .. + 127; accumulates over the 4C / 128 groups.
+//   weights       resident in LDS for the life of the workgroup, in fragment order (every A fragment is two conflict-free ds_read_b128, its scale one
+//                 byte per lane); one persistent workgroup per CU walks 128-token tiles.  NW waves own NTT x 16 tokens each: the library runs
+//                 8 x 1 - two waves per SIMD, so the GELU / quantiser VALU stream of one runs beside the MFMAs and LDS reads of the other.  With
+//                 NTT = 2 an A fragment read serves two MFMAs, but 4 x 2 leaves one wave per SIMD and 8 x 2 is slower than 8 x 1.
+// Pack image (sv_swin_mlp_mx_pack, bytes):  W1F [G][8 tiles][2 halves][64 lanes][16] | W2F [G][C/16][2][64][16] | W1S [G][8][64] | W2S [G][C/16][64],  G = 4C / 128.
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+template <int C> struct MlpMx {
+  static constexpr int HID = 4 * C, G = HID / 128, NJ = C / 16;
+  static constexpr int W1F = 0, W1F_BYTES = HID * 128;
+  static constexpr int W2F = W1F_BYTES, W2F_BYTES = C * HID;
+  static constexpr int W1S = W2F + W2F_BYTES, W1S_BYTES = G * 8 * 64;
+  static constexpr int W2S = W1S + W1S_BYTES, W2S_BYTES = G * NJ * 64;
+  static constexpr int PACK_BYTES = W2S + W2S_BYTES;
+};
+
+struct MlpMxArgs {
+  const __bf16* x1; __bf16* out;
+  const float* ln_g; const float* ln_b; float eps;
+  const uint8_t* packs;
+  const float* b1; const float* b2;
+  const float* row_scale; int rows_per_scale;
+  long long M; int ntiles;
+};
+
+__global__ __launch_bounds__(256) void swin_mlp_mx_pack_kernel(const uint8_t* __restrict__ w1q, const uint8_t* __restrict__ w1s, const uint8_t* __restrict__ w2q,
+                                                               const uint8_t* __restrict__ w2s, uint8_t* __restrict__ packs, int C) {
+  const int HID = 4 * C, G = HID / 128, NJ = C / 16;
+  const int n1 = HID * 128 / 16, n2 = C * HID / 16, n3 = G * 8 * 64, n4 = G * NJ * 64;     // 16-byte pieces, then scale bytes
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < n1) {
+    const int lane = idx & 63, hf = (idx >> 6) & 1, j = (idx >> 7) & 7, g = idx >> 10, r = lane & 15, lg = lane >> 4;
+    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
+    reinterpret_cast<i32x4*>(packs)[idx] = *reinterpret_cast<const i32x4*>(w1q + (size_t)hid * 128 + 64 * hf + 16 * lg);
+  } else if (idx < n1 + n2) {
+    const int e = idx - n1, lane = e & 63, hf = (e >> 6) & 1, t = e >> 7, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
+    reinterpret_cast<i32x4*>(packs)[idx] = *reinterpret_cast<const i32x4*>(w2q + (size_t)(16 * jc + r) * HID + 128 * g + 64 * hf + 16 * lg);
+  } else if (idx < n1 + n2 + n3) {
+    const int e = idx - n1 - n2, lane = e & 63, j = (e >> 6) & 7, g = e >> 9, r = lane & 15, lg = lane >> 4;
+    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
+    packs[(size_t)(n1 + n2) * 16 + e] = w1s[hid * 4 + lg];
+  } else if (idx < n1 + n2 + n3 + n4) {
+    const int e = idx - n1 - n2 - n3, lane = e & 63, t = e >> 6, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
+    packs[(size_t)(n1 + n2) * 16 + n3 + e] = w2s[(16 * jc + r) * (HID / 32) + 4 * g + lg];
+  }
+}
+
+// maximum of a lane's value and that of lane ^ 16 (the other half of a 32-element MX block)
+__device__ __forceinline__ float pair16_max(float v) { float w = v; permlane16_pair(v, w); return fmaxf(v, w); }
+// the E8M0 byte lane group lg passes to the MFMA (block lg of the k-step) from the bytes the lanes know: lane group lg' knows blocks lg' >> 1 (its
+// registers 0-3, `elo`) and 2 + (lg' >> 1) (registers 4-7, `ehi`)
+__device__ __forceinline__ int mx_lane_scale(int elo, int ehi, int lane) {
+  const int lg = lane >> 4;
+  const int got = __shfl((elo + 127) | ((ehi + 127) << 8), (lane & 15) + 32 * (lg & 1));
+  return (got >> (8 * (lg >> 1))) & 0xff;
+}
+
+template <int C, int NW, int NTT>
+__global__ __launch_bounds__(NW * 64, 1) void swin_mlp_fwd_mx_kernel(const MlpMxArgs p) {
+  typedef MlpMx<C> L;
+  constexpr int HID = L::HID, G = L::G, NJ = L::NJ, NT = NW * 64, TILE = NW * NTT * 16;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[L::PACK_BYTES + (HID + 2 * C) * 4];
+  float* sb1 = reinterpret_cast<float*>(smem + L::PACK_BYTES);
+  float* sgam = sb1 + HID;
+  float* sbet = sgam + C;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = lane & 15, lg = lane >> 4;
+  for (int i = tid; i < L::PACK_BYTES / 16; i += NT) reinterpret_cast<i32x4*>(smem)[i] = reinterpret_cast<const i32x4*>(p.packs)[i];
+  for (int i = tid; i < HID; i += NT) sb1[i] = p.b1[i];
+  for (int i = tid; i < C; i += NT) { sgam[i] = p.ln_g[i]; sbet[i] = p.ln_b[i]; }
+  __syncthreads();
+  const bool hi_live = 64 + 16 * lg < C;                   // C = 96: channels 96 .. 127 are padding
+
+#pragma unroll 1
+  for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
+    long long tok[NTT]; bool valid[NTT];
+    i32x8 xq[NTT]; int xsb[NTT];
+    // ---- LayerNorm (fp32, rounded to bf16 as the unfused chain stores it) -> MX B fragments of fc1
+#pragma unroll
+    for (int tt = 0; tt < NTT; ++tt) {
+      tok[tt] = (long long)tile * TILE + wave * (NTT * 16) + tt * 16 + t;
+      valid[tt] = tok[tt] < p.M;
+      float xv[2][16];
+      float s = 0.f;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          bf16x8 raw = VecN<__bf16, 8>::zero();
+          if (valid[tt] && (hf == 0 || hi_live)) raw = *reinterpret_cast<const bf16x8*>(p.x1 + tok[tt] * C + 64 * hf + 16 * lg + 8 * u);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { xv[hf][8 * u + j] = (float)raw[j]; s += xv[hf][8 * u + j]; }
+        }
+      s = lane_step_add<16>(s); s = lane_step_add<32>(s);
+      const float mean = s * (1.f / C);
+      float q = 0.f;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        if (hf == 0 || hi_live)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) { const float d = xv[hf][j] - mean; q += d * d; }
+      q = lane_step_add<16>(q); q = lane_step_add<32>(q);
+      const float rstd = rsqrtf(q * (1.f / C) + p.eps);
+      int e[2];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const bool live = hf == 0 || hi_live;
+        const int c0 = live ? 64 * hf + 16 * lg : 0;
+        float m = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const float v = live ? (float)(__bf16)((xv[hf][j] - mean) * rstd * sgam[c0 + j] + sbet[c0 + j]) : 0.f;
+          xv[hf][j] = v; m = fmaxf(m, fabsf(v));
+        }
+        e[hf] = mx_block_exp(pair16_max(m));
+#pragma unroll
+        for (int w = 0; w < 4; ++w) xq[tt][4 * hf + w] = (int)pack4_e4m3_mx(xv[hf][4 * w], xv[hf][4 * w + 1], xv[hf][4 * w + 2], xv[hf][4 * w + 3], e[hf]);
+      }
+      xsb[tt] = mx_lane_scale(e[0], e[1], lane);
+    }
+
+    f32x4 acc2[NJ][NTT];
+#pragma unroll
+    for (int jc = 0; jc < NJ; ++jc)
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt) acc2[jc][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      // ---- fc1: the 128 hidden units of group g, as 8 row tiles in the order the fc2 operand wants
+      f32x4 acc1[8][NTT];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint8_t* fa = smem + L::W1F + (size_t)((g * 8 + j) * 2) * 1024 + lane * 16;
+        const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
+        const i32x8 a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const int sa = smem[L::W1S + (g * 8 + j) * 64 + lane];
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt)
+          acc1[j][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, xq[tt], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, sa, 0, xsb[tt]);
+      }
+      // ---- + b1, GELU, bf16, MX quantisation in registers: the accumulators become the B fragment of fc2's k-step g
+      i32x8 hq[NTT]; int hsb[NTT];
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt) {
+        int e[2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          float m = 0.f;
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int j = 4 * hf + jj;
+            const float4 bi = *reinterpret_cast<const float4*>(sb1 + 128 * g + 64 * hf + 16 * lg + 4 * jj);
+            const f32x2 g0 = gelu_fast2((f32x2){acc1[j][tt][0] + bi.x, acc1[j][tt][1] + bi.y});
+            const f32x2 g1 = gelu_fast2((f32x2){acc1[j][tt][2] + bi.z, acc1[j][tt][3] + bi.w});
+            acc1[j][tt][0] = (float)(__bf16)g0[0]; acc1[j][tt][1] = (float)(__bf16)g0[1];
+            acc1[j][tt][2] = (float)(__bf16)g1[0]; acc1[j][tt][3] = (float)(__bf16)g1[1];
+            m = fmaxf(fmaxf(m, fmaxf(fabsf(acc1[j][tt][0]), fabsf(acc1[j][tt][1]))), fmaxf(fabsf(acc1[j][tt][2]), fabsf(acc1[j][tt][3])));
+          }
+          e[hf] = mx_block_exp(pair16_max(m));
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int j = 4 * hf + jj;
+            hq[tt][j] = (int)pack4_e4m3_mx(acc1[j][tt][0], acc1[j][tt][1], acc1[j][tt][2], acc1[j][tt][3], e[hf]);
+          }
+        }
+        hsb[tt] = mx_lane_scale(e[0], e[1], lane);
+      }
+      // ---- fc2: k-step g
+#pragma unroll
+      for (int jc = 0; jc < NJ; ++jc) {
+        const uint8_t* fa = smem + L::W2F + (size_t)((g * NJ + jc) * 2) * 1024 + lane * 16;
+        const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
+        const i32x8 a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const int sa = smem[L::W2S + (g * NJ + jc) * 64 + lane];
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt)
+          acc2[jc][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, hq[tt], acc2[jc][tt], 0, 0, 0, sa, 0, hsb[tt]);
+      }
+    }
+    // ---- epilogue of swin_mlp_fwd_kernel: + bias, drop-path scale, + residual; lane (t, lg) owns channels 16 jc + 4 lg .. + 3 of token t
+#pragma unroll
+    for (int tt = 0; tt < NTT; ++tt) {
+      if (!valid[tt]) continue;
+      const float sc = p.row_scale ? p.row_scale[tok[tt] / p.rows_per_scale] : 1.f;
+#pragma unroll
+      for (int jc = 0; jc < NJ; ++jc) {
+        const int c0 = 16 * jc + 4 * lg;
+        const float4 bi = *reinterpret_cast<const float4*>(p.b2 + c0);
+        const bf16x4 res = *reinterpret_cast<const bf16x4*>(p.x1 + tok[tt] * C + c0);
+        bf16x4 o;
+        o[0] = (__bf16)((float)res[0] + sc * (acc2[jc][tt][0] + bi.x));
+        o[1] = (__bf16)((float)res[1] + sc * (acc2[jc][tt][1] + bi.y));
+        o[2] = (__bf16)((float)res[2] + sc * (acc2[jc][tt][2] + bi.z));
+        o[3] = (__bf16)((float)res[3] + sc * (acc2[jc][tt][3] + bi.w));
+        *reinterpret_cast<bf16x4*>(p.out + tok[tt] * C + c0) = o;
+      }
+    }
+  }
+}
+
+static inline bool mlp_mx_supported(int C) { return C == 96 || C == 128; }
+static inline long long mlp_mx_pack_bytes(int C) { return C == 96 ? MlpMx<96>::PACK_BYTES : C == 128 ? MlpMx<128>::PACK_BYTES : 0; }
+
 }  // namespace sv
 
 using namespace sv;
@@ -768,4 +992,48 @@ extern "C" int sv_swin_mlp_wgrad(const void* x1, const void* dx2, const float* l
   else SV_MLP_WG(192, 8, 16, 64);
 #undef SV_MLP_WG
   return check_launch("sv_swin_mlp_wgrad");
+}
+
+// ---- MXFP8 forward ------------------------------------------------------------------------------------------------------------------
+static std::atomic<long long> swin_mlp_mx_launches{0};
+extern "C" long long sv_swin_mlp_mx_launches(void) { return swin_mlp_mx_launches.load(std::memory_order_relaxed); }
+extern "C" int sv_swin_mlp_mx_supported(int C) { return mlp_mx_supported(C) ? 1 : 0; }
+extern "C" long long sv_swin_mlp_mx_pack_bytes(int C) { return mlp_mx_pack_bytes(C); }
+
+extern "C" int sv_swin_mlp_mx_pack(const void* w1q, const void* w1s, const void* w2q, const void* w2s, void* packs, int C, void* stream) {
+  SV_REQUIRE(w1q && w1s && w2q && w2s && packs, "sv_swin_mlp_mx_pack: null pointer");
+  SV_REQUIRE(mlp_mx_supported(C), "sv_swin_mlp_mx_pack: unsupported C=%d (96 or 128)", C);
+  SV_REQUIRE((((uintptr_t)w1q | (uintptr_t)w2q | (uintptr_t)packs) & 15) == 0, "sv_swin_mlp_mx_pack: w1q, w2q and packs must be 16-byte aligned");
+  const long long HID = 4ll * C, G = HID / 128, NJ = C / 16;
+  const long long items = HID * 128 / 16 + C * HID / 16 + G * 8 * 64 + G * NJ * 64;
+  hipLaunchKernelGGL(swin_mlp_mx_pack_kernel, dim3(cdiv(items, 256)), dim3(256), 0, STREAM, static_cast<const uint8_t*>(w1q), static_cast<const uint8_t*>(w1s),
+                     static_cast<const uint8_t*>(w2q), static_cast<const uint8_t*>(w2s), static_cast<uint8_t*>(packs), C);
+  return check_launch("sv_swin_mlp_mx_pack");
+}
+
+extern "C" int sv_swin_mlp_fwd_mx(const void* x1, void* x2, const float* ln_g, const float* ln_b, const void* packs_mx, const float* b1,
+                                  const float* b2, const float* row_scale, int rows_per_scale, long long M, int C, float eps, void* stream) {
+  SV_REQUIRE(x1 && x2 && ln_g && ln_b && packs_mx && b1 && b2, "sv_swin_mlp_fwd_mx: null pointer");
+  SV_REQUIRE(mlp_mx_supported(C), "sv_swin_mlp_fwd_mx: unsupported C=%d (96 or 128)", C);
+  SV_REQUIRE(M > 0 && M < (1ll << 31), "sv_swin_mlp_fwd_mx: M=%lld out of range", M);
+  SV_REQUIRE((((uintptr_t)x1 | (uintptr_t)x2 | (uintptr_t)packs_mx | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)b2) & 15) == 0,
+             "sv_swin_mlp_fwd_mx: operands must be 16-byte aligned");
+  SV_REQUIRE(rows_per_scale > 0, "sv_swin_mlp_fwd_mx: rows_per_scale must be positive");
+  MlpMxArgs a{};
+  a.x1 = static_cast<const __bf16*>(x1); a.out = static_cast<__bf16*>(x2); a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps;
+  a.packs = static_cast<const uint8_t*>(packs_mx); a.b1 = b1; a.b2 = b2; a.row_scale = row_scale; a.rows_per_scale = rows_per_scale; a.M = M;
+  // 8 waves x 16 tokens: two waves per SIMD, so one wave's GELU / quantiser VALU stream runs beside the other's MFMAs and LDS reads
+  // (measured against 4 waves x 32 tokens and 8 x 32)
+#define SV_MLP_MX(CC, NW, NTT)                                                                                     \
+  do {                                                                                                             \
+    a.ntiles = cdiv(M, NW * NTT * 16);                                                                             \
+    const int grid = a.ntiles < 256 ? a.ntiles : 256;   /* one persistent workgroup per CU: the weights enter LDS once */ \
+    hipLaunchKernelGGL((swin_mlp_fwd_mx_kernel<CC, NW, NTT>), dim3(grid), dim3(NW * 64), 0, STREAM, a);            \
+  } while (0)
+  if (C == 96) SV_MLP_MX(96, 8, 1);
+  else SV_MLP_MX(128, 8, 1);
+#undef SV_MLP_MX
+  const int rc = check_launch("sv_swin_mlp_fwd_mx");
+  if (rc == SV_OK) swin_mlp_mx_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
 }

@@ -215,10 +215,19 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
             att = qa                                       # the tensor, where one was written, is dropped here
     if ops.fused_mlp_enabled(Cd):
         # norm2 -> fc1 -> GELU -> fc2 -> drop-path -> +x1 in ONE kernel; the 4C-wide hidden activation never reaches HBM
-        packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
-        call("sv_swin_mlp_pack", ptr(blk.mlp.fc1.weight), ptr(blk.mlp.fc2.weight), ptr(packs), Cd)
+        mx = ops.fused_mlp_mx_enabled(Cd)
+        packs = None
+        if save or not mx:                                 # the bf16 images: read by sv_swin_mlp_fwd and by the (unchanged) fused backward
+            packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
+            call("sv_swin_mlp_pack", ptr(blk.mlp.fc1.weight), ptr(blk.mlp.fc2.weight), ptr(packs), Cd)
         x2 = empty(M, Cd, like=x)
         unit = 2.0 * M * Cd * 4 * Cd
+        if mx:
+            # opt-in MXFP8 forward (set_fused_mlp_mx): both products on MX operands, quantised in registers; the backward recomputes in bf16
+            packs_mx = ops.swin_mlp_mx_packs(blk.mlp.fc1.weight, blk.mlp.fc2.weight, Cd)
+            ops.traced_call("sv_swin_mlp_fwd_mx", 2 * unit, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs_mx),
+                            ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
+            return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, packs, None, I)
         ops.traced_call("sv_swin_mlp_fwd", 2 * unit, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs),
                         ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
         return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, packs, None, I)
