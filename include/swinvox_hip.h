@@ -465,6 +465,30 @@ int sv_swin_mlp_fwd_mx(const void* x1, void* x2, const float* ln_g, const float*
                        const float* row_scale, int rows_per_scale, long long M, int C, float eps, void* stream); /* timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
 long long sv_swin_mlp_mx_launches(void); /* timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
 
+/* MXFP8 data gradient of the fused Swin MLP branch (backward of timm Mlp + norm2 + DropPath of a SwinTransformerBlock behind
+ * models/swin_transformer.py:78): the unfused MX backward chain sv_rowscale -> sv_quant_rows_mx_e4m3 (dy) -> sv_linear_mxfp8_dgrad (fc2, GELU' at the
+ * pre-activation) -> sv_quant_rows_mx_e4m3 (dh) -> sv_linear_mxfp8_dgrad (fc1) -> sv_layernorm_bwd (+ residual) composed in ONE kernel.  The
+ * pre-activation is recomputed as sv_swin_mlp_fwd_mx computes it; dy's MX rows, the pre-activation and dh never reach HBM.  bf16 token rows.  The
+ * weight gradients stay on sv_swin_mlp_wgrad.
+ *  sv_swin_mlp_bwd_mx_supported:  1 where the library has a spill-free instantiation (C = 96 and C = 128), else 0.
+ *  sv_swin_mlp_bwd_mx_pack_bytes: size of `packs` for C (0 when unsupported).
+ *  sv_swin_mlp_bwd_mx_pack:       w1q [4C, 128] / w1s [4C, 4] (sv_quant_rows_mx_e4m3 of fc1.weight), w2tq [4C, 128] / w2ts [4C, 4] and w1tq [C, 4C] /
+ *                                 w1ts [C, 4C / 32] (sv_quant_cols_mx_e4m3 of fc2.weight and of fc1.weight: the MX rows of W^T) -> `packs` in the kernel's
+ *                                 fragment order; w1q, w2tq, w1tq and packs 16-byte aligned.  The bytes are re-ordered, never re-quantised.
+ *  sv_swin_mlp_bwd_mx:            dx1 = dx2 + d(branch)/dx1, dgamma / dbeta += LayerNorm gradients; arguments and alignment rules of sv_swin_mlp_bwd,
+ *                                 with packs_mx from sv_swin_mlp_bwd_mx_pack.
+ *  sv_swin_mlp_bwd_mx_launches:   sv_swin_mlp_bwd_mx launches so far in this process (tests: the path they mean to exercise).
+ * Refusals (SV_ERR_INVALID before any GPU call, the entry's name in sv_last_error()): null pointers (row_scale may be NULL), unsupported C, M <= 0 or
+ * >= 2^31, x1 / dx2 / dx1 / packs_mx / ln_g / ln_b not 16-byte aligned, rows_per_scale <= 0.                                                    */
+int sv_swin_mlp_bwd_mx_supported(int C); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+long long sv_swin_mlp_bwd_mx_pack_bytes(int C); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+int sv_swin_mlp_bwd_mx_pack(const void* w1q, const void* w1s, const void* w2tq, const void* w2ts, const void* w1tq, const void* w1ts, void* packs, int C,
+                            void* stream); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+int sv_swin_mlp_bwd_mx(const void* x1, const void* dx2, void* dx1, const float* ln_g, const float* ln_b, const void* packs_mx, const float* b1,
+                       const float* row_scale, int rows_per_scale, float* dgamma, float* dbeta, long long M, int C, float eps,
+                       void* stream); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+long long sv_swin_mlp_bwd_mx_launches(void); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+
 /* Fused attention branch of a stage-0 Swin block (timm SwinTransformerBlock._attn + the residual of forward(), reached from
  * models/swin_transformer.py:78): x1 = x + row_scale * proj(window_attention(qkv(LayerNorm(x)))) in one kernel, the roll / 7x7 partition /
  * reverse and the shift mask folded into token index math as in sv_window_attention_fwd.  Built for C = 96, 3 heads, bf16 token rows

@@ -18,6 +18,8 @@
 //                         ds_read_b64_tr_b16: dW2 += dy^T . H, dW1^T += LN(x)^T . dH.  Accumulators stay in registers for the whole range.
 //   swin_mlp_fwd_mx_kernel  opt-in sibling of the forward (sv_swin_mlp_fwd_mx, C = 96, 128): both products on MXFP8 operands quantised in registers,
 //                         described in front of the kernel below.  The three kernels above are not touched by it.
+//   swin_mlp_bwd_mx_kernel  opt-in sibling of the data gradient (sv_swin_mlp_bwd_mx, C = 96, 128): differentiates that MX forward with all three of its
+//                         products on MXFP8 operands, described in front of the kernel below.  The weight gradients stay on swin_mlp_wgrad_kernel.
 // bf16 storage + bf16 MFMA only (the exact-fp32 parity mode keeps the unfused chain); C = 96, 128, 192 (Swin-T stages 0-1, Swin-B stage 0).
 #include "common.h"
 #include <atomic>
@@ -909,6 +911,309 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_fwd_mx_kernel(const MlpMx
 static inline bool mlp_mx_supported(int C) { return C == 96 || C == 128; }
 static inline long long mlp_mx_pack_bytes(int C) { return C == 96 ? MlpMx<96>::PACK_BYTES : C == 128 ? MlpMx<128>::PACK_BYTES : 0; }
 
+// ---- MXFP8 data gradient (opt-in sibling of swin_mlp_bwd_kernel; sv_swin_mlp_bwd_mx) ---------------------------------------------------
+// The unfused MX backward chain of the branch composed in one kernel: sv_rowscale -> row quantiser of dy -> sv_linear_mxfp8_dgrad (fc2, GELU' at the
+// stored pre-activation) -> row quantiser of dh -> sv_linear_mxfp8_dgrad (fc1) -> sv_layernorm_bwd (+ residual).  The pre-activation is RECOMPUTED as
+// swin_mlp_fwd_mx_kernel computes it (quantising LayerNorm, fc1 on the forward's W1 MX rows, bf16(acc + b1)), so GELU' is evaluated where the MX
+// forward evaluated GELU.  Neither dy's MX rows, hpre nor dh reach HBM.  Same NORMATIVE recipe (linear_fp8.hip "MX recipe"), same lane maps as the forward:
+//   recompute     acc1[j] = W1 row tile j of group g . LN(x)_q: lane (t, lg) holds hidden units 128 g + 64 hf + 16 lg + 4 jj + i (j = 4 hf + jj).
+//   fc2 dgrad     accd[j] = W2^T row tile j . dy_q: the W2^T image ([4C][Np = 128], quantize_weight_t_mx(fc2.weight)) has W1's shape and is tiled in W1's
+//                 row order, so accd and acc1 hold the same hidden units element for element; dy is quantised as LN(x) is (blocks of 32 channels).
+//                 dh = bf16(accd * gelu_grad_fast(bf16(acc1 + b1))) is, without lane movement, the lane's B fragment of k-step g of the next product;
+//                 a hardware block = 32 consecutive hidden units over lanes lg and lg ^ 1 (pair16_max, mx_lane_scale as in the forward).
+//   fc1 dgrad     dln[jc] += W1^T row tile jc (channels 16 jc + r; [C][4C], quantize_weight_t_mx(fc1.weight): W2's shape, W2's fragment order) . dh_q.
+//   epilogue      swin_mlp_bwd_kernel's LayerNorm backward + residual on bf16(dln); lane (t, lg) owns channels 16 jc + 4 lg .. + 3 of token t: the row
+//                 sums s1, s2 cross the four lane groups, dgamma / dbeta are sums over the 16 token lanes of a DPP row (row_shr 1/2/4/8), then LDS
+//                 atomics and one global atomic per workgroup and channel.
+//   weights       C = 96: all three images resident in LDS (139 KB with the scales).  C = 128: W1 and W2^T resident, the W1^T fragments of a group are
+//                 16-byte loads from L2 issued in front of the GELU' block (3 x 64 KB do not fit; staging the slice through a 16-KB LDS buffer costs two
+//                 workgroup barriers per group and measured 1.28 ms against 1.18 ms).  One persistent workgroup per CU.
+// Pack image (sv_swin_mlp_bwd_mx_pack, bytes):  W1F [G][8][2][64][16] | W2TF (same) | W1S [G][8][64] | W2TS (same) | W1TS [G][C/16][64] | W1TF [G][C/16][2][64][16];
+// everything in front of W1TF is resident for either C.
+template <int C> struct MlpMxB {
+  static constexpr int HID = 4 * C, G = HID / 128, NJ = C / 16;
+  static constexpr int W1F = 0, ROWF_BYTES = HID * 128;
+  static constexpr int W2TF = W1F + ROWF_BYTES;
+  static constexpr int W1S = W2TF + ROWF_BYTES, ROWS_BYTES = G * 8 * 64;
+  static constexpr int W2TS = W1S + ROWS_BYTES;
+  static constexpr int W1TS = W2TS + ROWS_BYTES, W1TS_BYTES = G * NJ * 64;
+  static constexpr int W1TF = W1TS + W1TS_BYTES, W1TF_BYTES = C * HID;
+  static constexpr int PACK_BYTES = W1TF + W1TF_BYTES;
+  static constexpr bool RESIDENT = C <= 96;                // W1TF in LDS as well
+  static constexpr int LDS_BYTES = RESIDENT ? PACK_BYTES : W1TF;
+};
+
+struct MlpMxBArgs {
+  const __bf16* x1; const __bf16* dx2; __bf16* out;
+  const float* ln_g; const float* ln_b; float eps;
+  const uint8_t* packs;
+  const float* b1;
+  const float* row_scale; int rows_per_scale;
+  float* dgamma; float* dbeta;
+  long long M; int ntiles;
+};
+
+__global__ __launch_bounds__(256) void swin_mlp_bwd_mx_pack_kernel(const uint8_t* __restrict__ w1q, const uint8_t* __restrict__ w1s, const uint8_t* __restrict__ w2tq,
+                                                                   const uint8_t* __restrict__ w2ts, const uint8_t* __restrict__ w1tq, const uint8_t* __restrict__ w1ts,
+                                                                   uint8_t* __restrict__ packs, int C) {
+  const int HID = 4 * C, G = HID / 128, NJ = C / 16;
+  const int nA = HID * 128 / 16, nS = G * 8 * 64, nST = G * NJ * 64, nT = C * HID / 16;     // 16-byte pieces of a row-tile image, scale bytes, pieces of W1TF
+  int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < 2 * nA) {                                      // W1F, W2TF: the forward's W1 row order
+    const int im = idx / nA, e = idx % nA, lane = e & 63, hf = (e >> 6) & 1, j = (e >> 7) & 7, g = e >> 10, r = lane & 15, lg = lane >> 4;
+    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
+    reinterpret_cast<i32x4*>(packs)[idx] = *reinterpret_cast<const i32x4*>((im ? w2tq : w1q) + (size_t)hid * 128 + 64 * hf + 16 * lg);
+    return;
+  }
+  idx -= 2 * nA;
+  uint8_t* sb = packs + (size_t)2 * nA * 16;
+  if (idx < 2 * nS) {
+    const int im = idx / nS, e = idx % nS, lane = e & 63, j = (e >> 6) & 7, g = e >> 9, r = lane & 15, lg = lane >> 4;
+    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
+    sb[idx] = (im ? w2ts : w1s)[hid * 4 + lg];
+    return;
+  }
+  idx -= 2 * nS; sb += 2 * nS;
+  if (idx < nST) {                                         // W1TS: the forward's W2 order
+    const int lane = idx & 63, t = idx >> 6, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
+    sb[idx] = w1ts[(16 * jc + r) * (HID / 32) + 4 * g + lg];
+    return;
+  }
+  idx -= nST; sb += nST;
+  if (idx < nT) {
+    const int lane = idx & 63, hf = (idx >> 6) & 1, t = idx >> 7, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
+    reinterpret_cast<i32x4*>(sb)[idx] = *reinterpret_cast<const i32x4*>(w1tq + (size_t)(16 * jc + r) * HID + 128 * g + 64 * hf + 16 * lg);
+  }
+}
+
+// a token's 16 + 16 values (registers 0-3 / 4-7 of a 128-wide k-step; already rounded to bf16) -> MX B fragment + the scale byte the lane passes
+__device__ __forceinline__ void mx_quant_frag(const float (&v)[2][16], i32x8& q, int& sbyte, int lane) {
+  int e[2];
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(v[hf][j]));
+    e[hf] = mx_block_exp(pair16_max(m));
+#pragma unroll
+    for (int w = 0; w < 4; ++w) q[4 * hf + w] = (int)pack4_e4m3_mx(v[hf][4 * w], v[hf][4 * w + 1], v[hf][4 * w + 2], v[hf][4 * w + 3], e[hf]);
+  }
+  sbyte = mx_lane_scale(e[0], e[1], lane);
+}
+// total over the 16 lanes of a DPP row, in lane 15 of the row
+__device__ __forceinline__ float row16_total(float v) {
+  v += dpp_shift<0x111, 0xf>(v);   // row_shr:1
+  v += dpp_shift<0x112, 0xf>(v);   // row_shr:2
+  v += dpp_shift<0x114, 0xf>(v);   // row_shr:4
+  v += dpp_shift<0x118, 0xf>(v);   // row_shr:8
+  return v;
+}
+
+template <int C, int NW, int NTT>
+__global__ __launch_bounds__(NW * 64, 1) void swin_mlp_bwd_mx_kernel(const MlpMxBArgs p) {
+  typedef MlpMxB<C> L;
+  constexpr int HID = L::HID, G = L::G, NJ = L::NJ, NT = NW * 64, TILE = NW * NTT * 16;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[L::LDS_BYTES + (HID + 4 * C) * 4];
+  float* sb1 = reinterpret_cast<float*>(smem + L::LDS_BYTES);
+  float* sdg = sb1 + HID;
+  float* sdb = sdg + C;
+  float* sgam = sdb + C;                                   // LayerNorm parameters in LDS: see swin_mlp_bwd_kernel
+  float* sbet = sgam + C;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = lane & 15, lg = lane >> 4;
+  for (int i = tid; i < L::LDS_BYTES / 16; i += NT) reinterpret_cast<i32x4*>(smem)[i] = reinterpret_cast<const i32x4*>(p.packs)[i];
+  for (int i = tid; i < HID; i += NT) sb1[i] = p.b1[i];
+  for (int i = tid; i < C; i += NT) { sdg[i] = 0.f; sdb[i] = 0.f; sgam[i] = p.ln_g[i]; sbet[i] = p.ln_b[i]; }
+  __syncthreads();
+  const bool hi_live = 64 + 16 * lg < C;                   // C = 96: channels 96 .. 127 are padding
+
+#pragma unroll 1
+  for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
+    long long tok[NTT]; bool valid[NTT];
+    float mean[NTT], rstd[NTT];
+    i32x8 xq[NTT], dq[NTT]; int xsb[NTT], dsb[NTT];
+    // ---- LayerNorm -> MX B fragments of the recompute (as swin_mlp_fwd_mx_kernel); dbr = bf16(sc dx2) -> MX B fragments of fc2's data gradient
+#pragma unroll
+    for (int tt = 0; tt < NTT; ++tt) {
+      tok[tt] = (long long)tile * TILE + wave * (NTT * 16) + tt * 16 + t;
+      valid[tt] = tok[tt] < p.M;
+      const float sc = (valid[tt] && p.row_scale) ? p.row_scale[tok[tt] / p.rows_per_scale] : 1.f;
+      float xv[2][16], dv[2][16];
+      float s = 0.f;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          bf16x8 raw = VecN<__bf16, 8>::zero(), dr = VecN<__bf16, 8>::zero();
+          if (valid[tt] && (hf == 0 || hi_live)) {
+            raw = *reinterpret_cast<const bf16x8*>(p.x1 + tok[tt] * C + 64 * hf + 16 * lg + 8 * u);
+            dr = *reinterpret_cast<const bf16x8*>(p.dx2 + tok[tt] * C + 64 * hf + 16 * lg + 8 * u);
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            xv[hf][8 * u + j] = (float)raw[j]; s += xv[hf][8 * u + j];
+            dv[hf][8 * u + j] = (float)(__bf16)(sc * (float)dr[j]);
+          }
+        }
+      s = lane_step_add<16>(s); s = lane_step_add<32>(s);
+      mean[tt] = s * (1.f / C);
+      float q = 0.f;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        if (hf == 0 || hi_live)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) { const float d = xv[hf][j] - mean[tt]; q += d * d; }
+      q = lane_step_add<16>(q); q = lane_step_add<32>(q);
+      rstd[tt] = rsqrtf(q * (1.f / C) + p.eps);
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const bool live = hf == 0 || hi_live;
+        const int c0 = live ? 64 * hf + 16 * lg : 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          xv[hf][j] = live ? (float)(__bf16)((xv[hf][j] - mean[tt]) * rstd[tt] * sgam[c0 + j] + sbet[c0 + j]) : 0.f;
+      }
+      mx_quant_frag(xv, xq[tt], xsb[tt], lane);
+      mx_quant_frag(dv, dq[tt], dsb[tt], lane);
+    }
+
+    f32x4 dln[NJ][NTT];
+#pragma unroll
+    for (int jc = 0; jc < NJ; ++jc)
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt) dln[jc][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      // ---- the 128 hidden units of group g: pre-activation (recomputed) and dy . W2, two independent chains interleaved on the matrix pipe
+      f32x4 acc1[8][NTT], accd[8][NTT];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint8_t* fa = smem + L::W1F + (size_t)((g * 8 + j) * 2) * 1024 + lane * 16;
+        const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
+        const i32x4 tlo = *reinterpret_cast<const i32x4*>(fa + L::W2TF), thi = *reinterpret_cast<const i32x4*>(fa + L::W2TF + 1024);
+        const i32x8 a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const i32x8 at = (i32x8){tlo[0], tlo[1], tlo[2], tlo[3], thi[0], thi[1], thi[2], thi[3]};
+        const int sa = smem[L::W1S + (g * 8 + j) * 64 + lane], sat = smem[L::W2TS + (g * 8 + j) * 64 + lane];
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt) {
+          acc1[j][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, xq[tt], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, sa, 0, xsb[tt]);
+          accd[j][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(at, dq[tt], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, sat, 0, dsb[tt]);
+        }
+      }
+      // W1^T fragments of the group that are not resident (C = 128): requested here, they arrive under the GELU' block
+      i32x8 wt[L::RESIDENT ? 1 : NJ];
+      if constexpr (!L::RESIDENT) {
+#pragma unroll
+        for (int jc = 0; jc < NJ; ++jc) {
+          const uint8_t* fa = p.packs + L::W1TF + (size_t)((g * NJ + jc) * 2) * 1024 + lane * 16;
+          const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
+          wt[jc] = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        }
+      }
+      // ---- dh = bf16(accd * GELU'(bf16(acc1 + b1))), MX quantisation in registers: the B fragment of k-step g of fc1's data gradient
+      i32x8 hq[NTT]; int hsb[NTT];
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt) {
+        int e[2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          float m = 0.f;
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int j = 4 * hf + jj;
+            const float4 bi = *reinterpret_cast<const float4*>(sb1 + 128 * g + 64 * hf + 16 * lg + 4 * jj);
+            const f32x2 d0 = gelu_grad_fast2((f32x2){(float)(__bf16)(acc1[j][tt][0] + bi.x), (float)(__bf16)(acc1[j][tt][1] + bi.y)});
+            const f32x2 d1 = gelu_grad_fast2((f32x2){(float)(__bf16)(acc1[j][tt][2] + bi.z), (float)(__bf16)(acc1[j][tt][3] + bi.w)});
+            accd[j][tt][0] = (float)(__bf16)(accd[j][tt][0] * d0[0]); accd[j][tt][1] = (float)(__bf16)(accd[j][tt][1] * d0[1]);
+            accd[j][tt][2] = (float)(__bf16)(accd[j][tt][2] * d1[0]); accd[j][tt][3] = (float)(__bf16)(accd[j][tt][3] * d1[1]);
+            m = fmaxf(fmaxf(m, fmaxf(fabsf(accd[j][tt][0]), fabsf(accd[j][tt][1]))), fmaxf(fabsf(accd[j][tt][2]), fabsf(accd[j][tt][3])));
+          }
+          e[hf] = mx_block_exp(pair16_max(m));
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int j = 4 * hf + jj;
+            hq[tt][j] = (int)pack4_e4m3_mx(accd[j][tt][0], accd[j][tt][1], accd[j][tt][2], accd[j][tt][3], e[hf]);
+          }
+        }
+        hsb[tt] = mx_lane_scale(e[0], e[1], lane);
+      }
+      // ---- fc1 data gradient: k-step g
+#pragma unroll
+      for (int jc = 0; jc < NJ; ++jc) {
+        i32x8 a;
+        if constexpr (L::RESIDENT) {
+          const uint8_t* fa = smem + L::W1TF + (size_t)((g * NJ + jc) * 2) * 1024 + lane * 16;
+          const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
+          a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        } else {
+          a = wt[jc];
+        }
+        const int sa = smem[L::W1TS + (g * NJ + jc) * 64 + lane];
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt)
+          dln[jc][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, hq[tt], dln[jc][tt], 0, 0, 0, sa, 0, hsb[tt]);
+      }
+    }
+    // ---- LayerNorm backward + residual on bf16(dln) (swin_mlp_bwd_kernel's epilogue); lane (t, lg): channels 16 jc + 4 lg + k of token t.
+    // The lane offset is laundered per tile so that the LDS addresses stay immediate offsets (see swin_mlp_bwd_kernel)
+    int lane_off = 4 * lg;
+    asm volatile("" : "+v"(lane_off));
+    float* const lg_ = sgam + lane_off;
+    float* const ldg_ = sdg + lane_off;
+    float* const ldb_ = sdb + lane_off;
+#pragma unroll
+    for (int tt = 0; tt < NTT; ++tt) {
+      const bool ok = valid[tt];
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int jc = 0; jc < NJ; ++jc) {
+        bf16x4 xr = V4<__bf16>::zero();
+        if (ok) xr = *reinterpret_cast<const bf16x4*>(p.x1 + tok[tt] * C + 16 * jc + 4 * lg);
+        const float4 gm = *reinterpret_cast<const float4*>(lg_ + 16 * jc);
+        const float gv[4] = {gm.x, gm.y, gm.z, gm.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          dln[jc][tt][k] = (float)(__bf16)dln[jc][tt][k];  // the value the unfused fc1 data gradient stores
+          const float xh = ok ? ((float)xr[k] - mean[tt]) * rstd[tt] : 0.f;
+          const float d = ok ? dln[jc][tt][k] : 0.f;
+          const float gg = d * gv[k];
+          s1 += gg; s2 += gg * xh;
+          const float tb = row16_total(d), tg = row16_total(d * xh);
+          if (t == 15) { atomicAdd(ldb_ + 16 * jc + k, tb); atomicAdd(ldg_ + 16 * jc + k, tg); }
+        }
+        __builtin_amdgcn_sched_barrier(0);                 // keep the 8 reduction chains of one channel group together
+      }
+      s1 = lane_step_add<16>(s1); s1 = lane_step_add<32>(s1);
+      s2 = lane_step_add<16>(s2); s2 = lane_step_add<32>(s2);
+      s1 *= (1.f / C); s2 *= (1.f / C);
+      if (ok) {
+#pragma unroll
+        for (int jc = 0; jc < NJ; ++jc) {
+          const int c0 = 16 * jc + 4 * lg;
+          const bf16x4 xr = *reinterpret_cast<const bf16x4*>(p.x1 + tok[tt] * C + c0);
+          const bf16x4 dr = *reinterpret_cast<const bf16x4*>(p.dx2 + tok[tt] * C + c0);
+          const float4 gm = *reinterpret_cast<const float4*>(lg_ + 16 * jc);
+          const float gv[4] = {gm.x, gm.y, gm.z, gm.w};
+          bf16x4 o;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float xh = ((float)xr[k] - mean[tt]) * rstd[tt];
+            o[k] = (__bf16)((float)dr[k] + rstd[tt] * (dln[jc][tt][k] * gv[k] - s1 - xh * s2));
+          }
+          *reinterpret_cast<bf16x4*>(p.out + tok[tt] * C + c0) = o;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < C; i += NT) { atomicAdd(p.dgamma + i, sdg[i]); atomicAdd(p.dbeta + i, sdb[i]); }
+}
+
+// C = 128 is served while its instantiation is free of spills and scratch; the host keeps the bf16 backward where this says no
+static inline bool mlp_bwd_mx_supported(int C) { return C == 96 || C == 128; }
+static inline long long mlp_bwd_mx_pack_bytes(int C) { return C == 96 ? MlpMxB<96>::PACK_BYTES : C == 128 ? MlpMxB<128>::PACK_BYTES : 0; }
+
 }  // namespace sv
 
 using namespace sv;
@@ -1035,5 +1340,52 @@ extern "C" int sv_swin_mlp_fwd_mx(const void* x1, void* x2, const float* ln_g, c
 #undef SV_MLP_MX
   const int rc = check_launch("sv_swin_mlp_fwd_mx");
   if (rc == SV_OK) swin_mlp_mx_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+// ---- MXFP8 data gradient ------------------------------------------------------------------------------------------------------------
+static std::atomic<long long> swin_mlp_bwd_mx_launches{0};
+extern "C" long long sv_swin_mlp_bwd_mx_launches(void) { return swin_mlp_bwd_mx_launches.load(std::memory_order_relaxed); }
+extern "C" int sv_swin_mlp_bwd_mx_supported(int C) { return mlp_bwd_mx_supported(C) ? 1 : 0; }
+extern "C" long long sv_swin_mlp_bwd_mx_pack_bytes(int C) { return mlp_bwd_mx_supported(C) ? mlp_bwd_mx_pack_bytes(C) : 0; }
+
+extern "C" int sv_swin_mlp_bwd_mx_pack(const void* w1q, const void* w1s, const void* w2tq, const void* w2ts, const void* w1tq, const void* w1ts, void* packs,
+                                       int C, void* stream) {
+  SV_REQUIRE(w1q && w1s && w2tq && w2ts && w1tq && w1ts && packs, "sv_swin_mlp_bwd_mx_pack: null pointer");
+  SV_REQUIRE(mlp_bwd_mx_supported(C), "sv_swin_mlp_bwd_mx_pack: unsupported C=%d", C);
+  SV_REQUIRE((((uintptr_t)w1q | (uintptr_t)w2tq | (uintptr_t)w1tq | (uintptr_t)packs) & 15) == 0,
+             "sv_swin_mlp_bwd_mx_pack: w1q, w2tq, w1tq and packs must be 16-byte aligned");
+  const long long HID = 4ll * C, G = HID / 128, NJ = C / 16;
+  const long long items = 2 * (HID * 128 / 16) + 2 * (G * 8 * 64) + G * NJ * 64 + C * HID / 16;
+  hipLaunchKernelGGL(swin_mlp_bwd_mx_pack_kernel, dim3(cdiv(items, 256)), dim3(256), 0, STREAM, static_cast<const uint8_t*>(w1q), static_cast<const uint8_t*>(w1s),
+                     static_cast<const uint8_t*>(w2tq), static_cast<const uint8_t*>(w2ts), static_cast<const uint8_t*>(w1tq), static_cast<const uint8_t*>(w1ts),
+                     static_cast<uint8_t*>(packs), C);
+  return check_launch("sv_swin_mlp_bwd_mx_pack");
+}
+
+extern "C" int sv_swin_mlp_bwd_mx(const void* x1, const void* dx2, void* dx1, const float* ln_g, const float* ln_b, const void* packs_mx, const float* b1,
+                                  const float* row_scale, int rows_per_scale, float* dgamma, float* dbeta, long long M, int C, float eps, void* stream) {
+  SV_REQUIRE(x1 && dx2 && dx1 && ln_g && ln_b && packs_mx && b1 && dgamma && dbeta, "sv_swin_mlp_bwd_mx: null pointer");
+  SV_REQUIRE(mlp_bwd_mx_supported(C), "sv_swin_mlp_bwd_mx: unsupported C=%d", C);
+  SV_REQUIRE(M > 0 && M < (1ll << 31), "sv_swin_mlp_bwd_mx: M=%lld out of range", M);
+  SV_REQUIRE((((uintptr_t)x1 | (uintptr_t)dx2 | (uintptr_t)dx1 | (uintptr_t)packs_mx | (uintptr_t)ln_g | (uintptr_t)ln_b) & 15) == 0,
+             "sv_swin_mlp_bwd_mx: operands must be 16-byte aligned");
+  SV_REQUIRE(rows_per_scale > 0, "sv_swin_mlp_bwd_mx: rows_per_scale must be positive");
+  MlpMxBArgs a{};
+  a.x1 = static_cast<const __bf16*>(x1); a.dx2 = static_cast<const __bf16*>(dx2); a.out = static_cast<__bf16*>(dx1);
+  a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps; a.packs = static_cast<const uint8_t*>(packs_mx); a.b1 = b1;
+  a.row_scale = row_scale; a.rows_per_scale = rows_per_scale; a.dgamma = dgamma; a.dbeta = dbeta; a.M = M;
+  // 8 waves x 16 tokens, one persistent workgroup per CU, as the forward; 8 x 32 spills and is slower
+#define SV_MLP_BWD_MX(CC, NW, NTT)                                                                                 \
+  do {                                                                                                             \
+    a.ntiles = cdiv(M, NW * NTT * 16);                                                                             \
+    const int grid = a.ntiles < 256 ? a.ntiles : 256;                                                              \
+    hipLaunchKernelGGL((swin_mlp_bwd_mx_kernel<CC, NW, NTT>), dim3(grid), dim3(NW * 64), 0, STREAM, a);            \
+  } while (0)
+  if (C == 96) SV_MLP_BWD_MX(96, 8, 1);
+  else SV_MLP_BWD_MX(128, 8, 1);
+#undef SV_MLP_BWD_MX
+  const int rc = check_launch("sv_swin_mlp_bwd_mx");
+  if (rc == SV_OK) swin_mlp_bwd_mx_launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }

@@ -217,13 +217,16 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         # norm2 -> fc1 -> GELU -> fc2 -> drop-path -> +x1 in ONE kernel; the 4C-wide hidden activation never reaches HBM
         mx = ops.fused_mlp_mx_enabled(Cd)
         packs = None
-        if save or not mx:                                 # the bf16 images: read by sv_swin_mlp_fwd and by the (unchanged) fused backward
+        # the bf16 images: read by sv_swin_mlp_fwd and by the fused bf16 backward (the MX data gradient packs its own operands; the weight
+        # gradient reads pack_fwd / pack_dgrad)
+        if not mx or (save and not ops.fused_mlp_mx_bwd_enabled(Cd)):
             packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
             call("sv_swin_mlp_pack", ptr(blk.mlp.fc1.weight), ptr(blk.mlp.fc2.weight), ptr(packs), Cd)
         x2 = empty(M, Cd, like=x)
         unit = 2.0 * M * Cd * 4 * Cd
         if mx:
-            # opt-in MXFP8 forward (set_fused_mlp_mx): both products on MX operands, quantised in registers; the backward recomputes in bf16
+            # opt-in MXFP8 forward (set_fused_mlp_mx): both products on MX operands, quantised in registers; the backward recomputes in bf16, or
+            # on MX operands as well with set_fused_mlp_mx(True, backward=True)
             packs_mx = ops.swin_mlp_mx_packs(blk.mlp.fc1.weight, blk.mlp.fc2.weight, Cd)
             ops.traced_call("sv_swin_mlp_fwd_mx", 2 * unit, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs_mx),
                             ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
@@ -285,8 +288,15 @@ def _fused_mlp_backward(blk, x1, packs, sc2, dx2, grads, M, Cd, HW):
     unit = 2.0 * M * Cd * 4 * Cd
     eps = float(blk.norm2.eps)
     dx1 = empty(M, Cd, like=x1)
-    ops.traced_call("sv_swin_mlp_bwd", 3 * unit, 6.0 * M * Cd, ptr(x1), ptr(dx2), ptr(dx1), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs),
-                    ptr(blk.mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.norm2.weight]), ptr(grads[blk.norm2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
+    if ops.fused_mlp_mx_bwd_enabled(Cd):
+        # opt-in MXFP8 data gradient (set_fused_mlp_mx(True, backward=True)): the unfused MX backward chain of the branch in one kernel
+        packs_mx = ops.swin_mlp_mx_bwd_packs(blk.mlp.fc1.weight, blk.mlp.fc2.weight, Cd)
+        ops.traced_call("sv_swin_mlp_bwd_mx", 3 * unit, 6.0 * M * Cd, ptr(x1), ptr(dx2), ptr(dx1), ptr(blk.norm2.weight), ptr(blk.norm2.bias),
+                        ptr(packs_mx), ptr(blk.mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.norm2.weight]), ptr(grads[blk.norm2.bias]), M, Cd, eps,
+                        tag=f"M={M} C={Cd}")
+    else:
+        ops.traced_call("sv_swin_mlp_bwd", 3 * unit, 6.0 * M * Cd, ptr(x1), ptr(dx2), ptr(dx1), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs),
+                        ptr(blk.mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.norm2.weight]), ptr(grads[blk.norm2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
     w1r, w2tr = blk.s_fc1.pack_fwd(blk.mlp.fc1.weight), blk.s_fc2.pack_dgrad(blk.mlp.fc2.weight)     # bf16 [4C][C] rows both
 
     def launch():

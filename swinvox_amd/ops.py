@@ -546,11 +546,15 @@ def set_fused_mlp(on: bool) -> None:
     _STATE["fused_mlp"] = bool(on)
 
 
-def set_fused_mlp_mx(on: bool) -> None:
+def set_fused_mlp_mx(on: bool, backward: bool = False) -> None:
     """Opt-in (off by default; SV_FUSED_MLP_MX=1 in the environment switches it on as well): under set_linear_fp8(True, recipe="mx") the blocks
-    that run the fused Swin MLP take its MXFP8 forward (sv_swin_mlp_fwd_mx: the unfused MX chain in one kernel).  The backward is the fused bf16
-    backward, unchanged: the quantisers are straight-through."""
+    that run the fused Swin MLP take its MXFP8 forward (sv_swin_mlp_fwd_mx: the unfused MX chain in one kernel).  Without `backward` the backward
+    is the fused bf16 backward, unchanged: the quantisers are straight-through.  backward=True (effective only with `on`; SV_FUSED_MLP_MX_BWD=1
+    sets it as well) lets the data gradient of those blocks differentiate that very forward on MX operands (sv_swin_mlp_bwd_mx: the unfused MX
+    backward chain in one kernel) while set_linear_fp8(..., backward=True, backward_recipe="mx") holds; the weight gradients stay on
+    sv_swin_mlp_wgrad."""
     _STATE["fused_mlp_mx"] = bool(on)
+    _STATE["fused_mlp_mx_bwd"] = bool(on) and bool(backward)
 
 
 def fused_mlp_mx_enabled(C: int) -> bool:
@@ -576,6 +580,30 @@ def swin_mlp_mx_packs(w1: torch.Tensor, w2: torch.Tensor, C: int) -> torch.Tenso
     return packs
 
 
+def fused_mlp_mx_bwd_enabled(C: int) -> bool:
+    """The MXFP8 data gradient of the fused Swin MLP: its switch, the MX forward of the same block (fused_mlp_mx_enabled), the MX backward recipe
+    of the Swin linears and a C the library serves.  Inert everywhere else."""
+    import os
+    if not (_STATE.get("fused_mlp_mx_bwd", False) or os.environ.get("SV_FUSED_MLP_MX_BWD", "0") == "1"):
+        return False
+    return (fused_mlp_mx_enabled(C) and linear_fp8_bwd_enabled() and linear_fp8_bwd_recipe() == "mx"
+            and hip.load().sv_swin_mlp_bwd_mx_supported(C) == 1)
+
+
+def swin_mlp_mx_bwd_launches() -> int:
+    """sv_swin_mlp_bwd_mx launches of this process so far."""
+    return int(hip.load().sv_swin_mlp_bwd_mx_launches())
+
+
+def swin_mlp_mx_bwd_packs(w1: torch.Tensor, w2: torch.Tensor, C: int) -> torch.Tensor:
+    """The MX rows of fc1.weight, of fc2.weight^T and of fc1.weight^T (quantize_weight_mx / quantize_weight_t_mx: the unfused sites' bytes, from
+    the module's pack cache) in the fragment order of sv_swin_mlp_bwd_mx."""
+    (w1q, w1s), (w2tq, w2ts), (w1tq, w1ts) = quantize_weight_mx(w1), quantize_weight_t_mx(w2), quantize_weight_t_mx(w1)
+    packs = torch.empty(int(hip.load().sv_swin_mlp_bwd_mx_pack_bytes(C)), dtype=torch.uint8, device=w1.device)
+    call("sv_swin_mlp_bwd_mx_pack", ptr(w1q), ptr(w1s), ptr(w2tq), ptr(w2ts), ptr(w1tq), ptr(w1ts), ptr(packs), C)
+    return packs
+
+
 def colsum(x, rows, cols, ld, out, accumulate=True):
     call("sv_colsum", ptr(x), rows, cols, ld, ptr(out), 1 if accumulate else 0)
 
@@ -594,7 +622,8 @@ def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backwa
     together with `on`) the data and weight gradients of the unfused Swin sites run on e4m3 operands as well (swin_linear_dgrad /
     swin_linear_wgrad).  Active only under set_math('bf16'); independent of set_attention_fp8.
     Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them).
-    Under recipe "mx" set_fused_mlp_mx(True) (off by default) gives the fused MLP an MXFP8 forward of its own (sv_swin_mlp_fwd_mx).
+    Under recipe "mx" set_fused_mlp_mx(True) (off by default) gives the fused MLP an MXFP8 forward of its own (sv_swin_mlp_fwd_mx), and
+    set_fused_mlp_mx(True, backward=True) under backward_recipe "mx" an MXFP8 data gradient as well (sv_swin_mlp_bwd_mx).
     The LayerNorms that feed qkv, fc1 and the reduction emit the quantised rows themselves (set_ln_quant_fused).
     recipe = "row" (default): one fp32 scale per operand row, divided out in the epilogue.  recipe = "mx": the FORWARD of the same call sites
     on MX operands - one E8M0 power-of-two scale per 32 consecutive elements of the contraction, applied by the MFMA (sv_linear_mxfp8).  A block

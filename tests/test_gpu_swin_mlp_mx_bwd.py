@@ -1,0 +1,386 @@
+"""MXFP8 data gradient of the fused Swin MLP (csrc/swin_mlp.hip: sv_swin_mlp_bwd_mx_pack, sv_swin_mlp_bwd_mx) through the C ABI against the recipe's
+torch emulation (tests/test_cpu_swin_mlp_mx_bwd_recipe.py, which checks it on the CPU), against the unfused MX backward chain run through the C ABI
+on the same bytes, against the bf16 fused backward, and the host switch ops.set_fused_mlp_mx(True, backward=True) inside block_backward.
+
+Shapes: C in {96, 128} x M in {1, 17, 147, 200} - the lone token, a partly filled 16-token fragment, a partly filled 128-token tile, a second tile on
+a second workgroup, scale groups that straddle fragments (rows_per_scale 5 and 49), the K padding of C = 96 - and one row_scale = NULL case per C.
+Every dx1 carries NaN guard rows.  C = 128 runs where sv_swin_mlp_bwd_mx_supported(128) says so; elsewhere the host keeps the bf16 backward and the
+C = 128 cases check exactly that."""
+import ctypes as C_
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_cpu_linear_fp8_recipe import l1_rel  # noqa: E402
+from test_cpu_swin_mlp_mx_recipe import gauss_mlp_case  # noqa: E402
+from test_cpu_swin_mlp_mx_bwd_recipe import dgrad_seed, emulate_swin_mlp_bwd_mx  # noqa: E402
+
+import swinvox_amd as S  # noqa: E402
+from swinvox_amd import hip, ops  # noqa: E402
+from swinvox_amd.ops import call, ptr  # noqa: E402
+
+GUARD = 2
+WIDTHS = [96, 128]
+TOKENS = [1, 17, 147, 200]
+RPS = {1: 1, 17: 5, 147: 49, 200: 49}
+CASES = [(Cd, M, True) for Cd in WIDTHS for M in TOKENS] + [(Cd, 147, False) for Cd in WIDTHS]     # (C, M, with row_scale)
+L1_BF16, MAX_BOUND = 3e-3, 1e-2  # the project's bounds on the unfused MX kernels in bf16 storage (tests/test_gpu_linear_mxfp8_bwd.py)
+MARGIN = 1.5                     # the issue's: rare e4m3 flips on fp32-ulp differences of accumulation order, here plus the LayerNorm backward's fp32 order
+UNIT = 2.0 ** -8                 # one bf16 rounding of the largest element: the floor of the chain's distance (M = 1 can lie below it)
+# the bf16 fused backward is at least this many times farther from the MX emulation than the MX kernel, on the branch gradient dx1 - dx2.
+# Measured on an MI355X: 21.7 x ... 28.0 x over the ten cases; the floor is the forward test's and lies 7 x below the smallest.
+SEPARATION = 3.0
+# Sanity bound on "the same gradient under another rounding" in the host test: one e4m3 product lies 3.7e-2 (L1-relative) from the exact one
+# (tests/test_cpu_linear_mxfp8_bwd_recipe.py); the branch gradient passes three such products (recompute, fc2, fc1), so 4 x that bounds it loosely.
+SAME_GRADIENT = 4 * 3.7e-2
+
+
+def _supported(Cd):
+    return hip.load().sv_swin_mlp_bwd_mx_supported(Cd) == 1
+
+
+def _unserved(Cd):
+    """True where sv_swin_mlp_bwd_mx_supported(Cd) says no (C = 96 never may): the library then has no pack size for it and the host keeps the bf16
+    backward there, which test_host_switch checks"""
+    if _supported(Cd):
+        return False
+    assert Cd != 96 and hip.load().sv_swin_mlp_bwd_mx_pack_bytes(Cd) == 0
+    return True
+
+
+def _quant_rows(w):
+    N, K = w.shape
+    Kp = (K + 127) // 128 * 128
+    q = torch.empty(N, Kp, dtype=torch.uint8, device=w.device)
+    s = torch.empty(N, Kp // 32, dtype=torch.uint8, device=w.device)
+    call("sv_quant_rows_mx_e4m3", ptr(w), hip.BF16 if w.dtype == torch.bfloat16 else hip.F32, N, K, K, ptr(q), Kp, ptr(s))
+    return q, s
+
+
+def _quant_cols(w):
+    """the MX rows of w^T: [K][roundup(N, 128)] bytes, a block = 32 consecutive rows n of one column k"""
+    N, K = w.shape
+    Np = (N + 127) // 128 * 128
+    q = torch.empty(K, Np, dtype=torch.uint8, device=w.device)
+    s = torch.empty(K, Np // 32, dtype=torch.uint8, device=w.device)
+    call("sv_quant_cols_mx_e4m3", ptr(w), hip.F32, N, K, K, ptr(q), Np, ptr(s), None)
+    return q, s
+
+
+def _upload(c, dx2, dev):
+    d = {k: (v.to(dev).contiguous() if isinstance(v, torch.Tensor) else v) for k, v in c.items()}
+    d["dx2"] = dx2.to(dev).contiguous()
+    d["w1"], d["w2t"], d["w1t"] = _quant_rows(d["W1"]), _quant_cols(d["W2"]), _quant_cols(d["W1"])
+    return d
+
+
+def _out(M, Cd, dev):
+    return torch.full((M + GUARD, Cd), float("nan"), dtype=torch.bfloat16, device=dev)
+
+
+def _guards_intact(out, M):
+    return bool(torch.isnan(out[M:].float()).all())
+
+
+def _prefill(Cd, dev):
+    """what dgamma / dbeta hold before the launch: the kernels ADD to it"""
+    g = torch.Generator().manual_seed(31 + Cd)
+    return torch.randn(Cd, generator=g).to(dev), torch.randn(Cd, generator=g).to(dev)
+
+
+def _fused_mx(d, M, Cd, dev):
+    lib = hip.load()
+    packs = torch.empty(int(lib.sv_swin_mlp_bwd_mx_pack_bytes(Cd)), dtype=torch.uint8, device=dev)
+    call("sv_swin_mlp_bwd_mx_pack", ptr(d["w1"][0]), ptr(d["w1"][1]), ptr(d["w2t"][0]), ptr(d["w2t"][1]), ptr(d["w1t"][0]), ptr(d["w1t"][1]), ptr(packs), Cd)
+    outs = []
+    for _ in range(2):                                                          # twice: dx1 has no atomics and must repeat bit for bit
+        dx1 = _out(M, Cd, dev)
+        dg, db = _prefill(Cd, dev)
+        n0 = ops.swin_mlp_mx_bwd_launches(), ops.linear_mxfp8_bwd_launches()
+        call("sv_swin_mlp_bwd_mx", ptr(d["x1"]), ptr(d["dx2"]), ptr(dx1), ptr(d["ln_g"]), ptr(d["ln_b"]), ptr(packs), ptr(d["b1"]), ptr(d["row_scale"]),
+             d["rows_per_scale"], ptr(dg), ptr(db), M, Cd, d["eps"])
+        torch.cuda.synchronize()
+        assert (ops.swin_mlp_mx_bwd_launches(), ops.linear_mxfp8_bwd_launches()) == (n0[0] + 1, n0[1])
+        outs.append((dx1.cpu(), dg.cpu(), db.cpu()))
+    return outs
+
+
+def _fused_bf16(d, M, Cd, dev):
+    packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=dev)
+    call("sv_swin_mlp_pack", ptr(d["W1"]), ptr(d["W2"]), ptr(packs), Cd)
+    dx1 = _out(M, Cd, dev)
+    dg, db = _prefill(Cd, dev)
+    call("sv_swin_mlp_bwd", ptr(d["x1"]), ptr(d["dx2"]), ptr(dx1), ptr(d["ln_g"]), ptr(d["ln_b"]), ptr(packs), ptr(d["b1"]), ptr(d["row_scale"]),
+         d["rows_per_scale"], ptr(dg), ptr(db), M, Cd, d["eps"])
+    torch.cuda.synchronize()
+    assert _guards_intact(dx1, M)
+    return dx1.cpu(), dg.cpu(), db.cpu()
+
+
+def _unfused_chain(d, M, Cd, dev):
+    """The parent's MX chain in bf16 storage.  Forward part (for the saved statistics and hpre): sv_layernorm_quant_mx_fwd -> sv_linear_mxfp8 (GELU,
+    pre_act, q_out).  Backward: sv_rowscale -> sv_quant_rows_mx_e4m3 -> sv_linear_mxfp8_dgrad (GELU' at hpre) -> sv_quant_rows_mx_e4m3 ->
+    sv_linear_mxfp8_dgrad -> sv_layernorm_bwd (accumulating into a copy of dx2) with the statistics the forward saved."""
+    HID = 4 * Cd
+    bf = dict(dtype=torch.bfloat16, device=dev)
+    y = torch.empty(M, Cd, **bf)
+    mean, rstd = torch.empty(M, device=dev), torch.empty(M, device=dev)
+    q = torch.empty(M, 128, dtype=torch.uint8, device=dev)
+    s = torch.empty(M, 4, dtype=torch.uint8, device=dev)
+    call("sv_layernorm_quant_mx_fwd", ptr(d["x1"]), ptr(d["ln_g"]), ptr(d["ln_b"]), ptr(y), ptr(mean), ptr(rstd), ptr(q), 128, ptr(s), M, Cd, d["eps"], 0, 0,
+         act=hip.BF16)
+    hq = torch.empty(M, HID, dtype=torch.uint8, device=dev)
+    hs = torch.empty(M, HID // 32, dtype=torch.uint8, device=dev)
+    hpre = torch.empty(M, HID, **bf)
+    e1 = ops._epilogue(HID, bias=d["b1"], act=hip.ACT_GELU, pre_act=hpre)
+    call("sv_linear_mxfp8", ptr(q), ptr(s), ptr(d["w1"][0]), ptr(d["w1"][1]), None, M, Cd, HID, C_.byref(e1), ptr(hq), ptr(hs), act=hip.BF16)
+    dbr = d["dx2"]
+    if d["row_scale"] is not None:
+        dbr = torch.empty(M, Cd, **bf)
+        call("sv_rowscale", ptr(d["dx2"]), ptr(d["row_scale"]), ptr(dbr), M, Cd, d["rows_per_scale"], act=hip.BF16)
+    dq, ds = _quant_rows(dbr[:M])
+    dh = torch.empty(M, HID, **bf)
+    e2 = ops._epilogue(HID, act_grad_src=hpre, act_grad_kind=hip.ACT_GELU)
+    call("sv_linear_mxfp8_dgrad", ptr(dq), ptr(ds), ptr(d["w2t"][0]), ptr(d["w2t"][1]), ptr(dh), M, Cd, HID, C_.byref(e2), act=hip.BF16)
+    hq2, hs2 = _quant_rows(dh)
+    dln = torch.empty(M, Cd, **bf)
+    e3 = ops._epilogue(Cd)
+    call("sv_linear_mxfp8_dgrad", ptr(hq2), ptr(hs2), ptr(d["w1t"][0]), ptr(d["w1t"][1]), ptr(dln), M, HID, Cd, C_.byref(e3), act=hip.BF16)
+    dx1 = _out(M, Cd, dev)
+    dx1[:M] = d["dx2"][:M]
+    dg, db = _prefill(Cd, dev)
+    ws = torch.zeros(ops.LN_BWD_SLOTS * Cd + 1, dtype=torch.float64, device=dev)
+    call("sv_layernorm_bwd", ptr(dln), ptr(d["x1"]), ptr(d["ln_g"]), ptr(mean), ptr(rstd), ptr(dx1), ptr(dg), ptr(db), ptr(ws), M, Cd, 0, 0, 1, act=hip.BF16)
+    torch.cuda.synchronize()
+    assert _guards_intact(dx1, M)
+    return dx1.cpu(), dg.cpu(), db.cpu()
+
+
+_RUNS = {}
+
+
+def _runs(dev, Cd, M, scaled):
+    """emulation, MX fused kernel (twice), unfused MX chain and bf16 fused kernel on one case: computed once, left unchanged"""
+    key = (Cd, M, scaled)
+    if key not in _RUNS:
+        c = gauss_mlp_case(M, Cd, windows=RPS[M] if scaled else None)
+        dx2 = dgrad_seed(c["x1"])
+        d = _upload(c, dx2, dev)
+        ref = emulate_swin_mlp_bwd_mx(dx2=dx2, **c)
+        pre = tuple(t.cpu().double() for t in _prefill(Cd, dev))
+        _RUNS[key] = dict(dx2=dx2.double(), ref=ref, pre=pre, mx=_fused_mx(d, M, Cd, dev), chain=_unfused_chain(d, M, Cd, dev), bf16=_fused_bf16(d, M, Cd, dev))
+    return _RUNS[key]
+
+
+def _triple(run, r, M):
+    """(dx1, dgamma, dbeta) of one run in fp64, the prefill taken off the parameter gradients"""
+    dx1, dg, db = run
+    return dx1[:M].double(), dg.double() - r["pre"][0], db.double() - r["pre"][1]
+
+
+def _dist(got, ref):
+    return l1_rel(got, ref), float((got - ref).abs().max() / ref.abs().max())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cd,M,scaled", CASES)
+def test_kernel_against_the_chain_and_the_emulation(dev, Cd, M, scaled):
+    """dx1, dgamma, dbeta: the fused kernel stays within 1.5 x d_chain of the emulation, mean (L1-relative) and worst element, d_chain being the
+    distance of the unfused MX chain - the reference, which meets the project's bounds - from the same emulation, floored at one bf16 rounding."""
+    if _unserved(Cd):
+        return
+    r = _runs(dev, Cd, M, scaled)
+    mx, chain = _triple(r["mx"][0], r, M), _triple(r["chain"], r, M)
+    for name, got, ch, ref in zip(("dx1", "dgamma", "dbeta"), mx, chain, r["ref"]):
+        assert bool(torch.isfinite(got).all()), name
+        (l1, wm), (l1c, wmc) = _dist(got, ref), _dist(ch, ref)
+        print(f"C={Cd} M={M} row_scale={scaled} {name}: fused MX vs emulation L1-rel {l1:.3e} worst {wm:.3e}; unfused MX chain vs emulation L1-rel "
+              f"{l1c:.3e} worst {wmc:.3e}; ratios {l1 / max(l1c, 1e-30):.2f} {wm / max(wmc, 1e-30):.2f}")
+        assert l1c <= L1_BF16 and wmc <= MAX_BOUND, (name, l1c, wmc)            # the chain meets the project's bounds
+        assert l1 <= MARGIN * max(l1c, UNIT), (name, l1, l1c)
+        assert wm <= MARGIN * max(wmc, UNIT), (name, wm, wmc)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cd,M,scaled", CASES)
+def test_it_is_the_mx_gradient_not_the_bf16_one(dev, Cd, M, scaled):
+    """On the branch gradient dx1 - dx2 the MX kernel is at least SEPARATION x closer to the MX emulation than the bf16 fused backward is."""
+    if _unserved(Cd):
+        return
+    r = _runs(dev, Cd, M, scaled)
+    bref = r["ref"][0] - r["dx2"]
+    d_mx = l1_rel(r["mx"][0][0][:M].double() - r["dx2"], bref)
+    d_bf16 = l1_rel(r["bf16"][0][:M].double() - r["dx2"], bref)
+    print(f"C={Cd} M={M} row_scale={scaled}: branch gradient distance from the MX emulation: fused MX {d_mx:.3e}, fused bf16 {d_bf16:.3e} "
+          f"({d_bf16 / max(d_mx, 1e-30):.1f} x)")
+    assert d_mx < d_bf16, (d_mx, d_bf16)
+    assert d_bf16 >= SEPARATION * d_mx, (d_mx, d_bf16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cd,M,scaled", CASES)
+def test_deterministic_guarded_and_accumulating(dev, Cd, M, scaled):
+    if _unserved(Cd):
+        return
+    r = _runs(dev, Cd, M, scaled)
+    (a, ag, ab), (b, bg, bb) = r["mx"]
+    assert _guards_intact(a, M) and _guards_intact(b, M)
+    assert torch.equal(a[:M], b[:M])                                             # no atomics on dx1
+    assert all(bool(torch.isfinite(t.float()).all()) for t in (a[:M], ag, ab, bg, bb))
+    # dgamma / dbeta were ADDED to the prefill: taken off, they are the emulation's; left on, they are not
+    _, dg, db = _triple(r["mx"][0], r, M)
+    for got, pre, ref in ((dg, r["pre"][0], r["ref"][1]), (db, r["pre"][1], r["ref"][2])):
+        scale = float(ref.abs().max())
+        assert float((got - ref).abs().max()) <= 0.05 * scale + 1e-5
+        assert float((got + pre - ref).abs().max()) > 0.05 * scale
+
+
+# ---- host switch ------------------------------------------------------------------------------------------------------------------------
+IMGS, RES = 2, 7                 # M = 98: one token tile and one token split of sv_swin_mlp_wgrad, whose float atomics are then order-free
+
+
+def _block(dev, Cd, heads, res=RES):
+    from swinvox_amd.models.swin_transformer import SwinBlock
+    torch.manual_seed(5)
+    blk = SwinBlock(Cd, res, heads, 3, 0.0)
+    g = torch.Generator().manual_seed(6 + Cd)
+    with torch.no_grad():
+        for n, p in blk.named_parameters():
+            if p.dim() == 1:
+                p.copy_((1.0 if "norm" in n and n.endswith("weight") else 0.0) + 0.1 * torch.randn(p.shape, generator=g))
+            elif "bias_table" not in n:
+                p.copy_(torch.randn(p.shape, generator=g) / p.shape[1] ** 0.5)
+    blk.to(dev)
+    M = IMGS * res * res
+    x = torch.randn(M, Cd, generator=g).bfloat16().to(dev)
+    dy = torch.randn(M, Cd, generator=g).bfloat16().to(dev)
+    return blk, x, dy
+
+
+def _counters():
+    return (ops.swin_mlp_mx_bwd_launches(), ops.swin_mlp_mx_launches(), ops.linear_mxfp8_launches(), ops.mx_act_quant_launches()) + ops.linear_mxfp8_bwd_launches()
+
+
+def _delta(a, b):
+    return tuple(y - x for x, y in zip(a, b))
+
+
+@pytest.fixture
+def switches():
+    try:
+        yield
+    finally:
+        ops.set_fused_mlp_mx(False)
+        ops.set_fused_mlp(True)
+        ops.set_pack_cache(None)
+        S.set_linear_fp8(False)
+        S.set_math("f32")
+
+
+def _step(blk, x, dy, spy_list=None):
+    from swinvox_amd.models import swin_transformer as st
+    grads = {p: torch.zeros_like(p, dtype=torch.float32) for p in blk.parameters()}
+    ops.set_pack_cache(ops.PackCache())
+    if spy_list is not None:
+        del spy_list[:]
+    n0 = _counters()
+    x2, ctx = st.block_forward(blk, x, IMGS, True, False, None, True)
+    dx = st.block_backward(blk, ctx, dy.clone(), grads)
+    torch.cuda.synchronize()
+    n = _delta(n0, _counters())
+    assert all(bool(torch.isfinite(g).all()) for g in grads.values())
+    mlp = blk.mlp
+    wg = [grads[p].cpu() for p in (mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)]
+    ln = [grads[p].cpu() for p in (blk.norm2.weight, blk.norm2.bias)]
+    return dict(x2=x2.cpu(), dx=dx.cpu(), ctx=ctx, n=n, wg=wg, ln=ln, packs=len(spy_list) if spy_list is not None else None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cd,heads", [(96, 3), (128, 4)])
+def test_host_switch(dev, monkeypatch, switches, Cd, heads):
+    from swinvox_amd.models import swin_transformer as st
+    blk, x, dy = _block(dev, Cd, heads)
+    bf16_packs = []
+    real_call = st.call
+
+    def spy(name, *a, **k):
+        if name == "sv_swin_mlp_pack":
+            bf16_packs.append(name)
+        return real_call(name, *a, **k)
+
+    monkeypatch.setattr(st, "call", spy)
+    ops.set_math("bf16")
+    ops.set_storage("bf16")
+    S.set_linear_fp8(True, backward=True, recipe="mx", backward_recipe="mx")
+    ops.set_fused_mlp_mx(True)                                                  # the parent's MX training mode: MX forward, bf16 fused backward
+    assert ops.fused_mlp_mx_enabled(Cd) and not ops.fused_mlp_mx_bwd_enabled(Cd)   # off by default
+    off = _step(blk, x, dy, bf16_packs)
+    assert off["n"][0] == 0 and off["n"][1] == 1 and off["packs"] == 1 and off["ctx"][12] is not None
+    ops.set_fused_mlp_mx(True, backward=True)
+    if not _supported(Cd):
+        assert not ops.fused_mlp_mx_bwd_enabled(Cd)                             # the host keeps the bf16 backward
+        same = _step(blk, x, dy, bf16_packs)
+        assert same["n"] == off["n"] and torch.equal(same["dx"], off["dx"])
+        return
+    assert ops.fused_mlp_mx_bwd_enabled(Cd)
+    on = _step(blk, x, dy, bf16_packs)
+    assert on["n"][0] == 1, on["n"]                                             # one sv_swin_mlp_bwd_mx launch per block backward
+    assert on["n"][1:] == off["n"][1:], (on["n"], off["n"])                     # no MX GEMM or activation quantiser launch added for the MLP branch
+    assert on["packs"] == 0 and on["ctx"][12] is None and len(on["ctx"]) == len(off["ctx"]) == 15
+    assert on["ctx"][11] is None                                                # ln2 is None still selects the fused path
+    assert torch.equal(on["x2"], off["x2"])                                     # the forward is the same launch
+    assert all(torch.equal(a, b) for a, b in zip(on["wg"], off["wg"]))          # weight gradients: the same sv_swin_mlp_wgrad launch, bit for bit
+    assert bool(torch.isfinite(on["dx"].float()).all()) and not torch.equal(on["dx"], off["dx"])
+    d = l1_rel(on["dx"].double(), off["dx"].double())
+    dl = max(l1_rel(a.double(), b.double()) for a, b in zip(on["ln"], off["ln"]))
+    print(f"C={Cd}: block dx, fused MX vs fused bf16 data gradient of the MLP: L1-rel {d:.3e}; norm2 gradients {dl:.3e}")
+    assert d < SAME_GRADIENT and dl < SAME_GRADIENT
+    ops.set_fused_mlp_mx(True)                                                  # off again: the parent's launches and dx, bit for bit
+    off2 = _step(blk, x, dy, bf16_packs)
+    assert off2["n"] == off["n"] and off2["packs"] == 1 and torch.equal(off2["dx"], off["dx"])
+    assert all(torch.equal(a, b) for a, b in zip(off2["wg"], off["wg"]))
+
+
+@pytest.mark.gpu
+def test_switch_is_inert_elsewhere(dev, switches):
+    blk, x, dy = _block(dev, 96, 3)
+    ops.set_math("bf16")
+    ops.set_storage("bf16")
+
+    def pair(configure, **blockargs):
+        """the same step with the backward switch off and on under one configuration: equal launches, equal results, counter at rest"""
+        b, xx, dd = _block(dev, **blockargs) if blockargs else (blk, x, dy)
+        Cd = b.dim
+        ops.set_fused_mlp_mx(True)
+        configure()
+        a0 = _step(b, xx, dd)
+        ops.set_fused_mlp_mx(True, backward=True)
+        configure()
+        assert not ops.fused_mlp_mx_bwd_enabled(Cd)
+        a1 = _step(b, xx, dd)
+        assert a1["n"][0] == 0 and a1["n"] == a0["n"], (a0["n"], a1["n"])
+        assert torch.equal(a1["dx"], a0["dx"]) and torch.equal(a1["x2"], a0["x2"])
+        assert (a1["ctx"][12] is None) == (a0["ctx"][12] is None)
+
+    pair(lambda: S.set_linear_fp8(True, backward=True, recipe="mx", backward_recipe="row"))       # the row backward recipe
+    pair(lambda: S.set_linear_fp8(True, backward=False, recipe="mx"))                             # no fp8 backward at all
+    pair(lambda: S.set_linear_fp8(True, backward=True, recipe="row", backward_recipe="mx"))       # the forward switch is inert: so is this one
+    pair(lambda: S.set_linear_fp8(True, backward=True, recipe="mx", backward_recipe="mx"), Cd=192, heads=6)     # C = 192
+    S.set_linear_fp8(True, backward=True, recipe="mx", backward_recipe="mx")
+    ops.set_fused_mlp_mx(False, backward=True)                                                    # the forward switch off
+    assert not ops.fused_mlp_mx_bwd_enabled(96)
+    n0 = _counters()
+    b0 = _step(blk, x, dy)
+    ops.set_fused_mlp_mx(False)
+    b1 = _step(blk, x, dy)
+    assert _delta(n0, _counters())[0] == 0 and torch.equal(b0["dx"], b1["dx"])
+    ops.set_fused_mlp_mx(True, backward=True)
+    ops.set_math("f32")                                                                           # f32 math (and with it f32 storage)
+    assert not ops.fused_mlp_mx_bwd_enabled(96) and not ops.fused_mlp_mx_enabled(96)
+    c1 = _step(blk, x.float(), dy.float())
+    ops.set_fused_mlp_mx(False)
+    c0 = _step(blk, x.float(), dy.float())
+    assert c1["n"][0] == 0 and c1["n"] == c0["n"] and torch.equal(c1["dx"], c0["dx"])
