@@ -711,17 +711,48 @@ static inline bool mlp_supported(int C) { return C == 96 || C == 128 || C == 192
 //                 8 x 1 - two waves per SIMD, so the GELU / quantiser VALU stream of one runs beside the MFMAs and LDS reads of the other.  With
 //                 NTT = 2 an A fragment read serves two MFMAs, but 4 x 2 leaves one wave per SIMD and 8 x 2 is slower than 8 x 1.
 // Pack image (sv_swin_mlp_mx_pack, bytes):  W1F [G][8 tiles][2 halves][64 lanes][16] | W2F [G][C/16][2][64][16] | W1S [G][8][64] | W2S [G][C/16][64],  G = 4C / 128.
+// The data gradient (swin_mlp_bwd_mx_kernel) runs the same pieces through the same code: MxImages / mx_pack_hidden_rows / mx_pack_channel_rows (the two
+// kinds of image and the only copy of the hidden-unit order), mx_a_frag / mx_a_scale (A fragment read), mx_layernorm (prologue), mx_quant_frag (token
+// rows -> B fragment) and mx_quant_acc (accumulator tiles -> elementwise operation -> B fragment).
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-template <int C> struct MlpMx {
-  static constexpr int HID = 4 * C, G = HID / 128, NJ = C / 16;
-  static constexpr int W1F = 0, W1F_BYTES = HID * 128;
-  static constexpr int W2F = W1F_BYTES, W2F_BYTES = C * HID;
-  static constexpr int W1S = W2F + W2F_BYTES, W1S_BYTES = G * 8 * 64;
-  static constexpr int W2S = W1S + W1S_BYTES, W2S_BYTES = G * NJ * 64;
-  static constexpr int PACK_BYTES = W2S + W2S_BYTES;
+// The two kinds of image a pack is made of, for width C (usable at compile time and, in the pack kernels and on the host, at run time).  A
+// "hidden-row" image holds a [4C][128] operand (W1, W2^T) as [G][8 tiles][2][64][16] bytes + [G][8][64] scale bytes, a "channel-row" image a [C][4C]
+// operand (W2, W1^T) as [G][C/16 tiles][2][64][16] + [G][C/16][64].  Either has one pack item per (tile, lane): two 16-byte pieces and one scale byte.
+struct MxImages {
+  int HID, G, NJ;
+  int HROW_DATA, HROW_SCALES, CROW_DATA, CROW_SCALES;      // bytes; the SCALES counts are the item counts too
+  constexpr explicit MxImages(int C)
+      : HID(4 * C), G(HID / 128), NJ(C / 16), HROW_DATA(HID * 128), HROW_SCALES(G * 8 * 64), CROW_DATA(C * HID), CROW_SCALES(G * NJ * 64) {}
 };
+
+struct MlpMx : MxImages {                                  // the forward's pack: W1F | W2F | W1S | W2S
+  int W1F, W2F, W1S, W2S, PACK_BYTES, PACK_ITEMS;
+  constexpr explicit MlpMx(int C)
+      : MxImages(C), W1F(0), W2F(W1F + HROW_DATA), W1S(W2F + CROW_DATA), W2S(W1S + HROW_SCALES), PACK_BYTES(W2S + CROW_SCALES),
+        PACK_ITEMS(HROW_SCALES + CROW_SCALES) {}
+};
+
+// item e = (tile, lane) of an image: the lane's two 16-byte halves (k = 16 lg .. and 64 + 16 lg .. of the row's 128-wide k-step at `src`) and its scale byte
+__device__ __forceinline__ void mx_pack_item(const uint8_t* src, uint8_t scale, uint8_t* data, uint8_t* scales, int e) {
+  i32x4* d = reinterpret_cast<i32x4*>(data) + (e >> 6) * 128 + (e & 63);
+  d[0] = *reinterpret_cast<const i32x4*>(src);
+  d[64] = *reinterpret_cast<const i32x4*>(src + 64);
+  scales[e] = scale;
+}
+// hidden-row image of q [4C][128], s [4C][4].  The ONLY copy of the hidden-unit order: tile j, row r of group g is hidden unit `hid`
+__device__ __forceinline__ void mx_pack_hidden_rows(const uint8_t* q, const uint8_t* s, uint8_t* data, uint8_t* scales, int e) {
+  const int lane = e & 63, j = (e >> 6) & 7, g = e >> 9, r = lane & 15, lg = lane >> 4;
+  const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
+  mx_pack_item(q + (size_t)hid * 128 + 16 * lg, s[hid * 4 + lg], data, scales, e);
+}
+// channel-row image of q [C][4C], s [C][4C / 32]: tile jc, row r is channel 16 jc + r, k-step g its hidden units 128 g .. + 127
+__device__ __forceinline__ void mx_pack_channel_rows(const uint8_t* q, const uint8_t* s, uint8_t* data, uint8_t* scales, int e, const MxImages& I) {
+  const int lane = e & 63, t = e >> 6, jc = t % I.NJ, g = t / I.NJ, r = lane & 15, lg = lane >> 4;
+  const int row = 16 * jc + r;
+  mx_pack_item(q + (size_t)row * I.HID + 128 * g + 16 * lg, s[row * (I.HID / 32) + 4 * g + lg], data, scales, e);
+}
 
 struct MlpMxArgs {
   const __bf16* x1; __bf16* out;
@@ -734,24 +765,10 @@ struct MlpMxArgs {
 
 __global__ __launch_bounds__(256) void swin_mlp_mx_pack_kernel(const uint8_t* __restrict__ w1q, const uint8_t* __restrict__ w1s, const uint8_t* __restrict__ w2q,
                                                                const uint8_t* __restrict__ w2s, uint8_t* __restrict__ packs, int C) {
-  const int HID = 4 * C, G = HID / 128, NJ = C / 16;
-  const int n1 = HID * 128 / 16, n2 = C * HID / 16, n3 = G * 8 * 64, n4 = G * NJ * 64;     // 16-byte pieces, then scale bytes
+  const MlpMx L(C);
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx < n1) {
-    const int lane = idx & 63, hf = (idx >> 6) & 1, j = (idx >> 7) & 7, g = idx >> 10, r = lane & 15, lg = lane >> 4;
-    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
-    reinterpret_cast<i32x4*>(packs)[idx] = *reinterpret_cast<const i32x4*>(w1q + (size_t)hid * 128 + 64 * hf + 16 * lg);
-  } else if (idx < n1 + n2) {
-    const int e = idx - n1, lane = e & 63, hf = (e >> 6) & 1, t = e >> 7, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
-    reinterpret_cast<i32x4*>(packs)[idx] = *reinterpret_cast<const i32x4*>(w2q + (size_t)(16 * jc + r) * HID + 128 * g + 64 * hf + 16 * lg);
-  } else if (idx < n1 + n2 + n3) {
-    const int e = idx - n1 - n2, lane = e & 63, j = (e >> 6) & 7, g = e >> 9, r = lane & 15, lg = lane >> 4;
-    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
-    packs[(size_t)(n1 + n2) * 16 + e] = w1s[hid * 4 + lg];
-  } else if (idx < n1 + n2 + n3 + n4) {
-    const int e = idx - n1 - n2 - n3, lane = e & 63, t = e >> 6, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
-    packs[(size_t)(n1 + n2) * 16 + n3 + e] = w2s[(16 * jc + r) * (HID / 32) + 4 * g + lg];
-  }
+  if (idx < L.HROW_SCALES) mx_pack_hidden_rows(w1q, w1s, packs + L.W1F, packs + L.W1S, idx);
+  else if (idx < L.PACK_ITEMS) mx_pack_channel_rows(w2q, w2s, packs + L.W2F, packs + L.W2S, idx - L.HROW_SCALES, L);
 }
 
 // maximum of a lane's value and that of lane ^ 16 (the other half of a 32-element MX block)
@@ -764,68 +781,120 @@ __device__ __forceinline__ int mx_lane_scale(int elo, int ehi, int lane) {
   return (got >> (8 * (lg >> 1))) & 0xff;
 }
 
+// a token's 16 + 16 values (registers 0-3 / 4-7 of a 128-wide k-step; already rounded to bf16) -> MX B fragment + the scale byte the lane passes
+__device__ __forceinline__ void mx_quant_frag(const float (&v)[2][16], i32x8& q, int& sbyte, int lane) {
+  int e[2];
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(v[hf][j]));
+    e[hf] = mx_block_exp(pair16_max(m));
+#pragma unroll
+    for (int w = 0; w < 4; ++w) q[4 * hf + w] = (int)pack4_e4m3_mx(v[hf][4 * w], v[hf][4 * w + 1], v[hf][4 * w + 2], v[hf][4 * w + 3], e[hf]);
+  }
+  sbyte = mx_lane_scale(e[0], e[1], lane);
+}
+// a token's eight accumulator tiles of a group (tile j = 4 hf + jj: hidden units 64 hf + 16 lg + 4 jj .. + 3) -> MX B fragment of k-step g of the next
+// product + the scale byte the lane passes.  elem(j) returns tile j's four values after the elementwise operation, rounded to bf16.
+template <class Elem>
+__device__ __forceinline__ void mx_quant_acc(Elem elem, i32x8& q, int& sbyte, int lane) {
+  int e[2];
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    f32x4 v[4];
+    float m = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      v[jj] = elem(4 * hf + jj);
+      m = fmaxf(fmaxf(m, fmaxf(fabsf(v[jj][0]), fabsf(v[jj][1]))), fmaxf(fabsf(v[jj][2]), fabsf(v[jj][3])));
+    }
+    e[hf] = mx_block_exp(pair16_max(m));
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) q[4 * hf + jj] = (int)pack4_e4m3_mx(v[jj][0], v[jj][1], v[jj][2], v[jj][3], e[hf]);
+  }
+  sbyte = mx_lane_scale(e[0], e[1], lane);
+}
+// A fragment of row tile `tile` of an image: two 16-byte reads at + 0 / + 1024 (ds_read_b128 where `data` is in LDS, global loads where it is the
+// pack in memory: the address space is inferred) - and its scale byte
+__device__ __forceinline__ i32x8 mx_a_frag(const uint8_t* data, int tile, int lane) {
+  const uint8_t* fa = data + (size_t)(tile * 2) * 1024 + lane * 16;
+  const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
+  return (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+__device__ __forceinline__ int mx_a_scale(const uint8_t* scales, int tile, int lane) { return scales[tile * 64 + lane]; }
+
+// LayerNorm prologue of lane (t, lg): the 16 + 16 channels 64 hf + 16 lg .. + 15 of token `tok` (zero for an invalid token and for the padding of
+// C = 96) -> xv = LayerNorm in fp32, rounded to bf16 as the unfused chain stores it; mean and rstd of the row.  The backward (WITH_DX2) passes dx2
+// as well: dv = bf16(dsc dx2) of the same channels, loaded under the same guard (sv_rowscale's value).
+template <int C, bool WITH_DX2>
+__device__ __forceinline__ void mx_layernorm(const __bf16* x1, long long tok, bool valid, int lg, const float* sgam, const float* sbet, float eps,
+                                             float (&xv)[2][16], float& mean, float& rstd, const __bf16* dx2 = nullptr, float dsc = 1.f,
+                                             float (*dv)[16] = nullptr) {
+  const bool hi_live = 64 + 16 * lg < C;                   // C = 96: channels 96 .. 127 are padding
+  float s = 0.f;
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      bf16x8 raw = VecN<__bf16, 8>::zero(), dr = VecN<__bf16, 8>::zero();
+      if (valid && (hf == 0 || hi_live)) {
+        raw = *reinterpret_cast<const bf16x8*>(x1 + tok * C + 64 * hf + 16 * lg + 8 * u);
+        if constexpr (WITH_DX2) dr = *reinterpret_cast<const bf16x8*>(dx2 + tok * C + 64 * hf + 16 * lg + 8 * u);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        xv[hf][8 * u + j] = (float)raw[j]; s += xv[hf][8 * u + j];
+        if constexpr (WITH_DX2) dv[hf][8 * u + j] = (float)(__bf16)(dsc * (float)dr[j]);
+      }
+    }
+  s = lane_step_add<16>(s); s = lane_step_add<32>(s);
+  mean = s * (1.f / C);
+  float q = 0.f;
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf)
+    if (hf == 0 || hi_live)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { const float d = xv[hf][j] - mean; q += d * d; }
+  q = lane_step_add<16>(q); q = lane_step_add<32>(q);
+  rstd = rsqrtf(q * (1.f / C) + eps);
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    const bool live = hf == 0 || hi_live;
+    const int c0 = live ? 64 * hf + 16 * lg : 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      xv[hf][j] = live ? (float)(__bf16)((xv[hf][j] - mean) * rstd * sgam[c0 + j] + sbet[c0 + j]) : 0.f;
+  }
+}
+
 template <int C, int NW, int NTT>
 __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_fwd_mx_kernel(const MlpMxArgs p) {
-  typedef MlpMx<C> L;
-  constexpr int HID = L::HID, G = L::G, NJ = L::NJ, NT = NW * 64, TILE = NW * NTT * 16;
-  __shared__ __attribute__((aligned(16))) uint8_t smem[L::PACK_BYTES + (HID + 2 * C) * 4];
-  float* sb1 = reinterpret_cast<float*>(smem + L::PACK_BYTES);
+  constexpr MlpMx L(C);
+  constexpr int HID = L.HID, G = L.G, NJ = L.NJ, NT = NW * 64, TILE = NW * NTT * 16;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[L.PACK_BYTES + (HID + 2 * C) * 4];
+  float* sb1 = reinterpret_cast<float*>(smem + L.PACK_BYTES);
   float* sgam = sb1 + HID;
   float* sbet = sgam + C;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = lane & 15, lg = lane >> 4;
-  for (int i = tid; i < L::PACK_BYTES / 16; i += NT) reinterpret_cast<i32x4*>(smem)[i] = reinterpret_cast<const i32x4*>(p.packs)[i];
+  for (int i = tid; i < L.PACK_BYTES / 16; i += NT) reinterpret_cast<i32x4*>(smem)[i] = reinterpret_cast<const i32x4*>(p.packs)[i];
   for (int i = tid; i < HID; i += NT) sb1[i] = p.b1[i];
   for (int i = tid; i < C; i += NT) { sgam[i] = p.ln_g[i]; sbet[i] = p.ln_b[i]; }
   __syncthreads();
-  const bool hi_live = 64 + 16 * lg < C;                   // C = 96: channels 96 .. 127 are padding
 
 #pragma unroll 1
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     long long tok[NTT]; bool valid[NTT];
     i32x8 xq[NTT]; int xsb[NTT];
-    // ---- LayerNorm (fp32, rounded to bf16 as the unfused chain stores it) -> MX B fragments of fc1
+    // ---- LayerNorm -> MX B fragments of fc1
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
       tok[tt] = (long long)tile * TILE + wave * (NTT * 16) + tt * 16 + t;
       valid[tt] = tok[tt] < p.M;
-      float xv[2][16];
-      float s = 0.f;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          bf16x8 raw = VecN<__bf16, 8>::zero();
-          if (valid[tt] && (hf == 0 || hi_live)) raw = *reinterpret_cast<const bf16x8*>(p.x1 + tok[tt] * C + 64 * hf + 16 * lg + 8 * u);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { xv[hf][8 * u + j] = (float)raw[j]; s += xv[hf][8 * u + j]; }
-        }
-      s = lane_step_add<16>(s); s = lane_step_add<32>(s);
-      const float mean = s * (1.f / C);
-      float q = 0.f;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf)
-        if (hf == 0 || hi_live)
-#pragma unroll
-          for (int j = 0; j < 16; ++j) { const float d = xv[hf][j] - mean; q += d * d; }
-      q = lane_step_add<16>(q); q = lane_step_add<32>(q);
-      const float rstd = rsqrtf(q * (1.f / C) + p.eps);
-      int e[2];
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const bool live = hf == 0 || hi_live;
-        const int c0 = live ? 64 * hf + 16 * lg : 0;
-        float m = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const float v = live ? (float)(__bf16)((xv[hf][j] - mean) * rstd * sgam[c0 + j] + sbet[c0 + j]) : 0.f;
-          xv[hf][j] = v; m = fmaxf(m, fabsf(v));
-        }
-        e[hf] = mx_block_exp(pair16_max(m));
-#pragma unroll
-        for (int w = 0; w < 4; ++w) xq[tt][4 * hf + w] = (int)pack4_e4m3_mx(xv[hf][4 * w], xv[hf][4 * w + 1], xv[hf][4 * w + 2], xv[hf][4 * w + 3], e[hf]);
-      }
-      xsb[tt] = mx_lane_scale(e[0], e[1], lane);
+      float xv[2][16], mean, rstd;
+      mx_layernorm<C, false>(p.x1, tok[tt], valid[tt], lg, sgam, sbet, p.eps, xv, mean, rstd);
+      mx_quant_frag(xv, xq[tt], xsb[tt], lane);
     }
 
     f32x4 acc2[NJ][NTT];
@@ -840,48 +909,28 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_fwd_mx_kernel(const MlpMx
       f32x4 acc1[8][NTT];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const uint8_t* fa = smem + L::W1F + (size_t)((g * 8 + j) * 2) * 1024 + lane * 16;
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
-        const i32x8 a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        const int sa = smem[L::W1S + (g * 8 + j) * 64 + lane];
+        const i32x8 a = mx_a_frag(smem + L.W1F, g * 8 + j, lane);
+        const int sa = mx_a_scale(smem + L.W1S, g * 8 + j, lane);
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt)
           acc1[j][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, xq[tt], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, sa, 0, xsb[tt]);
       }
-      // ---- + b1, GELU, bf16, MX quantisation in registers: the accumulators become the B fragment of fc2's k-step g
+      // ---- h = bf16(GELU(acc1 + b1)), MX quantisation in registers: the accumulators become the B fragment of fc2's k-step g
       i32x8 hq[NTT]; int hsb[NTT];
+      const float* gb1 = sb1 + 128 * g + 16 * lg;          // the lane's biases: tile j = 4 hf + jj at + 64 hf + 4 jj
 #pragma unroll
-      for (int tt = 0; tt < NTT; ++tt) {
-        int e[2];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          float m = 0.f;
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int j = 4 * hf + jj;
-            const float4 bi = *reinterpret_cast<const float4*>(sb1 + 128 * g + 64 * hf + 16 * lg + 4 * jj);
-            const f32x2 g0 = gelu_fast2((f32x2){acc1[j][tt][0] + bi.x, acc1[j][tt][1] + bi.y});
-            const f32x2 g1 = gelu_fast2((f32x2){acc1[j][tt][2] + bi.z, acc1[j][tt][3] + bi.w});
-            acc1[j][tt][0] = (float)(__bf16)g0[0]; acc1[j][tt][1] = (float)(__bf16)g0[1];
-            acc1[j][tt][2] = (float)(__bf16)g1[0]; acc1[j][tt][3] = (float)(__bf16)g1[1];
-            m = fmaxf(fmaxf(m, fmaxf(fabsf(acc1[j][tt][0]), fabsf(acc1[j][tt][1]))), fmaxf(fabsf(acc1[j][tt][2]), fabsf(acc1[j][tt][3])));
-          }
-          e[hf] = mx_block_exp(pair16_max(m));
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int j = 4 * hf + jj;
-            hq[tt][j] = (int)pack4_e4m3_mx(acc1[j][tt][0], acc1[j][tt][1], acc1[j][tt][2], acc1[j][tt][3], e[hf]);
-          }
-        }
-        hsb[tt] = mx_lane_scale(e[0], e[1], lane);
-      }
+      for (int tt = 0; tt < NTT; ++tt)
+        mx_quant_acc([&](int j) {
+          const float4 bi = *reinterpret_cast<const float4*>(gb1 + 64 * (j >> 2) + 4 * (j & 3));
+          const f32x2 g0 = gelu_fast2((f32x2){acc1[j][tt][0] + bi.x, acc1[j][tt][1] + bi.y});
+          const f32x2 g1 = gelu_fast2((f32x2){acc1[j][tt][2] + bi.z, acc1[j][tt][3] + bi.w});
+          return (f32x4){(float)(__bf16)g0[0], (float)(__bf16)g0[1], (float)(__bf16)g1[0], (float)(__bf16)g1[1]};
+        }, hq[tt], hsb[tt], lane);
       // ---- fc2: k-step g
 #pragma unroll
       for (int jc = 0; jc < NJ; ++jc) {
-        const uint8_t* fa = smem + L::W2F + (size_t)((g * NJ + jc) * 2) * 1024 + lane * 16;
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
-        const i32x8 a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        const int sa = smem[L::W2S + (g * NJ + jc) * 64 + lane];
+        const i32x8 a = mx_a_frag(smem + L.W2F, g * NJ + jc, lane);
+        const int sa = mx_a_scale(smem + L.W2S, g * NJ + jc, lane);
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt)
           acc2[jc][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, hq[tt], acc2[jc][tt], 0, 0, 0, sa, 0, hsb[tt]);
@@ -909,18 +958,19 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_fwd_mx_kernel(const MlpMx
 }
 
 static inline bool mlp_mx_supported(int C) { return C == 96 || C == 128; }
-static inline long long mlp_mx_pack_bytes(int C) { return C == 96 ? MlpMx<96>::PACK_BYTES : C == 128 ? MlpMx<128>::PACK_BYTES : 0; }
+static inline long long mlp_mx_pack_bytes(int C) { return mlp_mx_supported(C) ? MlpMx(C).PACK_BYTES : 0; }
 
 // ---- MXFP8 data gradient (opt-in sibling of swin_mlp_bwd_kernel; sv_swin_mlp_bwd_mx) ---------------------------------------------------
 // The unfused MX backward chain of the branch composed in one kernel: sv_rowscale -> row quantiser of dy -> sv_linear_mxfp8_dgrad (fc2, GELU' at the
 // stored pre-activation) -> row quantiser of dh -> sv_linear_mxfp8_dgrad (fc1) -> sv_layernorm_bwd (+ residual).  The pre-activation is RECOMPUTED as
 // swin_mlp_fwd_mx_kernel computes it (quantising LayerNorm, fc1 on the forward's W1 MX rows, bf16(acc + b1)), so GELU' is evaluated where the MX
-// forward evaluated GELU.  Neither dy's MX rows, hpre nor dh reach HBM.  Same NORMATIVE recipe (linear_fp8.hip "MX recipe"), same lane maps as the forward:
+// forward evaluated GELU.  Neither dy's MX rows, hpre nor dh reach HBM.  Same NORMATIVE recipe (linear_fp8.hip "MX recipe"); the lane maps, the image
+// kinds and the helpers that carry them are the forward's (see its comment) - described here is what this kernel does with them:
 //   recompute     acc1[j] = W1 row tile j of group g . LN(x)_q: lane (t, lg) holds hidden units 128 g + 64 hf + 16 lg + 4 jj + i (j = 4 hf + jj).
 //   fc2 dgrad     accd[j] = W2^T row tile j . dy_q: the W2^T image ([4C][Np = 128], quantize_weight_t_mx(fc2.weight)) has W1's shape and is tiled in W1's
 //                 row order, so accd and acc1 hold the same hidden units element for element; dy is quantised as LN(x) is (blocks of 32 channels).
 //                 dh = bf16(accd * gelu_grad_fast(bf16(acc1 + b1))) is, without lane movement, the lane's B fragment of k-step g of the next product;
-//                 a hardware block = 32 consecutive hidden units over lanes lg and lg ^ 1 (pair16_max, mx_lane_scale as in the forward).
+//                 it goes through mx_quant_acc as the forward's h does.
 //   fc1 dgrad     dln[jc] += W1^T row tile jc (channels 16 jc + r; [C][4C], quantize_weight_t_mx(fc1.weight): W2's shape, W2's fragment order) . dh_q.
 //   epilogue      swin_mlp_bwd_kernel's LayerNorm backward + residual on bf16(dln); lane (t, lg) owns channels 16 jc + 4 lg .. + 3 of token t: the row
 //                 sums s1, s2 cross the four lane groups, dgamma / dbeta are sums over the 16 token lanes of a DPP row (row_shr 1/2/4/8), then LDS
@@ -928,19 +978,15 @@ static inline long long mlp_mx_pack_bytes(int C) { return C == 96 ? MlpMx<96>::P
 //   weights       C = 96: all three images resident in LDS (139 KB with the scales).  C = 128: W1 and W2^T resident, the W1^T fragments of a group are
 //                 16-byte loads from L2 issued in front of the GELU' block (3 x 64 KB do not fit; staging the slice through a 16-KB LDS buffer costs two
 //                 workgroup barriers per group and measured 1.28 ms against 1.18 ms).  One persistent workgroup per CU.
-// Pack image (sv_swin_mlp_bwd_mx_pack, bytes):  W1F [G][8][2][64][16] | W2TF (same) | W1S [G][8][64] | W2TS (same) | W1TS [G][C/16][64] | W1TF [G][C/16][2][64][16];
-// everything in front of W1TF is resident for either C.
-template <int C> struct MlpMxB {
-  static constexpr int HID = 4 * C, G = HID / 128, NJ = C / 16;
-  static constexpr int W1F = 0, ROWF_BYTES = HID * 128;
-  static constexpr int W2TF = W1F + ROWF_BYTES;
-  static constexpr int W1S = W2TF + ROWF_BYTES, ROWS_BYTES = G * 8 * 64;
-  static constexpr int W2TS = W1S + ROWS_BYTES;
-  static constexpr int W1TS = W2TS + ROWS_BYTES, W1TS_BYTES = G * NJ * 64;
-  static constexpr int W1TF = W1TS + W1TS_BYTES, W1TF_BYTES = C * HID;
-  static constexpr int PACK_BYTES = W1TF + W1TF_BYTES;
-  static constexpr bool RESIDENT = C <= 96;                // W1TF in LDS as well
-  static constexpr int LDS_BYTES = RESIDENT ? PACK_BYTES : W1TF;
+// Pack image (sv_swin_mlp_bwd_mx_pack, bytes):  W1F [G][8][2][64][16] | W2TF (same) | W1S [G][8][64] | W2TS (same) | W1TS [G][C/16][64] | W1TF [G][C/16][2][64][16]:
+// two hidden-row images (W1, W2^T), then one channel-row image (W1^T), its scales first; everything in front of W1TF is resident for either C.
+struct MlpMxB : MxImages {
+  int W1F, W2TF, W1S, W2TS, W1TS, W1TF, PACK_BYTES, PACK_ITEMS;
+  bool RESIDENT;                                           // W1TF in LDS as well
+  int LDS_BYTES;
+  constexpr explicit MlpMxB(int C)
+      : MxImages(C), W1F(0), W2TF(W1F + HROW_DATA), W1S(W2TF + HROW_DATA), W2TS(W1S + HROW_SCALES), W1TS(W2TS + HROW_SCALES), W1TF(W1TS + CROW_SCALES),
+        PACK_BYTES(W1TF + CROW_DATA), PACK_ITEMS(2 * HROW_SCALES + CROW_SCALES), RESIDENT(C <= 96), LDS_BYTES(RESIDENT ? PACK_BYTES : W1TF) {}
 };
 
 struct MlpMxBArgs {
@@ -956,50 +1002,13 @@ struct MlpMxBArgs {
 __global__ __launch_bounds__(256) void swin_mlp_bwd_mx_pack_kernel(const uint8_t* __restrict__ w1q, const uint8_t* __restrict__ w1s, const uint8_t* __restrict__ w2tq,
                                                                    const uint8_t* __restrict__ w2ts, const uint8_t* __restrict__ w1tq, const uint8_t* __restrict__ w1ts,
                                                                    uint8_t* __restrict__ packs, int C) {
-  const int HID = 4 * C, G = HID / 128, NJ = C / 16;
-  const int nA = HID * 128 / 16, nS = G * 8 * 64, nST = G * NJ * 64, nT = C * HID / 16;     // 16-byte pieces of a row-tile image, scale bytes, pieces of W1TF
-  int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx < 2 * nA) {                                      // W1F, W2TF: the forward's W1 row order
-    const int im = idx / nA, e = idx % nA, lane = e & 63, hf = (e >> 6) & 1, j = (e >> 7) & 7, g = e >> 10, r = lane & 15, lg = lane >> 4;
-    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
-    reinterpret_cast<i32x4*>(packs)[idx] = *reinterpret_cast<const i32x4*>((im ? w2tq : w1q) + (size_t)hid * 128 + 64 * hf + 16 * lg);
-    return;
-  }
-  idx -= 2 * nA;
-  uint8_t* sb = packs + (size_t)2 * nA * 16;
-  if (idx < 2 * nS) {
-    const int im = idx / nS, e = idx % nS, lane = e & 63, j = (e >> 6) & 7, g = e >> 9, r = lane & 15, lg = lane >> 4;
-    const int hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3);
-    sb[idx] = (im ? w2ts : w1s)[hid * 4 + lg];
-    return;
-  }
-  idx -= 2 * nS; sb += 2 * nS;
-  if (idx < nST) {                                         // W1TS: the forward's W2 order
-    const int lane = idx & 63, t = idx >> 6, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
-    sb[idx] = w1ts[(16 * jc + r) * (HID / 32) + 4 * g + lg];
-    return;
-  }
-  idx -= nST; sb += nST;
-  if (idx < nT) {
-    const int lane = idx & 63, hf = (idx >> 6) & 1, t = idx >> 7, jc = t % NJ, g = t / NJ, r = lane & 15, lg = lane >> 4;
-    reinterpret_cast<i32x4*>(sb)[idx] = *reinterpret_cast<const i32x4*>(w1tq + (size_t)(16 * jc + r) * HID + 128 * g + 64 * hf + 16 * lg);
-  }
+  const MlpMxB L(C);
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < L.HROW_SCALES) mx_pack_hidden_rows(w1q, w1s, packs + L.W1F, packs + L.W1S, idx);
+  else if (idx < 2 * L.HROW_SCALES) mx_pack_hidden_rows(w2tq, w2ts, packs + L.W2TF, packs + L.W2TS, idx - L.HROW_SCALES);
+  else if (idx < L.PACK_ITEMS) mx_pack_channel_rows(w1tq, w1ts, packs + L.W1TF, packs + L.W1TS, idx - 2 * L.HROW_SCALES, L);
 }
 
-// a token's 16 + 16 values (registers 0-3 / 4-7 of a 128-wide k-step; already rounded to bf16) -> MX B fragment + the scale byte the lane passes
-__device__ __forceinline__ void mx_quant_frag(const float (&v)[2][16], i32x8& q, int& sbyte, int lane) {
-  int e[2];
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    float m = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(v[hf][j]));
-    e[hf] = mx_block_exp(pair16_max(m));
-#pragma unroll
-    for (int w = 0; w < 4; ++w) q[4 * hf + w] = (int)pack4_e4m3_mx(v[hf][4 * w], v[hf][4 * w + 1], v[hf][4 * w + 2], v[hf][4 * w + 3], e[hf]);
-  }
-  sbyte = mx_lane_scale(e[0], e[1], lane);
-}
 // total over the 16 lanes of a DPP row, in lane 15 of the row
 __device__ __forceinline__ float row16_total(float v) {
   v += dpp_shift<0x111, 0xf>(v);   // row_shr:1
@@ -1011,21 +1020,20 @@ __device__ __forceinline__ float row16_total(float v) {
 
 template <int C, int NW, int NTT>
 __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_bwd_mx_kernel(const MlpMxBArgs p) {
-  typedef MlpMxB<C> L;
-  constexpr int HID = L::HID, G = L::G, NJ = L::NJ, NT = NW * 64, TILE = NW * NTT * 16;
-  __shared__ __attribute__((aligned(16))) uint8_t smem[L::LDS_BYTES + (HID + 4 * C) * 4];
-  float* sb1 = reinterpret_cast<float*>(smem + L::LDS_BYTES);
+  constexpr MlpMxB L(C);
+  constexpr int HID = L.HID, G = L.G, NJ = L.NJ, NT = NW * 64, TILE = NW * NTT * 16;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[L.LDS_BYTES + (HID + 4 * C) * 4];
+  float* sb1 = reinterpret_cast<float*>(smem + L.LDS_BYTES);
   float* sdg = sb1 + HID;
   float* sdb = sdg + C;
   float* sgam = sdb + C;                                   // LayerNorm parameters in LDS: see swin_mlp_bwd_kernel
   float* sbet = sgam + C;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = lane & 15, lg = lane >> 4;
-  for (int i = tid; i < L::LDS_BYTES / 16; i += NT) reinterpret_cast<i32x4*>(smem)[i] = reinterpret_cast<const i32x4*>(p.packs)[i];
+  for (int i = tid; i < L.LDS_BYTES / 16; i += NT) reinterpret_cast<i32x4*>(smem)[i] = reinterpret_cast<const i32x4*>(p.packs)[i];
   for (int i = tid; i < HID; i += NT) sb1[i] = p.b1[i];
   for (int i = tid; i < C; i += NT) { sdg[i] = 0.f; sdb[i] = 0.f; sgam[i] = p.ln_g[i]; sbet[i] = p.ln_b[i]; }
   __syncthreads();
-  const bool hi_live = 64 + 16 * lg < C;                   // C = 96: channels 96 .. 127 are padding
 
 #pragma unroll 1
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
@@ -1039,40 +1047,7 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_bwd_mx_kernel(const MlpMx
       valid[tt] = tok[tt] < p.M;
       const float sc = (valid[tt] && p.row_scale) ? p.row_scale[tok[tt] / p.rows_per_scale] : 1.f;
       float xv[2][16], dv[2][16];
-      float s = 0.f;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          bf16x8 raw = VecN<__bf16, 8>::zero(), dr = VecN<__bf16, 8>::zero();
-          if (valid[tt] && (hf == 0 || hi_live)) {
-            raw = *reinterpret_cast<const bf16x8*>(p.x1 + tok[tt] * C + 64 * hf + 16 * lg + 8 * u);
-            dr = *reinterpret_cast<const bf16x8*>(p.dx2 + tok[tt] * C + 64 * hf + 16 * lg + 8 * u);
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            xv[hf][8 * u + j] = (float)raw[j]; s += xv[hf][8 * u + j];
-            dv[hf][8 * u + j] = (float)(__bf16)(sc * (float)dr[j]);
-          }
-        }
-      s = lane_step_add<16>(s); s = lane_step_add<32>(s);
-      mean[tt] = s * (1.f / C);
-      float q = 0.f;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf)
-        if (hf == 0 || hi_live)
-#pragma unroll
-          for (int j = 0; j < 16; ++j) { const float d = xv[hf][j] - mean[tt]; q += d * d; }
-      q = lane_step_add<16>(q); q = lane_step_add<32>(q);
-      rstd[tt] = rsqrtf(q * (1.f / C) + p.eps);
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const bool live = hf == 0 || hi_live;
-        const int c0 = live ? 64 * hf + 16 * lg : 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          xv[hf][j] = live ? (float)(__bf16)((xv[hf][j] - mean[tt]) * rstd[tt] * sgam[c0 + j] + sbet[c0 + j]) : 0.f;
-      }
+      mx_layernorm<C, true>(p.x1, tok[tt], valid[tt], lg, sgam, sbet, p.eps, xv, mean[tt], rstd[tt], p.dx2, sc, dv);
       mx_quant_frag(xv, xq[tt], xsb[tt], lane);
       mx_quant_frag(dv, dq[tt], dsb[tt], lane);
     }
@@ -1089,12 +1064,8 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_bwd_mx_kernel(const MlpMx
       f32x4 acc1[8][NTT], accd[8][NTT];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const uint8_t* fa = smem + L::W1F + (size_t)((g * 8 + j) * 2) * 1024 + lane * 16;
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
-        const i32x4 tlo = *reinterpret_cast<const i32x4*>(fa + L::W2TF), thi = *reinterpret_cast<const i32x4*>(fa + L::W2TF + 1024);
-        const i32x8 a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        const i32x8 at = (i32x8){tlo[0], tlo[1], tlo[2], tlo[3], thi[0], thi[1], thi[2], thi[3]};
-        const int sa = smem[L::W1S + (g * 8 + j) * 64 + lane], sat = smem[L::W2TS + (g * 8 + j) * 64 + lane];
+        const i32x8 a = mx_a_frag(smem + L.W1F, g * 8 + j, lane), at = mx_a_frag(smem + L.W2TF, g * 8 + j, lane);
+        const int sa = mx_a_scale(smem + L.W1S, g * 8 + j, lane), sat = mx_a_scale(smem + L.W2TS, g * 8 + j, lane);
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
           acc1[j][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, xq[tt], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, sa, 0, xsb[tt]);
@@ -1102,54 +1073,30 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_bwd_mx_kernel(const MlpMx
         }
       }
       // W1^T fragments of the group that are not resident (C = 128): requested here, they arrive under the GELU' block
-      i32x8 wt[L::RESIDENT ? 1 : NJ];
-      if constexpr (!L::RESIDENT) {
+      i32x8 wt[L.RESIDENT ? 1 : NJ];
+      if constexpr (!L.RESIDENT) {
 #pragma unroll
-        for (int jc = 0; jc < NJ; ++jc) {
-          const uint8_t* fa = p.packs + L::W1TF + (size_t)((g * NJ + jc) * 2) * 1024 + lane * 16;
-          const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
-          wt[jc] = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        }
+        for (int jc = 0; jc < NJ; ++jc) wt[jc] = mx_a_frag(p.packs + L.W1TF, g * NJ + jc, lane);
       }
       // ---- dh = bf16(accd * GELU'(bf16(acc1 + b1))), MX quantisation in registers: the B fragment of k-step g of fc1's data gradient
       i32x8 hq[NTT]; int hsb[NTT];
+      const float* gb1 = sb1 + 128 * g + 16 * lg;          // the lane's biases: tile j = 4 hf + jj at + 64 hf + 4 jj
 #pragma unroll
-      for (int tt = 0; tt < NTT; ++tt) {
-        int e[2];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          float m = 0.f;
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int j = 4 * hf + jj;
-            const float4 bi = *reinterpret_cast<const float4*>(sb1 + 128 * g + 64 * hf + 16 * lg + 4 * jj);
-            const f32x2 d0 = gelu_grad_fast2((f32x2){(float)(__bf16)(acc1[j][tt][0] + bi.x), (float)(__bf16)(acc1[j][tt][1] + bi.y)});
-            const f32x2 d1 = gelu_grad_fast2((f32x2){(float)(__bf16)(acc1[j][tt][2] + bi.z), (float)(__bf16)(acc1[j][tt][3] + bi.w)});
-            accd[j][tt][0] = (float)(__bf16)(accd[j][tt][0] * d0[0]); accd[j][tt][1] = (float)(__bf16)(accd[j][tt][1] * d0[1]);
-            accd[j][tt][2] = (float)(__bf16)(accd[j][tt][2] * d1[0]); accd[j][tt][3] = (float)(__bf16)(accd[j][tt][3] * d1[1]);
-            m = fmaxf(fmaxf(m, fmaxf(fabsf(accd[j][tt][0]), fabsf(accd[j][tt][1]))), fmaxf(fabsf(accd[j][tt][2]), fabsf(accd[j][tt][3])));
-          }
-          e[hf] = mx_block_exp(pair16_max(m));
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int j = 4 * hf + jj;
-            hq[tt][j] = (int)pack4_e4m3_mx(accd[j][tt][0], accd[j][tt][1], accd[j][tt][2], accd[j][tt][3], e[hf]);
-          }
-        }
-        hsb[tt] = mx_lane_scale(e[0], e[1], lane);
-      }
+      for (int tt = 0; tt < NTT; ++tt)
+        mx_quant_acc([&](int j) {
+          const float4 bi = *reinterpret_cast<const float4*>(gb1 + 64 * (j >> 2) + 4 * (j & 3));
+          const f32x2 d0 = gelu_grad_fast2((f32x2){(float)(__bf16)(acc1[j][tt][0] + bi.x), (float)(__bf16)(acc1[j][tt][1] + bi.y)});
+          const f32x2 d1 = gelu_grad_fast2((f32x2){(float)(__bf16)(acc1[j][tt][2] + bi.z), (float)(__bf16)(acc1[j][tt][3] + bi.w)});
+          return (f32x4){(float)(__bf16)(accd[j][tt][0] * d0[0]), (float)(__bf16)(accd[j][tt][1] * d0[1]),
+                         (float)(__bf16)(accd[j][tt][2] * d1[0]), (float)(__bf16)(accd[j][tt][3] * d1[1])};
+        }, hq[tt], hsb[tt], lane);
       // ---- fc1 data gradient: k-step g
 #pragma unroll
       for (int jc = 0; jc < NJ; ++jc) {
         i32x8 a;
-        if constexpr (L::RESIDENT) {
-          const uint8_t* fa = smem + L::W1TF + (size_t)((g * NJ + jc) * 2) * 1024 + lane * 16;
-          const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
-          a = (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        } else {
-          a = wt[jc];
-        }
-        const int sa = smem[L::W1TS + (g * NJ + jc) * 64 + lane];
+        if constexpr (L.RESIDENT) a = mx_a_frag(smem + L.W1TF, g * NJ + jc, lane);
+        else a = wt[jc];
+        const int sa = mx_a_scale(smem + L.W1TS, g * NJ + jc, lane);
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt)
           dln[jc][tt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, hq[tt], dln[jc][tt], 0, 0, 0, sa, 0, hsb[tt]);
@@ -1212,7 +1159,7 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_bwd_mx_kernel(const MlpMx
 
 // C = 128 is served while its instantiation is free of spills and scratch; the host keeps the bf16 backward where this says no
 static inline bool mlp_bwd_mx_supported(int C) { return C == 96 || C == 128; }
-static inline long long mlp_bwd_mx_pack_bytes(int C) { return C == 96 ? MlpMxB<96>::PACK_BYTES : C == 128 ? MlpMxB<128>::PACK_BYTES : 0; }
+static inline long long mlp_bwd_mx_pack_bytes(int C) { return mlp_bwd_mx_supported(C) ? MlpMxB(C).PACK_BYTES : 0; }
 
 }  // namespace sv
 
@@ -1299,6 +1246,29 @@ extern "C" int sv_swin_mlp_wgrad(const void* x1, const void* dx2, const float* l
   return check_launch("sv_swin_mlp_wgrad");
 }
 
+// ---- MXFP8: what the forward and the data gradient share on the host -------------------------------------------------------------------
+// what sv_swin_mlp_fwd_mx and sv_swin_mlp_bwd_mx ask alike; `who` names the entry point that was called, `widths` what it adds to "unsupported C"
+static int mlp_mx_check(const char* who, bool pointers, bool served, const char* widths, uintptr_t aligned16, long long M, int C, int rows_per_scale) {
+  SV_REQUIRE(pointers, "%s: null pointer", who);
+  SV_REQUIRE(served, "%s: unsupported C=%d%s", who, C, widths);
+  SV_REQUIRE(M > 0 && M < (1ll << 31), "%s: M=%lld out of range", who, M);
+  SV_REQUIRE((aligned16 & 15) == 0, "%s: operands must be 16-byte aligned", who);
+  SV_REQUIRE(rows_per_scale > 0, "%s: rows_per_scale must be positive", who);
+  return SV_OK;
+}
+// 8 waves x 16 tokens: two waves per SIMD, so one wave's GELU / quantiser VALU stream runs beside the other's MFMAs and LDS reads (measured against
+// 4 waves x 32 tokens and 8 x 32; in the backward 8 x 32 spills and is slower)
+constexpr int MX_NW = 8, MX_NTT = 1;
+template <class Args>
+static int mlp_mx_launch(const char* who, void (*k96)(Args), void (*k128)(Args), int C, Args& a, hipStream_t stream, std::atomic<long long>& launches) {
+  a.ntiles = cdiv(a.M, MX_NW * MX_NTT * 16);
+  const int grid = a.ntiles < 256 ? a.ntiles : 256;        // one persistent workgroup per CU: the weights enter LDS once
+  hipLaunchKernelGGL(C == 96 ? k96 : k128, dim3(grid), dim3(MX_NW * 64), 0, stream, a);
+  const int rc = check_launch(who);
+  if (rc == SV_OK) launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
 // ---- MXFP8 forward ------------------------------------------------------------------------------------------------------------------
 static std::atomic<long long> swin_mlp_mx_launches{0};
 extern "C" long long sv_swin_mlp_mx_launches(void) { return swin_mlp_mx_launches.load(std::memory_order_relaxed); }
@@ -1309,45 +1279,28 @@ extern "C" int sv_swin_mlp_mx_pack(const void* w1q, const void* w1s, const void*
   SV_REQUIRE(w1q && w1s && w2q && w2s && packs, "sv_swin_mlp_mx_pack: null pointer");
   SV_REQUIRE(mlp_mx_supported(C), "sv_swin_mlp_mx_pack: unsupported C=%d (96 or 128)", C);
   SV_REQUIRE((((uintptr_t)w1q | (uintptr_t)w2q | (uintptr_t)packs) & 15) == 0, "sv_swin_mlp_mx_pack: w1q, w2q and packs must be 16-byte aligned");
-  const long long HID = 4ll * C, G = HID / 128, NJ = C / 16;
-  const long long items = HID * 128 / 16 + C * HID / 16 + G * 8 * 64 + G * NJ * 64;
-  hipLaunchKernelGGL(swin_mlp_mx_pack_kernel, dim3(cdiv(items, 256)), dim3(256), 0, STREAM, static_cast<const uint8_t*>(w1q), static_cast<const uint8_t*>(w1s),
+  hipLaunchKernelGGL(swin_mlp_mx_pack_kernel, dim3(cdiv(MlpMx(C).PACK_ITEMS, 256)), dim3(256), 0, STREAM, static_cast<const uint8_t*>(w1q), static_cast<const uint8_t*>(w1s),
                      static_cast<const uint8_t*>(w2q), static_cast<const uint8_t*>(w2s), static_cast<uint8_t*>(packs), C);
   return check_launch("sv_swin_mlp_mx_pack");
 }
 
 extern "C" int sv_swin_mlp_fwd_mx(const void* x1, void* x2, const float* ln_g, const float* ln_b, const void* packs_mx, const float* b1,
                                   const float* b2, const float* row_scale, int rows_per_scale, long long M, int C, float eps, void* stream) {
-  SV_REQUIRE(x1 && x2 && ln_g && ln_b && packs_mx && b1 && b2, "sv_swin_mlp_fwd_mx: null pointer");
-  SV_REQUIRE(mlp_mx_supported(C), "sv_swin_mlp_fwd_mx: unsupported C=%d (96 or 128)", C);
-  SV_REQUIRE(M > 0 && M < (1ll << 31), "sv_swin_mlp_fwd_mx: M=%lld out of range", M);
-  SV_REQUIRE((((uintptr_t)x1 | (uintptr_t)x2 | (uintptr_t)packs_mx | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)b2) & 15) == 0,
-             "sv_swin_mlp_fwd_mx: operands must be 16-byte aligned");
-  SV_REQUIRE(rows_per_scale > 0, "sv_swin_mlp_fwd_mx: rows_per_scale must be positive");
+  if (int rc = mlp_mx_check("sv_swin_mlp_fwd_mx", x1 && x2 && ln_g && ln_b && packs_mx && b1 && b2, mlp_mx_supported(C), " (96 or 128)",
+                            (uintptr_t)x1 | (uintptr_t)x2 | (uintptr_t)packs_mx | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)b2, M, C, rows_per_scale))
+    return rc;
   MlpMxArgs a{};
   a.x1 = static_cast<const __bf16*>(x1); a.out = static_cast<__bf16*>(x2); a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps;
   a.packs = static_cast<const uint8_t*>(packs_mx); a.b1 = b1; a.b2 = b2; a.row_scale = row_scale; a.rows_per_scale = rows_per_scale; a.M = M;
-  // 8 waves x 16 tokens: two waves per SIMD, so one wave's GELU / quantiser VALU stream runs beside the other's MFMAs and LDS reads
-  // (measured against 4 waves x 32 tokens and 8 x 32)
-#define SV_MLP_MX(CC, NW, NTT)                                                                                     \
-  do {                                                                                                             \
-    a.ntiles = cdiv(M, NW * NTT * 16);                                                                             \
-    const int grid = a.ntiles < 256 ? a.ntiles : 256;   /* one persistent workgroup per CU: the weights enter LDS once */ \
-    hipLaunchKernelGGL((swin_mlp_fwd_mx_kernel<CC, NW, NTT>), dim3(grid), dim3(NW * 64), 0, STREAM, a);            \
-  } while (0)
-  if (C == 96) SV_MLP_MX(96, 8, 1);
-  else SV_MLP_MX(128, 8, 1);
-#undef SV_MLP_MX
-  const int rc = check_launch("sv_swin_mlp_fwd_mx");
-  if (rc == SV_OK) swin_mlp_mx_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
+  return mlp_mx_launch("sv_swin_mlp_fwd_mx", swin_mlp_fwd_mx_kernel<96, MX_NW, MX_NTT>, swin_mlp_fwd_mx_kernel<128, MX_NW, MX_NTT>, C, a, STREAM,
+                       swin_mlp_mx_launches);
 }
 
 // ---- MXFP8 data gradient ------------------------------------------------------------------------------------------------------------
 static std::atomic<long long> swin_mlp_bwd_mx_launches{0};
 extern "C" long long sv_swin_mlp_bwd_mx_launches(void) { return swin_mlp_bwd_mx_launches.load(std::memory_order_relaxed); }
 extern "C" int sv_swin_mlp_bwd_mx_supported(int C) { return mlp_bwd_mx_supported(C) ? 1 : 0; }
-extern "C" long long sv_swin_mlp_bwd_mx_pack_bytes(int C) { return mlp_bwd_mx_supported(C) ? mlp_bwd_mx_pack_bytes(C) : 0; }
+extern "C" long long sv_swin_mlp_bwd_mx_pack_bytes(int C) { return mlp_bwd_mx_pack_bytes(C); }
 
 extern "C" int sv_swin_mlp_bwd_mx_pack(const void* w1q, const void* w1s, const void* w2tq, const void* w2ts, const void* w1tq, const void* w1ts, void* packs,
                                        int C, void* stream) {
@@ -1355,9 +1308,7 @@ extern "C" int sv_swin_mlp_bwd_mx_pack(const void* w1q, const void* w1s, const v
   SV_REQUIRE(mlp_bwd_mx_supported(C), "sv_swin_mlp_bwd_mx_pack: unsupported C=%d", C);
   SV_REQUIRE((((uintptr_t)w1q | (uintptr_t)w2tq | (uintptr_t)w1tq | (uintptr_t)packs) & 15) == 0,
              "sv_swin_mlp_bwd_mx_pack: w1q, w2tq, w1tq and packs must be 16-byte aligned");
-  const long long HID = 4ll * C, G = HID / 128, NJ = C / 16;
-  const long long items = 2 * (HID * 128 / 16) + 2 * (G * 8 * 64) + G * NJ * 64 + C * HID / 16;
-  hipLaunchKernelGGL(swin_mlp_bwd_mx_pack_kernel, dim3(cdiv(items, 256)), dim3(256), 0, STREAM, static_cast<const uint8_t*>(w1q), static_cast<const uint8_t*>(w1s),
+  hipLaunchKernelGGL(swin_mlp_bwd_mx_pack_kernel, dim3(cdiv(MlpMxB(C).PACK_ITEMS, 256)), dim3(256), 0, STREAM, static_cast<const uint8_t*>(w1q), static_cast<const uint8_t*>(w1s),
                      static_cast<const uint8_t*>(w2tq), static_cast<const uint8_t*>(w2ts), static_cast<const uint8_t*>(w1tq), static_cast<const uint8_t*>(w1ts),
                      static_cast<uint8_t*>(packs), C);
   return check_launch("sv_swin_mlp_bwd_mx_pack");
@@ -1365,27 +1316,13 @@ extern "C" int sv_swin_mlp_bwd_mx_pack(const void* w1q, const void* w1s, const v
 
 extern "C" int sv_swin_mlp_bwd_mx(const void* x1, const void* dx2, void* dx1, const float* ln_g, const float* ln_b, const void* packs_mx, const float* b1,
                                   const float* row_scale, int rows_per_scale, float* dgamma, float* dbeta, long long M, int C, float eps, void* stream) {
-  SV_REQUIRE(x1 && dx2 && dx1 && ln_g && ln_b && packs_mx && b1 && dgamma && dbeta, "sv_swin_mlp_bwd_mx: null pointer");
-  SV_REQUIRE(mlp_bwd_mx_supported(C), "sv_swin_mlp_bwd_mx: unsupported C=%d", C);
-  SV_REQUIRE(M > 0 && M < (1ll << 31), "sv_swin_mlp_bwd_mx: M=%lld out of range", M);
-  SV_REQUIRE((((uintptr_t)x1 | (uintptr_t)dx2 | (uintptr_t)dx1 | (uintptr_t)packs_mx | (uintptr_t)ln_g | (uintptr_t)ln_b) & 15) == 0,
-             "sv_swin_mlp_bwd_mx: operands must be 16-byte aligned");
-  SV_REQUIRE(rows_per_scale > 0, "sv_swin_mlp_bwd_mx: rows_per_scale must be positive");
+  if (int rc = mlp_mx_check("sv_swin_mlp_bwd_mx", x1 && dx2 && dx1 && ln_g && ln_b && packs_mx && b1 && dgamma && dbeta, mlp_bwd_mx_supported(C), "",
+                            (uintptr_t)x1 | (uintptr_t)dx2 | (uintptr_t)dx1 | (uintptr_t)packs_mx | (uintptr_t)ln_g | (uintptr_t)ln_b, M, C, rows_per_scale))
+    return rc;
   MlpMxBArgs a{};
   a.x1 = static_cast<const __bf16*>(x1); a.dx2 = static_cast<const __bf16*>(dx2); a.out = static_cast<__bf16*>(dx1);
   a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps; a.packs = static_cast<const uint8_t*>(packs_mx); a.b1 = b1;
   a.row_scale = row_scale; a.rows_per_scale = rows_per_scale; a.dgamma = dgamma; a.dbeta = dbeta; a.M = M;
-  // 8 waves x 16 tokens, one persistent workgroup per CU, as the forward; 8 x 32 spills and is slower
-#define SV_MLP_BWD_MX(CC, NW, NTT)                                                                                 \
-  do {                                                                                                             \
-    a.ntiles = cdiv(M, NW * NTT * 16);                                                                             \
-    const int grid = a.ntiles < 256 ? a.ntiles : 256;                                                              \
-    hipLaunchKernelGGL((swin_mlp_bwd_mx_kernel<CC, NW, NTT>), dim3(grid), dim3(NW * 64), 0, STREAM, a);            \
-  } while (0)
-  if (C == 96) SV_MLP_BWD_MX(96, 8, 1);
-  else SV_MLP_BWD_MX(128, 8, 1);
-#undef SV_MLP_BWD_MX
-  const int rc = check_launch("sv_swin_mlp_bwd_mx");
-  if (rc == SV_OK) swin_mlp_bwd_mx_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
+  return mlp_mx_launch("sv_swin_mlp_bwd_mx", swin_mlp_bwd_mx_kernel<96, MX_NW, MX_NTT>, swin_mlp_bwd_mx_kernel<128, MX_NW, MX_NTT>, C, a, STREAM,
+                       swin_mlp_bwd_mx_launches);
 }

@@ -165,6 +165,59 @@ def test_integer_case_invariants(M, C):
     assert torch.equal(unit, ref)
 
 
+# ---- pack images ------------------------------------------------------------------------------------------------------------------------
+# The two kinds of image of the MX packs, gathered on the CPU from the layout the header comment of swin_mlp_fwd_mx_kernel documents (lane = (r, lg),
+# lane index 16 lg + r; a lane's half hf is the 16 bytes k = 64 hf + 16 lg .. + 15 of the 128-wide k-step, its scale byte block lg of the k-step).
+# tests/test_gpu_swin_mlp_mx.py and tests/test_gpu_swin_mlp_mx_bwd.py compare the device's images with them byte for byte.
+def hidden_row_image(q, s):
+    """q [4C][128], s [4C][4] (W1 or W2^T in MX rows) -> data [G][8 tiles][2 halves][64 lanes][16], scales [G][8][64]; tile j, row r of group g is
+    hidden unit 128 g + 64 (j >> 2) + 16 (r >> 2) + 4 (j & 3) + (r & 3)"""
+    HID = q.shape[0]
+    G = HID // 128
+    assert q.shape == (HID, 128) and s.shape == (HID, 4) and HID % 128 == 0
+    g, j, r = torch.arange(G)[:, None, None], torch.arange(8)[None, :, None], torch.arange(16)[None, None, :]
+    hid = 128 * g + 64 * (j >> 2) + 16 * (r >> 2) + 4 * (j & 3) + (r & 3)                          # [G][8][16]
+    data = q.reshape(HID, 2, 4, 16)[hid]                                                           # [G][8][r][hf][lg][16]
+    return data.permute(0, 1, 3, 4, 2, 5).reshape(G, 8, 2, 64, 16), s[hid].permute(0, 1, 3, 2).reshape(G, 8, 64)
+
+
+def channel_row_image(q, s):
+    """q [C][4C], s [C][4C / 32] (W2 or W1^T in MX rows) -> data [G][C/16][2][64][16], scales [G][C/16][64]; tile jc, row r is channel 16 jc + r,
+    k-step g its hidden units 128 g .. + 127"""
+    C, HID = q.shape
+    G, NJ = HID // 128, C // 16
+    assert HID == 4 * C and s.shape == (C, HID // 32)
+    data = q.reshape(NJ, 16, G, 2, 4, 16).permute(2, 0, 3, 4, 1, 5)                                # [G][jc][hf][lg][r][16]
+    return data.reshape(G, NJ, 2, 64, 16), s.reshape(NJ, 16, G, 4).permute(2, 0, 3, 1).reshape(G, NJ, 64)
+
+
+def random_bytes(seed, *shape):
+    return torch.randint(0, 256, shape, generator=torch.Generator().manual_seed(seed), dtype=torch.int32).to(torch.uint8)
+
+
+@pytest.mark.parametrize("C", [96, 128])
+def test_pack_images_are_permutations_in_fragment_order(C):
+    HID = 4 * C
+    # every byte keeps its identity: position codes instead of random bytes
+    q = torch.arange(HID * 128, dtype=torch.int32).reshape(HID, 128)
+    s = torch.arange(HID * 4, dtype=torch.int32).reshape(HID, 4)
+    d, sc = hidden_row_image(q, s)
+    assert sorted(d.flatten().tolist()) == list(range(HID * 128)) and sorted(sc.flatten().tolist()) == list(range(HID * 4))
+    # lane (r = 5, lg = 2) of tile 6 of group 1, upper half: hidden unit 128 + 64 + 16 + 8 + 1, k = 64 + 32 ..; scale block 2
+    assert d[1, 6, 1, 32 + 5].tolist() == q[217, 96:112].tolist() and int(sc[1, 6, 32 + 5]) == int(s[217, 2])
+    # accumulator rows 4 lg .. + 3 of tiles 0-3 are the 16 consecutive hidden units 16 lg .. + 15 (registers 0-3 of the fc2 operand), tiles 4-7
+    # the same 64 units on
+    units = (d[0, :, 0, :16, 0] // 128).T                                                          # [r][j]: the hidden unit of row r of tile j
+    for r in range(16):
+        lo = 16 * (r >> 2) + (r & 3)
+        assert units[r].tolist() == [lo + 4 * jj for jj in range(4)] + [64 + lo + 4 * jj for jj in range(4)]
+    q = torch.arange(C * HID, dtype=torch.int32).reshape(C, HID)
+    s = torch.arange(C * HID // 32, dtype=torch.int32).reshape(C, HID // 32)
+    d, sc = channel_row_image(q, s)
+    assert sorted(d.flatten().tolist()) == list(range(C * HID)) and sorted(sc.flatten().tolist()) == list(range(C * HID // 32))
+    assert d[2, 3, 1, 48 + 7].tolist() == q[55, 256 + 64 + 48:256 + 64 + 64].tolist() and int(sc[2, 3, 48 + 7]) == int(s[55, 8 + 3])
+
+
 # ---- C ABI ----------------------------------------------------------------------------------------------------------------------------
 ENTRIES = ("sv_swin_mlp_mx_supported", "sv_swin_mlp_mx_pack_bytes", "sv_swin_mlp_mx_pack", "sv_swin_mlp_fwd_mx", "sv_swin_mlp_mx_launches")
 SV_ERR_INVALID = -1

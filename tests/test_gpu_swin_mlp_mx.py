@@ -13,7 +13,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_cpu_linear_fp8_recipe import l1_rel  # noqa: E402
-from test_cpu_swin_mlp_mx_recipe import emulate_swin_mlp_mx, gauss_mlp_case, integer_case  # noqa: E402
+from test_cpu_swin_mlp_mx_recipe import (channel_row_image, emulate_swin_mlp_mx, gauss_mlp_case, hidden_row_image, integer_case,  # noqa: E402
+                                         random_bytes)
 
 import swinvox_amd as S  # noqa: E402
 from swinvox_amd import hip, ops  # noqa: E402
@@ -95,6 +96,27 @@ def _unfused_chain(d, M, Cd, dev):
     torch.cuda.synchronize()
     assert _guards_intact(x2, M)
     return x2[:M].cpu()
+
+
+# ---- 0. the pack image, byte for byte ----------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cd", WIDTHS)
+def test_pack_image_byte_for_byte(dev, Cd):
+    """W1F | W2F | W1S | W2S of random bytes against the CPU gather written from the kernel's header comment"""
+    HID = 4 * Cd
+    w1q, w1s = random_bytes(41 + Cd, HID, 128), random_bytes(42 + Cd, HID, 4)
+    w2q, w2s = random_bytes(43 + Cd, Cd, HID), random_bytes(44 + Cd, Cd, HID // 32)
+    (w1f, w1sc), (w2f, w2sc) = hidden_row_image(w1q, w1s), channel_row_image(w2q, w2s)
+    ref = torch.cat([t.flatten() for t in (w1f, w2f, w1sc, w2sc)])
+    nbytes = int(hip.load().sv_swin_mlp_mx_pack_bytes(Cd))
+    assert ref.numel() == nbytes
+    packs = torch.full((nbytes + 16,), 0xA5, dtype=torch.uint8, device=dev)    # 16 guard bytes behind the image
+    on_dev = [t.to(dev) for t in (w1q, w1s, w2q, w2s)]
+    call("sv_swin_mlp_mx_pack", *(ptr(t) for t in on_dev), ptr(packs), Cd)
+    torch.cuda.synchronize()
+    got = packs.cpu()
+    assert bool((got[nbytes:] == 0xA5).all())
+    assert torch.equal(got[:nbytes], ref), int((got[:nbytes] != ref).sum())
 
 
 # ---- 1. exact integers -----------------------------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_cpu_linear_fp8_recipe import l1_rel  # noqa: E402
-from test_cpu_swin_mlp_mx_recipe import gauss_mlp_case  # noqa: E402
+from test_cpu_swin_mlp_mx_recipe import channel_row_image, gauss_mlp_case, hidden_row_image, random_bytes  # noqa: E402
 from test_cpu_swin_mlp_mx_bwd_recipe import dgrad_seed, emulate_swin_mlp_bwd_mx  # noqa: E402
 
 import swinvox_amd as S  # noqa: E402
@@ -157,6 +157,29 @@ def _unfused_chain(d, M, Cd, dev):
     torch.cuda.synchronize()
     assert _guards_intact(dx1, M)
     return dx1.cpu(), dg.cpu(), db.cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cd", WIDTHS)
+def test_pack_image_byte_for_byte(dev, Cd):
+    """W1F | W2TF | W1S | W2TS | W1TS | W1TF of random bytes against the CPU gather written from the kernels' header comments"""
+    if _unserved(Cd):
+        return
+    HID = 4 * Cd
+    w1q, w1s = random_bytes(51 + Cd, HID, 128), random_bytes(52 + Cd, HID, 4)
+    w2tq, w2ts = random_bytes(53 + Cd, HID, 128), random_bytes(54 + Cd, HID, 4)
+    w1tq, w1ts = random_bytes(55 + Cd, Cd, HID), random_bytes(56 + Cd, Cd, HID // 32)
+    (w1f, w1sc), (w2tf, w2tsc), (w1tf, w1tsc) = hidden_row_image(w1q, w1s), hidden_row_image(w2tq, w2ts), channel_row_image(w1tq, w1ts)
+    ref = torch.cat([t.flatten() for t in (w1f, w2tf, w1sc, w2tsc, w1tsc, w1tf)])
+    nbytes = int(hip.load().sv_swin_mlp_bwd_mx_pack_bytes(Cd))
+    assert ref.numel() == nbytes
+    packs = torch.full((nbytes + 16,), 0xA5, dtype=torch.uint8, device=dev)    # 16 guard bytes behind the image
+    on_dev = [t.to(dev) for t in (w1q, w1s, w2tq, w2ts, w1tq, w1ts)]
+    call("sv_swin_mlp_bwd_mx_pack", *(ptr(t) for t in on_dev), ptr(packs), Cd)
+    torch.cuda.synchronize()
+    got = packs.cpu()
+    assert bool((got[nbytes:] == 0xA5).all())
+    assert torch.equal(got[:nbytes], ref), int((got[:nbytes] != ref).sum())
 
 
 _RUNS = {}
