@@ -353,6 +353,21 @@ int sv_scale_shift_act_signs(const void* x, int ldx, const float* scale, const f
 int sv_bn_bwd_signs(const void* dz, int lddz, const void* signs, const void* x, int ldx, const float* gamma, const float* save_mean,
                     const float* save_rstd, long long M, int C, int act, float slope, int training, void* dx, int lddx, void* dres, int lddres,
                     float* dgamma, float* dbeta, double* sums_ws, int act_dtype, void* stream);
+/* The first bottleneck of a ResNet layer, out = relu(bn3(y3) + bn_d(yd)) (reference models/encoder.py:22-23: torchvision Bottleneck with downsample):
+ * both BatchNorms in the same passes.  Train mode, ReLU, C % 256 == 0, every row stride a multiple of 4 and >= C, 4-element aligned tensors; any
+ * other case is refused (use the per-layer entry points).
+ * sv_scale_shift_act2_signs: y = relu(fma(x3, scale3, shift3) + t), t = fma(xd, scaled, shiftd) rounded to the storage type, and the sign words of
+ * the sum - the bytes of sv_scale_shift_act (down-sampling layer, no activation) followed by sv_scale_shift_act_signs (bn3, residual = its output),
+ * without the intermediate tensor.
+ * sv_bn_bwd2_signs: d = dz * [sign bit] is formed from dz and the words in both passes and never stored; dx3 / dxd = each layer's input gradient
+ * (double arithmetic, as sv_bn_bwd); dgamma / dbeta of both layers +=.  sums_ws3 / sums_wsd: sv_bn_bwd_workspace_doubles(C) doubles each, ZERO on
+ * entry (two buffers, or the two halves of one). */
+int sv_scale_shift_act2_signs(const void* x3, int ldx3, const float* scale3, const float* shift3, const void* xd, int ldxd, const float* scaled,
+                              const float* shiftd, void* y, int ldy, long long M, int C, void* signs, int act_dtype, void* stream);
+int sv_bn_bwd2_signs(const void* dz, int lddz, const void* signs, const void* x3, int ldx3, const float* gamma3, const float* save_mean3,
+                     const float* save_rstd3, const void* xd, int ldxd, const float* gammad, const float* save_meand, const float* save_rstdd,
+                     long long M, int C, void* dx3, int lddx3, void* dxd, int lddxd, float* dgamma3, float* dbeta3, float* dgammad, float* dbetad,
+                     double* sums_ws3, double* sums_wsd, int act_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Attention cores.  Window attention = timm WindowAttention + SwinTransformerBlock roll/partition/mask

@@ -981,6 +981,171 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const AT* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The first bottleneck of a ResNet layer: out = relu(bn3(y3) + bn_d(yd)), two BatchNorms on tensors of one shape [M, C] whose outputs are
+// only ever summed.  One pass each way handles BOTH layers (C % 256 == 0, G == 64: a wave is the 64 column groups of one row, as in the
+// sign-word passes above): the normalised down-sampling branch is never stored, nor is the masked gradient dout * [out > 0] that both
+// backwards consume - each pass forms it again from dout and the sign words.
+//   forward: t = fma(yd, scale_d, shift_d) rounded to the storage type (what the separate pass stored), o = fma(y3, scale_3, shift_3) + t,
+//            sign bit = o > 0, out = relu(o) - the bytes of sv_scale_shift_act (down-sampling layer) + sv_scale_shift_act_signs (bn3)
+//   reduce : d = dout * bit; sum d (shared by both layers), sum d xhat_3, sum d xhat_d into the two [slot][2C] images
+//   apply  : dy3 = k1 d - k2 - k3 y3 and dyd likewise with each layer's constants (double, see bn_bwd_apply_cg_kernel)
+// ------------------------------------------------------------------------------------------------
+template <typename AT>
+__global__ __launch_bounds__(256) void scale_shift_act2_cg_kernel(const AT* __restrict__ x3, int ldx3, const float* __restrict__ scale3,
+                                                                  const float* __restrict__ shift3, const AT* __restrict__ xd, int ldxd,
+                                                                  const float* __restrict__ scaled, const float* __restrict__ shiftd,
+                                                                  AT* __restrict__ y, int ldy, long long M, int C, long long rows_per_block,
+                                                                  unsigned long long* __restrict__ signs) {
+  const int gq = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int c = (blockIdx.x * 64 + gq) * 4;
+  const float4 s3 = *reinterpret_cast<const float4*>(scale3 + c), h3 = *reinterpret_cast<const float4*>(shift3 + c);
+  const float4 sd = *reinterpret_cast<const float4*>(scaled + c), hd = *reinterpret_cast<const float4*>(shiftd + c);
+  const long long r0 = (long long)blockIdx.y * rows_per_block;
+  long long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
+#pragma unroll 2
+  for (long long r = r0 + rl; r < r1; r += 4) {
+    const float4 xv = ld4f(x3 + (size_t)r * ldx3 + c), dv = ld4f(xd + (size_t)r * ldxd + c);
+    const float t[4] = {__fmaf_rn(dv.x, sd.x, hd.x), __fmaf_rn(dv.y, sd.y, hd.y), __fmaf_rn(dv.z, sd.z, hd.z), __fmaf_rn(dv.w, sd.w, hd.w)};
+    float o[4] = {__fmaf_rn(xv.x, s3.x, h3.x), __fmaf_rn(xv.y, s3.y, h3.y), __fmaf_rn(xv.z, s3.z, h3.z), __fmaf_rn(xv.w, s3.w, h3.w)};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] += (float)(AT)t[j];
+    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(o[0] > 0.f), b1 = __builtin_amdgcn_ballot_w64(o[1] > 0.f);
+    const unsigned long long b2 = __builtin_amdgcn_ballot_w64(o[2] > 0.f), b3 = __builtin_amdgcn_ballot_w64(o[3] > 0.f);
+    if (gq == 0) {
+      unsigned long long* w = signs + ((size_t)r * (C >> 8) + blockIdx.x) * 4;
+      *reinterpret_cast<ulonglong2*>(w) = make_ulonglong2(b0, b1);
+      *reinterpret_cast<ulonglong2*>(w + 2) = make_ulonglong2(b2, b3);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = apply_act(o[j], SV_ACT_RELU, 0.f);
+    st4f(y + (size_t)r * ldy + c, make_float4(o[0], o[1], o[2], o[3]));
+  }
+}
+
+// d of one row: dout where the row's sign bit of the lane's channel is set, else 0
+template <typename AT>
+__device__ __forceinline__ void bn2_masked(const AT* __restrict__ dz, const unsigned long long* __restrict__ w, int gq, float (&d)[4]) {
+  const float4 dv = ld4f(dz);
+  const ulonglong2 p0 = reinterpret_cast<const ulonglong2*>(w)[0], p1 = reinterpret_cast<const ulonglong2*>(w)[1];   // the same four words for the whole wave
+  d[0] = ((p0.x >> gq) & 1ull) ? dv.x : 0.f; d[1] = ((p0.y >> gq) & 1ull) ? dv.y : 0.f;
+  d[2] = ((p1.x >> gq) & 1ull) ? dv.z : 0.f; d[3] = ((p1.y >> gq) & 1ull) ? dv.w : 0.f;
+}
+
+template <typename AT>
+__global__ __launch_bounds__(256) void bn_bwd2_reduce_kernel(const AT* __restrict__ dz, int lddz, const unsigned long long* __restrict__ signs,
+                                                             const AT* __restrict__ x3, int ldx3, const float* __restrict__ mean3,
+                                                             const float* __restrict__ rstd3, const AT* __restrict__ xd, int ldxd,
+                                                             const float* __restrict__ meand, const float* __restrict__ rstdd, long long M, int C,
+                                                             double* __restrict__ sums3, double* __restrict__ sumsd, long long rows_per_block) {
+  __shared__ double red[256][13];   // [thread][sum d | sum d xhat_3 | sum d xhat_d] x 4 channels (+1 pad)
+  const int gq = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int c = (blockIdx.x * 64 + gq) * 4, W = C >> 8;
+  const long long r0 = (long long)blockIdx.y * rows_per_block;
+  long long r1e = r0 + rows_per_block; if (r1e > M) r1e = M;
+  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0}, s3[4] = {0.0, 0.0, 0.0, 0.0};
+  const float4 mu3 = *reinterpret_cast<const float4*>(mean3 + c), rs3 = *reinterpret_cast<const float4*>(rstd3 + c);
+  const float4 mud = *reinterpret_cast<const float4*>(meand + c), rsd = *reinterpret_cast<const float4*>(rstdd + c);
+  const float m3[4] = {mu3.x, mu3.y, mu3.z, mu3.w}, q3[4] = {rs3.x, rs3.y, rs3.z, rs3.w};
+  const float md[4] = {mud.x, mud.y, mud.z, mud.w}, qd[4] = {rsd.x, rsd.y, rsd.z, rsd.w};
+  long long r = r0 + rl;
+  for (; r + 4 < r1e; r += 8) {   // two rows in flight
+    float a0[4], a1[4];
+    const float4 x0 = ld4f(x3 + (size_t)r * ldx3 + c), x1 = ld4f(x3 + (size_t)(r + 4) * ldx3 + c);
+    const float4 e0 = ld4f(xd + (size_t)r * ldxd + c), e1 = ld4f(xd + (size_t)(r + 4) * ldxd + c);
+    bn2_masked(dz + (size_t)r * lddz + c, signs + ((size_t)r * W + blockIdx.x) * 4, gq, a0);
+    bn2_masked(dz + (size_t)(r + 4) * lddz + c, signs + ((size_t)(r + 4) * W + blockIdx.x) * 4, gq, a1);
+    const float xa[4] = {x0.x, x0.y, x0.z, x0.w}, xb[4] = {x1.x, x1.y, x1.z, x1.w};
+    const float ea[4] = {e0.x, e0.y, e0.z, e0.w}, eb[4] = {e1.x, e1.y, e1.z, e1.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s1[j] += (double)a0[j] + (double)a1[j];
+      s2[j] += (double)(a0[j] * (xa[j] - m3[j]) * q3[j]) + (double)(a1[j] * (xb[j] - m3[j]) * q3[j]);
+      s3[j] += (double)(a0[j] * (ea[j] - md[j]) * qd[j]) + (double)(a1[j] * (eb[j] - md[j]) * qd[j]);
+    }
+  }
+  for (; r < r1e; r += 4) {
+    float a0[4];
+    const float4 x0 = ld4f(x3 + (size_t)r * ldx3 + c), e0 = ld4f(xd + (size_t)r * ldxd + c);
+    bn2_masked(dz + (size_t)r * lddz + c, signs + ((size_t)r * W + blockIdx.x) * 4, gq, a0);
+    const float xa[4] = {x0.x, x0.y, x0.z, x0.w}, ea[4] = {e0.x, e0.y, e0.z, e0.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s1[j] += (double)a0[j];
+      s2[j] += (double)(a0[j] * (xa[j] - m3[j]) * q3[j]);
+      s3[j] += (double)(a0[j] * (ea[j] - md[j]) * qd[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { red[threadIdx.x][j] = s1[j]; red[threadIdx.x][4 + j] = s2[j]; red[threadIdx.x][8 + j] = s3[j]; }
+  __syncthreads();
+  // thread t < 12 * 64 folds partial (t % 12) of column group (t / 12) over the four row lanes
+  for (int t = threadIdx.x; t < 12 * 64; t += 256) {
+    const int q = t / 12, k = t - q * 12;
+    const int cc = (blockIdx.x * 64 + q) * 4 + (k & 3);
+    const double a = red[q][k] + red[64 + q][k] + red[128 + q][k] + red[192 + q][k];
+    const size_t slot = (size_t)(blockIdx.y % BN_BWD_SLOTS) * 2 * C;
+    if (k < 4) { atomicAdd(sums3 + slot + cc, a); atomicAdd(sumsd + slot + cc, a); }
+    else if (k < 8) atomicAdd(sums3 + slot + C + cc, a);
+    else atomicAdd(sumsd + slot + C + cc, a);
+  }
+}
+
+// bn_bwd_fold_kernel for the two images of the pass above in one launch (blockIdx.y = image)
+__global__ __launch_bounds__(256) void bn_bwd_fold2_kernel(double* __restrict__ ws3, double* __restrict__ wsd, int C, float* __restrict__ dgamma3,
+                                                           float* __restrict__ dbeta3, float* __restrict__ dgammad, float* __restrict__ dbetad) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= 2 * C) return;
+  double* ws = blockIdx.y ? wsd : ws3;
+  float* dgamma = blockIdx.y ? dgammad : dgamma3;
+  float* dbeta = blockIdx.y ? dbetad : dbeta3;
+  double a = 0.0;
+#pragma unroll
+  for (int sl = 0; sl < BN_BWD_SLOTS; ++sl) a += ws[(size_t)sl * 2 * C + c];
+  ws[(size_t)BN_BWD_SLOTS * 2 * C + c] = a;
+  if (c < C) dbeta[c] += (float)a; else dgamma[c - C] += (float)a;
+}
+
+template <typename AT>
+__global__ __launch_bounds__(256) void bn_bwd2_apply_kernel(const AT* __restrict__ dz, int lddz, const unsigned long long* __restrict__ signs,
+                                                            const AT* __restrict__ x3, int ldx3, const float* __restrict__ gamma3,
+                                                            const float* __restrict__ mean3, const float* __restrict__ rstd3,
+                                                            const AT* __restrict__ xd, int ldxd, const float* __restrict__ gammad,
+                                                            const float* __restrict__ meand, const float* __restrict__ rstdd,
+                                                            const double* __restrict__ sums3, const double* __restrict__ sumsd, long long M, int C,
+                                                            AT* __restrict__ dx3, int lddx3, AT* __restrict__ dxd, int lddxd, long long rows_per_block) {
+  const int gq = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int c = (blockIdx.x * 64 + gq) * 4, W = C >> 8;
+  sums3 += (size_t)BN_BWD_SLOTS * 2 * C; sumsd += (size_t)BN_BWD_SLOTS * 2 * C;     // the folded images
+  // dx = k1*d - k2 - k3*x per layer, in double as bn_bwd_apply_cg_kernel forms it
+  double k1[4], k2[4], k3[4], l1[4], l2[4], l3[4];
+  const double invM = 1.0 / (double)M;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    { const double gm = gamma3[c + j], rs = rstd3[c + j], mu = mean3[c + j], a = sums3[c + j] * invM, b = sums3[C + c + j] * invM;
+      k1[j] = gm * rs; k3[j] = gm * rs * b * rs; k2[j] = gm * rs * a - k3[j] * mu; }
+    { const double gm = gammad[c + j], rs = rstdd[c + j], mu = meand[c + j], a = sumsd[c + j] * invM, b = sumsd[C + c + j] * invM;
+      l1[j] = gm * rs; l3[j] = gm * rs * b * rs; l2[j] = gm * rs * a - l3[j] * mu; }
+  }
+  const long long r0 = (long long)blockIdx.y * rows_per_block;
+  long long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
+#pragma unroll 2
+  for (long long r = r0 + rl; r < r1; r += 4) {
+    float d[4];
+    const float4 xv = ld4f(x3 + (size_t)r * ldx3 + c), ev = ld4f(xd + (size_t)r * ldxd + c);
+    bn2_masked(dz + (size_t)r * lddz + c, signs + ((size_t)r * W + blockIdx.x) * 4, gq, d);
+    const float xx[4] = {xv.x, xv.y, xv.z, xv.w}, ee[4] = {ev.x, ev.y, ev.z, ev.w};
+    float o[4], u[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[j] = (float)(k1[j] * (double)d[j] - k2[j] - k3[j] * (double)xx[j]);
+      u[j] = (float)(l1[j] * (double)d[j] - l2[j] - l3[j] * (double)ee[j]);
+    }
+    st4f(dx3 + (size_t)r * lddx3 + c, make_float4(o[0], o[1], o[2], o[3]));
+    st4f(dxd + (size_t)r * lddxd + c, make_float4(u[0], u[1], u[2], u[3]));
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // ResNet stem: BatchNorm + ReLU + MaxPool2d(3, stride 2, padding 1) (reference models/encoder.py:22-23: torchvision resnet50's bn1 / relu /
@@ -1762,4 +1927,65 @@ extern "C" int sv_bn_bwd_signs(const void* dz, int lddz, const void* signs, cons
   SV_REQUIRE(signs, "bn_bwd_signs: null sign buffer");
   return bn_bwd_impl(dz, lddz, nullptr, 0, static_cast<const unsigned long long*>(signs), x, ldx, gamma, save_mean, save_rstd, M, C, act, slope, training,
                      dx, lddx, dres, lddres, dgamma, dbeta, sums_ws, nullptr, nullptr, act_dtype, stream);
+}
+
+// ---- bn3 + the down-sampling BatchNorm of a ResNet layer's first bottleneck in the same passes (kernels above).  Vector geometry only:
+// C % 256 == 0, every row stride a multiple of 4, 4-element aligned tensors, train mode, ReLU; anything else is refused and stays with the
+// per-layer entry points.
+static bool bn_dual_ok(int act_dtype, int C, const int* lds, int nld, const void* a, const void* b, const void* c, const void* d = nullptr,
+                       const void* e = nullptr) {
+  if (!bn_signs_ok(C) || C <= 0) return false;
+  for (int i = 0; i < nld; ++i) if (lds[i] % 4 != 0 || lds[i] < C) return false;
+  return aligned4(act_dtype, a, b, c, d, e);
+}
+
+extern "C" int sv_scale_shift_act2_signs(const void* x3, int ldx3, const float* scale3, const float* shift3, const void* xd, int ldxd,
+                                         const float* scaled, const float* shiftd, void* y, int ldy, long long M, int C, void* signs,
+                                         int act_dtype, void* stream) {
+  SV_REQUIRE(x3 && scale3 && shift3 && xd && scaled && shiftd && y && M > 0, "scale_shift_act2_signs: null/empty argument");
+  SV_REQUIRE(signs, "scale_shift_act2_signs: null sign buffer");
+  SV_REQUIRE_ACT(act_dtype);
+  const int lds[3] = {ldx3, ldxd, ldy};
+  SV_REQUIRE(bn_dual_ok(act_dtype, C, lds, 3, x3, xd, y) &&
+             (((uintptr_t)scale3 | (uintptr_t)shift3 | (uintptr_t)scaled | (uintptr_t)shiftd | (uintptr_t)signs) & 15) == 0,
+             "scale_shift_act2_signs: needs C %% 256 == 0 and 4-aligned rows (C=%d)", C);
+  const int cg = C / 256;
+  long long splits = 4096 / cg; if (splits < 1) splits = 1;
+  const long long maxs = (M + 15) / 16; if (splits > maxs) splits = maxs;
+  const long long rpb = (M + splits - 1) / splits;
+  SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(scale_shift_act2_cg_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, (hipStream_t)stream,
+                                                static_cast<const AT*>(x3), ldx3, scale3, shift3, static_cast<const AT*>(xd), ldxd, scaled, shiftd,
+                                                static_cast<AT*>(y), ldy, M, C, rpb, static_cast<unsigned long long*>(signs)););
+  return check_launch("sv_scale_shift_act2_signs");
+}
+
+extern "C" int sv_bn_bwd2_signs(const void* dz, int lddz, const void* signs, const void* x3, int ldx3, const float* gamma3, const float* save_mean3,
+                                const float* save_rstd3, const void* xd, int ldxd, const float* gammad, const float* save_meand,
+                                const float* save_rstdd, long long M, int C, void* dx3, int lddx3, void* dxd, int lddxd, float* dgamma3,
+                                float* dbeta3, float* dgammad, float* dbetad, double* sums_ws3, double* sums_wsd, int act_dtype, void* stream) {
+  SV_REQUIRE(dz && x3 && gamma3 && save_mean3 && save_rstd3 && xd && gammad && save_meand && save_rstdd && dx3 && dxd && dgamma3 && dbeta3 &&
+             dgammad && dbetad && sums_ws3 && sums_wsd && M > 0, "bn_bwd2_signs: null/empty argument");
+  SV_REQUIRE(signs, "bn_bwd2_signs: null sign buffer");
+  SV_REQUIRE_ACT(act_dtype);
+  const int lds[5] = {lddz, ldx3, ldxd, lddx3, lddxd};
+  SV_REQUIRE(bn_dual_ok(act_dtype, C, lds, 5, dz, x3, xd, dx3, dxd) &&
+             (((uintptr_t)save_mean3 | (uintptr_t)save_rstd3 | (uintptr_t)save_meand | (uintptr_t)save_rstdd | (uintptr_t)signs) & 15) == 0,
+             "bn_bwd2_signs: needs C %% 256 == 0 and 4-aligned rows (C=%d)", C);
+  hipStream_t s = (hipStream_t)stream;
+  const int cg = C / 256;
+  long long splits = 2048 / cg; if (splits < 1) splits = 1;
+  const long long maxs = (M + 7) / 8; if (splits > maxs) splits = maxs;
+  const long long rpb = (M + splits - 1) / splits;
+  long long asplits = 4096 / cg; if (asplits < 1) asplits = 1;
+  const long long amax = (M + 15) / 16; if (asplits > amax) asplits = amax;
+  const long long arpb = (M + asplits - 1) / asplits;
+  const unsigned long long* w = static_cast<const unsigned long long*>(signs);
+  SV_DISPATCH_ACT(act_dtype,
+    const AT* dz_ = static_cast<const AT*>(dz); const AT* x3_ = static_cast<const AT*>(x3); const AT* xd_ = static_cast<const AT*>(xd);
+    hipLaunchKernelGGL(bn_bwd2_reduce_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, dz_, lddz, w, x3_, ldx3, save_mean3, save_rstd3, xd_, ldxd,
+                       save_meand, save_rstdd, M, C, sums_ws3, sums_wsd, rpb);
+    hipLaunchKernelGGL(bn_bwd_fold2_kernel, dim3(cdiv(2 * C, 256), 2), dim3(256), 0, s, sums_ws3, sums_wsd, C, dgamma3, dbeta3, dgammad, dbetad);
+    hipLaunchKernelGGL(bn_bwd2_apply_kernel<AT>, dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, dz_, lddz, w, x3_, ldx3, gamma3, save_mean3, save_rstd3, xd_, ldxd,
+                       gammad, save_meand, save_rstdd, sums_ws3, sums_wsd, M, C, static_cast<AT*>(dx3), lddx3, static_cast<AT*>(dxd), lddxd, arpb););
+  return check_launch("sv_bn_bwd2_signs");
 }

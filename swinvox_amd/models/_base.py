@@ -183,19 +183,37 @@ class ConvBnAct:
         # without a residual the backward recomputes the activation mask from y (scale*y + shift > 0) and never reads z
         return z, og, (x, ldi, y, z if residual is not None else None, ldz, st, n, in_grid, M)
 
+    def forward_stats(self, x, n, in_grid, training, *, ldi=None):
+        """Convolution + finalized statistics without the normalisation pass (the caller applies it: ops.bn_dual_apply).
+        -> (y, og, st, ctx); ctx is what backward_conv takes."""
+        sp = self.spec
+        og = sp.out_grid(in_grid)
+        M = n * og[0] * og[1] * og[2]
+        y = empty(M, sp.cout, like=x)
+        st = BatchNormState(self.bn, M, training)
+        sp.forward(x, n, in_grid, self._pack("f"), y, ldi=ldi, bias=self.conv.bias, stats=st.sums)
+        st.finalize()
+        return y, og, st, (x, ldi, y, None, sp.cout, st, n, in_grid, M)
+
     def backward(self, ctx, dz, lddz, grads, *, need_dx=True, dres=None, lddres=0, dx=None, lddx=None, dx_epi=None):
         x, ldi, y, z, ldz, st, n, in_grid, M = ctx
         sp = self.spec
         dy = (zeros if sp.cout_mem != sp.cout else empty)(M, sp.cout_mem, like=dz)
         st.backward(dz, lddz, z, ldz, y, sp.cout, dy, sp.cout_mem, grads[self.bn.weight], grads[self.bn.bias], self.act, self.slope,
                     dres, lddres)
+        return self.backward_conv(ctx, dy, grads, need_dx=need_dx, dx=dx, lddx=lddx, dx_epi=dx_epi)
+
+    def backward_conv(self, ctx, dy, grads, *, need_dx=True, dx=None, lddx=None, dx_epi=None):
+        """The convolution's backward from dy [M, cout_mem], the gradient of its own output (the BatchNorm backward already done)."""
+        x, ldi, y, z, ldz, st, n, in_grid, M = ctx
+        sp = self.spec
         sp.wgrad(dy, x, n, in_grid, self._dw(grads), lddy=sp.cout_mem, ldx=ldi,
                  db=grads[self.conv.bias] if self.conv.bias is not None else None)
         if not need_dx:
             return None
         Min = n * in_grid[0] * in_grid[1] * in_grid[2]
         if dx is None:
-            dx = (zeros if sp.cin_mem != sp.cin else empty)(Min, sp.cin_mem, like=dz)
+            dx = (zeros if sp.cin_mem != sp.cin else empty)(Min, sp.cin_mem, like=dy)
             lddx = sp.cin_mem
         sp.dgrad(dy, n, in_grid, self._pack("d"), dx, lddy=sp.cout_mem, lddx=lddx, **(dx_epi or {}))
         return dx

@@ -42,14 +42,31 @@ class Bottleneck(nn.Module):
         a, g1, c1 = self._c1.forward(x, n, grid, training)
         b, g2, c2 = self._c2.forward(a, n, g1, training)
         idt, cd = x, None
+        Co = self.conv3.out_channels
+        if self._cd is not None and ops.bn_dual_enabled(training, Co, self._c3.act):
+            # bn3 and the down-sampling BatchNorm act on tensors of one shape and are only ever summed: one normalisation pass for both,
+            # the normalised skip branch is never stored (ops.bn_dual_apply; the backward likewise, see bwd)
+            yd, _, std, cd = self._cd.forward_stats(x, n, grid, training)
+            y3, g3, st3, c3 = self._c3.forward_stats(b, n, g2, training)
+            out = empty(y3.shape[0], Co, like=y3)
+            ops.bn_dual_apply(st3, y3, Co, std, yd, Co, out, Co)
+            return out, g3, (c1, c2, c3, cd, True)
         if self._cd is not None:
             idt, _, cd = self._cd.forward(x, n, grid, training)
-        out, g3, c3 = self._c3.forward(b, n, g2, training, residual=idt, ldr=self.conv3.out_channels)
-        return out, g3, (c1, c2, c3, cd)
+        out, g3, c3 = self._c3.forward(b, n, g2, training, residual=idt, ldr=Co)
+        return out, g3, (c1, c2, c3, cd, False)
 
     def bwd(self, ctx, dout, grads):
-        c1, c2, c3, cd = ctx
+        c1, c2, c3, cd, dual = ctx
         Co = self.conv3.out_channels
+        if dual:
+            M = dout.shape[0]
+            dy3, dyd = empty(M, Co, like=dout), empty(M, Co, like=dout)
+            ops.bn_dual_backward(c3[5], cd[5], dout, Co, c3[2], Co, cd[2], Co, dy3, Co, dyd, Co, grads)
+            db = self._c3.backward_conv(c3, dy3, grads)
+            da = self._c2.backward(c2, db, self.conv2.out_channels, grads)
+            skip = self._cd.backward_conv(cd, dyd, grads)
+            return self._c1.backward(c1, da, self.conv1.out_channels, grads, dx_epi=dict(residual=skip, ldr=self.conv1.in_channels))
         didt = empty(dout.shape[0], Co, like=dout)
         db = self._c3.backward(c3, dout, Co, grads, dres=didt, lddres=Co)
         da = self._c2.backward(c2, db, self.conv2.out_channels, grads)

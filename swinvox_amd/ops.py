@@ -1186,6 +1186,38 @@ class BatchNormState:
              ptr(self.scale), ptr(self.shift))
 
 
+def bn_dual_enabled(training: bool, C: int, act: int) -> bool:
+    """bn3 and the down-sampling BatchNorm of a layer's first bottleneck in the same passes (bn_dual_apply / bn_dual_backward): the
+    switch (set_bn_dual / SV_BN_DUAL, default on) and what the kernels need - train mode, ReLU, sign words in use, C % 256 == 0."""
+    import os
+    on = _STATE.get("bn_dual", os.environ.get("SV_BN_DUAL", "1") != "0")
+    return bool(on and training and act == ACT_RELU and _bn_signs_on() and C % 256 == 0)
+
+
+def set_bn_dual(on: bool) -> None:
+    """A/B switch: False runs the two BatchNorms of a down-sampling bottleneck as two layers (sv_scale_shift_act + sv_scale_shift_act_signs,
+    sv_bn_bwd_signs + sv_bn_bwd)."""
+    _STATE["bn_dual"] = bool(on)
+
+
+def bn_dual_apply(st3: "BatchNormState", x3, ldx3, std: "BatchNormState", xd, ldxd, y, ldy) -> None:
+    """y = relu(bn3(x3) + bn_d(xd)) in one pass, both layers finalized before; st3 keeps the sign words of the sum"""
+    std.probe(xd, ldxd)
+    st3.probe(x3, ldx3)
+    st3.signs = torch.empty(st3.M * (st3.C // 64), dtype=torch.int64, device=x3.device)
+    call("sv_scale_shift_act2_signs", ptr(x3), ldx3, ptr(st3.scale), ptr(st3.shift), ptr(xd), ldxd, ptr(std.scale), ptr(std.shift), ptr(y), ldy,
+         st3.M, st3.C, ptr(st3.signs))
+
+
+def bn_dual_backward(st3: "BatchNormState", std: "BatchNormState", dz, lddz, x3, ldx3, xd, ldxd, dx3, lddx3, dxd, lddxd, grads) -> None:
+    """both layers' input gradients from dz and st3's sign words; grads[...] of the four BatchNorm parameters +="""
+    n = (BN_BWD_SLOTS + 1) * 2 * st3.C + 2          # sv_bn_bwd_workspace_doubles(C), one image per layer, zero on entry
+    ws = zeros_f64(2 * n, dz.device)
+    call("sv_bn_bwd2_signs", ptr(dz), lddz, ptr(st3.signs), ptr(x3), ldx3, ptr(st3.bn.weight), ptr(st3.mean), ptr(st3.rstd),
+         ptr(xd), ldxd, ptr(std.bn.weight), ptr(std.mean), ptr(std.rstd), st3.M, st3.C, ptr(dx3), lddx3, ptr(dxd), lddxd,
+         ptr(grads[st3.bn.weight]), ptr(grads[st3.bn.bias]), ptr(grads[std.bn.weight]), ptr(grads[std.bn.bias]), ptr(ws[:n]), ptr(ws[n:]))
+
+
 def _bn_signs_on() -> bool:
     import os
     return _STATE.get("bn_signs", os.environ.get("SV_BN_SIGNS", "1") != "0")
