@@ -12,7 +12,7 @@ The modules below only HOLD parameters; the arithmetic is the kernel chain in sw
 from __future__ import annotations
 
 import logging
-from typing import List
+from typing import Any, List, NamedTuple
 
 import torch
 import torch.nn as nn
@@ -140,31 +140,39 @@ def _drop_scale(I, p, seed, like):
     return sc
 
 
-def _norm_for_linear(x, norm, rows, Cd, spec, w, save, merge_hw=(0, 0), store_mx=False, **epi):
-    """The LayerNorm in front of a Swin linear (norm1 -> qkv, norm2 -> fc1, patch-merge norm -> reduction; **epi: that linear's epilogue form)
-    -> (ln, mean, rstd, xq).  When the linear will take the fp8 kernel and the fused quantiser is on (row recipe: ops.ln_quant_site, MX
-    recipe: ops.ln_quant_mx_site), the LayerNorm kernel emits the quantised rows xq = (bytes, scales) itself, and without `save` (no backward
-    follows) stores nothing else (ln, mean, rstd are None); otherwise xq is None and this is ops.layernorm_fwd.
-    store_mx (the caller asked ops.mx_store_site): the tape will keep xq in place of ln, so ln comes back as None and xq always - an emitting
-    LayerNorm does not write ln at all, otherwise ln is quantised here by the stand-alone quantiser and dropped."""
-    if ops.ln_quant_site(spec, w, **epi):
+# What block_forward keeps for block_backward.  ln1, att, ln2 and h are tensors or, under store "mx" (LinearPlan.keep), the MX rows (bytes,
+# scales) the forward GEMM consumed; a fused branch leaves the entries it does not store None.  packs: the fused MLP's bf16 weight images, when
+# its backward reads them; fused_mlp: the fused MLP took the block (block_backward runs _fused_mlp_backward).
+BlockTape = NamedTuple("BlockTape", [(n, Any) for n in "x m1 r1 ln1 qkv att sc1 sc2 x1 m2 r2 ln2 hpre h I packs fused_mlp".split()])
+# What stage_forward keeps of the patch merging: its input, the norm's output (or its MX rows, store "mx") and statistics, the rows, Hin.
+MergeTape = NamedTuple("MergeTape", [(n, Any) for n in "x ln mean rstd rows Hin".split()])
+
+
+def _norm_for_linear(x, norm, rows, Cd, plan, save, merge_hw=(0, 0)):
+    """The LayerNorm in front of a Swin linear (norm1 -> qkv, norm2 -> fc1, patch-merge norm -> reduction; plan: that linear's
+    ops.swin_linear_plan) -> (ln, mean, rstd, xq).  plan.ln_emits: the LayerNorm kernel emits the quantised rows xq = (bytes, scales) itself, and
+    without `save` (no backward follows) stores nothing else (ln, mean, rstd are None); otherwise xq is None and this is ops.layernorm_fwd.
+    plan.keep: the tape will keep xq in place of ln, so ln comes back as None and xq always - an emitting LayerNorm does not write ln at all,
+    otherwise ln is quantised here by the stand-alone quantiser and dropped."""
+    if plan.ln_emits and plan.kind == "mx":
+        ln, m, r, q, sq = ops.layernorm_quant_mx_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save, store_y=not plan.keep)
+        return ln, m, r, (q, sq)
+    if plan.ln_emits:
         ln, m, r, q, sq = ops.layernorm_quant_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save)
         return ln, m, r, (q, sq)
-    if ops.ln_quant_mx_site(spec, w, **epi):
-        ln, m, r, q, sq = ops.layernorm_quant_mx_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw, store=save, store_y=not store_mx)
-        return ln, m, r, (q, sq)
     ln, m, r = ops.layernorm_fwd(x, norm.weight, norm.bias, rows, Cd, merge_hw=merge_hw)
-    if store_mx:
+    if plan.keep:
         return None, m, r, ops.quantize_rows_mx(ln, rows, Cd)
     return ln, m, r, None
 
 
 def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
     """x [I*res*res, C] -> same shape; returns (out, ctx).  save=False (no backward will follow): the fused attention branch
-    skips the tensors it would store for the backward.  Store "mx" (ops.mx_store_site, unfused branches with `save`): the ctx slots of ln1,
-    att, ln2 and h hold the MX rows the forward GEMM consumed, (bytes, scales), in place of the tensor."""
+    skips the tensors it would store for the backward.  ctx is a BlockTape.  Every unfused linear runs under its ops.swin_linear_plan, made
+    before its input is produced: who quantises the rows, and whether the tape keeps them in place of the tensor (store "mx")."""
     H = W = blk.res
     Cd, M = blk.dim, I * H * W
+    a, mlp = blk.attn, blk.mlp
     dp = blk.drop_path if (training and stochastic) else 0.0
     esz = 2.0 if x.dtype == torch.bfloat16 else 4.0
     if ops.fused_attn_block_enabled(Cd, blk.heads):
@@ -176,7 +184,6 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         if save:
             ln1, qkv, att = empty(M, Cd, like=x), empty(M, 3 * Cd, like=x), empty(M, Cd, like=x)
             m1, r1 = fempty(M, like=x), fempty(M, like=x)
-        a = blk.attn
         # LayerNorm-free products of the branch: qkv + QK^T + PV + proj per token; bytes: x in, x1 out (+ the 5 saved rows when training)
         ops.traced_call("sv_swin_attn_block_fwd", 2.0 * M * Cd * 4 * Cd + 4.0 * 49 * 32 * M * blk.heads, esz * M * Cd * (7 if save else 2),
                         ptr(x), ptr(blk.norm1.weight), ptr(blk.norm1.bias), ptr(a.qkv.weight), ptr(a.qkv.bias), ptr(a.relative_position_bias_table),
@@ -185,33 +192,32 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
     else:
         # the fused attention backward reads ln1 and att as tensors: the branch then keeps its bf16 tape
         store_a = save and ops.linear_fp8_store() == "mx" and not ops.fused_attn_block_bwd_enabled(Cd, blk.heads)
-        st1 = store_a and ops.mx_store_site(blk.s_qkv, blk.attn.qkv.weight, bias=blk.attn.qkv.bias)
-        ln1, m1, r1, q1 = _norm_for_linear(x, blk.norm1, M, Cd, blk.s_qkv, blk.attn.qkv.weight, save, store_mx=st1, bias=blk.attn.qkv.bias)
+        p_qkv = ops.swin_linear_plan(blk.s_qkv, a.qkv.weight, store_a, bias=a.qkv.bias)
+        ln1, m1, r1, q1 = _norm_for_linear(x, blk.norm1, M, Cd, p_qkv, save)
         qkv = empty(M, 3 * Cd, like=x)
-        ops.swin_linear_fwd(ln1, M, blk.s_qkv, blk.attn.qkv.weight, qkv, xq=q1, bias=blk.attn.qkv.bias)
+        ops.swin_linear_fwd(ln1, M, blk.s_qkv, a.qkv.weight, qkv, xq=q1, plan=p_qkv)
         sc1 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
         sc2 = _drop_scale(I, dp, seeds(), x) if dp > 0 else None
-        proj_epi = dict(bias=blk.attn.proj.bias, residual=x, ldr=Cd, row_scale=sc1, rows_per_scale=H * W)
-        sta = store_a and ops.mx_store_site(blk.s_proj, blk.attn.proj.weight, **proj_epi)
+        p_proj = ops.swin_linear_plan(blk.s_proj, a.proj.weight, store_a, producer=True,
+                                      bias=a.proj.bias, residual=x, ldr=Cd, row_scale=sc1, rows_per_scale=H * W)
         # algorithmic work of the core (49-token windows, no padding): QK^T + PV = 4 * 49 * 32 flop per (token, head); bytes: qkv in, out
-        if ops.mx_emit_site(blk.s_proj, blk.attn.proj.weight, proj_epi):
+        if p_proj.prod_emits:
             # MX recipe: the core emits the operand rows of proj (one head of a token = one block); without `save` att itself is not stored
-            att, Kp = (empty(M, Cd, like=x) if (save and not sta) else None), (Cd + 127) // 128 * 128
-            qa = (torch.empty(M, Kp, dtype=torch.uint8, device=x.device), torch.empty(M, Kp // 32, dtype=torch.uint8, device=x.device))
+            att, qa = (empty(M, Cd, like=x) if (save and not p_proj.keep) else None), ops.operand_buffers(M, Cd, True, x.device)
             ops.traced_call("sv_window_attention_fwd_mxq", 4.0 * 49 * 32 * M * blk.heads, (esz * (4 if save else 3) + 1) * M * Cd, ptr(qkv),
-                            ptr(blk.attn.relative_position_bias_table), ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(),
-                            ptr(qa[0]), Kp, ptr(qa[1]), tag=f"M={M} C={Cd}")
+                            ptr(a.relative_position_bias_table), ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(),
+                            ptr(qa[0]), qa[0].shape[1], ptr(qa[1]), tag=f"M={M} C={Cd}")
         else:
             att, qa = empty(M, Cd, like=x), None
-            ops.traced_call("sv_window_attention_fwd", 4.0 * 49 * 32 * M * blk.heads, esz * 4 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
+            ops.traced_call("sv_window_attention_fwd", 4.0 * 49 * 32 * M * blk.heads, esz * 4 * M * Cd, ptr(qkv), ptr(a.relative_position_bias_table),
                             ptr(att), I, H, W, Cd, blk.heads, blk.shift, ops.attention_math(), tag=f"M={M} C={Cd}")
-            if sta:
+            if p_proj.keep:
                 qa = ops.quantize_rows_mx(att, M, Cd)
         x1 = empty(M, Cd, like=x)
-        ops.swin_linear_fwd(att, M, blk.s_proj, blk.attn.proj.weight, x1, xq=qa, **proj_epi)
-        if st1:
+        ops.swin_linear_fwd(att, M, blk.s_proj, a.proj.weight, x1, xq=qa, plan=p_proj)
+        if p_qkv.keep:
             ln1 = q1
-        if sta:
+        if p_proj.keep:
             att = qa                                       # the tensor, where one was written, is dropped here
     if ops.fused_mlp_enabled(Cd):
         # norm2 -> fc1 -> GELU -> fc2 -> drop-path -> +x1 in ONE kernel; the 4C-wide hidden activation never reaches HBM
@@ -221,88 +227,74 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         # gradient reads pack_fwd / pack_dgrad)
         if not mx or (save and not ops.fused_mlp_mx_bwd_enabled(Cd)):
             packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
-            call("sv_swin_mlp_pack", ptr(blk.mlp.fc1.weight), ptr(blk.mlp.fc2.weight), ptr(packs), Cd)
+            call("sv_swin_mlp_pack", ptr(mlp.fc1.weight), ptr(mlp.fc2.weight), ptr(packs), Cd)
         x2 = empty(M, Cd, like=x)
-        unit = 2.0 * M * Cd * 4 * Cd
-        if mx:
-            # opt-in MXFP8 forward (set_fused_mlp_mx): both products on MX operands, quantised in registers; the backward recomputes in bf16, or
-            # on MX operands as well with set_fused_mlp_mx(True, backward=True)
-            packs_mx = ops.swin_mlp_mx_packs(blk.mlp.fc1.weight, blk.mlp.fc2.weight, Cd)
-            ops.traced_call("sv_swin_mlp_fwd_mx", 2 * unit, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs_mx),
-                            ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
-            return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, packs, None, I)
-        ops.traced_call("sv_swin_mlp_fwd", 2 * unit, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs),
-                        ptr(blk.mlp.fc1.bias), ptr(blk.mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
-        return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, packs, None, I)
-    st2 = save and ops.mx_store_site(blk.s_fc1, blk.mlp.fc1.weight, bias=blk.mlp.fc1.bias, act=ACT_GELU)
-    ln2, m2, r2, q2 = _norm_for_linear(x1, blk.norm2, M, Cd, blk.s_fc1, blk.mlp.fc1.weight, save, store_mx=st2, bias=blk.mlp.fc1.bias, act=ACT_GELU)
-    fc2_epi = dict(bias=blk.mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2, rows_per_scale=H * W)
-    sth = save and ops.mx_store_site(blk.s_fc2, blk.mlp.fc2.weight, **fc2_epi)
+        # opt-in MXFP8 forward (set_fused_mlp_mx): both products on MX operands, quantised in registers; the backward recomputes in bf16, or on
+        # MX operands as well with set_fused_mlp_mx(True, backward=True)
+        name, images = ("sv_swin_mlp_fwd_mx", ops.swin_mlp_mx_packs(mlp.fc1.weight, mlp.fc2.weight, Cd)) if mx else ("sv_swin_mlp_fwd", packs)
+        ops.traced_call(name, 4.0 * M * Cd * 4 * Cd, 4.0 * M * Cd, ptr(x1), ptr(x2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(images),
+                        ptr(mlp.fc1.bias), ptr(mlp.fc2.bias), ptr(sc2), H * W, M, Cd, float(blk.norm2.eps), tag=f"M={M} C={Cd}")
+        return x2, BlockTape(x, m1, r1, ln1, qkv, att, sc1, sc2, x1, None, None, None, None, None, I, packs, True)
+    p_fc1 = ops.swin_linear_plan(blk.s_fc1, mlp.fc1.weight, save, bias=mlp.fc1.bias, act=ACT_GELU)
+    ln2, m2, r2, q2 = _norm_for_linear(x1, blk.norm2, M, Cd, p_fc1, save)
+    p_fc2 = ops.swin_linear_plan(blk.s_fc2, mlp.fc2.weight, save, producer=p_fc1,
+                                 bias=mlp.fc2.bias, residual=x1, ldr=Cd, row_scale=sc2, rows_per_scale=H * W)
     # MX recipe: fc1 emits the operand rows of fc2 from its epilogue; without `save` neither h nor hpre is allocated or written
-    emit = ops.mx_emit_site(blk.s_fc2, blk.mlp.fc2.weight, fc2_epi, blk.s_fc1, blk.mlp.fc1.weight, dict(bias=blk.mlp.fc1.bias, act=ACT_GELU))
+    emit = p_fc2.prod_emits
     hpre = h = None
     if save or not emit:
         hpre = empty(M, 4 * Cd, like=x)
-        h = empty(M, 4 * Cd, like=x) if not (emit and sth) else None   # store "mx": fc1 writes hpre and the MX rows of h, not h
-    qh = ops.swin_linear_fwd(ln2, M, blk.s_fc1, blk.mlp.fc1.weight, h, xq=q2, emit=emit, bias=blk.mlp.fc1.bias, act=ACT_GELU, pre_act=hpre)
-    if sth and not emit:
+        h = empty(M, 4 * Cd, like=x) if not (emit and p_fc2.keep) else None   # store "mx": fc1 writes hpre and the MX rows of h, not h
+    qh = ops.swin_linear_fwd(ln2, M, blk.s_fc1, mlp.fc1.weight, h, xq=q2, emit=emit, plan=p_fc1, pre_act=hpre)
+    if p_fc2.keep and not emit:
         qh = ops.quantize_rows_mx(h, M, 4 * Cd)
     x2 = empty(M, Cd, like=x)
-    ops.swin_linear_fwd(h, M, blk.s_fc2, blk.mlp.fc2.weight, x2, xq=qh, **fc2_epi)
-    if st2:
-        ln2 = q2
-    if sth:
-        h = qh
-    return x2, (x, m1, r1, ln1, qkv, att, sc1, sc2, x1, m2, r2, ln2, hpre, h, I)
+    ops.swin_linear_fwd(h, M, blk.s_fc2, mlp.fc2.weight, x2, xq=qh, plan=p_fc2)
+    return x2, BlockTape(x, m1, r1, ln1, qkv, att, sc1, sc2, x1, m2, r2, q2 if p_fc1.keep else ln2, hpre, qh if p_fc2.keep else h, I, None, False)
 
 
-def block_backward(blk: SwinBlock, ctx, dx2, grads):
-    """dx2 is consumed (used as the accumulator of the residual path); returns dx.  ln1, att, ln2 and h are tensors or, under store "mx", the MX
-    rows (bytes, scales) the forward kept: ops.swin_linear_wgrad takes either."""
-    x, m1, r1, ln1, qkv, att, sc1, sc2, x1, m2, r2, ln2, hpre, h, I = ctx
+def block_backward(blk: SwinBlock, t: BlockTape, dx2, grads):
+    """dx2 is consumed (used as the accumulator of the residual path); returns dx.  t.ln1, t.att, t.ln2 and t.h are tensors or, under store
+    "mx", the MX rows (bytes, scales) the forward kept: ops.swin_linear_wgrad takes either."""
     H = W = blk.res
-    Cd, M = blk.dim, I * H * W
+    Cd, M, mlp = blk.dim, t.I * H * W, blk.mlp
     # ---- MLP branch: x2 = x1 + s2 * fc2(gelu(fc1(ln2)))
-    if ln2 is None:
-        dx1 = _fused_mlp_backward(blk, x1, hpre, sc2, dx2, grads, M, Cd, H * W)
-        return _attention_backward(blk, x, m1, r1, ln1, qkv, att, sc1, dx1, grads, I, H, W, Cd, M)
+    if t.fused_mlp:
+        return _attention_backward(blk, t, _fused_mlp_backward(blk, t, dx2, grads), grads)
     dbr = dx2
-    if sc2 is not None:
-        dbr = empty(M, Cd, like=x)
-        call("sv_rowscale", ptr(dx2), ptr(sc2), ptr(dbr), M, Cd, H * W)
+    if t.sc2 is not None:
+        dbr = empty(M, Cd, like=t.x)
+        call("sv_rowscale", ptr(dx2), ptr(t.sc2), ptr(dbr), M, Cd, H * W)
     # without a drop-path copy dbr IS dx2, which the LayerNorm backward below updates in place -> keep this one in order
-    ops.swin_linear_wgrad(dbr, h, M, blk.s_fc2, blk.mlp.fc2.weight, grads[blk.mlp.fc2.weight], grads[blk.mlp.fc2.bias], async_ok=sc2 is not None)
-    dh = empty(M, 4 * Cd, like=x)
-    ops.swin_linear_dgrad(dbr, M, blk.s_fc2, blk.mlp.fc2.weight, dh, act_grad_src=hpre, act_grad_kind=ACT_GELU)
-    ops.swin_linear_wgrad(dh, ln2, M, blk.s_fc1, blk.mlp.fc1.weight, grads[blk.mlp.fc1.weight], grads[blk.mlp.fc1.bias])
-    dln2 = empty(M, Cd, like=x)
-    ops.swin_linear_dgrad(dh, M, blk.s_fc1, blk.mlp.fc1.weight, dln2)
-    ops.layernorm_bwd(dln2, x1, blk.norm2.weight, m2, r2, dx2, grads[blk.norm2.weight], grads[blk.norm2.bias], M, Cd, accumulate_dx=True)
-    dx1 = dx2
-    return _attention_backward(blk, x, m1, r1, ln1, qkv, att, sc1, dx1, grads, I, H, W, Cd, M)
+    ops.swin_linear_wgrad(dbr, t.h, M, blk.s_fc2, mlp.fc2.weight, grads[mlp.fc2.weight], grads[mlp.fc2.bias], async_ok=t.sc2 is not None)
+    dh = empty(M, 4 * Cd, like=t.x)
+    ops.swin_linear_dgrad(dbr, M, blk.s_fc2, mlp.fc2.weight, dh, act_grad_src=t.hpre, act_grad_kind=ACT_GELU)
+    ops.swin_linear_wgrad(dh, t.ln2, M, blk.s_fc1, mlp.fc1.weight, grads[mlp.fc1.weight], grads[mlp.fc1.bias])
+    dln2 = empty(M, Cd, like=t.x)
+    ops.swin_linear_dgrad(dh, M, blk.s_fc1, mlp.fc1.weight, dln2)
+    ops.layernorm_bwd(dln2, t.x1, blk.norm2.weight, t.m2, t.r2, dx2, grads[blk.norm2.weight], grads[blk.norm2.bias], M, Cd, accumulate_dx=True)
+    return _attention_backward(blk, t, dx2, grads)
 
 
-def _fused_mlp_backward(blk, x1, packs, sc2, dx2, grads, M, Cd, HW):
+def _fused_mlp_backward(blk, t: BlockTape, dx2, grads):
     """Data gradient (dx1 = dx2 + branch gradient, LayerNorm parameter gradients) and weight gradients of the fused MLP branch:
     both recompute norm2 and the pre-activation from x1; the weight gradients run on the weight-gradient stream."""
+    x1, sc2, mlp, Cd, HW = t.x1, t.sc2, blk.mlp, blk.dim, blk.res * blk.res
+    M = t.I * HW
     unit = 2.0 * M * Cd * 4 * Cd
     eps = float(blk.norm2.eps)
     dx1 = empty(M, Cd, like=x1)
-    if ops.fused_mlp_mx_bwd_enabled(Cd):
-        # opt-in MXFP8 data gradient (set_fused_mlp_mx(True, backward=True)): the unfused MX backward chain of the branch in one kernel
-        packs_mx = ops.swin_mlp_mx_bwd_packs(blk.mlp.fc1.weight, blk.mlp.fc2.weight, Cd)
-        ops.traced_call("sv_swin_mlp_bwd_mx", 3 * unit, 6.0 * M * Cd, ptr(x1), ptr(dx2), ptr(dx1), ptr(blk.norm2.weight), ptr(blk.norm2.bias),
-                        ptr(packs_mx), ptr(blk.mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.norm2.weight]), ptr(grads[blk.norm2.bias]), M, Cd, eps,
-                        tag=f"M={M} C={Cd}")
-    else:
-        ops.traced_call("sv_swin_mlp_bwd", 3 * unit, 6.0 * M * Cd, ptr(x1), ptr(dx2), ptr(dx1), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(packs),
-                        ptr(blk.mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.norm2.weight]), ptr(grads[blk.norm2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
-    w1r, w2tr = blk.s_fc1.pack_fwd(blk.mlp.fc1.weight), blk.s_fc2.pack_dgrad(blk.mlp.fc2.weight)     # bf16 [4C][C] rows both
+    # opt-in MXFP8 data gradient (set_fused_mlp_mx(True, backward=True)): the unfused MX backward chain of the branch in one kernel
+    name, images = (("sv_swin_mlp_bwd_mx", ops.swin_mlp_mx_bwd_packs(mlp.fc1.weight, mlp.fc2.weight, Cd)) if ops.fused_mlp_mx_bwd_enabled(Cd)
+                    else ("sv_swin_mlp_bwd", t.packs))
+    ops.traced_call(name, 3 * unit, 6.0 * M * Cd, ptr(x1), ptr(dx2), ptr(dx1), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(images),
+                    ptr(mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.norm2.weight]), ptr(grads[blk.norm2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
+    w1r, w2tr = blk.s_fc1.pack_fwd(mlp.fc1.weight), blk.s_fc2.pack_dgrad(mlp.fc2.weight)     # bf16 [4C][C] rows both
 
     def launch():
         ops.traced_call("sv_swin_mlp_wgrad", 4 * unit, 4.0 * M * Cd, ptr(x1), ptr(dx2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(w1r), ptr(w2tr),
-                        ptr(blk.mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.mlp.fc1.weight]), ptr(grads[blk.mlp.fc1.bias]),
-                        ptr(grads[blk.mlp.fc2.weight]), ptr(grads[blk.mlp.fc2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
+                        ptr(mlp.fc1.bias), ptr(sc2), HW, ptr(grads[mlp.fc1.weight]), ptr(grads[mlp.fc1.bias]),
+                        ptr(grads[mlp.fc2.weight]), ptr(grads[mlp.fc2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
 
     aw = ops._CTX.awg
     if aw is not None:
@@ -315,13 +307,15 @@ def _fused_mlp_backward(blk, x1, packs, sc2, dx2, grads, M, Cd, HW):
     return dx1
 
 
-def _attention_backward(blk, x, m1, r1, ln1, qkv, att, sc1, dx1, grads, I, H, W, Cd, M):
+def _attention_backward(blk, t: BlockTape, dx1, grads):
     """x1 = x + s1 * proj(attn(qkv(ln1))): dx1 is consumed (accumulator of the residual path); returns dx."""
+    x, qkv, sc1, m1, r1, I, a = t.x, t.qkv, t.sc1, t.m1, t.r1, t.I, blk.attn
+    H = W = blk.res
+    Cd, M = blk.dim, I * H * W
     esz = 2.0 if x.dtype == torch.bfloat16 else 4.0
     if ops.fused_attn_block_bwd_enabled(Cd, blk.heads):
         # data path in ONE kernel: dx1 -> projection data gradient -> attention backward (P recomputed) -> qkv data gradient -> LayerNorm
         # backward + residual; dqkv goes to HBM for the weight gradients, which stay on the engine (weight-gradient stream)
-        a = blk.attn
         dqkv, dx = empty(M, 3 * Cd, like=x), empty(M, Cd, like=x)
         dbr = empty(M, Cd, like=x) if sc1 is not None else None
         ws = ops.zeros_f64(8 * 169 * blk.heads, x.device)    # sv_window_attention_bwd_workspace_floats(heads) floats, zero on entry
@@ -330,26 +324,26 @@ def _attention_backward(blk, x, m1, r1, ln1, qkv, att, sc1, dx1, grads, I, H, W,
                         ptr(a.relative_position_bias_table), ptr(sc1), ptr(dqkv), ptr(dx), ptr(dbr), ptr(grads[blk.norm1.weight]),
                         ptr(grads[blk.norm1.bias]), ptr(grads[a.relative_position_bias_table]), ptr(ws), I, H, W, Cd, blk.heads, blk.shift,
                         tag=f"M={M} C={Cd}")
-        ops.linear_wgrad(dbr if dbr is not None else dx1, att, M, blk.s_proj, grads[a.proj.weight], grads[a.proj.bias])
-        ops.linear_wgrad(dqkv, ln1, M, blk.s_qkv, grads[a.qkv.weight], grads[a.qkv.bias])
+        ops.linear_wgrad(dbr if dbr is not None else dx1, t.att, M, blk.s_proj, grads[a.proj.weight], grads[a.proj.bias])
+        ops.linear_wgrad(dqkv, t.ln1, M, blk.s_qkv, grads[a.qkv.weight], grads[a.qkv.bias])
         return dx
     # ---- attention branch: x1 = x + s1 * proj(attn(qkv(ln1)))
     dbr = dx1
     if sc1 is not None:
         dbr = empty(M, Cd, like=x)
         call("sv_rowscale", ptr(dx1), ptr(sc1), ptr(dbr), M, Cd, H * W)
-    ops.swin_linear_wgrad(dbr, att, M, blk.s_proj, blk.attn.proj.weight, grads[blk.attn.proj.weight], grads[blk.attn.proj.bias], async_ok=sc1 is not None)
+    ops.swin_linear_wgrad(dbr, t.att, M, blk.s_proj, a.proj.weight, grads[a.proj.weight], grads[a.proj.bias], async_ok=sc1 is not None)
     datt = empty(M, Cd, like=x)
-    ops.swin_linear_dgrad(dbr, M, blk.s_proj, blk.attn.proj.weight, datt)
+    ops.swin_linear_dgrad(dbr, M, blk.s_proj, a.proj.weight, datt)
     dqkv = empty(M, 3 * Cd, like=x)
     ws = ops.zeros_f64(8 * 169 * blk.heads, x.device)    # sv_window_attention_bwd_workspace_floats(heads) floats, zero on entry
     # backward = 2.5 x the forward products (recomputed P, dP, dQ, dK, dV); bytes: qkv + dout in, dqkv out
-    ops.traced_call("sv_window_attention_bwd", 10.0 * 49 * 32 * M * blk.heads, esz * 7 * M * Cd, ptr(qkv), ptr(blk.attn.relative_position_bias_table),
-                    ptr(datt), ptr(dqkv), ptr(grads[blk.attn.relative_position_bias_table]), ptr(ws), I, H, W, Cd, blk.heads, blk.shift,
+    ops.traced_call("sv_window_attention_bwd", 10.0 * 49 * 32 * M * blk.heads, esz * 7 * M * Cd, ptr(qkv), ptr(a.relative_position_bias_table),
+                    ptr(datt), ptr(dqkv), ptr(grads[a.relative_position_bias_table]), ptr(ws), I, H, W, Cd, blk.heads, blk.shift,
                     ops.attention_bwd_math(), tag=f"M={M} C={Cd}")
-    ops.swin_linear_wgrad(dqkv, ln1, M, blk.s_qkv, blk.attn.qkv.weight, grads[blk.attn.qkv.weight], grads[blk.attn.qkv.bias])
+    ops.swin_linear_wgrad(dqkv, t.ln1, M, blk.s_qkv, a.qkv.weight, grads[a.qkv.weight], grads[a.qkv.bias])
     dln1 = empty(M, Cd, like=x)
-    ops.swin_linear_dgrad(dqkv, M, blk.s_qkv, blk.attn.qkv.weight, dln1)
+    ops.swin_linear_dgrad(dqkv, M, blk.s_qkv, a.qkv.weight, dln1)
     ops.layernorm_bwd(dln1, x, blk.norm1.weight, m1, r1, dx1, grads[blk.norm1.weight], grads[blk.norm1.bias], M, Cd, accumulate_dx=True)
     return dx1
 
@@ -362,11 +356,11 @@ def stage_forward(stage: SwinStage, x, I, training, stochastic, seeds, save=True
         ds = stage.downsample
         Hin = stage.res * 2
         Mo = I * stage.res * stage.res
-        stm = save and ops.mx_store_site(ds.spec, ds.reduction.weight)
-        lnm, mm, rm, qm = _norm_for_linear(x, ds.norm, Mo, 2 * stage.dim, ds.spec, ds.reduction.weight, save, merge_hw=(Hin, Hin), store_mx=stm)
+        plan = ops.swin_linear_plan(ds.spec, ds.reduction.weight, save)
+        lnm, mm, rm, qm = _norm_for_linear(x, ds.norm, Mo, 2 * stage.dim, plan, save, merge_hw=(Hin, Hin))
         y = empty(Mo, stage.dim, like=x)
-        ops.swin_linear_fwd(lnm, Mo, ds.spec, ds.reduction.weight, y, xq=qm)
-        sctx["merge"] = (x, qm if stm else lnm, mm, rm, Mo, Hin)   # store "mx": the MX rows of the norm's output in place of the tensor
+        ops.swin_linear_fwd(lnm, Mo, ds.spec, ds.reduction.weight, y, xq=qm, plan=plan)
+        sctx["merge"] = MergeTape(x, qm if plan.keep else lnm, mm, rm, Mo, Hin)   # store "mx": the MX rows of the norm's output, not the tensor
         x = y
     for blk in stage.blocks:
         x, bctx = block_forward(blk, x, I, training, stochastic, seeds, save)
@@ -380,18 +374,18 @@ def stage_backward(stage: SwinStage, sctx, dx, grads, I):
         dx = block_backward(blk, bctx, dx, grads)
     if sctx["merge"] is not None:
         ds = stage.downsample
-        xin, lnm, mm, rm, Mo, Hin = sctx["merge"]
-        ops.swin_linear_wgrad(dx, lnm, Mo, ds.spec, ds.reduction.weight, grads[ds.reduction.weight], None)
-        dln = empty(Mo, 2 * stage.dim, like=dx)
-        ops.swin_linear_dgrad(dx, Mo, ds.spec, ds.reduction.weight, dln)
-        dxin = empty(I * Hin * Hin, stage.dim // 2, like=dx)
-        ops.layernorm_bwd(dln, xin, ds.norm.weight, mm, rm, dxin, grads[ds.norm.weight], grads[ds.norm.bias], Mo, 2 * stage.dim,
-                          merge_hw=(Hin, Hin))
+        mt = sctx["merge"]
+        ops.swin_linear_wgrad(dx, mt.ln, mt.rows, ds.spec, ds.reduction.weight, grads[ds.reduction.weight], None)
+        dln = empty(mt.rows, 2 * stage.dim, like=dx)
+        ops.swin_linear_dgrad(dx, mt.rows, ds.spec, ds.reduction.weight, dln)
+        dxin = empty(I * mt.Hin * mt.Hin, stage.dim // 2, like=dx)
+        ops.layernorm_bwd(dln, mt.x, ds.norm.weight, mt.mean, mt.rstd, dxin, grads[ds.norm.weight], grads[ds.norm.bias], mt.rows, 2 * stage.dim,
+                          merge_hw=(mt.Hin, mt.Hin))
         dx = dxin
     return dx
 
 
-def swin_forward(st: SwinTransformer, img_nhwc, I, training, stochastic, seeds, ready=None, save=True, patches=None):
+def swin_forward(st: SwinTransformer, img_nhwc, I, training, stochastic, seeds, ready=None, save=True, *, patches=None):
     """img_nhwc [I,224,224,3] - or `patches` [I*56*56, 48], the 4 x 4 x 3 pixel blocks as rows [(ky, kx, c)] (sv_encoder_prep) - -> list of
     stage-head outputs [I*HW, C] (NHWC rows) + tape.  `ready` (optional list) receives one event per head output, recorded on the current
     stream as soon as that output is complete, so that another stream can consume the early stages while the later ones are still being
@@ -428,7 +422,7 @@ def swin_forward(st: SwinTransformer, img_nhwc, I, training, stochastic, seeds, 
             ops.transpose(ln.bias, bt, 1, Cs, Hs * Hs)
             y = empty(I * Hs * Hs, Cs, like=x)
             mr = fempty(2 * I, like=x)
-            ws = fempty(int(hipws(I, L)), like=x)
+            ws = fempty(int(ops.hip.load().sv_ln_image_workspace_floats(I, L)), like=x)
             p = st.dropout.p if (training and stochastic) else 0.0
             seed = seeds() if p > 0 else 0
             call("sv_ln_image_fwd", ptr(x), ptr(wt), ptr(bt), ptr(y), ptr(mr), ptr(ws), I, L, float(ln.eps), float(p), seed, ops.seed_epoch_ptr())
@@ -440,11 +434,6 @@ def swin_forward(st: SwinTransformer, img_nhwc, I, training, stochastic, seeds, 
                 ready.append(ev)
             head_i += 1
     return feats, tape
-
-
-def hipws(I, L):
-    from .. import hip
-    return hip.load().sv_ln_image_workspace_floats(I, L)
 
 
 def swin_backward(st: SwinTransformer, tape, dfeats, I, grads, ready=None, need_dx=False):

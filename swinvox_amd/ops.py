@@ -8,9 +8,10 @@ dtype (fp32, or bf16 under set_storage("bf16")); parameters, their gradients and
 from __future__ import annotations
 
 import ctypes as C
+import os
 import threading
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -35,6 +36,14 @@ class _CallContext(threading.local):
 _CTX = _CallContext()
 BN_SLOTS = 16   # SV_BN_SLOTS of include/swinvox_hip.h
 BN_BWD_SLOTS, LN_BWD_SLOTS = 16, 32   # slot counts behind sv_bn_bwd_workspace_doubles / sv_layernorm_bwd_workspace_floats
+
+
+def _switch(key: str, env: str, default: bool) -> bool:
+    """An A/B switch: the flag set_X() keeps in _STATE, or the environment variable.  A default-on switch is switched OFF by set_X(False) or
+    VAR=0, a default-off switch is switched ON by set_X(True) or VAR=1."""
+    if default:
+        return bool(_STATE.get(key, True)) and os.environ.get(env, "1") != "0"
+    return bool(_STATE.get(key, False)) or os.environ.get(env, "0") == "1"
 
 
 def set_math(mode: str) -> None:
@@ -479,7 +488,6 @@ def traced_call(name, flops, nbytes, *args, tag=""):
 
 def fused_mlp_enabled(C: int) -> bool:
     """The fused Swin MLP kernels (csrc/swin_mlp.hip) serve bf16 MFMA + bf16 storage and the channel counts they are built for."""
-    import os
     # C = 192 (Swin-T stage 1) is built too, but since the wide dense kernels (csrc/igemm.hip) serve K = 192 the unfused chain is the faster
     # one there: 123.0 -> 121.7 ms per step at B = 64.  SV_FUSED_MLP_MAX_C overrides the limit for measurements.
     lim = int(os.environ.get("SV_FUSED_MLP_MAX_C", "128"))
@@ -490,8 +498,7 @@ def fused_mlp_enabled(C: int) -> bool:
 def fused_attn_block_enabled(C: int, heads: int) -> bool:
     """The fused attention branch (LayerNorm -> qkv -> window attention -> proj -> residual, csrc/attn.hip) serves stage 0 of Swin-T
     (C = 96, 3 heads) in bf16 MFMA + bf16 storage; fp8 attention keeps the unfused chain (its core kernel is a separate build)."""
-    import os
-    if os.environ.get("SV_FUSED_ATTN_BLOCK", "1") == "0" or not _STATE.get("fused_attn_block", True) or _STATE.get("attn_fp8"):
+    if not _switch("fused_attn_block", "SV_FUSED_ATTN_BLOCK", True) or _STATE.get("attn_fp8"):
         return False
     return (_STATE["math"] == hip.MATH_BF16 and _STATE["store"] == torch.bfloat16
             and hip.load().sv_swin_attn_block_supported(C, heads, hip.BF16, hip.MATH_BF16) == 1)
@@ -502,8 +509,7 @@ def fused_attn_block_bwd_enabled(C: int, heads: int) -> bool:
     reads what either forward stores (qkv, LayerNorm statistics), so fp8 attention in the forward does not switch it off.
     A/B: SV_FUSED_ATTN_BWD=0 or set_fused_attn_block_bwd(False) route the branch through the unfused four-kernel chain.  The fp8
     backward (set_attention_fp8(True, backward=True)) switches it off: its core kernel is a separate build."""
-    import os
-    if os.environ.get("SV_FUSED_ATTN_BWD", "1") == "0" or not _STATE.get("fused_attn_block_bwd", True):
+    if not _switch("fused_attn_block_bwd", "SV_FUSED_ATTN_BWD", True):
         return False
     if _STATE.get("attn_fp8") and _STATE.get("attn_fp8_bwd"):
         return False
@@ -559,8 +565,7 @@ def set_fused_mlp_mx(on: bool, backward: bool = False) -> None:
 
 def fused_mlp_mx_enabled(C: int) -> bool:
     """The MXFP8 forward of the fused Swin MLP: the switch, the fused MLP itself, MX linears, bf16 math and storage, C in {96, 128}."""
-    import os
-    if not (_STATE.get("fused_mlp_mx", False) or os.environ.get("SV_FUSED_MLP_MX", "0") == "1"):
+    if not _switch("fused_mlp_mx", "SV_FUSED_MLP_MX", False):
         return False
     return (fused_mlp_enabled(C) and linear_fp8_enabled() and linear_fp8_recipe() == "mx"
             and _STATE["math"] == hip.MATH_BF16 and _STATE["store"] == torch.bfloat16 and hip.load().sv_swin_mlp_mx_supported(C) == 1)
@@ -583,8 +588,7 @@ def swin_mlp_mx_packs(w1: torch.Tensor, w2: torch.Tensor, C: int) -> torch.Tenso
 def fused_mlp_mx_bwd_enabled(C: int) -> bool:
     """The MXFP8 data gradient of the fused Swin MLP: its switch, the MX forward of the same block (fused_mlp_mx_enabled), the MX backward recipe
     of the Swin linears and a C the library serves.  Inert everywhere else."""
-    import os
-    if not (_STATE.get("fused_mlp_mx_bwd", False) or os.environ.get("SV_FUSED_MLP_MX_BWD", "0") == "1"):
+    if not _switch("fused_mlp_mx_bwd", "SV_FUSED_MLP_MX_BWD", False):
         return False
     return (fused_mlp_mx_enabled(C) and linear_fp8_bwd_enabled() and linear_fp8_bwd_recipe() == "mx"
             and hip.load().sv_swin_mlp_bwd_mx_supported(C) == 1)
@@ -675,8 +679,7 @@ def set_mx_producer_quant(on: bool) -> None:
 
 
 def mx_producer_quant_enabled() -> bool:
-    import os
-    return _mx() and _STATE.get("mx_producer_quant", True) and os.environ.get("SV_MX_PRODUCER_QUANT", "1") != "0"
+    return _mx() and _switch("mx_producer_quant", "SV_MX_PRODUCER_QUANT", True)
 
 
 _MX_ACT_QUANT = [0]
@@ -692,39 +695,53 @@ def linear_mxfp8_launches() -> int:
     return int(hip.load().sv_linear_mxfp8_launches())
 
 
+def _dtype_code(t: torch.Tensor) -> int:
+    return hip.BF16 if t.dtype == torch.bfloat16 else hip.F32
+
+
+def operand_buffers(rows: int, K: int, mx: bool, device):
+    """The uninitialised (e4m3 bytes [rows, roundup(K, 128)], scales) pair of a quantised operand: fp32 scales [rows], one per row, or - mx -
+    E8M0 block scales [rows, roundup(K, 128) / 32] uint8, one per 32 consecutive elements of a row."""
+    Kp = (K + 127) // 128 * 128
+    q = torch.empty(rows, Kp, dtype=torch.uint8, device=device)
+    if mx:
+        return q, torch.empty(rows, Kp // 32, dtype=torch.uint8, device=device)
+    return q, torch.empty(rows, dtype=torch.float32, device=device)
+
+
 def quantize_rows_mx(t: torch.Tensor, rows: int, K: int, ld: Optional[int] = None, activation: bool = True):
     """t [rows, K] (fp32 or bf16, row stride ld) -> (e4m3 bytes [rows, roundup(K, 128)], E8M0 block scales [rows, roundup(K, 128) / 32] uint8)
     by sv_quant_rows_mx_e4m3."""
-    Kp = (K + 127) // 128 * 128
-    q = torch.empty(rows, Kp, dtype=torch.uint8, device=t.device)
-    sc = torch.empty(rows, Kp // 32, dtype=torch.uint8, device=t.device)
-    call("sv_quant_rows_mx_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, K, ld or K, ptr(q), Kp, ptr(sc))
+    q, sc = operand_buffers(rows, K, True, t.device)
+    call("sv_quant_rows_mx_e4m3", ptr(t), _dtype_code(t), rows, K, ld or K, ptr(q), q.shape[1], ptr(sc))
     if activation:
         _MX_ACT_QUANT[0] += 1
     return q, sc
 
 
-def quantize_weight_mx(w: torch.Tensor):
-    """MX rows of a Linear weight [N, K], cached like quantize_weight_fp8's for the running forward of the module."""
+def _weight_operand(w: torch.Tensor, table: str, quantise):
+    """quantise(w, N, K) of a Linear weight [N, K]: one small launch, kept in PackCache table `table` for the running forward of the module
+    (weights change only in optimizer.step(), the lifetime of the weight packs)."""
     cache = _CTX.packs
     if cache is None or not isinstance(w, torch.nn.Parameter):
-        return quantize_rows_mx(w, w.shape[0], w.shape[1], activation=False)
-    hit = cache.w8mx.get(id(w))
+        return quantise(w, w.shape[0], w.shape[1])
+    held = getattr(cache, table)
+    hit = held.get(id(w))
     if hit is None:
-        hit = cache.w8mx[id(w)] = quantize_rows_mx(w, w.shape[0], w.shape[1], activation=False)
+        hit = held[id(w)] = quantise(w, w.shape[0], w.shape[1])
     return hit
 
 
+def quantize_weight_mx(w: torch.Tensor):
+    """MX rows of a Linear weight [N, K] (not counted as an activation quantiser launch)."""
+    return _weight_operand(w, "w8mx", lambda t, N, K: quantize_rows_mx(t, N, K, activation=False))
+
+
 def mx_emit_site(cons_spec: ConvSpec, cons_w, cons_epi: dict, prod_spec: Optional[ConvSpec] = None, prod_w=None, prod_epi: Optional[dict] = None) -> bool:
-    """Whether the producer of a Swin linear's input emits that linear's MX operand rows: recipe "mx", the producer switch on, the consuming
-    linear (cons_*) takes the MX kernel, and - when the producer is a linear itself (prod_*: fc1 in front of fc2) - it takes the MX kernel too,
-    carries no residual and has N % 128 == 0.  With set_linear_fp8 off this is one flag test."""
-    if not mx_producer_quant_enabled() or swin_linear_fp8_epilogue(cons_spec, cons_w, **cons_epi) is None:
-        return False
-    if prod_spec is None:
-        return True
-    return (prod_spec.cout % 128 == 0 and prod_epi.get("residual") is None
-            and swin_linear_fp8_epilogue(prod_spec, prod_w, **prod_epi) is not None)
+    """Whether the producer of a Swin linear's input emits that linear's MX operand rows (LinearPlan.prod_emits); prod_*: the producer when it is
+    a linear itself (fc1 in front of fc2).  With set_linear_fp8 off this is one flag test."""
+    producer = True if prod_spec is None else swin_linear_plan(prod_spec, prod_w, False, **prod_epi)
+    return swin_linear_plan(cons_spec, cons_w, False, producer=producer, **cons_epi).prod_emits
 
 
 def linear_fp8_bwd_enabled() -> bool:
@@ -743,10 +760,9 @@ def linear_fp8_store() -> str:
 
 
 def mx_store_site(spec: ConvSpec, w, **epi) -> bool:
-    """Whether the tape keeps the MX rows of this Swin linear's input in place of the tensor (**epi: the linear's epilogue form): the store
-    switch is effective, the linear takes the MX forward kernel and its weight gradient the MX kernel.  The one copy of the per-site condition;
-    with the switch off this is one flag test."""
-    return linear_fp8_store() == "mx" and _fp8_bwd_site(spec, w) and swin_linear_fp8_epilogue(spec, w, **epi) is not None
+    """Whether the tape keeps the MX rows of this Swin linear's input in place of the tensor (**epi: the linear's epilogue form;
+    LinearPlan.keep of a forward that saves).  With the switch off this is one flag test."""
+    return linear_fp8_store() == "mx" and swin_linear_plan(spec, w, True, **epi).keep
 
 
 def mx_rows_to_cols_launches() -> int:
@@ -758,10 +774,8 @@ def mx_rows_to_cols(xq: torch.Tensor, xs: torch.Tensor, rows: int, K: int):
     """MX rows (xq [rows, roundup(K, 128)] e4m3 bytes, xs [rows, roundup(K, 128) / 32] E8M0 bytes) -> the MX column operand of the weight
     gradient (bytes [K, roundup(rows, 128)], block scales [K, roundup(rows, 128) / 32]; a block = 32 tokens of a column) by sv_mx_rows_to_cols:
     equal to quantize_cols_mx on the dequantised rows."""
-    Mp = (rows + 127) // 128 * 128
-    q = torch.empty(K, Mp, dtype=torch.uint8, device=xq.device)
-    sc = torch.empty(K, Mp // 32, dtype=torch.uint8, device=xq.device)
-    call("sv_mx_rows_to_cols", ptr(xq), xq.shape[1], ptr(xs), rows, K, ptr(q), Mp, ptr(sc))
+    q, sc = operand_buffers(K, rows, True, xq.device)
+    call("sv_mx_rows_to_cols", ptr(xq), xq.shape[1], ptr(xs), rows, K, ptr(q), q.shape[1], ptr(sc))
     return q, sc
 
 
@@ -784,23 +798,14 @@ def linear_fp8_launches() -> int:
 
 def quantize_rows_fp8(t: torch.Tensor, rows: int, K: int, ld: Optional[int] = None):
     """t [rows, K] (fp32 or bf16, row stride ld) -> (e4m3 bytes [rows, roundup(K, 128)], fp32 row scales [rows]) by sv_quant_rows_e4m3."""
-    Kp = (K + 127) // 128 * 128
-    q = torch.empty(rows, Kp, dtype=torch.uint8, device=t.device)
-    sc = torch.empty(rows, dtype=torch.float32, device=t.device)
-    call("sv_quant_rows_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, K, ld or K, ptr(q), Kp, ptr(sc))
+    q, sc = operand_buffers(rows, K, False, t.device)
+    call("sv_quant_rows_e4m3", ptr(t), _dtype_code(t), rows, K, ld or K, ptr(q), q.shape[1], ptr(sc))
     return q, sc
 
 
 def quantize_weight_fp8(w: torch.Tensor):
-    """Quantised rows of a Linear weight [N, K]: one small launch, cached for the running forward of the module (weights change only in
-    optimizer.step(), the lifetime of the weight packs)."""
-    cache = _CTX.packs
-    if cache is None or not isinstance(w, torch.nn.Parameter):
-        return quantize_rows_fp8(w, w.shape[0], w.shape[1])
-    hit = cache.w8.get(id(w))
-    if hit is None:
-        hit = cache.w8[id(w)] = quantize_rows_fp8(w, w.shape[0], w.shape[1])
-    return hit
+    """Quantised rows and row scales of a Linear weight [N, K]."""
+    return _weight_operand(w, "w8", quantize_rows_fp8)
 
 
 def swin_linear_fp8_epilogue(spec: ConvSpec, w, **epi):
@@ -814,72 +819,102 @@ def swin_linear_fp8_epilogue(spec: ConvSpec, w, **epi):
     return e if hip.load().sv_linear_fp8_supported(spec.cin, spec.cout, C.byref(e), _STATE["math"], hip.ACT) == 1 else None
 
 
-def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, xq=None, emit=False, **epi):
+# What the row and the MX recipe of the fp8 Swin linears differ in besides their MX-only parts: the three entry points, and the quantisers of
+# activation rows, of their transpose, of W and of W^T BY NAME - looked up in the module's globals at every call (_fn), so that a replaced
+# ops.quantize_* is the one that runs.
+_Recipe = NamedTuple("_Recipe", [("mx", bool)] + [(f, str) for f in ("fwd", "dgrad", "wgrad", "rows", "cols", "weight", "weight_t")])
+_RECIPES = {
+    "row": _Recipe(False, "sv_linear_fp8", "sv_linear_fp8_dgrad", "sv_linear_fp8_wgrad",
+                   "quantize_rows_fp8", "quantize_cols_fp8", "quantize_weight_fp8", "quantize_weight_t_fp8"),
+    "mx": _Recipe(True, "sv_linear_mxfp8", "sv_linear_mxfp8_dgrad", "sv_linear_mxfp8_wgrad",
+                  "quantize_rows_mx", "quantize_cols_mx", "quantize_weight_mx", "quantize_weight_t_mx"),
+}
+
+
+def _fn(name: str):
+    return globals()[name]
+
+
+class LinearPlan(NamedTuple):
+    """How one Swin linear runs its forward and who quantises its input rows (swin_linear_plan)."""
+    kind: Optional[str]          # None: the contraction engine; "row" / "mx": the fp8 kernel of that recipe
+    epi: Optional[Epilogue]      # the sv_epilogue of the fp8 kernel (of `form`)
+    form: dict                   # the epilogue keywords the plan was made with
+    ln_emits: bool = False       # the LayerNorm in front emits the quantised rows (row: set_ln_quant_fused, MX: set_ln_quant_mx)
+    prod_emits: bool = False     # the producer in front (window attention, fc1) emits the MX rows (set_mx_producer_quant)
+    keep: bool = False           # the tape keeps the MX rows of the input in place of the tensor (store "mx")
+    may_emit: bool = False       # as a producer this linear can emit the MX rows of its output
+
+
+def swin_linear_plan(spec: ConvSpec, w, save, producer=None, **epi) -> LinearPlan:
+    """The one evaluation of swin_linear_fp8_epilogue for a Swin linear with epilogue form **epi, asked BEFORE its input is produced.
+    save: a backward will read this site's tape entry.  producer: None when a LayerNorm feeds the linear, True for the window attention, the
+    LinearPlan of the linear in front (fc1 in front of fc2: it emits only if it takes the MX kernel itself, carries no residual and has
+    N % 128 == 0).  ln_quant_site / ln_quant_mx_site / mx_emit_site / mx_store_site are these conditions under their historical names.
+    With set_linear_fp8 off this is one flag test."""
+    e = swin_linear_fp8_epilogue(spec, w, **epi)
+    if e is None:
+        return LinearPlan(None, None, epi)
+    kind = linear_fp8_recipe()
+    return LinearPlan(kind, e, epi,
+                      ln_emits=producer is None and (ln_quant_fused_enabled() or ln_quant_mx_enabled()),
+                      prod_emits=producer is not None and mx_producer_quant_enabled() and (producer is True or producer.may_emit),
+                      keep=bool(save) and linear_fp8_store() == "mx" and _fp8_bwd_site(spec, w),
+                      may_emit=kind == "mx" and spec.cout % 128 == 0 and epi.get("residual") is None)
+
+
+def swin_linear_fwd(x, rows, spec: ConvSpec, w, out, xq=None, emit=False, plan: Optional[LinearPlan] = None, **epi):
     """linear_fwd of the Swin call sites: with set_linear_fp8(True) (and a form sv_linear_fp8 serves) the activation rows are quantised, the
-    quantised weight fetched and the product runs on the fp8 kernel; otherwise exactly linear_fwd.  xq = (bytes, scales): the rows of x
-    already quantised by its producer (layernorm_quant_fwd; under recipe "mx" the MX pair of an emitting fc1 or window attention), which the
-    caller obtained because swin_linear_fp8_epilogue said this linear takes the fp8 kernel; the quantiser pass is skipped and x itself is not
-    read (it may be None).  emit=True (recipe "mx" only, the caller asked mx_emit_site): the kernel also writes the MX rows of its stored
+    quantised weight fetched and the product runs on the fp8 kernel; otherwise exactly linear_fwd.  plan: this site's swin_linear_plan, when
+    the caller made it already; **epi then holds only the keywords that were not known at that time (pre_act).  xq = (bytes, scales): the rows
+    of x already quantised by its producer (layernorm_quant_fwd; under recipe "mx" the MX pair of an emitting fc1 or window attention), which
+    the caller obtained because the plan said this linear takes the fp8 kernel; the quantiser pass is skipped and x itself is not read (it may
+    be None).  emit=True (recipe "mx" only, the plan of the consumer said prod_emits): the kernel also writes the MX rows of its stored
     output, returned as (bytes, scales); `out` may then be None: besides the rows only pre_act is written, when it is given (the library
     serves that form in front of an activation only: fc1)."""
-    e = swin_linear_fp8_epilogue(spec, w, **epi)
-    if e is not None and linear_fp8_recipe() == "mx":
-        xq, xs = xq if xq is not None else quantize_rows_mx(x, rows, spec.cin)
-        wq, ws = quantize_weight_mx(w)
-        q_out = qs_out = None
-        if emit:
-            q_out = torch.empty(rows, spec.cout, dtype=torch.uint8, device=xq.device)
-            qs_out = torch.empty(rows, spec.cout // 32, dtype=torch.uint8, device=xq.device)
-        esz = 0 if out is None else out.element_size()
-        if out is None and epi.get("pre_act") is not None:
-            esz = epi["pre_act"].element_size()            # the form without out (store "mx"): pre_act is the tensor the call writes
-        traced_call("sv_linear_mxfp8", 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + (esz + (1 if emit else 0)) * spec.cout) + wq.numel(),
-                    ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(out), rows, spec.cin, spec.cout, C.byref(e), ptr(q_out), ptr(qs_out),
-                    tag=f"M={rows} K={spec.cin} N={spec.cout}")
-        return (q_out, qs_out) if emit else None
-    if emit:
+    if plan is None:
+        plan, epi = swin_linear_plan(spec, w, False, **epi), {}
+    if emit and plan.kind != "mx":
         raise RuntimeError("swin_linear_fwd: emit=True was passed to a linear that does not take the MX kernel")
-    if e is not None:
-        xq, sx = xq if xq is not None else quantize_rows_fp8(x, rows, spec.cin)
-        wq, sw = quantize_weight_fp8(w)
-        traced_call("sv_linear_fp8", 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + out.element_size() * spec.cout) + wq.numel(),
-                    ptr(xq), ptr(sx), ptr(wq), ptr(sw), ptr(out), rows, spec.cin, spec.cout, C.byref(e), tag=f"M={rows} K={spec.cin} N={spec.cout}")
-        return
-    if xq is not None:
-        raise RuntimeError("swin_linear_fwd: pre-quantised rows were passed to a linear that does not take the fp8 kernel")
-    linear_fwd(x, rows, spec, w, out, **epi)
+    if plan.kind is None:
+        if xq is not None:
+            raise RuntimeError("swin_linear_fwd: pre-quantised rows were passed to a linear that does not take the fp8 kernel")
+        return linear_fwd(x, rows, spec, w, out, **plan.form, **epi)
+    r = _RECIPES[plan.kind]
+    e = _epilogue(spec.cout, **plan.form, **epi) if epi else plan.epi
+    xq, xs = xq if xq is not None else _fn(r.rows)(x, rows, spec.cin)
+    wq, ws = _fn(r.weight)(w)
+    esz, emitted = (0 if out is None else out.element_size()), ()
+    if r.mx:
+        pre = epi.get("pre_act", plan.form.get("pre_act"))
+        if out is None and pre is not None:
+            esz = pre.element_size()                       # the form without out (store "mx"): pre_act is the tensor the call writes
+        emitted = operand_buffers(rows, spec.cout, True, xq.device) if emit else (None, None)     # N % 128 == 0: no padding
+    traced_call(r.fwd, 2.0 * rows * spec.cin * spec.cout, float(rows) * (xq.shape[1] + (esz + (1 if emit else 0)) * spec.cout) + wq.numel(),
+                ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(out), rows, spec.cin, spec.cout, C.byref(e), *[ptr(t) for t in emitted],
+                tag=f"M={rows} K={spec.cin} N={spec.cout}")
+    return emitted if emit else None
 
 
 def quantize_cols_fp8(t: torch.Tensor, rows: int, Cc: int, ld: Optional[int] = None, colsum: Optional[torch.Tensor] = None):
     """t [rows, Cc] (fp32 or bf16, row stride ld) -> (e4m3 bytes of the TRANSPOSE [Cc, roundup(rows, 128)], fp32 column scales [Cc]) by
     sv_quant_cols_e4m3; colsum (fp32 [Cc]) += the column sums of the unquantised values."""
-    Mp = (rows + 127) // 128 * 128
-    q = torch.empty(Cc, Mp, dtype=torch.uint8, device=t.device)
-    sc = torch.empty(Cc, dtype=torch.float32, device=t.device)
-    call("sv_quant_cols_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, Cc, ld or Cc, ptr(q), Mp, ptr(sc), ptr(colsum))
+    q, sc = operand_buffers(Cc, rows, False, t.device)
+    call("sv_quant_cols_e4m3", ptr(t), _dtype_code(t), rows, Cc, ld or Cc, ptr(q), q.shape[1], ptr(sc), ptr(colsum))
     return q, sc
 
 
 def quantize_weight_t_fp8(w: torch.Tensor):
-    """Quantised rows of W^T for a Linear weight W [N, K] (one scale per column k of W): the operand of the fp8 data gradient, cached next to
-    quantize_weight_fp8's rows with the same lifetime."""
-    cache = _CTX.packs
-    if cache is None or not isinstance(w, torch.nn.Parameter):
-        return quantize_cols_fp8(w, w.shape[0], w.shape[1])
-    hit = cache.w8t.get(id(w))
-    if hit is None:
-        hit = cache.w8t[id(w)] = quantize_cols_fp8(w, w.shape[0], w.shape[1])
-    return hit
+    """Quantised rows of W^T for a Linear weight W [N, K] (one scale per column k of W): the operand of the fp8 data gradient."""
+    return _weight_operand(w, "w8t", quantize_cols_fp8)
 
 
 def quantize_cols_mx(t: torch.Tensor, rows: int, Cc: int, ld: Optional[int] = None, colsum: Optional[torch.Tensor] = None):
     """t [rows, Cc] (fp32 or bf16, row stride ld) -> (e4m3 bytes of the TRANSPOSE [Cc, roundup(rows, 128)], E8M0 block scales
     [Cc, roundup(rows, 128) / 32] uint8, a block = 32 consecutive rows of one column) by sv_quant_cols_mx_e4m3: one launch, t read once;
     colsum (fp32 [Cc]) += the column sums of the unquantised values."""
-    Mp = (rows + 127) // 128 * 128
-    q = torch.empty(Cc, Mp, dtype=torch.uint8, device=t.device)
-    sc = torch.empty(Cc, Mp // 32, dtype=torch.uint8, device=t.device)
-    call("sv_quant_cols_mx_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, Cc, ld or Cc, ptr(q), Mp, ptr(sc), ptr(colsum))
+    q, sc = operand_buffers(Cc, rows, True, t.device)
+    call("sv_quant_cols_mx_e4m3", ptr(t), _dtype_code(t), rows, Cc, ld or Cc, ptr(q), q.shape[1], ptr(sc), ptr(colsum))
     return q, sc
 
 
@@ -892,14 +927,9 @@ def quantize_rows_cols_mx(t: torch.Tensor, rows: int, N: int, ld: Optional[int] 
     """t [rows, N] (fp32 or bf16, row stride ld) -> ((dq, ds), (dyt, dys)) by sv_quant_rows_cols_mx_e4m3, one launch and one read of t: (dq, ds)
     equals quantize_rows_mx(t) and (dyt, dys) equals quantize_cols_mx(t), bit for bit; colsum (fp32 [N]) += the column sums of the unquantised
     values.  rows_out=False: the column form alone, (None, (dyt, dys))."""
-    Np, Mp = (N + 127) // 128 * 128, (rows + 127) // 128 * 128
-    dq = ds = None
-    if rows_out:
-        dq = torch.empty(rows, Np, dtype=torch.uint8, device=t.device)
-        ds = torch.empty(rows, Np // 32, dtype=torch.uint8, device=t.device)
-    q = torch.empty(N, Mp, dtype=torch.uint8, device=t.device)
-    sc = torch.empty(N, Mp // 32, dtype=torch.uint8, device=t.device)
-    call("sv_quant_rows_cols_mx_e4m3", ptr(t), hip.BF16 if t.dtype == torch.bfloat16 else hip.F32, rows, N, ld or N, ptr(dq), Np, ptr(ds), ptr(q), Mp,
+    dq, ds = operand_buffers(rows, N, True, t.device) if rows_out else (None, None)
+    q, sc = operand_buffers(N, rows, True, t.device)
+    call("sv_quant_rows_cols_mx_e4m3", ptr(t), _dtype_code(t), rows, N, ld or N, ptr(dq), (N + 127) // 128 * 128, ptr(ds), ptr(q), q.shape[1],
          ptr(sc), ptr(colsum))
     return ((dq, ds) if rows_out else None), (q, sc)
 
@@ -915,21 +945,13 @@ def set_mx_dual_quant(on: bool) -> None:
 
 
 def mx_dual_quant_enabled() -> bool:
-    import os
-    return (linear_fp8_bwd_enabled() and linear_fp8_bwd_recipe() == "mx"
-            and (_STATE.get("mx_dual_quant", False) or os.environ.get("SV_MX_DUAL_QUANT", "0") == "1"))
+    return linear_fp8_bwd_enabled() and linear_fp8_bwd_recipe() == "mx" and _switch("mx_dual_quant", "SV_MX_DUAL_QUANT", False)
 
 
 def quantize_weight_t_mx(w: torch.Tensor):
     """MX rows of W^T for a Linear weight W [N, K] ([K][Np] bytes, a block = 32 consecutive n of one column k): the operand of the MX data
-    gradient, cached next to quantize_weight_t_fp8's rows with the same lifetime."""
-    cache = _CTX.packs
-    if cache is None or not isinstance(w, torch.nn.Parameter):
-        return quantize_cols_mx(w, w.shape[0], w.shape[1])
-    hit = cache.w8mxt.get(id(w))
-    if hit is None:
-        hit = cache.w8mxt[id(w)] = quantize_cols_mx(w, w.shape[0], w.shape[1])
-    return hit
+    gradient."""
+    return _weight_operand(w, "w8mxt", quantize_cols_mx)
 
 
 def _fp8_bwd_site(spec: ConvSpec, w) -> bool:
@@ -937,30 +959,32 @@ def _fp8_bwd_site(spec: ConvSpec, w) -> bool:
             and isinstance(w, torch.nn.Parameter))
 
 
+def _fp8_dgrad_epilogue(spec: ConvSpec, **epi):
+    """The sv_epilogue of the fp8 data gradient of an _fp8_bwd_site, None when the library does not serve the form."""
+    e = _epilogue(spec.cin, **epi)
+    return e if hip.load().sv_linear_fp8_dgrad_supported(spec.cout, spec.cin, C.byref(e), _STATE["math"], hip.ACT) == 1 else None
+
+
 def swin_linear_dgrad(dy, rows, spec: ConvSpec, w, dx, **epi):
     """linear_dgrad of the unfused Swin call sites (w is the PARAMETER): with set_linear_fp8(True, backward=True) (and a form
     sv_linear_fp8_dgrad serves) dy is quantised per row, the quantised W^T fetched and the product runs on the fp8 kernel; otherwise exactly
     linear_dgrad on the data-gradient weight pack.  Under the MX recipe the rows of dy come from the stash of the dual quantiser when it holds
     this very tensor (set_mx_dual_quant, swin_linear_wgrad); the slot is emptied by the look either way."""
-    if _fp8_bwd_site(spec, w):
-        e = _epilogue(spec.cin, **epi)
-        if hip.load().sv_linear_fp8_dgrad_supported(spec.cout, spec.cin, C.byref(e), _STATE["math"], hip.ACT) == 1:
-            if linear_fp8_bwd_recipe() == "mx":
-                st, _CTX.dyq = _CTX.dyq, None              # the dual quantiser's rows of this very dy (swin_linear_wgrad), taken once
-                if st is not None and st[0] is dy and st[1] == rows and st[2] == spec.cout:
-                    dq, ds = st[3], st[4]
-                else:
-                    dq, ds = quantize_rows_mx(dy, rows, spec.cout, activation=False)
-                wtq, wts = quantize_weight_t_mx(w)
-                traced_call("sv_linear_mxfp8_dgrad", 2.0 * rows * spec.cin * spec.cout, float(rows) * (dq.shape[1] + dy.element_size() * spec.cin) + wtq.numel(),
-                            ptr(dq), ptr(ds), ptr(wtq), ptr(wts), ptr(dx), rows, spec.cout, spec.cin, C.byref(e), tag=f"M={rows} N={spec.cout} K={spec.cin}")
-                return
-            dq, sd = quantize_rows_fp8(dy, rows, spec.cout)
-            wtq, swt = quantize_weight_t_fp8(w)
-            traced_call("sv_linear_fp8_dgrad", 2.0 * rows * spec.cin * spec.cout, float(rows) * (dq.shape[1] + dy.element_size() * spec.cin) + wtq.numel(),
-                        ptr(dq), ptr(sd), ptr(wtq), ptr(swt), ptr(dx), rows, spec.cout, spec.cin, C.byref(e), tag=f"M={rows} N={spec.cout} K={spec.cin}")
-            return
-    linear_dgrad(dy, rows, spec, spec.pack_dgrad(w), dx, **epi)
+    e = _fp8_dgrad_epilogue(spec, **epi) if _fp8_bwd_site(spec, w) else None
+    if e is None:
+        return linear_dgrad(dy, rows, spec, spec.pack_dgrad(w), dx, **epi)
+    r = _RECIPES[linear_fp8_bwd_recipe()]
+    if r.mx:
+        st, _CTX.dyq = _CTX.dyq, None                      # the dual quantiser's rows of this very dy (swin_linear_wgrad), taken once
+        if st is not None and st[0] is dy and st[1] == rows and st[2] == spec.cout:
+            dq, ds = st[3], st[4]
+        else:
+            dq, ds = quantize_rows_mx(dy, rows, spec.cout, activation=False)
+    else:
+        dq, ds = quantize_rows_fp8(dy, rows, spec.cout)
+    wtq, wts = _fn(r.weight_t)(w)
+    traced_call(r.dgrad, 2.0 * rows * spec.cin * spec.cout, float(rows) * (dq.shape[1] + dy.element_size() * spec.cin) + wtq.numel(),
+                ptr(dq), ptr(ds), ptr(wtq), ptr(wts), ptr(dx), rows, spec.cout, spec.cin, C.byref(e), tag=f"M={rows} N={spec.cout} K={spec.cin}")
 
 
 def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True):
@@ -980,39 +1004,36 @@ def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True
     is cleared here on entry, by AsyncWgrad.join() and by set_async_wgrad()."""
     pair = isinstance(x, tuple)
     _CTX.dyq = None
-    mx_site = _fp8_bwd_site(spec, w) and linear_fp8_bwd_recipe() == "mx"
-    if pair and not mx_site:
+    site, r = _fp8_bwd_site(spec, w), _RECIPES[linear_fp8_bwd_recipe()]
+    if pair and not (site and r.mx):
         raise RuntimeError("swin_linear_wgrad: stored MX rows were passed to a linear whose weight gradient does not take the MX kernel")
-    if not _fp8_bwd_site(spec, w):
+    if not site:
         return linear_wgrad(dy, x, rows, spec, dw, db, async_ok=async_ok)
 
-    dual = mx_site and mx_dual_quant_enabled()
+    dual = r.mx and mx_dual_quant_enabled()
     dcols = None
     if dual:                                               # dy is read once, on the caller's stream: db, the column pair, and the row pair
-        e = _epilogue(spec.cin)                            # when the data gradient of this site (its plain form) takes the MX kernel
-        rows_out = hip.load().sv_linear_fp8_dgrad_supported(spec.cout, spec.cin, C.byref(e), _STATE["math"], hip.ACT) == 1
+        rows_out = _fp8_dgrad_epilogue(spec) is not None   # when the data gradient of this site (its plain form) takes the MX kernel
         drows, dcols = quantize_rows_cols_mx(dy, rows, spec.cout, colsum=db, rows_out=rows_out)
         if rows_out:
             _CTX.dyq = (dy, rows, spec.cout) + drows
 
-    def run_mx():
-        dyt, dys = dcols if dual else quantize_cols_mx(dy, rows, spec.cout, colsum=db)
+    def run():
+        dyt, dys = dcols if dual else _fn(r.cols)(dy, rows, spec.cout, colsum=db)
         if pair:
             xt, xs = mx_rows_to_cols(x[0], x[1], rows, spec.cin)
+        elif dual:
+            xt, xs = quantize_rows_cols_mx(x, rows, spec.cin, rows_out=False)[1]
         else:
-            xt, xs = quantize_rows_cols_mx(x, rows, spec.cin, rows_out=False)[1] if dual else quantize_cols_mx(x, rows, spec.cin)
-        nws = int(hip.load().sv_linear_mxfp8_wgrad_workspace_floats(rows, spec.cout, spec.cin, 0))
-        ws = fempty(nws, like=dw) if nws else None         # the splits' fp32 partials: written before they are read, dropped once enqueued
-        traced_call("sv_linear_mxfp8_wgrad", 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout + 8.0 * nws,
-                    ptr(dyt), ptr(dys), ptr(xt), ptr(xs), ptr(dw), rows, spec.cout, spec.cin, spec.cin, 0, ptr(ws), tag=f"M={rows} N={spec.cout} K={spec.cin}")
+            xt, xs = _fn(r.cols)(x, rows, spec.cin)
+        nws, ws = 0, ()
+        if r.mx:
+            nws = int(hip.load().sv_linear_mxfp8_wgrad_workspace_floats(rows, spec.cout, spec.cin, 0))
+            ws = (fempty(nws, like=dw) if nws else None,)  # the splits' fp32 partials: written before they are read, dropped once enqueued
+        traced_call(r.wgrad, 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout + 8.0 * nws,
+                    ptr(dyt), ptr(dys), ptr(xt), ptr(xs), ptr(dw), rows, spec.cout, spec.cin, spec.cin, 0, *[ptr(t) for t in ws],
+                    tag=f"M={rows} N={spec.cout} K={spec.cin}")
 
-    def run_row():
-        dyt, sdc = quantize_cols_fp8(dy, rows, spec.cout, colsum=db)
-        xt, sxc = quantize_cols_fp8(x, rows, spec.cin)
-        traced_call("sv_linear_fp8_wgrad", 2.0 * rows * spec.cin * spec.cout, float(dyt.numel() + xt.numel()) + 8.0 * spec.cin * spec.cout,
-                    ptr(dyt), ptr(sdc), ptr(xt), ptr(sxc), ptr(dw), rows, spec.cout, spec.cin, spec.cin, 0, tag=f"M={rows} N={spec.cout} K={spec.cin}")
-
-    run = run_mx if linear_fp8_bwd_recipe() == "mx" else run_row
     aw = _CTX.awg
     if aw is not None and async_ok:
         aw.stream.wait_stream(torch.cuda.current_stream())     # dy and x are complete on the producing stream
@@ -1053,15 +1074,14 @@ def set_ln_quant_fused(on: bool) -> None:
 
 
 def ln_quant_fused_enabled() -> bool:
-    import os
     # recipe "mx": this form writes per-row scales; the MX form has a switch of its own (ln_quant_mx_enabled)
-    return linear_fp8_enabled() and linear_fp8_recipe() == "row" and _STATE.get("ln_quant_fused", True) and os.environ.get("SV_LN_QUANT_FUSED", "1") != "0"
+    return linear_fp8_enabled() and linear_fp8_recipe() == "row" and _switch("ln_quant_fused", "SV_LN_QUANT_FUSED", True)
 
 
 def ln_quant_site(spec: ConvSpec, w, **epi) -> bool:
     """Whether the LayerNorm in front of this Swin linear takes the quantising form: the linear will run on the fp8 kernel and the fused
-    quantiser is on.  With set_linear_fp8 off this is one flag test."""
-    return ln_quant_fused_enabled() and swin_linear_fp8_epilogue(spec, w, **epi) is not None
+    quantiser is on (LinearPlan.ln_emits under the row recipe).  With set_linear_fp8 off this is one flag test."""
+    return ln_quant_fused_enabled() and swin_linear_plan(spec, w, False, **epi).ln_emits
 
 
 def layernorm_quant_launches() -> int:
@@ -1073,16 +1093,18 @@ def layernorm_quant_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5, s
     """layernorm_fwd that also returns the operand rows of the fp8 linear it feeds: (y, mean, rstd, xq, sx) with xq [rows, roundup(Cdim, 128)]
     e4m3 bytes and sx [rows] fp32 scales, equal to quantize_rows_fp8(y).  store=False (no backward follows): y, mean and rstd are neither
     allocated nor written and come back as None."""
+    return _layernorm_quant(False, x, gamma, beta, rows, Cdim, merge_hw, eps, store, True)
+
+
+def _layernorm_quant(mx, x, gamma, beta, rows, Cdim, merge_hw, eps, store, store_y):
     y = mean = rstd = None
     if store:
-        y = empty(rows, Cdim, like=x)
+        y = empty(rows, Cdim, like=x) if store_y else None
         mean = fempty(rows, like=x)
         rstd = fempty(rows, like=x)
-    Kp = (Cdim + 127) // 128 * 128
-    xq = torch.empty(rows, Kp, dtype=torch.uint8, device=x.device)
-    sx = torch.empty(rows, dtype=torch.float32, device=x.device)
-    call("sv_layernorm_quant_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), ptr(xq), Kp, ptr(sx), rows, Cdim, eps,
-         merge_hw[0], merge_hw[1])
+    xq, sx = operand_buffers(rows, Cdim, mx, x.device)
+    call("sv_layernorm_quant_mx_fwd" if mx else "sv_layernorm_quant_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), ptr(xq),
+         xq.shape[1], ptr(sx), rows, Cdim, eps, merge_hw[0], merge_hw[1])
     return y, mean, rstd, xq, sx
 
 
@@ -1095,14 +1117,13 @@ def set_ln_quant_mx(on: bool) -> None:
 
 
 def ln_quant_mx_enabled() -> bool:
-    import os
-    return _mx() and (_STATE.get("ln_quant_mx", False) or os.environ.get("SV_LN_QUANT_MX", "0") == "1")
+    return _mx() and _switch("ln_quant_mx", "SV_LN_QUANT_MX", False)
 
 
 def ln_quant_mx_site(spec: ConvSpec, w, **epi) -> bool:
-    """MX counterpart of ln_quant_site: the linear behind this LayerNorm will run on the MX kernel and the MX quantising LayerNorm is on.
-    With set_linear_fp8 off this is one flag test."""
-    return ln_quant_mx_enabled() and swin_linear_fp8_epilogue(spec, w, **epi) is not None
+    """MX counterpart of ln_quant_site: the linear behind this LayerNorm will run on the MX kernel and the MX quantising LayerNorm is on
+    (LinearPlan.ln_emits under recipe "mx").  With set_linear_fp8 off this is one flag test."""
+    return ln_quant_mx_enabled() and swin_linear_plan(spec, w, False, **epi).ln_emits
 
 
 def layernorm_quant_mx_launches() -> int:
@@ -1116,17 +1137,7 @@ def layernorm_quant_mx_fwd(x, gamma, beta, rows, Cdim, merge_hw=(0, 0), eps=1e-5
     mx_act_quant_launches() does not move).  store=False (no backward follows): y, mean and rstd are neither allocated nor written and come
     back as None.  store_y=False (the tape keeps the MX rows, store "mx"): the statistics are kept for layernorm_bwd, y is neither allocated
     nor written."""
-    y = mean = rstd = None
-    if store:
-        y = empty(rows, Cdim, like=x) if store_y else None
-        mean = fempty(rows, like=x)
-        rstd = fempty(rows, like=x)
-    Kp = (Cdim + 127) // 128 * 128
-    xq = torch.empty(rows, Kp, dtype=torch.uint8, device=x.device)
-    xs = torch.empty(rows, Kp // 32, dtype=torch.uint8, device=x.device)
-    call("sv_layernorm_quant_mx_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), ptr(xq), Kp, ptr(xs), rows, Cdim, eps,
-         merge_hw[0], merge_hw[1])
-    return y, mean, rstd, xq, xs
+    return _layernorm_quant(True, x, gamma, beta, rows, Cdim, merge_hw, eps, store, store_y)
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, Cdim, merge_hw=(0, 0), accumulate_dx=False):
@@ -1189,7 +1200,6 @@ class BatchNormState:
 def bn_dual_enabled(training: bool, C: int, act: int) -> bool:
     """bn3 and the down-sampling BatchNorm of a layer's first bottleneck in the same passes (bn_dual_apply / bn_dual_backward): the
     switch (set_bn_dual / SV_BN_DUAL, default on) and what the kernels need - train mode, ReLU, sign words in use, C % 256 == 0."""
-    import os
     on = _STATE.get("bn_dual", os.environ.get("SV_BN_DUAL", "1") != "0")
     return bool(on and training and act == ACT_RELU and _bn_signs_on() and C % 256 == 0)
 
@@ -1219,7 +1229,6 @@ def bn_dual_backward(st3: "BatchNormState", std: "BatchNormState", dz, lddz, x3,
 
 
 def _bn_signs_on() -> bool:
-    import os
     return _STATE.get("bn_signs", os.environ.get("SV_BN_SIGNS", "1") != "0")
 
 
@@ -1229,7 +1238,6 @@ def set_bn_signs(on: bool) -> None:
 
 
 def input_prep_enabled() -> bool:
-    import os
     return _STATE.get("input_prep", os.environ.get("SV_INPUT_PREP", "1") != "0")
 
 
@@ -1240,7 +1248,6 @@ def set_input_prep(on: bool) -> None:
 
 
 def bn_pool_fused_enabled() -> bool:
-    import os
     return _STATE.get("bn_pool_fused", os.environ.get("SV_BN_POOL_FUSED", "1") != "0")
 
 

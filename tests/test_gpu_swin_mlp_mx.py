@@ -271,8 +271,8 @@ def test_host_switch(dev, monkeypatch, switches, Cd, heads):
     x2_on, ctx_on, n_on, pk_on, dx_on = run(True)
     assert n_on[0] == 1 and n_on[1:] == n_off[1:], (n_on, n_off)                # one fused MX launch; no MX GEMM or quantiser for the MLP branch
     assert n_on[1:] == ((0, 0) if Cd == 96 else (2, 1)), n_on                   # C = 96: fused bf16 attention branch; C = 128: qkv + proj, one norm1 quantiser
-    assert pk_on == 1 and len(ctx_on) == len(ctx_off) == 15
-    assert ctx_on[12] is not None and ctx_on[12].dtype == torch.bfloat16 and ctx_on[12].numel() == 16 * Cd * Cd
+    assert pk_on == 1 and len(ctx_on) == len(ctx_off) == 17 and ctx_on.fused_mlp and ctx_off.fused_mlp and ctx_on[12] is None
+    assert ctx_on.packs is not None and ctx_on.packs.dtype == torch.bfloat16 and ctx_on.packs.numel() == 16 * Cd * Cd
     assert [type(a) for a in ctx_on] == [type(a) for a in ctx_off]              # the ctx tuple keeps its layout
     assert bool(torch.isfinite(x2_on.float()).all()) and not torch.equal(x2_on, x2_off)
     d = l1_rel(x2_on.double(), x2_off.double())
@@ -281,7 +281,7 @@ def test_host_switch(dev, monkeypatch, switches, Cd, heads):
     assert torch.equal(dx_on, dx_off)                                           # the backward does not read the forward's output
     # torch.no_grad(): no bf16 packs are built
     _, ctx_ng, n_ng, pk_ng, _ = run(False)
-    assert n_ng[0] == 1 and pk_ng == 0 and ctx_ng[12] is None
+    assert n_ng[0] == 1 and pk_ng == 0 and ctx_ng.packs is None and ctx_ng[12] is None
     ops.set_fused_mlp_mx(False)
     x2_ng_off, _, n_ng_off, pk_ng_off, _ = run(False)
     assert n_ng_off[0] == 0 and pk_ng_off == 1                                  # as on the parent

@@ -341,7 +341,7 @@ def test_host_switch(dev, monkeypatch, switches, Cd, heads):
     ops.set_fused_mlp_mx(True)                                                  # the parent's MX training mode: MX forward, bf16 fused backward
     assert ops.fused_mlp_mx_enabled(Cd) and not ops.fused_mlp_mx_bwd_enabled(Cd)   # off by default
     off = _step(blk, x, dy, bf16_packs)
-    assert off["n"][0] == 0 and off["n"][1] == 1 and off["packs"] == 1 and off["ctx"][12] is not None
+    assert off["n"][0] == 0 and off["n"][1] == 1 and off["packs"] == 1 and off["ctx"].packs is not None and off["ctx"][12] is None
     ops.set_fused_mlp_mx(True, backward=True)
     if not _supported(Cd):
         assert not ops.fused_mlp_mx_bwd_enabled(Cd)                             # the host keeps the bf16 backward
@@ -352,8 +352,8 @@ def test_host_switch(dev, monkeypatch, switches, Cd, heads):
     on = _step(blk, x, dy, bf16_packs)
     assert on["n"][0] == 1, on["n"]                                             # one sv_swin_mlp_bwd_mx launch per block backward
     assert on["n"][1:] == off["n"][1:], (on["n"], off["n"])                     # no MX GEMM or activation quantiser launch added for the MLP branch
-    assert on["packs"] == 0 and on["ctx"][12] is None and len(on["ctx"]) == len(off["ctx"]) == 15
-    assert on["ctx"][11] is None                                                # ln2 is None still selects the fused path
+    assert on["packs"] == 0 and on["ctx"].packs is None and on["ctx"][12] is None and len(on["ctx"]) == len(off["ctx"]) == 17
+    assert on["ctx"][11] is None and on["ctx"].fused_mlp and off["ctx"].fused_mlp  # the named flag selects the fused path; ln2 is None as before
     assert torch.equal(on["x2"], off["x2"])                                     # the forward is the same launch
     assert all(torch.equal(a, b) for a, b in zip(on["wg"], off["wg"]))          # weight gradients: the same sv_swin_mlp_wgrad launch, bit for bit
     assert bool(torch.isfinite(on["dx"].float()).all()) and not torch.equal(on["dx"], off["dx"])
@@ -386,7 +386,7 @@ def test_switch_is_inert_elsewhere(dev, switches):
         a1 = _step(b, xx, dd)
         assert a1["n"][0] == 0 and a1["n"] == a0["n"], (a0["n"], a1["n"])
         assert torch.equal(a1["dx"], a0["dx"]) and torch.equal(a1["x2"], a0["x2"])
-        assert (a1["ctx"][12] is None) == (a0["ctx"][12] is None)
+        assert (a1["ctx"].packs is None) == (a0["ctx"].packs is None) and (a1["ctx"][12] is None) == (a0["ctx"][12] is None)
 
     pair(lambda: S.set_linear_fp8(True, backward=True, recipe="mx", backward_recipe="row"))       # the row backward recipe
     pair(lambda: S.set_linear_fp8(True, backward=False, recipe="mx"))                             # no fp8 backward at all
