@@ -2,7 +2,6 @@
 // LayerNorm([C,H,W]) of the Swin stage heads, BatchNorm statistics / apply / backward on channels-last data.
 #include "common.h"
 #include <atomic>
-#include <stdlib.h>
 
 namespace sv {
 
@@ -551,10 +550,149 @@ __global__ __launch_bounds__(256) void scale_shift_act_scalar_kernel(const AT* _
   }
 }
 
-// fold the BatchNorm backward slots: fin[c] = sum_slot ws[slot][c] (c < 2C), dgamma += fin[C + c], dbeta += fin[c]
-__global__ __launch_bounds__(256) void bn_bwd_fold_kernel(double* __restrict__ ws, int C, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+// ------------------------------------------------------------------------------------------------
+// Pieces every BatchNorm backward path below shares.  The paths differ in thread mapping (scalar, narrow, vector, the bn3 + down-sampling
+// pair, the pool fusions) for measured reasons; the sign-word layout, the mask rule, the apply coefficients and the slot scheme are
+// written here once, and a new path uses them.
+// ------------------------------------------------------------------------------------------------
+// Sign words (optional output of the vector forward passes; G == 64 and C % 256 == 0, so that a wave is the 64 column groups of ONE row):
+// bit `lane` of word signs[(row * (C / 256) + blockIdx.x) * 4 + j] = (value of channel 256 blockIdx.x + 4 lane + j before the activation) > 0 -
+// the activation mask the backward needs, 1/16 of the bytes of the output it would otherwise re-read.
+template <typename W> __device__ __forceinline__ W* bn_sign_words(W* signs, long long row, int C) {
+  return signs + ((size_t)row * (C >> 8) + blockIdx.x) * 4;
+}
+__device__ __forceinline__ void bn_signs_store(unsigned long long* signs, long long row, int C, int gq, const float (&o)[4]) {
+  const unsigned long long b0 = __builtin_amdgcn_ballot_w64(o[0] > 0.f), b1 = __builtin_amdgcn_ballot_w64(o[1] > 0.f);
+  const unsigned long long b2 = __builtin_amdgcn_ballot_w64(o[2] > 0.f), b3 = __builtin_amdgcn_ballot_w64(o[3] > 0.f);
+  if (gq == 0) {
+    ulonglong2* w = reinterpret_cast<ulonglong2*>(bn_sign_words(signs, row, C));
+    w[0] = make_ulonglong2(b0, b1);
+    w[1] = make_ulonglong2(b2, b3);
+  }
+}
+__device__ __forceinline__ void bn_signs_load(const unsigned long long* signs, long long row, int C, unsigned long long (&m)[4]) {
+  const ulonglong2* w = reinterpret_cast<const ulonglong2*>(bn_sign_words(signs, row, C));   // the same four words for the whole wave
+  const ulonglong2 p0 = w[0], p1 = w[1];
+  m[0] = p0.x; m[1] = p0.y; m[2] = p1.x; m[3] = p1.y;
+}
+
+// The masked gradient dz' = dz * act'(mask) of N adjacent channels of one row.  The mask comes from the stored output z, from the row's
+// sign words (lane gq owns bit gq) or, with neither saved, from the pre-activation recomputed as fma(x, msc, msh) with the forward's
+// scale / shift.  bn_mask_load fetches what the source needs (so that a pass can issue it with its other loads), bn_mask_grad applies it.
+enum BnMaskSrc { BN_MASK_Z, BN_MASK_X, BN_MASK_SIGNS };
+__device__ __forceinline__ BnMaskSrc bn_mask_src(const void* z, const void* signs) { return signs ? BN_MASK_SIGNS : z ? BN_MASK_Z : BN_MASK_X; }
+template <int N> struct BnMaskRule {
+  int act; float neg; BnMaskSrc src; int gq;
+  float msc[N], msh[N];     // BN_MASK_X only (fsc / fsh may be NULL when there is no activation)
+};
+template <int N> struct BnMask { float z[N]; unsigned long long m[4]; };     // what bn_mask_load fetched for one row
+
+template <int N>
+__device__ __forceinline__ void bn_mask_rule(BnMaskRule<N>& m, int act, float slope, BnMaskSrc src, int gq, const float* __restrict__ fsc,
+                                             const float* __restrict__ fsh, int c, int nreal = N) {     // nreal < N: padding channels (narrow rows)
+  m.act = act; m.neg = act == SV_ACT_LRELU ? slope : 0.f; m.src = src; m.gq = gq;
+  if (src == BN_MASK_X && act != SV_ACT_NONE) {      // one branch around all 2 N loads
+#pragma unroll
+    for (int j = 0; j < N; ++j) { m.msc[j] = j < nreal ? fsc[c + j] : 0.f; m.msh[j] = j < nreal ? fsh[c + j] : 0.f; }
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j) { m.msc[j] = 0.f; m.msh[j] = 0.f; }
+  }
+}
+// the rule of channel j alone, for a pass that masks inside its loop over the channels
+template <int N> __device__ __forceinline__ BnMaskRule<1> bn_mask_rule_of(const BnMaskRule<N>& m, int j) {
+  return BnMaskRule<1>{m.act, m.neg, m.src, m.gq, {m.msc[j]}, {m.msh[j]}};
+}
+template <int N, typename AT>
+__device__ __forceinline__ void bn_mask_load(const BnMaskRule<N>& m, BnMask<N>& k, const AT* __restrict__ z, size_t off,
+                                             const unsigned long long* __restrict__ signs, long long row, int C) {
+  if (m.act == SV_ACT_NONE) return;
+  if (m.src == BN_MASK_Z) { if constexpr (N == 1) k.z[0] = ldf(z + off); else ldnf<N>(z + off, k.z); }
+  else if (m.src == BN_MASK_SIGNS) bn_signs_load(signs, row, C, k.m);
+}
+template <int N>
+__device__ __forceinline__ void bn_mask_grad(const BnMaskRule<N>& m, const BnMask<N>& k, float* d, const float* x) {
+  if (m.act == SV_ACT_NONE) return;
+  if (m.src == BN_MASK_SIGNS) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) d[j] *= ((k.m[j & 3] >> m.gq) & 1ull) ? 1.f : m.neg;
+    return;
+  }
+  float zz[N];
+  if (m.src == BN_MASK_Z) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) zz[j] = k.z[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j) zz[j] = __fmaf_rn(x[j], m.msc[j], m.msh[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) d[j] *= zz[j] > 0.f ? 1.f : m.neg;
+}
+template <int N> __device__ __forceinline__ void bn_mask_grad(const BnMaskRule<N>& m, float* d, const float* x) {   // BN_MASK_X: nothing was fetched
+  BnMask<N> none;
+  bn_mask_grad(m, none, d, x);
+}
+// both steps for a pass with one row in flight (one guard around the fetch and its use: what was fetched does not stay live across a branch)
+template <int N, typename AT>
+__device__ __forceinline__ void bn_mask_row(const BnMaskRule<N>& m, const AT* __restrict__ z, size_t off, const unsigned long long* __restrict__ signs,
+                                            long long row, int C, float* d, const float* x) {
+  if (m.act == SV_ACT_NONE) return;
+  BnMask<N> k;
+  bn_mask_load(m, k, z, off, signs, row, C);
+  bn_mask_grad(m, k, d, x);
+}
+
+// Apply pass: dx = k1*d - k2 - k3*x with per-channel constants from the folded sums (the image behind the slots), k1 = gamma rstd,
+// k3 = k1 rstd sum(dz' xhat)/M, k2 = k1 sum(dz')/M - k3 mean; eval: k2 = k3 = 0.  Double: the mean-removal terms must cancel to
+// rounding, otherwise the residual of sum_r dx is amplified by every later reduction over positions (torch's CPU kernel evaluates this
+// in double too).
+__device__ __forceinline__ const double* bn_bwd_folded(const double* sums, int C) { return sums + (size_t)BN_BWD_SLOTS * 2 * C; }   // written by bn_bwd_fold_kernel
+__device__ __forceinline__ void bn_bwd_coef(const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                            const double* __restrict__ fin, double invM, int training, int c, int C, double& k1, double& k2,
+                                            double& k3) {
+  const double gm = gamma[c], rs = rstd[c], mu = mean[c];
+  k1 = gm * rs;
+  if (training) { const double a = fin[c] * invM, b = fin[C + c] * invM; k3 = gm * rs * b * rs; k2 = gm * rs * a - k3 * mu; }
+  else { k2 = 0.0; k3 = 0.0; }
+}
+__device__ __forceinline__ float bn_bwd_dx(double k1, double k2, double k3, float d, float x) { return (float)(k1 * (double)d - k2 - k3 * (double)x); }
+
+// Reduce pass, vector geometries (G column groups of CV channels x RL = 256 / G row lanes, channel block cb): park the NS * CV per-thread
+// double partials (sum s of channel j at [s * CV + j]) in LDS, fold them over the row lanes (thread t folds partial t % NP of column group
+// t / NP, l ascending) and hand each total to add(s, index, total), index = the channel's place in slot image `block % BN_BWD_SLOTS`;
+// add issues the atomicAdd(s) - which image(s) sum s belongs to is the caller's rule.
+template <int CV, int NS, typename Add>
+__device__ __forceinline__ void bn_slot_fold(double (*red)[NS * CV + 1], const double (&part)[NS * CV], int G, int RL, int cb, unsigned block, int C,
+                                             Add add) {
+  constexpr int NP = NS * CV;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) red[threadIdx.x][j] = part[j];
+  __syncthreads();
+  for (int t = threadIdx.x; t < NP * G; t += 256) {
+    const int q = t / NP, k = t % NP;
+    const int cc = (cb * G + q) * CV + k % CV;
+    if (cc < C) {
+      double a = 0.0;
+      for (int l = 0; l < RL; ++l) a += red[l * G + q][k];
+      add(k / CV, (size_t)(block % BN_BWD_SLOTS) * 2 * C + cc, a);
+    }
+  }
+}
+template <int CV>     // one layer: [sum dz' | sum dz' xhat] into its own image
+__device__ __forceinline__ void bn_slot_fold_one(double (*red)[2 * CV + 1], const double (&part)[2 * CV], int G, int RL, int cb, unsigned block, int C, double* __restrict__ sums) {
+  bn_slot_fold<CV, 2>(red, part, G, RL, cb, block, C, [&](int s, size_t i, double a) { atomicAdd(sums + i + (size_t)s * C, a); });
+}
+
+// fold the BatchNorm backward slots: fin[c] = sum_slot ws[slot][c] (c < 2C), dgamma += fin[C + c], dbeta += fin[c]; blockIdx.y = image
+// (gridDim.y = 2 for the two layers of the bn3 + down-sampling pass, 1 otherwise)
+__global__ __launch_bounds__(256) void bn_bwd_fold_kernel(double* __restrict__ ws0, double* __restrict__ ws1, int C, float* __restrict__ dgamma0,
+                                                          float* __restrict__ dbeta0, float* __restrict__ dgamma1, float* __restrict__ dbeta1) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= 2 * C) return;
+  double* ws = blockIdx.y ? ws1 : ws0;
+  float* dgamma = blockIdx.y ? dgamma1 : dgamma0;
+  float* dbeta = blockIdx.y ? dbeta1 : dbeta0;
   double a = 0.0;
 #pragma unroll
   for (int sl = 0; sl < BN_BWD_SLOTS; ++sl) a += ws[(size_t)sl * 2 * C + c];
@@ -577,22 +715,22 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const AT* __restrict
   double s1 = 0.0, s2 = 0.0;
   if (c < C) {
     const float mu = mean[c], rs = rstd[c];
-    const bool remask = !z && act != SV_ACT_NONE;                   // no saved output: the mask is recomputed from x
-    const float msc = remask ? fsc[c] : 0.f, msh = remask ? fsh[c] : 0.f;   // (fsc / fsh may be NULL when there is no activation)
-    const float neg = act == SV_ACT_LRELU ? slope : 0.f;
+    BnMaskRule<1> mk;
+    bn_mask_rule(mk, act, slope, bn_mask_src(z, nullptr), 0, fsc, fsh, c);
     long long r = r0 + rl;
     for (; r + 3 * RL < r1e; r += 4 * RL) {   // 4 rows in flight per thread (independent loads), then the serial tail
-      float d[4], xv[4], zv[4];
+      float d[4], xv[4];
+      BnMask<1> zv[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         d[u] = ldf(dz + (size_t)(r + RL * u) * lddz + c);
         xv[u] = ldf(x + (size_t)(r + RL * u) * ldx + c);
-        zv[u] = act != SV_ACT_NONE ? (z ? ldf(z + (size_t)(r + RL * u) * ldz + c) : __fmaf_rn(xv[u], msc, msh)) : 1.f;
+        bn_mask_load(mk, zv[u], z, (size_t)(r + RL * u) * ldz + c, nullptr, 0, C);
       }
       float f1 = 0.f, f2 = 0.f;               // four rows in fp32, then into the double accumulators
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if (act != SV_ACT_NONE) d[u] *= (zv[u] > 0.f) ? 1.f : neg;
+        bn_mask_grad(mk, zv[u], &d[u], &xv[u]);
         f1 += d[u]; f2 += d[u] * (xv[u] - mu) * rs;
       }
       s1 += (double)f1; s2 += (double)f2;
@@ -600,7 +738,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const AT* __restrict
     for (; r < r1e; r += RL) {
       float d = ldf(dz + (size_t)r * lddz + c);
       const float xq = ldf(x + (size_t)r * ldx + c);
-      if (act != SV_ACT_NONE) d *= ((z ? ldf(z + (size_t)r * ldz + c) : __fmaf_rn(xq, msc, msh)) > 0.f) ? 1.f : neg;
+      bn_mask_row(mk, z, (size_t)r * ldz + c, nullptr, 0, C, &d, &xq);
       s1 += (double)d; s2 += (double)(d * (xq - mu) * rs);
     }
   }
@@ -615,30 +753,30 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const AT* __restrict
   }
 }
 
-// backward pass 2: dx = gamma*rstd*(dz' - s1/M - xhat*s2/M) (train) or dz'*gamma*rstd (eval); dres = dz' (optional);
-// block 0 also folds the sums into dgamma/dbeta
+// backward pass 2: dx = gamma*rstd*(dz' - s1/M - xhat*s2/M) (train) or dz'*gamma*rstd (eval); dres = dz' (optional).  Evaluated per element
+// in this association, not as bn_bwd_dx's k1*d - k2 - k3*x: this family carries the largest measured error and keeps its own expression.
 template <typename AT>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const AT* __restrict__ dz, int lddz, const AT* __restrict__ z, int ldz,
                                                            const AT* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
                                                            const double* __restrict__ sums, long long M, int C, int act, float slope,
                                                            int training, AT* __restrict__ dx, int lddx, AT* __restrict__ dres,
-                                                           int lddres, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                           const float* __restrict__ fsc, const float* __restrict__ fsh) {
+                                                           int lddres, const float* __restrict__ fsc, const float* __restrict__ fsh) {
   const long long total = M * C;
   const double invM = 1.0 / (double)M;
-  sums += (size_t)BN_BWD_SLOTS * 2 * C;     // the folded image written by the reduce pass
+  sums = bn_bwd_folded(sums, C);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const long long r = i / C; const int c = (int)(i - r * C);
     float d = ldf(dz + (size_t)r * lddz + c);
     const float xq = ldf(x + (size_t)r * ldx + c);
-    if (act != SV_ACT_NONE) d *= ((z ? ldf(z + (size_t)r * ldz + c) : __fmaf_rn(xq, fsc[c], fsh[c])) > 0.f) ? 1.f : (act == SV_ACT_LRELU ? slope : 0.f);
+    BnMaskRule<1> mk;
+    bn_mask_rule(mk, act, slope, bn_mask_src(z, nullptr), 0, fsc, fsh, c);
+    bn_mask_row(mk, z, (size_t)r * ldz + c, nullptr, 0, C, &d, &xq);
     if (dres) stf(dres + (size_t)r * lddres + c, d);
     const float rs = rstd[c];
     float o;
     if (training) {
-      // double arithmetic for the mean-subtraction terms: sum_r dx must vanish to rounding, otherwise the residual is
-      // amplified by every later reduction over positions (torch's CPU kernel evaluates this expression in double too)
+      // double arithmetic for the mean-subtraction terms (see bn_bwd_coef)
       const double xh = ((double)xq - (double)mean[c]) * (double)rs;
       o = (float)((double)gamma[c] * (double)rs * ((double)d - sums[c] * invM - xh * (sums[C + c] * invM)));
     } else {
@@ -685,32 +823,19 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_narrow_kernel(const AT* __r
                                                                    const float* __restrict__ fsc, const float* __restrict__ fsh) {
   __shared__ double red[64][9];     // [row lane][4 x s1, 4 x s2] (+1 pad) per group, folded group by group
   const int g = threadIdx.x & 3, rl = threadIdx.x >> 2;
-  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, mu[4], rs[4], msc[4], msh[4];
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, mu[4], rs[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int c = 4 * g + j;
-    mu[j] = c < C ? mean[c] : 0.f; rs[j] = c < C ? rstd[c] : 0.f;
-    msc[j] = (!z && fsc && c < C) ? fsc[c] : 0.f; msh[j] = (!z && fsh && c < C) ? fsh[c] : 0.f;
-  }
-  const float neg = act == SV_ACT_LRELU ? slope : 0.f;
+  for (int j = 0; j < 4; ++j) { const int c = 4 * g + j; mu[j] = c < C ? mean[c] : 0.f; rs[j] = c < C ? rstd[c] : 0.f; }
+  BnMaskRule<4> mk;
+  bn_mask_rule(mk, act, slope, bn_mask_src(z, nullptr), 0, fsc, fsh, 4 * g, C - 4 * g);
   if (4 * g < C) {
     const long long r0 = (long long)blockIdx.x * 64 * rows_per_thread + rl;
     for (int k = 0; k < rows_per_thread; ++k) {
       const long long r = r0 + (long long)k * 64;
       if (r >= M) break;
-      const float4 dv = ld4f(dz + (size_t)r * lddz + 4 * g), xv = ld4f(x + (size_t)r * ldx + 4 * g);
-      float d[4] = {dv.x, dv.y, dv.z, dv.w};
-      const float xx[4] = {xv.x, xv.y, xv.z, xv.w};
-      if (act != SV_ACT_NONE) {
-        float zz[4];
-        if (z) { const float4 zv = ld4f(z + (size_t)r * ldz + 4 * g); zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w; }
-        else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) zz[j] = __fmaf_rn(xx[j], msc[j], msh[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] *= zz[j] > 0.f ? 1.f : neg;
-      }
+      float d[4], xx[4];
+      ldnf<4>(dz + (size_t)r * lddz + 4 * g, d); ldnf<4>(x + (size_t)r * ldx + 4 * g, xx);
+      bn_mask_row(mk, z, (size_t)r * ldz + 4 * g, nullptr, 0, C, d, xx);
 #pragma unroll
       for (int j = 0; j < 4; ++j) { s1[j] += d[j]; s2[j] += d[j] * (xx[j] - mu[j]) * rs[j]; }
     }
@@ -740,49 +865,29 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_narrow_kernel(const AT* __re
                                                                   const double* __restrict__ sums, long long M, int C, int act, float slope,
                                                                   int training, AT* __restrict__ dx, int lddx, AT* __restrict__ dres, int lddres,
                                                                   const float* __restrict__ fsc, const float* __restrict__ fsh) {
-  sums += (size_t)BN_BWD_SLOTS * 2 * C;     // the folded image
   const int g = threadIdx.x & 3, rl = threadIdx.x >> 2;
   if (4 * g >= C) return;
-  float msc[4], msh[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { const int c = 4 * g + j; msc[j] = (!z && fsc && c < C) ? fsc[c] : 0.f; msh[j] = (!z && fsh && c < C) ? fsh[c] : 0.f; }
-  // dx = k1*d - k2 - k3*x with per-channel constants (double: the mean-removal terms must cancel to rounding)
+  BnMaskRule<4> mk;
+  bn_mask_rule(mk, act, slope, bn_mask_src(z, nullptr), 0, fsc, fsh, 4 * g, C - 4 * g);
   double k1[4], k2[4], k3[4];
   const double invM = 1.0 / (double)M;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int c = 4 * g + j;
-    if (c < C) {
-      const double gm = gamma[c], rs = rstd[c], mu = mean[c];
-      k1[j] = gm * rs;
-      if (training) { const double a = sums[c] * invM, b = sums[C + c] * invM; k3[j] = gm * rs * b * rs; k2[j] = gm * rs * a - k3[j] * mu; }
-      else { k2[j] = 0.0; k3[j] = 0.0; }
-    } else { k1[j] = k2[j] = k3[j] = 0.0; }
+    if (4 * g + j < C) bn_bwd_coef(gamma, mean, rstd, bn_bwd_folded(sums, C), invM, training, 4 * g + j, C, k1[j], k2[j], k3[j]);
+    else k1[j] = k2[j] = k3[j] = 0.0;
   }
-  const float neg = act == SV_ACT_LRELU ? slope : 0.f;
   for (long long r = (long long)blockIdx.x * 64 + rl; r < M; r += (long long)gridDim.x * 64) {
-    const float4 dv = ld4f(dz + (size_t)r * lddz + 4 * g), xv = ld4f(x + (size_t)r * ldx + 4 * g);
-    float d[4] = {dv.x, dv.y, dv.z, dv.w};
-    const float xx[4] = {xv.x, xv.y, xv.z, xv.w};
-    if (act != SV_ACT_NONE) {
-      float zz[4];
-      if (z) { const float4 zv = ld4f(z + (size_t)r * ldz + 4 * g); zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w; }
-      else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) zz[j] = __fmaf_rn(xx[j], msc[j], msh[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) d[j] *= zz[j] > 0.f ? 1.f : neg;
-    }
-    float o[4];
+    float d[4], xx[4], o[4];
+    ldnf<4>(dz + (size_t)r * lddz + 4 * g, d); ldnf<4>(x + (size_t)r * ldx + 4 * g, xx);
+    bn_mask_row(mk, z, (size_t)r * ldz + 4 * g, nullptr, 0, C, d, xx);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {   // padding columns: whatever was read (possibly uninitialised memory) is ignored, zero is written
       const bool real = 4 * g + j < C;
-      o[j] = real ? (float)(k1[j] * (double)d[j] - k2[j] - k3[j] * (double)xx[j]) : 0.f;
+      o[j] = real ? bn_bwd_dx(k1[j], k2[j], k3[j], d[j], xx[j]) : 0.f;
       if (!real) d[j] = 0.f;
     }
-    if (dres) st4f(dres + (size_t)r * lddres + 4 * g, make_float4(d[0], d[1], d[2], d[3]));
-    st4f(dx + (size_t)r * lddx + 4 * g, make_float4(o[0], o[1], o[2], o[3]));
+    if (dres) stnf<4>(dres + (size_t)r * lddres + 4 * g, d);
+    stnf<4>(dx + (size_t)r * lddx + 4 * g, o);
   }
 }
 
@@ -794,9 +899,7 @@ __global__ __launch_bounds__(256) void scale_shift_act_cg_kernel(const AT* __res
                                                                  const float* __restrict__ shift, const AT* __restrict__ res, int ldr,
                                                                  AT* __restrict__ y, int ldy, long long M, int C, int act, float slope,
                                                                  long long rows_per_block, int G, unsigned long long* __restrict__ signs) {
-  // signs (optional; G == 64 and C % 256 == 0, so that a wave is the 64 column groups of ONE row): bit `lane` of word
-  // signs[(row * (C / 256) + blockIdx.x) * 4 + j] = (value of channel 256 blockIdx.x + 4 lane + j before the activation) > 0 - the
-  // activation mask the backward needs, 1/16 of the bytes of the output it would otherwise re-read
+  // signs (optional; G == 64 and C % 256 == 0): the activation mask for the backward, see bn_signs_store
   const int gq = threadIdx.x % G, rl = threadIdx.x / G, RL = 256 / G;
   const int c = (blockIdx.x * G + gq) * 4;
   if (c >= C || rl >= RL) return;
@@ -811,15 +914,7 @@ __global__ __launch_bounds__(256) void scale_shift_act_cg_kernel(const AT* __res
       const float4 rv = ld4f(res + (size_t)r * ldr + c);
       o[0] += rv.x; o[1] += rv.y; o[2] += rv.z; o[3] += rv.w;
     }
-    if (signs) {
-      const unsigned long long b0 = __builtin_amdgcn_ballot_w64(o[0] > 0.f), b1 = __builtin_amdgcn_ballot_w64(o[1] > 0.f);
-      const unsigned long long b2 = __builtin_amdgcn_ballot_w64(o[2] > 0.f), b3 = __builtin_amdgcn_ballot_w64(o[3] > 0.f);
-      if (gq == 0) {
-        unsigned long long* w = signs + ((size_t)r * (C >> 8) + blockIdx.x) * 4;
-        *reinterpret_cast<ulonglong2*>(w) = make_ulonglong2(b0, b1);
-        *reinterpret_cast<ulonglong2*>(w + 2) = make_ulonglong2(b2, b3);
-      }
-    }
+    if (signs) bn_signs_store(signs, r, C, gq, o);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = apply_act(o[j], act, slope);
     st4f(y + (size_t)r * ldy + c, make_float4(o[0], o[1], o[2], o[3]));
@@ -839,50 +934,23 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cg_kernel(const AT* __restri
   const int gq = threadIdx.x % G, rl = threadIdx.x / G, RL = 256 / G;
   const int c = (blockIdx.x * G + gq) * 4;
   if (c >= C || rl >= RL) return;
-  sums += (size_t)BN_BWD_SLOTS * 2 * C;     // the folded image written by the reduce pass
-  // dx = k1*d - k2 - k3*x (double: the mean-removal terms must cancel to rounding), see bn_bwd_apply_narrow_kernel
+  BnMaskRule<4> mk;
+  bn_mask_rule(mk, act, slope, SIGNS ? BN_MASK_SIGNS : bn_mask_src(z, nullptr), gq, fsc, fsh, c);
   double k1[4], k2[4], k3[4];
   const double invM = 1.0 / (double)M;
-  float msc[4] = {0.f, 0.f, 0.f, 0.f}, msh[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const double gm = gamma[c + j], rs = rstd[c + j], mu = mean[c + j];
-    k1[j] = gm * rs;
-    if (training) { const double a = sums[c + j] * invM, b = sums[C + c + j] * invM; k3[j] = gm * rs * b * rs; k2[j] = gm * rs * a - k3[j] * mu; }
-    else { k2[j] = 0.0; k3[j] = 0.0; }
-    if (!SIGNS && !z && act != SV_ACT_NONE) { msc[j] = fsc[c + j]; msh[j] = fsh[c + j]; }
-  }
-  const float neg = act == SV_ACT_LRELU ? slope : 0.f;
+  for (int j = 0; j < 4; ++j) bn_bwd_coef(gamma, mean, rstd, bn_bwd_folded(sums, C), invM, training, c + j, C, k1[j], k2[j], k3[j]);
   const long long r0 = (long long)blockIdx.y * rows_per_block;
   long long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
 #pragma unroll 2
   for (long long r = r0 + rl; r < r1; r += RL) {
-    const float4 dv = ld4f(dz + (size_t)r * lddz + c), xv = ld4f(x + (size_t)r * ldx + c);
-    float d[4] = {dv.x, dv.y, dv.z, dv.w};
-    const float xx[4] = {xv.x, xv.y, xv.z, xv.w};
-    if constexpr (SIGNS) {
-      if (act != SV_ACT_NONE) {
-        const ulonglong2* w = reinterpret_cast<const ulonglong2*>(signs + ((size_t)r * (C >> 8) + blockIdx.x) * 4);
-        const ulonglong2 p0 = w[0], p1 = w[1];
-        const unsigned long long m[4] = {p0.x, p0.y, p1.x, p1.y};
+    float d[4], xx[4], o[4];
+    ldnf<4>(dz + (size_t)r * lddz + c, d); ldnf<4>(x + (size_t)r * ldx + c, xx);
+    bn_mask_row(mk, z, (size_t)r * ldz + c, signs, r, C, d, xx);
+    if (dres) stnf<4>(dres + (size_t)r * lddres + c, d);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] *= ((m[j] >> gq) & 1ull) ? 1.f : neg;
-      }
-    } else if (act != SV_ACT_NONE) {
-      float zz[4];
-      if (z) { const float4 zv = ld4f(z + (size_t)r * ldz + c); zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w; }
-      else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) zz[j] = __fmaf_rn(xx[j], msc[j], msh[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) d[j] *= zz[j] > 0.f ? 1.f : neg;
-    }
-    if (dres) st4f(dres + (size_t)r * lddres + c, make_float4(d[0], d[1], d[2], d[3]));
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (float)(k1[j] * (double)d[j] - k2[j] - k3[j] * (double)xx[j]);
-    st4f(dx + (size_t)r * lddx + c, make_float4(o[0], o[1], o[2], o[3]));
+    for (int j = 0; j < 4; ++j) o[j] = bn_bwd_dx(k1[j], k2[j], k3[j], d[j], xx[j]);
+    stnf<4>(dx + (size_t)r * lddx + c, o);
   }
 }
 
@@ -895,7 +963,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const AT* __rest
                                                                 double* __restrict__ sums, long long rows_per_block, int G,
                                                                 const float* __restrict__ fsc, const float* __restrict__ fsh,
                                                                 AT* __restrict__ dmask, int lddm, const unsigned long long* __restrict__ signs) {
-  // signs (optional, instead of z; G == 64, C % 256 == 0): the forward's activation mask, one bit per element (scale_shift_act_cg_kernel)
+  // signs (optional, instead of z; G == 64, C % 256 == 0): the forward's activation mask, one bit per element (bn_signs_store)
   // dmask (optional): receives dz' = dz * act'(z) - the gradient of the residual branch AND what pass 2 then reads instead of (dz, z):
   // a BatchNorm in front of a residual sum (bn3 / the down-sampling branch of every bottleneck) saves one read of the widest tensors
   __shared__ double red[256][9];   // [thread][8 partials] (+1 pad)
@@ -903,82 +971,46 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const AT* __rest
   const int c = (blockIdx.x * G + gq) * 4;
   const long long r0 = (long long)blockIdx.y * rows_per_block;
   long long r1e = r0 + rows_per_block; if (r1e > M) r1e = M;
-  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // [sum dz' | sum dz' xhat] x 4 channels
   if (c < C && rl < RL) {
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c), rs = *reinterpret_cast<const float4*>(rstd + c);
-    float4 msc = make_float4(0.f, 0.f, 0.f, 0.f), msh = msc;          // no saved output: the mask is recomputed from x
-    if (!z && !signs && act != SV_ACT_NONE) { msc = *reinterpret_cast<const float4*>(fsc + c); msh = *reinterpret_cast<const float4*>(fsh + c); }
-    const float neg = act == SV_ACT_LRELU ? slope : 0.f;
+    float mm[4], rr[4];
+    ldnf<4>(mean + c, mm); ldnf<4>(rstd + c, rr);
+    BnMaskRule<4> mk;
+    bn_mask_rule(mk, act, slope, bn_mask_src(z, signs), gq, fsc, fsh, c);
+    // a row in two steps, so that the loop can issue the loads of both its rows before the arithmetic of either; dz and x of every row
+    // go out before the branch on the mask source
+    struct Row { float d[4], x[4]; BnMask<4> k; };
+    auto load = [&](long long r, Row* w, int n) __attribute__((always_inline)) {     // n rows, RL apart
+#pragma unroll
+      for (int i = 0; i < n; ++i) ldnf<4>(dz + (size_t)(r + i * RL) * lddz + c, w[i].d);
+#pragma unroll
+      for (int i = 0; i < n; ++i) ldnf<4>(x + (size_t)(r + i * RL) * ldx + c, w[i].x);
+#pragma unroll
+      for (int i = 0; i < n; ++i) bn_mask_load(mk, w[i].k, z, (size_t)(r + i * RL) * ldz + c, signs, r + i * RL, C);
+    };
+    auto terms = [&](long long r, Row& w, float (&t)[8]) __attribute__((always_inline)) {
+      bn_mask_grad(mk, w.k, w.d, w.x);
+      if (dmask) stnf<4>(dmask + (size_t)r * lddm + c, w.d);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { t[j] = w.d[j]; t[4 + j] = w.d[j] * (w.x[j] - mm[j]) * rr[j]; }
+    };
+    Row w[2];
+    float t0[8], t1[8];
     long long r = r0 + rl;
     for (; r + RL < r1e; r += 2 * RL) {   // two rows in flight
-      const float4 d0 = ld4f(dz + (size_t)r * lddz + c), d1 = ld4f(dz + (size_t)(r + RL) * lddz + c);
-      const float4 x0 = ld4f(x + (size_t)r * ldx + c), x1 = ld4f(x + (size_t)(r + RL) * ldx + c);
-      float a0[4] = {d0.x, d0.y, d0.z, d0.w}, a1[4] = {d1.x, d1.y, d1.z, d1.w};
-      if (act != SV_ACT_NONE && signs) {
-        const ulonglong2* w0 = reinterpret_cast<const ulonglong2*>(signs + ((size_t)r * (C >> 8) + blockIdx.x) * 4);
-        const ulonglong2* w1 = reinterpret_cast<const ulonglong2*>(signs + ((size_t)(r + RL) * (C >> 8) + blockIdx.x) * 4);
-        const ulonglong2 p0 = w0[0], p1 = w0[1], q0 = w1[0], q1 = w1[1];       // the same four words for the whole wave (one row each)
-        const unsigned long long m0[4] = {p0.x, p0.y, p1.x, p1.y}, m1[4] = {q0.x, q0.y, q1.x, q1.y};
+      load(r, w, 2);
+      terms(r, w[0], t0); terms(r + RL, w[1], t1);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { a0[j] *= ((m0[j] >> gq) & 1ull) ? 1.f : neg; a1[j] *= ((m1[j] >> gq) & 1ull) ? 1.f : neg; }
-      } else if (act != SV_ACT_NONE) {
-        float4 z0, z1;
-        if (z) { z0 = ld4f(z + (size_t)r * ldz + c); z1 = ld4f(z + (size_t)(r + RL) * ldz + c); }
-        else {
-          z0 = make_float4(__fmaf_rn(x0.x, msc.x, msh.x), __fmaf_rn(x0.y, msc.y, msh.y), __fmaf_rn(x0.z, msc.z, msh.z), __fmaf_rn(x0.w, msc.w, msh.w));
-          z1 = make_float4(__fmaf_rn(x1.x, msc.x, msh.x), __fmaf_rn(x1.y, msc.y, msh.y), __fmaf_rn(x1.z, msc.z, msh.z), __fmaf_rn(x1.w, msc.w, msh.w));
-        }
-        const float q0[4] = {z0.x, z0.y, z0.z, z0.w}, q1[4] = {z1.x, z1.y, z1.z, z1.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { a0[j] *= q0[j] > 0.f ? 1.f : neg; a1[j] *= q1[j] > 0.f ? 1.f : neg; }
-      }
-      if (dmask) {
-        st4f(dmask + (size_t)r * lddm + c, make_float4(a0[0], a0[1], a0[2], a0[3]));
-        st4f(dmask + (size_t)(r + RL) * lddm + c, make_float4(a1[0], a1[1], a1[2], a1[3]));
-      }
-      const float xa[4] = {x0.x, x0.y, x0.z, x0.w}, xb[4] = {x1.x, x1.y, x1.z, x1.w};
-      const float mm[4] = {mu.x, mu.y, mu.z, mu.w}, rr[4] = {rs.x, rs.y, rs.z, rs.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s1[j] += (double)a0[j] + (double)a1[j];
-        s2[j] += (double)(a0[j] * (xa[j] - mm[j]) * rr[j]) + (double)(a1[j] * (xb[j] - mm[j]) * rr[j]);
-      }
+      for (int j = 0; j < 8; ++j) s[j] += (double)t0[j] + (double)t1[j];
     }
     for (; r < r1e; r += RL) {
-      const float4 d0 = ld4f(dz + (size_t)r * lddz + c), x0 = ld4f(x + (size_t)r * ldx + c);
-      float a0[4] = {d0.x, d0.y, d0.z, d0.w};
-      if (act != SV_ACT_NONE && signs) {
-        const ulonglong2* w0 = reinterpret_cast<const ulonglong2*>(signs + ((size_t)r * (C >> 8) + blockIdx.x) * 4);
-        const ulonglong2 p0 = w0[0], p1 = w0[1];
-        const unsigned long long m0[4] = {p0.x, p0.y, p1.x, p1.y};
+      load(r, w, 1);
+      terms(r, w[0], t0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) a0[j] *= ((m0[j] >> gq) & 1ull) ? 1.f : neg;
-      } else if (act != SV_ACT_NONE) {
-        const float4 z0 = z ? ld4f(z + (size_t)r * ldz + c)
-                            : make_float4(__fmaf_rn(x0.x, msc.x, msh.x), __fmaf_rn(x0.y, msc.y, msh.y), __fmaf_rn(x0.z, msc.z, msh.z), __fmaf_rn(x0.w, msc.w, msh.w));
-        const float q0[4] = {z0.x, z0.y, z0.z, z0.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a0[j] *= q0[j] > 0.f ? 1.f : neg;
-      }
-      if (dmask) st4f(dmask + (size_t)r * lddm + c, make_float4(a0[0], a0[1], a0[2], a0[3]));
-      const float xa[4] = {x0.x, x0.y, x0.z, x0.w}, mm[4] = {mu.x, mu.y, mu.z, mu.w}, rr[4] = {rs.x, rs.y, rs.z, rs.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s1[j] += (double)a0[j]; s2[j] += (double)(a0[j] * (xa[j] - mm[j]) * rr[j]); }
+      for (int j = 0; j < 8; ++j) s[j] += (double)t0[j];
     }
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { red[threadIdx.x][j] = s1[j]; red[threadIdx.x][4 + j] = s2[j]; }
-  __syncthreads();
-  // thread t < 8*G folds partial (t % 8) of column group (t / 8) over the row lanes
-  for (int t = threadIdx.x; t < 8 * G; t += 256) {
-    const int q = t >> 3, k = t & 7;
-    const int cc = (blockIdx.x * G + q) * 4 + (k & 3);
-    if (cc < C) {
-      double a = 0.0;
-      for (int l = 0; l < RL; ++l) a += red[l * G + q][k];
-      atomicAdd(sums + (size_t)(blockIdx.y % BN_BWD_SLOTS) * 2 * C + (k < 4 ? 0 : C) + cc, a);
-    }
-  }
+  bn_slot_fold_one<4>(red, s, G, RL, blockIdx.x, blockIdx.y, C, sums);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1010,26 +1042,11 @@ __global__ __launch_bounds__(256) void scale_shift_act2_cg_kernel(const AT* __re
     float o[4] = {__fmaf_rn(xv.x, s3.x, h3.x), __fmaf_rn(xv.y, s3.y, h3.y), __fmaf_rn(xv.z, s3.z, h3.z), __fmaf_rn(xv.w, s3.w, h3.w)};
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] += (float)(AT)t[j];
-    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(o[0] > 0.f), b1 = __builtin_amdgcn_ballot_w64(o[1] > 0.f);
-    const unsigned long long b2 = __builtin_amdgcn_ballot_w64(o[2] > 0.f), b3 = __builtin_amdgcn_ballot_w64(o[3] > 0.f);
-    if (gq == 0) {
-      unsigned long long* w = signs + ((size_t)r * (C >> 8) + blockIdx.x) * 4;
-      *reinterpret_cast<ulonglong2*>(w) = make_ulonglong2(b0, b1);
-      *reinterpret_cast<ulonglong2*>(w + 2) = make_ulonglong2(b2, b3);
-    }
+    bn_signs_store(signs, r, C, gq, o);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = apply_act(o[j], SV_ACT_RELU, 0.f);
     st4f(y + (size_t)r * ldy + c, make_float4(o[0], o[1], o[2], o[3]));
   }
-}
-
-// d of one row: dout where the row's sign bit of the lane's channel is set, else 0
-template <typename AT>
-__device__ __forceinline__ void bn2_masked(const AT* __restrict__ dz, const unsigned long long* __restrict__ w, int gq, float (&d)[4]) {
-  const float4 dv = ld4f(dz);
-  const ulonglong2 p0 = reinterpret_cast<const ulonglong2*>(w)[0], p1 = reinterpret_cast<const ulonglong2*>(w)[1];   // the same four words for the whole wave
-  d[0] = ((p0.x >> gq) & 1ull) ? dv.x : 0.f; d[1] = ((p0.y >> gq) & 1ull) ? dv.y : 0.f;
-  d[2] = ((p1.x >> gq) & 1ull) ? dv.z : 0.f; d[3] = ((p1.y >> gq) & 1ull) ? dv.w : 0.f;
 }
 
 template <typename AT>
@@ -1040,70 +1057,46 @@ __global__ __launch_bounds__(256) void bn_bwd2_reduce_kernel(const AT* __restric
                                                              double* __restrict__ sums3, double* __restrict__ sumsd, long long rows_per_block) {
   __shared__ double red[256][13];   // [thread][sum d | sum d xhat_3 | sum d xhat_d] x 4 channels (+1 pad)
   const int gq = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = (blockIdx.x * 64 + gq) * 4, W = C >> 8;
+  const int c = (blockIdx.x * 64 + gq) * 4;
   const long long r0 = (long long)blockIdx.y * rows_per_block;
   long long r1e = r0 + rows_per_block; if (r1e > M) r1e = M;
-  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0}, s3[4] = {0.0, 0.0, 0.0, 0.0};
-  const float4 mu3 = *reinterpret_cast<const float4*>(mean3 + c), rs3 = *reinterpret_cast<const float4*>(rstd3 + c);
-  const float4 mud = *reinterpret_cast<const float4*>(meand + c), rsd = *reinterpret_cast<const float4*>(rstdd + c);
-  const float m3[4] = {mu3.x, mu3.y, mu3.z, mu3.w}, q3[4] = {rs3.x, rs3.y, rs3.z, rs3.w};
-  const float md[4] = {mud.x, mud.y, mud.z, mud.w}, qd[4] = {rsd.x, rsd.y, rsd.z, rsd.w};
+  double s[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  float m3[4], q3[4], md[4], qd[4];
+  ldnf<4>(mean3 + c, m3); ldnf<4>(rstd3 + c, q3); ldnf<4>(meand + c, md); ldnf<4>(rstdd + c, qd);
+  BnMaskRule<4> mk;
+  bn_mask_rule(mk, SV_ACT_RELU, 0.f, BN_MASK_SIGNS, gq, nullptr, nullptr, c);
+  // a row in two steps, as in bn_bwd_reduce_vec_kernel
+  struct Row { float d[4], x[4], e[4]; BnMask<4> k; };
+  auto load = [&](long long r, Row& w) __attribute__((always_inline)) {
+    ldnf<4>(x3 + (size_t)r * ldx3 + c, w.x); ldnf<4>(xd + (size_t)r * ldxd + c, w.e); ldnf<4>(dz + (size_t)r * lddz + c, w.d);
+    bn_mask_load(mk, w.k, (const AT*)nullptr, 0, signs, r, C);
+  };
+  auto terms = [&](Row& w, float (&t)[12]) __attribute__((always_inline)) {
+    bn_mask_grad(mk, w.k, w.d, w.x);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { t[j] = w.d[j]; t[4 + j] = w.d[j] * (w.x[j] - m3[j]) * q3[j]; t[8 + j] = w.d[j] * (w.e[j] - md[j]) * qd[j]; }
+  };
+  Row w0, w1;
+  float t0[12], t1[12];
   long long r = r0 + rl;
   for (; r + 4 < r1e; r += 8) {   // two rows in flight
-    float a0[4], a1[4];
-    const float4 x0 = ld4f(x3 + (size_t)r * ldx3 + c), x1 = ld4f(x3 + (size_t)(r + 4) * ldx3 + c);
-    const float4 e0 = ld4f(xd + (size_t)r * ldxd + c), e1 = ld4f(xd + (size_t)(r + 4) * ldxd + c);
-    bn2_masked(dz + (size_t)r * lddz + c, signs + ((size_t)r * W + blockIdx.x) * 4, gq, a0);
-    bn2_masked(dz + (size_t)(r + 4) * lddz + c, signs + ((size_t)(r + 4) * W + blockIdx.x) * 4, gq, a1);
-    const float xa[4] = {x0.x, x0.y, x0.z, x0.w}, xb[4] = {x1.x, x1.y, x1.z, x1.w};
-    const float ea[4] = {e0.x, e0.y, e0.z, e0.w}, eb[4] = {e1.x, e1.y, e1.z, e1.w};
+    load(r, w0); load(r + 4, w1);
+    terms(w0, t0); terms(w1, t1);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s1[j] += (double)a0[j] + (double)a1[j];
-      s2[j] += (double)(a0[j] * (xa[j] - m3[j]) * q3[j]) + (double)(a1[j] * (xb[j] - m3[j]) * q3[j]);
-      s3[j] += (double)(a0[j] * (ea[j] - md[j]) * qd[j]) + (double)(a1[j] * (eb[j] - md[j]) * qd[j]);
-    }
+    for (int j = 0; j < 12; ++j) s[j] += (double)t0[j] + (double)t1[j];
   }
   for (; r < r1e; r += 4) {
-    float a0[4];
-    const float4 x0 = ld4f(x3 + (size_t)r * ldx3 + c), e0 = ld4f(xd + (size_t)r * ldxd + c);
-    bn2_masked(dz + (size_t)r * lddz + c, signs + ((size_t)r * W + blockIdx.x) * 4, gq, a0);
-    const float xa[4] = {x0.x, x0.y, x0.z, x0.w}, ea[4] = {e0.x, e0.y, e0.z, e0.w};
+    load(r, w0);
+    terms(w0, t0);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s1[j] += (double)a0[j];
-      s2[j] += (double)(a0[j] * (xa[j] - m3[j]) * q3[j]);
-      s3[j] += (double)(a0[j] * (ea[j] - md[j]) * qd[j]);
-    }
+    for (int j = 0; j < 12; ++j) s[j] += (double)t0[j];
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { red[threadIdx.x][j] = s1[j]; red[threadIdx.x][4 + j] = s2[j]; red[threadIdx.x][8 + j] = s3[j]; }
-  __syncthreads();
-  // thread t < 12 * 64 folds partial (t % 12) of column group (t / 12) over the four row lanes
-  for (int t = threadIdx.x; t < 12 * 64; t += 256) {
-    const int q = t / 12, k = t - q * 12;
-    const int cc = (blockIdx.x * 64 + q) * 4 + (k & 3);
-    const double a = red[q][k] + red[64 + q][k] + red[128 + q][k] + red[192 + q][k];
-    const size_t slot = (size_t)(blockIdx.y % BN_BWD_SLOTS) * 2 * C;
-    if (k < 4) { atomicAdd(sums3 + slot + cc, a); atomicAdd(sumsd + slot + cc, a); }
-    else if (k < 8) atomicAdd(sums3 + slot + C + cc, a);
-    else atomicAdd(sumsd + slot + C + cc, a);
-  }
-}
-
-// bn_bwd_fold_kernel for the two images of the pass above in one launch (blockIdx.y = image)
-__global__ __launch_bounds__(256) void bn_bwd_fold2_kernel(double* __restrict__ ws3, double* __restrict__ wsd, int C, float* __restrict__ dgamma3,
-                                                           float* __restrict__ dbeta3, float* __restrict__ dgammad, float* __restrict__ dbetad) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= 2 * C) return;
-  double* ws = blockIdx.y ? wsd : ws3;
-  float* dgamma = blockIdx.y ? dgammad : dgamma3;
-  float* dbeta = blockIdx.y ? dbetad : dbeta3;
-  double a = 0.0;
-#pragma unroll
-  for (int sl = 0; sl < BN_BWD_SLOTS; ++sl) a += ws[(size_t)sl * 2 * C + c];
-  ws[(size_t)BN_BWD_SLOTS * 2 * C + c] = a;
-  if (c < C) dbeta[c] += (float)a; else dgamma[c - C] += (float)a;
+  // sum d belongs to both layers' images
+  bn_slot_fold<4, 3>(red, s, 64, 4, blockIdx.x, blockIdx.y, C, [&](int k, size_t i, double a) {
+    if (k == 0) { atomicAdd(sums3 + i, a); atomicAdd(sumsd + i, a); }
+    else if (k == 1) atomicAdd(sums3 + i + C, a);
+    else atomicAdd(sumsd + i + C, a);
+  });
 }
 
 template <typename AT>
@@ -1115,34 +1108,27 @@ __global__ __launch_bounds__(256) void bn_bwd2_apply_kernel(const AT* __restrict
                                                             const double* __restrict__ sums3, const double* __restrict__ sumsd, long long M, int C,
                                                             AT* __restrict__ dx3, int lddx3, AT* __restrict__ dxd, int lddxd, long long rows_per_block) {
   const int gq = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = (blockIdx.x * 64 + gq) * 4, W = C >> 8;
-  sums3 += (size_t)BN_BWD_SLOTS * 2 * C; sumsd += (size_t)BN_BWD_SLOTS * 2 * C;     // the folded images
-  // dx = k1*d - k2 - k3*x per layer, in double as bn_bwd_apply_cg_kernel forms it
-  double k1[4], k2[4], k3[4], l1[4], l2[4], l3[4];
+  const int c = (blockIdx.x * 64 + gq) * 4;
+  BnMaskRule<4> mk;
+  bn_mask_rule(mk, SV_ACT_RELU, 0.f, BN_MASK_SIGNS, gq, nullptr, nullptr, c);
+  double k1[4], k2[4], k3[4], l1[4], l2[4], l3[4];     // per layer
   const double invM = 1.0 / (double)M;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    { const double gm = gamma3[c + j], rs = rstd3[c + j], mu = mean3[c + j], a = sums3[c + j] * invM, b = sums3[C + c + j] * invM;
-      k1[j] = gm * rs; k3[j] = gm * rs * b * rs; k2[j] = gm * rs * a - k3[j] * mu; }
-    { const double gm = gammad[c + j], rs = rstdd[c + j], mu = meand[c + j], a = sumsd[c + j] * invM, b = sumsd[C + c + j] * invM;
-      l1[j] = gm * rs; l3[j] = gm * rs * b * rs; l2[j] = gm * rs * a - l3[j] * mu; }
+    bn_bwd_coef(gamma3, mean3, rstd3, bn_bwd_folded(sums3, C), invM, 1, c + j, C, k1[j], k2[j], k3[j]);
+    bn_bwd_coef(gammad, meand, rstdd, bn_bwd_folded(sumsd, C), invM, 1, c + j, C, l1[j], l2[j], l3[j]);
   }
   const long long r0 = (long long)blockIdx.y * rows_per_block;
   long long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
 #pragma unroll 2
   for (long long r = r0 + rl; r < r1; r += 4) {
-    float d[4];
-    const float4 xv = ld4f(x3 + (size_t)r * ldx3 + c), ev = ld4f(xd + (size_t)r * ldxd + c);
-    bn2_masked(dz + (size_t)r * lddz + c, signs + ((size_t)r * W + blockIdx.x) * 4, gq, d);
-    const float xx[4] = {xv.x, xv.y, xv.z, xv.w}, ee[4] = {ev.x, ev.y, ev.z, ev.w};
-    float o[4], u[4];
+    float d[4], xx[4], ee[4], o[4], u[4];
+    ldnf<4>(x3 + (size_t)r * ldx3 + c, xx); ldnf<4>(xd + (size_t)r * ldxd + c, ee); ldnf<4>(dz + (size_t)r * lddz + c, d);
+    bn_mask_row(mk, (const AT*)nullptr, 0, signs, r, C, d, xx);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      o[j] = (float)(k1[j] * (double)d[j] - k2[j] - k3[j] * (double)xx[j]);
-      u[j] = (float)(l1[j] * (double)d[j] - l2[j] - l3[j] * (double)ee[j]);
-    }
-    st4f(dx3 + (size_t)r * lddx3 + c, make_float4(o[0], o[1], o[2], o[3]));
-    st4f(dxd + (size_t)r * lddxd + c, make_float4(u[0], u[1], u[2], u[3]));
+    for (int j = 0; j < 4; ++j) { o[j] = bn_bwd_dx(k1[j], k2[j], k3[j], d[j], xx[j]); u[j] = bn_bwd_dx(l1[j], l2[j], l3[j], d[j], ee[j]); }
+    stnf<4>(dx3 + (size_t)r * lddx3 + c, o);
+    stnf<4>(dxd + (size_t)r * lddxd + c, u);
   }
 }
 
@@ -1228,22 +1214,29 @@ __device__ __forceinline__ void pool_block_grad(const AT* __restrict__ dmp, cons
   }
 }
 
-// pass 1: G = C / CV column groups x 256 / G block lanes; blockIdx.x owns image-row PAIRS [blockIdx.x * rpb, +rpb) of the N * Ho pairs
-template <typename AT, int CV>
-__global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const AT* __restrict__ dmp, const uint8_t* __restrict__ idx, const AT* __restrict__ x,
-                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                 const float* __restrict__ fsc, const float* __restrict__ fsh, double* __restrict__ sums,
-                                                                 int N, int H, int W, int C, int Ho, int Wo, int act, float slope, int rpb) {
-  __shared__ double red[256][2 * CV + 1];
+// G = C / CV column groups x 256 / G block lanes; blockIdx.x owns image-row PAIRS [blockIdx.x * rpb, +rpb) of the N * Ho pairs.
+// APPLY = false: pass 1 (sums of dz' and dz' * xhat into slot images); APPLY = true: pass 2 (dx = k1 dz' - k2 - k3 x, dz' gathered again)
+template <typename AT, int CV, bool APPLY>
+__global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const AT* __restrict__ dmp, const uint8_t* __restrict__ idx, const AT* __restrict__ x,
+                                                          const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                          const float* __restrict__ fsc, const float* __restrict__ fsh, double* __restrict__ sums,
+                                                          AT* __restrict__ dx, int N, int H, int W, int C, int Ho, int Wo, int act, float slope,
+                                                          int training, int rpb) {
+  __shared__ double red[APPLY ? 1 : 256][2 * CV + 1];
   const int G = C / CV, gq = threadIdx.x % G, rl = threadIdx.x / G, RL = 256 / G, c = gq * CV;
-  double s1[CV], s2[CV];
+  double s[2 * CV];
 #pragma unroll
-  for (int j = 0; j < CV; ++j) { s1[j] = 0.0; s2[j] = 0.0; }
+  for (int j = 0; j < 2 * CV; ++j) s[j] = 0.0;
   if (rl < RL) {
-    float mm[CV], rr[CV], s_[CV], h_[CV];
+    double k1[CV], k2[CV], k3[CV];     // APPLY
+    float mm[CV], rr[CV];              // !APPLY
+    BnMaskRule<CV> mk;
+    bn_mask_rule(mk, act, slope, BN_MASK_X, 0, fsc, fsh, c);
 #pragma unroll
-    for (int j = 0; j < CV; ++j) { mm[j] = mean[c + j]; rr[j] = rstd[c + j]; s_[j] = fsc[c + j]; h_[j] = fsh[c + j]; }
-    const float neg = act == SV_ACT_LRELU ? slope : 0.f;
+    for (int j = 0; j < CV; ++j) {
+      if constexpr (APPLY) bn_bwd_coef(gamma, mean, rstd, bn_bwd_folded(sums, C), 1.0 / ((double)N * H * W), training, c + j, C, k1[j], k2[j], k3[j]);
+      else { mm[j] = mean[c + j]; rr[j] = rstd[c + j]; }
+    }
     const int rp0 = blockIdx.x * rpb, rp1 = min(rp0 + rpb, N * Ho);
     for (int rp = rp0; rp < rp1; ++rp) {
       const int n = rp / Ho, a = rp - n * Ho;
@@ -1257,78 +1250,24 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const AT* __res
         for (int p = 0; p < 4; ++p) {
           const int ih = 2 * a + (p >> 1), iw = 2 * b + (p & 1);
           if (ih < H && iw < W) {
-            float xx[CV];
-            ldnf<CV>(x + (((size_t)n * H + ih) * W + iw) * C + c, xx);
+            const size_t o = (((size_t)n * H + ih) * W + iw) * C + c;
+            float xx[CV], out[CV];
+            ldnf<CV>(x + o, xx);
 #pragma unroll
             for (int j = 0; j < CV; ++j) {
-              float dd = d[p][j];
-              if (act != SV_ACT_NONE) dd *= __fmaf_rn(xx[j], s_[j], h_[j]) > 0.f ? 1.f : neg;
-              t1[j] += dd; t2[j] += dd * (xx[j] - mm[j]) * rr[j];
+              bn_mask_grad(bn_mask_rule_of(mk, j), &d[p][j], &xx[j]);      // per channel: fewer live registers than all CV up front
+              if constexpr (APPLY) out[j] = bn_bwd_dx(k1[j], k2[j], k3[j], d[p][j], xx[j]);
+              else { t1[j] += d[p][j]; t2[j] += d[p][j] * (xx[j] - mm[j]) * rr[j]; }
             }
+            if constexpr (APPLY) stnf<CV>(dx + o, out);
           }
         }
       }
 #pragma unroll
-      for (int j = 0; j < CV; ++j) { s1[j] += (double)t1[j]; s2[j] += (double)t2[j]; }
+      for (int j = 0; j < CV; ++j) { s[j] += (double)t1[j]; s[CV + j] += (double)t2[j]; }
     }
   }
-#pragma unroll
-  for (int j = 0; j < CV; ++j) { red[threadIdx.x][j] = s1[j]; red[threadIdx.x][CV + j] = s2[j]; }
-  __syncthreads();
-  for (int t = threadIdx.x; t < 2 * CV * G; t += 256) {
-    const int q = t / (2 * CV), k = t % (2 * CV);
-    double acc = 0.0;
-    for (int l = 0; l < RL; ++l) acc += red[l * G + q][k];
-    atomicAdd(sums + (size_t)(blockIdx.x % BN_BWD_SLOTS) * 2 * C + (k < CV ? 0 : C) + q * CV + (k % CV), acc);
-  }
-}
-
-// pass 2: dx = k1 dz' - k2 - k3 x (double coefficients: the mean-removal terms must cancel to rounding), dz' gathered again
-template <typename AT, int CV>
-__global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const AT* __restrict__ dmp, const uint8_t* __restrict__ idx, const AT* __restrict__ x,
-                                                                const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                const float* __restrict__ fsc, const float* __restrict__ fsh, const double* __restrict__ sums,
-                                                                AT* __restrict__ dx, int N, int H, int W, int C, int Ho, int Wo, int act, float slope,
-                                                                int training, int rpb) {
-  const int G = C / CV, gq = threadIdx.x % G, rl = threadIdx.x / G, RL = 256 / G, c = gq * CV;
-  if (rl >= RL) return;
-  sums += (size_t)BN_BWD_SLOTS * 2 * C;     // the folded image (bn_bwd_fold_kernel)
-  double k1[CV], k2[CV], k3[CV];
-  float s_[CV], h_[CV];
-  const double invM = 1.0 / ((double)N * H * W);
-#pragma unroll
-  for (int j = 0; j < CV; ++j) {
-    const double gm = gamma[c + j], rs = rstd[c + j], mu = mean[c + j];
-    k1[j] = gm * rs;
-    if (training) { const double sa = sums[c + j] * invM, sb = sums[C + c + j] * invM; k3[j] = gm * rs * sb * rs; k2[j] = gm * rs * sa - k3[j] * mu; }
-    else { k2[j] = 0.0; k3[j] = 0.0; }
-    s_[j] = fsc[c + j]; h_[j] = fsh[c + j];
-  }
-  const float neg = act == SV_ACT_LRELU ? slope : 0.f;
-  const int rp0 = blockIdx.x * rpb, rp1 = min(rp0 + rpb, N * Ho);
-  for (int rp = rp0; rp < rp1; ++rp) {
-    const int n = rp / Ho, a = rp - n * Ho;
-    for (int b = rl; b < Wo; b += RL) {
-      float d[4][CV];
-      pool_block_grad<AT, CV>(dmp, idx, n, a, b, c, C, Ho, Wo, d);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int ih = 2 * a + (p >> 1), iw = 2 * b + (p & 1);
-        if (ih < H && iw < W) {
-          const size_t o = (((size_t)n * H + ih) * W + iw) * C + c;
-          float xx[CV], out[CV];
-          ldnf<CV>(x + o, xx);
-#pragma unroll
-          for (int j = 0; j < CV; ++j) {
-            float dd = d[p][j];
-            if (act != SV_ACT_NONE) dd *= __fmaf_rn(xx[j], s_[j], h_[j]) > 0.f ? 1.f : neg;
-            out[j] = (float)(k1[j] * (double)dd - k2[j] - k3[j] * (double)xx[j]);
-          }
-          stnf<CV>(dx + o, out);
-        }
-      }
-    }
-  }
+  if constexpr (!APPLY) bn_slot_fold_one<CV>(red, s, G, RL, 0, blockIdx.x, C, sums);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1381,24 +1320,19 @@ __global__ __launch_bounds__(256) void bn_pool3d_bwd_kernel(const AT* __restrict
   const int G = C / CV, gq = threadIdx.x % G, rl = threadIdx.x / G, RL = 256 / G, c = gq * CV;
   const long long nblk = (long long)N * BD * BH * BW;
   const long long q0 = (long long)blockIdx.x * bpw, q1 = q0 + bpw < nblk ? q0 + bpw : nblk;
-  double s1[CV], s2[CV], k1[CV], k2[CV], k3[CV];
-  float mm[CV], rr[CV], s_[CV], h_[CV];
+  double s[2 * CV];
 #pragma unroll
-  for (int j = 0; j < CV; ++j) { s1[j] = 0.0; s2[j] = 0.0; k1[j] = k2[j] = k3[j] = 0.0; mm[j] = rr[j] = s_[j] = h_[j] = 0.f; }
+  for (int j = 0; j < 2 * CV; ++j) s[j] = 0.0;
   if (rl < RL) {
+    double k1[CV], k2[CV], k3[CV];     // APPLY
+    float mm[CV], rr[CV];              // !APPLY
+    BnMaskRule<CV> mk;
+    bn_mask_rule(mk, act, slope, BN_MASK_X, 0, fsc, fsh, c);
 #pragma unroll
-    for (int j = 0; j < CV; ++j) { mm[j] = mean[c + j]; rr[j] = rstd[c + j]; s_[j] = fsc[c + j]; h_[j] = fsh[c + j]; }
-    if constexpr (APPLY) {
-      const double* fin = sums + (size_t)BN_BWD_SLOTS * 2 * C;     // the folded image (bn_bwd_fold_kernel)
-      const double invM = 1.0 / ((double)N * D * H * W);
-#pragma unroll
-      for (int j = 0; j < CV; ++j) {
-        const double gm = gamma[c + j], rs = rr[j], mu = mm[j];
-        k1[j] = gm * rs;
-        if (training) { const double sa = fin[c + j] * invM, sb = fin[C + c + j] * invM; k3[j] = gm * rs * sb * rs; k2[j] = gm * rs * sa - k3[j] * mu; }
-      }
+    for (int j = 0; j < CV; ++j) {
+      if constexpr (APPLY) bn_bwd_coef(gamma, mean, rstd, bn_bwd_folded(sums, C), 1.0 / ((double)N * D * H * W), training, c + j, C, k1[j], k2[j], k3[j]);
+      else { mm[j] = mean[c + j]; rr[j] = rstd[c + j]; }
     }
-    const float neg = act == SV_ACT_LRELU ? slope : 0.f;
     for (long long q = q0 + rl; q < q1; q += RL) {
       long long t = q;
       const int bw = (int)(t % BW); t /= BW; const int bh = (int)(t % BH); t /= BH; const int bd = (int)(t % BD); const int n = (int)(t / BD);
@@ -1420,36 +1354,26 @@ __global__ __launch_bounds__(256) void bn_pool3d_bwd_kernel(const AT* __restrict
         const int id = 2 * bd + (k >> 2), ih = 2 * bh + ((k >> 1) & 1), iw = 2 * bw + (k & 1);
         if (id < D && ih < H && iw < W) {
           const size_t o = ((((size_t)n * D + id) * H + ih) * W + iw) * C + c;
-          float xx[CV], out[CV];
+          float xx[CV], dd[CV], out[CV];
           ldnf<CV>(x + o, xx);
 #pragma unroll
+          for (int j = 0; j < CV; ++j) dd[j] = tp[j] == k ? g[j] : 0.f;
+          bn_mask_grad(mk, dd, xx);
+#pragma unroll
           for (int j = 0; j < CV; ++j) {
-            float dd = tp[j] == k ? g[j] : 0.f;
-            if (act != SV_ACT_NONE) dd *= __fmaf_rn(xx[j], s_[j], h_[j]) > 0.f ? 1.f : neg;
-            if constexpr (APPLY) out[j] = (float)(k1[j] * (double)dd - k2[j] - k3[j] * (double)xx[j]);
-            else { t1[j] += dd; t2[j] += dd * (xx[j] - mm[j]) * rr[j]; }
+            if constexpr (APPLY) out[j] = bn_bwd_dx(k1[j], k2[j], k3[j], dd[j], xx[j]);
+            else { t1[j] += dd[j]; t2[j] += dd[j] * (xx[j] - mm[j]) * rr[j]; }
           }
           if constexpr (APPLY) stnf<CV>(dx + o, out);
         }
       }
-      if constexpr (!APPLY) {
 #pragma unroll
-        for (int j = 0; j < CV; ++j) { s1[j] += (double)t1[j]; s2[j] += (double)t2[j]; }
-      }
+      for (int j = 0; j < CV; ++j) { s[j] += (double)t1[j]; s[CV + j] += (double)t2[j]; }
     }
   }
-  if constexpr (!APPLY) {
-#pragma unroll
-    for (int j = 0; j < CV; ++j) { red[threadIdx.x][j] = s1[j]; red[threadIdx.x][CV + j] = s2[j]; }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 2 * CV * G; t += 256) {
-      const int q = t / (2 * CV), k = t % (2 * CV);
-      double acc = 0.0;
-      for (int l = 0; l < RL; ++l) acc += red[l * G + q][k];
-      atomicAdd(sums + (size_t)(blockIdx.x % BN_BWD_SLOTS) * 2 * C + (k < CV ? 0 : C) + q * CV + (k % CV), acc);
-    }
-  }
+  if constexpr (!APPLY) bn_slot_fold_one<CV>(red, s, G, RL, 0, blockIdx.x, C, sums);
 }
+
 
 }  // namespace sv
 
@@ -1654,13 +1578,24 @@ extern "C" int sv_ln_image_bwd(const void* dy, const void* x, const float* w, co
   return check_launch("sv_ln_image_bwd");
 }
 
+// Rows per workgroup of a BatchNorm pass whose grid is (cg column groups, row blocks): about `target` workgroups in all, but none with less
+// than one loop step of `step` rows
+static inline long long bn_rows_per_block(long long M, int cg, int target, int step) {
+  long long splits = target / cg; if (splits < 1) splits = 1;
+  const long long maxs = (M + step - 1) / step; if (splits > maxs) splits = maxs;
+  return (M + splits - 1) / splits;
+}
+// fold the slot images of one layer, or (wsd given) of the two layers of the bn3 + down-sampling pass in one launch
+static inline void bn_bwd_fold(hipStream_t s, int C, double* ws, float* dgamma, float* dbeta, double* wsd = nullptr, float* dgammad = nullptr,
+                               float* dbetad = nullptr) {
+  hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256), wsd ? 2 : 1), dim3(256), 0, s, ws, wsd, C, dgamma, dbeta, dgammad, dbetad);
+}
+
 extern "C" int sv_bn_stats(const void* x, long long M, int C, int ld, double* sums, int act_dtype, void* stream) {
   SV_REQUIRE(x && sums && M > 0 && C > 0 && ld >= C, "bn_stats: bad arguments");
   SV_REQUIRE_ACT(act_dtype);
   const int cg = cdiv(C, 64);
-  long long splits = 2048 / cg; if (splits < 1) splits = 1;
-  const long long maxs = (M + 63) / 64; if (splits > maxs) splits = maxs;
-  const long long rpb = (M + splits - 1) / splits;
+  const long long rpb = bn_rows_per_block(M, cg, 2048, 64);
   SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(bn_stats_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, (hipStream_t)stream, static_cast<const AT*>(x), M, C, ld, sums, rpb););
   return check_launch("sv_bn_stats");
 }
@@ -1702,9 +1637,7 @@ static int scale_shift_act_impl(const void* x, int ldx, const float* scale, cons
   } else if (vec) {
     const int G = C / 4 < 64 ? C / 4 : 64, RL = 256 / G;
     const int cg = cdiv(C / 4, G);
-    long long splits = 4096 / cg; if (splits < 1) splits = 1;
-    const long long maxs = (M + 4 * RL - 1) / (4 * RL); if (splits > maxs) splits = maxs;
-    const long long rpb = (M + splits - 1) / splits;
+    const long long rpb = bn_rows_per_block(M, cg, 4096, 4 * RL);
     SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(scale_shift_act_cg_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, static_cast<const AT*>(x), ldx, scale, shift,
                                                   static_cast<const AT*>(residual), ldr, static_cast<AT*>(y), ldy, M, C, act, slope, rpb, G, signs););
   } else {
@@ -1772,21 +1705,17 @@ extern "C" int sv_bn_maxpool_bwd(const void* dpooled, const void* idx, const voi
   const unsigned nb = (unsigned)((rows + rpb - 1) / rpb);
   int rpa = (int)((rows + 8191) / 8192); if (rpa < 1) rpa = 1;
   const unsigned na = (unsigned)((rows + rpa - 1) / rpa);
-  if (bn_pool_cv8(act_dtype, C, dpooled, x, dx) && ((uintptr_t)idx & 7) == 0) {
-    typedef __bf16 AT;
-    hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<AT, 8>), dim3(nb), dim3(256), 0, s, static_cast<const AT*>(dpooled), static_cast<const uint8_t*>(idx), static_cast<const AT*>(x),
-                       save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, N, H, W, C, Ho, Wo, act, slope, rpb);
-    hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, sums_ws, C, dgamma, dbeta);
-    hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<AT, 8>), dim3(na), dim3(256), 0, s, static_cast<const AT*>(dpooled), static_cast<const uint8_t*>(idx), static_cast<const AT*>(x),
-                       gamma, save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, static_cast<AT*>(dx), N, H, W, C, Ho, Wo, act, slope, training, rpa);
-    return check_launch("sv_bn_maxpool_bwd");
-  }
-  SV_DISPATCH_ACT(act_dtype,
-    hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<AT, 4>), dim3(nb), dim3(256), 0, s, static_cast<const AT*>(dpooled), static_cast<const uint8_t*>(idx), static_cast<const AT*>(x),
-                       save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, N, H, W, C, Ho, Wo, act, slope, rpb);
-    hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, sums_ws, C, dgamma, dbeta);
-    hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<AT, 4>), dim3(na), dim3(256), 0, s, static_cast<const AT*>(dpooled), static_cast<const uint8_t*>(idx), static_cast<const AT*>(x),
-                       gamma, save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, static_cast<AT*>(dx), N, H, W, C, Ho, Wo, act, slope, training, rpa););
+#define SV_POOL_BWD(AT_, CV_)                                                                                                                               \
+  hipLaunchKernelGGL((bn_pool_bwd_kernel<AT_, CV_, false>), dim3(nb), dim3(256), 0, s, static_cast<const AT_*>(dpooled), static_cast<const uint8_t*>(idx),     \
+                     static_cast<const AT_*>(x), gamma, save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, static_cast<AT_*>(dx), N, H, W, C, Ho, Wo, act,    \
+                     slope, training, rpb);                                                                                                                 \
+  bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);                                                                                                                \
+  hipLaunchKernelGGL((bn_pool_bwd_kernel<AT_, CV_, true>), dim3(na), dim3(256), 0, s, static_cast<const AT_*>(dpooled), static_cast<const uint8_t*>(idx),      \
+                     static_cast<const AT_*>(x), gamma, save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, static_cast<AT_*>(dx), N, H, W, C, Ho, Wo, act,    \
+                     slope, training, rpa);
+  if (bn_pool_cv8(act_dtype, C, dpooled, x, dx) && ((uintptr_t)idx & 7) == 0) { SV_POOL_BWD(__bf16, 8) }
+  else { SV_DISPATCH_ACT(act_dtype, SV_POOL_BWD(AT, 4)); }
+#undef SV_POOL_BWD
   return check_launch("sv_bn_maxpool_bwd");
 }
 
@@ -1827,7 +1756,7 @@ extern "C" int sv_bn_maxpool3d_bwd(const void* dpooled, const void* idx, const v
   hipLaunchKernelGGL((bn_pool3d_bwd_kernel<AT_, CV_, false>), dim3(nr), dim3(256), 0, s, static_cast<const AT_*>(dpooled), static_cast<const uint8_t*>(idx),   \
                      static_cast<const AT_*>(x), gamma, save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, static_cast<AT_*>(dx), N, D, H, W, C, act, slope,  \
                      training, bpr);                                                                                                                        \
-  hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, sums_ws, C, dgamma, dbeta);                                               \
+  bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);                                                                                                                \
   hipLaunchKernelGGL((bn_pool3d_bwd_kernel<AT_, CV_, true>), dim3(na), dim3(256), 0, s, static_cast<const AT_*>(dpooled), static_cast<const uint8_t*>(idx),    \
                      static_cast<const AT_*>(x), gamma, save_mean, save_rstd, fwd_scale, fwd_shift, sums_ws, static_cast<AT_*>(dx), N, D, H, W, C, act, slope,  \
                      training, bpa);
@@ -1865,31 +1794,25 @@ static int bn_bwd_impl(const void* dz, int lddz, const void* z, int ldz, const u
       const long long nb = (M + 64LL * rpt - 1) / (64LL * rpt);
       hipLaunchKernelGGL(bn_bwd_reduce_narrow_kernel<AT>, dim3((unsigned)nb), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope,
                          sums_ws, rpt, fsc, fsh);
-      hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, sums_ws, C, dgamma, dbeta);
+      bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
       long long blocks = (M + 63) / 64; if (blocks > 8192) blocks = 8192;
       hipLaunchKernelGGL(bn_bwd_apply_narrow_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
                          act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh);
     } else if (vec) {
       const int G = C / 4 < 64 ? C / 4 : 64, RL = 256 / G;
       const int cg = cdiv(C / 4, G);
-      long long splits = 2048 / cg; if (splits < 1) splits = 1;
-      const long long maxs = (M + 2 * RL - 1) / (2 * RL); if (splits > maxs) splits = maxs;
-      const long long rpb = (M + splits - 1) / splits;
+      const long long rpb = bn_rows_per_block(M, cg, 2048, 2 * RL), arpb = bn_rows_per_block(M, cg, 4096, 4 * RL);
       // with a residual-branch gradient to produce (dres) the reduce pass stores the masked gradient there and the apply pass reads IT,
       // mask-free, instead of (dz, z): 7 instead of 8 passes over the tensor.  The sums are of the fp32 values, the stored ones are
       // rounded to the storage type - as dres always was.  The hand-off needs the stored value to BE the masked gradient: true for ReLU
       // (dz or 0) and for fp32 storage, not for LeakyReLU in bf16, where slope * dz rounds and dx would inherit 2^-9 |gamma rstd dz'| -
       // there the apply pass masks dz itself (from z / x, or from the sign words) and dres only carries the residual branch's gradient.
-      static const int premask_on = [] { const char* v = getenv("SV_BN_PREMASK"); return v ? atoi(v) : 1; }();
       const bool exact = !(act == SV_ACT_LRELU && act_dtype == SV_BF16);
-      const bool premask = (premask_on || signs) && dres_ && act != SV_ACT_NONE && exact;
+      const bool premask = dres_ && act != SV_ACT_NONE && exact;
       const bool sign_apply = signs && !premask;       // the reduce pass still delivers dres, the apply pass reads (dz, words)
       hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope,
                          sums_ws, rpb, G, fsc, fsh, (premask || sign_apply) ? dres_ : (AT*)nullptr, lddres, signs);
-      hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, sums_ws, C, dgamma, dbeta);
-      long long asplits = 4096 / cg; if (asplits < 1) asplits = 1;
-      const long long amax = (M + 4 * RL - 1) / (4 * RL); if (asplits > amax) asplits = amax;
-      const long long arpb = (M + asplits - 1) / asplits;
+      bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
       if (sign_apply)
         hipLaunchKernelGGL((bn_bwd_apply_cg_kernel<AT, true>), dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, dz_, lddz, (const AT*)nullptr, 0, x_, ldx, gamma, save_mean,
                            save_rstd, sums_ws, M, C, act, slope, training, dx_, lddx, (AT*)nullptr, 0, fsc, fsh, arpb, G, signs);
@@ -1902,14 +1825,12 @@ static int bn_bwd_impl(const void* dz, int lddz, const void* z, int ldz, const u
     } else {
       int CW = 1; while (CW < C && CW < 64) CW <<= 1;         // channel lanes: next power of two of C, at most 64
       const int cg = cdiv(C, CW), RLg = 256 / CW;
-      long long splits = 2048 / cg; if (splits < 1) splits = 1;
-      const long long maxs = (M + 4 * RLg - 1) / (4 * RLg); if (splits > maxs) splits = maxs;
-      const long long rpb = (M + splits - 1) / splits;
+      const long long rpb = bn_rows_per_block(M, cg, 2048, 4 * RLg);
       hipLaunchKernelGGL(bn_bwd_reduce_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope, sums_ws, rpb, CW, fsc, fsh);
-      hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, sums_ws, C, dgamma, dbeta);
+      bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
       long long blocks = (M * C + 255) / 256; if (blocks > 8192) blocks = 8192;
       hipLaunchKernelGGL(bn_bwd_apply_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
-                         act, slope, training, dx_, lddx, dres_, lddres, dgamma, dbeta, fsc, fsh);
+                         act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh);
     });
   return check_launch("sv_bn_bwd");
 }
@@ -1950,9 +1871,7 @@ extern "C" int sv_scale_shift_act2_signs(const void* x3, int ldx3, const float* 
              (((uintptr_t)scale3 | (uintptr_t)shift3 | (uintptr_t)scaled | (uintptr_t)shiftd | (uintptr_t)signs) & 15) == 0,
              "scale_shift_act2_signs: needs C %% 256 == 0 and 4-aligned rows (C=%d)", C);
   const int cg = C / 256;
-  long long splits = 4096 / cg; if (splits < 1) splits = 1;
-  const long long maxs = (M + 15) / 16; if (splits > maxs) splits = maxs;
-  const long long rpb = (M + splits - 1) / splits;
+  const long long rpb = bn_rows_per_block(M, cg, 4096, 16);
   SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(scale_shift_act2_cg_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, (hipStream_t)stream,
                                                 static_cast<const AT*>(x3), ldx3, scale3, shift3, static_cast<const AT*>(xd), ldxd, scaled, shiftd,
                                                 static_cast<AT*>(y), ldy, M, C, rpb, static_cast<unsigned long long*>(signs)););
@@ -1973,18 +1892,13 @@ extern "C" int sv_bn_bwd2_signs(const void* dz, int lddz, const void* signs, con
              "bn_bwd2_signs: needs C %% 256 == 0 and 4-aligned rows (C=%d)", C);
   hipStream_t s = (hipStream_t)stream;
   const int cg = C / 256;
-  long long splits = 2048 / cg; if (splits < 1) splits = 1;
-  const long long maxs = (M + 7) / 8; if (splits > maxs) splits = maxs;
-  const long long rpb = (M + splits - 1) / splits;
-  long long asplits = 4096 / cg; if (asplits < 1) asplits = 1;
-  const long long amax = (M + 15) / 16; if (asplits > amax) asplits = amax;
-  const long long arpb = (M + asplits - 1) / asplits;
+  const long long rpb = bn_rows_per_block(M, cg, 2048, 8), arpb = bn_rows_per_block(M, cg, 4096, 16);
   const unsigned long long* w = static_cast<const unsigned long long*>(signs);
   SV_DISPATCH_ACT(act_dtype,
     const AT* dz_ = static_cast<const AT*>(dz); const AT* x3_ = static_cast<const AT*>(x3); const AT* xd_ = static_cast<const AT*>(xd);
     hipLaunchKernelGGL(bn_bwd2_reduce_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, dz_, lddz, w, x3_, ldx3, save_mean3, save_rstd3, xd_, ldxd,
                        save_meand, save_rstdd, M, C, sums_ws3, sums_wsd, rpb);
-    hipLaunchKernelGGL(bn_bwd_fold2_kernel, dim3(cdiv(2 * C, 256), 2), dim3(256), 0, s, sums_ws3, sums_wsd, C, dgamma3, dbeta3, dgammad, dbetad);
+    bn_bwd_fold(s, C, sums_ws3, dgamma3, dbeta3, sums_wsd, dgammad, dbetad);
     hipLaunchKernelGGL(bn_bwd2_apply_kernel<AT>, dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, dz_, lddz, w, x3_, ldx3, gamma3, save_mean3, save_rstd3, xd_, ldxd,
                        gammad, save_meand, save_rstdd, sums_ws3, sums_wsd, M, C, static_cast<AT*>(dx3), lddx3, static_cast<AT*>(dxd), lddxd, arpb););
   return check_launch("sv_bn_bwd2_signs");
