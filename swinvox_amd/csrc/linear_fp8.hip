@@ -84,10 +84,15 @@
 //                    scales in place; pass 2: a 128-row x 64-column tile is scaled, rounded and transposed through LDS, 16-byte stores along M.
 //   lf_contract      the k-loop of linear_fp8_kernel (staging, swizzled LDS image, fragment reads, MFMA block) over a range of k-steps: the one
 //                    copy the forward, the data-gradient and the weight-gradient kernel run.
+//   shared by the GEMM kernels (both recipes)   lf_tile_contract: the tile of blockIdx.x, the LDS buffers, lf_contract.  lf_col_scales / lf_row:
+//                    the lane's rows and 16 columns, with the division of the per-row recipe.  lf_pieces: the width of a lane's loads and
+//                    stores (16 bytes, 4 elements, 1 element), chosen once per lane, one templated body per epilogue.  The data-gradient
+//                    kernel shares the first and writes the other two out (reason at the kernel).  LinArgs / DgradArgs / WgradArgs<MX>.
 //   linear_fp8_dgrad_kernel   lf_contract over the full contraction + the epilogue above.
-//   linear_fp8_wgrad_kernel   grid tiles(N) x tiles(K) x splits, split z contracts the k-steps [z nk / splits, (z + 1) nk / splits); dy^T is the
-//                    row operand, so a lane's 16 consecutive outputs run along k, the contiguous dimension of dw; fp32 atomicAdd into dw
-//                    (a plain read-add-write when splits == 1).  splits = 0 picks enough workgroups for 2 per CU of 256 CUs.
+//   linear_fp8_wgrad_kernel<MX = false>   grid tiles(N) x tiles(K) x splits, split z contracts the k-steps [z nk / splits, (z + 1) nk / splits); dy^T
+//                    is the row operand, so a lane's 16 consecutive outputs run along k, the contiguous dimension of dw; fp32 atomicAdd into dw
+//                    (a plain read-add-write when splits == 1).  splits = 0 picks enough workgroups for 2 per CU of 256 CUs
+//                    (linear_wgrad_splits, for both recipes).
 //
 // MX backward (opt-in: set_linear_fp8(True, backward=True, backward_recipe="mx")): both gradients on MX operands.  A block scale over 32 TOKENS of a
 // column needs no global maximum, so the transposing quantiser is one launch and one read, and nothing is left to divide out.  NORMATIVE: everything
@@ -103,11 +108,12 @@
 //                    the maximum of its valid rows.
 // Kernels of the MX backward
 //   quant_cols_mx_kernel   ONE launch, src read once: the 128-row x 64-column tile of quant_cols_write_kernel; thread (tx, ty) owns rows 32 ty .. + 31
-//                    of column tx = exactly one MX block, so the block maximum stays in its registers (32 values held, no exchange).  8 packed dwords
-//                    go through the same LDS transpose (pitch 33 dwords) into 16-byte stores along M; the four scale bytes of a column and tile are
-//                    gathered in LDS into one dword store.  Column sums: fp64 partial per workgroup, one fp32 atomic per workgroup and column.
+//                    of column tx = exactly one MX block, so the block maximum stays in its registers (32 values held, no exchange:
+//                    mx_pack_block32).  The way out is the transposing quantisers' shared one (store_cols_tile): the [column][33 dwords] LDS
+//                    image, 16-byte stores along M, the four scale bytes of a column and tile as one dword, and for the column sums the fp64
+//                    partials of a workgroup as one fp32 atomic per column.
 //   linear_fp8_dgrad_kernel<.., MX = true>   lf_contract<true> + the epilogue above without its 16 divisions per lane and row; LDS 67 584 bytes.
-//   linear_mxfp8_wgrad_kernel   lf_contract<true> over split z's k-steps; NO atomics into dw.  One split: the only writer of an element does a
+//   linear_fp8_wgrad_kernel<MX = true>   lf_contract<true> over split z's k-steps; NO atomics into dw.  One split: the only writer of an element does a
 //                    16-byte read-add-write into dw.  More: split z stores its fp32 partial tile into a caller-owned workspace [splits][N][K]
 //                    (16-byte stores) and linear_mxfp8_wgrad_reduce_kernel adds the partials to dw in ascending z: dw is bit-identical from run to
 //                    run for a given `splits`.  splits = 0: enough workgroups for two per CU of 256 CUs, at most one per 128 tokens.
@@ -126,8 +132,8 @@
 //                  under one of the two (tests/test_cpu_linear_mxfp8_store_recipe.py: the weight gradient moves by <= 2.5e-6, L1-relative; bound 1e-5).
 // Kernel of the MX store
 //   mx_rows_to_cols_kernel   ONE launch, xq and xs read once, no atomics: a 128-token x 128-column tile per workgroup, 16-byte global loads along
-//                  K (8 lanes = the 128 contiguous bytes of a row), a byte transpose through LDS (described at the kernel), 16-byte stores along M,
-//                  the four scale bytes of a column and tile as one aligned dword.
+//                  K (8 lanes = the 128 contiguous bytes of a row), a byte transpose through LDS (described at the kernel), mx_pack_block32 and
+//                  store_cols_tile as in quant_cols_mx_kernel.
 //
 // MX dual quantiser (opt-in on the host: set_mx_dual_quant(True) under the MX backward): the upstream gradient dy feeds the data gradient as MX rows
 // and the weight gradient as MX columns; one launch reads it once and writes both.  NORMATIVE, for finite inputs:
@@ -146,6 +152,7 @@
 //                  four row blocks of a token and the four token blocks of a column lie inside the tile: no maximum crosses workgroups.
 #include "common.h"
 #include <atomic>
+#include <type_traits>
 
 namespace sv {
 
@@ -211,10 +218,24 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const T* __restrict_
 }
 
 // ---- GEMM ----------------------------------------------------------------------------------------------------------------------------
-struct LinFp8Args {
-  const uint8_t* xq; const float* sx; const uint8_t* wq; const float* sw; void* out;
+// One by-value argument struct per GEMM kind.  MX selects the scale operands: E8M0 bytes [rows][pitch / 32] in place of one fp32 scale per row.
+template <bool MX> using LfScale = std::conditional_t<MX, uint8_t, float>;
+
+template <bool MX> struct LinArgs {
+  const uint8_t* xq; const LfScale<MX>* sx; const uint8_t* wq; const LfScale<MX>* sw; void* out;
   int M, N, Kp;
   const float* bias; const void* residual; int ldr; const float* row_scale; int rows_per_scale; void* pre_act; int act; float slope; int ldc;
+  uint8_t* q_out; uint8_t* qs_out;   // MX: [M][N] e4m3 bytes and [M][N / 32] scale bytes of the stored output (N % 128 == 0, no residual), or both null
+};
+template <bool MX> struct DgradArgs {    // dx[M, K] = dy[M, N] W[N, K]: dy rows and W^T rows, contraction over Np
+  const uint8_t* dq; const LfScale<MX>* sd; const uint8_t* wtq; const LfScale<MX>* swt; void* out;
+  int M, K, Np;
+  const void* act_grad_src; int act_grad_kind; float slope; int ldc;
+};
+template <bool MX> struct WgradArgs {    // dw[N, K] += dy^T[N, M] x[M, K]: dy^T rows and x^T rows, contraction over Mp
+  const uint8_t* dyt; const LfScale<MX>* sdc; const uint8_t* xt; const LfScale<MX>* sxc; float* dw;
+  float* ws;                             // MX: [splits][N][K] fp32, used when splits > 1
+  int N, K, Mp, ldw, splits;
 };
 
 constexpr int LF_BM = 128, LF_BN = 128, LF_BK = 128, LF_PITCH = 128, LF_TILE = LF_BM * LF_PITCH;   // bytes
@@ -322,42 +343,92 @@ __device__ __forceinline__ void lf_contract(const uint8_t* __restrict__ xq, int 
   }
 }
 
-__device__ __forceinline__ void lf_zero(f32x4 (&acc)[4][4]) {
+// Where a lane stands in its workgroup's 128 x 128 output tile: wave (wm, wn) owns a 64 x 64 quarter, lane (lr, lg) of it the rows
+// row0 + 64 wm + 16 mt + lr and the 16 consecutive columns from c0 (lf_contract's result map).
+struct LfTile { int wm, wn, lr, lg, row0, col0, c0; };
+
+// The part every GEMM kernel of this file begins with: tile blockIdx.x of a [R] x [C] output (consecutive workgroups share the row operand),
+// the LDS buffers, and acc = the contraction of a [R][pitch] with b [C][pitch] over the k-steps ks0 .. ks1 - 1.
+// LDS: [2 buffers][a tile, b tile][128 rows][128 bytes, swizzled] (+ [2][scale dwords] under MX).
+template <bool MX>
+__device__ __forceinline__ LfTile lf_tile_contract(const uint8_t* __restrict__ a, const LfScale<MX>* __restrict__ sa, int R, const uint8_t* __restrict__ b,
+                                                   const LfScale<MX>* __restrict__ sb, int C, int pitch, int ks0, int ks1, f32x4 (&acc)[4][4]) {
+  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE + (MX ? 2 * LF_SCALES : 0)];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tiles_c = (C + LF_BN - 1) / LF_BN;
+  LfTile t;
+  t.wm = wave >> 1; t.wn = wave & 1; t.lr = lane & 15; t.lg = lane >> 4;
+  t.row0 = (blockIdx.x / tiles_c) * LF_BM; t.col0 = (blockIdx.x % tiles_c) * LF_BN;
+  t.c0 = t.col0 + t.wn * 64 + t.lg * 16;
 #pragma unroll
-  for (int a = 0; a < 4; ++a)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if constexpr (MX) lf_contract<true>(a, R, b, C, (size_t)pitch, t.row0, t.col0, ks0, ks1, lf_smem, acc, sa, sb);
+  else lf_contract(a, R, b, C, (size_t)pitch, t.row0, t.col0, ks0, ks1, lf_smem, acc);
+  return t;
 }
 
-// MX form of the call: E8M0 scale bytes [rows][Kp / 32] in place of the fp32 row scales, and the optional emission of the stored output's own MX rows
-struct LinMxArgs {
-  const uint8_t* xq; const uint8_t* xs; const uint8_t* wq; const uint8_t* ws; void* out;
-  int M, N, Kp;
-  const float* bias; const void* residual; int ldr; const float* row_scale; int rows_per_scale; void* pre_act; int act; float slope; int ldc;
-  uint8_t* q_out; uint8_t* qs_out;   // [M][N] e4m3 bytes and [M][N / 32] scale bytes of the stored output (N % 128 == 0, no residual), or both null
-};
-template <bool MX> struct LinArgsOf { typedef LinFp8Args type; };
-template <> struct LinArgsOf<true> { typedef LinMxArgs type; };
+// The walk over a lane's outputs (forward and weight gradient; the data gradient writes its own out, see there).  A kernel whose lane has
+// columns (c0 < C) calls lf_col_scales once and then, for mt = 0 .. 3, lf_row: false when the lane's row m of block mt is past R, else v = the
+// values of the columns c0 .. c0 + 15 of row m (columns >= C are the caller's to skip).  Per-row recipe: val = acc / (sa[m] sb[c]), fp32 IEEE
+// division; MX: val = acc, the MFMA applied both block scales, and sc stays unset.
+template <bool MX>
+__device__ __forceinline__ void lf_col_scales(const LfTile& t, const LfScale<MX>* __restrict__ sb, int C, float (&sc)[16]) {
+  if constexpr (!MX) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) sc[j] = sb[min(t.c0 + j, C - 1)];
+  }
+}
+template <bool MX>
+__device__ __forceinline__ bool lf_row(const LfTile& t, const f32x4 (&acc)[4][4], int mt, const LfScale<MX>* __restrict__ sa, int R,
+                                       const float (&sc)[16], int& m, float (&v)[16]) {
+  m = t.row0 + t.wm * 64 + mt * 16 + t.lr;
+  if (m >= R) return false;
+  if constexpr (MX) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3];
+  } else {
+    const float sm = sa[m];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sm * sc[j]);
+  }
+  return true;
+}
 
-// MX = false: the per-row recipe (val = acc / (sx sw)).  MX = true: the MX recipe (block scales applied by the MFMA, val = acc); out may then be
-// null when q_out is given.  Emission: the stored row (after the activation, rounded to AT) is quantised as quant_rows_mx_kernel would quantise
-// it; a 32-column block is the 16 + 16 columns of lanes lg and lg ^ 1 (lane ^ 16) of the same row, so one exchange gives its maximum.
+// W consecutive elements <-> registers: common.h's ldnf / stnf, and ldf / stf for a single element
+template <int W, typename T> __device__ __forceinline__ void ld_piece(const T* p, float (&v)[W]) {
+  if constexpr (W == 1) v[0] = ldf(p); else ldnf<W>(p, v);
+}
+template <int W, typename T> __device__ __forceinline__ void st_piece(T* p, const float (&v)[W]) {
+  if constexpr (W == 1) stf(p, v[0]); else stnf<W>(p, v);
+}
+
+// A lane's 16 columns from c0, cut into pieces of W elements: body(integral_constant W, q) for each piece at columns c0 + q .. + W - 1 that
+// begins inside C (callers pick W so that a piece is in range as a whole).  A guard per piece, not a break: the loop must unroll fully, q indexes
+// registers.  lf_pieces picks W once per lane: CV (one 16-byte access) when `wide`, 4 when `quad`, else single elements.
+template <int W, typename F>
+__device__ __forceinline__ void lf_pieces_of(int c0, int C, F& body) {
+#pragma unroll
+  for (int q = 0; q < 16; q += W)
+    if (c0 + q < C) body(std::integral_constant<int, W>{}, q);
+}
+template <int CV, typename F>
+__device__ __forceinline__ void lf_pieces(bool wide, bool quad, int c0, int C, F&& body) {
+  if (wide || (CV == 4 && quad)) lf_pieces_of<CV>(c0, C, body);
+  else if (CV != 4 && quad) lf_pieces_of<4>(c0, C, body);
+  else lf_pieces_of<1>(c0, C, body);
+}
+
+// ---- forward --------------------------------------------------------------------------------------------------------------------------------------
+// MX = false: the per-row recipe.  MX = true: the MX recipe; out may then be null when q_out is given.  Emission: the stored row (after the
+// activation, rounded to AT) is quantised as quant_rows_mx_kernel would quantise it; a 32-column block is the 16 + 16 columns of lanes lg and
+// lg ^ 1 (lane ^ 16) of the same row, so one exchange gives its maximum.
+// Epilogue on the registers: 16-byte pieces (8 bf16 / 4 fp32), 32 / 64 contiguous bytes per lane and row.
 template <typename AT, bool FAST, bool MX = false>
-__global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const typename LinArgsOf<MX>::type p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE + (MX ? 2 * LF_SCALES : 0)];   // [2 buffers][x tile, w tile][128 rows][128 bytes, swizzled] (+ [2][scale dwords])
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int tiles_n = (p.N + LF_BN - 1) / LF_BN;
-  const int row0 = (blockIdx.x / tiles_n) * LF_BM, col0 = (blockIdx.x % tiles_n) * LF_BN;   // consecutive workgroups share the x rows
-
+__global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const LinArgs<MX> p) {
   f32x4 acc[4][4];   // [column block nt][row block mt]
-  lf_zero(acc);
-  if constexpr (MX) lf_contract<true>(p.xq, p.M, p.wq, p.N, (size_t)p.Kp, row0, col0, 0, p.Kp / LF_BK, lf_smem, acc, p.xs, p.ws);
-  else lf_contract(p.xq, p.M, p.wq, p.N, (size_t)p.Kp, row0, col0, 0, p.Kp / LF_BK, lf_smem, acc);
+  const LfTile t = lf_tile_contract<MX>(p.xq, p.sx, p.M, p.wq, p.sw, p.N, p.Kp, 0, p.Kp / LF_BK, acc);
 
-  // ---- epilogue on the registers: with the permuted W rows, lane (lr, lg) holds row 16 mt + lr and, over its four blocks nt, the 16
-  // consecutive columns 16 lg + 4 nt + j of the wave's 64: 16-byte stores (8 bf16 / 4 fp32), 32 / 64 contiguous bytes per lane and row
   AT* __restrict__ Y = static_cast<AT*>(p.out);
   AT* __restrict__ PRE = static_cast<AT*>(p.pre_act);
   const AT* __restrict__ RES = static_cast<const AT*>(p.residual);
@@ -365,137 +436,73 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_kernel(const typename LinAr
   const bool vec4 = ((p.ldc | p.N) & 3) == 0 && (!RES || (p.ldr & 3) == 0);   // (base pointers: 4 elements, checked on the host)
   const bool vecw = ((p.ldc | p.N) & (CV - 1)) == 0 && (!RES || (p.ldr & (CV - 1)) == 0) &&
                     ((((uintptr_t)Y) | ((uintptr_t)PRE) | ((uintptr_t)RES)) & 15) == 0;
-  const int c0 = col0 + wn * 64 + lg * 16;
-  if (c0 < p.N) {
-    float swn[16], bias[16];
+  if (t.c0 >= p.N) return;
+  float bias[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int n = min(c0 + j, p.N - 1);
-      if constexpr (!MX) swn[j] = p.sw[n];
-      bias[j] = p.bias ? p.bias[n] : 0.f;
-    }
+  for (int j = 0; j < 16; ++j) bias[j] = p.bias ? p.bias[min(t.c0 + j, p.N - 1)] : 0.f;
+  float scol[16];
+  lf_col_scales<MX>(t, p.sw, p.N, scol);
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int m = row0 + wm * 64 + mt * 16 + lr;
-      if (m >= p.M) continue;
-      float sxm = 1.f;
-      if constexpr (!MX) sxm = p.sx[m];
-      const float sc = (RES && p.row_scale) ? p.row_scale[m / p.rows_per_scale] : 1.f;
-      float v[16];
-      if constexpr (MX) {
+  for (int mt = 0; mt < 4; ++mt) {
+    int m;
+    float v[16];
+    if (!lf_row<MX>(t, acc, mt, p.sx, p.M, scol, m, v)) continue;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] + bias[j];
-        if (p.q_out) {   // N % 128 == 0 and no residual (host): all 16 columns are in range and the stored value is act(v)
-          float t[16], am = 0.f;
-#pragma unroll
-          for (int j = 0; j < 16; ++j) {
-            t[j] = (float)(AT)apply_act_t<FAST>(v[j], p.act, p.slope);
-            am = fmaxf(am, fabsf(t[j]));
-          }
-          am = fmaxf(am, __shfl_xor(am, 16));              // the partner holds the same row: it is here whenever this lane is
-          const int E = mx_block_exp(am);
-          *reinterpret_cast<uint4*>(p.q_out + (size_t)m * p.N + c0) =
-              make_uint4(pack4_e4m3_mx(t[0], t[1], t[2], t[3], E), pack4_e4m3_mx(t[4], t[5], t[6], t[7], E),
-                         pack4_e4m3_mx(t[8], t[9], t[10], t[11], E), pack4_e4m3_mx(t[12], t[13], t[14], t[15], E));
-          if ((lg & 1) == 0) p.qs_out[(size_t)m * (p.N >> 5) + (c0 >> 5)] = (uint8_t)(E + 127);
-          if (!Y && !PRE) continue;                        // no backward follows: neither out nor pre_act is stored
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = acc[j >> 2][mt][j & 3] / (sxm * swn[j]) + bias[j];
-      }
-      const size_t o = (size_t)m * p.ldc + c0;
-      const size_t orow = (size_t)m * p.ldr + c0;
-      if (vecw) {   // N % CV == 0: a piece is in range as a whole
-#pragma unroll
-        for (int q = 0; q < 16 / CV; ++q) {
-          if (c0 + q * CV >= p.N) break;
-          float t[CV];
-#pragma unroll
-          for (int j = 0; j < CV; ++j) t[j] = v[q * CV + j];
-          if (PRE) stnf<CV>(PRE + o + q * CV, t);
-          if constexpr (MX) { if (!Y) continue; }          // MX store: pre_act and the emitted rows are all the backward reads
-#pragma unroll
-          for (int j = 0; j < CV; ++j) t[j] = apply_act_t<FAST>(t[j], p.act, p.slope);
-          if (RES) {
-            float r[CV];
-            ldnf<CV>(RES + orow + q * CV, r);
-#pragma unroll
-            for (int j = 0; j < CV; ++j) t[j] = r[j] + sc * t[j];
-          }
-          stnf<CV>(Y + o + q * CV, t);
-        }
-      } else if (vec4) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (c0 + q * 4 >= p.N) break;
-          float t[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) t[j] = v[q * 4 + j];
-          if (PRE) stnf<4>(PRE + o + q * 4, t);
-          if constexpr (MX) { if (!Y) continue; }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) t[j] = apply_act_t<FAST>(t[j], p.act, p.slope);
-          if (RES) {
-            float r[4];
-            ldnf<4>(RES + orow + q * 4, r);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) t[j] = r[j] + sc * t[j];
-          }
-          stnf<4>(Y + o + q * 4, t);
-        }
-      } else {
+    for (int j = 0; j < 16; ++j) v[j] += bias[j];
+    if constexpr (MX) {
+      if (p.q_out) {   // N % 128 == 0 and no residual (host): all 16 columns are in range and the stored value is act(v)
+        float s[16], am = 0.f;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-          if (c0 + j < p.N) {
-            float t = v[j];
-            if (PRE) stf(PRE + o + j, t);
-            if constexpr (MX) { if (!Y) continue; }
-            t = apply_act_t<FAST>(t, p.act, p.slope);
-            if (RES) t = ldf(RES + orow + j) + sc * t;
-            stf(Y + o + j, t);
-          }
+          s[j] = (float)(AT)apply_act_t<FAST>(v[j], p.act, p.slope);
+          am = fmaxf(am, fabsf(s[j]));
         }
+        am = fmaxf(am, __shfl_xor(am, 16));                // the partner holds the same row: it is here whenever this lane is
+        const int E = mx_block_exp(am);
+        *reinterpret_cast<uint4*>(p.q_out + (size_t)m * p.N + t.c0) =
+            make_uint4(pack4_e4m3_mx(s[0], s[1], s[2], s[3], E), pack4_e4m3_mx(s[4], s[5], s[6], s[7], E),
+                       pack4_e4m3_mx(s[8], s[9], s[10], s[11], E), pack4_e4m3_mx(s[12], s[13], s[14], s[15], E));
+        if ((t.lg & 1) == 0) p.qs_out[(size_t)m * (p.N >> 5) + (t.c0 >> 5)] = (uint8_t)(E + 127);
+        if (!Y && !PRE) continue;                          // no backward follows: neither out nor pre_act is stored
       }
     }
+    const float sc = (RES && p.row_scale) ? p.row_scale[m / p.rows_per_scale] : 1.f;
+    const size_t o = (size_t)m * p.ldc + t.c0, orow = (size_t)m * p.ldr + t.c0;
+    lf_pieces<CV>(vecw, vec4, t.c0, p.N, [&](auto w, int q) {
+      constexpr int W = decltype(w)::value;
+      float x[W];
+#pragma unroll
+      for (int j = 0; j < W; ++j) x[j] = v[q + j];
+      if (PRE) st_piece(PRE + o + q, x);
+      if constexpr (MX) { if (!Y) return; }                // MX store: pre_act and the emitted rows are all the backward reads
+#pragma unroll
+      for (int j = 0; j < W; ++j) x[j] = apply_act_t<FAST>(x[j], p.act, p.slope);
+      if (RES) {
+        float r[W];
+        ld_piece(RES + orow + q, r);
+#pragma unroll
+        for (int j = 0; j < W; ++j) x[j] = r[j] + sc * x[j];
+      }
+      st_piece(Y + o + q, x);
+    });
   }
 }
 
 // ---- data gradient: dx[M, K] = dy[M, N] W[N, K], the contraction runs over N -----------------------------------------------------------------
-struct LinFp8DgradArgs {
-  const uint8_t* dq; const float* sd; const uint8_t* wtq; const float* swt; void* out;
-  int M, K, Np;
-  const void* act_grad_src; int act_grad_kind; float slope; int ldc;
-};
-
-// MX form of the call: E8M0 scale bytes [M][Np / 32] of dy and [K][Np / 32] of W^T in place of the fp32 scales
-struct LinMxDgradArgs {
-  const uint8_t* dq; const uint8_t* ds; const uint8_t* wtq; const uint8_t* wts; void* out;
-  int M, K, Np;
-  const void* act_grad_src; int act_grad_kind; float slope; int ldc;
-};
-template <bool MX> struct DgradArgsOf { typedef LinFp8DgradArgs type; };
-template <> struct DgradArgsOf<true> { typedef LinMxDgradArgs type; };
-
+// The walk and the two piece widths are written out in this kernel, as they were before the other GEMM kernels came to share lf_row and
+// lf_pieces: through either helper its epilogue compiles to other code and measures 0.5 - 2.4 % slower.  The layers with
+// a short contraction (fc2: two k-steps) are all epilogue.
 template <typename AT, bool FAST, bool MX = false>
-__global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const typename DgradArgsOf<MX>::type p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE + (MX ? 2 * LF_SCALES : 0)];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int tiles_k = (p.K + LF_BN - 1) / LF_BN;
-  const int row0 = (blockIdx.x / tiles_k) * LF_BM, col0 = (blockIdx.x % tiles_k) * LF_BN;   // consecutive workgroups share the dy rows
-
+__global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const DgradArgs<MX> p) {
   f32x4 acc[4][4];
-  lf_zero(acc);
-  if constexpr (MX) lf_contract<true>(p.dq, p.M, p.wtq, p.K, (size_t)p.Np, row0, col0, 0, p.Np / LF_BK, lf_smem, acc, p.ds, p.wts);
-  else lf_contract(p.dq, p.M, p.wtq, p.K, (size_t)p.Np, row0, col0, 0, p.Np / LF_BK, lf_smem, acc);
+  const LfTile t = lf_tile_contract<MX>(p.dq, p.sd, p.M, p.wtq, p.swt, p.K, p.Np, 0, p.Np / LF_BK, acc);
+  const int wm = t.wm, lr = t.lr, row0 = t.row0;
 
   AT* __restrict__ Y = static_cast<AT*>(p.out);
   const AT* __restrict__ G = static_cast<const AT*>(p.act_grad_src);   // layout of the output
   constexpr int CV = sizeof(AT) == 2 ? 8 : 4;
   const bool vecw = ((p.ldc | p.K) & (CV - 1)) == 0 && ((((uintptr_t)Y) | ((uintptr_t)G)) & 15) == 0;
-  const int c0 = col0 + wn * 64 + lg * 16;
+  const int c0 = t.c0;
   if (c0 >= p.K) return;
   float swk[16];
   if constexpr (!MX) {
@@ -545,99 +552,44 @@ __global__ __launch_bounds__(256, 2) void linear_fp8_dgrad_kernel(const typename
 }
 
 // ---- weight gradient: dw[N, K] += dy^T[N, M] x[M, K], the contraction runs over M (the tokens) ------------------------------------------------------
-struct LinFp8WgradArgs {
-  const uint8_t* dyt; const float* sdc; const uint8_t* xt; const float* sxc; float* dw;
-  int N, K, Mp, ldw, splits;
-};
-
-__global__ __launch_bounds__(256, 2) void linear_fp8_wgrad_kernel(const LinFp8WgradArgs p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int tiles_k = (p.K + LF_BN - 1) / LF_BN;
-  const int row0 = (blockIdx.x / tiles_k) * LF_BM, col0 = (blockIdx.x % tiles_k) * LF_BN;   // rows of dw = n, columns = k
+// Grid tiles(N) x tiles(K) x splits; split z contracts the k-steps [z nk / splits, (z + 1) nk / splits).  dy^T is the row operand and x^T the
+// permuted one: a lane's 16 consecutive outputs run along k, the contiguous dimension of dw.
+template <bool MX>
+__global__ __launch_bounds__(256, 2) void linear_fp8_wgrad_kernel(const WgradArgs<MX> p) {
   const int nk = p.Mp / LF_BK, z = blockIdx.y;
   const int ks0 = (int)((long long)z * nk / p.splits), ks1 = (int)((long long)(z + 1) * nk / p.splits);   // splits <= nk: no share is empty
-
   f32x4 acc[4][4];
-  lf_zero(acc);
-  // dy^T is the row operand and x^T the permuted one: a lane's 16 consecutive outputs run along k, the contiguous dimension of dw
-  lf_contract(p.dyt, p.N, p.xt, p.K, (size_t)p.Mp, row0, col0, ks0, ks1, lf_smem, acc);
-
-  const int c0 = col0 + wn * 64 + lg * 16;
-  if (c0 >= p.K) return;
-  float sxk[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) sxk[j] = p.sxc[min(c0 + j, p.K - 1)];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int n = row0 + wm * 64 + mt * 16 + lr;
-    if (n >= p.N) continue;
-    const float sdn = p.sdc[n];
-    float* __restrict__ d = p.dw + (size_t)n * p.ldw + c0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      if (c0 + j < p.K) {
-        const float val = acc[j >> 2][mt][j & 3] / (sdn * sxk[j]);
-        if (p.splits == 1) d[j] += val;                    // the only writer of this element
-        else atomicAdd(d + j, val);
-      }
-    }
-  }
-}
-
-// ---- MX weight gradient: the same contraction on MX operands, no atomics into dw ----------------------------------------------------------------
-struct LinMxWgradArgs {
-  const uint8_t* dyt; const uint8_t* dys; const uint8_t* xt; const uint8_t* xs; float* dw; float* ws;   // ws [splits][N][K] fp32, used when splits > 1
-  int N, K, Mp, ldw, splits;
-};
-
-__global__ __launch_bounds__(256, 2) void linear_mxfp8_wgrad_kernel(const LinMxWgradArgs p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lf_smem[2 * 2 * LF_TILE + 2 * LF_SCALES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int tiles_k = (p.K + LF_BN - 1) / LF_BN;
-  const int row0 = (blockIdx.x / tiles_k) * LF_BM, col0 = (blockIdx.x % tiles_k) * LF_BN;   // rows of dw = n, columns = k
-  const int nk = p.Mp / LF_BK, z = blockIdx.y;
-  const int ks0 = (int)((long long)z * nk / p.splits), ks1 = (int)((long long)(z + 1) * nk / p.splits);   // splits <= nk: no share is empty
-
-  f32x4 acc[4][4];
-  lf_zero(acc);
-  // dy^T is the row operand and x^T the permuted one: a lane's 16 consecutive outputs run along k, the contiguous dimension of dw
-  lf_contract<true>(p.dyt, p.N, p.xt, p.K, (size_t)p.Mp, row0, col0, ks0, ks1, lf_smem, acc, p.dys, p.xs);
-
-  const int c0 = col0 + wn * 64 + lg * 16;
-  if (c0 >= p.K) return;
-  // one split: read-add-write into dw (row stride ldw), this lane is the only writer of its elements; more: a plain store of the partial
-  // into slice z of the workspace (row stride K), which the reduce kernel folds into dw
+  const LfTile t = lf_tile_contract<MX>(p.dyt, p.sdc, p.N, p.xt, p.sxc, p.K, p.Mp, ks0, ks1, acc);   // rows of dw = n, columns = k
+  if (t.c0 >= p.K) return;
   const bool one = p.splits == 1;
-  float* __restrict__ base = one ? p.dw : p.ws + (size_t)z * p.N * p.K;
-  const int ldo = one ? p.ldw : p.K;
+  // MX: NO atomics into dw.  One split: read-add-write into dw (row stride ldw), this lane is the only writer of its elements; more: a plain
+  // store of the partial into slice z of the workspace (row stride K), which the reduce kernel folds into dw
+  float* __restrict__ base = (!MX || one) ? p.dw : p.ws + (size_t)z * p.N * p.K;
+  const int ldo = (!MX || one) ? p.ldw : p.K;
   const bool vec = ((ldo | p.K) & 3) == 0 && (((uintptr_t)base) & 15) == 0;   // K % 4 == 0: a 16-byte piece is in range as a whole
+  float scol[16];
+  lf_col_scales<MX>(t, p.sxc, p.K, scol);
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
-    const int n = row0 + wm * 64 + mt * 16 + lr;
-    if (n >= p.N) continue;
-    float* __restrict__ d = base + (size_t)n * ldo + c0;
-    if (vec) {
+    int n;
+    float v[16];
+    if (!lf_row<MX>(t, acc, mt, p.sdc, p.N, scol, n, v)) continue;
+    float* __restrict__ d = base + (size_t)n * ldo + t.c0;
+    if constexpr (MX) {
+      lf_pieces<4>(vec, false, t.c0, p.K, [&](auto w, int q) {
+        constexpr int W = decltype(w)::value;
+        float x[W], o[W];
+        if (one) ld_piece(d + q, o);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (c0 + q * 4 >= p.K) break;
-        float4 t = make_float4(acc[q][mt][0], acc[q][mt][1], acc[q][mt][2], acc[q][mt][3]);
-        if (one) {
-          const float4 o = *reinterpret_cast<const float4*>(d + q * 4);
-          t = make_float4(o.x + t.x, o.y + t.y, o.z + t.z, o.w + t.w);
-        }
-        *reinterpret_cast<float4*>(d + q * 4) = t;
-      }
+        for (int j = 0; j < W; ++j) x[j] = one ? o[j] + v[q + j] : v[q + j];
+        st_piece(d + q, x);
+      });
     } else {
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (c0 + j < p.K) {
-          const float val = acc[j >> 2][mt][j & 3];
-          d[j] = one ? d[j] + val : val;
+        if (t.c0 + j < p.K) {
+          if (one) d[j] += v[j];                           // the only writer of this element
+          else atomicAdd(d + j, v[j]);
         }
       }
     }
@@ -672,11 +624,53 @@ __global__ __launch_bounds__(256) void linear_mxfp8_wgrad_reduce_kernel(const fl
   }
 }
 
-// ---- column quantiser: src [M, C] (row stride ld) -> dst [C][Mp] e4m3 bytes, one scale per column ---------------------------------------------------
-constexpr int QC_COLS = 64, QC_ROWS1 = 256, QC_ROWS2 = 128, QC_PITCH = 33;   // pass-2 LDS rows: 32 dwords + 1, conflict-free on both sides
+// ---- transposing quantisers: src [M, C] (row stride ld) -> dst [C][Mp] e4m3 bytes ---------------------------------------------------------------------
+// Shared by all four: a tile of 128 rows x COLS columns leaves through an LDS image [column][COLS_PITCH dwords] (32 dwords = 128 rows, + 1:
+// conflict-free on both sides - 32 consecutive columns x pitch 33 on the way in, 4 columns x 8 pieces on the way out).
+constexpr int COLS_PITCH = 33;
+constexpr int QC_COLS = 64, QC_ROWS1 = 256, QC_ROWS2 = 128;   // the column quantisers' tiles: pass 1, pass 2 / MX
+constexpr int RB_ROWS = 128, RB_COLS = 128;                   // the re-blocker's and the dual quantiser's tile
 
-// pass 1: amax[c] = max over the rows of |src[m, c]| as the bit pattern of the non-negative float (integer max = float max there), into a zeroed
-// buffer; optionally colsum[c] += sum over the rows (fp64 partial per workgroup, one fp32 atomic per workgroup and column)
+// The way out of the image: 16-byte stores along M (COLS x 8 pieces over 256 threads); then thread t < COLS, for column c0 + t, the column's four
+// E8M0 bytes of this tile as one aligned dword (sbytes [COLS], or null) and the column sum - the four fp64 partials ssum [4][COLS] of the
+// workgroup, added in ascending order, as ONE fp32 atomicAdd (ssum or colsum null: none).  Columns >= C write nothing.
+template <int COLS>
+__device__ __forceinline__ void store_cols_tile(const uint32_t* tile, const uint32_t* sbytes, const double* ssum, int c0, int C, int m0, int Mp,
+                                                uint8_t* __restrict__ dst, uint8_t* __restrict__ scales, float* __restrict__ colsum) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < COLS / 32; ++i) {
+    const int pc = tid + 256 * i, col = pc >> 3, piece = pc & 7;
+    if (c0 + col < C) {
+      const uint32_t* t = tile + col * COLS_PITCH + piece * 4;
+      *reinterpret_cast<uint4*>(dst + (size_t)(c0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
+    }
+  }
+  if (tid < COLS && c0 + tid < C) {
+    if (sbytes) reinterpret_cast<uint32_t*>(scales + (size_t)(c0 + tid) * (Mp >> 5))[m0 >> 7] = sbytes[tid];
+    if (ssum && colsum) atomicAdd(colsum + c0 + tid, (float)(ssum[tid] + ssum[COLS + tid] + ssum[2 * COLS + tid] + ssum[3 * COLS + tid]));
+  }
+}
+
+// One MX block: the maximum of 32 values of one column, mx_block_exp, 8 x pack4_e4m3_mx into registers; returns the exponent E (byte E + 127).
+__device__ __forceinline__ int mx_pack_block32(const float (&v)[32], uint32_t (&pk)[8]) {
+  float am = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) am = fmaxf(am, fabsf(v[j]));
+  const int E = mx_block_exp(am);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) pk[i] = pack4_e4m3_mx(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], E);
+  return E;
+}
+// ... and its place in the image: rows 32 b .. + 31 of column col, byte b of the column's scale dword
+__device__ __forceinline__ void place_block32(uint32_t* tile, uint32_t* sbytes, int col, int b, const uint32_t (&pk)[8], int E) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) tile[col * COLS_PITCH + b * 8 + i] = pk[i];
+  reinterpret_cast<uint8_t*>(sbytes)[col * 4 + b] = (uint8_t)(E + 127);
+}
+
+// per-row recipe, pass 1: amax[c] = max over the rows of |src[m, c]| as the bit pattern of the non-negative float (integer max = float max there),
+// into a zeroed buffer; optionally colsum[c] += sum over the rows (fp64 partial per workgroup, one fp32 atomic per workgroup and column)
 template <typename T>
 __global__ __launch_bounds__(256) void quant_cols_amax_kernel(const T* __restrict__ src, int M, int C, long long ld, int* __restrict__ amax_bits,
                                                               float* __restrict__ colsum) {
@@ -713,11 +707,11 @@ __global__ void quant_cols_scale_kernel(float* __restrict__ scales, int C) {
   }
 }
 
-// pass 2: a tile of 128 rows x 64 columns is scaled, rounded to e4m3 and transposed through LDS; 16-byte stores along M.  Rows past M are zero bytes.
+// pass 2: a tile of 128 rows x 64 columns is scaled, rounded to e4m3 and transposed through the image.  Rows past M are zero bytes.
 template <typename T>
 __global__ __launch_bounds__(256) void quant_cols_write_kernel(const T* __restrict__ src, int M, int C, long long ld, const float* __restrict__ scales,
                                                                uint8_t* __restrict__ dst, int Mp) {
-  __shared__ uint32_t tile[QC_COLS * QC_PITCH];            // [column][32 dwords = 128 rows]
+  __shared__ uint32_t tile[QC_COLS * COLS_PITCH];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c0 = blockIdx.x * QC_COLS, m0 = blockIdx.y * QC_ROWS2;
   const int c = c0 + tx;
@@ -728,17 +722,10 @@ __global__ __launch_bounds__(256) void quant_cols_write_kernel(const T* __restri
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = (c < C && m + j < M) ? ldf(src + (size_t)(m + j) * ld + c) : 0.f;
-    tile[tx * QC_PITCH + ty * 8 + i] = pack4_e4m3(v[0] * s, v[1] * s, v[2] * s, v[3] * s);
+    tile[tx * COLS_PITCH + ty * 8 + i] = pack4_e4m3(v[0] * s, v[1] * s, v[2] * s, v[3] * s);
   }
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {                            // 64 columns x 8 pieces of 16 bytes
-    const int pc = threadIdx.x + 256 * i, col = pc >> 3, piece = pc & 7;
-    if (c0 + col < C) {
-      const uint32_t* t = tile + col * QC_PITCH + piece * 4;
-      *reinterpret_cast<uint4*>(dst + (size_t)(c0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
-    }
-  }
+  store_cols_tile<QC_COLS>(tile, nullptr, nullptr, c0, C, m0, Mp, dst, nullptr, nullptr);
 }
 
 // MX column quantiser: src [M, C] -> dst [C][Mp] e4m3 bytes + scales [C][Mp / 32] E8M0 bytes, equal to quant_rows_mx_kernel on the transposed tensor.
@@ -748,42 +735,26 @@ __global__ __launch_bounds__(256) void quant_cols_write_kernel(const T* __restri
 template <typename T>
 __global__ __launch_bounds__(256) void quant_cols_mx_kernel(const T* __restrict__ src, int M, int C, long long ld, uint8_t* __restrict__ dst, int Mp,
                                                             uint8_t* __restrict__ scales, float* __restrict__ colsum) {
-  __shared__ uint32_t tile[QC_COLS * QC_PITCH];            // [column][32 dwords = 128 rows]
-  __shared__ uint32_t sbytes[QC_COLS];                     // [column][4 blocks of the tile]: one dword per column
-  __shared__ double ssum[4][QC_COLS];
+  __shared__ uint32_t tile[QC_COLS * COLS_PITCH];
+  __shared__ uint32_t sbytes[QC_COLS];
+  __shared__ double ssum[4 * QC_COLS];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c0 = blockIdx.x * QC_COLS, m0 = blockIdx.y * QC_ROWS2;
   const int c = c0 + tx, mb = m0 + ty * 32;
   float v[32];
-  float am = 0.f;
-  double sum = 0.0;
 #pragma unroll
-  for (int j = 0; j < 32; ++j) {
-    v[j] = (c < C && mb + j < M) ? ldf(src + (size_t)(mb + j) * ld + c) : 0.f;
-    am = fmaxf(am, fabsf(v[j]));
-  }
+  for (int j = 0; j < 32; ++j) v[j] = (c < C && mb + j < M) ? ldf(src + (size_t)(mb + j) * ld + c) : 0.f;
   if (colsum) {
+    double sum = 0.0;
 #pragma unroll
     for (int j = 0; j < 32; ++j) sum += (double)v[j];
-    ssum[ty][tx] = sum;
+    ssum[ty * QC_COLS + tx] = sum;
   }
-  const int E = mx_block_exp(am);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) tile[tx * QC_PITCH + ty * 8 + i] = pack4_e4m3_mx(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], E);
-  reinterpret_cast<uint8_t*>(sbytes)[tx * 4 + ty] = (uint8_t)(E + 127);
+  uint32_t pk[8];
+  const int E = mx_pack_block32(v, pk);
+  place_block32(tile, sbytes, tx, ty, pk, E);
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {                            // 64 columns x 8 pieces of 16 bytes
-    const int pc = threadIdx.x + 256 * i, col = pc >> 3, piece = pc & 7;
-    if (c0 + col < C) {
-      const uint32_t* t = tile + col * QC_PITCH + piece * 4;
-      *reinterpret_cast<uint4*>(dst + (size_t)(c0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
-    }
-  }
-  if (ty == 0 && c < C) {
-    reinterpret_cast<uint32_t*>(scales + (size_t)c * (Mp >> 5))[m0 >> 7] = sbytes[tx];   // the tile's four blocks of column c: one aligned dword
-    if (colsum) atomicAdd(colsum + c, (float)(ssum[0][tx] + ssum[1][tx] + ssum[2][tx] + ssum[3][tx]));
-  }
+  store_cols_tile<QC_COLS>(tile, sbytes, ssum, c0, C, m0, Mp, dst, scales, colsum);
 }
 
 // MX re-blocker: the MX ROWS of a stored tensor (xq [M][Kp] bytes + xs [M][Kp / 32] scale bytes, a block = 32 columns of a row) become the MX COLUMN
@@ -794,16 +765,14 @@ __global__ __launch_bounds__(256) void quant_cols_mx_kernel(const T* __restrict_
 //            four k-blocks of the tile).  Rows past M are zero bytes.
 //   compute  wave b owns tokens 32 b .. + 31; lane l owns column 64 u + l, u = 0, 1: one MX block per (lane, u).  It reads its 32 bytes down the
 //            column (the 32 lanes of a group read 8 consecutive dwords of one row: no conflict), decodes byte 2^(s - 127) in fp32 (exact; the row's
-//            scale dword comes from lane j of the wave by v_readlane), takes the maximum and packs 8 dwords under the column block's exponent.
-//   store    the 8 dwords go into the [128][33]-dword image of quant_cols_mx_kernel (conflict-free on both sides: 32 consecutive columns x pitch 33
-//            on the way in, 4 columns x 8 pieces on the way out) and leave as 16-byte stores along M; the four scale bytes of a column are one dword.
-constexpr int RB_ROWS = 128, RB_COLS = 128, RB_PITCH = 33;
+//            scale dword comes from lane j of the wave by v_readlane) and packs the block under the column block's exponent.
+//   store    the shared image and way out (store_cols_tile).
 __global__ __launch_bounds__(256) void mx_rows_to_cols_kernel(const uint8_t* __restrict__ xq, int Kp, const uint8_t* __restrict__ xs, int M, int K,
                                                               uint8_t* __restrict__ dst, int Mp, uint8_t* __restrict__ scales) {
   __shared__ __attribute__((aligned(16))) uint8_t in[RB_ROWS * RB_COLS];   // [token][column] bytes
   __shared__ uint32_t srows[RB_ROWS];                        // [token]: the scale bytes of the tile's four k-blocks
-  __shared__ uint32_t tile[RB_COLS * RB_PITCH];            // [column][32 dwords = 128 tokens]
-  __shared__ uint32_t sbytes[RB_COLS];                     // [column][4 token blocks]: one dword per column
+  __shared__ uint32_t tile[RB_COLS * COLS_PITCH];
+  __shared__ uint32_t sbytes[RB_COLS];
   const int tid = threadIdx.x, lane = tid & 63, b = tid >> 6;
   const int k0 = blockIdx.x * RB_COLS, m0 = blockIdx.y * RB_ROWS;
 #pragma unroll
@@ -820,33 +789,22 @@ __global__ __launch_bounds__(256) void mx_rows_to_cols_kernel(const uint8_t* __r
   for (int u = 0; u < 2; ++u) {
     const int col = u * 64 + lane, sh = (col >> 5) * 8;    // the column's k-block inside the tile selects the byte of the scale dword
     float v[32];
-    float am = 0.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
       const int s = (__builtin_amdgcn_readlane(srow, j) >> sh) & 0xff;
       v[j] = ldexpf(__builtin_amdgcn_cvt_f32_fp8((int)in[(b * 32 + j) * RB_COLS + col], 0), s - 127);
-      am = fmaxf(am, fabsf(v[j]));
     }
-    const int E = mx_block_exp(am);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) tile[col * RB_PITCH + b * 8 + i] = pack4_e4m3_mx(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], E);
-    reinterpret_cast<uint8_t*>(sbytes)[col * 4 + b] = (uint8_t)(E + 127);
+    uint32_t pk[8];
+    const int E = mx_pack_block32(v, pk);
+    place_block32(tile, sbytes, col, b, pk, E);
   }
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {                            // 128 columns x 8 pieces of 16 bytes
-    const int pc = tid + 256 * i, col = pc >> 3, piece = pc & 7;
-    if (k0 + col < K) {
-      const uint32_t* t = tile + col * RB_PITCH + piece * 4;
-      *reinterpret_cast<uint4*>(dst + (size_t)(k0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
-    }
-  }
-  if (tid < RB_COLS && k0 + tid < K) reinterpret_cast<uint32_t*>(scales + (size_t)(k0 + tid) * (Mp >> 5))[m0 >> 7] = sbytes[tid];   // one aligned dword
+  store_cols_tile<RB_COLS>(tile, sbytes, nullptr, k0, K, m0, Mp, dst, scales, nullptr);
 }
 
 // MX dual quantiser: ONE read of src [M, N] gives the MX ROW operand (row_q [M][Np] + row_s [M][Np / 32], equal to quant_rows_mx_kernel) and the MX
 // COLUMN operand (col_q [N][Mp] + col_s [N][Mp / 32] + colsum, equal to quant_cols_mx_kernel) - see "MX dual quantiser" in the header.  One workgroup =
-// 128 tokens x 128 columns; ROWS_OUT = false compiles the row work out (the column form alone, with this kernel's loader).
+// 128 tokens x 128 columns (the re-blocker's tile); ROWS_OUT = false compiles the row work out (the column form alone, with this kernel's loader).
 //   load     a chunk = 16 consecutive elements of one tile row (sizeof(T) 16-byte pieces: two for bf16, four for fp32); thread t moves the chunks t,
 //            t + 256, t + 512, t + 768 (8 lanes = the 128 columns of one row).  A row that is not 16-byte aligned, and the chunk that crosses N, take
 //            load4_guarded's per-element path.  Rows past M and columns >= N are zeros.  The chunk goes into a plain [128][128] LDS image of T
@@ -856,10 +814,9 @@ __global__ __launch_bounds__(256) void mx_rows_to_cols_kernel(const uint8_t* __r
 //            (zero bytes, byte 127), written like any other chunk.
 //   columns  mx_rows_to_cols_kernel's compute and store on the staged values: wave b owns tokens 32 b .. + 31, lane l columns l and 64 + l, one MX
 //            block per (lane, column) read down the tile (a wave reads 64 consecutive elements of one row: no conflict); fp64 column sums as in
-//            quant_cols_mx_kernel.  The 8 packed dwords, the scale byte and the sum wait in registers for a barrier, after which the [column][33
-//            dwords] image, the scale dwords and the partial sums take the place of the input image: LDS is 32 KB (bf16) / 64 KB (fp32).
+//            quant_cols_mx_kernel.  The 8 packed dwords, the exponent and the sum wait in registers for a barrier, after which the image, the scale
+//            dwords and the partial sums take the place of the input image: LDS is 32 KB (bf16) / 64 KB (fp32).
 //            Columns >= N write nothing; rows past M were loaded as zeros and leave as the zero bytes of the column rows.
-constexpr int DQ_ROWS = 128, DQ_COLS = 128, DQ_PITCH = 33;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <typename T>
@@ -873,15 +830,15 @@ __global__ __launch_bounds__(256) void quant_rows_cols_mx_kernel(const T* __rest
                                                                  uint8_t* __restrict__ row_s, uint8_t* __restrict__ col_q, int Mp,
                                                                  uint8_t* __restrict__ col_s, float* __restrict__ colsum) {
   constexpr int P = sizeof(T);                             // 16-byte pieces per chunk
-  constexpr int IN_BYTES = DQ_ROWS * DQ_COLS * (int)sizeof(T);
-  constexpr int SUM_BYTES = 4 * DQ_COLS * 8, TILE_BYTES = DQ_COLS * DQ_PITCH * 4, OUT_BYTES = SUM_BYTES + TILE_BYTES + DQ_COLS * 4;
+  constexpr int IN_BYTES = RB_ROWS * RB_COLS * (int)sizeof(T);
+  constexpr int SUM_BYTES = 4 * RB_COLS * 8, TILE_BYTES = RB_COLS * COLS_PITCH * 4, OUT_BYTES = SUM_BYTES + TILE_BYTES + RB_COLS * 4;
   __shared__ __attribute__((aligned(16))) uint8_t smem[IN_BYTES > OUT_BYTES ? IN_BYTES : OUT_BYTES];
   const T* in = reinterpret_cast<const T*>(smem);          // [token][column], then (after the second barrier):
   double* ssum = reinterpret_cast<double*>(smem);          // [4 token blocks][column]
-  uint32_t* tile = reinterpret_cast<uint32_t*>(smem + SUM_BYTES);               // [column][32 dwords = 128 tokens]
-  uint32_t* sbytes = reinterpret_cast<uint32_t*>(smem + SUM_BYTES + TILE_BYTES);   // [column][4 token blocks]: one dword per column
+  uint32_t* tile = reinterpret_cast<uint32_t*>(smem + SUM_BYTES);
+  uint32_t* sbytes = reinterpret_cast<uint32_t*>(smem + SUM_BYTES + TILE_BYTES);
   const int tid = threadIdx.x, lane = tid & 63, b = tid >> 6;
-  const int k0 = blockIdx.x * DQ_COLS, m0 = blockIdx.y * DQ_ROWS;
+  const int k0 = blockIdx.x * RB_COLS, m0 = blockIdx.y * RB_ROWS;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int ch = tid + 256 * i, r = ch >> 3, c = ch & 7;
@@ -910,7 +867,7 @@ __global__ __launch_bounds__(256) void quant_rows_cols_mx_kernel(const T* __rest
       }
     }
 #pragma unroll
-    for (int p = 0; p < P; ++p) *reinterpret_cast<u32x4*>(smem + ((size_t)r * DQ_COLS + 16 * c) * sizeof(T) + 16 * p) = raw[p];
+    for (int p = 0; p < P; ++p) *reinterpret_cast<u32x4*>(smem + ((size_t)r * RB_COLS + 16 * c) * sizeof(T) + 16 * p) = raw[p];
     if constexpr (ROWS_OUT) {
       float v[16];
       float am = 0.f;
@@ -933,52 +890,49 @@ __global__ __launch_bounds__(256) void quant_rows_cols_mx_kernel(const T* __rest
   double sum[2] = {0.0, 0.0};
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const int col = u * 64 + lane;
     float v[32];
-    float am = 0.f;
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      v[j] = ldf(in + (b * 32 + j) * DQ_COLS + col);
-      am = fmaxf(am, fabsf(v[j]));
-    }
+    for (int j = 0; j < 32; ++j) v[j] = ldf(in + (b * 32 + j) * RB_COLS + u * 64 + lane);
     if (colsum) {
 #pragma unroll
       for (int j = 0; j < 32; ++j) sum[u] += (double)v[j];
     }
-    Eb[u] = mx_block_exp(am);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) pk[u][i] = pack4_e4m3_mx(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], Eb[u]);
+    Eb[u] = mx_pack_block32(v, pk[u]);
   }
   __syncthreads();                                         // every wave has read the input image: the output images take its place
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const int col = u * 64 + lane;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) tile[col * DQ_PITCH + b * 8 + i] = pk[u][i];
-    reinterpret_cast<uint8_t*>(sbytes)[col * 4 + b] = (uint8_t)(Eb[u] + 127);
-    if (colsum) ssum[b * DQ_COLS + col] = sum[u];
+    place_block32(tile, sbytes, u * 64 + lane, b, pk[u], Eb[u]);
+    if (colsum) ssum[b * RB_COLS + u * 64 + lane] = sum[u];
   }
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {                            // 128 columns x 8 pieces of 16 bytes
-    const int pc = tid + 256 * i, col = pc >> 3, piece = pc & 7;
-    if (k0 + col < N) {
-      const uint32_t* t = tile + col * DQ_PITCH + piece * 4;
-      *reinterpret_cast<uint4*>(col_q + (size_t)(k0 + col) * Mp + m0 + piece * 16) = make_uint4(t[0], t[1], t[2], t[3]);
-    }
-  }
-  if (tid < DQ_COLS && k0 + tid < N) {
-    reinterpret_cast<uint32_t*>(col_s + (size_t)(k0 + tid) * (Mp >> 5))[m0 >> 7] = sbytes[tid];   // the tile's four blocks of the column: one aligned dword
-    if (colsum) atomicAdd(colsum + k0 + tid, (float)(ssum[tid] + ssum[DQ_COLS + tid] + ssum[2 * DQ_COLS + tid] + ssum[3 * DQ_COLS + tid]));
-  }
+  store_cols_tile<RB_COLS>(tile, sbytes, ssum, k0, N, m0, Mp, col_q, col_s, colsum);
 }
 
-static std::atomic<long long> linear_fp8_launches{0};
-static std::atomic<long long> quant_rows_cols_mx_launches{0};
-static std::atomic<long long> linear_mxfp8_bwd_launches[2], quant_cols_mx_launches{0};   // MX data gradient, MX weight gradient; the MX column quantiser
-static std::atomic<long long> mx_rows_to_cols_launches{0};
-static std::atomic<long long> linear_mxfp8_launches{0}, quant_rows_mx_launches{0};
-static std::atomic<long long> linear_fp8_bwd_launches[2];   // data gradient, weight gradient
+// ---- host ------------------------------------------------------------------------------------------------------------------------------------------
+static std::atomic<long long> linear_fp8_launches{0}, linear_mxfp8_launches{0};
+static std::atomic<long long> linear_fp8_bwd_launches[2], linear_mxfp8_bwd_launches[2];   // data gradient, weight gradient
+static std::atomic<long long> quant_rows_mx_launches{0}, quant_cols_mx_launches{0}, mx_rows_to_cols_launches{0}, quant_rows_cols_mx_launches{0};
+
+// a clean launch moves the entry point's counter (null: the entry point has none)
+static int finish_launch(const char* fn, std::atomic<long long>* counter) {
+  const int rc = check_launch(fn);
+  if (rc == SV_OK && counter) counter->fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+// the epilogue forms the forward kernel serves; `why` receives the reason of a refusal
+static bool linear_fp8_epilogue_ok(const sv_epilogue* e, int N, const char** why) {
+  *why = nullptr;
+  if (!e) *why = "null epilogue";
+  else if (e->stats) *why = "per-channel statistics (stats) are not served";
+  else if (e->act_grad_src) *why = "an activation-gradient source (act_grad_src) is not served";
+  else if (e->act != SV_ACT_NONE && e->act != SV_ACT_GELU) *why = "only SV_ACT_NONE and SV_ACT_GELU are served";
+  else if (e->col_off != 0) *why = "col_off must be 0";
+  else if (e->ldc < N) *why = "ldc < N";
+  else if (e->residual && e->ldr < N) *why = "ldr < N";
+  return *why == nullptr;
+}
 
 // the epilogue forms the data-gradient kernel serves
 static bool linear_fp8_dgrad_epilogue_ok(const sv_epilogue* e, int K, const char** why) {
@@ -995,216 +949,203 @@ static bool linear_fp8_dgrad_epilogue_ok(const sv_epilogue* e, int K, const char
   return *why == nullptr;
 }
 
-// the epilogue forms the kernel serves; `why` receives the reason of a refusal
-static bool linear_fp8_epilogue_ok(const sv_epilogue* e, int N, const char** why) {
-  *why = nullptr;
-  if (!e) *why = "null epilogue";
-  else if (e->stats) *why = "per-channel statistics (stats) are not served";
-  else if (e->act_grad_src) *why = "an activation-gradient source (act_grad_src) is not served";
-  else if (e->act != SV_ACT_NONE && e->act != SV_ACT_GELU) *why = "only SV_ACT_NONE and SV_ACT_GELU are served";
-  else if (e->col_off != 0) *why = "col_off must be 0";
-  else if (e->ldc < N) *why = "ldc < N";
-  else if (e->residual && e->ldr < N) *why = "ldr < N";
-  return *why == nullptr;
+// What the quantiser entry points ask of their operands, in one place.  Every refusal names the entry point (fn) and the operands as its
+// signature does; the alignment of the outputs is asked by each entry point under its own pointer names.
+struct QuantSrc { const char* fn; const void* src; int dtype; const char* rn; int rows; const char* cn; int cols; int ld; };
+static int require_quant_source(const QuantSrc& q) {       // a bf16 / fp32 source of rows x cols elements with row stride ld
+  SV_REQUIRE(q.dtype == SV_F32 || q.dtype == SV_BF16, "%s: bad source dtype %d", q.fn, q.dtype);
+  SV_REQUIRE(q.rows > 0 && q.cols > 0 && q.ld >= q.cols, "%s: %s (%d) and %s (%d) must be positive, ld (%d) >= %s", q.fn, q.rn, q.rows, q.cn, q.cols, q.ld, q.cn);
+  return SV_OK;
+}
+static int require_padded(const char* fn, const char* pn, int P, const char* ln, int L) {   // the padded length of a quantised dimension
+  SV_REQUIRE(P == cdiv(L, 128) * 128, "%s: %s (%d) must be %s (%d) rounded up to a multiple of 128", fn, pn, P, ln, L);
+  return SV_OK;
+}
+static bool quant_src_aligned(const void* src, int dtype) { return ((uintptr_t)src & (dtype == SV_BF16 ? 1 : 3)) == 0; }
+
+// sv_linear_fp8 and sv_linear_mxfp8: the same checks, tile count and storage dispatch; what only the MX form has is asked under MX
+template <bool MX>
+static int launch_linear(const char* fn, std::atomic<long long>& counter, const void* xq, const void* xs, const void* wq, const void* ws, void* out, int M,
+                         int K, int N, const sv_epilogue* e, void* q_out, void* qs_out, int act_dtype, void* stream) {
+  SV_REQUIRE(xq && xs && wq && ws && e && (MX || out), "%s: null argument", fn);
+  if constexpr (MX) {
+    SV_REQUIRE(out || q_out, "%s: out may be null only when q_out is given", fn);
+    SV_REQUIRE((q_out != nullptr) == (qs_out != nullptr), "%s: q_out and qs_out go together", fn);
+  }
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE(M > 0 && K > 0 && N > 0, "%s: M (%d), K (%d), N (%d) must be positive", fn, M, K, N);
+  const char* why;
+  SV_REQUIRE(linear_fp8_epilogue_ok(e, N, &why), "%s: %s", fn, why);
+  if constexpr (MX) {
+    SV_REQUIRE(!q_out || (!e->residual && !e->row_scale), "%s: the emission of the output's MX rows is not served with a residual", fn);
+    SV_REQUIRE(!q_out || N % 128 == 0, "%s: the emission of the output's MX rows needs N (%d) %% 128 == 0", fn, N);
+    // pre_act exists for the derivative of the activation: without an activation it would be the unstored out under another name
+    SV_REQUIRE(out || !e->pre_act || e->act != SV_ACT_NONE, "%s: pre_act without out is served only in front of an activation", fn);
+  }
+  SV_REQUIRE((((uintptr_t)xq | (uintptr_t)wq | (uintptr_t)q_out) & 15) == 0, "%s: quantised operands must be 16-byte aligned", fn);
+  SV_REQUIRE(!MX || (((uintptr_t)xs | (uintptr_t)ws | (uintptr_t)qs_out) & 3) == 0, "%s: scale bytes must be 4-byte aligned", fn);
+  const uintptr_t amask = act_dtype == SV_BF16 ? 7 : 15;
+  SV_REQUIRE((((uintptr_t)out | (uintptr_t)e->residual | (uintptr_t)e->pre_act) & amask) == 0, "%s: out / residual / pre_act must be aligned to 4 elements", fn);
+  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(N, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "%s: too many tiles", fn);
+  const LinArgs<MX> a{static_cast<const uint8_t*>(xq), static_cast<const LfScale<MX>*>(xs), static_cast<const uint8_t*>(wq), static_cast<const LfScale<MX>*>(ws),
+                      out, M, N, cdiv(K, LF_BK) * LF_BK, e->bias, e->residual, e->ldr, e->row_scale, e->rows_per_scale > 0 ? e->rows_per_scale : 1,
+                      e->pre_act, e->act, e->slope, e->ldc, static_cast<uint8_t*>(q_out), static_cast<uint8_t*>(qs_out)};
+  SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL((linear_fp8_kernel<AT, sizeof(AT) == 2, MX>), dim3((unsigned)tiles), dim3(256), 0, static_cast<hipStream_t>(stream), a););
+  return finish_launch(fn, &counter);
+}
+
+// sv_linear_fp8_dgrad and sv_linear_mxfp8_dgrad
+template <bool MX>
+static int launch_dgrad(const char* fn, std::atomic<long long>& counter, const void* dq, const void* ds, const void* wtq, const void* wts, void* dx, int M,
+                        int N, int K, const sv_epilogue* e, int act_dtype, void* stream) {
+  SV_REQUIRE(dq && ds && wtq && wts && dx && e, "%s: null argument", fn);
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE(M > 0 && N > 0 && K > 0, "%s: M (%d), N (%d), K (%d) must be positive", fn, M, N, K);
+  const char* why;
+  SV_REQUIRE(linear_fp8_dgrad_epilogue_ok(e, K, &why), "%s: %s", fn, why);
+  SV_REQUIRE((((uintptr_t)dq | (uintptr_t)wtq) & 15) == 0, "%s: quantised operands must be 16-byte aligned", fn);
+  SV_REQUIRE(!MX || (((uintptr_t)ds | (uintptr_t)wts) & 3) == 0, "%s: scale bytes must be 4-byte aligned", fn);
+  const uintptr_t amask = act_dtype == SV_BF16 ? 1 : 3;
+  SV_REQUIRE((((uintptr_t)dx | (uintptr_t)e->act_grad_src) & amask) == 0, "%s: dx / act_grad_src are not aligned to their element", fn);
+  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(K, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "%s: too many tiles", fn);
+  const DgradArgs<MX> a{static_cast<const uint8_t*>(dq), static_cast<const LfScale<MX>*>(ds), static_cast<const uint8_t*>(wtq),
+                        static_cast<const LfScale<MX>*>(wts), dx, M, K, cdiv(N, LF_BK) * LF_BK, e->act_grad_src, e->act_grad_kind, e->slope, e->ldc};
+  SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL((linear_fp8_dgrad_kernel<AT, sizeof(AT) == 2, MX>), dim3((unsigned)tiles), dim3(256), 0, static_cast<hipStream_t>(stream), a););
+  return finish_launch(fn, &counter);
+}
+
+// the number of splits a weight-gradient call resolves to, under either recipe: the request (0 = two workgroups for each of 256 CUs), at most one
+// per 128 tokens and the grid's y limit
+static int linear_wgrad_splits(int M, int N, int K, int splits) {
+  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
+  const int nk = cdiv(M, LF_BK);
+  if (splits == 0) splits = (int)((2 * 256 + tiles - 1) / tiles);
+  splits = splits < nk ? splits : nk;
+  return splits > 65535 ? 65535 : splits;
+}
+
+// sv_linear_fp8_wgrad and sv_linear_mxfp8_wgrad; the workspace and the reduce launch are the MX form's
+template <bool MX>
+static int launch_wgrad(const char* fn, std::atomic<long long>& counter, const void* dyt, const void* dys, const void* xt, const void* xs, float* dw, int M, int N,
+                        int K, int ldw, int splits, float* workspace, void* stream) {
+  SV_REQUIRE(dyt && dys && xt && xs && dw, "%s: null argument", fn);
+  SV_REQUIRE(M > 0 && N > 0 && K > 0 && ldw >= K, "%s: M (%d), N (%d), K (%d) must be positive, ldw (%d) >= K", fn, M, N, K, ldw);
+  SV_REQUIRE(splits >= 0, "%s: splits (%d) must be >= 0", fn, splits);
+  SV_REQUIRE((((uintptr_t)dyt | (uintptr_t)xt) & 15) == 0 && (((MX ? (uintptr_t)dys | (uintptr_t)xs : 0) | (uintptr_t)dw) & 3) == 0, "%s: operands are not aligned", fn);
+  if constexpr (MX) SV_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", fn);
+  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
+  SV_REQUIRE(tiles < (1ll << 31), "%s: too many tiles", fn);
+  splits = linear_wgrad_splits(M, N, K, splits);
+  if constexpr (MX) SV_REQUIRE(splits == 1 || workspace, "%s: %d splits need a workspace of sv_linear_mxfp8_wgrad_workspace_floats floats", fn, splits);
+  const WgradArgs<MX> a{static_cast<const uint8_t*>(dyt), static_cast<const LfScale<MX>*>(dys), static_cast<const uint8_t*>(xt),
+                        static_cast<const LfScale<MX>*>(xs), dw, workspace, N, K, cdiv(M, LF_BK) * LF_BK, ldw, splits};
+  int vec = 0;                                             // MX: the reduce kernel's 16-byte form and its work items
+  size_t items = 0;
+  if constexpr (MX) {
+    vec = ((K | ldw) & 3) == 0 && ((uintptr_t)dw & 15) == 0;
+    items = vec ? (size_t)N * (K >> 2) : (size_t)N * K;
+    SV_REQUIRE(items / 256 + 1 < (1ull << 31), "%s: dw is too large", fn);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(linear_fp8_wgrad_kernel<MX>, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, s, a);
+  if constexpr (MX) {
+    if (splits > 1) hipLaunchKernelGGL(linear_mxfp8_wgrad_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, workspace, dw, N, K, ldw, splits, vec);
+  }
+  return finish_launch(fn, &counter);
 }
 
 }  // namespace sv
 
 using namespace sv;
 
-extern "C" int sv_quant_rows_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, float* scales, void* stream) {
-  SV_REQUIRE(src && dst_q && scales, "sv_quant_rows_e4m3: null argument");
-  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_rows_e4m3: bad source dtype %d", src_dtype);
-  SV_REQUIRE(rows > 0 && K > 0 && ld >= K, "sv_quant_rows_e4m3: rows (%d) and K (%d) must be positive, ld (%d) >= K", rows, K, ld);
-  SV_REQUIRE(Kp >= K && Kp % 128 == 0, "sv_quant_rows_e4m3: Kp (%d) must be a multiple of 128 and >= K (%d)", Kp, K);
-  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0, "sv_quant_rows_e4m3: dst_q must be 16-byte aligned");
-  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0, "sv_quant_rows_e4m3: src is not aligned to its element");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(cdiv(rows, 4));
-  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_rows_kernel<__bf16>, grid, dim3(256), 0, s, static_cast<const __bf16*>(src), rows, K, (long long)ld, static_cast<uint8_t*>(dst_q), Kp, scales);
-  else hipLaunchKernelGGL(quant_rows_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(src), rows, K, (long long)ld, static_cast<uint8_t*>(dst_q), Kp, scales);
-  return check_launch("sv_quant_rows_e4m3");
+// ---- counters and capability queries -------------------------------------------------------------------------------------------------------------
+extern "C" long long sv_linear_fp8_launches(void) { return linear_fp8_launches.load(std::memory_order_relaxed); }
+extern "C" long long sv_linear_mxfp8_launches(void) { return linear_mxfp8_launches.load(std::memory_order_relaxed); }
+extern "C" long long sv_quant_rows_mx_launches(void) { return quant_rows_mx_launches.load(std::memory_order_relaxed); }
+extern "C" long long sv_quant_cols_mx_launches(void) { return quant_cols_mx_launches.load(std::memory_order_relaxed); }
+extern "C" long long sv_mx_rows_to_cols_launches(void) { return mx_rows_to_cols_launches.load(std::memory_order_relaxed); }
+extern "C" long long sv_quant_rows_cols_mx_launches(void) { return quant_rows_cols_mx_launches.load(std::memory_order_relaxed); }
+extern "C" long long sv_linear_fp8_bwd_launches(int which) {
+  return (which == 0 || which == 1) ? linear_fp8_bwd_launches[which].load(std::memory_order_relaxed) : -1;
+}
+extern "C" long long sv_linear_mxfp8_bwd_launches(int which) {
+  return (which == 0 || which == 1) ? linear_mxfp8_bwd_launches[which].load(std::memory_order_relaxed) : -1;
 }
 
 extern "C" int sv_linear_fp8_supported(int K, int N, const sv_epilogue* e, int math, int act_dtype) {
   const char* why;
   return (K > 0 && N > 0 && math == SV_MATH_BF16 && (act_dtype == SV_F32 || act_dtype == SV_BF16) && linear_fp8_epilogue_ok(e, N, &why)) ? 1 : 0;
 }
-
-extern "C" long long sv_linear_fp8_launches(void) { return linear_fp8_launches.load(std::memory_order_relaxed); }
-
-extern "C" int sv_linear_fp8(const void* xq, const float* sx, const void* wq, const float* sw, void* out, int M, int K, int N, const sv_epilogue* e,
-                             int act_dtype, void* stream) {
-  SV_REQUIRE(xq && sx && wq && sw && out && e, "sv_linear_fp8: null argument");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(M > 0 && K > 0 && N > 0, "sv_linear_fp8: M (%d), K (%d), N (%d) must be positive", M, K, N);
-  const char* why;
-  SV_REQUIRE(linear_fp8_epilogue_ok(e, N, &why), "sv_linear_fp8: %s", why);
-  SV_REQUIRE((((uintptr_t)xq | (uintptr_t)wq) & 15) == 0, "sv_linear_fp8: quantised operands must be 16-byte aligned");
-  const uintptr_t amask = act_dtype == SV_BF16 ? 7 : 15;
-  SV_REQUIRE((((uintptr_t)out | (uintptr_t)e->residual | (uintptr_t)e->pre_act) & amask) == 0, "sv_linear_fp8: out / residual / pre_act must be aligned to 4 elements");
-  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(N, LF_BN);
-  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_fp8: too many tiles");
-  LinFp8Args a{static_cast<const uint8_t*>(xq), sx, static_cast<const uint8_t*>(wq), sw, out, M, N, cdiv(K, LF_BK) * LF_BK,
-               e->bias, e->residual, e->ldr, e->row_scale, e->rows_per_scale > 0 ? e->rows_per_scale : 1, e->pre_act, e->act, e->slope, e->ldc};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)tiles), block(256);
-  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_kernel<__bf16, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((linear_fp8_kernel<float, false>), grid, block, 0, s, a);
-  const int rc = check_launch("sv_linear_fp8");
-  if (rc == SV_OK) linear_fp8_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
-}
-
-extern "C" long long sv_linear_mxfp8_launches(void) { return linear_mxfp8_launches.load(std::memory_order_relaxed); }
-extern "C" long long sv_quant_rows_mx_launches(void) { return quant_rows_mx_launches.load(std::memory_order_relaxed); }
-
-extern "C" int sv_quant_rows_mx_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, void* scales_u8, void* stream) {
-  SV_REQUIRE(src && dst_q && scales_u8, "sv_quant_rows_mx_e4m3: null argument");
-  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_rows_mx_e4m3: bad source dtype %d", src_dtype);
-  SV_REQUIRE(rows > 0 && K > 0 && ld >= K, "sv_quant_rows_mx_e4m3: rows (%d) and K (%d) must be positive, ld (%d) >= K", rows, K, ld);
-  SV_REQUIRE(Kp == cdiv(K, 128) * 128, "sv_quant_rows_mx_e4m3: Kp (%d) must be K (%d) rounded up to a multiple of 128", Kp, K);
-  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0, "sv_quant_rows_mx_e4m3: dst_q must be 16-byte aligned, scales_u8 4-byte aligned");
-  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0, "sv_quant_rows_mx_e4m3: src is not aligned to its element");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(cdiv(rows, 4));
-  uint8_t* q = static_cast<uint8_t*>(dst_q);
-  uint8_t* sc = static_cast<uint8_t*>(scales_u8);
-  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_rows_mx_kernel<__bf16>, grid, dim3(256), 0, s, static_cast<const __bf16*>(src), rows, K, (long long)ld, q, Kp, sc);
-  else hipLaunchKernelGGL(quant_rows_mx_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(src), rows, K, (long long)ld, q, Kp, sc);
-  const int rc = check_launch("sv_quant_rows_mx_e4m3");
-  if (rc == SV_OK) quant_rows_mx_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
-}
-
-extern "C" int sv_linear_mxfp8(const void* xq, const void* xs, const void* wq, const void* ws, void* out, int M, int K, int N, const sv_epilogue* e,
-                               void* q_out, void* qs_out, int act_dtype, void* stream) {
-  SV_REQUIRE(xq && xs && wq && ws && e, "sv_linear_mxfp8: null argument");
-  SV_REQUIRE(out || q_out, "sv_linear_mxfp8: out may be null only when q_out is given");
-  SV_REQUIRE((q_out != nullptr) == (qs_out != nullptr), "sv_linear_mxfp8: q_out and qs_out go together");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(M > 0 && K > 0 && N > 0, "sv_linear_mxfp8: M (%d), K (%d), N (%d) must be positive", M, K, N);
-  const char* why;
-  SV_REQUIRE(linear_fp8_epilogue_ok(e, N, &why), "sv_linear_mxfp8: %s", why);
-  SV_REQUIRE(!q_out || (!e->residual && !e->row_scale), "sv_linear_mxfp8: the emission of the output's MX rows is not served with a residual");
-  SV_REQUIRE(!q_out || N % 128 == 0, "sv_linear_mxfp8: the emission of the output's MX rows needs N (%d) %% 128 == 0", N);
-  // pre_act exists for the derivative of the activation: without an activation it would be the unstored out under another name
-  SV_REQUIRE(out || !e->pre_act || e->act != SV_ACT_NONE, "sv_linear_mxfp8: pre_act without out is served only in front of an activation");
-  SV_REQUIRE((((uintptr_t)xq | (uintptr_t)wq | (uintptr_t)q_out) & 15) == 0, "sv_linear_mxfp8: quantised operands must be 16-byte aligned");
-  SV_REQUIRE((((uintptr_t)xs | (uintptr_t)ws | (uintptr_t)qs_out) & 3) == 0, "sv_linear_mxfp8: scale bytes must be 4-byte aligned");
-  const uintptr_t amask = act_dtype == SV_BF16 ? 7 : 15;
-  SV_REQUIRE((((uintptr_t)out | (uintptr_t)e->residual | (uintptr_t)e->pre_act) & amask) == 0, "sv_linear_mxfp8: out / residual / pre_act must be aligned to 4 elements");
-  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(N, LF_BN);
-  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_mxfp8: too many tiles");
-  LinMxArgs a{static_cast<const uint8_t*>(xq), static_cast<const uint8_t*>(xs), static_cast<const uint8_t*>(wq), static_cast<const uint8_t*>(ws), out,
-              M, N, cdiv(K, LF_BK) * LF_BK, e->bias, e->residual, e->ldr, e->row_scale, e->rows_per_scale > 0 ? e->rows_per_scale : 1, e->pre_act,
-              e->act, e->slope, e->ldc, static_cast<uint8_t*>(q_out), static_cast<uint8_t*>(qs_out)};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)tiles), block(256);
-  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_kernel<__bf16, true, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((linear_fp8_kernel<float, false, true>), grid, block, 0, s, a);
-  const int rc = check_launch("sv_linear_mxfp8");
-  if (rc == SV_OK) linear_mxfp8_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
-}
-
-extern "C" int sv_quant_cols_e4m3(const void* src, int src_dtype, int M, int C, int ld, void* dst_q, int Mp, float* scales, float* colsum, void* stream) {
-  SV_REQUIRE(src && dst_q && scales, "sv_quant_cols_e4m3: null argument");
-  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_cols_e4m3: bad source dtype %d", src_dtype);
-  SV_REQUIRE(M > 0 && C > 0 && ld >= C, "sv_quant_cols_e4m3: M (%d) and C (%d) must be positive, ld (%d) >= C", M, C, ld);
-  SV_REQUIRE(Mp >= M && Mp % 128 == 0 && Mp - M < 128, "sv_quant_cols_e4m3: Mp (%d) must be M (%d) rounded up to a multiple of 128", Mp, M);
-  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0, "sv_quant_cols_e4m3: dst_q must be 16-byte aligned");
-  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0, "sv_quant_cols_e4m3: src is not aligned to its element");
-  SV_REQUIRE(cdiv(M, QC_ROWS2) <= 65535, "sv_quant_cols_e4m3: M (%d) is too large", M);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scales, 0, sizeof(float) * (size_t)C, s) != hipSuccess) return check_launch("sv_quant_cols_e4m3 (clear)");
-  const dim3 g1(cdiv(C, QC_COLS), cdiv(M, QC_ROWS1)), g2(cdiv(C, QC_COLS), Mp / QC_ROWS2);
-  uint8_t* dst = static_cast<uint8_t*>(dst_q);
-  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_cols_amax_kernel<__bf16>, g1, dim3(256), 0, s, static_cast<const __bf16*>(src), M, C, (long long)ld, reinterpret_cast<int*>(scales), colsum);
-  else hipLaunchKernelGGL(quant_cols_amax_kernel<float>, g1, dim3(256), 0, s, static_cast<const float*>(src), M, C, (long long)ld, reinterpret_cast<int*>(scales), colsum);
-  hipLaunchKernelGGL(quant_cols_scale_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, scales, C);
-  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_cols_write_kernel<__bf16>, g2, dim3(256), 0, s, static_cast<const __bf16*>(src), M, C, (long long)ld, scales, dst, Mp);
-  else hipLaunchKernelGGL(quant_cols_write_kernel<float>, g2, dim3(256), 0, s, static_cast<const float*>(src), M, C, (long long)ld, scales, dst, Mp);
-  return check_launch("sv_quant_cols_e4m3");
-}
-
 extern "C" int sv_linear_fp8_dgrad_supported(int N, int K, const sv_epilogue* e, int math, int act_dtype) {
   const char* why;
   return (N > 0 && K > 0 && math == SV_MATH_BF16 && (act_dtype == SV_F32 || act_dtype == SV_BF16) && linear_fp8_dgrad_epilogue_ok(e, K, &why)) ? 1 : 0;
 }
-
-extern "C" long long sv_linear_fp8_bwd_launches(int which) {
-  return (which == 0 || which == 1) ? linear_fp8_bwd_launches[which].load(std::memory_order_relaxed) : -1;
+extern "C" size_t sv_linear_mxfp8_wgrad_workspace_floats(int M, int N, int K, int splits) {
+  if (M <= 0 || N <= 0 || K <= 0 || splits < 0) return 0;
+  const int sp = linear_wgrad_splits(M, N, K, splits);
+  return sp > 1 ? (size_t)sp * (size_t)N * (size_t)K : 0;
 }
 
-extern "C" int sv_linear_fp8_dgrad(const void* dq, const float* sd, const void* wtq, const float* swt, void* dx, int M, int N, int K, const sv_epilogue* e,
-                                   int act_dtype, void* stream) {
-  SV_REQUIRE(dq && sd && wtq && swt && dx && e, "sv_linear_fp8_dgrad: null argument");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(M > 0 && N > 0 && K > 0, "sv_linear_fp8_dgrad: M (%d), N (%d), K (%d) must be positive", M, N, K);
-  const char* why;
-  SV_REQUIRE(linear_fp8_dgrad_epilogue_ok(e, K, &why), "sv_linear_fp8_dgrad: %s", why);
-  SV_REQUIRE((((uintptr_t)dq | (uintptr_t)wtq) & 15) == 0, "sv_linear_fp8_dgrad: quantised operands must be 16-byte aligned");
-  const uintptr_t amask = act_dtype == SV_BF16 ? 1 : 3;
-  SV_REQUIRE((((uintptr_t)dx | (uintptr_t)e->act_grad_src) & amask) == 0, "sv_linear_fp8_dgrad: dx / act_grad_src are not aligned to their element");
-  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(K, LF_BN);
-  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_fp8_dgrad: too many tiles");
-  LinFp8DgradArgs a{static_cast<const uint8_t*>(dq), sd, static_cast<const uint8_t*>(wtq), swt, dx, M, K, cdiv(N, LF_BK) * LF_BK,
-                    e->act_grad_src, e->act_grad_kind, e->slope, e->ldc};
+// ---- quantisers ------------------------------------------------------------------------------------------------------------------------------------
+extern "C" int sv_quant_rows_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, float* scales, void* stream) {
+  const char* fn = "sv_quant_rows_e4m3";
+  SV_REQUIRE(src && dst_q && scales, "%s: null argument", fn);
+  if (const int rc = require_quant_source({fn, src, src_dtype, "rows", rows, "K", K, ld})) return rc;
+  SV_REQUIRE(Kp >= K && Kp % 128 == 0, "%s: Kp (%d) must be a multiple of 128 and >= K (%d)", fn, Kp, K);
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0, "%s: dst_q must be 16-byte aligned", fn);
+  SV_REQUIRE(quant_src_aligned(src, src_dtype), "%s: src is not aligned to its element", fn);
+  SV_DISPATCH_ACT(src_dtype, hipLaunchKernelGGL(quant_rows_kernel<AT>, dim3(cdiv(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                                                static_cast<const AT*>(src), rows, K, (long long)ld, static_cast<uint8_t*>(dst_q), Kp, scales););
+  return finish_launch(fn, nullptr);
+}
+
+extern "C" int sv_quant_rows_mx_e4m3(const void* src, int src_dtype, int rows, int K, int ld, void* dst_q, int Kp, void* scales_u8, void* stream) {
+  const char* fn = "sv_quant_rows_mx_e4m3";
+  SV_REQUIRE(src && dst_q && scales_u8, "%s: null argument", fn);
+  if (const int rc = require_quant_source({fn, src, src_dtype, "rows", rows, "K", K, ld})) return rc;
+  if (const int rc = require_padded(fn, "Kp", Kp, "K", K)) return rc;
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0, "%s: dst_q must be 16-byte aligned, scales_u8 4-byte aligned", fn);
+  SV_REQUIRE(quant_src_aligned(src, src_dtype), "%s: src is not aligned to its element", fn);
+  SV_DISPATCH_ACT(src_dtype, hipLaunchKernelGGL(quant_rows_mx_kernel<AT>, dim3(cdiv(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                                                static_cast<const AT*>(src), rows, K, (long long)ld, static_cast<uint8_t*>(dst_q), Kp,
+                                                static_cast<uint8_t*>(scales_u8)););
+  return finish_launch(fn, &quant_rows_mx_launches);
+}
+
+extern "C" int sv_quant_cols_e4m3(const void* src, int src_dtype, int M, int C, int ld, void* dst_q, int Mp, float* scales, float* colsum, void* stream) {
+  const char* fn = "sv_quant_cols_e4m3";
+  SV_REQUIRE(src && dst_q && scales, "%s: null argument", fn);
+  if (const int rc = require_quant_source({fn, src, src_dtype, "M", M, "C", C, ld})) return rc;
+  if (const int rc = require_padded(fn, "Mp", Mp, "M", M)) return rc;
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0, "%s: dst_q must be 16-byte aligned", fn);
+  SV_REQUIRE(quant_src_aligned(src, src_dtype), "%s: src is not aligned to its element", fn);
+  SV_REQUIRE(cdiv(M, QC_ROWS2) <= 65535, "%s: M (%d) is too large", fn, M);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)tiles), block(256);
-  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_dgrad_kernel<__bf16, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((linear_fp8_dgrad_kernel<float, false>), grid, block, 0, s, a);
-  const int rc = check_launch("sv_linear_fp8_dgrad");
-  if (rc == SV_OK) linear_fp8_bwd_launches[0].fetch_add(1, std::memory_order_relaxed);
-  return rc;
+  if (hipMemsetAsync(scales, 0, sizeof(float) * (size_t)C, s) != hipSuccess) return check_launch("sv_quant_cols_e4m3 (clear)");
+  const dim3 g1(cdiv(C, QC_COLS), cdiv(M, QC_ROWS1)), g2(cdiv(C, QC_COLS), Mp / QC_ROWS2);
+  SV_DISPATCH_ACT(src_dtype, hipLaunchKernelGGL(quant_cols_amax_kernel<AT>, g1, dim3(256), 0, s, static_cast<const AT*>(src), M, C, (long long)ld,
+                                                reinterpret_cast<int*>(scales), colsum););
+  hipLaunchKernelGGL(quant_cols_scale_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, scales, C);
+  SV_DISPATCH_ACT(src_dtype, hipLaunchKernelGGL(quant_cols_write_kernel<AT>, g2, dim3(256), 0, s, static_cast<const AT*>(src), M, C, (long long)ld, scales,
+                                                static_cast<uint8_t*>(dst_q), Mp););
+  return finish_launch(fn, nullptr);
 }
-
-extern "C" int sv_linear_fp8_wgrad(const void* dyt, const float* sdc, const void* xt, const float* sxc, float* dw, int M, int N, int K, int ldw, int splits,
-                                   void* stream) {
-  SV_REQUIRE(dyt && sdc && xt && sxc && dw, "sv_linear_fp8_wgrad: null argument");
-  SV_REQUIRE(M > 0 && N > 0 && K > 0 && ldw >= K, "sv_linear_fp8_wgrad: M (%d), N (%d), K (%d) must be positive, ldw (%d) >= K", M, N, K, ldw);
-  SV_REQUIRE(splits >= 0, "sv_linear_fp8_wgrad: splits (%d) must be >= 0", splits);
-  SV_REQUIRE((((uintptr_t)dyt | (uintptr_t)xt) & 15) == 0 && ((uintptr_t)dw & 3) == 0, "sv_linear_fp8_wgrad: operands are not aligned");
-  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
-  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_fp8_wgrad: too many tiles");
-  const int nk = cdiv(M, LF_BK);
-  if (splits == 0) splits = (int)((2 * 256 + tiles - 1) / tiles);   // two workgroups for each of the 256 CUs
-  splits = splits < nk ? splits : nk;
-  if (splits > 65535) splits = 65535;
-  LinFp8WgradArgs a{static_cast<const uint8_t*>(dyt), sdc, static_cast<const uint8_t*>(xt), sxc, dw, N, K, nk * LF_BK, ldw, splits};
-  hipLaunchKernelGGL(linear_fp8_wgrad_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  const int rc = check_launch("sv_linear_fp8_wgrad");
-  if (rc == SV_OK) linear_fp8_bwd_launches[1].fetch_add(1, std::memory_order_relaxed);
-  return rc;
-}
-
-// ---- MX backward --------------------------------------------------------------------------------------------------------------------------------
-extern "C" long long sv_linear_mxfp8_bwd_launches(int which) {
-  return (which == 0 || which == 1) ? linear_mxfp8_bwd_launches[which].load(std::memory_order_relaxed) : -1;
-}
-extern "C" long long sv_quant_cols_mx_launches(void) { return quant_cols_mx_launches.load(std::memory_order_relaxed); }
 
 extern "C" int sv_quant_cols_mx_e4m3(const void* src, int src_dtype, int M, int C, int ld, void* dst_q, int Mp, void* scales_u8, float* colsum, void* stream) {
-  SV_REQUIRE(src && dst_q && scales_u8, "sv_quant_cols_mx_e4m3: null argument");
-  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_cols_mx_e4m3: bad source dtype %d", src_dtype);
-  SV_REQUIRE(M > 0 && C > 0 && ld >= C, "sv_quant_cols_mx_e4m3: M (%d) and C (%d) must be positive, ld (%d) >= C", M, C, ld);
-  SV_REQUIRE(Mp >= M && Mp % 128 == 0 && Mp - M < 128, "sv_quant_cols_mx_e4m3: Mp (%d) must be M (%d) rounded up to a multiple of 128", Mp, M);
-  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0, "sv_quant_cols_mx_e4m3: dst_q must be 16-byte aligned, scales_u8 4-byte aligned");
-  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0 && ((uintptr_t)colsum & 3) == 0, "sv_quant_cols_mx_e4m3: src / colsum are not aligned to their element");
-  SV_REQUIRE(cdiv(M, QC_ROWS2) <= 65535, "sv_quant_cols_mx_e4m3: M (%d) is too large", M);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(cdiv(C, QC_COLS), Mp / QC_ROWS2);
-  uint8_t* q = static_cast<uint8_t*>(dst_q);
-  uint8_t* sc = static_cast<uint8_t*>(scales_u8);
-  if (src_dtype == SV_BF16) hipLaunchKernelGGL(quant_cols_mx_kernel<__bf16>, grid, dim3(256), 0, s, static_cast<const __bf16*>(src), M, C, (long long)ld, q, Mp, sc, colsum);
-  else hipLaunchKernelGGL(quant_cols_mx_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(src), M, C, (long long)ld, q, Mp, sc, colsum);
-  const int rc = check_launch("sv_quant_cols_mx_e4m3");
-  if (rc == SV_OK) quant_cols_mx_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
+  const char* fn = "sv_quant_cols_mx_e4m3";
+  SV_REQUIRE(src && dst_q && scales_u8, "%s: null argument", fn);
+  if (const int rc = require_quant_source({fn, src, src_dtype, "M", M, "C", C, ld})) return rc;
+  if (const int rc = require_padded(fn, "Mp", Mp, "M", M)) return rc;
+  SV_REQUIRE(((uintptr_t)dst_q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0, "%s: dst_q must be 16-byte aligned, scales_u8 4-byte aligned", fn);
+  SV_REQUIRE(quant_src_aligned(src, src_dtype) && ((uintptr_t)colsum & 3) == 0, "%s: src / colsum are not aligned to their element", fn);
+  SV_REQUIRE(cdiv(M, QC_ROWS2) <= 65535, "%s: M (%d) is too large", fn, M);
+  SV_DISPATCH_ACT(src_dtype, hipLaunchKernelGGL(quant_cols_mx_kernel<AT>, dim3(cdiv(C, QC_COLS), Mp / QC_ROWS2), dim3(256), 0, static_cast<hipStream_t>(stream),
+                                                static_cast<const AT*>(src), M, C, (long long)ld, static_cast<uint8_t*>(dst_q), Mp,
+                                                static_cast<uint8_t*>(scales_u8), colsum););
+  return finish_launch(fn, &quant_cols_mx_launches);
 }
-
-extern "C" long long sv_mx_rows_to_cols_launches(void) { return mx_rows_to_cols_launches.load(std::memory_order_relaxed); }
 
 extern "C" int sv_mx_rows_to_cols(const void* xq, int Kp, const void* xs, int M, int K, void* dst_q, int Mp, void* scales_u8, void* stream) {
   SV_REQUIRE(xq && xs && dst_q && scales_u8, "sv_mx_rows_to_cols: null argument");
@@ -1214,107 +1155,53 @@ extern "C" int sv_mx_rows_to_cols(const void* xq, int Kp, const void* xs, int M,
   SV_REQUIRE((((uintptr_t)xq | (uintptr_t)dst_q) & 15) == 0, "sv_mx_rows_to_cols: xq and dst_q must be 16-byte aligned");
   SV_REQUIRE((((uintptr_t)xs | (uintptr_t)scales_u8) & 3) == 0, "sv_mx_rows_to_cols: xs and scales_u8 must be 4-byte aligned");
   SV_REQUIRE(Mp / RB_ROWS <= 65535, "sv_mx_rows_to_cols: M (%d) is too large", M);
-  const dim3 grid(Kp / RB_COLS, Mp / RB_ROWS);
-  hipLaunchKernelGGL(mx_rows_to_cols_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const uint8_t*>(xq), Kp,
+  hipLaunchKernelGGL(mx_rows_to_cols_kernel, dim3(Kp / RB_COLS, Mp / RB_ROWS), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const uint8_t*>(xq), Kp,
                      static_cast<const uint8_t*>(xs), M, K, static_cast<uint8_t*>(dst_q), Mp, static_cast<uint8_t*>(scales_u8));
-  const int rc = check_launch("sv_mx_rows_to_cols");
-  if (rc == SV_OK) mx_rows_to_cols_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
-}
-
-extern "C" long long sv_quant_rows_cols_mx_launches(void) { return quant_rows_cols_mx_launches.load(std::memory_order_relaxed); }
-
-template <typename T>
-static void launch_quant_rows_cols_mx(dim3 grid, hipStream_t s, const void* src, int M, int N, int ld, uint8_t* rq, int Np, uint8_t* rs, uint8_t* cq, int Mp,
-                                      uint8_t* cs, float* colsum) {
-  if (rq) hipLaunchKernelGGL((quant_rows_cols_mx_kernel<T, true>), grid, dim3(256), 0, s, static_cast<const T*>(src), M, N, (long long)ld, rq, Np, rs, cq, Mp, cs, colsum);
-  else hipLaunchKernelGGL((quant_rows_cols_mx_kernel<T, false>), grid, dim3(256), 0, s, static_cast<const T*>(src), M, N, (long long)ld, rq, Np, rs, cq, Mp, cs, colsum);
+  return finish_launch("sv_mx_rows_to_cols", &mx_rows_to_cols_launches);
 }
 
 extern "C" int sv_quant_rows_cols_mx_e4m3(const void* src, int src_dtype, int M, int N, int ld, void* row_q, int Np, void* row_s, void* col_q, int Mp,
                                           void* col_s, float* colsum, void* stream) {
-  SV_REQUIRE(src && col_q && col_s, "sv_quant_rows_cols_mx_e4m3: null argument (src, col_q and col_s are required)");
-  SV_REQUIRE((row_q != nullptr) == (row_s != nullptr), "sv_quant_rows_cols_mx_e4m3: row_q and row_s go together");
-  SV_REQUIRE(src_dtype == SV_F32 || src_dtype == SV_BF16, "sv_quant_rows_cols_mx_e4m3: bad source dtype %d", src_dtype);
-  SV_REQUIRE(M > 0 && N > 0 && ld >= N, "sv_quant_rows_cols_mx_e4m3: M (%d) and N (%d) must be positive, ld (%d) >= N", M, N, ld);
-  SV_REQUIRE(Np == cdiv(N, 128) * 128, "sv_quant_rows_cols_mx_e4m3: Np (%d) must be N (%d) rounded up to a multiple of 128", Np, N);
-  SV_REQUIRE(Mp == cdiv(M, 128) * 128, "sv_quant_rows_cols_mx_e4m3: Mp (%d) must be M (%d) rounded up to a multiple of 128", Mp, M);
-  SV_REQUIRE((((uintptr_t)row_q | (uintptr_t)col_q) & 15) == 0, "sv_quant_rows_cols_mx_e4m3: row_q and col_q must be 16-byte aligned");
-  SV_REQUIRE((((uintptr_t)row_s | (uintptr_t)col_s) & 3) == 0, "sv_quant_rows_cols_mx_e4m3: row_s and col_s must be 4-byte aligned");
-  SV_REQUIRE(((uintptr_t)src & (src_dtype == SV_BF16 ? 1 : 3)) == 0 && ((uintptr_t)colsum & 3) == 0, "sv_quant_rows_cols_mx_e4m3: src / colsum are not aligned to their element");
-  SV_REQUIRE(Mp / DQ_ROWS <= 65535, "sv_quant_rows_cols_mx_e4m3: M (%d) is too large", M);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(Np / DQ_COLS, Mp / DQ_ROWS);
-  uint8_t *rq = static_cast<uint8_t*>(row_q), *rs = static_cast<uint8_t*>(row_s), *cq = static_cast<uint8_t*>(col_q), *cs = static_cast<uint8_t*>(col_s);
-  if (src_dtype == SV_BF16) launch_quant_rows_cols_mx<__bf16>(grid, s, src, M, N, ld, rq, Np, rs, cq, Mp, cs, colsum);
-  else launch_quant_rows_cols_mx<float>(grid, s, src, M, N, ld, rq, Np, rs, cq, Mp, cs, colsum);
-  const int rc = check_launch("sv_quant_rows_cols_mx_e4m3");
-  if (rc == SV_OK) quant_rows_cols_mx_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
+  const char* fn = "sv_quant_rows_cols_mx_e4m3";
+  SV_REQUIRE(src && col_q && col_s, "%s: null argument (src, col_q and col_s are required)", fn);
+  SV_REQUIRE((row_q != nullptr) == (row_s != nullptr), "%s: row_q and row_s go together", fn);
+  if (const int rc = require_quant_source({fn, src, src_dtype, "M", M, "N", N, ld})) return rc;
+  if (const int rc = require_padded(fn, "Np", Np, "N", N)) return rc;
+  if (const int rc = require_padded(fn, "Mp", Mp, "M", M)) return rc;
+  SV_REQUIRE((((uintptr_t)row_q | (uintptr_t)col_q) & 15) == 0, "%s: row_q and col_q must be 16-byte aligned", fn);
+  SV_REQUIRE((((uintptr_t)row_s | (uintptr_t)col_s) & 3) == 0, "%s: row_s and col_s must be 4-byte aligned", fn);
+  SV_REQUIRE(quant_src_aligned(src, src_dtype) && ((uintptr_t)colsum & 3) == 0, "%s: src / colsum are not aligned to their element", fn);
+  SV_REQUIRE(Mp / RB_ROWS <= 65535, "%s: M (%d) is too large", fn, M);
+  SV_DISPATCH_ACT(src_dtype, {
+    const auto kernel = row_q ? quant_rows_cols_mx_kernel<AT, true> : quant_rows_cols_mx_kernel<AT, false>;   // no rows asked for: the row work is compiled out
+    hipLaunchKernelGGL(kernel, dim3(Np / RB_COLS, Mp / RB_ROWS), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const AT*>(src), M, N, (long long)ld,
+                       static_cast<uint8_t*>(row_q), Np, static_cast<uint8_t*>(row_s), static_cast<uint8_t*>(col_q), Mp, static_cast<uint8_t*>(col_s), colsum);
+  });
+  return finish_launch(fn, &quant_rows_cols_mx_launches);
 }
 
+// ---- GEMMs -----------------------------------------------------------------------------------------------------------------------------------------
+extern "C" int sv_linear_fp8(const void* xq, const float* sx, const void* wq, const float* sw, void* out, int M, int K, int N, const sv_epilogue* e,
+                             int act_dtype, void* stream) {
+  return launch_linear<false>("sv_linear_fp8", linear_fp8_launches, xq, sx, wq, sw, out, M, K, N, e, nullptr, nullptr, act_dtype, stream);
+}
+extern "C" int sv_linear_mxfp8(const void* xq, const void* xs, const void* wq, const void* ws, void* out, int M, int K, int N, const sv_epilogue* e,
+                               void* q_out, void* qs_out, int act_dtype, void* stream) {
+  return launch_linear<true>("sv_linear_mxfp8", linear_mxfp8_launches, xq, xs, wq, ws, out, M, K, N, e, q_out, qs_out, act_dtype, stream);
+}
+extern "C" int sv_linear_fp8_dgrad(const void* dq, const float* sd, const void* wtq, const float* swt, void* dx, int M, int N, int K, const sv_epilogue* e,
+                                   int act_dtype, void* stream) {
+  return launch_dgrad<false>("sv_linear_fp8_dgrad", linear_fp8_bwd_launches[0], dq, sd, wtq, swt, dx, M, N, K, e, act_dtype, stream);
+}
 extern "C" int sv_linear_mxfp8_dgrad(const void* dq, const void* ds, const void* wtq, const void* wts, void* dx, int M, int N, int K, const sv_epilogue* e,
                                      int act_dtype, void* stream) {
-  SV_REQUIRE(dq && ds && wtq && wts && dx && e, "sv_linear_mxfp8_dgrad: null argument");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(M > 0 && N > 0 && K > 0, "sv_linear_mxfp8_dgrad: M (%d), N (%d), K (%d) must be positive", M, N, K);
-  const char* why;
-  SV_REQUIRE(linear_fp8_dgrad_epilogue_ok(e, K, &why), "sv_linear_mxfp8_dgrad: %s", why);
-  SV_REQUIRE((((uintptr_t)dq | (uintptr_t)wtq) & 15) == 0, "sv_linear_mxfp8_dgrad: quantised operands must be 16-byte aligned");
-  SV_REQUIRE((((uintptr_t)ds | (uintptr_t)wts) & 3) == 0, "sv_linear_mxfp8_dgrad: scale bytes must be 4-byte aligned");
-  const uintptr_t amask = act_dtype == SV_BF16 ? 1 : 3;
-  SV_REQUIRE((((uintptr_t)dx | (uintptr_t)e->act_grad_src) & amask) == 0, "sv_linear_mxfp8_dgrad: dx / act_grad_src are not aligned to their element");
-  const long long tiles = (long long)cdiv(M, LF_BM) * cdiv(K, LF_BN);
-  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_mxfp8_dgrad: too many tiles");
-  LinMxDgradArgs a{static_cast<const uint8_t*>(dq), static_cast<const uint8_t*>(ds), static_cast<const uint8_t*>(wtq), static_cast<const uint8_t*>(wts), dx,
-                   M, K, cdiv(N, LF_BK) * LF_BK, e->act_grad_src, e->act_grad_kind, e->slope, e->ldc};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)tiles), block(256);
-  if (act_dtype == SV_BF16) hipLaunchKernelGGL((linear_fp8_dgrad_kernel<__bf16, true, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((linear_fp8_dgrad_kernel<float, false, true>), grid, block, 0, s, a);
-  const int rc = check_launch("sv_linear_mxfp8_dgrad");
-  if (rc == SV_OK) linear_mxfp8_bwd_launches[0].fetch_add(1, std::memory_order_relaxed);
-  return rc;
+  return launch_dgrad<true>("sv_linear_mxfp8_dgrad", linear_mxfp8_bwd_launches[0], dq, ds, wtq, wts, dx, M, N, K, e, act_dtype, stream);
 }
-
-// the number of splits a call resolves to: the request (0 = two workgroups for each of 256 CUs), at most one per 128 tokens and the grid's y limit
-static int mxfp8_wgrad_splits(int M, int N, int K, int splits) {
-  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
-  const int nk = cdiv(M, LF_BK);
-  if (splits == 0) splits = (int)((2 * 256 + tiles - 1) / tiles);
-  splits = splits < nk ? splits : nk;
-  return splits > 65535 ? 65535 : splits;
+extern "C" int sv_linear_fp8_wgrad(const void* dyt, const float* sdc, const void* xt, const float* sxc, float* dw, int M, int N, int K, int ldw, int splits,
+                                   void* stream) {
+  return launch_wgrad<false>("sv_linear_fp8_wgrad", linear_fp8_bwd_launches[1], dyt, sdc, xt, sxc, dw, M, N, K, ldw, splits, nullptr, stream);
 }
-
-extern "C" size_t sv_linear_mxfp8_wgrad_workspace_floats(int M, int N, int K, int splits) {
-  if (M <= 0 || N <= 0 || K <= 0 || splits < 0) return 0;
-  const int sp = mxfp8_wgrad_splits(M, N, K, splits);
-  return sp > 1 ? (size_t)sp * (size_t)N * (size_t)K : 0;
-}
-
 extern "C" int sv_linear_mxfp8_wgrad(const void* dyt, const void* dys, const void* xt, const void* xs, float* dw, int M, int N, int K, int ldw, int splits,
                                      float* workspace, void* stream) {
-  SV_REQUIRE(dyt && dys && xt && xs && dw, "sv_linear_mxfp8_wgrad: null argument");
-  SV_REQUIRE(M > 0 && N > 0 && K > 0 && ldw >= K, "sv_linear_mxfp8_wgrad: M (%d), N (%d), K (%d) must be positive, ldw (%d) >= K", M, N, K, ldw);
-  SV_REQUIRE(splits >= 0, "sv_linear_mxfp8_wgrad: splits (%d) must be >= 0", splits);
-  SV_REQUIRE((((uintptr_t)dyt | (uintptr_t)xt) & 15) == 0 && (((uintptr_t)dys | (uintptr_t)xs | (uintptr_t)dw) & 3) == 0, "sv_linear_mxfp8_wgrad: operands are not aligned");
-  SV_REQUIRE(((uintptr_t)workspace & 15) == 0, "sv_linear_mxfp8_wgrad: workspace must be 16-byte aligned");
-  const long long tiles = (long long)cdiv(N, LF_BM) * cdiv(K, LF_BN);
-  SV_REQUIRE(tiles < (1ll << 31), "sv_linear_mxfp8_wgrad: too many tiles");
-  const int nk = cdiv(M, LF_BK);
-  splits = mxfp8_wgrad_splits(M, N, K, splits);
-  SV_REQUIRE(splits == 1 || workspace, "sv_linear_mxfp8_wgrad: %d splits need a workspace of sv_linear_mxfp8_wgrad_workspace_floats floats", splits);
-  LinMxWgradArgs a{static_cast<const uint8_t*>(dyt), static_cast<const uint8_t*>(dys), static_cast<const uint8_t*>(xt), static_cast<const uint8_t*>(xs), dw,
-                   workspace, N, K, nk * LF_BK, ldw, splits};
-  const int vec = ((K | ldw) & 3) == 0 && ((uintptr_t)dw & 15) == 0;   // the reduce kernel's 16-byte form
-  const size_t items = vec ? (size_t)N * (K >> 2) : (size_t)N * K;
-  SV_REQUIRE(items / 256 + 1 < (1ull << 31), "sv_linear_mxfp8_wgrad: dw is too large");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(linear_mxfp8_wgrad_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, s, a);
-  if (splits > 1) {
-    hipLaunchKernelGGL(linear_mxfp8_wgrad_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, workspace, dw, N, K, ldw, splits, vec);
-  }
-  const int rc = check_launch("sv_linear_mxfp8_wgrad");
-  if (rc == SV_OK) linear_mxfp8_bwd_launches[1].fetch_add(1, std::memory_order_relaxed);
-  return rc;
+  return launch_wgrad<true>("sv_linear_mxfp8_wgrad", linear_mxfp8_bwd_launches[1], dyt, dys, xt, xs, dw, M, N, K, ldw, splits, workspace, stream);
 }

@@ -70,6 +70,18 @@ def l1_rel(a, ref):
     return float((a.double() - ref.double()).abs().sum() / ref.double().abs().sum())
 
 
+def nan_padded(t, rows, ld, dev):
+    """t in the corner of a NaN-filled [rows, ld] buffer of its type on `dev` (the GPU tests' guard regions)"""
+    buf = torch.full((rows, ld), float("nan"), dtype=t.dtype, device=dev)
+    buf[: t.shape[0], : t.shape[1]] = t.to(dev)
+    return buf
+
+
+def raw_bytes(t):
+    """the bytes of a tensor, for bit comparisons across storage types"""
+    return t.contiguous().view(torch.uint8).cpu()
+
+
 def gauss_case(M, K, N, seed=0):
     g = torch.Generator().manual_seed(2000 + seed)
     return torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K)

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_cpu_linear_fp8_recipe import l1_rel, quantize_rows  # noqa: E402
+from test_cpu_linear_fp8_recipe import l1_rel, quantize_rows, raw_bytes  # noqa: E402
 from test_cpu_linear_fp8_bwd_recipe import emulate_dgrad, emulate_wgrad, gauss_bwd_case, integer_bwd_case  # noqa: E402
 
 import swinvox_amd as S  # noqa: E402
@@ -210,6 +210,36 @@ def test_recipe_dgrad(dev, shape, store, form):
     _dgrad(c["dy"].to(dev), c["W"].to(dev), out, M, K, N, **epi)
     torch.cuda.synchronize()
     _check(f"dgrad {shape} {store} {form}", out, ref, L1_BF16 if store == "bf16" else L1_F32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["none", "gelu"])
+@pytest.mark.parametrize("store", ["f32", "bf16"])
+def test_store_widths_agree(dev, store, form):
+    """The data gradient's two piece widths perform the same arithmetic per element: the same quantised operands with ldc = 40 (16-byte
+    pieces) and 41 (single elements) give the same bytes of dx [37, 40], and nothing else of the NaN-filled buffers is written.  No tolerance."""
+    M, K, N = 37, 40, 99
+    dy, _, W = gauss_bwd_case(M, K, N, seed=11)
+    hpre = (1.5 * torch.randn(M, K, generator=torch.Generator().manual_seed(80))).to(_dt(store))
+    dq, sd = _quant_rows(dy.to(_dt(store)).to(dev), M, N)
+    wtq, swt = _quant_cols(W.to(dev), N, K)
+    runs = []
+    for ld in (40, 41):
+        out = torch.full((M + 3, ld), float("nan"), dtype=_dt(store), device=dev)
+        epi = {}
+        if form == "gelu":
+            src = torch.full((M + 3, ld), float("nan"), dtype=_dt(store), device=dev)     # act_grad_src has the layout of the output
+            src[:M, :K] = hpre.to(dev)
+            epi = dict(act_grad_src=src, act_grad_kind=hip.ACT_GELU)
+        e = ops._epilogue(ld, **epi)
+        call("sv_linear_fp8_dgrad", ptr(dq), ptr(sd), ptr(wtq), ptr(swt), ptr(out), M, N, K, C.byref(e), act=_code(out))
+        torch.cuda.synchronize()
+        runs.append(out)
+    for ld, t in zip((40, 41), runs):
+        got, first = raw_bytes(t[:M, :K]), raw_bytes(runs[0][:M, :K])
+        assert bool(torch.isfinite(t[:M, :K].float()).all()), ld
+        assert torch.equal(got, first), (ld, int((got != first).sum()))
+        assert bool(torch.isnan(t[M:]).all()) and bool(torch.isnan(t[:, K:]).all()), ld
 
 
 @pytest.mark.gpu

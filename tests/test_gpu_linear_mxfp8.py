@@ -9,7 +9,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_cpu_linear_fp8_recipe import INT_SHAPES, RECIPE_SHAPES, gauss_case, l1_rel  # noqa: E402
+from test_cpu_linear_fp8_recipe import INT_SHAPES, RECIPE_SHAPES, gauss_case, l1_rel, nan_padded, raw_bytes  # noqa: E402
 from test_cpu_linear_mxfp8_recipe import emulate_linear_mx, mx_dequant, mx_integer_case, mx_quant_rows  # noqa: E402
 
 from swinvox_amd import hip, ops  # noqa: E402
@@ -154,6 +154,36 @@ def test_recipe(dev, shape, store, form):
     _check(f"{shape} {store} {form}", out, ref, store)
     if pre is not None:
         _check(f"{shape} {store} {form} pre_act", pre, ref_pre, store)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["gelu", "residual"])
+@pytest.mark.parametrize("store", ["f32", "bf16"])
+def test_store_widths_agree(dev, store, form):
+    """tests/test_gpu_linear_fp8.py's test of the same name on the MX kernel: ldc = ldr = 40 (16-byte pieces), 44 (4-element pieces under bf16
+    storage) and 41 (single elements) give the same bytes of out and pre_act, and nothing outside [:M, :N] is written.  No tolerance."""
+    M, K, N = 37, 99, 40
+    x, W = gauss_case(M, K, N, seed=11)
+    g = torch.Generator().manual_seed(79)
+    bias = (0.5 * torch.randn(N, generator=g)).to(dev)
+    res = torch.randn(M, N, generator=g).to(_dt(store))
+    rs = (0.5 + torch.rand((M + RPS - 1) // RPS, generator=g)).to(dev)
+    xq, xs = _quant(x.to(_dt(store)).to(dev), M, K)
+    wq, ws = _quant(W.to(dev), N, K)
+    runs = []
+    for ld in (40, 44, 41):
+        out = torch.full((M + 3, ld), float("nan"), dtype=_dt(store), device=dev)
+        pre = torch.full((M + 3, ld), float("nan"), dtype=_dt(store), device=dev) if form == "gelu" else None
+        epi = dict(bias=bias, act=hip.ACT_GELU, pre_act=pre) if form == "gelu" else \
+            dict(bias=bias, residual=nan_padded(res, M + 3, ld, dev), ldr=ld, row_scale=rs, rows_per_scale=RPS)
+        _mx_linear(xq, xs, wq, ws, out, M, K, N, store, ldc=ld, **epi)
+        torch.cuda.synchronize()
+        runs.append([t for t in (out, pre) if t is not None])
+    for ld, bufs in zip((40, 44, 41), runs):
+        for t, t0 in zip(bufs, runs[0]):
+            assert bool(torch.isfinite(t[:M, :N].float()).all()), ld
+            assert torch.equal(raw_bytes(t[:M, :N]), raw_bytes(t0[:M, :N])), (ld, int((raw_bytes(t[:M, :N]) != raw_bytes(t0[:M, :N])).sum()))
+            assert bool(torch.isnan(t[M:]).all()) and bool(torch.isnan(t[:, N:]).all()), ld
 
 
 @pytest.mark.gpu
