@@ -461,7 +461,8 @@ int sv_swin_mlp_wgrad(const void* x1, const void* dx2, const float* ln_g, const 
 /* MXFP8 forward of the fused Swin MLP branch (timm Mlp + norm2 + DropPath of a SwinTransformerBlock behind models/swin_transformer.py:78): the
  * unfused MX chain sv_layernorm_quant_mx_fwd -> sv_linear_mxfp8 (GELU, q_out) -> sv_linear_mxfp8 (residual) composed in ONE kernel, both products
  * on the block-scaled K = 128 MFMA with E8M0 scales per 32 channels / 32 hidden units; neither the hidden activation nor a quantised activation
- * reaches HBM.  bf16 token rows, C in {96, 128}.  The backward is sv_swin_mlp_bwd / sv_swin_mlp_wgrad, unchanged (straight-through quantisers).
+ * reaches HBM.  bf16 token rows, C in {96, 128}.  The backward is sv_swin_mlp_bwd / sv_swin_mlp_wgrad, unchanged (straight-through quantisers),
+ * unless the MX siblings below (sv_swin_mlp_bwd_mx, sv_swin_mlp_wgrad_mx) are asked for.
  *  sv_swin_mlp_mx_supported:  1 for C = 96 and C = 128, else 0 (timm Mlp behind models/swin_transformer.py:78).
  *  sv_swin_mlp_mx_pack_bytes: size of `packs` for C (0 when unsupported) (timm Mlp weights behind models/swin_transformer.py:78).
  *  sv_swin_mlp_mx_pack:       w1q [4C, 128] / w1s [4C, 4] and w2q [C, 4C] / w2s [C, 4C / 32], the MX rows sv_quant_rows_mx_e4m3 makes of fc1.weight and
@@ -484,7 +485,7 @@ long long sv_swin_mlp_mx_launches(void); /* timm Mlp + norm2 + DropPath behind m
  * models/swin_transformer.py:78): the unfused MX backward chain sv_rowscale -> sv_quant_rows_mx_e4m3 (dy) -> sv_linear_mxfp8_dgrad (fc2, GELU' at the
  * pre-activation) -> sv_quant_rows_mx_e4m3 (dh) -> sv_linear_mxfp8_dgrad (fc1) -> sv_layernorm_bwd (+ residual) composed in ONE kernel.  The
  * pre-activation is recomputed as sv_swin_mlp_fwd_mx computes it; dy's MX rows, the pre-activation and dh never reach HBM.  bf16 token rows.  The
- * weight gradients stay on sv_swin_mlp_wgrad.
+ * weight gradients are sv_swin_mlp_wgrad's (bf16 operands) or, on MX operands, sv_swin_mlp_wgrad_mx's below.
  *  sv_swin_mlp_bwd_mx_supported:  1 where the library has a spill-free instantiation (C = 96 and C = 128), else 0.
  *  sv_swin_mlp_bwd_mx_pack_bytes: size of `packs` for C (0 when unsupported).
  *  sv_swin_mlp_bwd_mx_pack:       w1q [4C, 128] / w1s [4C, 4] (sv_quant_rows_mx_e4m3 of fc1.weight), w2tq [4C, 128] / w2ts [4C, 4] and w1tq [C, 4C] /
@@ -503,6 +504,26 @@ int sv_swin_mlp_bwd_mx(const void* x1, const void* dx2, void* dx1, const float* 
                        const float* row_scale, int rows_per_scale, float* dgamma, float* dbeta, long long M, int C, float eps,
                        void* stream); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
 long long sv_swin_mlp_bwd_mx_launches(void); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+
+/* MXFP8 weight gradients of the fused Swin MLP branch (backward of timm Mlp + norm2 + DropPath of a SwinTransformerBlock behind
+ * models/swin_transformer.py:78): the unfused MX weight-gradient chain sv_layernorm_quant_mx_fwd -> sv_linear_mxfp8 (GELU, pre_act) -> sv_rowscale ->
+ * sv_quant_rows_mx_e4m3 (dy) -> sv_linear_mxfp8_dgrad (fc2, GELU' at the bf16 pre-activation) -> sv_quant_cols_mx_e4m3 x 4 (blocks of 32 tokens per
+ * column, counted from token 0; colsum = db2 / db1) -> sv_linear_mxfp8_wgrad x 2 composed in ONE kernel.  h and dh are recomputed as sv_swin_mlp_fwd_mx /
+ * sv_swin_mlp_bwd_mx compute them (K = C <= 128: one scaled MFMA per output tile, bit-identical operands); only the fp32 order of the sum over the
+ * tokens differs from the chain.  Nothing 4C wide and no quantised operand reaches HBM.  bf16 token rows.
+ *  sv_swin_mlp_wgrad_mx_supported: 1 where the library has a spill-free instantiation (C = 96 and C = 128), else 0.
+ *  sv_swin_mlp_wgrad_mx:           dw1 [4C, C], db1 [4C], dw2 [C, 4C], db2 [C] += weight gradients (fp32, native layouts, float atomics across token
+ *                                  splits only: one split, and bit-repeatable results, for M <= 128).  w1q [4C, 128] / w1s [4C, 4]: sv_quant_rows_mx_e4m3 of
+ *                                  fc1.weight; w2tq [4C, 128] / w2ts [4C, 4]: sv_quant_cols_mx_e4m3 of fc2.weight - the native images, no pack entry.
+ *  sv_swin_mlp_wgrad_mx_launches:  sv_swin_mlp_wgrad_mx launches so far in this process (tests: the path they mean to exercise).
+ * Refusals (SV_ERR_INVALID before any GPU call, the entry's name in sv_last_error()): null pointers (row_scale may be NULL), unsupported C, M <= 0 or
+ * >= 2^31, x1 / dx2 / w1q / w2tq not 16-byte aligned, w1s / w2ts not 4-byte aligned, rows_per_scale <= 0, row_scale with rows_per_scale < 128
+ * (the rule of sv_swin_mlp_wgrad).                                                                                                           */
+int sv_swin_mlp_wgrad_mx_supported(int C); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+int sv_swin_mlp_wgrad_mx(const void* x1, const void* dx2, const float* ln_g, const float* ln_b, const void* w1q, const void* w1s, const void* w2tq,
+                         const void* w2ts, const float* b1, const float* row_scale, int rows_per_scale, float* dw1, float* db1, float* dw2, float* db2,
+                         long long M, int C, float eps, void* stream); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
+long long sv_swin_mlp_wgrad_mx_launches(void); /* backward of timm Mlp + norm2 + DropPath behind models/swin_transformer.py:78 */
 
 /* Fused attention branch of a stage-0 Swin block (timm SwinTransformerBlock._attn + the residual of forward(), reached from
  * models/swin_transformer.py:78): x1 = x + row_scale * proj(window_attention(qkv(LayerNorm(x)))) in one kernel, the roll / 7x7 partition /

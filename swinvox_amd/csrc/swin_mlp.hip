@@ -19,7 +19,10 @@
 //   swin_mlp_fwd_mx_kernel  opt-in sibling of the forward (sv_swin_mlp_fwd_mx, C = 96, 128): both products on MXFP8 operands quantised in registers,
 //                         described in front of the kernel below.  The three kernels above are not touched by it.
 //   swin_mlp_bwd_mx_kernel  opt-in sibling of the data gradient (sv_swin_mlp_bwd_mx, C = 96, 128): differentiates that MX forward with all three of its
-//                         products on MXFP8 operands, described in front of the kernel below.  The weight gradients stay on swin_mlp_wgrad_kernel.
+//                         products on MXFP8 operands, described in front of the kernel below.
+//   swin_mlp_wgrad_mx_kernel  opt-in sibling of the weight gradients (sv_swin_mlp_wgrad_mx, C = 96, 128): the unfused MX weight-gradient chain of that
+//                         forward (recompute on MX rows, contraction over the tokens on MX columns), described in front of the kernel below.  Where
+//                         it is off or says no, the weight gradients stay on swin_mlp_wgrad_kernel.
 // bf16 storage + bf16 MFMA only (the exact-fp32 parity mode keeps the unfused chain); C = 96, 128, 192 (Swin-T stages 0-1, Swin-B stage 0).
 #include "common.h"
 #include <atomic>
@@ -1161,6 +1164,238 @@ __global__ __launch_bounds__(NW * 64, 1) void swin_mlp_bwd_mx_kernel(const MlpMx
 static inline bool mlp_bwd_mx_supported(int C) { return C == 96 || C == 128; }
 static inline long long mlp_bwd_mx_pack_bytes(int C) { return mlp_bwd_mx_supported(C) ? MlpMxB(C).PACK_BYTES : 0; }
 
+// ---- MXFP8 weight gradients (opt-in sibling of swin_mlp_wgrad_kernel; sv_swin_mlp_wgrad_mx) ---------------------------------------------
+// The unfused MX weight-gradient chain of the branch composed in one kernel: quantising LayerNorm -> fc1 on MX rows (hpre = bf16(acc + b1), h =
+// bf16(gelu_fast(acc + b1)) at the fp32 value) -> sv_rowscale -> row quantiser of dbr -> fc2's data gradient on MX rows, dh = bf16(acc *
+// gelu_grad_fast(hpre)) -> the four COLUMN quantisers (blocks of 32 consecutive tokens of one column, counted from token 0; rows past M are zero) ->
+// dW2[c][hid] += q_cols(dbr)[c] . q_cols(h)[hid], dW1[hid][c] += q_cols(dh)[hid] . q_cols(ln)[c] over the tokens; db2 / db1 are the fp32 column
+// sums of the unquantised dbr / dh.  Neither hpre, h, dh nor any quantised operand reaches HBM.  Same NORMATIVE recipe (linear_fp8.hip "MX
+// recipe").  K = C <= 128, so fc1 and fc2's data gradient are one scaled MFMA per output tile and hpre, h, dh are the chain's bit for bit; only the
+// fp32 order of the sum over token k-steps and token splits differs.  All four products on v_mfma_scale_f32_16x16x128_f8f6f4.
+//   skeleton      swin_mlp_wgrad_kernel's: a workgroup of 8 waves owns 128 hidden units (16 per wave) and walks a token range in 128-token tiles (tiles
+//                 and splits start at multiples of 128 tokens, so the kernel's 32-token blocks are the chain's); dW accumulators stay in registers over
+//                 the range, one float atomicAdd per element at the end (across token splits only).
+//   per tile      (1) wave w runs mx_layernorm on tokens 16 w .. + 15 (lane (t, lg), as the other two MX kernels), zeroes rows past the end, and
+//                 leaves in LDS: the MX row fragments of ln and dbr (mx_quant_frag; the [tile][2][64][16] + [tile][64] image mx_a_frag reads) and
+//                 the bf16 values themselves, LT / DT [128 tokens][C + 8] (16-byte stores).  (2) The 2 C / 16 column fragments (16 channels x 128
+//                 tokens of ln^T / dbr^T) are shared among the waves: lane (c, lg) takes tokens 64 hf + 16 lg .. + 15 of its channel out of LT / DT by
+//                 ds_read_b64_tr_b16 - with a row of the TRANSPOSED tensor on the lane the column quantiser IS mx_quant_frag - and the fragments go to
+//                 LDS once for all waves; workgroups of hidden group 0 add the column sums of DT to db2 (four threads per channel, combined in a fixed
+//                 order at the end).  (3) Each wave, for each 16-token tile T: acc1 = ln_q[T] . W1_q[wave's units], accd = dbr_q[T] . W2^T_q[wave's
+//                 units] (tokens on the accumulator rows: lane (u, lg) holds tokens 16 T + 4 lg + i of unit u; the W1 / W2^T rows are the lane's B
+//                 fragments, read once from the native [4C][128] images), h and dh as above, 8-byte stores into the wave's own [16 units][128 tokens]
+//                 bf16 images.  Read back as rows (lane (u, lg): tokens 64 hf + 16 lg .. + 15) they go through mx_quant_frag and are the B fragments
+//                 of the two contractions against the C / 16 column fragments of (2).
+//   LDS           row fragments 2 x 8 x (2048 + 64), column fragments 2 x C/16 x (2048 + 64), one region that holds LT | DT in (1)-(2) and the waves'
+//                 h / dh images in (3) (69 632 bytes), gamma / beta: 126.5 KB (C = 96) / 135 KB (C = 128).  Three workgroup barriers per tile.
+struct MlpMxWArgs {
+  const __bf16* x1; const __bf16* dx2;
+  const float* ln_g; const float* ln_b; float eps;
+  const uint8_t* w1q; const uint8_t* w1s;    // [4C][128], [4C][4]  sv_quant_rows_mx_e4m3 of fc1.weight
+  const uint8_t* w2tq; const uint8_t* w2ts;  // [4C][128], [4C][4]  sv_quant_cols_mx_e4m3 of fc2.weight
+  const float* b1; const float* row_scale; int rows_per_scale;
+  float* dw1; float* db1; float* dw2; float* db2;     // native layouts [4C][C], [4C], [C][4C], [C]
+  long long M; int tok_per_split; int HG;
+};
+
+constexpr int MXW_NW = 8, MXW_TT = 128;
+struct MlpMxW {                                            // LDS plan (bytes); LTS / HTS: row strides of the LT | DT tiles ([token][C + 8] bf16) and of a wave's h / dh image
+  int NJ, XF, DF, XS, DS, XTF, DTF, XTS, DTS, UN, LTS, HTS, UN_BYTES, PAR, LDS_BYTES;
+  constexpr explicit MlpMxW(int C)
+      : NJ(C / 16), XF(0), DF(XF + 8 * 2048), XS(DF + 8 * 2048), DS(XS + 8 * 64), XTF(DS + 8 * 64), DTF(XTF + NJ * 2048), XTS(DTF + NJ * 2048),
+        DTS(XTS + NJ * 64), UN(DTS + NJ * 64), LTS(2 * C + 16), HTS(2 * MXW_TT + 16),
+        UN_BYTES(2 * MXW_TT * LTS > MXW_NW * 2 * 16 * HTS ? 2 * MXW_TT * LTS : MXW_NW * 2 * 16 * HTS), PAR(UN + UN_BYTES), LDS_BYTES(PAR + 2 * C * 4) {}
+};
+
+// a fragment (tile `tile` of an image mx_a_frag reads) and its scale bytes into LDS
+__device__ __forceinline__ void mx_put_frag(uint8_t* data, uint8_t* scales, int tile, int lane, const i32x8& q, int sbyte) {
+  uint8_t* fa = data + (size_t)(tile * 2) * 1024 + lane * 16;
+  *reinterpret_cast<i32x4*>(fa) = (i32x4){q[0], q[1], q[2], q[3]};
+  *reinterpret_cast<i32x4*>(fa + 1024) = (i32x4){q[4], q[5], q[6], q[7]};
+  scales[tile * 64 + lane] = (uint8_t)sbyte;
+}
+
+template <int C>
+__global__ __launch_bounds__(MXW_NW * 64, 1) void swin_mlp_wgrad_mx_kernel(const MlpMxWArgs p) {
+  constexpr MlpMxW L(C);
+  constexpr int NW = MXW_NW, TT = MXW_TT, NT = NW * 64, HID = 4 * C, NJ = L.NJ;
+  static_assert(TT == NW * 16, "one 16-token tile per wave");
+  __shared__ __attribute__((aligned(16))) uint8_t smem[L.LDS_BYTES];
+  float* sgam = reinterpret_cast<float*>(smem + L.PAR);
+  float* sbet = sgam + C;
+  const int tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < C; i += NT) { sgam[i] = p.ln_g[i]; sbet[i] = p.ln_b[i]; }
+  const int hg = blockIdx.x % p.HG, split = blockIdx.x / p.HG;
+  const int hid = (hg * NW + wave) * 16 + (lane0 & 15);    // the lane's hidden unit in phase (3)
+  const long long t_begin = (long long)split * p.tok_per_split;
+  long long t_end = t_begin + p.tok_per_split;
+  if (t_end > p.M) t_end = p.M;
+
+  // per-wave constant B fragments: the MX rows of W1 / W2^T of the wave's hidden units (k = channels) and their block scales
+  i32x8 w1b, w2b;
+  {
+    const int lg = lane0 >> 4;
+    const i32x4 a0 = *reinterpret_cast<const i32x4*>(p.w1q + (size_t)hid * 128 + 16 * lg), a1 = *reinterpret_cast<const i32x4*>(p.w1q + (size_t)hid * 128 + 64 + 16 * lg);
+    const i32x4 c0 = *reinterpret_cast<const i32x4*>(p.w2tq + (size_t)hid * 128 + 16 * lg), c1 = *reinterpret_cast<const i32x4*>(p.w2tq + (size_t)hid * 128 + 64 + 16 * lg);
+    w1b = (i32x8){a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+    w2b = (i32x8){c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+  }
+  const int w1sb = p.w1s[hid * 4 + (lane0 >> 4)], w2sb = p.w2ts[hid * 4 + (lane0 >> 4)];
+  const float b1v = p.b1[hid];
+
+  f32x4 G2[NJ], G1[NJ];
+#pragma unroll
+  for (int jc = 0; jc < NJ; ++jc) { G2[jc] = (f32x4){0.f, 0.f, 0.f, 0.f}; G1[jc] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+  float db1acc = 0.f, db2acc = 0.f;
+
+  __bf16* const LT = reinterpret_cast<__bf16*>(smem + L.UN);                   // [128 tokens][LTS / 2]  ln of the tile, bf16 (C + 8 elements per row)
+  __bf16* const DT = reinterpret_cast<__bf16*>(smem + L.UN + TT * L.LTS);      // [128 tokens][LTS / 2]  dbr
+  uint8_t* const hth = smem + L.UN + wave * (2 * 16 * L.HTS);                  // [16][HTS] bytes  the wave's h image (aliases LT | DT)
+  uint8_t* const htd = hth + 16 * L.HTS;                                       //                  the wave's dh image
+
+#pragma unroll 1
+  for (long long t0 = t_begin; t0 < t_end; t0 += TT) {
+    __syncthreads();                                       // the previous tile's fragments and h / dh images have been consumed
+    // lane index laundered per tile: otherwise hipcc materialises the ~100 per-lane LDS addresses of the tile once, outside the token loop, and spills
+    // them around it; with an opaque lane they stay immediate offsets of the ds instructions (see swin_mlp_bwd_kernel)
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int t = lane & 15, lg = lane >> 4;
+    // ---- (1) LayerNorm and row scale of the wave's 16 tokens -> MX row fragments, bf16 values transposed
+    {
+      const int tl = 16 * wave + t;
+      const long long tok = t0 + tl;
+      const bool valid = tok < t_end;
+      const float sc = (valid && p.row_scale) ? p.row_scale[tok / p.rows_per_scale] : 1.f;
+      float xv[2][16], dv[2][16], mean, rstd;
+      mx_layernorm<C, true>(p.x1, tok, valid, lg, sgam, sbet, p.eps, xv, mean, rstd, p.dx2, sc, dv);
+      if (!valid) {                                        // rows past the end are zero in every operand (dv already is)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) xv[hf][j] = 0.f;
+      }
+      i32x8 q; int sb;
+      mx_quant_frag(xv, q, sb, lane);
+      mx_put_frag(smem + L.XF, smem + L.XS, wave, lane, q, sb);
+      mx_quant_frag(dv, q, sb, lane);
+      mx_put_frag(smem + L.DF, smem + L.DS, wave, lane, q, sb);
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        if (64 * hf + 16 * lg < C) {
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            bf16x8 xo, dd;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { xo[j] = (__bf16)xv[hf][8 * u + j]; dd[j] = (__bf16)dv[hf][8 * u + j]; }   // exact: bf16 values already
+            *reinterpret_cast<bf16x8*>(LT + tl * (L.LTS / 2) + 64 * hf + 16 * lg + 8 * u) = xo;
+            *reinterpret_cast<bf16x8*>(DT + tl * (L.LTS / 2) + 64 * hf + 16 * lg + 8 * u) = dd;
+          }
+        }
+    }
+    __syncthreads();
+    // ---- (2) column quantisers of ln and dbr: fragment f = (tensor, 16-channel tile), shared among the waves
+#pragma unroll 1
+    for (int f = wave; f < 2 * NJ; f += NW) {
+      const int which = f / NJ, jc = f % NJ;
+      // ds_read_b64_tr_b16: the 16 lanes of a group read a 4-token x 16-channel block (lane: token + (t >> 2), channels 4 (t & 3) .. + 3) and
+      // receive it transposed - lane t gets channel t of the block, its 4 tokens (as in swin_mlp_wgrad_kernel)
+      const __bf16* src = (which ? DT : LT) + (16 * lg + (t >> 2)) * (L.LTS / 2) + 16 * jc + 4 * (t & 3);
+      float v[2][16];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const bf16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(src + (64 * hf + 4 * u) * (L.LTS / 2)));
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[hf][4 * u + k] = (float)r[k];
+        }
+      i32x8 q; int sb;
+      mx_quant_frag(v, q, sb, lane);
+      mx_put_frag(smem + (which ? L.DTF : L.XTF), smem + (which ? L.DTS : L.XTS), jc, lane, q, sb);
+    }
+    if (hg == 0 && tid < 4 * C) {                          // bias gradient of fc2: column sums of the unquantised dbr, 32 tokens per thread
+      const __bf16* col = DT + (tid / C) * 32 * (L.LTS / 2) + tid % C;
+      float s = 0.f;
+#pragma unroll 8
+      for (int r = 0; r < 32; ++r) s += (float)col[r * (L.LTS / 2)];
+      db2acc += s;
+    }
+    __syncthreads();                                       // column fragments ready; LT / DT are dead, their space is the waves' h / dh images
+    // ---- (3) recompute h and dh of the wave's 16 hidden units, tokens on the accumulator rows
+#pragma unroll 2
+    for (int T = 0; T < 8; ++T) {
+      const i32x8 a = mx_a_frag(smem + L.XF, T, lane), d = mx_a_frag(smem + L.DF, T, lane);
+      const int sa = mx_a_scale(smem + L.XS, T, lane), sd = mx_a_scale(smem + L.DS, T, lane);
+      const f32x4 acc1 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, w1b, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, sa, 0, w1sb);
+      const f32x4 accd = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(d, w2b, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, sd, 0, w2sb);
+      const f32x2 p0 = (f32x2){acc1[0] + b1v, acc1[1] + b1v}, p1 = (f32x2){acc1[2] + b1v, acc1[3] + b1v};
+      const f32x2 g0 = gelu_fast2(p0), g1 = gelu_fast2(p1);                   // GELU at the fp32 value ...
+      const f32x2 e0 = gelu_grad_fast2((f32x2){(float)(__bf16)p0[0], (float)(__bf16)p0[1]});   // ... GELU' at the stored (bf16) pre-activation
+      const f32x2 e1 = gelu_grad_fast2((f32x2){(float)(__bf16)p1[0], (float)(__bf16)p1[1]});
+      const float hv[4] = {g0[0], g0[1], g1[0], g1[1]};
+      const float ev[4] = {e0[0], e0[1], e1[0], e1[1]};
+      const long long tk = t0 + 16 * T + 4 * lg;           // the lane's tokens tk .. tk + 3
+      bf16x4 hb, db;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        hb[i] = tk + i < t_end ? (__bf16)hv[i] : (__bf16)0.f;   // rows past the end: zero (acc1 = 0 there gives GELU(b1))
+        db[i] = (__bf16)(accd[i] * ev[i]);                      // accd = 0 there
+        db1acc += (float)db[i];
+      }
+      *reinterpret_cast<bf16x4*>(hth + t * L.HTS + (16 * T + 4 * lg) * 2) = hb;
+      *reinterpret_cast<bf16x4*>(htd + t * L.HTS + (16 * T + 4 * lg) * 2) = db;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's own stores have landed before its lanes read each other's
+    // ---- the token contractions: the wave's h / dh rows (column-quantised: blocks of 32 tokens) against the column fragments of dbr / ln
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+      const uint8_t* src = (which ? htd : hth) + t * L.HTS;
+      float v[2][16];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const bf16x8 r = *reinterpret_cast<const bf16x8*>(src + (64 * hf + 16 * lg + 8 * u) * 2);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) v[hf][8 * u + k] = (float)r[k];
+        }
+      i32x8 q; int sb;
+      mx_quant_frag(v, q, sb, lane);
+#pragma unroll
+      for (int jc = 0; jc < NJ; ++jc) {
+        if (which == 0)   // dW2[c][hid]: rows = channels 16 jc + 4 lg + i, column = the lane's hidden unit
+          G2[jc] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(mx_a_frag(smem + L.DTF, jc, lane), q, G2[jc], 0, 0, 0, mx_a_scale(smem + L.DTS, jc, lane), 0, sb);
+        else              // dW1[hid][c], held transposed
+          G1[jc] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(mx_a_frag(smem + L.XTF, jc, lane), q, G1[jc], 0, 0, 0, mx_a_scale(smem + L.XTS, jc, lane), 0, sb);
+      }
+    }
+  }
+  // ---- write out (accumulator: row = channel 16 jc + 4 lg + i, column = hidden unit `hid`)
+  const int lg = lane0 >> 4;
+#pragma unroll
+  for (int jc = 0; jc < NJ; ++jc)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = 16 * jc + 4 * lg + i;
+      atomicAdd(p.dw2 + (size_t)c * HID + hid, G2[jc][i]);
+      atomicAdd(p.dw1 + (size_t)hid * C + c, G1[jc][i]);
+    }
+  db1acc = lane_step_add<16>(db1acc);
+  db1acc = lane_step_add<32>(db1acc);
+  if (lg == 0) atomicAdd(p.db1 + hid, db1acc);
+  if (hg == 0) {                                           // the four partial sums of a channel in a fixed order, then one atomic
+    float* red = reinterpret_cast<float*>(smem);
+    __syncthreads();
+    if (tid < 4 * C) red[tid] = db2acc;
+    __syncthreads();
+    if (tid < C) atomicAdd(p.db2 + tid, (red[tid] + red[C + tid]) + (red[2 * C + tid] + red[3 * C + tid]));
+  }
+}
+
+// both widths are served while their instantiations are free of spills and scratch; the host keeps swin_mlp_wgrad_kernel where this says no
+static inline bool mlp_wgrad_mx_supported(int C) { return C == 96 || C == 128; }
+
 }  // namespace sv
 
 using namespace sv;
@@ -1325,4 +1560,37 @@ extern "C" int sv_swin_mlp_bwd_mx(const void* x1, const void* dx2, void* dx1, co
   a.row_scale = row_scale; a.rows_per_scale = rows_per_scale; a.dgamma = dgamma; a.dbeta = dbeta; a.M = M;
   return mlp_mx_launch("sv_swin_mlp_bwd_mx", swin_mlp_bwd_mx_kernel<96, MX_NW, MX_NTT>, swin_mlp_bwd_mx_kernel<128, MX_NW, MX_NTT>, C, a, STREAM,
                        swin_mlp_bwd_mx_launches);
+}
+
+// ---- MXFP8 weight gradients ---------------------------------------------------------------------------------------------------------
+static std::atomic<long long> swin_mlp_wgrad_mx_launches{0};
+extern "C" long long sv_swin_mlp_wgrad_mx_launches(void) { return swin_mlp_wgrad_mx_launches.load(std::memory_order_relaxed); }
+extern "C" int sv_swin_mlp_wgrad_mx_supported(int C) { return mlp_wgrad_mx_supported(C) ? 1 : 0; }
+
+extern "C" int sv_swin_mlp_wgrad_mx(const void* x1, const void* dx2, const float* ln_g, const float* ln_b, const void* w1q, const void* w1s, const void* w2tq,
+                                    const void* w2ts, const float* b1, const float* row_scale, int rows_per_scale, float* dw1, float* db1, float* dw2,
+                                    float* db2, long long M, int C, float eps, void* stream) {
+  const char* who = "sv_swin_mlp_wgrad_mx";
+  SV_REQUIRE(x1 && dx2 && ln_g && ln_b && w1q && w1s && w2tq && w2ts && b1 && dw1 && db1 && dw2 && db2, "%s: null pointer", who);
+  SV_REQUIRE(mlp_wgrad_mx_supported(C), "%s: unsupported C=%d", who, C);
+  SV_REQUIRE(M > 0 && M < (1ll << 31), "%s: M=%lld out of range", who, M);
+  SV_REQUIRE((((uintptr_t)x1 | (uintptr_t)dx2 | (uintptr_t)w1q | (uintptr_t)w2tq) & 15) == 0, "%s: x1, dx2, w1q and w2tq must be 16-byte aligned", who);
+  SV_REQUIRE((((uintptr_t)w1s | (uintptr_t)w2ts) & 3) == 0, "%s: w1s and w2ts must be 4-byte aligned", who);
+  SV_REQUIRE(rows_per_scale > 0, "%s: rows_per_scale must be positive", who);
+  SV_REQUIRE(!row_scale || rows_per_scale >= 128, "%s: rows_per_scale (%d) must be >= 128 with row_scale (the rule of sv_swin_mlp_wgrad)", who, rows_per_scale);
+  MlpMxWArgs a{};
+  a.x1 = static_cast<const __bf16*>(x1); a.dx2 = static_cast<const __bf16*>(dx2); a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps;
+  a.w1q = static_cast<const uint8_t*>(w1q); a.w1s = static_cast<const uint8_t*>(w1s); a.w2tq = static_cast<const uint8_t*>(w2tq); a.w2ts = static_cast<const uint8_t*>(w2ts);
+  a.b1 = b1; a.row_scale = row_scale; a.rows_per_scale = rows_per_scale; a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2; a.M = M;
+  // hidden groups x token splits as sv_swin_mlp_wgrad; splits start at multiples of the 128-token tile, so the 32-token blocks count from token 0
+  a.HG = (4 * C) / (MXW_NW * 16);
+  long long splits = 256 / a.HG;
+  long long tps = (M + splits - 1) / splits; tps = (tps + MXW_TT - 1) / MXW_TT * MXW_TT;
+  splits = (M + tps - 1) / tps;
+  a.tok_per_split = (int)tps;
+  if (C == 96) hipLaunchKernelGGL(swin_mlp_wgrad_mx_kernel<96>, dim3((unsigned)(splits * a.HG)), dim3(MXW_NW * 64), 0, STREAM, a);
+  else hipLaunchKernelGGL(swin_mlp_wgrad_mx_kernel<128>, dim3((unsigned)(splits * a.HG)), dim3(MXW_NW * 64), 0, STREAM, a);
+  const int rc = check_launch(who);
+  if (rc == SV_OK) swin_mlp_wgrad_mx_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
 }

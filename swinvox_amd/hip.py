@@ -155,6 +155,9 @@ _PROTOS = {
     "sv_swin_mlp_bwd_mx_pack": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "sv_swin_mlp_bwd_mx": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _I, _F]),
     "sv_swin_mlp_bwd_mx_launches": (_L, None),
+    "sv_swin_mlp_wgrad_mx_supported": (_I, None, [_I]),
+    "sv_swin_mlp_wgrad_mx": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _I, _F]),
+    "sv_swin_mlp_wgrad_mx_launches": (_L, None),
     "sv_swin_attn_block_supported": (_I, None, [_I, _I, _I, _I]),
     "sv_swin_attn_block_windows_per_group": (_I, None, [_I, _I, _I, _I]),
     "sv_swin_attn_block_fwd": (_I, [_P] * 15 + [_I, _I, _I, _I, _I, _I, _F]),

@@ -224,7 +224,7 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
         mx = ops.fused_mlp_mx_enabled(Cd)
         packs = None
         # the bf16 images: read by sv_swin_mlp_fwd and by the fused bf16 backward (the MX data gradient packs its own operands; the weight
-        # gradient reads pack_fwd / pack_dgrad)
+        # gradient reads pack_fwd / pack_dgrad, or the MX rows of the weights)
         if not mx or (save and not ops.fused_mlp_mx_bwd_enabled(Cd)):
             packs = torch.empty(16 * Cd * Cd, dtype=torch.bfloat16, device=x.device)
             call("sv_swin_mlp_pack", ptr(mlp.fc1.weight), ptr(mlp.fc2.weight), ptr(packs), Cd)
@@ -289,17 +289,24 @@ def _fused_mlp_backward(blk, t: BlockTape, dx2, grads):
                     else ("sv_swin_mlp_bwd", t.packs))
     ops.traced_call(name, 3 * unit, 6.0 * M * Cd, ptr(x1), ptr(dx2), ptr(dx1), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(images),
                     ptr(mlp.fc1.bias), ptr(sc2), HW, ptr(grads[blk.norm2.weight]), ptr(grads[blk.norm2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
-    w1r, w2tr = blk.s_fc1.pack_fwd(mlp.fc1.weight), blk.s_fc2.pack_dgrad(mlp.fc2.weight)     # bf16 [4C][C] rows both
+    # opt-in MXFP8 weight gradients (set_fused_mlp_mx(True, wgrad=True)): the unfused MX weight-gradient chain of the branch in one kernel, on the
+    # MX rows of fc1.weight and of fc2.weight^T (the bytes of the unfused sites and of the other two MX kernels); the bf16 rows are not built
+    if ops.fused_mlp_mx_wgrad_enabled(Cd):
+        name = "sv_swin_mlp_wgrad_mx"
+        operands = (*ops.quantize_weight_mx(mlp.fc1.weight), *ops.quantize_weight_t_mx(mlp.fc2.weight))
+    else:
+        name = "sv_swin_mlp_wgrad"
+        operands = (blk.s_fc1.pack_fwd(mlp.fc1.weight), blk.s_fc2.pack_dgrad(mlp.fc2.weight))     # bf16 [4C][C] rows both
 
     def launch():
-        ops.traced_call("sv_swin_mlp_wgrad", 4 * unit, 4.0 * M * Cd, ptr(x1), ptr(dx2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), ptr(w1r), ptr(w2tr),
+        ops.traced_call(name, 4 * unit, 4.0 * M * Cd, ptr(x1), ptr(dx2), ptr(blk.norm2.weight), ptr(blk.norm2.bias), *(ptr(o) for o in operands),
                         ptr(mlp.fc1.bias), ptr(sc2), HW, ptr(grads[mlp.fc1.weight]), ptr(grads[mlp.fc1.bias]),
                         ptr(grads[mlp.fc2.weight]), ptr(grads[mlp.fc2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
 
     aw = ops._CTX.awg
     if aw is not None:
         aw.stream.wait_stream(torch.cuda.current_stream())
-        aw.held.append((x1, dx2, w1r, w2tr))
+        aw.held.append((x1, dx2, *operands))
         with torch.cuda.stream(aw.stream):
             launch()
     else:

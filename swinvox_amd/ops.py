@@ -552,15 +552,18 @@ def set_fused_mlp(on: bool) -> None:
     _STATE["fused_mlp"] = bool(on)
 
 
-def set_fused_mlp_mx(on: bool, backward: bool = False) -> None:
+def set_fused_mlp_mx(on: bool, backward: bool = False, wgrad: bool = False) -> None:
     """Opt-in (off by default; SV_FUSED_MLP_MX=1 in the environment switches it on as well): under set_linear_fp8(True, recipe="mx") the blocks
     that run the fused Swin MLP take its MXFP8 forward (sv_swin_mlp_fwd_mx: the unfused MX chain in one kernel).  Without `backward` the backward
     is the fused bf16 backward, unchanged: the quantisers are straight-through.  backward=True (effective only with `on`; SV_FUSED_MLP_MX_BWD=1
     sets it as well) lets the data gradient of those blocks differentiate that very forward on MX operands (sv_swin_mlp_bwd_mx: the unfused MX
-    backward chain in one kernel) while set_linear_fp8(..., backward=True, backward_recipe="mx") holds; the weight gradients stay on
-    sv_swin_mlp_wgrad."""
+    backward chain in one kernel) while set_linear_fp8(..., backward=True, backward_recipe="mx") holds.  wgrad=True (effective only with `on`;
+    SV_FUSED_MLP_MX_WGRAD=1 sets it as well; independent of `backward`) does the same for the weight gradients of those blocks
+    (sv_swin_mlp_wgrad_mx: the unfused MX weight-gradient chain in one kernel, blocks of 32 tokens per column); without it they stay on
+    sv_swin_mlp_wgrad (bf16 operands)."""
     _STATE["fused_mlp_mx"] = bool(on)
     _STATE["fused_mlp_mx_bwd"] = bool(on) and bool(backward)
+    _STATE["fused_mlp_mx_wgrad"] = bool(on) and bool(wgrad)
 
 
 def fused_mlp_mx_enabled(C: int) -> bool:
@@ -608,6 +611,20 @@ def swin_mlp_mx_bwd_packs(w1: torch.Tensor, w2: torch.Tensor, C: int) -> torch.T
     return packs
 
 
+def fused_mlp_mx_wgrad_enabled(C: int) -> bool:
+    """The MXFP8 weight gradients of the fused Swin MLP: their switch, the MX forward of the same block (fused_mlp_mx_enabled), the MX backward
+    recipe of the Swin linears and a C the library serves.  Independent of the data-gradient switch; inert everywhere else."""
+    if not _switch("fused_mlp_mx_wgrad", "SV_FUSED_MLP_MX_WGRAD", False):
+        return False
+    return (fused_mlp_mx_enabled(C) and linear_fp8_bwd_enabled() and linear_fp8_bwd_recipe() == "mx"
+            and hip.load().sv_swin_mlp_wgrad_mx_supported(C) == 1)
+
+
+def swin_mlp_mx_wgrad_launches() -> int:
+    """sv_swin_mlp_wgrad_mx launches of this process so far."""
+    return int(hip.load().sv_swin_mlp_wgrad_mx_launches())
+
+
 def colsum(x, rows, cols, ld, out, accumulate=True):
     call("sv_colsum", ptr(x), rows, cols, ld, ptr(out), 1 if accumulate else 0)
 
@@ -627,7 +644,8 @@ def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backwa
     swin_linear_wgrad).  Active only under set_math('bf16'); independent of set_attention_fp8.
     Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them).
     Under recipe "mx" set_fused_mlp_mx(True) (off by default) gives the fused MLP an MXFP8 forward of its own (sv_swin_mlp_fwd_mx), and
-    set_fused_mlp_mx(True, backward=True) under backward_recipe "mx" an MXFP8 data gradient as well (sv_swin_mlp_bwd_mx).
+    set_fused_mlp_mx(True, backward=True) under backward_recipe "mx" an MXFP8 data gradient as well (sv_swin_mlp_bwd_mx), wgrad=True its MXFP8
+    weight gradients (sv_swin_mlp_wgrad_mx).
     The LayerNorms that feed qkv, fc1 and the reduction emit the quantised rows themselves (set_ln_quant_fused).
     recipe = "row" (default): one fp32 scale per operand row, divided out in the epilogue.  recipe = "mx": the FORWARD of the same call sites
     on MX operands - one E8M0 power-of-two scale per 32 consecutive elements of the contraction, applied by the MFMA (sv_linear_mxfp8).  A block
