@@ -95,16 +95,48 @@ int sv_conv_halo_mode(void);
 int sv_set_conv_halo_wgrad(int mode); /* the same switch for the halo-tile WEIGHT gradient of the 3 x 3 / stride 1 convolutions with 64 k channels on both
                                          sides behind sv_conv_wgrad (SV_CONV_HALO_WGRAD; 1 = calls of >= 4 tiles per split) */
 long long sv_conv_halo_launches(void); /* calls taken by the halo-tile kernels so far in this process (tests: the path they mean to exercise) */
-/* 1 when sv_conv_gather would run this call on the wide dense kernel (256 x 128 tile, LDS-DMA operand ring: Linear / 1x1 layers with
- * bf16 storage, K % 32 == 0, K >= 128, Co >= 128, 8-aligned rows and >= 256 tiles), else 0.  SV_GEMM_WIDE=0 in the environment disables it. */
+/* Launch plans: which kernel, tile, operand variant and grid sv_conv_gather / sv_tconv_gather / sv_conv_wgrad give a call.  The entry points
+ * launch what the same pure host functions plan, so a caller (tests: the path they mean to exercise) can name the path of a shape without
+ * running it; the queries make no GPU call and look at the pointers for their alignment only.  They report the plan for the current halo
+ * modes (sv_set_conv_halo, sv_set_conv_halo_wgrad) and the environment switches, with the scheduler counters of the wide and halo kernels
+ * available (a launch that cannot get a counter slot runs the plan without those paths). */
+enum { SV_PATH_GATHER = 0,               /* igemm_kernel: gathers k = (tap, ci) on the fly; grid_y = parity classes of a transposed gather */
+       SV_PATH_DENSE = 1,                /* gemm_dense_kernel: Linear / 1x1 stride-1 layers with bf16 storage, persistent workgroups */
+       SV_PATH_WIDE = 2,                 /* gemm_wide_kernel (256 x 128 tile, LDS-DMA ring), bias / activation / statistics epilogue */
+       SV_PATH_WIDE_GENERAL = 3,         /* the same with a residual or an activation-gradient source */
+       SV_PATH_HALO0 = 4, SV_PATH_HALO1 = 5, SV_PATH_HALO2 = 6,               /* resident-weights halo kernels: 3 x 3 / 64 -> 64, stem, stem data gradient */
+       SV_PATH_HALO_BLOCKED_8X32 = 7, SV_PATH_HALO_BLOCKED_16X16 = 8,         /* 3 x 3 halo kernel with blocks of 64 channels, by tile shape */
+       SV_PATH_WGRAD_TILED = 9,          /* wgrad_kernel, position splits along the grid */
+       SV_PATH_WGRAD_WIDE = 10, SV_PATH_WGRAD_WIDE_SWAP = 11,                 /* wgrad_wide_kernel; SWAP: the 256-side of the tile runs over Ci */
+       SV_PATH_WGRAD_HALO = 12 };        /* halo-tile weight gradient of the 3 x 3 convolutions */
+enum { SV_OPERANDS_F32 = 0, SV_OPERANDS_BF16_F32 = 1, SV_OPERANDS_BF16 = 2 }; /* fp32 MFMA; bf16 MFMA on fp32 storage; bf16 MFMA on bf16 storage */
+typedef struct sv_launch_plan {
+  int path;                  /* SV_PATH_* */
+  int tile_rows, tile_cols;  /* output tile of a workgroup: rows x columns (halo paths: tile height x width in positions) */
+  int operands;              /* SV_OPERANDS_* */
+  int vec;                   /* elements per operand load: 4, or 8 (16 bytes of bf16) */
+  int grid_x, grid_y, block; /* launch geometry */
+} sv_launch_plan;
+/* transposed = 0: the plan of sv_conv_gather, 1: of sv_tconv_gather (the layers of models/encoder.py:22-23,36,41-111 and the other call sites
+ * above).  Returns what the entry point returns for these arguments up to its launch: 0, or SV_ERR_INVALID for what it refuses. */
+int sv_conv_gather_plan(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype, int transposed,
+                        sv_launch_plan* plan);
+/* 1 when the plan of sv_conv_gather for this call is SV_PATH_WIDE or SV_PATH_WIDE_GENERAL (Linear / 1x1 layers with bf16 storage, K % 64 == 0,
+ * K >= 192, Co >= 128, 8-aligned rows and >= 256 tiles), else 0.  SV_GEMM_WIDE=0 in the environment disables the path. */
 int sv_conv_gather_is_wide(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype);
 /* scatter-as-gather form: out[o, co] = sum_{tap,ci : (o+p-tap)%s==0} in[(o+p-tap)/s, ci] * w[co, tap, ci]
  * (transposed-conv forward; strided-conv data-grad), decomposed per output parity class            */
 int sv_tconv_gather(const void* in, const void* w_packed, void* out, const sv_geom* g, const sv_epilogue* e,
                     int math, int act_dtype, void* stream);
-/* 1 when sv_conv_wgrad would run this call on the wide weight-gradient kernel (256 x 128 tile of dW, LDS-DMA ring fed by producer waves:
- * Linear / 1x1 stride-1 layers with bf16 storage, rows % 64 == 0 and >= 16384, >= 128 8-aligned columns on both sides), else 0.
- * SV_WGRAD_WIDE=0 in the environment disables it. */
+/* The plan of sv_conv_wgrad for these arguments (weight gradient of the layers of models/encoder.py:22-23,36,41-111 and the other call sites
+ * above; see sv_launch_plan): SV_PATH_WGRAD_*; tile_rows x tile_cols = anchor channels x (tap, gathered channel) columns of a workgroup's
+ * tile of dW, 256 x 128 on the wide path. */
+int sv_conv_wgrad_plan(const void* anchor, int lda, const void* gathered, const sv_geom* g, int cg_valid, int math, int act_dtype,
+                       sv_launch_plan* plan);
+/* 1 when that plan is SV_PATH_WGRAD_WIDE or SV_PATH_WGRAD_WIDE_SWAP (256 x 128 tile of dW, LDS-DMA ring fed by producer waves: Linear / 1x1
+ * stride-1 layers with bf16 storage, rows % 64 == 0 and >= 16384, >= 128 8-aligned columns on both sides, at most 256 tiles), else 0.
+ * SV_WGRAD_WIDE=0 in the environment disables the path.  Shapes of more than 256 tiles (e.g. Co = 896, Ci = 9344) always ran the tiled kernel;
+ * since the query is taken from the plan it answers 0 for them, where it used to answer 1. */
 int sv_conv_wgrad_is_wide(const void* anchor, int lda, const void* gathered, const sv_geom* g, int cg_valid, int math, int act_dtype);
 /* weight gradient: dw[ca, cg, tap] += sum_r anchor[r, ca] * gathered[r*s - p + tap, cg]   (fp32 atomics; dw pre-zeroed
  * or holding a running sum).  g->Do.. = anchor grid, g->Di.. = gathered grid, g->Co = anchor channels (row stride lda),

@@ -842,61 +842,47 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo_blocked_kernel(const Halo
 static std::atomic<long long> halo_launches{0};
 bool conv_halo_enabled() { return halo_mode().load(std::memory_order_relaxed) != 0; }
 
-int conv_halo_launch(const HaloConvArgs& a, int kind, hipStream_t stream) {
-  if (!conv_halo_enabled()) return 0;
-  const int tiles_h = cdiv(a.H, kind == 2 ? 16 : 8), tiles_w = cdiv(a.W, 32);
-  const long long nt = (long long)a.N * tiles_h * tiles_w;
+// ---- plans: every shape condition of the halo route (conv_halo.h) ----
+// share of the positions of th x tw tiles that lie inside an H x W image
+static double tile_use(int H, int W, int th, int tw) { return (double)H * W / ((double)cdiv(H, th) * th * cdiv(W, tw) * tw); }
+
+HaloPlan conv_halo_plan(int kind, int N, int H, int W) {
   const int mode = halo_mode().load(std::memory_order_relaxed);
-  if ((long long)a.N * a.H * a.W * 128 >= (1ll << 31)) return 0;          // buffer descriptors: 32-bit byte offsets, bit 31 = "outside"
-  if ((mode == 1 && nt < 256) || nt >= (1ll << 30)) return 0;   // fewer tiles than CUs: 72 KB of weights per workgroup for one tile each
-  int* ctr = tile_draw_counters();
-  if (!ctr) return 0;
-  const int ntiles = (int)nt;
-  if (kind == 0)
-    hipLaunchKernelGGL((conv_halo_kernel<64, 3, 3, 1, 1>), dim3(256), dim3(256), 0, stream, a, tiles_h, tiles_w, ntiles, ctr);
-  else if (kind == 1)   // 32 KB of weights + 18 KB patch + 16 KB staging: two workgroups per CU - one's epilogue runs under the other's MFMAs
-    hipLaunchKernelGGL((conv_halo_kernel<16, 4, 4, 2, 2>), dim3(512), dim3(256), 0, stream, a, tiles_h, tiles_w, ntiles, ctr);
-  else                  // 32 KB of weights + 94 KB patch: one workgroup per CU
-    hipLaunchKernelGGL(conv_halo_dgrad16_kernel, dim3(256), dim3(256), 0, stream, a, tiles_h, tiles_w, ntiles, ctr);
-  halo_launches.fetch_add(1, std::memory_order_relaxed);
-  return 1;
+  const int th = kind == 2 ? 16 : 8, tiles_h = cdiv(H, th), tiles_w = cdiv(W, 32);
+  const long long nt = (long long)N * tiles_h * tiles_w;
+  if (mode == 0 || (long long)N * H * W * 128 >= (1ll << 31)) return HaloPlan{};   // buffer descriptors: 32-bit byte offsets, bit 31 = "outside"
+  if ((mode == 1 && nt < 256) || nt >= (1ll << 30)) return HaloPlan{};   // fewer tiles than CUs: 72 KB of weights per workgroup for one tile each
+  // kind 1: 32 KB of weights + 18 KB patch + 16 KB staging: two workgroups per CU - one's epilogue runs under the other's MFMAs
+  // kind 2: 32 KB of weights + 94 KB patch: one workgroup per CU
+  return HaloPlan{kind, th, 32, 1, tiles_h, tiles_w, (int)nt, 0, kind == 1 ? 512 : 256};
 }
 
-// 3 x 3 / stride 1 / padding 1 with Ci, Co multiples of 64 (not both 64: that is conv_halo_launch's resident-weights kernel); 1 = taken
-int conv_halo_blocked_launch(const void* x, const void* w, void* y, double* stats, int N, int H, int W, int Ci, int Co, int flip, hipStream_t stream) {
+// 3 x 3 / stride 1 / padding 1 with Ci, Co multiples of 64 (not both 64: that is the resident-weights kernel of kind 0)
+HaloPlan conv_halo_blocked_plan(int N, int H, int W, int Ci, int Co) {
   const int mode = halo_mode().load(std::memory_order_relaxed);
   static const int blocked_on = [] { const char* v = getenv("SV_CONV_HALO_BLOCKED"); return v ? atoi(v) : 1; }();
-  if (mode == 0 || !blocked_on || (Ci & 63) || (Co & 63) || Ci > 512 || Co > 512) return 0;
-  if ((long long)N * H * W * (Ci > Co ? Ci : Co) * 2 >= (1ll << 31)) return 0;
-  const double u0 = (double)H * W / ((double)cdiv(H, 8) * 8 * cdiv(W, 32) * 32), u1 = (double)H * W / ((double)cdiv(H, 16) * 16 * cdiv(W, 16) * 16);
+  if (mode == 0 || !blocked_on || (Ci & 63) || (Co & 63) || Ci > 512 || Co > 512) return HaloPlan{};
+  if ((long long)N * H * W * (Ci > Co ? Ci : Co) * 2 >= (1ll << 31)) return HaloPlan{};
+  const double u0 = tile_use(H, W, 8, 32), u1 = tile_use(H, W, 16, 16);
   const bool sq = u1 > u0;
-  if (mode == 1 && (sq ? u1 : u0) < 0.5) return 0;
-  const int tiles_h = cdiv(H, sq ? 16 : 8), tiles_w = cdiv(W, sq ? 16 : 32);
+  if (mode == 1 && (sq ? u1 : u0) < 0.5) return HaloPlan{};
+  const int th = sq ? 16 : 8, tw = sq ? 16 : 32, tiles_h = cdiv(H, th), tiles_w = cdiv(W, tw);
   const long long ni = (long long)N * tiles_h * tiles_w * (Co >> 6);
-  if ((mode == 1 && ni < 1024) || ni >= (1ll << 30)) return 0;
-  int* ctr = tile_draw_counters();
-  if (!ctr) return 0;
-  HaloBlockedArgs a{x, w, y, stats, N, H, W, Ci, Co, flip};
-  if (sq) hipLaunchKernelGGL((conv3x3_halo_blocked_kernel<16, 16>), dim3(256), dim3(256), 0, stream, a, tiles_h, tiles_w, (int)ni, ctr);
-  else hipLaunchKernelGGL((conv3x3_halo_blocked_kernel<8, 32>), dim3(256), dim3(256), 0, stream, a, tiles_h, tiles_w, (int)ni, ctr);
-  halo_launches.fetch_add(1, std::memory_order_relaxed);
-  return 1;
+  if ((mode == 1 && ni < 1024) || ni >= (1ll << 30)) return HaloPlan{};
+  return HaloPlan{3, th, tw, 1, tiles_h, tiles_w, (int)ni, 0, 256};
 }
 
-// 3 x 3 / padding 1 / stride 1 or 2 weight gradient into the packed workspace ws [Co][9][Ci] (zero on entry), dbias += column sums of dy; 1 = taken
-int conv_halo_wgrad_launch(const void* x, const void* dy, float* ws, float* dbias, int N, int H, int W, int Ho, int Wo, int stride, int Ci, int Co,
-                           hipStream_t stream) {
+HaloPlan conv_halo_wgrad_plan(int N, int H, int W, int Ho, int Wo, int stride, int Ci, int Co) {
   const int mode = halo_wgrad_mode().load(std::memory_order_relaxed);
-  if (mode == 0 || (Ci & 63) || (Co & 63) || (stride != 1 && stride != 2)) return 0;
-  if (Ho != (H + 2 - 3) / stride + 1 || Wo != (W + 2 - 3) / stride + 1) return 0;
-  if ((long long)N * H * W * Ci * 2 >= (1ll << 31) || (long long)N * Ho * Wo * Co * 2 >= (1ll << 31)) return 0;
+  if (mode == 0 || (Ci & 63) || (Co & 63) || (stride != 1 && stride != 2)) return HaloPlan{};
+  if (Ho != (H + 2 - 3) / stride + 1 || Wo != (W + 2 - 3) / stride + 1) return HaloPlan{};
+  if ((long long)N * H * W * Ci * 2 >= (1ll << 31) || (long long)N * Ho * Wo * Co * 2 >= (1ll << 31)) return HaloPlan{};
   // tile shape by the share of tile positions that lie inside the (output) image
-  const double u0 = (double)Ho * Wo / ((double)cdiv(Ho, 8) * 8 * cdiv(Wo, 32) * 32), u1 = (double)Ho * Wo / ((double)cdiv(Ho, 16) * 16 * cdiv(Wo, 16) * 16);
-  const double u2 = (double)Ho * Wo / ((double)cdiv(Ho, 8) * 8 * cdiv(Wo, 16) * 16);
+  const double u0 = tile_use(Ho, Wo, 8, 32), u1 = tile_use(Ho, Wo, 16, 16), u2 = tile_use(Ho, Wo, 8, 16);
   const bool sq = u1 > u0;
   const double util = stride == 2 ? u2 : (sq ? u1 : u0);
-  if (mode == 1 && util < 0.5) return 0;                    // small maps (7 x 7): most of every tile would be padding
-  if (mode == 1 && stride == 2 && Ho * Wo < 28 * 28 / 2) return 0;     // stride 2 below 28 x 28 outputs: wgrad_kernel is as fast (14^2 -> 7^2: 106 vs 129 us)
+  if (mode == 1 && util < 0.5) return HaloPlan{};       // small maps (7 x 7): most of every tile would be padding
+  if (mode == 1 && stride == 2 && Ho * Wo < 28 * 28 / 2) return HaloPlan{};   // stride 2 below 28 x 28 outputs: wgrad_kernel is as fast (14^2 -> 7^2: 106 vs 129 us)
   const int th = stride == 2 ? 8 : (sq ? 16 : 8), tw = stride == 2 ? 16 : (sq ? 16 : 32);
   const int tiles_h = cdiv(Ho, th), tiles_w = cdiv(Wo, tw);
   const long long nt = (long long)N * tiles_h * tiles_w;
@@ -904,21 +890,44 @@ int conv_halo_wgrad_launch(const void* x, const void* dy, float* ws, float* dbia
   // splits: a multiple of 8 (one group of consecutive splits per XCD), about one workgroup per CU, at least 4 tiles per split
   int nsplit = 256 / nob; nsplit = nsplit / 8 * 8;
   if (nsplit < 8) nsplit = 8;
-  if (mode == 1 && nt < 4ll * nsplit) return 0;
-  if (nt >= (1ll << 30)) return 0;
-  HaloWgradArgs a{x, dy, ws, N, H, W, Ci, Co};
-  const dim3 grid(nsplit * nob);
+  if ((mode == 1 && nt < 4ll * nsplit) || nt >= (1ll << 30)) return HaloPlan{};
+  return HaloPlan{4, th, tw, stride, tiles_h, tiles_w, (int)nt, nsplit, nsplit * nob};
+}
+
+// ---- launches of a taken plan: no shape condition below this line ----
+void conv_halo_launch(const HaloConvArgs& a, const HaloPlan& p, int* ctr, hipStream_t stream) {
+  const dim3 grid(p.grid), block(256);
+  switch (p.kind) {
+    case 0: hipLaunchKernelGGL((conv_halo_kernel<64, 3, 3, 1, 1>), grid, block, 0, stream, a, p.tiles_h, p.tiles_w, p.nitems, ctr); break;
+    case 1: hipLaunchKernelGGL((conv_halo_kernel<16, 4, 4, 2, 2>), grid, block, 0, stream, a, p.tiles_h, p.tiles_w, p.nitems, ctr); break;
+    default: hipLaunchKernelGGL(conv_halo_dgrad16_kernel, grid, block, 0, stream, a, p.tiles_h, p.tiles_w, p.nitems, ctr); break;
+  }
+  halo_launches.fetch_add(1, std::memory_order_relaxed);
+}
+
+void conv_halo_blocked_launch(const void* x, const void* w, void* y, double* stats, int N, int H, int W, int Ci, int Co, int flip, const HaloPlan& p,
+                              int* ctr, hipStream_t stream) {
+  const HaloBlockedArgs a{x, w, y, stats, N, H, W, Ci, Co, flip};
+  const dim3 grid(p.grid), block(256);
+  if (p.th == 16) hipLaunchKernelGGL((conv3x3_halo_blocked_kernel<16, 16>), grid, block, 0, stream, a, p.tiles_h, p.tiles_w, p.nitems, ctr);
+  else hipLaunchKernelGGL((conv3x3_halo_blocked_kernel<8, 32>), grid, block, 0, stream, a, p.tiles_h, p.tiles_w, p.nitems, ctr);
+  halo_launches.fetch_add(1, std::memory_order_relaxed);
+}
+
+void conv_halo_wgrad_launch(const void* x, const void* dy, float* ws, float* dbias, int N, int H, int W, int Ho, int Wo, int Ci, int Co, const HaloPlan& p,
+                            hipStream_t stream) {
+  const HaloWgradArgs a{x, dy, ws, N, H, W, Ci, Co};
+  const dim3 grid(p.grid);
 #define SV_HALO_WG(TH_, TW_, S_)                                                                                                                           \
   do {                                                                                                                                                   \
-    if (dbias) hipLaunchKernelGGL((conv3x3_wgrad_halo_kernel<TH_, TW_, S_, true>), grid, dim3(256), 0, stream, a, Ho, Wo, tiles_h, tiles_w, (int)nt, nsplit, dbias); \
-    else hipLaunchKernelGGL((conv3x3_wgrad_halo_kernel<TH_, TW_, S_, false>), grid, dim3(256), 0, stream, a, Ho, Wo, tiles_h, tiles_w, (int)nt, nsplit, dbias);      \
+    if (dbias) hipLaunchKernelGGL((conv3x3_wgrad_halo_kernel<TH_, TW_, S_, true>), grid, dim3(256), 0, stream, a, Ho, Wo, p.tiles_h, p.tiles_w, p.nitems, p.nsplit, dbias); \
+    else hipLaunchKernelGGL((conv3x3_wgrad_halo_kernel<TH_, TW_, S_, false>), grid, dim3(256), 0, stream, a, Ho, Wo, p.tiles_h, p.tiles_w, p.nitems, p.nsplit, dbias);      \
   } while (0)
-  if (stride == 2) SV_HALO_WG(8, 16, 2);
-  else if (sq) SV_HALO_WG(16, 16, 1);
+  if (p.stride == 2) SV_HALO_WG(8, 16, 2);
+  else if (p.th == 16) SV_HALO_WG(16, 16, 1);
   else SV_HALO_WG(8, 32, 1);
 #undef SV_HALO_WG
   halo_launches.fetch_add(1, std::memory_order_relaxed);
-  return 1;
 }
 
 }  // namespace sv

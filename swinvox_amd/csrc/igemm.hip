@@ -64,12 +64,7 @@ template <int WM_, int WN_, int MT_, int NT_> struct Tile {
   static constexpr int NW = WM_ * WN_, NTHR = NW * 64;
 };
 typedef Tile<4, 2, 2, 2> TileDefault;   // 128 x 64, 8 waves of 32x32 (few registers per thread -> 2-3 workgroups per CU)
-#ifndef SV_IG_REG_EPILOGUE
 typedef Tile<2, 4, 4, 2> TileBig;       // 128 x 128, 8 waves (512 threads): halves the A re-reads of TileDefault at equal registers
-#else
-typedef Tile<4, 2, 2, 4> TileBig;       // the same tile with 32 x 64 wave tiles (6 operand fragments per 8 MFMAs either way): a wave owns whole
-                                        // 128-byte pieces of output rows, which the register epilogue (wave_epilogue) stores as full lines
-#endif
 typedef Tile<4, 1, 2, 1> TileNarrow;    // 128 x 16
 typedef Tile<4, 2, 2, 3> Tile96;        // 128 x 96, 8 waves: the Swin channel counts are multiples of 96 (no padded columns for 96 / 192 / 288)
 
@@ -312,23 +307,6 @@ __device__ __forceinline__ void epilogue_rows(const IGemmArgs& p, const ClassInf
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Register epilogue of the 128 x 128 tile with bf16 storage (8-aligned rows and columns): no LDS staging, no workgroup barrier.
-// A/B BUILD ONLY (-DSV_IG_REG_EPILOGUE) - round 3 built it in three forms because a probe build without any epilogue had suggested
-// that the LDS-staged form costs 9.4 of the 34.8 ms per step of these kernels; measured in the step it never won:
-// what the probe had removed was the output stream itself, which bounds the short-K layers either way.
-// With the macro the tile runs as Tile<4, 2, 2, 4>: a wave owns 32 rows x 64 columns, i.e. WHOLE 128-byte pieces of output rows.  mma_slab
-// leaves lane (lr, lg) with row lr, columns 4 lg .. 4 lg + 3 of every 16 x 16 block (8 bytes of bf16).  Lane exchanges, all VALU:
-//   v_permlane32_swap X, Y : lanes 32-63 of X <-> lanes 0-31 of Y      rows (X: A0 A1 A2 A3, Y: B0 B1 B2 B3) -> (A0 A1 B0 B1), (A2 A3 B2 B3)
-//   v_permlane16_swap X, Y : odd 16-lane rows of X <-> even rows of Y                                       -> (A0 A2 B0 B2), (A1 A3 B1 B3)
-// turn the pieces of a PAIR of blocks into 16 consecutive bytes: lane group lg then holds columns 8 lg .. 8 lg + 7 of blocks 0 | 1 (piece
-// P0) and of blocks 2 | 3 (piece P1) of row lr.  A DPP row_ror:8 then trades P1 of the lanes lr < 8 for P0 of the lanes lr >= 8, after
-// which ONE store instruction covers rows 0-7 of the 16-row block with all eight 16-byte pieces of each (lane -> row lr & 7, piece
-// lg + 4 (lr >> 3)): 8 whole 128-byte lines, and a second one rows 8-15.  Residual / activation-gradient rows are loaded in the store
-// layout and brought back by the inverse exchanges; every load of the tile is issued before its first store (vmcnt retires in issue
-// order - which is also why a single spilled register is poison here: a scratch reload behind the stores waits for them).
-// Semantics = epilogue_rows.
-// ------------------------------------------------------------------------------------------------
 template <int CTRL> __device__ __forceinline__ float gw_dpp_add(float v) {
   return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
@@ -337,213 +315,26 @@ __device__ __forceinline__ float row16_total(float v) {
   v = gw_dpp_add<0x111>(v); v = gw_dpp_add<0x112>(v); v = gw_dpp_add<0x114>(v); v = gw_dpp_add<0x118>(v);
   return v;
 }
-__device__ __forceinline__ void lane_swap32(uint32_t& a, uint32_t& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void lane_swap16(uint32_t& a, uint32_t& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-struct U2 { uint32_t x, y; };
-struct U4 { uint32_t x, y, z, w; };
-// accumulator-layout pieces of a block pair -> this lane's 16 bytes (columns 8 lg .. 8 lg + 7 of the pair's 32), and back
-__device__ __forceinline__ U4 pair_to_rows(bf16x4 a, bf16x4 b) {
-  U2 x = __builtin_bit_cast(U2, a), y = __builtin_bit_cast(U2, b);
-  lane_swap32(x.x, y.x); lane_swap32(x.y, y.y);
-  lane_swap16(x.x, y.x); lane_swap16(x.y, y.y);
-  return U4{x.x, x.y, y.x, y.y};
-}
-__device__ __forceinline__ void rows_to_pair(U4 u, bf16x4& a, bf16x4& b) {
-  U2 x{u.x, u.y}, y{u.z, u.w};
-  lane_swap16(x.x, y.x); lane_swap16(x.y, y.y);
-  lane_swap32(x.x, y.x); lane_swap32(x.y, y.y);
-  a = __builtin_bit_cast(bf16x4, x); b = __builtin_bit_cast(bf16x4, y);
-}
-__device__ __forceinline__ uint32_t ror8(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false); }   // lane lr <- lane (lr + 8) % 16 of its row
-__device__ __forceinline__ U4 ror8(U4 v) { return U4{ror8(v.x), ror8(v.y), ror8(v.z), ror8(v.w)}; }
-__device__ __forceinline__ U4 pick(bool c, U4 a, U4 b) { return U4{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w}; }
-// (P0, P1) of row lr  ->  (S1, S2): S1 = piece lg + 4 (lr >> 3) of row lr & 7, S2 = the same piece of row 8 + (lr & 7); its own inverse
-__device__ __forceinline__ void halves_trade(bool low, U4& a, U4& b) {
-  const U4 got = ror8(pick(low, b, a));
-  a = pick(low, a, got); b = pick(low, got, b);
-}
-
 // bf16 rows of the output (and of every tensor the epilogue reads or writes beside it) start on 16-byte boundaries and are whole 8-column pieces
 __host__ __device__ __forceinline__ bool rows_16_byte_aligned(const IGemmArgs& p) {
   const Epi& e = p.e;
   return ((e.ldc | e.col_off | p.g.Co) & 7) == 0 && (!e.residual || (e.ldr & 7) == 0) &&
          (((uintptr_t)p.y | (uintptr_t)e.residual | (uintptr_t)e.pre_act | (uintptr_t)e.act_grad_src) & 15) == 0;
 }
-// what wave_epilogue serves (bf16 storage is the caller's business)
-static inline bool epilogue_in_registers(const IGemmArgs& p) {
-  return rows_16_byte_aligned(p) && !(p.e.residual && p.e.act_grad_src) && !(p.e.stats && (p.e.residual || p.e.act_grad_src));
-}
-
-// GENERAL = the epilogue reads a residual or an activation-gradient source (16 + 6 more registers per lane)
-template <bool TCONV, typename TL, bool GENERAL = true>
-__device__ __forceinline__ void wave_epilogue(const IGemmArgs& p, const ClassInfo& ci, int cnt0, int cnt1, int cnt2, float* red,
-                                              const f32x4 (&acc)[TL::MT][TL::NT], int row0, int col0, int Mrows) {
-  constexpr int MT = TL::MT, NT = TL::NT, BM = TL::BM, BN = TL::BN;
-  static_assert(NT == 4, "a wave owns 64 columns = whole 128-byte row pieces");
-  const Geom& g = p.g;
-  const Epi& e = p.e;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lg = lane >> 4;
-  const int wm = wave / TL::WN, wn = wave % TL::WN;
-  const bool low = lr < 8;
-  __bf16* __restrict__ Y = static_cast<__bf16*>(p.y);
-  const __bf16* __restrict__ RES = GENERAL ? static_cast<const __bf16*>(e.residual) : nullptr;
-  const __bf16* __restrict__ AGS = GENERAL ? static_cast<const __bf16*>(e.act_grad_src) : nullptr;
-  __bf16* __restrict__ PRE = static_cast<__bf16*>(e.pre_act);
-  const int cw0 = col0 + wn * 64;                          // first column of the wave
-  const int cs = cw0 + (lg + 4 * (lr >> 3)) * 8;           // the 16-byte piece this lane loads / stores
-  const bool csok = cs < g.Co;                             // Co % 8 == 0: a piece is whole or absent
-  // rows this lane loads / stores: (lr & 7) and 8 + (lr & 7) of every 16-row block; its accumulator row lr is one of the two
-  int posA[MT], posB[MT];
-  bool rokA[MT], rokB[MT];
-  float sc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int mA = row0 + (wm * MT + mt) * 16 + (lr & 7), mB = mA + 8;
-    rokA[mt] = mA < Mrows; rokB[mt] = mB < Mrows;
-    posA[mt] = rokA[mt] ? mA : 0; posB[mt] = rokB[mt] ? mB : 0;
-    if constexpr (TCONV) {
-      int n_, d_, h_, w_;
-      decode_row(posA[mt], cnt0, cnt1, cnt2, n_, d_, h_, w_);
-      posA[mt] = ((n_ * g.Do + ci.o0[0] + g.sd * d_) * g.Ho + ci.o0[1] + g.sh * h_) * g.Wo + ci.o0[2] + g.sw * w_;
-      decode_row(posB[mt], cnt0, cnt1, cnt2, n_, d_, h_, w_);
-      posB[mt] = ((n_ * g.Do + ci.o0[0] + g.sd * d_) * g.Ho + ci.o0[1] + g.sh * h_) * g.Wo + ci.o0[2] + g.sw * w_;
-    }
-    sc[mt] = (RES && e.row_scale) ? e.row_scale[(low ? posA[mt] : posB[mt]) / e.rows_per_scale] : 1.f;
-  }
-  float bias[NT][4];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = cw0 + nt * 16 + lg * 4 + j;
-      bias[nt][j] = (e.bias && n < g.Co) ? e.bias[n] : 0.f;
-    }
-  // ---- every load of the tile: residual rows OR activation-gradient source rows (never both on this path), in the store layout
-  U4 rawA[MT], rawB[MT];
-  if (RES || AGS) {
-    const __bf16* src = RES ? RES : AGS + e.col_off;
-    const int lds_ = RES ? e.ldr : e.ldc;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      rawA[mt] = (rokA[mt] && csok) ? *reinterpret_cast<const U4*>(src + (size_t)posA[mt] * lds_ + cs) : U4{0, 0, 0, 0};
-      rawB[mt] = (rokB[mt] && csok) ? *reinterpret_cast<const U4*>(src + (size_t)posB[mt] * lds_ + cs) : U4{0, 0, 0, 0};
-    }
-  }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    bf16x4 aux[NT] = {}, ob[NT], pb[NT];                   // aux: the residual / activation-gradient source in the accumulator layout
-    if (RES || AGS) {
-      U4 a = rawA[mt], b = rawB[mt];
-      halves_trade(low, a, b);
-      rows_to_pair(a, aux[0], aux[1]);
-      rows_to_pair(b, aux[2], aux[3]);
-    }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = acc[mt][nt][j] + bias[nt][j];
-      if (AGS) {
-        if (e.act_grad_kind == SV_ACT_GELU) {              // pairs: packed fp32 math (common.h)
-#pragma unroll
-          for (int j = 0; j < 4; j += 2) {
-            const f32x2 dg = gelu_grad_fast2((f32x2){(float)aux[nt][j], (float)aux[nt][j + 1]});
-            v[j] *= dg[0]; v[j + 1] *= dg[1];
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] *= act_grad_t<true>((float)aux[nt][j], e.act_grad_kind, e.slope);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) pb[nt][j] = (__bf16)v[j];
-      if (e.act == SV_ACT_GELU) {
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-          const f32x2 gl = gelu_fast2((f32x2){v[j], v[j + 1]});
-          v[j] = gl[0]; v[j + 1] = gl[1];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = apply_act_t<true>(v[j], e.act, e.slope);
-      }
-      if (RES) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (float)aux[nt][j] + sc[mt] * v[j];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ob[nt][j] = (__bf16)v[j];
-    }
-    const size_t oA = (size_t)posA[mt] * e.ldc + e.col_off + cs, oB = (size_t)posB[mt] * e.ldc + e.col_off + cs;
-    if (PRE) {
-      U4 a = pair_to_rows(pb[0], pb[1]), b = pair_to_rows(pb[2], pb[3]);
-      halves_trade(low, a, b);
-      if (rokA[mt] && csok) *reinterpret_cast<U4*>(PRE + oA) = a;
-      if (rokB[mt] && csok) *reinterpret_cast<U4*>(PRE + oB) = b;
-    }
-    U4 a = pair_to_rows(ob[0], ob[1]), b = pair_to_rows(ob[2], ob[3]);
-    halves_trade(low, a, b);
-    if (rokA[mt] && csok) *reinterpret_cast<U4*>(Y + oA) = a;
-    if (rokB[mt] && csok) *reinterpret_cast<U4*>(Y + oB) = b;
-  }
-  if (e.stats) {
-    // Per-channel sum / sum of squares of what was stored, in a second sweep over the accumulators (a BatchNorm producer's epilogue is bias +
-    // activation: nothing to load - epilogue_in_registers() keeps statistics with a residual / activation-gradient source off this path;
-    // carrying 2 x 16 running sums through the store loop cost the persistent kernel 100 bytes of scratch per lane).  The 16 rows of a lane
-    // group by DPP, the WM waves that share the columns through LDS, then ONE double atomic per column and workgroup.
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const float f = (float)(__bf16)apply_act_t<true>(acc[mt][nt][j] + bias[nt][j], e.act, e.slope);
-          if (low ? rokA[mt] : rokB[mt]) { t1 += f; t2 += f * f; }
-        }
-        const float a1 = row16_total(t1), a2 = row16_total(t2);
-        if (lr == 15) {
-          const int c = (wn * NT + nt) * 16 + lg * 4 + j;
-          red[(wm * BN + c) * 2] = a1; red[(wm * BN + c) * 2 + 1] = a2;
-        }
-      }
-    __syncthreads();
-    if (tid < BN && col0 + tid < g.Co) {
-      float a = 0.f, b = 0.f;
-#pragma unroll
-      for (int w = 0; w < TL::WM; ++w) { a += red[(w * BN + tid) * 2]; b += red[(w * BN + tid) * 2 + 1]; }
-      double* st = e.stats + (size_t)((row0 / BM) % SV_BN_SLOTS) * 2 * g.Co;
-      atomicAdd(st + col0 + tid, (double)a);
-      atomicAdd(st + g.Co + col0 + tid, (double)b);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // tile epilogue shared by the gather kernels: accumulators -> LDS tile -> cooperative, row-contiguous vector reads/writes with
 // the fused bias / activation(-gradient) / residual / pre-activation copy / per-channel statistics.  Every wave must have
 // finished reading the operand tiles (Cs aliases them) before the call.
 // ------------------------------------------------------------------------------------------------
 template <bool BF16, bool TCONV, typename TL, typename AT>
-__device__ __forceinline__ bool tile_epilogue(const IGemmArgs& p, const ClassInfo& ci, int cnt0, int cnt1, int cnt2, float* Cs, float* red,
+__device__ __forceinline__ void tile_epilogue(const IGemmArgs& p, const ClassInfo& ci, int cnt0, int cnt1, int cnt2, float* Cs, float* red,
                                               const f32x4 (&acc)[TL::MT][TL::NT], int row0, int col0, int Mrows) {
-  constexpr int BM = TL::BM, BN = TL::BN, MT = TL::MT, NT = TL::NT, NTHR = TL::NTHR, NW = TL::NW, LDC = BN + 4;
-  const Geom& g = p.g;
+  constexpr int BN = TL::BN, MT = TL::MT, NT = TL::NT, LDC = BN + 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / TL::WN, wn = wave % TL::WN;
-  AT* __restrict__ Y = static_cast<AT*>(p.y);
-  const Epi& e = p.e;
   // bf16 storage with 8-aligned rows: 16 bytes per lane
   bool wide = false;
   if constexpr (sizeof(AT) == 2 && BN % 8 == 0) wide = rows_16_byte_aligned(p);
-#ifdef SV_IG_REG_EPILOGUE      // A/B build (measured: loses): 128 x 128 tiles store straight from the accumulator registers
-  if constexpr (BF16 && sizeof(AT) == 2 && NT == 4) {
-    if (wide && !(e.residual && e.act_grad_src) && !(e.stats && (e.residual || e.act_grad_src))) {   // straight from the accumulator registers: no LDS tile, no barrier
-      wave_epilogue<TCONV, TL>(p, ci, cnt0, cnt1, cnt2, red, acc, row0, col0, Mrows);
-      return false;
-    }
-  }
-#endif
   {
     const int lr = lane & 15, lg = lane >> 4;
 #pragma unroll
@@ -557,10 +348,9 @@ __device__ __forceinline__ bool tile_epilogue(const IGemmArgs& p, const ClassInf
   // row pass: CV consecutive columns per thread.  bf16 storage with 8-aligned rows moves 16 bytes per lane (half the
   // global-memory instructions, 1 KB per wave store); everything else keeps 4 columns per thread.
   if constexpr (sizeof(AT) == 2 && BN % 8 == 0) {
-    if (wide) { epilogue_rows<BF16, TCONV, TL, AT, 8>(p, ci, cnt0, cnt1, cnt2, Cs, red, row0, col0, Mrows); return true; }
+    if (wide) { epilogue_rows<BF16, TCONV, TL, AT, 8>(p, ci, cnt0, cnt1, cnt2, Cs, red, row0, col0, Mrows); return; }
   }
   epilogue_rows<BF16, TCONV, TL, AT, 4>(p, ci, cnt0, cnt1, cnt2, Cs, red, row0, col0, Mrows);
-  return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -771,7 +561,7 @@ __global__ __launch_bounds__(TL::NTHR, TL::NTHR == 512 ? 4 : 2) void igemm_kerne
 // the NEXT tile's first operand slab before the epilogue of the current one, so that latency hides behind the epilogue
 // and the start-up cost is paid once.  Same tiles, loader mapping, LDS layout and epilogue as igemm_kernel.
 // ------------------------------------------------------------------------------------------------
-template <typename TL, typename AT, typename WT, int VEC, bool GENERAL = true>
+template <typename TL, typename AT, typename WT, int VEC>
 __global__ __launch_bounds__(TL::NTHR, TL::NTHR >= 512 ? 4 : 2) void gemm_dense_kernel(const IGemmArgs p, int ntiles) {
   typedef __bf16 LT;
   constexpr int BK = Cfg<true>::BK, LD = BK + Cfg<true>::PAD;
@@ -855,15 +645,8 @@ __global__ __launch_bounds__(TL::NTHR, TL::NTHR >= 512 ? 4 : 2) void gemm_dense_
 #ifdef SV_IG_PROBE_NOEPI
     if (acc[0][0][0] == 12345.678f) static_cast<AT*>(p.y)[0] = (AT)acc[0][0][1];
 #else
-    // 128 x 128 tile (Tile<4, 2, 2, 4>) with 16-byte aligned rows: straight from the accumulator registers - no LDS tile, no barrier, a wave
-    // that is done with its stores goes on to the next tile's first slab; the other tiles stage through LDS
-    // (the host sends a layer to this instantiation only when epilogue_in_registers() holds)
-    if constexpr (TL::NT == 4) {
-      wave_epilogue<false, TL, GENERAL>(p, ci, g.Do, g.Ho, g.Wo, red, acc, row0, col0, Mrows);
-    } else {
-      tile_epilogue<true, false, TL, AT>(p, ci, g.Do, g.Ho, g.Wo, Cs, red, acc, row0, col0, Mrows);
-      __syncthreads();                                   // the staged tile is consumed: operand slabs may land again
-    }
+    tile_epilogue<true, false, TL, AT>(p, ci, g.Do, g.Ho, g.Wo, Cs, red, acc, row0, col0, Mrows);
+    __syncthreads();                                     // the staged tile is consumed: operand slabs may land again
 #endif
     have = more; row0 = row0n; col0 = col0n;
   }
@@ -1541,7 +1324,6 @@ static GwCounters* gemm_wide_counter_table() {
   }
   return c.buf ? &c : nullptr;
 }
-static bool gemm_wide_counters_ready() { return gemm_wide_counter_table() != nullptr; }
 static int* gemm_wide_counters() {     // next launch slot of the current device
   GwCounters* c = gemm_wide_counter_table();
   return c ? c->buf + 16 * (c->next.fetch_add(1) % GW_SLOTS) : nullptr;
@@ -1549,32 +1331,46 @@ static int* gemm_wide_counters() {     // next launch slot of the current device
 
 int* tile_draw_counters() { return gemm_wide_counters(); }
 
-// Halo-tile kernels (conv_halo.hip) take the shapes they are built for - 3 x 3 / stride 1 / 64 -> 64 (forward and data gradient) and
-// the 4 x 4 stem on the space-to-depth image (forward, and its 64 -> 16 data gradient) - when the call is a plain store (+ BatchNorm
-// statistics); 0 = not taken
-static int try_halo(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype, bool dgrad,
-                    hipStream_t s) {
-  if (math != SV_MATH_BF16 || act_dtype != SV_BF16 || !conv_halo_enabled()) return 0;
-  if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)out) & 15) return 0;
-  // the stem's data gradient (kind 1 backwards: 64 -> 16 channels, a plain store) on the tile that reads each dy patch once
-  if (dgrad && g->kh == 4 && g->kw == 4 && g->ph == 2 && g->pw == 2 && g->Ci == 64 && g->Co == 16 && g->kd == 1 && g->Di == 1 && g->Do == 1 &&
-      g->sd == 1 && g->sh == 1 && g->sw == 1 && g->pd == 0 && g->Hi == g->Ho && g->Wi == g->Wo && g->ldi == 64 && !e->bias && !e->residual &&
-      !e->row_scale && !e->pre_act && !e->stats && e->act == SV_ACT_NONE && !e->act_grad_src && e->ldc == 16 && e->col_off == 0) {
-    HaloConvArgs a{in, w, out, nullptr, g->N, g->Hi, g->Wi, 1};
-    return conv_halo_launch(a, 2, s);
+// ------------------------------------------------------------------------------------------------
+// Launch plans of sv_conv_gather / sv_tconv_gather.  Which kernel, tile, operand variant and grid a call gets is decided HERE, by pure host
+// functions (no HIP call); the entry points launch what plan_gather returns and sv_conv_gather_plan reports the same struct.
+// ------------------------------------------------------------------------------------------------
+enum { TILE_NARROW, TILE_DEFAULT, TILE_96, TILE_BIG };
+struct GatherPlan {
+  sv_launch_plan q;     // path, tile, operand variant, grid, block: what the query reports
+  int tile;             // TILE_* of the dense and the gathering kernels
+  int ntiles;           // dense and wide kernels: the tiles their persistent workgroups walk
+  bool counters;        // the launch needs a slot of the scheduler counters
+  HaloPlan halo;        // halo paths: tile counts of conv_halo.hip
+};
+template <typename F> static void with_tile(int tile, F&& f) {
+  switch (tile) {
+    case TILE_NARROW: f(TileNarrow{}); break;
+    case TILE_96: f(Tile96{}); break;
+    case TILE_BIG: f(TileBig{}); break;
+    default: f(TileDefault{}); break;
   }
-  if ((g->Co & 63) || g->kd != 1 || g->Di != 1 || g->Do != 1 || g->sd != 1 || g->sh != 1 || g->sw != 1 || g->pd != 0) return 0;
-  if (g->Hi != g->Ho || g->Wi != g->Wo || g->ldi != g->Ci) return 0;
-  if (e->bias || e->residual || e->row_scale || e->pre_act || e->act != SV_ACT_NONE || e->act_grad_src || e->ldc != g->Co || e->col_off != 0) return 0;
-  int kind;
-  if (g->kh == 3 && g->kw == 3 && g->ph == 1 && g->pw == 1 && g->Ci == 64 && g->Co == 64) kind = 0;
-  else if (g->kh == 3 && g->kw == 3 && g->ph == 1 && g->pw == 1 && !(dgrad && e->stats))      // more channels: blocks of 64 x 64 (conv_halo.hip)
-    return conv_halo_blocked_launch(in, w, out, e->stats, g->N, g->Hi, g->Wi, g->Ci, g->Co, dgrad ? 1 : 0, s);
-  else if (!dgrad && g->kh == 4 && g->kw == 4 && g->ph == 2 && g->pw == 2 && g->Ci == 16 && g->Co == 64) kind = 1;
-  else return 0;
-  if (dgrad && e->stats) return 0;
-  HaloConvArgs a{in, w, out, e->stats, g->N, g->Hi, g->Wi, dgrad ? 1 : 0};
-  return conv_halo_launch(a, kind, s);
+}
+
+// Halo-tile kernels (conv_halo.hip) take the shapes they are built for - 3 x 3 / stride 1 / 64 k -> 64 k channels (forward and data gradient)
+// and the 4 x 4 stem on the space-to-depth image (forward, and its 64 -> 16 data gradient) - when the call is a plain store (+ BatchNorm
+// statistics in the forward); kind -1 = not taken
+static HaloPlan plan_halo(const IGemmArgs& a, int math, int act, bool dgrad) {
+  const Geom& g = a.g;
+  const Epi& e = a.e;
+  if (math != SV_MATH_BF16 || act != SV_BF16 || !conv_halo_enabled()) return HaloPlan{};
+  if (((uintptr_t)a.x | (uintptr_t)a.w | (uintptr_t)a.y) & 15) return HaloPlan{};
+  if (g.kd != 1 || g.Di != 1 || g.Do != 1 || g.sd != 1 || g.sh != 1 || g.sw != 1 || g.pd != 0) return HaloPlan{};
+  if (g.Hi != g.Ho || g.Wi != g.Wo || g.ldi != g.Ci) return HaloPlan{};
+  if (e.bias || e.residual || e.row_scale || e.pre_act || e.act != SV_ACT_NONE || e.act_grad_src || e.ldc != g.Co || e.col_off != 0) return HaloPlan{};
+  if (dgrad && e.stats) return HaloPlan{};
+  const bool k3 = g.kh == 3 && g.kw == 3 && g.ph == 1 && g.pw == 1, k4 = g.kh == 4 && g.kw == 4 && g.ph == 2 && g.pw == 2;
+  // the stem's data gradient (kind 1 backwards: 64 -> 16 channels) on the tile that reads each dy patch once
+  if (dgrad && k4 && g.Ci == 64 && g.Co == 16) return conv_halo_plan(2, g.N, g.Hi, g.Wi);
+  if (g.Co & 63) return HaloPlan{};
+  if (k3) return g.Ci == 64 && g.Co == 64 ? conv_halo_plan(0, g.N, g.Hi, g.Wi) : conv_halo_blocked_plan(g.N, g.Hi, g.Wi, g.Ci, g.Co);   // more channels: blocks of 64 x 64
+  if (!dgrad && k4 && g.Ci == 16 && g.Co == 64) return conv_halo_plan(1, g.N, g.Hi, g.Wi);
+  return HaloPlan{};
 }
 
 // the wide kernel takes the dense layers whose K loop is worth a DMA ring and whose tile count fills the chip;
@@ -1588,25 +1384,39 @@ static bool gemm_wide_ok(const IGemmArgs& a, long long M) {
   // atomics per column and 64 rows), which need a K loop long enough to carry them
   if (enabled == 1 && e.stats && K < 1024) return false;
   if (enabled == 1 && e.act_grad_src && K < 384) return false;   // 192 -> 768 with GELU': 573 us against 522 on the 128-wide kernel
-  if (((e.ldc | e.col_off | Co) & 7) || (e.residual && (e.ldr & 7))) return false;
+  if (!rows_16_byte_aligned(a) || ((uintptr_t)a.w & 15)) return false;
   // the general epilogue variant keeps no statistics registers and one set of prefetched rows (residual OR activation-gradient source)
   if ((e.stats && (e.residual || e.act_grad_src)) || (e.residual && e.act_grad_src)) return false;
-  if (((uintptr_t)a.y | (uintptr_t)e.residual | (uintptr_t)e.pre_act | (uintptr_t)e.act_grad_src | (uintptr_t)a.w) & 15) return false;
   return (long long)cdiv(M, 256) * cdiv(Co, GW_BN) >= 256;
 }
-template <bool TCONV>
-static void launch_igemm(const IGemmArgs& a, long long M, int ncls, int math, int act, hipStream_t s) {
-  const int Co = a.g.Co;
-  const bool bf = math == SV_MATH_BF16;
+
+// M = rows of the call (transposed: of its largest parity class), ncls = parity classes (1 unless transposed), counters = a slot of the
+// scheduler counters can be had.  Order: halo tiles, wide kernel, dense kernel, gathering kernel.
+static GatherPlan plan_gather(const IGemmArgs& a, long long M, int ncls, int math, int act, bool tconv, bool counters) {
+  const Geom& g = a.g;
+  const int Co = g.Co;
+  GatherPlan p{};
   // bf16 storage: weights are bf16 too; 16-byte operand chunks when the gathered rows allow it
-  const bool v8 = act == SV_BF16 && (a.g.Ci % 8) == 0 && (a.g.ldi % 8) == 0 && ((uintptr_t)a.x & 15) == 0;
-#define SV_LAUNCH_IG(TL)                                                                                                           \
-  do {                                                                                                                             \
-    if (!bf) hipLaunchKernelGGL((igemm_kernel<false, TCONV, TL, float, float, 4>), grid, dim3(TL::NTHR), 0, s, a);                  \
-    else if (act != SV_BF16) hipLaunchKernelGGL((igemm_kernel<true, TCONV, TL, float, float, 4>), grid, dim3(TL::NTHR), 0, s, a);   \
-    else if (v8) hipLaunchKernelGGL((igemm_kernel<true, TCONV, TL, __bf16, __bf16, 8>), grid, dim3(TL::NTHR), 0, s, a);            \
-    else hipLaunchKernelGGL((igemm_kernel<true, TCONV, TL, __bf16, __bf16, 4>), grid, dim3(TL::NTHR), 0, s, a);                    \
-  } while (0)
+  const bool v8 = act == SV_BF16 && (g.Ci % 8) == 0 && (g.ldi % 8) == 0 && ((uintptr_t)a.x & 15) == 0;
+  p.q.operands = math != SV_MATH_BF16 ? SV_OPERANDS_F32 : act != SV_BF16 ? SV_OPERANDS_BF16_F32 : SV_OPERANDS_BF16;
+  p.q.vec = v8 ? 8 : 4;
+  p.q.grid_y = 1;
+  if (counters && (p.halo = plan_halo(a, math, act, tconv)).kind >= 0) {
+    p.q.path = p.halo.kind < 3 ? SV_PATH_HALO0 + p.halo.kind : p.halo.th == 16 ? SV_PATH_HALO_BLOCKED_16X16 : SV_PATH_HALO_BLOCKED_8X32;
+    p.q.tile_rows = p.halo.th; p.q.tile_cols = p.halo.tw; p.q.grid_x = p.halo.grid; p.q.block = 256;
+    p.counters = true;
+    return p;
+  }
+  // Linear / 1x1 stride-1 layers with bf16 storage: the wide kernel, or the persistent dense kernel (2 workgroups per CU walk the tiles)
+  const bool dense = !tconv && v8 && g.kd * g.kh * g.kw == 1 && g.sd == 1 && g.sh == 1 && g.sw == 1 &&
+                     g.pd == 0 && g.ph == 0 && g.pw == 0 && g.Di == g.Do && g.Hi == g.Ho && g.Wi == g.Wo;
+  if (dense && counters && gemm_wide_ok(a, M)) {
+    p.q.path = a.e.residual || a.e.act_grad_src ? SV_PATH_WIDE_GENERAL : SV_PATH_WIDE;
+    p.q.tile_rows = 256; p.q.tile_cols = GW_BN; p.q.grid_x = 256; p.q.block = 768;
+    p.ntiles = cdiv(M, 256) * cdiv(Co, GW_BN);
+    p.counters = true;
+    return p;
+  }
   // 96-wide tile for Co = 96 k when it wins the estimate  ceil(tiles / 256 CUs) x tile area x (1 + 2 % per extra pass over A)
   // (the per-channel statistics epilogue needs a power-of-two column-group count, so BatchNorm producers never take it)
   bool use96 = false;
@@ -1618,55 +1428,90 @@ static void launch_igemm(const IGemmArgs& a, long long M, int ncls, int math, in
     const double e96 = est(128, 96), e64 = est(128, 64), e128 = Co > 64 ? est(128, 128) : 1e300;
     use96 = e96 <= e64 && e96 <= e128;
   }
-  // Linear / 1x1 stride-1 layers with bf16 storage: the persistent dense kernel (2 workgroups per CU walk the tiles)
-  const bool dense = !TCONV && v8 && a.g.kd * a.g.kh * a.g.kw == 1 && a.g.sd == 1 && a.g.sh == 1 && a.g.sw == 1 &&
-               a.g.pd == 0 && a.g.ph == 0 && a.g.pw == 0 && a.g.Di == a.g.Do && a.g.Hi == a.g.Ho && a.g.Wi == a.g.Wo;
-#define SV_LAUNCH_DENSE(TL)                                                                                         \
-  do {                                                                                                              \
-    const int ntiles = cdiv(M, TL::BM) * cdiv(Co, TL::BN);                                                          \
-    int nb = 256 * (TL::NTHR >= 512 ? 2 : 4);                                                                       \
-    if (nb > ntiles) nb = ntiles;                                                                                   \
-    if constexpr (TL::NT == 4) {                                                                                    \
-      if (!a.e.residual && !a.e.act_grad_src) {                                                                     \
-        hipLaunchKernelGGL((gemm_dense_kernel<TL, __bf16, __bf16, 8, false>), dim3(nb), dim3(TL::NTHR), 0, s, a, ntiles); \
-        break;                                                                                                      \
-      }                                                                                                             \
-    }                                                                                                               \
-    hipLaunchKernelGGL((gemm_dense_kernel<TL, __bf16, __bf16, 8, true>), dim3(nb), dim3(TL::NTHR), 0, s, a, ntiles);    \
-  } while (0)
-  if constexpr (!TCONV) {
-    if (dense && gemm_wide_ok(a, M) && gemm_wide_counters_ready()) {
-      int* ctr = gemm_wide_counters();
-      const bool general = a.e.residual || a.e.act_grad_src;
-      const int ntiles = cdiv(M, 256) * cdiv(Co, GW_BN);
-      if (general) hipLaunchKernelGGL((gemm_wide_kernel<true, 4, 4, 3>), dim3(256), dim3(768), 0, s, a, ntiles, ctr);
-      else hipLaunchKernelGGL((gemm_wide_kernel<false, 4, 4, 3>), dim3(256), dim3(768), 0, s, a, ntiles, ctr);
+  // one tile ladder for both kernels (a dense call has one class); 8-wave 128 x 128: one pass over A per 128 output columns
+  p.tile = Co <= 16 ? TILE_NARROW : use96 ? TILE_96 : Co > 64 && (long long)cdiv(M, 128) * cdiv(Co, 128) * ncls >= 384 ? TILE_BIG : TILE_DEFAULT;
+  with_tile(p.tile, [&](auto tl) {
+    typedef decltype(tl) TL;
+    const int ntiles = cdiv(M, TL::BM) * cdiv(Co, TL::BN), resident = 256 * (TL::NTHR >= 512 ? 2 : 4);
+    p.q.tile_rows = TL::BM; p.q.tile_cols = TL::BN; p.q.block = TL::NTHR;
+    if (dense && Co > 16) { p.q.path = SV_PATH_DENSE; p.ntiles = ntiles; p.q.grid_x = resident < ntiles ? resident : ntiles; }
+    else { p.q.path = SV_PATH_GATHER; p.q.grid_x = ntiles; p.q.grid_y = ncls; }
+  });
+  return p;
+}
+
+// the one place the gather family is launched: a switch over the plan, no shape condition.  TCONV = transposed gather (the halo kernels then run
+// the data gradient: mirrored taps)
+template <bool TCONV>
+static void launch_gather(const GatherPlan& p, const IGemmArgs& a, int* ctr, hipStream_t s) {
+  const dim3 grid(p.q.grid_x, p.q.grid_y), block(p.q.block);
+  switch (p.q.path) {
+    case SV_PATH_HALO0: case SV_PATH_HALO1: case SV_PATH_HALO2:
+      conv_halo_launch(HaloConvArgs{a.x, a.w, a.y, a.e.stats, a.g.N, a.g.Hi, a.g.Wi, TCONV ? 1 : 0}, p.halo, ctr, s);
       return;
-    }
-    if (dense && Co > 16) {
-      if (use96) SV_LAUNCH_DENSE(Tile96);
-      else if (Co > 64 && (long long)cdiv(M, 128) * cdiv(Co, 128) >= 384) {
-        if (TileBig::NT != 4 || epilogue_in_registers(a)) { SV_LAUNCH_DENSE(TileBig); return; }
-        // rows that are not 16-byte aligned: the gathering kernel below carries both epilogues
-      } else { SV_LAUNCH_DENSE(TileDefault); return; }
-      if (use96) return;
-    }
+    case SV_PATH_HALO_BLOCKED_8X32: case SV_PATH_HALO_BLOCKED_16X16:
+      conv_halo_blocked_launch(a.x, a.w, a.y, a.e.stats, a.g.N, a.g.Hi, a.g.Wi, a.g.Ci, a.g.Co, TCONV ? 1 : 0, p.halo, ctr, s);
+      return;
+    case SV_PATH_WIDE: hipLaunchKernelGGL((gemm_wide_kernel<false, 4, 4, 3>), grid, block, 0, s, a, p.ntiles, ctr); return;
+    case SV_PATH_WIDE_GENERAL: hipLaunchKernelGGL((gemm_wide_kernel<true, 4, 4, 3>), grid, block, 0, s, a, p.ntiles, ctr); return;
+    default: break;
   }
-#undef SV_LAUNCH_DENSE
-  if (Co <= 16) {
-    dim3 grid(cdiv(M, TileNarrow::BM) * cdiv(Co, TileNarrow::BN), ncls);
-    SV_LAUNCH_IG(TileNarrow);
-  } else if (use96) {
-    dim3 grid(cdiv(M, Tile96::BM) * cdiv(Co, Tile96::BN), ncls);
-    SV_LAUNCH_IG(Tile96);
-  } else if (Co > 64 && (long long)cdiv(M, 128) * cdiv(Co, 128) * ncls >= 384) {   // 8-wave 128x128: one pass over A per 128 output columns
-    dim3 grid(cdiv(M, TileBig::BM) * cdiv(Co, TileBig::BN), ncls);
-    SV_LAUNCH_IG(TileBig);
-  } else {
-    dim3 grid(cdiv(M, TileDefault::BM) * cdiv(Co, TileDefault::BN), ncls);
-    SV_LAUNCH_IG(TileDefault);
+  with_tile(p.tile, [&](auto tl) {
+    typedef decltype(tl) TL;
+    if constexpr (!TCONV && TL::BN > 16) {   // the dense kernel is never built for the transposed gather or the 16-column tile
+      if (p.q.path == SV_PATH_DENSE) { hipLaunchKernelGGL((gemm_dense_kernel<TL, __bf16, __bf16, 8>), grid, block, 0, s, a, p.ntiles); return; }
+    }
+    if (p.q.operands == SV_OPERANDS_F32) hipLaunchKernelGGL((igemm_kernel<false, TCONV, TL, float, float, 4>), grid, block, 0, s, a);
+    else if (p.q.operands == SV_OPERANDS_BF16_F32) hipLaunchKernelGGL((igemm_kernel<true, TCONV, TL, float, float, 4>), grid, block, 0, s, a);
+    else if (p.q.vec == 8) hipLaunchKernelGGL((igemm_kernel<true, TCONV, TL, __bf16, __bf16, 8>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((igemm_kernel<true, TCONV, TL, __bf16, __bf16, 4>), grid, block, 0, s, a);
+  });
+}
+
+// arguments of a gather call -> plan -> (query: report it) -> launch; behind sv_conv_gather, sv_tconv_gather and sv_conv_gather_plan
+static int gather_entry(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype, bool transposed,
+                        hipStream_t s, sv_launch_plan* query) {
+  if (int rc = check_common(g, e, in, w, out, act_dtype)) return rc;
+  SV_REQUIRE_ACT(act_dtype);
+  SV_REQUIRE(act_dtype == SV_F32 || math == SV_MATH_BF16, "igemm: bf16 activations require SV_MATH_BF16");
+  IGemmArgs a{};
+  a.x = in; a.w = w; a.y = out; a.g = to_geom(g); a.e = to_epi(e);
+  a.Ktot = g->kd * g->kh * g->kw * g->Ci;
+  long long M = (long long)g->N * g->Do * g->Ho * g->Wo;
+  int ncls = 1;
+  if (transposed) {
+    SV_REQUIRE(g->sd <= 2 && g->sh <= 2 && g->sw <= 2, "tconv_gather: stride > 2 unsupported (%d,%d,%d)", g->sd, g->sh, g->sw);
+    const int O[3] = {g->Do, g->Ho, g->Wo}, S[3] = {g->sd, g->sh, g->sw}, P[3] = {g->pd, g->ph, g->pw}, Kx[3] = {g->kd, g->kh, g->kw};
+    ncls = 0; M = 0;
+    for (int rd = 0; rd < S[0]; ++rd)
+      for (int rh = 0; rh < S[1]; ++rh)
+        for (int rw = 0; rw < S[2]; ++rw) {
+          const int r[3] = {rd, rh, rw};
+          ClassInfo c{};
+          long long m = g->N;
+          for (int ax = 0; ax < 3; ++ax) {
+            c.r[ax] = r[ax];
+            c.T[ax] = r[ax] < Kx[ax] ? (Kx[ax] - r[ax] + S[ax] - 1) / S[ax] : 0;
+            int o0 = ((r[ax] - P[ax]) % S[ax] + S[ax]) % S[ax];
+            c.o0[ax] = o0;
+            c.cnt[ax] = o0 < O[ax] ? (O[ax] - o0 + S[ax] - 1) / S[ax] : 0;
+            c.ib0[ax] = (o0 + P[ax] - r[ax]) / S[ax];
+            m *= c.cnt[ax];
+          }
+          if (m > M) M = m;
+          a.cls[ncls++] = c;
+        }
   }
-#undef SV_LAUNCH_IG
+  GatherPlan p = plan_gather(a, M, ncls, math, act_dtype, transposed, true);
+  if (query) { *query = p.q; return SV_OK; }
+  if (M == 0) return SV_OK;
+  // one counter slot per launch, asked for after planning; none to be had: what the plan is without them
+  int* ctr = p.counters ? gemm_wide_counters() : nullptr;
+  if (p.counters && !ctr) p = plan_gather(a, M, ncls, math, act_dtype, transposed, false);
+  if (transposed) launch_gather<true>(p, a, ctr, s);
+  else launch_gather<false>(p, a, ctr, s);
+  if (p.q.path >= SV_PATH_HALO0) return check_launch(transposed ? "sv_tconv_gather (halo tiles)" : "sv_conv_gather (halo tiles)");
+  return check_launch(transposed ? "sv_tconv_gather" : "sv_conv_gather");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1678,7 +1523,7 @@ static void launch_igemm(const IGemmArgs& a, long long M, int ncls, int math, in
 // 8 rows a 32-lane half reads over all 64 banks.  P = the operand whose columns take the 256-side of the tile (SWAP: X, else dY),
 // Q the other; a workgroup owns one tile and a contiguous range of row slices (workgroups of one row range sit on one XCD: they share
 // the operand rows through its L2) and adds its fp32 tile into dW once, at the end (16 consecutive floats per lane group).
-// Host-side conditions: rows % 64 == 0, 8-aligned columns and row strides, <= 256 tiles (wgrad_wide_ok).
+// Host-side conditions: rows % 64 == 0, 8-aligned columns and row strides, <= 256 tiles (plan_wgrad).
 // ------------------------------------------------------------------------------------------------
 struct WGradWideArgs {
   const __bf16* P; int ldp; int pcols; const __bf16* Q; int ldq; int qcols;
@@ -1830,156 +1675,68 @@ typedef Tile<2, 4, 4, 2> WTileWide;      // 128 x 128, 8 waves
 typedef Tile<2, 4, 2, 2> WTile64;        // 64 x 128, 8 waves: layers with <= 64 anchor channels (half of a 128-row tile would multiply zeros)
 typedef Tile<2, 4, 3, 2> WTile96;        // 96 x 128, 8 waves: anchor channel counts 96 k that are not multiples of 128 (Swin stage 0)
 
-}  // namespace sv
-
-using namespace sv;
-
-extern "C" int sv_conv_gather(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e,
-                              int math, int act_dtype, void* stream) {
-  if (int rc = check_common(g, e, in, w, out, act_dtype)) return rc;
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(act_dtype == SV_F32 || math == SV_MATH_BF16, "igemm: bf16 activations require SV_MATH_BF16");
-  if (try_halo(in, w, out, g, e, math, act_dtype, false, (hipStream_t)stream)) return check_launch("sv_conv_gather (halo tiles)");
-  IGemmArgs a{};
-  a.x = in; a.w = w; a.y = out; a.g = to_geom(g); a.e = to_epi(e);
-  a.Ktot = g->kd * g->kh * g->kw * g->Ci;
-  const long long M = (long long)g->N * g->Do * g->Ho * g->Wo;
-  launch_igemm<false>(a, M, 1, math, act_dtype, (hipStream_t)stream);
-  return check_launch("sv_conv_gather");
+// ---- launch plan of sv_conv_wgrad (pure host function; sv_conv_wgrad_plan reports it).  Order: halo tiles, wide kernel, tiled kernel ----
+enum { WTILE_NARROW, WTILE_64, WTILE_96, WTILE_WIDE, WTILE_DEFAULT };
+struct WGradPlan {
+  sv_launch_plan q;              // path, tile, operand variant, grid, block: what the query reports
+  int tile, rows_per_split;      // tiled kernel: WTILE_*, positions per split (grid = tiles x splits)
+  int ntiles, tiles_p, groups;   // wide kernel: 256 x 128 tiles, of which tiles_p along the 256-side; workgroups per tile
+  HaloPlan halo;                 // halo weight gradient: tile shape, stride, splits
+};
+template <typename F> static void with_wtile(int tile, F&& f) {
+  switch (tile) {
+    case WTILE_NARROW: f(WTileNarrow{}); break;
+    case WTILE_64: f(WTile64{}); break;
+    case WTILE_96: f(WTile96{}); break;
+    case WTILE_WIDE: f(WTileWide{}); break;
+    default: f(WTileDefault{}); break;
+  }
 }
 
-/* 1 when sv_conv_gather would run this call on the wide (256 x 128, LDS-DMA ring) kernel, 0 for the 128-wide kernels; tests use it
- * to make sure they exercise the path they mean to. */
-extern "C" int sv_conv_gather_is_wide(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype) {
-  if (!g || !e || math != SV_MATH_BF16 || act_dtype != SV_BF16) return 0;
-  IGemmArgs a{};
-  a.x = in; a.w = w; a.y = out; a.g = to_geom(g); a.e = to_epi(e);
-  a.Ktot = g->kd * g->kh * g->kw * g->Ci;
-  const bool v8 = (a.g.Ci % 8) == 0 && (a.g.ldi % 8) == 0 && ((uintptr_t)a.x & 15) == 0;
-  const bool dense = v8 && a.g.kd * a.g.kh * a.g.kw == 1 && a.g.sd == 1 && a.g.sh == 1 && a.g.sw == 1 &&
-                     a.g.pd == 0 && a.g.ph == 0 && a.g.pw == 0 && a.g.Di == a.g.Do && a.g.Hi == a.g.Ho && a.g.Wi == a.g.Wo;
-  return dense && gemm_wide_ok(a, (long long)g->N * g->Do * g->Ho * g->Wo) ? 1 : 0;
-}
-
-extern "C" int sv_tconv_gather(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e,
-                               int math, int act_dtype, void* stream) {
-  if (int rc = check_common(g, e, in, w, out, act_dtype)) return rc;
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(act_dtype == SV_F32 || math == SV_MATH_BF16, "igemm: bf16 activations require SV_MATH_BF16");
-  SV_REQUIRE(g->sd <= 2 && g->sh <= 2 && g->sw <= 2, "tconv_gather: stride > 2 unsupported (%d,%d,%d)", g->sd, g->sh, g->sw);
-  if (try_halo(in, w, out, g, e, math, act_dtype, true, (hipStream_t)stream)) return check_launch("sv_tconv_gather (halo tiles)");
-  IGemmArgs a{};
-  a.x = in; a.w = w; a.y = out; a.g = to_geom(g); a.e = to_epi(e);
-  a.Ktot = g->kd * g->kh * g->kw * g->Ci;
-  const int O[3] = {g->Do, g->Ho, g->Wo}, S[3] = {g->sd, g->sh, g->sw}, P[3] = {g->pd, g->ph, g->pw}, Kx[3] = {g->kd, g->kh, g->kw};
-  int ncls = 0;
-  long long maxM = 0;
-  for (int rd = 0; rd < S[0]; ++rd)
-    for (int rh = 0; rh < S[1]; ++rh)
-      for (int rw = 0; rw < S[2]; ++rw) {
-        const int r[3] = {rd, rh, rw};
-        ClassInfo c{};
-        long long m = g->N;
-        for (int ax = 0; ax < 3; ++ax) {
-          c.r[ax] = r[ax];
-          c.T[ax] = r[ax] < Kx[ax] ? (Kx[ax] - r[ax] + S[ax] - 1) / S[ax] : 0;
-          int o0 = ((r[ax] - P[ax]) % S[ax] + S[ax]) % S[ax];
-          c.o0[ax] = o0;
-          c.cnt[ax] = o0 < O[ax] ? (O[ax] - o0 + S[ax] - 1) / S[ax] : 0;
-          c.ib0[ax] = (o0 + P[ax] - r[ax]) / S[ax];
-          m *= c.cnt[ax];
-        }
-        if (m > maxM) maxM = m;
-        a.cls[ncls++] = c;
-      }
-  if (maxM == 0) return SV_OK;
-  launch_igemm<true>(a, maxM, ncls, math, act_dtype, (hipStream_t)stream);
-  return check_launch("sv_tconv_gather");
-}
-
-extern "C" size_t sv_conv_wgrad_workspace_floats(const sv_geom* g) {
-  const int taps = g->kd * g->kh * g->kw;
-  return taps == 1 ? 0 : (size_t)g->Co * taps * g->Ci;
-}
-
-// dense layers with bf16 storage take the wide weight-gradient kernel (SV_WGRAD_WIDE=0 in the environment keeps the 128-wide one)
-static bool wgrad_wide_ok(const void* anchor, int lda, const void* gathered, const sv_geom* g, int cg_valid, int math, int act) {
-  static const int wide_on = [] { const char* v = getenv("SV_WGRAD_WIDE"); return v ? atoi(v) : 1; }();
+static WGradPlan plan_wgrad(const void* anchor, int lda, const void* gathered, const sv_geom* g, int cg_valid, int math, int act) {
+  WGradPlan p{};
   const long long Mll = (long long)g->N * g->Do * g->Ho * g->Wo;
+  const int Kout = g->kd * g->kh * g->kw * g->Ci;
+  const bool bf = math == SV_MATH_BF16, bf16 = bf && act == SV_BF16, aligned16 = (((uintptr_t)anchor | (uintptr_t)gathered) & 15) == 0;
+  p.q.operands = !bf ? SV_OPERANDS_F32 : act != SV_BF16 ? SV_OPERANDS_BF16_F32 : SV_OPERANDS_BF16;
+  p.q.vec = 8; p.q.grid_y = 1;
+  // 3 x 3 / stride 1 or 2 / padding 1 with 64 k channels on both sides and bf16 storage: the halo-tile weight gradient (conv_halo.hip) fills the
+  // packed workspace
+  if (bf16 && g->kd == 1 && g->kh == 3 && g->kw == 3 && g->sd == 1 && g->sh == g->sw && g->pd == 0 && g->ph == 1 && g->pw == 1 && g->Di == 1 &&
+      g->Do == 1 && cg_valid == g->Ci && lda == g->Co && g->ldi == g->Ci && aligned16 &&
+      (p.halo = conv_halo_wgrad_plan(g->N, g->Hi, g->Wi, g->Ho, g->Wo, g->sh, g->Ci, g->Co)).kind >= 0) {
+    p.q.path = SV_PATH_WGRAD_HALO; p.q.tile_rows = p.halo.th; p.q.tile_cols = p.halo.tw; p.q.grid_x = p.halo.grid; p.q.block = 256;
+    return p;
+  }
+  // dense layers with bf16 storage take the wide weight-gradient kernel (SV_WGRAD_WIDE=0 in the environment keeps the 128-wide one)
+  static const int wide_on = [] { const char* v = getenv("SV_WGRAD_WIDE"); return v ? atoi(v) : 1; }();
   const bool same_rows = g->kd * g->kh * g->kw == 1 && g->sd == 1 && g->sh == 1 && g->sw == 1 && g->pd == 0 && g->ph == 0 && g->pw == 0 &&
                          g->Di == g->Do && g->Hi == g->Ho && g->Wi == g->Wo;
-  return wide_on && same_rows && act == SV_BF16 && math == SV_MATH_BF16 && cg_valid == g->Ci && Mll % 64 == 0 && Mll >= 16384 &&
-         g->Co >= 128 && g->Ci >= 128 && ((g->Co | g->Ci | lda | g->ldi) & 7) == 0 && (((uintptr_t)anchor | (uintptr_t)gathered) & 15) == 0 &&
-         (long long)cdiv(g->Co, 128) * cdiv(g->Ci, 128) <= 512;
-}
-/* 1 when sv_conv_wgrad would run this call on the wide kernel (tests) */
-extern "C" int sv_conv_wgrad_is_wide(const void* anchor, int lda, const void* gathered, const sv_geom* g, int cg_valid, int math, int act_dtype) {
-  return g && wgrad_wide_ok(anchor, lda, gathered, g, cg_valid, math, act_dtype) ? 1 : 0;
-}
-
-extern "C" int sv_conv_wgrad(const void* anchor, int lda, const void* gathered, float* dw, const sv_geom* g, int cg_valid,
-                             float* workspace, float* dbias, int math, int act_dtype, void* stream) {
-  SV_REQUIRE(anchor && gathered && dw && g, "wgrad: null argument");
-  SV_REQUIRE_ACT(act_dtype);
-  SV_REQUIRE(act_dtype == SV_F32 || math == SV_MATH_BF16, "wgrad: bf16 activations require SV_MATH_BF16");
-  const int act = act_dtype;
-  SV_REQUIRE(lda >= g->Co && g->ldi >= g->Ci && cg_valid > 0 && cg_valid <= g->Ci, "wgrad: bad strides (lda=%d Co=%d ldi=%d Ci=%d cg_valid=%d)",
-             lda, g->Co, g->ldi, g->Ci, cg_valid);
-  SV_REQUIRE((((uintptr_t)anchor | (uintptr_t)gathered) & (act_dtype == SV_BF16 ? 7 : 15)) == 0, "wgrad: operands must be aligned to 4 elements");
-  const long long Mll = (long long)g->N * g->Do * g->Ho * g->Wo;
-  SV_REQUIRE(Mll > 0 && Mll < (1ll << 31), "wgrad: row count out of range");
-  const int taps = g->kd * g->kh * g->kw;
-  const int Kout = taps * g->Ci;
-  SV_REQUIRE(taps == 1 || workspace, "wgrad: a workspace of sv_conv_wgrad_workspace_floats() floats is required when taps > 1");
-  hipStream_t s = (hipStream_t)stream;
-  WGradArgs a{};
-  a.anchor = anchor; a.lda = lda; a.gathered = gathered; a.g = to_geom(g); a.cg_valid = cg_valid;
-  a.Mrows = (int)Mll;
-  a.direct = taps == 1;
-  a.dbias = dbias;
-  a.out = a.direct ? dw : workspace;
-  if (!a.direct) (void)hipMemsetAsync(workspace, 0, sizeof(float) * (size_t)g->Co * Kout, s);
-  // 3 x 3 / stride 1 or 2 / padding 1 with 64 k channels on both sides and bf16 storage: the halo-tile weight gradient (conv_halo.hip) fills the
-  // packed workspace; the unpack below is shared
-  if (!a.direct && math == SV_MATH_BF16 && act == SV_BF16 && g->kd == 1 && g->kh == 3 && g->kw == 3 && g->sd == 1 && g->sh == g->sw &&
-      g->pd == 0 && g->ph == 1 && g->pw == 1 && g->Di == 1 && g->Do == 1 && cg_valid == g->Ci && lda == g->Co &&
-      g->ldi == g->Ci && (((uintptr_t)anchor | (uintptr_t)gathered) & 15) == 0 &&
-      conv_halo_wgrad_launch(gathered, anchor, workspace, dbias, g->N, g->Hi, g->Wi, g->Ho, g->Wo, g->sh, g->Ci, g->Co, s)) {
-    const long long total = (long long)g->Co * cg_valid * taps;
-    int blocks = cdiv(total, 256); if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(wgrad_unpack_kernel, dim3(blocks), dim3(256), 0, s, workspace, dw, g->Co, g->Ci, cg_valid, taps);
-    return check_launch("sv_conv_wgrad (halo tiles)");
-  }
-  {
-    if (wgrad_wide_ok(anchor, lda, gathered, g, cg_valid, math, act)) {
-      // the 256-side of the tile goes to the operand it wastes less on (dY columns = Co, X columns = Ci)
-      const long long w0 = (long long)cdiv(g->Co, 256) * 256 * cdiv(g->Ci, 128) * 128, w1 = (long long)cdiv(g->Ci, 256) * 256 * cdiv(g->Co, 128) * 128;
-      const bool swap = w1 < w0;
-      const int pcols = swap ? g->Ci : g->Co, qcols = swap ? g->Co : g->Ci;
-      const int tiles_p = cdiv(pcols, 256), ntiles = tiles_p * cdiv(qcols, 128);
-      if (ntiles <= 256) {
-        WGradWideArgs wa{};
-        wa.P = static_cast<const __bf16*>(swap ? gathered : anchor); wa.ldp = swap ? g->ldi : lda; wa.pcols = pcols;
-        wa.Q = static_cast<const __bf16*>(swap ? anchor : gathered); wa.ldq = swap ? lda : g->ldi; wa.qcols = qcols;
-        wa.dw = dw; wa.ld_dw = g->Ci; wa.nslices = (int)(Mll / 64); wa.ntiles = ntiles; wa.tiles_p = tiles_p;
-        wa.dbias = dbias;
-        wa.groups = 256 / ntiles;
-        if (wa.groups > wa.nslices) wa.groups = wa.nslices;
-        if (swap) hipLaunchKernelGGL(wgrad_wide_kernel<true>, dim3(ntiles * wa.groups), dim3(GW_NTHR), 0, s, wa);
-        else hipLaunchKernelGGL(wgrad_wide_kernel<false>, dim3(ntiles * wa.groups), dim3(GW_NTHR), 0, s, wa);
-        return check_launch("sv_conv_wgrad");
-      }
+  if (wide_on && same_rows && bf16 && cg_valid == g->Ci && Mll % 64 == 0 && Mll >= 16384 && g->Co >= 128 && g->Ci >= 128 &&
+      ((g->Co | g->Ci | lda | g->ldi) & 7) == 0 && aligned16) {
+    // the 256-side of the tile goes to the operand it wastes less on (dY columns = Co, X columns = Ci)
+    const long long w0 = (long long)cdiv(g->Co, 256) * 256 * cdiv(g->Ci, 128) * 128, w1 = (long long)cdiv(g->Ci, 256) * 256 * cdiv(g->Co, 128) * 128;
+    const bool swap = w1 < w0;
+    const int tiles_p = cdiv(swap ? g->Ci : g->Co, 256);
+    const long long ntiles = (long long)tiles_p * cdiv(swap ? g->Co : g->Ci, 128);
+    if (ntiles <= 256) {   // one workgroup per CU owns a tile (this also bounds the 128 x 128 blocks of dW by 512, the earlier pre-check)
+      p.ntiles = (int)ntiles; p.tiles_p = tiles_p;
+      p.groups = 256 / p.ntiles;
+      if (p.groups > Mll / 64) p.groups = (int)(Mll / 64);
+      p.q.path = swap ? SV_PATH_WGRAD_WIDE_SWAP : SV_PATH_WGRAD_WIDE;
+      p.q.tile_rows = 256; p.q.tile_cols = GW_BN; p.q.grid_x = p.ntiles * p.groups; p.q.block = GW_NTHR;
+      return p;
     }
   }
   const bool narrow = g->Co <= 16;
   const bool wide = !narrow && Kout >= 128;      // 128 x 128 tile: the anchor operand is re-read once per 128 (tap, channel) columns
   static const int tile64_on = [] { const char* v = getenv("SV_WGRAD_TILE64"); return v ? atoi(v) : 1; }();
-  const bool t64 = tile64_on && !narrow && wide && g->Co <= 64;
-  const bool t96 = tile64_on && !narrow && wide && !t64 && g->Co % 96 == 0 && g->Co % 128 != 0;
-  const int BMw = narrow ? WTileNarrow::BM : (t64 ? WTile64::BM : (t96 ? WTile96::BM : WTileDefault::BM));
-  const int BNw = narrow ? WTileNarrow::BN : (wide ? WTileWide::BN : WTileDefault::BN);
-  const int BKs = math == SV_MATH_BF16 ? 64 : 32;
-  const int tiles = cdiv(g->Co, BMw) * cdiv(Kout, BNw);
+  const bool t64 = tile64_on && wide && g->Co <= 64;
+  const bool t96 = tile64_on && wide && !t64 && g->Co % 96 == 0 && g->Co % 128 != 0;
+  p.tile = narrow ? WTILE_NARROW : t64 ? WTILE_64 : t96 ? WTILE_96 : wide ? WTILE_WIDE : WTILE_DEFAULT;
+  with_wtile(p.tile, [&](auto tl) { typedef decltype(tl) TL; p.q.tile_rows = TL::BM; p.q.tile_cols = TL::BN; p.q.block = TL::NTHR; });
+  const int BKs = bf ? 64 : 32;
+  const int tiles = cdiv(g->Co, p.q.tile_rows) * cdiv(Kout, p.q.tile_cols);
   // at most ONE wave of workgroups (2 resident per CU x 256 CUs = 512 slots) and >= 8 K-steps per split.  Every workgroup
   // does the same amount of work, so tiles * splits must not exceed the slots: rounding the split count UP (e.g. 36 tiles
   // x 15 = 540) leaves a 28-workgroup second wave that costs as much as the first (measured: 173 -> ~90 us for 384x1536 over
@@ -1993,32 +1750,109 @@ extern "C" int sv_conv_wgrad(const void* anchor, int lda, const void* gathered, 
   long long rps = (Mll + splits - 1) / splits;
   rps = (rps + BKs - 1) / BKs * BKs;
   splits = (Mll + rps - 1) / rps;
-  a.rows_per_split = (int)rps;
-  dim3 grid((unsigned)(cdiv(g->Co, BMw) * cdiv(Kout, BNw) * splits));
-  const bool bf = math == SV_MATH_BF16;
+  p.rows_per_split = (int)rps;
   // 16-byte operand chunks with bf16 storage when every row start and channel count allows it (Co % 8 keeps the edge
   // chunk of the anchor whole; otherwise the 4-element variant with its scalar edge path is used)
-  const bool v8 = act == SV_BF16 && (lda % 8) == 0 && (g->Co % 8) == 0 && (g->Ci % 8) == 0 && (g->ldi % 8) == 0 &&
-                  (((uintptr_t)anchor | (uintptr_t)gathered) & 15) == 0;
-#define SV_LAUNCH_WG(TL)                                                                                               \
-  do {                                                                                                                 \
-    if (!bf) hipLaunchKernelGGL((wgrad_kernel<false, TL, float, 4>), grid, dim3(TL::NTHR), 0, s, a);                    \
-    else if (act != SV_BF16) hipLaunchKernelGGL((wgrad_kernel<true, TL, float, 4>), grid, dim3(TL::NTHR), 0, s, a);     \
-    else if (v8) hipLaunchKernelGGL((wgrad_kernel<true, TL, __bf16, 8>), grid, dim3(TL::NTHR), 0, s, a);               \
-    else hipLaunchKernelGGL((wgrad_kernel<true, TL, __bf16, 4>), grid, dim3(TL::NTHR), 0, s, a);                       \
-  } while (0)
-  if (narrow) SV_LAUNCH_WG(WTileNarrow);
-  else if (t64) SV_LAUNCH_WG(WTile64);
-  else if (t96) SV_LAUNCH_WG(WTile96);
-  else if (wide) SV_LAUNCH_WG(WTileWide);
-  else SV_LAUNCH_WG(WTileDefault);
-#undef SV_LAUNCH_WG
-  if (!a.direct) {
+  const bool v8 = act == SV_BF16 && (lda % 8) == 0 && (g->Co % 8) == 0 && (g->Ci % 8) == 0 && (g->ldi % 8) == 0 && aligned16;
+  p.q.path = SV_PATH_WGRAD_TILED; p.q.vec = v8 ? 8 : 4; p.q.grid_x = (int)(unsigned)(tiles * splits);
+  return p;
+}
+
+// arguments of a weight-gradient call -> plan -> (query: report it) -> launch; behind sv_conv_wgrad and sv_conv_wgrad_plan
+static int wgrad_entry(const void* anchor, int lda, const void* gathered, float* dw, const sv_geom* g, int cg_valid, float* workspace, float* dbias,
+                       int math, int act, hipStream_t s, sv_launch_plan* query) {
+  SV_REQUIRE(anchor && gathered && g && (dw || query), "wgrad: null argument");
+  SV_REQUIRE_ACT(act);
+  SV_REQUIRE(act == SV_F32 || math == SV_MATH_BF16, "wgrad: bf16 activations require SV_MATH_BF16");
+  SV_REQUIRE(lda >= g->Co && g->ldi >= g->Ci && cg_valid > 0 && cg_valid <= g->Ci, "wgrad: bad strides (lda=%d Co=%d ldi=%d Ci=%d cg_valid=%d)",
+             lda, g->Co, g->ldi, g->Ci, cg_valid);
+  SV_REQUIRE((((uintptr_t)anchor | (uintptr_t)gathered) & (act == SV_BF16 ? 7 : 15)) == 0, "wgrad: operands must be aligned to 4 elements");
+  const long long Mll = (long long)g->N * g->Do * g->Ho * g->Wo;
+  SV_REQUIRE(Mll > 0 && Mll < (1ll << 31), "wgrad: row count out of range");
+  const int taps = g->kd * g->kh * g->kw;
+  const WGradPlan p = plan_wgrad(anchor, lda, gathered, g, cg_valid, math, act);
+  if (query) { *query = p.q; return SV_OK; }
+  SV_REQUIRE(taps == 1 || workspace, "wgrad: a workspace of sv_conv_wgrad_workspace_floats() floats is required when taps > 1");
+  WGradArgs a{};
+  a.anchor = anchor; a.lda = lda; a.gathered = gathered; a.g = to_geom(g); a.cg_valid = cg_valid;
+  a.Mrows = (int)Mll;
+  a.direct = taps == 1;
+  a.dbias = dbias;
+  a.out = a.direct ? dw : workspace;
+  a.rows_per_split = p.rows_per_split;
+  if (!a.direct) (void)hipMemsetAsync(workspace, 0, sizeof(float) * (size_t)g->Co * taps * g->Ci, s);
+  const dim3 grid(p.q.grid_x), block(p.q.block);
+  switch (p.q.path) {
+    case SV_PATH_WGRAD_HALO:
+      conv_halo_wgrad_launch(gathered, anchor, workspace, dbias, g->N, g->Hi, g->Wi, g->Ho, g->Wo, g->Ci, g->Co, p.halo, s);
+      break;
+    case SV_PATH_WGRAD_WIDE: case SV_PATH_WGRAD_WIDE_SWAP: {
+      const bool swap = p.q.path == SV_PATH_WGRAD_WIDE_SWAP;
+      WGradWideArgs wa{};
+      wa.P = static_cast<const __bf16*>(swap ? gathered : anchor); wa.ldp = swap ? g->ldi : lda; wa.pcols = swap ? g->Ci : g->Co;
+      wa.Q = static_cast<const __bf16*>(swap ? anchor : gathered); wa.ldq = swap ? lda : g->ldi; wa.qcols = swap ? g->Co : g->Ci;
+      wa.dw = dw; wa.ld_dw = g->Ci; wa.nslices = (int)(Mll / 64); wa.ntiles = p.ntiles; wa.tiles_p = p.tiles_p; wa.groups = p.groups;
+      wa.dbias = dbias;
+      if (swap) hipLaunchKernelGGL(wgrad_wide_kernel<true>, grid, block, 0, s, wa);
+      else hipLaunchKernelGGL(wgrad_wide_kernel<false>, grid, block, 0, s, wa);
+      break;
+    }
+    default:
+      with_wtile(p.tile, [&](auto tl) {
+        typedef decltype(tl) TL;
+        if (p.q.operands == SV_OPERANDS_F32) hipLaunchKernelGGL((wgrad_kernel<false, TL, float, 4>), grid, block, 0, s, a);
+        else if (p.q.operands == SV_OPERANDS_BF16_F32) hipLaunchKernelGGL((wgrad_kernel<true, TL, float, 4>), grid, block, 0, s, a);
+        else if (p.q.vec == 8) hipLaunchKernelGGL((wgrad_kernel<true, TL, __bf16, 8>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((wgrad_kernel<true, TL, __bf16, 4>), grid, block, 0, s, a);
+      });
+  }
+  if (!a.direct) {   // the packed workspace of the halo and the tiled kernel -> dw
     const long long total = (long long)g->Co * cg_valid * taps;
     int blocks = cdiv(total, 256); if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(wgrad_unpack_kernel, dim3(blocks), dim3(256), 0, s, workspace, dw, g->Co, g->Ci, cg_valid, taps);
   }
-  return check_launch("sv_conv_wgrad");
+  return check_launch(p.q.path == SV_PATH_WGRAD_HALO ? "sv_conv_wgrad (halo tiles)" : "sv_conv_wgrad");
+}
+
+}  // namespace sv
+
+using namespace sv;
+
+extern "C" int sv_conv_gather(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e,
+                              int math, int act_dtype, void* stream) {
+  return gather_entry(in, w, out, g, e, math, act_dtype, false, (hipStream_t)stream, nullptr);
+}
+extern "C" int sv_tconv_gather(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e,
+                               int math, int act_dtype, void* stream) {
+  return gather_entry(in, w, out, g, e, math, act_dtype, true, (hipStream_t)stream, nullptr);
+}
+extern "C" int sv_conv_gather_plan(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype,
+                                   int transposed, sv_launch_plan* plan) {
+  SV_REQUIRE(plan, "conv_gather_plan: null plan");
+  return gather_entry(in, w, out, g, e, math, act_dtype, transposed != 0, nullptr, plan);
+}
+extern "C" int sv_conv_gather_is_wide(const void* in, const void* w, void* out, const sv_geom* g, const sv_epilogue* e, int math, int act_dtype) {
+  sv_launch_plan q;
+  return sv_conv_gather_plan(in, w, out, g, e, math, act_dtype, 0, &q) == SV_OK && (q.path == SV_PATH_WIDE || q.path == SV_PATH_WIDE_GENERAL);
+}
+
+extern "C" size_t sv_conv_wgrad_workspace_floats(const sv_geom* g) {
+  const int taps = g->kd * g->kh * g->kw;
+  return taps == 1 ? 0 : (size_t)g->Co * taps * g->Ci;
+}
+extern "C" int sv_conv_wgrad(const void* anchor, int lda, const void* gathered, float* dw, const sv_geom* g, int cg_valid,
+                             float* workspace, float* dbias, int math, int act_dtype, void* stream) {
+  return wgrad_entry(anchor, lda, gathered, dw, g, cg_valid, workspace, dbias, math, act_dtype, (hipStream_t)stream, nullptr);
+}
+extern "C" int sv_conv_wgrad_plan(const void* anchor, int lda, const void* gathered, const sv_geom* g, int cg_valid, int math, int act_dtype,
+                                  sv_launch_plan* plan) {
+  SV_REQUIRE(plan, "conv_wgrad_plan: null plan");
+  return wgrad_entry(anchor, lda, gathered, nullptr, g, cg_valid, nullptr, nullptr, math, act_dtype, nullptr, plan);
+}
+extern "C" int sv_conv_wgrad_is_wide(const void* anchor, int lda, const void* gathered, const sv_geom* g, int cg_valid, int math, int act_dtype) {
+  sv_launch_plan q;
+  return sv_conv_wgrad_plan(anchor, lda, gathered, g, cg_valid, math, act_dtype, &q) == SV_OK &&
+         (q.path == SV_PATH_WGRAD_WIDE || q.path == SV_PATH_WGRAD_WIDE_SWAP);
 }
 
 extern "C" int sv_pack_weight(const float* src, void* dst, int A, int B, int T, int swap, int pad_to, int out_dtype, void* stream) {

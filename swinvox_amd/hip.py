@@ -33,6 +33,16 @@ class Epilogue(C.Structure):
                 ("col_off", C.c_int)]
 
 
+class LaunchPlan(C.Structure):   # sv_launch_plan: what sv_conv_gather_plan / sv_conv_wgrad_plan report
+    _fields_ = [(n, C.c_int) for n in ("path", "tile_rows", "tile_cols", "operands", "vec", "grid_x", "grid_y", "block")]
+
+
+# SV_PATH_* / SV_OPERANDS_* of a LaunchPlan
+(PATH_GATHER, PATH_DENSE, PATH_WIDE, PATH_WIDE_GENERAL, PATH_HALO0, PATH_HALO1, PATH_HALO2, PATH_HALO_BLOCKED_8X32, PATH_HALO_BLOCKED_16X16,
+ PATH_WGRAD_TILED, PATH_WGRAD_WIDE, PATH_WGRAD_WIDE_SWAP, PATH_WGRAD_HALO) = range(13)
+OPERANDS_F32, OPERANDS_BF16_F32, OPERANDS_BF16 = 0, 1, 2
+
+
 class PackDesc(C.Structure):   # sv_pack_desc
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("A", C.c_int), ("B", C.c_int), ("T", C.c_int), ("swap", C.c_int),
                 ("rows_out", C.c_int), ("inner_out", C.c_int), ("block0", C.c_int), ("reserved", C.c_int)]
@@ -62,7 +72,9 @@ _PROTOS = {
     "sv_version": (_I, None),
     "sv_conv_gather": (_I, [_P, _P, _P, C.POINTER(Geom), C.POINTER(Epilogue), _I]),
     "sv_tconv_gather": (_I, [_P, _P, _P, C.POINTER(Geom), C.POINTER(Epilogue), _I]),
+    "sv_conv_gather_plan": (_I, None, [_P, _P, _P, C.POINTER(Geom), C.POINTER(Epilogue), _I, _I, _I, C.POINTER(LaunchPlan)]),
     "sv_conv_gather_is_wide": (_I, None, [_P, _P, _P, C.POINTER(Geom), C.POINTER(Epilogue), _I, _I]),
+    "sv_conv_wgrad_plan": (_I, None, [_P, _I, _P, C.POINTER(Geom), _I, _I, _I, C.POINTER(LaunchPlan)]),
     "sv_conv_wgrad_is_wide": (_I, None, [_P, _I, _P, C.POINTER(Geom), _I, _I, _I]),
     "sv_conv_wgrad_workspace_floats": (C.c_size_t, None, [C.POINTER(Geom)]),
     "sv_conv_wgrad": (_I, [_P, _I, _P, _P, C.POINTER(Geom), _I, _P, _P, _I]),

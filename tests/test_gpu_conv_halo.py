@@ -216,3 +216,31 @@ def test_conv3x3_blocked_forward_statistics_and_data_gradient(dev, bf16_mode, n,
     edx, _ = _run(sp, 0, dgrad)
     assert rel(out, eout) < 8e-3 and float((out.float() - eout.float()).abs().mean() / eout.float().abs().mean()) < 5e-4
     assert rel(dx, edx) < 8e-3 and float((dx.float() - edx.float()).abs().mean() / edx.float().abs().mean()) < 5e-4
+
+
+def test_plan_and_launch_agree_on_the_halo_route(dev, bf16_mode):
+    """sv_conv_gather_plan and the launch take the route from the same host function: one 8 x 32 image (one tile) runs the resident-weights halo
+    kernel under mode 2 and the gather engine under mode 1, and the plan names that path before each launch."""
+    import ctypes as C
+    n, H, W = 1, 8, 32
+    g = torch.Generator().manual_seed(832)
+    x = torch.randn(n, 64, H, W, generator=g).bfloat16().float()
+    w = (torch.randn(64, 64, 3, 3, generator=g) / math.sqrt(576)).bfloat16().float()
+    y = F.conv2d(x, w, None, stride=1, padding=1)
+    sp = ConvSpec.conv2d(64, 64, 3, 1, 1)
+    xd, wf = cl(x).to(dev).bfloat16(), ops.pack_one(sp, w.to(dev), "f")
+    out = ops.empty(n * H * W, 64, device=dev)
+    gm, e = sp._geom(n, (1, H, W), (1, H, W), 64, 64, 64), ops._epilogue(64)
+
+    def planned():
+        q = hip.LaunchPlan()
+        assert hip.load().sv_conv_gather_plan(ops.ptr(xd), ops.ptr(wf), ops.ptr(out), C.byref(gm), C.byref(e), hip.MATH_BF16, hip.BF16, 0, C.byref(q)) == 0
+        return q.path
+
+    for mode, took_want, path_want in ((2, 1, hip.PATH_HALO0), (1, 0, hip.PATH_GATHER)):
+        out.zero_()
+        ops.set_conv_halo(mode)
+        assert planned() == path_want
+        _, took = _run(sp, mode, lambda: sp.forward(xd, n, (1, H, W), wf, out))
+        assert took == took_want
+        assert rel(out, cl(y)) < 6e-3
