@@ -8,6 +8,7 @@ clip_grad_norm_ and checkpoints behave exactly as with the reference modules.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Sequence
 
 import torch
@@ -161,6 +162,12 @@ class HipModule(nn.Module):
         return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
 
 
+# What one ConvBnAct forward keeps for its backward.  z, ldz: the activation, only where the backward's mask needs it (a residual was added);
+# otherwise None and the mask is recomputed from y (scale * y + shift > 0).  idx: the arg-max bytes of the pool form.  w: the weight a sub-class
+# ran the step on in place of conv.weight.  Forms that do not store an entry leave it None.
+LayerTape = ops.named_tape("LayerTape", "x ldi y st n in_grid M og z ldz idx w")
+
+
 class ConvBnAct:
     """Conv/ConvTranspose (+bias) -> BatchNorm (train: batch statistics gathered in the contraction's epilogue)
     -> activation, on channels-last data; forward and backward."""
@@ -168,46 +175,39 @@ class ConvBnAct:
     def __init__(self, conv: nn.Module, bn: nn.Module, spec: ConvSpec, act: int, slope: float = 0.0):
         self.conv, self.bn, self.spec, self.act, self.slope = conv, bn, spec, act, slope
 
+    def forward_stats(self, x, n, in_grid, training, *, ldi=None, w=None):
+        """The step every form starts with: convolution with the statistics in its epilogue, then finalize; the normalisation pass is the
+        caller's (forward, forward_pool, ops.bn_dual_apply).  w: the forward pack, where it is not self._pack("f").
+        The tape is what backward_conv takes."""
+        sp = self.spec
+        og = sp.out_grid(in_grid)
+        M = n * og[0] * og[1] * og[2]
+        y = empty(M, sp.cout, like=x)
+        st = BatchNormState(self.bn, M, training)
+        sp.forward(x, n, in_grid, self._pack("f") if w is None else w, y, ldi=ldi, bias=self.conv.bias, stats=st.sums)
+        st.finalize()
+        return LayerTape(x, ldi, y, st, n, in_grid, M, og, None, None, None, None)
+
     def forward(self, x, n, in_grid, training, *, ldi=None, z=None, ldz=None, residual=None, ldr=0):
-        sp = self.spec
-        og = sp.out_grid(in_grid)
-        M = n * og[0] * og[1] * og[2]
-        wf = self._pack("f")
-        y = empty(M, sp.cout, like=x)
-        st = BatchNormState(self.bn, M, training)
-        sp.forward(x, n, in_grid, wf, y, ldi=ldi, bias=self.conv.bias, stats=st.sums)
-        st.finalize()
+        """-> (z, og, tape)"""
+        t = self.forward_stats(x, n, in_grid, training, ldi=ldi)
+        C = self.spec.cout
         if z is None:
-            z, ldz = empty(M, sp.cout, like=x), sp.cout
-        st.apply(y, sp.cout, z, ldz, self.act, self.slope, residual, ldr)
-        # without a residual the backward recomputes the activation mask from y (scale*y + shift > 0) and never reads z
-        return z, og, (x, ldi, y, z if residual is not None else None, ldz, st, n, in_grid, M)
+            z, ldz = empty(t.M, C, like=x), C
+        t.st.apply(t.y, C, z, ldz, self.act, self.slope, residual, ldr)
+        return z, t.og, t._replace(z=z if residual is not None else None, ldz=ldz)
 
-    def forward_stats(self, x, n, in_grid, training, *, ldi=None):
-        """Convolution + finalized statistics without the normalisation pass (the caller applies it: ops.bn_dual_apply).
-        -> (y, og, st, ctx); ctx is what backward_conv takes."""
+    def backward(self, t, dz, lddz, grads, *, need_dx=True, dres=None, lddres=0, dx=None, lddx=None, dx_epi=None):
         sp = self.spec
-        og = sp.out_grid(in_grid)
-        M = n * og[0] * og[1] * og[2]
-        y = empty(M, sp.cout, like=x)
-        st = BatchNormState(self.bn, M, training)
-        sp.forward(x, n, in_grid, self._pack("f"), y, ldi=ldi, bias=self.conv.bias, stats=st.sums)
-        st.finalize()
-        return y, og, st, (x, ldi, y, None, sp.cout, st, n, in_grid, M)
+        dy = (zeros if sp.cout_mem != sp.cout else empty)(t.M, sp.cout_mem, like=dz)
+        t.st.backward(dz, lddz, t.z, t.ldz, t.y, sp.cout, dy, sp.cout_mem, grads[self.bn.weight], grads[self.bn.bias], self.act, self.slope,
+                      dres, lddres)
+        return self.backward_conv(t, dy, grads, need_dx=need_dx, dx=dx, lddx=lddx, dx_epi=dx_epi)
 
-    def backward(self, ctx, dz, lddz, grads, *, need_dx=True, dres=None, lddres=0, dx=None, lddx=None, dx_epi=None):
-        x, ldi, y, z, ldz, st, n, in_grid, M = ctx
-        sp = self.spec
-        dy = (zeros if sp.cout_mem != sp.cout else empty)(M, sp.cout_mem, like=dz)
-        st.backward(dz, lddz, z, ldz, y, sp.cout, dy, sp.cout_mem, grads[self.bn.weight], grads[self.bn.bias], self.act, self.slope,
-                    dres, lddres)
-        return self.backward_conv(ctx, dy, grads, need_dx=need_dx, dx=dx, lddx=lddx, dx_epi=dx_epi)
-
-    def backward_conv(self, ctx, dy, grads, *, need_dx=True, dx=None, lddx=None, dx_epi=None):
+    def backward_conv(self, t, dy, grads, *, need_dx=True, dx=None, lddx=None, dx_epi=None):
         """The convolution's backward from dy [M, cout_mem], the gradient of its own output (the BatchNorm backward already done)."""
-        x, ldi, y, z, ldz, st, n, in_grid, M = ctx
-        sp = self.spec
-        sp.wgrad(dy, x, n, in_grid, self._dw(grads), lddy=sp.cout_mem, ldx=ldi,
+        sp, n, in_grid = self.spec, t.n, t.in_grid
+        sp.wgrad(dy, t.x, n, in_grid, self._dw(grads), lddy=sp.cout_mem, ldx=t.ldi,
                  db=grads[self.conv.bias] if self.conv.bias is not None else None)
         if not need_dx:
             return None
@@ -218,39 +218,34 @@ class ConvBnAct:
         sp.dgrad(dy, n, in_grid, self._pack("d"), dx, lddy=sp.cout_mem, lddx=lddx, **(dx_epi or {}))
         return dx
 
-    # ---- the layer followed by MaxPool3d(2): BatchNorm + activation + pool in one pass, the pool's backward inside the BatchNorm backward
-    def forward_pool3d(self, x, n, in_grid, training):
-        """-> (pooled [n * prod(og // 2), cout], og, ctx); the normalised activation is never stored (sv_bn_act_maxpool3d_fwd)"""
-        sp = self.spec
-        og = sp.out_grid(in_grid)
-        M = n * og[0] * og[1] * og[2]
-        y = empty(M, sp.cout, like=x)
-        st = BatchNormState(self.bn, M, training)
-        sp.forward(x, n, in_grid, self._pack("f"), y, bias=self.conv.bias, stats=st.sums)
-        st.finalize()
-        st.probe(y, sp.cout)
-        pg = (og[0] // 2, og[1] // 2, og[2] // 2)
-        p = empty(n * pg[0] * pg[1] * pg[2], sp.cout, like=x)
+    # ---- the layer followed by a max-pool that halves the grid (MaxPool3d(2); on a 2-D layer, unit depth axis, the ResNet stem's
+    # MaxPool2d(3, 2, 1)): BatchNorm + activation + pool in one pass, the pool's backward inside the BatchNorm backward
+    def forward_pool(self, x, n, in_grid, training, *, w=None):
+        """-> (pooled [n * prod(og // 2), cout], og, tape); the normalised activation is never stored (sv_bn_act_maxpool*_fwd)"""
+        t = self.forward_stats(x, n, in_grid, training, w=w)
+        C, st = self.spec.cout, t.st
+        st.probe(t.y, C)
+        dims = t.og[1:] if t.og[0] == 1 else t.og
+        p = empty(n * math.prod(d // 2 for d in dims), C, like=x)
         idx = torch.empty(p.numel(), dtype=torch.uint8, device=x.device)
-        call("sv_bn_act_maxpool3d_fwd", ptr(y), ptr(st.scale), ptr(st.shift), ptr(p), ptr(idx), n, og[0], og[1], og[2], sp.cout, self.act, self.slope)
-        return p, og, (x, y, st, n, in_grid, og, M, idx)
+        call("sv_bn_act_maxpool_fwd" if len(dims) == 2 else "sv_bn_act_maxpool3d_fwd", ptr(t.y), ptr(st.scale), ptr(st.shift), ptr(p), ptr(idx),
+             n, *dims, C, self.act, self.slope)
+        return p, t.og, t._replace(idx=idx)
 
-    def backward_pool3d(self, ctx, dp, grads, *, need_dx=True):
-        x, y, st, n, in_grid, og, M, idx = ctx
-        sp = self.spec
+    def backward_pool_bn(self, t, dp, grads):
+        """dp, the gradient of the pooled map -> dy, the gradient of the convolution's output (sv_bn_maxpool*_bwd)"""
+        sp, st = self.spec, t.st
         assert sp.cout_mem == sp.cout
-        dy = empty(M, sp.cout, like=dp)
-        ws = ops.zeros_f64((ops.BN_BWD_SLOTS + 1) * 2 * sp.cout + 2, dp.device)
-        call("sv_bn_maxpool3d_bwd", ptr(dp), ptr(idx), ptr(y), ptr(self.bn.weight), ptr(st.mean), ptr(st.rstd), ptr(st.scale), ptr(st.shift),
-             n, og[0], og[1], og[2], sp.cout, self.act, self.slope, 1 if st.training else 0, ptr(dy), ptr(grads[self.bn.weight]), ptr(grads[self.bn.bias]),
-             ptr(ws))
-        sp.wgrad(dy, x, n, in_grid, self._dw(grads), lddy=sp.cout, db=grads[self.conv.bias] if self.conv.bias is not None else None)
-        if not need_dx:
-            return None
-        Min = n * in_grid[0] * in_grid[1] * in_grid[2]
-        dx = (zeros if sp.cin_mem != sp.cin else empty)(Min, sp.cin_mem, like=dp)
-        sp.dgrad(dy, n, in_grid, self._pack("d"), dx, lddy=sp.cout, lddx=sp.cin_mem)
-        return dx
+        dy = empty(t.M, sp.cout, like=dp)
+        ws = ops.bn_bwd_workspace(sp.cout, dp.device)
+        dims = t.og[1:] if t.og[0] == 1 else t.og
+        call("sv_bn_maxpool_bwd" if len(dims) == 2 else "sv_bn_maxpool3d_bwd", ptr(dp), ptr(t.idx), ptr(t.y), ptr(self.bn.weight), ptr(st.mean),
+             ptr(st.rstd), ptr(st.scale), ptr(st.shift), t.n, *dims, sp.cout, self.act, self.slope, 1 if st.training else 0, ptr(dy),
+             ptr(grads[self.bn.weight]), ptr(grads[self.bn.bias]), ptr(ws))
+        return dy
+
+    def backward_pool(self, t, dp, grads, *, need_dx=True):
+        return self.backward_conv(t, self.backward_pool_bn(t, dp, grads), grads, need_dx=need_dx)
 
     # the two places a layer that runs on a re-indexed weight (Refiner head) overrides
     def _pack(self, kind):

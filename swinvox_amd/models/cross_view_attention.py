@@ -11,6 +11,9 @@ import torch.nn as nn
 from .. import ops
 from ..ops import ACT_GELU, ACT_NONE, BatchNormState, ConvSpec, call, empty, ptr
 
+# x: the input rows; dw: the depth-wise down-sampled rows (x itself at ratio 1); st: the BatchNormState; p, seed: the dropout of the forward
+CvaTape = ops.named_tape("CvaTape", "x dw qkv att up f1pre f1 f2 st p seed B V")
+
 
 class CrossViewAttention(nn.Module):
     def __init__(self, cfg, in_channels):
@@ -88,21 +91,21 @@ class CrossViewAttention(nn.Module):
             seed = seeds()
             out = empty(I * 49, C, like=x)
             call("sv_dropout", ptr(z), ptr(out), z.numel(), float(p), seed, ops.seed_epoch_ptr())
-        return out, (x, dw, qkv, att, up, f1pre, f1, f2, st, p, seed, B, V)
+        return out, CvaTape(x, dw, qkv, att, up, f1pre, f1, f2, st, p, seed, B, V)
 
-    def cva_backward(self, ctx, dout, grads):
-        x, dw, qkv, att, up, f1pre, f1, f2, st, p, seed, B, V = ctx
+    def cva_backward(self, t, dout, grads):
+        x, p, B, V = t.x, t.p, t.B, t.V
         C, R, I = self.in_channels, self.reduced_channels, B * V
         dz = dout
         if p > 0:
             dz = empty(I * 49, C, like=x)
-            call("sv_dropout", ptr(dout), ptr(dz), dz.numel(), float(p), seed, ops.seed_epoch_ptr())
+            call("sv_dropout", ptr(dout), ptr(dz), dz.numel(), float(p), t.seed, ops.seed_epoch_ptr())
         df2 = empty(I * 49, C, like=x)
-        st.backward(dz, C, None, 0, f2, C, df2, C, grads[self.batch_norm.weight], grads[self.batch_norm.bias], ACT_NONE)
-        ops.linear_wgrad(df2, f1, I * 49, self._s_f2, grads[self.ffn[2].weight], grads[self.ffn[2].bias])
+        t.st.backward(dz, C, None, 0, t.f2, C, df2, C, grads[self.batch_norm.weight], grads[self.batch_norm.bias], ACT_NONE)
+        ops.linear_wgrad(df2, t.f1, I * 49, self._s_f2, grads[self.ffn[2].weight], grads[self.ffn[2].bias])
         df1 = empty(I * 49, C, like=x)
-        ops.linear_dgrad(df2, I * 49, self._s_f2, self._s_f2.pack_dgrad(self.ffn[2].weight), df1, act_grad_src=f1pre, act_grad_kind=ACT_GELU)
-        ops.linear_wgrad(df1, up, I * 49, self._s_f0, grads[self.ffn[0].weight], grads[self.ffn[0].bias])
+        ops.linear_dgrad(df2, I * 49, self._s_f2, self._s_f2.pack_dgrad(self.ffn[2].weight), df1, act_grad_src=t.f1pre, act_grad_kind=ACT_GELU)
+        ops.linear_wgrad(df1, t.up, I * 49, self._s_f0, grads[self.ffn[0].weight], grads[self.ffn[0].bias])
         dup = empty(I * 49, C, like=x)
         ops.linear_dgrad(df1, I * 49, self._s_f0, self._s_f0.pack_dgrad(self.ffn[0].weight), dup)
         full = self.downsample_qkv is None             # ATT_SPATIAL_DOWNSAMPLE_RATIO = 1: attention on the 7x7 grid itself
@@ -112,12 +115,12 @@ class CrossViewAttention(nn.Module):
         else:
             dpr = empty(I * P, C, like=x)
             call("sv_cva_upsample_bwd", ptr(dup), ptr(dpr), I, C, r)
-        ops.linear_wgrad(dpr, att, I * P, self._s_proj, grads[self.proj_conv.weight], grads[self.proj_conv.bias])
+        ops.linear_wgrad(dpr, t.att, I * P, self._s_proj, grads[self.proj_conv.weight], grads[self.proj_conv.bias])
         datt = empty(I * P, R, like=x)
         ops.linear_dgrad(dpr, I * P, self._s_proj, self._s_proj.pack_dgrad(self.proj_conv.weight), datt)
         dqkv = empty(I * P, 3 * R, like=x)
-        call("sv_cross_view_attention_bwd", ptr(qkv), ptr(datt), ptr(dqkv), B, V, P, R, self.num_heads)
-        ops.linear_wgrad(dqkv, dw, I * P, self._s_qkv, grads[self.qkv_conv.weight], grads[self.qkv_conv.bias])
+        call("sv_cross_view_attention_bwd", ptr(t.qkv), ptr(datt), ptr(dqkv), B, V, P, R, self.num_heads)
+        ops.linear_wgrad(dqkv, t.dw, I * P, self._s_qkv, grads[self.qkv_conv.weight], grads[self.qkv_conv.bias])
         if full:                                       # dx = qkv data gradient + the residual path, added in the epilogue
             dx = empty(I * 49, C, like=x)
             ops.linear_dgrad(dqkv, I * 49, self._s_qkv, self._s_qkv.pack_dgrad(self.qkv_conv.weight), dx, residual=dup, ldr=C)

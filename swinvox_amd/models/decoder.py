@@ -15,6 +15,8 @@ from ..ops import ACT_RELU, call, empty, ptr, zeros
 from ._base import ConvBnAct, HipModule, conv_spec_of
 
 VOX = 32 * 32 * 32
+# layers: the four LayerTapes; x8: layer4's activation [I * VOX, 8], the head's input
+DecoderTape = ops.named_tape("DecoderTape", "B V layers x8")
 
 
 def raw_view(buf12: torch.Tensor, B: int, V: int) -> torch.Tensor:
@@ -76,7 +78,7 @@ class Decoder(HipModule):
         vol = empty(B, V, 32, 32, 32, like=f)
         w5 = self.layer5[0]
         call("sv_decoder_head_fwd", ptr(x), ptr(w5.weight), ptr(w5.bias), ptr(raw12), ptr(vol), I * VOX)
-        tape = (B, V, ctxs, x) if save else None
+        tape = DecoderTape(B, V, ctxs, x) if save else None
         # raw_features [B,V,9,32,32,32] is by far the largest tensor that crosses a module boundary (9 x 32^3 values per view) and its only
         # consumer is Merger: it is handed over in the activation storage dtype - under bf16 storage a bf16 tensor, as the reference's
         # autocast region (core/train.py:235) returns half-precision module outputs too - which saves a bf16 -> fp32 -> bf16 round trip of
@@ -84,7 +86,7 @@ class Decoder(HipModule):
         return (raw_view(raw12, B, V), ops.to_f32(vol)), tape
 
     def _bwd(self, tape, grads, in_needs, draw, dvol):
-        B, V, ctxs, x8 = tape
+        B, V, x8 = tape.B, tape.V, tape.x8
         I = B * V
         draw12 = ops.to_store(as_channels_last12(draw)) if draw is not None else zeros(I * VOX, 12, like=x8)
         dvol = ops.to_store(dvol) if dvol is not None else None
@@ -93,7 +95,7 @@ class Decoder(HipModule):
         call("sv_decoder_head_bwd", ptr(draw12), ptr(dvol), ptr(x8), ptr(w5.weight), ptr(dx), ptr(grads[w5.weight]),
              ptr(grads[w5.bias]) if w5.bias is not None else None, I * VOX)
         ld = 8
-        for cba, c in zip(reversed(self._cbas), reversed(ctxs)):
+        for cba, c in zip(reversed(self._cbas), reversed(tape.layers)):
             dx = cba.backward(c, dx, ld, grads)
             ld = cba.spec.cin_mem
         if not in_needs[0]:

@@ -7,16 +7,24 @@ are not fetched (offline) - load a checkpoint with load_state_dict instead.
 from __future__ import annotations
 
 import logging
-from typing import List
 
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..ops import ACT_NONE, ACT_RELU, BatchNormState, ConvSpec, call, empty, ptr, zeros
+from ..ops import ACT_NONE, ACT_RELU, ConvSpec, call, empty, ptr, zeros
 from ._base import ConvBnAct, HipModule, conv_spec_of
 from .cross_view_attention import CrossViewAttention
 from .swin_transformer import SwinTransformer, swin_backward, swin_forward
+
+
+# Bottleneck: the four LayerTapes (cd: None without a down-sampling branch); dual: bn3 and the down-sampling BatchNorm ran as one pass
+BottleneckTape = ops.named_tape("BottleneckTape", "c1 c2 c3 cd dual")
+# Encoder: the stem's LayerTape + whether BatchNorm and pool ran fused; one stage of the Swin neck (stage-head output, its 1x1 reduce, the
+# LayerTapes of its stride-2 chain; red and chain are None on the single-stage path); the module's tape
+StemTape = ops.named_tape("StemTape", "layer fused")
+NeckTape = ops.named_tape("NeckTape", "f red chain")
+EncoderTape = ops.named_tape("EncoderTape", "B V stem blocks res_feat rr swin neck cva post in_dtype")
 
 
 class Bottleneck(nn.Module):
@@ -46,37 +54,45 @@ class Bottleneck(nn.Module):
         if self._cd is not None and ops.bn_dual_enabled(training, Co, self._c3.act):
             # bn3 and the down-sampling BatchNorm act on tensors of one shape and are only ever summed: one normalisation pass for both,
             # the normalised skip branch is never stored (ops.bn_dual_apply; the backward likewise, see bwd)
-            yd, _, std, cd = self._cd.forward_stats(x, n, grid, training)
-            y3, g3, st3, c3 = self._c3.forward_stats(b, n, g2, training)
-            out = empty(y3.shape[0], Co, like=y3)
-            ops.bn_dual_apply(st3, y3, Co, std, yd, Co, out, Co)
-            return out, g3, (c1, c2, c3, cd, True)
+            cd = self._cd.forward_stats(x, n, grid, training)
+            c3 = self._c3.forward_stats(b, n, g2, training)
+            out = empty(c3.M, Co, like=c3.y)
+            ops.bn_dual_apply(c3.st, c3.y, Co, cd.st, cd.y, Co, out, Co)
+            return out, c3.og, BottleneckTape(c1, c2, c3, cd, True)
         if self._cd is not None:
             idt, _, cd = self._cd.forward(x, n, grid, training)
         out, g3, c3 = self._c3.forward(b, n, g2, training, residual=idt, ldr=Co)
-        return out, g3, (c1, c2, c3, cd, False)
+        return out, g3, BottleneckTape(c1, c2, c3, cd, False)
 
     def bwd(self, ctx, dout, grads):
-        c1, c2, c3, cd, dual = ctx
+        c1, c2, c3, cd = ctx.c1, ctx.c2, ctx.c3, ctx.cd
         Co = self.conv3.out_channels
-        if dual:
-            M = dout.shape[0]
-            dy3, dyd = empty(M, Co, like=dout), empty(M, Co, like=dout)
-            ops.bn_dual_backward(c3[5], cd[5], dout, Co, c3[2], Co, cd[2], Co, dy3, Co, dyd, Co, grads)
+        if ctx.dual:
+            dy3, dyd = empty(c3.M, Co, like=dout), empty(c3.M, Co, like=dout)
+            ops.bn_dual_backward(c3.st, cd.st, dout, Co, c3.y, Co, cd.y, Co, dy3, Co, dyd, Co, grads)
             db = self._c3.backward_conv(c3, dy3, grads)
-            da = self._c2.backward(c2, db, self.conv2.out_channels, grads)
-            skip = self._cd.backward_conv(cd, dyd, grads)
-            return self._c1.backward(c1, da, self.conv1.out_channels, grads, dx_epi=dict(residual=skip, ldr=self.conv1.in_channels))
-        didt = empty(dout.shape[0], Co, like=dout)
-        db = self._c3.backward(c3, dout, Co, grads, dres=didt, lddres=Co)
+        else:
+            didt = empty(c3.M, Co, like=dout)
+            db = self._c3.backward(c3, dout, Co, grads, dres=didt, lddres=Co)
         da = self._c2.backward(c2, db, self.conv2.out_channels, grads)
+        if ctx.dual:
+            skip = self._cd.backward_conv(cd, dyd, grads)
+        else:
+            skip = self._cd.backward(cd, didt, Co, grads) if cd is not None else didt
         # the skip-path gradient joins in the epilogue of conv1's data-gradient (no separate add pass)
-        skip = self._cd.backward(cd, didt, Co, grads) if cd is not None else didt
         return self._c1.backward(c1, da, self.conv1.out_channels, grads, dx_epi=dict(residual=skip, ldr=self.conv1.in_channels))
 
 
 def _res_layer(inplanes, planes, blocks, stride):
     return nn.Sequential(Bottleneck(inplanes, planes, stride, True), *[Bottleneck(planes * 4, planes, 1, False) for _ in range(blocks - 1)])
+
+
+def _reduce_bwd(sp, conv, d, ld, x, rows, grads):
+    """a 1x1 reduce of the Swin neck: weight and bias gradient from d [rows, ld] and the input x, -> the data gradient [rows, cin]"""
+    sp.wgrad(d, x, rows, (1, 1, 1), grads[conv.weight], lddy=ld, db=grads[conv.bias])
+    dx = empty(rows, sp.cin, like=d)
+    sp.dgrad(d, rows, (1, 1, 1), sp.pack_dgrad(conv.weight), dx, lddy=ld)
+    return dx
 
 
 class Encoder(HipModule):
@@ -113,6 +129,7 @@ class Encoder(HipModule):
         # [112][112][(sy, sx, c) = 16]: input row 2*oy - 3 + ky = 2*(oy - 2 + ty) + sy with ky = 2*ty + sy - 1, i.e. pads (2, 1) and
         # an explicit 112 x 112 output grid.  Same products, but every tap is a 32-byte channel vector instead of 3 scalars.
         self._stem_spec = ConvSpec.conv2d(16, 64, 4, 1, 2, og_fixed=(1, 112, 112))
+        self._stem = ConvBnAct(self.resnet[0], self.resnet[1], self._stem_spec, ACT_RELU)
         self._s_rr = ConvSpec.linear(1024, 256)
         self._post = [ConvBnAct(m[0], m[1], conv_spec_of(m[0]), ACT_RELU) for m in (self.fusion_layer, self.layer1, self.layer2, self.layer3)]
         if n.USE_SWIN_T_MULTI_STAGE:
@@ -153,37 +170,31 @@ class Encoder(HipModule):
         if x16 is None:
             x16 = empty(I * 112 * 112, 16, like=images)                   # [.., (sy, sx, c)], channel 3 of every (sy, sx) group = 0
             call("sv_stem_space_to_depth", ptr(images), ptr(x16), I)
-        sp, bn, M = self._stem_spec, self.resnet[1], I * 112 * 112
-        y = empty(M, 64, like=x16)
-        st = BatchNormState(bn, M, tr)
-        sp.forward(x16, I, (1, 112, 112), self._stem_pack(), y, stats=st.sums)
-        st.finalize()
+        if ops.bn_pool_fused_enabled():
+            mp, _, t = self._stem.forward_pool(x16, I, (1, 112, 112), tr, w=self._stem_pack())
+            return mp, (1, 56, 56), StemTape(t, True)
+        t = self._stem.forward_stats(x16, I, (1, 112, 112), tr, w=self._stem_pack())
         mp = empty(I * 56 * 56, 64, like=x16)
         idx = torch.empty(I * 56 * 56 * 64, dtype=torch.uint8, device=x16.device)
-        fused = ops.bn_pool_fused_enabled()
-        if fused:
-            st.probe(y, 64)
-            call("sv_bn_act_maxpool_fwd", ptr(y), ptr(st.scale), ptr(st.shift), ptr(mp), ptr(idx), I, 112, 112, 64, ACT_RELU, 0.0)
-        else:
-            z = empty(M, 64, like=x16)
-            st.apply(y, 64, z, 64, ACT_RELU, 0.0)
-            call("sv_maxpool2d_fwd", ptr(z), ptr(mp), ptr(idx), I, 112, 112, 64)
-        return mp, (1, 56, 56), (x16, y, st, M, I, idx, fused)
+        z = empty(t.M, 64, like=x16)
+        t.st.apply(t.y, 64, z, 64, ACT_RELU, 0.0)
+        call("sv_maxpool2d_fwd", ptr(z), ptr(mp), ptr(idx), I, 112, 112, 64)
+        return mp, (1, 56, 56), StemTape(t._replace(idx=idx), False)
 
     def _stem_bwd(self, ctx, dmp, grads, need_dx=False):
         """dmp: gradient of the pooled 56 x 56 x 64 map; need_dx: also return the data gradient on the space-to-depth image [I*112*112, 16]"""
-        x16, y, st, M, I, idx, fused = ctx
+        t = ctx.layer
+        x16, M, I = t.x, t.M, t.n
         conv, bn = self.resnet[0], self.resnet[1]
-        dy = empty(M, 64, like=dmp)
-        if fused:
-            ws = ops.zeros_f64((ops.BN_BWD_SLOTS + 1) * 2 * 64 + 2, dmp.device)
-            call("sv_bn_maxpool_bwd", ptr(dmp), ptr(idx), ptr(y), ptr(bn.weight), ptr(st.mean), ptr(st.rstd), ptr(st.scale), ptr(st.shift), I, 112, 112, 64,
-                 ACT_RELU, 0.0, 1 if st.training else 0, ptr(dy), ptr(grads[bn.weight]), ptr(grads[bn.bias]), ptr(ws))
+        if ctx.fused:
+            dy = self._stem.backward_pool_bn(t, dmp, grads)
         else:
+            dy = empty(M, 64, like=dmp)
             dz = empty(M, 64, like=dmp)                                      # the gather-form max-pool backward writes every element
-            call("sv_maxpool2d_bwd", ptr(dmp), ptr(idx), ptr(dz), I, 112, 112, 64)
-            st.backward(dz, 64, None, 64, y, 64, dy, 64, grads[bn.weight], grads[bn.bias], ACT_RELU, 0.0)
-        dw16 = ops.fzeros(64, 16, 4, 4, like=dy)                         # native layout of the 4x4 formulation: [co][(sy,sx,c)][ty][tx]
+            call("sv_maxpool2d_bwd", ptr(dmp), ptr(t.idx), ptr(dz), I, 112, 112, 64)
+            t.st.backward(dz, 64, None, 64, t.y, 64, dy, 64, grads[bn.weight], grads[bn.bias], ACT_RELU, 0.0)
+        # the weight and its gradient live in the 4x4 formulation's native layout here, so the convolution's backward is spelled out
+        dw16 = ops.fzeros(64, 16, 4, 4, like=dy)                         # [co][(sy,sx,c)][ty][tx]
         self._stem_spec.wgrad(dy, x16, I, (1, 112, 112), dw16, async_ok=False)   # read back right below
         call("sv_stem_unpack_grad", ptr(dw16), ptr(grads[conv.weight]))  # dw[co][c][ky][kx] += dw16[co][(sy,sx,c)][ty][tx]
         if not need_dx:
@@ -248,7 +259,7 @@ class Encoder(HipModule):
             c_post.append(c)
         out = empty(B, V, 256, 7, 7, like=x)
         ops.transpose(y, out, I, 49, 256)                                  # [I][49][256] -> [I][256][49]
-        tape = (B, V, c_stem, c_blocks, res_feat, rr, swin_tape, neck, c_cva, c_post, in_dtype) if save else None
+        tape = EncoderTape(B, V, c_stem, c_blocks, res_feat, rr, swin_tape, neck, c_cva, c_post, in_dtype) if save else None
         return ops.to_f32(out), tape
 
     def _swin_neck_fwd(self, feats, ready, cat, I, tr, multi, stream):
@@ -269,7 +280,7 @@ class Encoder(HipModule):
                     cc.append(c)
                 assert gg == (1, 7, 7), "multi-stage neck must end at 7x7"
                 outs.append(y)
-                neck.append((f, red, cc))
+                neck.append(NeckTape(f, red, cc))
             cat_s = cat[:, 256:]
             if len(outs) == 1:
                 outs = outs + [zeros(I * 49, 256, like=img)]
@@ -279,22 +290,22 @@ class Encoder(HipModule):
             f = feats if not isinstance(feats, list) else feats[-1]
             stream.wait_event(ready[-1])
             ops.linear_fwd(f, I * 49, self._s_red1, self.swin_reduce.weight, cat, ldc=512, col_off=256, bias=self.swin_reduce.bias)
-            neck.append((f, None, None))
+            neck.append(NeckTape(f, None, None))
         return neck
 
     def _bwd(self, tape, grads, in_needs, dout):
-        B, V, c_stem, c_blocks, res_feat, rr, swin_tape, neck, c_cva, c_post, in_dtype = tape
+        B, V, neck, in_dtype = tape.B, tape.V, tape.neck, tape.in_dtype
         I = B * V
         need_img = bool(in_needs[0])                                       # images.requires_grad: the gradient wrt the renderings
         multi = self.cfg.NETWORK.USE_SWIN_T_MULTI_STAGE
         dout = ops.to_store(dout)
         dy = empty(I * 49, 256, like=dout)
         ops.transpose(dout, dy, I, 256, 49)                   # [I][256][49] -> [I][49][256]
-        for cba, c in zip(reversed(self._post), reversed(c_post)):
+        for cba, c in zip(reversed(self._post), reversed(tape.post)):
             dy = cba.backward(c, dy, 256, grads)
         dcat = dy                                                          # [I*49, 512]
-        if c_cva is not None:
-            dcat = self.cross_view_attention.cva_backward(c_cva, dcat, grads)
+        if tape.cva is not None:
+            dcat = self.cross_view_attention.cva_backward(tape.cva, dcat, grads)
         # ---- Swin neck + backbone on the side stream, ResNet branch on the main stream
         main = torch.cuda.current_stream()
         side = ops.side_stream(dcat.device) if ops.overlap_enabled() else main
@@ -306,48 +317,35 @@ class Encoder(HipModule):
             # the side stream waits for each stage's event and meanwhile works on the later stages
             dfeats, dready = [None] * len(neck), [None] * len(neck)
             for k in reversed(range(len(neck))):
-                f, red, cc = neck[k]
                 hw = self.swin_transformer.out_spatial[k]
                 d, ld = dcat_s, 512
-                for cba, c in zip(reversed(self._chains[k]), reversed(cc)):
+                for cba, c in zip(reversed(self._chains[k]), reversed(neck[k].chain)):
                     d = cba.backward(c, d, ld, grads)
                     ld = 256
-                conv = self.swin_stage_reduces[k]
-                sp = self._s_red[k]
-                rows = I * hw * hw
-                sp.wgrad(d, f, rows, (1, 1, 1), grads[conv.weight], lddy=ld, db=grads[conv.bias])
-                df = empty(rows, sp.cin, like=dout)
-                sp.dgrad(d, rows, (1, 1, 1), sp.pack_dgrad(conv.weight), df, lddy=ld)
-                dfeats[k] = df
+                dfeats[k] = _reduce_bwd(self._s_red[k], self.swin_stage_reduces[k], d, ld, neck[k].f, I * hw * hw, grads)
                 dready[k] = torch.cuda.Event()
                 dready[k].record(main)
         with torch.cuda.stream(side):
-            if multi:
-                pass
-            else:
-                f = neck[0][0]
-                sp = self._s_red1
-                sp.wgrad(dcat_s, f, I * 49, (1, 1, 1), grads[self.swin_reduce.weight], lddy=512, db=grads[self.swin_reduce.bias])
-                df = empty(I * 49, sp.cin, like=dout)
-                sp.dgrad(dcat_s, I * 49, (1, 1, 1), sp.pack_dgrad(self.swin_reduce.weight), df, lddy=512)
+            if not multi:
+                df = _reduce_bwd(self._s_red1, self.swin_reduce, dcat_s, 512, neck[0].f, I * 49, grads)
                 dfeats = [None] * (len(self.swin_transformer.layer_norm) - 1) + [df]
                 for i in range(len(dfeats) - 1):   # unused heads of the single-stage path receive zero gradient
                     hw, ch = self.swin_transformer.out_spatial[i], self.swin_transformer.out_channels[i]
                     dfeats[i] = zeros(I * hw * hw, ch, like=dout)
-            dxp = swin_backward(self.swin_transformer, swin_tape, dfeats, I, grads, dready, need_dx=need_img)   # patch rows [I*3136, 48]
+            dxp = swin_backward(self.swin_transformer, tape.swin, dfeats, I, grads, dready, need_dx=need_img)   # patch rows [I*3136, 48]
             self._announce(grads, 1)                                       # Swin backbone + stage heads are enqueued
         # ---- ResNet branch
         drr = empty(I * 196, 256, like=dout)
         call("sv_avgpool2_bwd", ptr(dcat), ptr(drr), I, 14, 14, 256, 512, 0)
-        self._s_rr.wgrad(drr, res_feat, I * 196, (1, 1, 1), grads[self.resnet_reduce.weight], db=grads[self.resnet_reduce.bias])
+        self._s_rr.wgrad(drr, tape.res_feat, I * 196, (1, 1, 1), grads[self.resnet_reduce.weight], db=grads[self.resnet_reduce.bias])
         tail_on_main = multi or side is main                               # single-stage: swin_reduce's gradient is written on the side stream
         if tail_on_main:
             self._announce(grads, 0)                                       # neck + cross-view attention + fusion head are enqueued
         d = empty(I * 196, 1024, like=dout)
         self._s_rr.dgrad(drr, I * 196, (1, 1, 1), self._s_rr.pack_dgrad(self.resnet_reduce.weight), d)
-        for blk, c in reversed(c_blocks):
+        for blk, c in reversed(tape.blocks):
             d = blk.bwd(c, d, grads)
-        dx16 = self._stem_bwd(c_stem, d, grads, need_img)                  # max-pool + BatchNorm + stem conv (+ its data gradient)
+        dx16 = self._stem_bwd(tape.stem, d, grads, need_img)                  # max-pool + BatchNorm + stem conv (+ its data gradient)
         self._announce(grads, 2)                                           # ResNet trunk
         main.wait_stream(side)                                             # join: every parameter gradient is complete
         if not tail_on_main:

@@ -8,6 +8,10 @@ from .. import ops
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, ConvSpec, call, empty, ptr, zeros
 from ._base import ConvBnAct, HipModule, conv_spec_of
 
+# one down-sampling layer: its LayerTape and, where the pool ran as a pass of its own, the arg-max bytes (None: fused form, the tape has them)
+DownTape = ops.named_tape("DownTape", "layer idx")
+RefinerTape = ops.named_tape("RefinerTape", "B v32 down flat h1 h2 r4 c6 u8 r8 c7 u16 r16")
+
 
 class HeadConvBnAct(ConvBnAct):
     """layer1's Conv3d(1, 32, k = 4, p = 2) + BatchNorm + LeakyReLU (reference models/refiner.py:21-26) as a (4, 1, 1)-tap convolution over the 16
@@ -22,46 +26,23 @@ class HeadConvBnAct(ConvBnAct):
         super().__init__(conv, bn, ConvSpec.conv3d(16, conv.out_channels, (4, 1, 1), 1, (2, 0, 0)), act, slope)
         self._w16 = self._dw16 = None
 
-    def _packed(self, x, n, in_grid):
-        D = in_grid[0]
+    def forward_stats(self, x, n, in_grid, training, **kw):
+        """x [n * D^3, 1] -> the step on the packed input and the re-indexed weight, grid (D, D + 1, D + 1)"""
+        D, co = in_grid[0], self.spec.cout
         assert tuple(in_grid) == (D, D, D)
-        co = self.spec.cout
         xc = empty(n * D * (D + 1) * (D + 1), 16, like=x)
         call("sv_head_pack_x", ptr(x), ptr(xc), n, D)
         self._w16 = torch.empty(co, 16, 4, dtype=torch.float32, device=x.device)
         ops.transpose(self.conv.weight, self._w16, co, 4, 16)
-        return xc, D
+        return super().forward_stats(xc, n, (D, D + 1, D + 1), training, **kw)._replace(w=self._w16)
 
-    def forward(self, x, n, in_grid, training):
-        xc, D = self._packed(x, n, in_grid)
-        z, og, c = super().forward(xc, n, (D, D + 1, D + 1), training)
-        return z, og, (c, self._w16, D, n)
-
-    def forward_pool3d(self, x, n, in_grid, training):
-        xc, D = self._packed(x, n, in_grid)
-        p, og, c = super().forward_pool3d(xc, n, (D, D + 1, D + 1), training)
-        return p, og, (c, self._w16, D, n)
-
-    def backward(self, ctx, dz, lddz, grads, *, need_dx=True):
-        return self._backward(ctx, grads, need_dx, lambda c: ConvBnAct.backward(self, c, dz, lddz, grads, need_dx=need_dx))
-
-    def backward_pool3d(self, ctx, dp, grads, *, need_dx=True):
-        return self._backward(ctx, grads, need_dx, lambda c: ConvBnAct.backward_pool3d(self, c, dp, grads, need_dx=need_dx))
-
-    def _backward(self, ctx, grads, need_dx, inner):
-        c, self._w16, D, n = ctx
-        co = self.spec.cout
-        dev = self._w16.device
-        self._dw16 = torch.zeros(co, 16, 4, dtype=torch.float32, device=dev)
-        dxc = inner(c)
-        # the weight gradient went out on the weight-gradient stream when a module backward runs one: its way back follows it there
-        aw = ops._CTX.awg
-        if aw is not None:
-            aw.held.append((self._dw16,))
-            with torch.cuda.stream(aw.stream):
-                ops.transpose(self._dw16, grads[self.conv.weight], co, 16, 4)
-        else:
-            ops.transpose(self._dw16, grads[self.conv.weight], co, 16, 4)
+    def backward_conv(self, t, dy, grads, *, need_dx=True, **kw):
+        self._w16, n, D, co = t.w, t.n, t.in_grid[0], self.spec.cout
+        self._dw16 = torch.zeros(co, 16, 4, dtype=torch.float32, device=t.w.device)
+        dxc = super().backward_conv(t, dy, grads, need_dx=need_dx, **kw)
+        # the weight gradient went out on the weight-gradient stream when a module backward runs one: its way back follows it there (no wait:
+        # stream order)
+        ops.run_on_wgrad_stream((self._dw16,), lambda: ops.transpose(self._dw16, grads[self.conv.weight], co, 16, 4), wait=False)
         if not need_dx:
             return None
         dx = empty(n * D * D * D, 1, like=dxc)
@@ -108,20 +89,17 @@ class Refiner(HipModule):
         x, g, dctx, skips = v32, (32, 32, 32), [], []
         fused = ops.bn_pool_fused_enabled()
         for cba in self._down:
-            C = cba.spec.cout
             if fused:                                                      # conv k4 p2 -> 33/17/9 grid, BN over all of it, pool in the same pass
-                p, og, c = cba.forward_pool3d(x, B, g, tr)
+                p, og, c = cba.forward_pool(x, B, g, tr)
                 idx = None
             else:
                 z, og, c = cba.forward(x, B, g, tr)
-            pg = (og[0] // 2, og[1] // 2, og[2] // 2)
-            if not fused:
-                p = empty(B * pg[0] * pg[1] * pg[2], C, like=vol)
+                p = empty(B * (og[0] // 2) * (og[1] // 2) * (og[2] // 2), cba.spec.cout, like=vol)
                 idx = torch.empty(p.numel(), dtype=torch.uint8, device=vol.device)
-                call("sv_maxpool3d_fwd", ptr(z), ptr(p), ptr(idx), B, og[0], og[1], og[2], C)
-            dctx.append((c, og, idx))
+                call("sv_maxpool3d_fwd", ptr(z), ptr(p), ptr(idx), B, *og, cba.spec.cout)
+            dctx.append(DownTape(c, idx))
             skips.append(p)
-            x, g = p, pg
+            x, g = p, (og[0] // 2, og[1] // 2, og[2] // 2)
         v16, v8, v4 = skips
         flat = empty(B, 8192, like=vol)
         ops.transpose(v4, flat, B, 64, 128)                                # [b][pos][c] -> [b][c][pos] = NCDHW flatten order
@@ -144,11 +122,11 @@ class Refiner(HipModule):
         self._s8.forward(r16, B, (16, 16, 16), self._s8.pack_fwd(c8.weight), t8, ldc=1, bias=c8.bias)
         out = empty(B, 32, 32, 32, like=vol)
         call("sv_axpby", ptr(v32), ptr(t8), ptr(out), 0.5, 0.5, out.numel())
-        tape = (B, v32, dctx, flat, h1, h2, r4, c6, u8, r8, c7, u16, r16) if save else None
+        tape = RefinerTape(B, v32, dctx, flat, h1, h2, r4, c6, u8, r8, c7, u16, r16) if save else None
         return ops.to_f32(out), tape
 
     def _bwd(self, tape, grads, in_needs, dout):
-        B, v32, dctx, flat, h1, h2, r4, c6, u8, r8, c7, u16, r16 = tape
+        B, h1 = tape.B, tape.h1
         dout = ops.to_store(dout)
         c8 = self.layer8[0]
         dt8 = zeros(B * 32768, 4, like=dout)                                # 1 real column, padded to 4 for 16-byte gathers
@@ -156,22 +134,22 @@ class Refiner(HipModule):
         call("sv_axpby", ptr(dt8), None, ptr(dt8), 0.5, 0.0, dt8.numel())
         if c8.bias is not None:
             ops.colsum(dt8, B * 32768, 1, 4, grads[c8.bias])
-        self._s8.wgrad(dt8, r16, B, (16, 16, 16), grads[c8.weight], lddy=4, ldx=32)
+        self._s8.wgrad(dt8, tape.r16, B, (16, 16, 16), grads[c8.weight], lddy=4, ldx=32)
         dr16 = empty(B * 4096, 32, like=dout)
         self._s8.dgrad(dt8, B, (16, 16, 16), self._s8.pack_dgrad(c8.weight), dr16, lddy=4, lddx=32)
         # r16 = v16 + u16
-        dr8 = self._up[1].backward(c7, dr16, 32, grads)                     # through layer7 -> d r8
-        dr4 = self._up[0].backward(c6, dr8, 64, grads)                      # through layer6 -> d r4   (dr8 also feeds v8)
+        dr8 = self._up[1].backward(tape.c7, dr16, 32, grads)                     # through layer7 -> d r8
+        dr4 = self._up[0].backward(tape.c6, dr8, 64, grads)                      # through layer6 -> d r4   (dr8 also feeds v8)
         # FC bottleneck: r4 = v4 + T(relu(fc5(relu(fc4(T(v4))))))
         dh2 = empty(B, 8192, like=dout)
         ops.transpose(dr4, dh2, B, 64, 128)
         # ReLU backward of layer5: dpre5 = dh2 * (h2 > 0)
         dpre5 = empty(B, 8192, like=dout)
-        _relu_mask(dh2, h2, dpre5)
+        _relu_mask(dh2, tape.h2, dpre5)
         ops.linear_wgrad(dpre5, h1, B, self._s5, grads[self.layer5[0].weight], grads[self.layer5[0].bias])
         dh1 = empty(B, 2048, like=dout)
         ops.linear_dgrad(dpre5, B, self._s5, self._s5.pack_dgrad(self.layer5[0].weight), dh1, act_grad_src=h1, act_grad_kind=ACT_RELU)
-        ops.linear_wgrad(dh1, flat, B, self._s4, grads[self.layer4[0].weight], grads[self.layer4[0].bias])
+        ops.linear_wgrad(dh1, tape.flat, B, self._s4, grads[self.layer4[0].weight], grads[self.layer4[0].bias])
         dflat = empty(B, 8192, like=dout)
         ops.linear_dgrad(dh1, B, self._s4, self._s4.pack_dgrad(self.layer4[0].weight), dflat)
         dv4 = empty(B * 64, 128, like=dout)
@@ -181,18 +159,17 @@ class Refiner(HipModule):
         d_skip = [dr16, dr8, dv4]
         dx = None
         for li in (2, 1, 0):
-            cba = self._down[li]
-            c, og, idx = dctx[li]
-            C = cba.spec.cout
-            dp = d_skip[li]
+            cba, t, dp = self._down[li], tape.down[li], d_skip[li]
+            need_dx = li > 0 or in_needs[0]
             if dx is not None:
                 call("sv_axpby", ptr(dp), ptr(dx), ptr(dp), 1.0, 1.0, dp.numel())
-            if idx is None:                                                # fused forward: the pool's backward runs inside the BatchNorm backward
-                dx = cba.backward_pool3d(c, dp, grads, need_dx=(li > 0 or in_needs[0]))
-                continue
-            dz = empty(B * og[0] * og[1] * og[2], C, like=dout)
-            call("sv_maxpool3d_bwd", ptr(dp), ptr(idx), ptr(dz), B, og[0], og[1], og[2], C)
-            dx = cba.backward(c, dz, C, grads, need_dx=(li > 0 or in_needs[0]))
+            if t.idx is None:                                              # fused forward: the pool's backward runs inside the BatchNorm backward
+                dx = cba.backward_pool(t.layer, dp, grads, need_dx=need_dx)
+            else:
+                C = cba.spec.cout
+                dz = empty(t.layer.M, C, like=dout)
+                call("sv_maxpool3d_bwd", ptr(dp), ptr(t.idx), ptr(dz), B, *t.layer.og, C)
+                dx = cba.backward(t.layer, dz, C, grads, need_dx=need_dx)
         if not in_needs[0]:
             return (None,)
         dvol = empty(B, 32, 32, 32, like=dout)

@@ -12,7 +12,7 @@ The modules below only HOLD parameters; the arithmetic is the kernel chain in sw
 from __future__ import annotations
 
 import logging
-from typing import Any, List, NamedTuple
+from typing import List
 
 import torch
 import torch.nn as nn
@@ -143,9 +143,9 @@ def _drop_scale(I, p, seed, like):
 # What block_forward keeps for block_backward.  ln1, att, ln2 and h are tensors or, under store "mx" (LinearPlan.keep), the MX rows (bytes,
 # scales) the forward GEMM consumed; a fused branch leaves the entries it does not store None.  packs: the fused MLP's bf16 weight images, when
 # its backward reads them; fused_mlp: the fused MLP took the block (block_backward runs _fused_mlp_backward).
-BlockTape = NamedTuple("BlockTape", [(n, Any) for n in "x m1 r1 ln1 qkv att sc1 sc2 x1 m2 r2 ln2 hpre h I packs fused_mlp".split()])
+BlockTape = ops.named_tape("BlockTape", "x m1 r1 ln1 qkv att sc1 sc2 x1 m2 r2 ln2 hpre h I packs fused_mlp")
 # What stage_forward keeps of the patch merging: its input, the norm's output (or its MX rows, store "mx") and statistics, the rows, Hin.
-MergeTape = NamedTuple("MergeTape", [(n, Any) for n in "x ln mean rstd rows Hin".split()])
+MergeTape = ops.named_tape("MergeTape", "x ln mean rstd rows Hin")
 
 
 def _norm_for_linear(x, norm, rows, Cd, plan, save, merge_hw=(0, 0)):
@@ -303,14 +303,7 @@ def _fused_mlp_backward(blk, t: BlockTape, dx2, grads):
                         ptr(mlp.fc1.bias), ptr(sc2), HW, ptr(grads[mlp.fc1.weight]), ptr(grads[mlp.fc1.bias]),
                         ptr(grads[mlp.fc2.weight]), ptr(grads[mlp.fc2.bias]), M, Cd, eps, tag=f"M={M} C={Cd}")
 
-    aw = ops._CTX.awg
-    if aw is not None:
-        aw.stream.wait_stream(torch.cuda.current_stream())
-        aw.held.append((x1, dx2, *operands))
-        with torch.cuda.stream(aw.stream):
-            launch()
-    else:
-        launch()
+    ops.run_on_wgrad_stream((x1, dx2, *operands), launch)
     return dx1
 
 
@@ -325,7 +318,7 @@ def _attention_backward(blk, t: BlockTape, dx1, grads):
         # backward + residual; dqkv goes to HBM for the weight gradients, which stay on the engine (weight-gradient stream)
         dqkv, dx = empty(M, 3 * Cd, like=x), empty(M, Cd, like=x)
         dbr = empty(M, Cd, like=x) if sc1 is not None else None
-        ws = ops.zeros_f64(8 * 169 * blk.heads, x.device)    # sv_window_attention_bwd_workspace_floats(heads) floats, zero on entry
+        ws = ops.attn_bwd_workspace(blk.heads, x.device)
         ops.traced_call("sv_swin_attn_block_bwd", 2.0 * M * Cd * 4 * Cd + 10.0 * 49 * 32 * M * blk.heads, esz * M * Cd * (10 if sc1 is not None else 9),
                         ptr(dx1), ptr(qkv), ptr(x), ptr(m1), ptr(r1), ptr(blk.norm1.weight), ptr(a.qkv.weight), ptr(a.proj.weight),
                         ptr(a.relative_position_bias_table), ptr(sc1), ptr(dqkv), ptr(dx), ptr(dbr), ptr(grads[blk.norm1.weight]),
@@ -343,7 +336,7 @@ def _attention_backward(blk, t: BlockTape, dx1, grads):
     datt = empty(M, Cd, like=x)
     ops.swin_linear_dgrad(dbr, M, blk.s_proj, a.proj.weight, datt)
     dqkv = empty(M, 3 * Cd, like=x)
-    ws = ops.zeros_f64(8 * 169 * blk.heads, x.device)    # sv_window_attention_bwd_workspace_floats(heads) floats, zero on entry
+    ws = ops.attn_bwd_workspace(blk.heads, x.device)
     # backward = 2.5 x the forward products (recomputed P, dP, dQ, dK, dV); bytes: qkv + dout in, dqkv out
     ops.traced_call("sv_window_attention_bwd", 10.0 * 49 * 32 * M * blk.heads, esz * 7 * M * Cd, ptr(qkv), ptr(a.relative_position_bias_table),
                     ptr(datt), ptr(dqkv), ptr(grads[a.relative_position_bias_table]), ptr(ws), I, H, W, Cd, blk.heads, blk.shift,
@@ -482,13 +475,8 @@ def swin_backward(st: SwinTransformer, tape, dfeats, I, grads, ready=None, need_
     if as_patches:
         dw48 = torch.zeros(Ce, 48, dtype=torch.float32, device=dx.device)
         bb.embed_lin.wgrad(demb, img, M, (1, 1, 1), dw48, db=grads[pe.proj.bias])
-        aw = ops._CTX.awg          # the weight gradient went out on the weight-gradient stream: its way back to [co][c][(ky, kx)] follows it there
-        if aw is not None:
-            aw.held.append((dw48,))
-            with torch.cuda.stream(aw.stream):
-                ops.transpose(dw48, grads[pe.proj.weight], Ce, 16, 3)
-        else:
-            ops.transpose(dw48, grads[pe.proj.weight], Ce, 16, 3)
+        # the weight gradient went out on the weight-gradient stream: its way back to [co][c][(ky, kx)] follows it there (no wait: stream order)
+        ops.run_on_wgrad_stream((dw48,), lambda: ops.transpose(dw48, grads[pe.proj.weight], Ce, 16, 3), wait=False)
     else:
         bb.embed_spec.wgrad(demb, img, I, (1, S, S), grads[pe.proj.weight], db=grads[pe.proj.bias])
     if not need_dx:

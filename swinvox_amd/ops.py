@@ -11,7 +11,7 @@ import ctypes as C
 import os
 import threading
 from dataclasses import dataclass
-from typing import NamedTuple, Optional, Tuple
+from typing import Any, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -34,6 +34,12 @@ class _CallContext(threading.local):
 
 
 _CTX = _CallContext()
+
+
+def named_tape(name: str, fields: str):
+    """The type of what a forward keeps for its backward: a tuple whose entries are read by name."""
+    return NamedTuple(name, [(f, Any) for f in fields.split()])
+
 BN_SLOTS = 16   # SV_BN_SLOTS of include/swinvox_hip.h
 BN_BWD_SLOTS, LN_BWD_SLOTS = 16, 32   # slot counts behind sv_bn_bwd_workspace_doubles / sv_layernorm_bwd_workspace_floats
 
@@ -260,15 +266,7 @@ class ConvSpec:
         Inside a module backward the launch goes to the weight-gradient stream (AsyncWgrad): nothing on the data-gradient
         chain waits for a weight gradient.  async_ok=False keeps it on the caller's stream - required when dy or x is
         modified in place afterwards."""
-        aw = _CTX.awg
-        if aw is not None and async_ok:
-            cur = torch.cuda.current_stream()
-            aw.stream.wait_stream(cur)                 # dy and x are complete on the producing stream
-            aw.held.append((dy, x))                    # keep the operands alive (and unrecycled) until the join
-            with torch.cuda.stream(aw.stream):
-                self._wgrad(dy, x, n, in_grid, dw, lddy, ldx, db)
-            return
-        self._wgrad(dy, x, n, in_grid, dw, lddy, ldx, db)
+        run_on_wgrad_stream((dy, x), lambda: self._wgrad(dy, x, n, in_grid, dw, lddy, ldx, db), enable=async_ok)
 
     def _wgrad(self, dy, x, n, in_grid, dw, lddy, ldx, db):
         og = self.out_grid(in_grid)
@@ -387,6 +385,16 @@ def zeros_f64(n, dev):
     return a.take(n, dev) if a is not None else torch.zeros(n, dtype=torch.float64, device=dev)
 
 
+def bn_bwd_workspace(C, dev, layers=1):
+    """[layers][sv_bn_bwd_workspace_doubles(C)] doubles, zero on entry: the slot images of one BatchNorm backward launch per row"""
+    return zeros_f64(layers * ((BN_BWD_SLOTS + 1) * 2 * C + 2), dev).view(layers, -1)
+
+
+def attn_bwd_workspace(heads, dev):
+    """sv_window_attention_bwd_workspace_floats(heads) floats, zero on entry: the relative-position-bias gradient's slot images"""
+    return zeros_f64(8 * 169 * heads, dev)
+
+
 def set_arena(arena) -> None:
     _CTX.arena = arena
 
@@ -419,6 +427,25 @@ class AsyncWgrad:
 def set_async_wgrad(aw) -> None:
     _CTX.awg = aw
     _CTX.dyq = None
+
+
+def run_on_wgrad_stream(held, fn, wait=True, enable=True) -> bool:
+    """fn() - launches that produce or move a weight gradient - on the weight-gradient stream of the running module backward; in place, on the
+    caller's stream, when there is none or `enable` is False.  -> whether it went to that stream.
+    held: the tensors fn reads that the caller's stream made; they stay referenced (alive and unrecycled) until AsyncWgrad.join().
+    wait=True: the stream first waits for the caller's stream, where those tensors are complete.  wait=False is for a launch that only follows
+    one already sent to that stream (it reads what that launch wrote): stream order is all it needs, and the caller's stream is not waited for.
+    Temporaries fn allocates belong to the weight-gradient stream's pool and are recycled in its order."""
+    aw = _CTX.awg
+    if aw is None or not enable:
+        fn()
+        return False
+    if wait:
+        aw.stream.wait_stream(torch.cuda.current_stream())
+    aw.held.append(held)
+    with torch.cuda.stream(aw.stream):
+        fn()
+    return True
 
 
 _SIDE = {}
@@ -1052,17 +1079,10 @@ def swin_linear_wgrad(dy, x, rows, spec: ConvSpec, w, dw, db=None, async_ok=True
                     ptr(dyt), ptr(dys), ptr(xt), ptr(xs), ptr(dw), rows, spec.cout, spec.cin, spec.cin, 0, *[ptr(t) for t in ws],
                     tag=f"M={rows} N={spec.cout} K={spec.cin}")
 
-    aw = _CTX.awg
-    if aw is not None and async_ok:
-        aw.stream.wait_stream(torch.cuda.current_stream())     # dy and x are complete on the producing stream
-        aw.held.append((dy,) + x if pair else (dy, x))         # the operands stay alive (and unrecycled) until the join
-        with torch.cuda.stream(aw.stream):
-            run()      # the temporaries are allocated on the weight-gradient stream and dropped here: its allocator recycles them in stream order
-        if dual:       # the column pair of dy was allocated on the caller's stream and is read on this one: not held, recorded
-            dcols[0].record_stream(aw.stream)
-            dcols[1].record_stream(aw.stream)
-        return
-    run()
+    # run()'s temporaries are allocated on the weight-gradient stream and dropped there: its allocator recycles them in stream order
+    if run_on_wgrad_stream((dy,) + x if pair else (dy, x), run, enable=async_ok) and dual:
+        for t in dcols:    # the column pair of dy was allocated on the caller's stream and is read on that one: not held, recorded
+            t.record_stream(_CTX.awg.stream)
 
 
 def linear_dgrad(dy, rows, spec: ConvSpec, w_t, dx, **epi):
@@ -1202,7 +1222,7 @@ class BatchNormState:
         call("sv_scale_shift_act", ptr(x), ldx, ptr(self.scale), ptr(self.shift), ptr(residual), ldr, ptr(y), ldy, self.M, self.C, act, slope)
 
     def backward(self, dz, lddz, z, ldz, x, ldx, dx, lddx, dgamma, dbeta, act=ACT_NONE, slope=0.0, dres=None, lddres=0):
-        ws = zeros_f64((BN_BWD_SLOTS + 1) * 2 * self.C + 2, dz.device)     # sv_bn_bwd_workspace_doubles(C), zero on entry
+        ws = bn_bwd_workspace(self.C, dz.device)
         if getattr(self, "signs", None) is not None and dres is not None:
             # mask from the forward's sign words: the reduce pass reads (dz, x, words) and stores the masked gradient in dres, the apply pass
             # reads (dres, x): 6 passes over the tensor instead of the 8 of (dz, z, x) + (dz, z, x, dx, dres)
@@ -1239,11 +1259,10 @@ def bn_dual_apply(st3: "BatchNormState", x3, ldx3, std: "BatchNormState", xd, ld
 
 def bn_dual_backward(st3: "BatchNormState", std: "BatchNormState", dz, lddz, x3, ldx3, xd, ldxd, dx3, lddx3, dxd, lddxd, grads) -> None:
     """both layers' input gradients from dz and st3's sign words; grads[...] of the four BatchNorm parameters +="""
-    n = (BN_BWD_SLOTS + 1) * 2 * st3.C + 2          # sv_bn_bwd_workspace_doubles(C), one image per layer, zero on entry
-    ws = zeros_f64(2 * n, dz.device)
+    ws = bn_bwd_workspace(st3.C, dz.device, layers=2)
     call("sv_bn_bwd2_signs", ptr(dz), lddz, ptr(st3.signs), ptr(x3), ldx3, ptr(st3.bn.weight), ptr(st3.mean), ptr(st3.rstd),
          ptr(xd), ldxd, ptr(std.bn.weight), ptr(std.mean), ptr(std.rstd), st3.M, st3.C, ptr(dx3), lddx3, ptr(dxd), lddxd,
-         ptr(grads[st3.bn.weight]), ptr(grads[st3.bn.bias]), ptr(grads[std.bn.weight]), ptr(grads[std.bn.bias]), ptr(ws[:n]), ptr(ws[n:]))
+         ptr(grads[st3.bn.weight]), ptr(grads[st3.bn.bias]), ptr(grads[std.bn.weight]), ptr(grads[std.bn.bias]), ptr(ws[0]), ptr(ws[1]))
 
 
 def _bn_signs_on() -> bool:
