@@ -574,6 +574,31 @@ int sv_swin_attn_block_fwd(const void* x, const float* ln_g, const float* ln_b, 
  * (backward = 0) / _bwd (backward = 1) makes for these arguments (call site models/swin_transformer.py:78); pure host function, negative
  * SV_ERR_* for a geometry the entry points refuse. */
 int sv_swin_attn_block_windows_per_group(int I, int H, int W, int backward);
+/* MXFP8 forward of the same branch (timm SwinTransformerBlock._attn + norm1 + DropPath behind models/swin_transformer.py:78), opt-in: the unfused MX
+ * chain sv_layernorm_quant_mx_fwd -> sv_linear_mxfp8 (bias) -> sv_window_attention_fwd_mxq (bf16 core) -> sv_linear_mxfp8 (bias, residual x,
+ * row_scale per image) composed in ONE kernel.  qkv and proj run on the block-scaled K = 128 MFMA with E8M0 scales per 32 channels (one head of a
+ * token = one block of the projection's operand); LN(x) and the head outputs are quantised in registers, no quantised activation reaches HBM.  The
+ * attention core, the launch geometry (sv_swin_attn_block_windows_per_group(I, H, W, 0)) and the side outputs are sv_swin_attn_block_fwd's; the
+ * backward is sv_swin_attn_block_bwd + the engine's weight gradients on the stored bf16 tensors, unchanged (straight-through quantisers).
+ *  sv_swin_attn_block_mx_supported:  1 for C = 96 with 3 heads, else 0 (timm WindowAttention behind models/swin_transformer.py:78).
+ *  sv_swin_attn_block_mx_pack_bytes: size of `packs` for C (0 when unsupported) (timm WindowAttention weights behind models/swin_transformer.py:78).
+ *  sv_swin_attn_block_mx_pack:       wqkv_q [288, 128] / wqkv_s [288, 4] and wproj_q [96, 128] / wproj_s [96, 4], the MX rows sv_quant_rows_mx_e4m3
+ *                                    makes of qkv.weight and proj.weight (timm WindowAttention behind models/swin_transformer.py:78), -> `packs` in the
+ *                                    kernel's fragment order; wqkv_q, wproj_q and packs 16-byte aligned.  The bytes are re-ordered, never re-quantised.
+ *  sv_swin_attn_block_fwd_mx:        the arguments of sv_swin_attn_block_fwd with packs_mx (from sv_swin_attn_block_mx_pack) in place of wqkv / wproj
+ *                                    (timm SwinTransformerBlock._attn behind models/swin_transformer.py:78); side outputs all or none.
+ *  sv_swin_attn_block_mx_launches:   sv_swin_attn_block_fwd_mx launches so far in this process (timm SwinTransformerBlock._attn behind
+ *                                    models/swin_transformer.py:78; tests: the path they mean to exercise).
+ * Refusals (SV_ERR_INVALID before any GPU call, the entry's name in sv_last_error()): everything sv_swin_attn_block_fwd refuses, unsupported
+ * (C, heads), NULL or misaligned packs or pack operands, side outputs given only in part.                                                */
+int sv_swin_attn_block_mx_supported(int C, int heads); /* timm SwinTransformerBlock._attn behind models/swin_transformer.py:78 */
+long long sv_swin_attn_block_mx_pack_bytes(int C); /* timm SwinTransformerBlock._attn behind models/swin_transformer.py:78 */
+int sv_swin_attn_block_mx_pack(const void* wqkv_q, const void* wqkv_s, const void* wproj_q, const void* wproj_s, void* packs, int C,
+                               void* stream); /* timm SwinTransformerBlock._attn behind models/swin_transformer.py:78 */
+int sv_swin_attn_block_fwd_mx(const void* x, const float* ln_g, const float* ln_b, const void* packs_mx, const float* bqkv, const float* table,
+                              const float* bproj, const float* row_scale, void* x1, void* ln1, float* mean, float* rstd, void* qkv, void* att,
+                              int I, int H, int W, int C, int heads, int shift, float eps, int act_dtype, void* stream); /* timm SwinTransformerBlock._attn + norm1 + DropPath behind models/swin_transformer.py:78 */
+long long sv_swin_attn_block_mx_launches(void); /* timm SwinTransformerBlock._attn behind models/swin_transformer.py:78 */
 /* Fused BACKWARD of the same branch (data path): reads dx1 [M,96], the qkv rows and LayerNorm statistics the forward stored, and x; writes
  * dqkv [M,288] (the engine's weight-gradient kernels read it: d qkv.weight / bias from (dqkv, ln1), d proj.weight / bias from (s dx1, att)) and
  * dx = dx1 + LayerNormBackward(dqkv Wqkv) [M,96]; accumulates into dgamma / dbeta of norm1 [96] and dtable [169,3].  dbr (optional) receives

@@ -11,10 +11,12 @@
 //  * Cross-view attention core (models/cross_view_attention.py:81-105): one workgroup per (sample, head),
 //    V x V scores over 288-long features -- tiny, plain FMA.
 #include "common.h"
+#include "mx_frag.h"
+#include <atomic>
 
 namespace sv {
 
-constexpr int WT = 49;       // tokens per window
+constexpr int WT = 49;      // tokens per window
 constexpr int HD = 32;       // head dim (Swin-T/B: always 32)
 constexpr int LDQ_F = 36;    // fp32 row stride of q/k/v tiles
 constexpr int LDP_F = 68;    // fp32 row stride of the P tile
@@ -1369,6 +1371,79 @@ struct BlockFwdArgs {
 };
 constexpr int FB_SMEM = (288 + 96) * FB_LDW * 2 + 2 * 64 * FB_LDT * 2 + (3 * 176 + 288 + 3 * 96) * 4;
 
+// The three sections of swin_attn_block_fwd_kernel that its MXFP8 sibling (swin_attn_block_fwd_mx_kernel) runs expression for expression, on a lane
+// that holds token q = 16 wave + lr and, of a 32-column chunk ck, the 8 consecutive columns n0 = 32 ck + 8 lg .. + 7 in the two accumulator blocks
+// acc[0] | acc[1].  The bf16 kernel keeps its own text: calling these from it moves its register allocation (182 -> 178 VGPRs) and the kernel of the
+// default step is pinned, resource row included; a change to either copy belongs in both.
+// qkv chunk ck: + bias, bf16 rounding, side output, the softmax scale on the bf16 q, the window tile
+__device__ __forceinline__ void fb_put_qkv(const f32x4 (&acc)[2], int ck, const float* bq, __bf16* T, int q, int lg, float qscale, bool store, __bf16* qkv, size_t row) {
+  const int n0 = ck * 32 + lg * 8;
+  const float4 b0 = *reinterpret_cast<const float4*>(bq + n0), b1 = *reinterpret_cast<const float4*>(bq + n0 + 4);
+  bf16x8 o;
+  o[0] = (__bf16)(acc[0][0] + b0.x); o[1] = (__bf16)(acc[0][1] + b0.y); o[2] = (__bf16)(acc[0][2] + b0.z); o[3] = (__bf16)(acc[0][3] + b0.w);
+  o[4] = (__bf16)(acc[1][0] + b1.x); o[5] = (__bf16)(acc[1][1] + b1.y); o[6] = (__bf16)(acc[1][2] + b1.z); o[7] = (__bf16)(acc[1][3] + b1.w);
+  if (store) *reinterpret_cast<bf16x8*>(qkv + row * (3 * FB_C) + n0) = o;
+  if (ck < 3) {   // q: the softmax scale (and log2 e) goes onto the bf16 value, as the core kernel applies it to the q it reads from HBM
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (__bf16)((float)o[e] * qscale);
+  }
+  *reinterpret_cast<bf16x8*>(T + q * FB_LDT + n0) = o;
+}
+// attention of one window on its tile, one head at a time; lane -> query lr, keys nt*16 + lg*4 + j.  The head outputs overwrite the q columns.
+__device__ __forceinline__ void fb_attention(__bf16* T, const float (&bias)[FB_HEADS][4][4], const TokMap& tm, int q, int lr, int lg, bool store,
+                                             __bf16* att, size_t row) {
+  const bool masked = tm.seam();                                       // uniform over the window
+  const unsigned kdiff = masked ? seam_kdiff(tm, q, lg) : 0u;
+#pragma unroll
+  for (int h = 0; h < FB_HEADS; ++h) {
+    f32x4 s[4];
+    {
+      const bf16x8 qf = *reinterpret_cast<const bf16x8*>(T + q * FB_LDT + h * HD + lg * 8);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(T + (nt * 16 + lr) * FB_LDT + FB_C + h * HD + lg * 8);
+        s[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+      }
+    }
+    // key padding: bias = -1e30 and the padded K rows are finite (LayerNorm of a zero row = beta)
+    const float inv = softmax_lane<true, false>(s, bias[h], 1.f, masked, kdiff);
+    bf16x8 pf[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { pf[ks][j] = (__bf16)(s[2 * ks][j] * inv); pf[ks][4 + j] = (__bf16)(s[2 * ks + 1][j] * inv); }
+    f32x4 o[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        // V^T fragment of block nt: MFMA row lr <- head channel 8 (lr >> 2) + 4 nt + (lr & 3) (the chunk permutation of the weight rows: the
+        // lanes with lr & 3 = c supply the 4-column group that the lanes with lr >> 2 = c receive), the 8 keys of this lane group in the order
+        // the P fragment holds them: keys 32 ks + 4 lg .. + 3 and 32 ks + 16 + 4 lg .. + 3
+        const __bf16* src = T + (2 * ks * 16 + lg * 4 + (lr >> 2)) * FB_LDT + 2 * FB_C + h * HD + (lr & 3) * 8 + nt * 4;
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_a*)(src));
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_a*)(src + 16 * FB_LDT));
+        const bf16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        o[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[ks], o[nt], 0, 0, 0);
+      }
+    bf16x8 ob;                                                         // lane -> query lr, head channels 8 lg .. 8 lg + 7
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { ob[j] = (__bf16)o[0][j]; ob[4 + j] = (__bf16)o[1][j]; }
+    if (store) *reinterpret_cast<bf16x8*>(att + row * FB_C + h * HD + lg * 8) = ob;
+    *reinterpret_cast<bf16x8*>(T + q * FB_LDT + h * HD + lg * 8) = ob;   // over this wave's own q rows
+  }
+}
+// x1 chunk ck = x + s * (acc + bp)
+__device__ __forceinline__ void fb_put_x1(const f32x4 (&acc)[2], int ck, const float* bp, int lg, float sc, const bf16x8& xr, __bf16* x1_row) {
+  const int n0 = ck * 32 + lg * 8;
+  const float4 b0 = *reinterpret_cast<const float4*>(bp + n0), b1 = *reinterpret_cast<const float4*>(bp + n0 + 4);
+  const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+  bf16x8 y;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] = (__bf16)((float)xr[e] + sc * (acc[e >> 2][e & 3] + bb[e]));
+  *reinterpret_cast<bf16x8*>(x1_row + n0) = y;
+}
+
 __global__ __launch_bounds__(512, 1) void swin_attn_block_fwd_kernel(const BlockFwdArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char fb_smem[FB_SMEM];
   __bf16* Wq = reinterpret_cast<__bf16*>(fb_smem);          // [288][FB_LDW]  qkv.weight rows (out, in), rows permuted inside 32-row chunks (below)
@@ -1558,6 +1633,146 @@ __global__ __launch_bounds__(512, 1) void swin_attn_block_fwd_kernel(const Block
         }
       }
     }
+  }
+}
+
+// ---- MXFP8 forward of the same branch (opt-in sibling of swin_attn_block_fwd_kernel; sv_swin_attn_block_fwd_mx) --------------------------------
+// The unfused MX chain composed in one kernel: sv_layernorm_quant_mx_fwd -> sv_linear_mxfp8 (bias) -> sv_window_attention_fwd_mxq (bf16 core) ->
+// sv_linear_mxfp8 (bias, residual x, row_scale per image).  qkv and proj run on v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 x e4m3, cbsz = blgp = 0,
+// E8M0 block scales as the two scale operands), ONE scaled MFMA per 16-column tile: Kp = roundup(96, 128) = 128 is a single k-step, bytes 96 .. 127
+// are zero and block 3 carries scale byte 127.  No quantiser pass: LN(x) is quantised in the registers it is computed in, the head outputs from
+// the wave's own rows of the LDS tile - one head of one token (32 channels) is exactly one MX block.  NORMATIVE recipe: linear_fp8.hip "MX recipe";
+// the rounding is mx_block_exp / pack4_e4m3_mx (common.h), the quantiser, the prologue and the fragment reads are mx_frag.h's.
+//   lanes         token q = 16 wave + t on lane (t, lg) everywhere (geometry, window walk and barriers of the bf16 kernel: 512 threads, two window
+//                 groups, 4 waves x 16 rows per window).  B operand (mx_frag.h): the lane holds channels 16 lg .. + 15 and 64 + 16 lg .. + 15 of its
+//                 token, lane groups 2 and 3 zeros in the upper half.  A operand: 16 weight rows per tile; tile 2 ck + hf, MFMA row i is output column
+//                 32 ck + 8 (i >> 2) + 4 hf + (i & 3) (fbm_pack_row: the bf16 kernel's order), so the accumulators of a chunk's two tiles are the 8
+//                 consecutive columns 32 ck + 8 lg .. + 7 of the lane's token: qkv, att and x1 keep the 16-byte accesses and the epilogues
+//                 (fb_put_qkv, fb_put_x1) and the attention core (fb_attention) of the bf16 kernel.
+//   LayerNorm     mx_layernorm on the B-operand layout (ln1 leaves as two + two 16-byte vectors), then mx_quant_frag.
+//   proj operand  att (bf16, in the q columns of the wave's own tile rows) is read back in the B-operand layout - 2 + 2 ds_read_b128 - and goes
+//                 through mx_quant_frag: blocks 0 / 1 / 2 are heads 0 / 1 / 2.
+//   x             each window's rows are loaded where mx_layernorm needs them.  Fetching the NEXT window's rows ahead (as the bf16 kernel does) was
+//                 built and measured: 208 VGPRs instead of 176 and 9 % SLOWER in the training form, level in the inference form - the
+//                 kernel is not waiting for x.
+//   residual      x arrives in the B-operand layout but x1 leaves in the chunk layout, so the residual is RE-READ from x in front of the projection
+//                 epilogue: 3 x 16 bytes per lane = 192 bytes per token from L2 (the row was fetched by this very wave earlier in the window).
+//                 Carrying it across would cost a second tile (64 x 96 bf16 = 12 KB per window) and a write + read of LDS per token.
+//   weights       resident in LDS for the life of the workgroup in fragment order (every A fragment: two ds_read_b128, its scale one byte per lane).
+// Pack image (sv_swin_attn_block_mx_pack, bytes):  WF [24 tiles][2 halves][64 lanes][16] | WS [24 tiles][64 lanes]; tiles 0 - 17 are qkv.weight's
+// rows, tiles 18 - 23 proj.weight's; lane (r, lg) of tile T holds row fbm_pack_row(T, r), its bytes k = 16 lg .. + 15 (half 0) and 64 + 16 lg ..
+// + 15 (half 1), and that row's scale byte lg.  The bytes are sv_quant_rows_mx_e4m3's, re-ordered, never re-quantised.
+// LDS: 48 KB fragments + 1.5 KB scale bytes + 2 x 37 KB q | k | v tiles (FB_LDT) + 4.3 KB tables = 127.8 KB.
+constexpr int FBM_QKV_TILES = 18, FBM_TILES = 24;
+constexpr int FBM_WS = FBM_TILES * 2048, FBM_PACK_BYTES = FBM_WS + FBM_TILES * 64;
+constexpr int FBM_SMEM = FBM_PACK_BYTES + 2 * 64 * FB_LDT * 2 + (3 * 176 + 288 + 3 * 96) * 4;
+struct BlockFwdMxArgs : BlockFwdArgs { const uint8_t* packs; };   // wqkv / wproj stay NULL
+
+// The ONLY copy of the row order of the image: output column (0 .. 287 of qkv, then 288 + 0 .. 95 of proj) of MFMA row r of tile T
+__host__ __device__ __forceinline__ int fbm_pack_row(int T, int r) { return 32 * (T >> 1) + 8 * (r >> 2) + 4 * (T & 1) + (r & 3); }
+
+__global__ __launch_bounds__(256) void swin_attn_block_mx_pack_kernel(const uint8_t* __restrict__ wqkv_q, const uint8_t* __restrict__ wqkv_s,
+                                                                      const uint8_t* __restrict__ wproj_q, const uint8_t* __restrict__ wproj_s,
+                                                                      uint8_t* __restrict__ packs) {
+  const int e = blockIdx.x * 256 + threadIdx.x;              // item (tile, lane)
+  if (e >= FBM_TILES * 64) return;
+  const int T = e >> 6, lane = e & 63, lg = lane >> 4;
+  const int n = fbm_pack_row(T, lane & 15);
+  const bool proj = T >= FBM_QKV_TILES;
+  const uint8_t* q = proj ? wproj_q + (size_t)(n - 3 * FB_C) * 128 : wqkv_q + (size_t)n * 128;
+  const uint8_t* s = proj ? wproj_s + (n - 3 * FB_C) * 4 : wqkv_s + n * 4;
+  mx_pack_item(q + 16 * lg, s[lg], packs, packs + FBM_WS, e);
+}
+
+__global__ __launch_bounds__(512, 1) void swin_attn_block_fwd_mx_kernel(const BlockFwdMxArgs p) {
+  __shared__ __attribute__((aligned(16))) unsigned char fbm_smem[FBM_SMEM];
+  const uint8_t* WF = fbm_smem;                              // [24][2][64][16] weight fragments
+  const uint8_t* WS = fbm_smem + FBM_WS;                     // [24][64] their scale bytes
+  __bf16* Tb = reinterpret_cast<__bf16*>(fbm_smem + FBM_PACK_BYTES);   // 2 x [64][FB_LDT]  q (-> O) | k | v of the two windows in flight
+  float* bt = reinterpret_cast<float*>(Tb + 2 * 64 * FB_LDT);   // [3][176] relative-position bias table per head, times log2 e
+  float* bq = bt + 3 * 176;                                  // [288] qkv bias
+  float* bp = bq + 288;                                      // [96] proj bias
+  float* lng = bp + 96;                                      // [96] norm1 weight
+  float* lnb = lng + 96;                                     // [96] norm1 bias
+  const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, grp = tid >> 8;
+  const int lr = lane & 15, lg = lane >> 4;
+  for (int i = tid; i < FBM_PACK_BYTES / 16; i += 512) reinterpret_cast<i32x4*>(fbm_smem)[i] = reinterpret_cast<const i32x4*>(p.packs)[i];
+  for (int i = tid; i < 3 * 169; i += 512) { const int h = i / 169, e = i - h * 169; bt[h * 176 + e] = p.table[e * FB_HEADS + h] * ATTN_LOG2E; }
+  for (int i = tid; i < 288; i += 512) bq[i] = p.bqkv[i];
+  if (tid < 96) { bp[tid] = p.bproj[tid]; lng[tid] = p.ln_g[tid]; lnb[tid] = p.ln_b[tid]; }
+  __syncthreads();
+
+  const int q = wave * 16 + lr;                      // the token (query) of this lane: B-operand column and transposed accumulator alike
+  const bool qok = q < WT;
+  float bias[FB_HEADS][4][4];
+#pragma unroll
+  for (int h = 0; h < FB_HEADS; ++h) lane_bias(bias[h], bt + h * 176, q, lg);
+  __bf16* T = Tb + grp * 64 * FB_LDT;
+  const int nWx = p.W / 7, nW = (p.H / 7) * nWx;
+  const long long task0 = ((long long)blockIdx.x * 2 + grp) * p.tasks_per_group;
+  const float qscale = p.scale * ATTN_LOG2E;
+  const bool hi_live = lg < 2;                       // channels 64 + 16 lg .. + 15 exist (C = 96)
+  auto to_bf16x8 = [](const float* v) { bf16x8 b; for (int e = 0; e < 8; ++e) b[e] = (__bf16)v[e]; return b; };
+
+  TokMap tm = task_map(task0 < p.ntasks ? task0 : 0, nW, nWx, p.H, p.W, p.shift);
+  const int qty = (qok ? q : 0) / 7, qtx = (qok ? q : 0) - qty * 7;       // this lane's token inside the window
+  for (int tt = 0; tt < p.tasks_per_group; ++tt) {
+    const bool valid = task0 + tt < p.ntasks && qok;                     // a dead window is uniform over its 4 waves
+    int ys = tm.wy * 7 + qty + tm.shift; if (ys >= tm.H) ys -= tm.H;
+    int xs = tm.wx * 7 + qtx + tm.shift; if (xs >= tm.W) xs -= tm.W;
+    const size_t row = ((size_t)tm.img * tm.H + ys) * tm.W + xs;
+    // ---- LayerNorm of the lane's token on the B-operand layout -> MX fragment of qkv; padded tokens load zeros (LayerNorm = beta: finite keys)
+    i32x8 xq; int xsb;
+    {
+      float xv[2][16], mean, rstd;
+      mx_layernorm<FB_C, false>(p.x, (long long)row, valid, lg, lng, lnb, p.eps, xv, mean, rstd);
+      if (valid && p.ln1) {
+        __bf16* dst = p.ln1 + row * FB_C + 16 * lg;
+        *reinterpret_cast<bf16x8*>(dst) = to_bf16x8(xv[0]); *reinterpret_cast<bf16x8*>(dst + 8) = to_bf16x8(xv[0] + 8);
+        if (hi_live) { *reinterpret_cast<bf16x8*>(dst + 64) = to_bf16x8(xv[1]); *reinterpret_cast<bf16x8*>(dst + 72) = to_bf16x8(xv[1] + 8); }
+        if (lg == 0) { p.mean[row] = mean; p.rstd[row] = rstd; }
+      }
+      mx_quant_frag(xv, xq, xsb, lane);
+    }
+    // ---- qkv = bf16(acc + b), one 32-column chunk (= one head of q, k or v) = two scaled MFMAs at a time
+#pragma unroll 3
+    for (int ck = 0; ck < 9; ++ck) {
+      f32x4 acc[2];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        acc[hf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(mx_a_frag(WF, 2 * ck + hf, lane), xq, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0,
+                                                                   mx_a_scale(WS, 2 * ck + hf, lane), 0, xsb);
+      fb_put_qkv(acc, ck, bq, T, q, lg, qscale, valid && p.qkv, p.qkv, row);
+    }
+    __syncthreads();                                                     // all key / value rows of both windows are in LDS
+    fb_attention(T, bias, tm, q, lr, lg, valid && p.att, p.att, row);
+    __syncthreads();                                                     // keys / values are consumed: the next window may overwrite them
+    // ---- x1 = x + s * (att_q Wp_q^T + bp): att from the wave's own tile rows, one block per head
+    {
+      float av[2][16];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          bf16x8 raw = VecN<__bf16, 8>::zero();
+          if (hf == 0 || hi_live) raw = *reinterpret_cast<const bf16x8*>(T + q * FB_LDT + 64 * hf + 16 * lg + 8 * u);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) av[hf][8 * u + e] = (float)raw[e];
+        }
+      i32x8 aq; int asb;
+      mx_quant_frag(av, aq, asb, lane);
+      const float sc = valid && p.row_scale ? p.row_scale[tm.img] : 1.f;
+#pragma unroll
+      for (int ck = 0; ck < 3; ++ck) {
+        f32x4 acc[2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf)
+          acc[hf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(mx_a_frag(WF, FBM_QKV_TILES + 2 * ck + hf, lane), aq, (f32x4){0.f, 0.f, 0.f, 0.f},
+                                                                     0, 0, 0, mx_a_scale(WS, FBM_QKV_TILES + 2 * ck + hf, lane), 0, asb);
+        if (valid) fb_put_x1(acc, ck, bp, lg, sc, *reinterpret_cast<const bf16x8*>(p.x + row * FB_C + ck * 32 + lg * 8), p.x1 + row * FB_C);
+      }
+    }
+    if (++tm.wx == nWx) { tm.wx = 0; if (++tm.wy == p.H / 7) { tm.wy = 0; ++tm.img; } }
   }
 }
 
@@ -2051,28 +2266,74 @@ extern "C" int sv_swin_attn_block_supported(int C, int heads, int act_dtype, int
   return C == FB_C && heads == FB_HEADS && act_dtype == SV_BF16 && math == SV_MATH_BF16;
 }
 
-extern "C" int sv_swin_attn_block_fwd(const void* x, const float* ln_g, const float* ln_b, const float* wqkv, const float* bqkv, const float* table,
-                                      const float* wproj, const float* bproj, const float* row_scale, void* x1, void* ln1, float* mean,
-                                      float* rstd, void* qkv, void* att, int I, int H, int W, int C, int heads, int shift, float eps,
-                                      int act_dtype, void* stream) {
-  SV_REQUIRE(x && ln_g && ln_b && wqkv && bqkv && table && wproj && bproj && x1 && I > 0, "swin_attn_block_fwd: null/empty argument");
-  SV_REQUIRE(C == FB_C && heads == FB_HEADS && act_dtype == SV_BF16, "swin_attn_block_fwd: built for C = 96, 3 heads, bf16 token rows (got C=%d heads=%d dtype=%d)",
+// What sv_swin_attn_block_fwd and sv_swin_attn_block_fwd_mx ask alike, and the arguments and launch geometry they share; `who` names the entry
+// that was called, `weights` are its weight operands (fp32 matrices or the MX pack): all present, or-ed together for the alignment rule.
+static int block_fwd_args(const char* who, BlockFwdArgs& a, bool weights, uintptr_t weight_bits, const void* x, const float* ln_g, const float* ln_b,
+                          const float* bqkv, const float* table, const float* bproj, const float* row_scale, void* x1, void* ln1, float* mean,
+                          float* rstd, void* qkv, void* att, int I, int H, int W, int C, int heads, int shift, float eps, int act_dtype) {
+  SV_REQUIRE(x && ln_g && ln_b && weights && bqkv && table && bproj && x1 && I > 0, "%s: null/empty argument", who);
+  SV_REQUIRE(C == FB_C && heads == FB_HEADS && act_dtype == SV_BF16, "%s: built for C = 96, 3 heads, bf16 token rows (got C=%d heads=%d dtype=%d)", who,
              C, heads, act_dtype);
-  if (int rc = win_geom_check("swin_attn_block_fwd", H, W, shift)) return rc;
+  if (int rc = win_geom_check(who, H, W, shift)) return rc;
   const bool side = ln1 || mean || rstd || qkv || att;
-  SV_REQUIRE(!side || (ln1 && mean && rstd && qkv && att), "swin_attn_block_fwd: the side outputs (ln1, mean, rstd, qkv, att) come all or none");
-  SV_REQUIRE((((uintptr_t)x | (uintptr_t)x1 | (uintptr_t)ln1 | (uintptr_t)qkv | (uintptr_t)att | (uintptr_t)wqkv | (uintptr_t)wproj) & 15) == 0,
-             "swin_attn_block_fwd: tensors must be 16-byte aligned");
-  BlockFwdArgs a{};
-  a.x = static_cast<const __bf16*>(x); a.ln_g = ln_g; a.ln_b = ln_b; a.wqkv = wqkv; a.bqkv = bqkv; a.table = table; a.wproj = wproj; a.bproj = bproj;
+  SV_REQUIRE(!side || (ln1 && mean && rstd && qkv && att), "%s: the side outputs (ln1, mean, rstd, qkv, att) come all or none", who);
+  SV_REQUIRE((((uintptr_t)x | (uintptr_t)x1 | (uintptr_t)ln1 | (uintptr_t)qkv | (uintptr_t)att | weight_bits) & 15) == 0,
+             "%s: tensors must be 16-byte aligned", who);
+  a.x = static_cast<const __bf16*>(x); a.ln_g = ln_g; a.ln_b = ln_b; a.bqkv = bqkv; a.table = table; a.bproj = bproj;
   a.row_scale = row_scale; a.x1 = static_cast<__bf16*>(x1); a.ln1 = static_cast<__bf16*>(ln1); a.qkv = static_cast<__bf16*>(qkv);
   a.att = static_cast<__bf16*>(att); a.mean = mean; a.rstd = rstd;
   a.I = I; a.H = H; a.W = W; a.shift = shift; a.eps = eps; a.scale = 1.0f / sqrtf((float)HD);
   a.ntasks = I * (H / 7) * (W / 7);
   a.tasks_per_group = block_share(a.ntasks, false);
-  const int nblocks = cdiv(a.ntasks, 2 * a.tasks_per_group);
-  hipLaunchKernelGGL(swin_attn_block_fwd_kernel, dim3(nblocks), dim3(512), 0, (hipStream_t)stream, a);
+  return SV_OK;
+}
+static inline unsigned block_fwd_grid(const BlockFwdArgs& a) { return (unsigned)cdiv(a.ntasks, 2 * a.tasks_per_group); }
+
+extern "C" int sv_swin_attn_block_fwd(const void* x, const float* ln_g, const float* ln_b, const float* wqkv, const float* bqkv, const float* table,
+                                      const float* wproj, const float* bproj, const float* row_scale, void* x1, void* ln1, float* mean,
+                                      float* rstd, void* qkv, void* att, int I, int H, int W, int C, int heads, int shift, float eps,
+                                      int act_dtype, void* stream) {
+  BlockFwdArgs a{};
+  if (int rc = block_fwd_args("swin_attn_block_fwd", a, wqkv && wproj, (uintptr_t)wqkv | (uintptr_t)wproj, x, ln_g, ln_b, bqkv, table, bproj, row_scale,
+                              x1, ln1, mean, rstd, qkv, att, I, H, W, C, heads, shift, eps, act_dtype))
+    return rc;
+  a.wqkv = wqkv; a.wproj = wproj;
+  hipLaunchKernelGGL(swin_attn_block_fwd_kernel, dim3(block_fwd_grid(a)), dim3(512), 0, (hipStream_t)stream, a);
   return check_launch("sv_swin_attn_block_fwd");
+}
+
+// ---- MXFP8 forward of the branch (swin_attn_block_fwd_mx_kernel) ------------------------------------------------------------------------
+static inline bool block_mx_supported(int C, int heads) { return C == FB_C && heads == FB_HEADS; }
+static std::atomic<long long> swin_attn_block_mx_launches{0};
+extern "C" long long sv_swin_attn_block_mx_launches(void) { return swin_attn_block_mx_launches.load(std::memory_order_relaxed); }
+extern "C" int sv_swin_attn_block_mx_supported(int C, int heads) { return block_mx_supported(C, heads) ? 1 : 0; }
+extern "C" long long sv_swin_attn_block_mx_pack_bytes(int C) { return C == FB_C ? FBM_PACK_BYTES : 0; }
+
+extern "C" int sv_swin_attn_block_mx_pack(const void* wqkv_q, const void* wqkv_s, const void* wproj_q, const void* wproj_s, void* packs, int C,
+                                          void* stream) {
+  SV_REQUIRE(wqkv_q && wqkv_s && wproj_q && wproj_s && packs, "sv_swin_attn_block_mx_pack: null pointer");
+  SV_REQUIRE(C == FB_C, "sv_swin_attn_block_mx_pack: unsupported C=%d (96)", C);
+  SV_REQUIRE((((uintptr_t)wqkv_q | (uintptr_t)wproj_q | (uintptr_t)packs) & 15) == 0,
+             "sv_swin_attn_block_mx_pack: wqkv_q, wproj_q and packs must be 16-byte aligned");
+  hipLaunchKernelGGL(swin_attn_block_mx_pack_kernel, dim3(cdiv(FBM_TILES * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                     static_cast<const uint8_t*>(wqkv_q), static_cast<const uint8_t*>(wqkv_s), static_cast<const uint8_t*>(wproj_q),
+                     static_cast<const uint8_t*>(wproj_s), static_cast<uint8_t*>(packs));
+  return check_launch("sv_swin_attn_block_mx_pack");
+}
+
+extern "C" int sv_swin_attn_block_fwd_mx(const void* x, const float* ln_g, const float* ln_b, const void* packs_mx, const float* bqkv,
+                                         const float* table, const float* bproj, const float* row_scale, void* x1, void* ln1, float* mean,
+                                         float* rstd, void* qkv, void* att, int I, int H, int W, int C, int heads, int shift, float eps,
+                                         int act_dtype, void* stream) {
+  BlockFwdMxArgs a{};
+  if (int rc = block_fwd_args("sv_swin_attn_block_fwd_mx", a, packs_mx != nullptr, (uintptr_t)packs_mx, x, ln_g, ln_b, bqkv, table, bproj, row_scale,
+                              x1, ln1, mean, rstd, qkv, att, I, H, W, C, heads, shift, eps, act_dtype))
+    return rc;
+  a.packs = static_cast<const uint8_t*>(packs_mx);
+  hipLaunchKernelGGL(swin_attn_block_fwd_mx_kernel, dim3(block_fwd_grid(a)), dim3(512), 0, (hipStream_t)stream, a);
+  const int rc = check_launch("sv_swin_attn_block_fwd_mx");
+  if (rc == SV_OK) swin_attn_block_mx_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
 }
 
 extern "C" int sv_swin_attn_block_windows_per_group(int I, int H, int W, int backward) {

@@ -25,6 +25,7 @@
 //                         it is off or says no, the weight gradients stay on swin_mlp_wgrad_kernel.
 // bf16 storage + bf16 MFMA only (the exact-fp32 parity mode keeps the unfused chain); C = 96, 128, 192 (Swin-T stages 0-1, Swin-B stage 0).
 #include "common.h"
+#include "mx_frag.h"
 #include <atomic>
 
 namespace sv {
@@ -716,9 +717,8 @@ static inline bool mlp_supported(int C) { return C == 96 || C == 128 || C == 192
 // Pack image (sv_swin_mlp_mx_pack, bytes):  W1F [G][8 tiles][2 halves][64 lanes][16] | W2F [G][C/16][2][64][16] | W1S [G][8][64] | W2S [G][C/16][64],  G = 4C / 128.
 // The data gradient (swin_mlp_bwd_mx_kernel) runs the same pieces through the same code: MxImages / mx_pack_hidden_rows / mx_pack_channel_rows (the two
 // kinds of image and the only copy of the hidden-unit order), mx_a_frag / mx_a_scale (A fragment read), mx_layernorm (prologue), mx_quant_frag (token
-// rows -> B fragment) and mx_quant_acc (accumulator tiles -> elementwise operation -> B fragment).
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+// rows -> B fragment) and mx_quant_acc (accumulator tiles -> elementwise operation -> B fragment).  mx_pack_item, mx_a_frag / mx_a_scale, mx_quant_frag
+// and mx_layernorm live in mx_frag.h: the fused attention branch (attn.hip, swin_attn_block_fwd_mx_kernel) runs them too.
 
 // The two kinds of image a pack is made of, for width C (usable at compile time and, in the pack kernels and on the host, at run time).  A
 // "hidden-row" image holds a [4C][128] operand (W1, W2^T) as [G][8 tiles][2][64][16] bytes + [G][8][64] scale bytes, a "channel-row" image a [C][4C]
@@ -737,13 +737,6 @@ struct MlpMx : MxImages {                                  // the forward's pack
         PACK_ITEMS(HROW_SCALES + CROW_SCALES) {}
 };
 
-// item e = (tile, lane) of an image: the lane's two 16-byte halves (k = 16 lg .. and 64 + 16 lg .. of the row's 128-wide k-step at `src`) and its scale byte
-__device__ __forceinline__ void mx_pack_item(const uint8_t* src, uint8_t scale, uint8_t* data, uint8_t* scales, int e) {
-  i32x4* d = reinterpret_cast<i32x4*>(data) + (e >> 6) * 128 + (e & 63);
-  d[0] = *reinterpret_cast<const i32x4*>(src);
-  d[64] = *reinterpret_cast<const i32x4*>(src + 64);
-  scales[e] = scale;
-}
 // hidden-row image of q [4C][128], s [4C][4].  The ONLY copy of the hidden-unit order: tile j, row r of group g is hidden unit `hid`
 __device__ __forceinline__ void mx_pack_hidden_rows(const uint8_t* q, const uint8_t* s, uint8_t* data, uint8_t* scales, int e) {
   const int lane = e & 63, j = (e >> 6) & 7, g = e >> 9, r = lane & 15, lg = lane >> 4;
@@ -774,30 +767,6 @@ __global__ __launch_bounds__(256) void swin_mlp_mx_pack_kernel(const uint8_t* __
   else if (idx < L.PACK_ITEMS) mx_pack_channel_rows(w2q, w2s, packs + L.W2F, packs + L.W2S, idx - L.HROW_SCALES, L);
 }
 
-// maximum of a lane's value and that of lane ^ 16 (the other half of a 32-element MX block)
-__device__ __forceinline__ float pair16_max(float v) { float w = v; permlane16_pair(v, w); return fmaxf(v, w); }
-// the E8M0 byte lane group lg passes to the MFMA (block lg of the k-step) from the bytes the lanes know: lane group lg' knows blocks lg' >> 1 (its
-// registers 0-3, `elo`) and 2 + (lg' >> 1) (registers 4-7, `ehi`)
-__device__ __forceinline__ int mx_lane_scale(int elo, int ehi, int lane) {
-  const int lg = lane >> 4;
-  const int got = __shfl((elo + 127) | ((ehi + 127) << 8), (lane & 15) + 32 * (lg & 1));
-  return (got >> (8 * (lg >> 1))) & 0xff;
-}
-
-// a token's 16 + 16 values (registers 0-3 / 4-7 of a 128-wide k-step; already rounded to bf16) -> MX B fragment + the scale byte the lane passes
-__device__ __forceinline__ void mx_quant_frag(const float (&v)[2][16], i32x8& q, int& sbyte, int lane) {
-  int e[2];
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    float m = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(v[hf][j]));
-    e[hf] = mx_block_exp(pair16_max(m));
-#pragma unroll
-    for (int w = 0; w < 4; ++w) q[4 * hf + w] = (int)pack4_e4m3_mx(v[hf][4 * w], v[hf][4 * w + 1], v[hf][4 * w + 2], v[hf][4 * w + 3], e[hf]);
-  }
-  sbyte = mx_lane_scale(e[0], e[1], lane);
-}
 // a token's eight accumulator tiles of a group (tile j = 4 hf + jj: hidden units 64 hf + 16 lg + 4 jj .. + 3) -> MX B fragment of k-step g of the next
 // product + the scale byte the lane passes.  elem(j) returns tile j's four values after the elementwise operation, rounded to bf16.
 template <class Elem>
@@ -817,58 +786,6 @@ __device__ __forceinline__ void mx_quant_acc(Elem elem, i32x8& q, int& sbyte, in
     for (int jj = 0; jj < 4; ++jj) q[4 * hf + jj] = (int)pack4_e4m3_mx(v[jj][0], v[jj][1], v[jj][2], v[jj][3], e[hf]);
   }
   sbyte = mx_lane_scale(e[0], e[1], lane);
-}
-// A fragment of row tile `tile` of an image: two 16-byte reads at + 0 / + 1024 (ds_read_b128 where `data` is in LDS, global loads where it is the
-// pack in memory: the address space is inferred) - and its scale byte
-__device__ __forceinline__ i32x8 mx_a_frag(const uint8_t* data, int tile, int lane) {
-  const uint8_t* fa = data + (size_t)(tile * 2) * 1024 + lane * 16;
-  const i32x4 lo = *reinterpret_cast<const i32x4*>(fa), hi = *reinterpret_cast<const i32x4*>(fa + 1024);
-  return (i32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-__device__ __forceinline__ int mx_a_scale(const uint8_t* scales, int tile, int lane) { return scales[tile * 64 + lane]; }
-
-// LayerNorm prologue of lane (t, lg): the 16 + 16 channels 64 hf + 16 lg .. + 15 of token `tok` (zero for an invalid token and for the padding of
-// C = 96) -> xv = LayerNorm in fp32, rounded to bf16 as the unfused chain stores it; mean and rstd of the row.  The backward (WITH_DX2) passes dx2
-// as well: dv = bf16(dsc dx2) of the same channels, loaded under the same guard (sv_rowscale's value).
-template <int C, bool WITH_DX2>
-__device__ __forceinline__ void mx_layernorm(const __bf16* x1, long long tok, bool valid, int lg, const float* sgam, const float* sbet, float eps,
-                                             float (&xv)[2][16], float& mean, float& rstd, const __bf16* dx2 = nullptr, float dsc = 1.f,
-                                             float (*dv)[16] = nullptr) {
-  const bool hi_live = 64 + 16 * lg < C;                   // C = 96: channels 96 .. 127 are padding
-  float s = 0.f;
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      bf16x8 raw = VecN<__bf16, 8>::zero(), dr = VecN<__bf16, 8>::zero();
-      if (valid && (hf == 0 || hi_live)) {
-        raw = *reinterpret_cast<const bf16x8*>(x1 + tok * C + 64 * hf + 16 * lg + 8 * u);
-        if constexpr (WITH_DX2) dr = *reinterpret_cast<const bf16x8*>(dx2 + tok * C + 64 * hf + 16 * lg + 8 * u);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        xv[hf][8 * u + j] = (float)raw[j]; s += xv[hf][8 * u + j];
-        if constexpr (WITH_DX2) dv[hf][8 * u + j] = (float)(__bf16)(dsc * (float)dr[j]);
-      }
-    }
-  s = lane_step_add<16>(s); s = lane_step_add<32>(s);
-  mean = s * (1.f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf)
-    if (hf == 0 || hi_live)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { const float d = xv[hf][j] - mean; q += d * d; }
-  q = lane_step_add<16>(q); q = lane_step_add<32>(q);
-  rstd = rsqrtf(q * (1.f / C) + eps);
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    const bool live = hf == 0 || hi_live;
-    const int c0 = live ? 64 * hf + 16 * lg : 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      xv[hf][j] = live ? (float)(__bf16)((xv[hf][j] - mean) * rstd * sgam[c0 + j] + sbet[c0 + j]) : 0.f;
-  }
 }
 
 template <int C, int NW, int NTT>

@@ -64,7 +64,7 @@ _ACT_TYPED = {
     "sv_decoder_seed_fwd", "sv_decoder_seed_bwd", "sv_maxpool3d_fwd", "sv_maxpool3d_bwd", "sv_dropout", "sv_rowscale",
     "sv_dwconv2x2_fwd", "sv_dwconv2x2_bwd", "sv_upsample3to7_add_fwd", "sv_upsample3to7_bwd",
     "sv_cva_downsample_fwd", "sv_cva_downsample_bwd", "sv_cva_upsample_add_fwd", "sv_cva_upsample_bwd", "sv_decoder_head_fwd", "sv_decoder_head_bwd",
-    "sv_merge_views_fwd", "sv_merge_views_bwd", "sv_stem_space_to_depth", "sv_encoder_prep", "sv_encoder_prep_bwd", "sv_bn_act_maxpool_fwd", "sv_bn_maxpool_bwd", "sv_bn_act_maxpool3d_fwd", "sv_bn_maxpool3d_bwd", "sv_head_pack_x", "sv_head_unpack_dx", "sv_swin_attn_block_fwd", "sv_swin_attn_block_bwd",
+    "sv_merge_views_fwd", "sv_merge_views_bwd", "sv_stem_space_to_depth", "sv_encoder_prep", "sv_encoder_prep_bwd", "sv_bn_act_maxpool_fwd", "sv_bn_maxpool_bwd", "sv_bn_act_maxpool3d_fwd", "sv_bn_maxpool3d_bwd", "sv_head_pack_x", "sv_head_unpack_dx", "sv_swin_attn_block_fwd", "sv_swin_attn_block_fwd_mx", "sv_swin_attn_block_bwd",
     "sv_linear_fp8", "sv_linear_fp8_dgrad", "sv_linear_mxfp8", "sv_linear_mxfp8_dgrad",
 }
 # argument lists WITHOUT the act_dtype / stream tail (added in load())
@@ -174,6 +174,11 @@ _PROTOS = {
     "sv_swin_attn_block_windows_per_group": (_I, None, [_I, _I, _I, _I]),
     "sv_swin_attn_block_fwd": (_I, [_P] * 15 + [_I, _I, _I, _I, _I, _I, _F]),
     "sv_swin_attn_block_bwd": (_I, [_P] * 17 + [_I, _I, _I, _I, _I, _I]),
+    "sv_swin_attn_block_mx_supported": (_I, None, [_I, _I]),
+    "sv_swin_attn_block_mx_pack_bytes": (_L, None, [_I]),
+    "sv_swin_attn_block_mx_pack": (_I, [_P, _P, _P, _P, _P, _I]),
+    "sv_swin_attn_block_fwd_mx": (_I, [_P] * 14 + [_I, _I, _I, _I, _I, _I, _F]),
+    "sv_swin_attn_block_mx_launches": (_L, None),
     "sv_cross_view_attention_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I]),
     "sv_cross_view_attention_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "sv_transpose": (_I, [_P, _P, _I, _I, _I, _I, _I, _L, _L]),

@@ -185,10 +185,20 @@ def block_forward(blk: SwinBlock, x, I, training, stochastic, seeds, save=True):
             ln1, qkv, att = empty(M, Cd, like=x), empty(M, 3 * Cd, like=x), empty(M, Cd, like=x)
             m1, r1 = fempty(M, like=x), fempty(M, like=x)
         # LayerNorm-free products of the branch: qkv + QK^T + PV + proj per token; bytes: x in, x1 out (+ the 5 saved rows when training)
-        ops.traced_call("sv_swin_attn_block_fwd", 2.0 * M * Cd * 4 * Cd + 4.0 * 49 * 32 * M * blk.heads, esz * M * Cd * (7 if save else 2),
-                        ptr(x), ptr(blk.norm1.weight), ptr(blk.norm1.bias), ptr(a.qkv.weight), ptr(a.qkv.bias), ptr(a.relative_position_bias_table),
-                        ptr(a.proj.weight), ptr(a.proj.bias), ptr(sc1), ptr(x1), ptr(ln1), ptr(m1), ptr(r1), ptr(qkv), ptr(att),
-                        I, H, W, Cd, blk.heads, blk.shift, float(blk.norm1.eps), tag=f"M={M} C={Cd}")
+        flops, nbytes = 2.0 * M * Cd * 4 * Cd + 4.0 * 49 * 32 * M * blk.heads, esz * M * Cd * (7 if save else 2)
+        if ops.fused_attn_block_mx_enabled(Cd, blk.heads):
+            # opt-in MXFP8 forward (set_fused_attn_block_mx): qkv and proj on MX operands, quantised in registers; same side outputs, so the
+            # backward and the tape do not change
+            images = ops.swin_attn_block_mx_packs(a.qkv.weight, a.proj.weight, Cd)
+            ops.traced_call("sv_swin_attn_block_fwd_mx", flops, nbytes, ptr(x), ptr(blk.norm1.weight), ptr(blk.norm1.bias),
+                            ptr(images), ptr(a.qkv.bias), ptr(a.relative_position_bias_table),
+                            ptr(a.proj.bias), ptr(sc1), ptr(x1), ptr(ln1), ptr(m1), ptr(r1), ptr(qkv), ptr(att),
+                            I, H, W, Cd, blk.heads, blk.shift, float(blk.norm1.eps), tag=f"M={M} C={Cd}")
+        else:
+            ops.traced_call("sv_swin_attn_block_fwd", flops, nbytes,
+                            ptr(x), ptr(blk.norm1.weight), ptr(blk.norm1.bias), ptr(a.qkv.weight), ptr(a.qkv.bias), ptr(a.relative_position_bias_table),
+                            ptr(a.proj.weight), ptr(a.proj.bias), ptr(sc1), ptr(x1), ptr(ln1), ptr(m1), ptr(r1), ptr(qkv), ptr(att),
+                            I, H, W, Cd, blk.heads, blk.shift, float(blk.norm1.eps), tag=f"M={M} C={Cd}")
     else:
         # the fused attention backward reads ln1 and att as tensors: the branch then keeps its bf16 tape
         store_a = save and ops.linear_fp8_store() == "mx" and not ops.fused_attn_block_bwd_enabled(Cd, blk.heads)

@@ -553,6 +553,38 @@ def set_fused_attn_block(on: bool) -> None:
     _STATE["fused_attn_block"] = bool(on)
 
 
+def set_fused_attn_block_mx(on: bool) -> None:
+    """Opt-in (off by default; SV_FUSED_ATTN_BLOCK_MX=1 in the environment switches it on as well): under set_linear_fp8(True, recipe="mx") the
+    blocks that run the fused attention branch take its MXFP8 forward (sv_swin_attn_block_fwd_mx: the unfused MX chain norm1 -> qkv -> window
+    attention -> proj in one kernel, qkv and proj on MX operands quantised in registers, the attention core in bf16).  The backward is the fused
+    bf16 backward on the stored bf16 tensors, unchanged: the quantisers are straight-through, and the tape stays bf16 also under store "mx"."""
+    _STATE["fused_attn_block_mx"] = bool(on)
+
+
+def fused_attn_block_mx_enabled(C: int, heads: int) -> bool:
+    """The MXFP8 forward of the fused attention branch: the switch, the fused branch itself (so it is inert under set_attention_fp8 and
+    set_fused_attn_block(False)), MX linears, bf16 math and storage, C = 96 with 3 heads.  Inert everywhere else."""
+    if not _switch("fused_attn_block_mx", "SV_FUSED_ATTN_BLOCK_MX", False):
+        return False
+    return (fused_attn_block_enabled(C, heads) and linear_fp8_enabled() and linear_fp8_recipe() == "mx"
+            and _STATE["math"] == hip.MATH_BF16 and _STATE["store"] == torch.bfloat16
+            and hip.load().sv_swin_attn_block_mx_supported(C, heads) == 1)
+
+
+def swin_attn_block_mx_launches() -> int:
+    """sv_swin_attn_block_fwd_mx launches of this process so far."""
+    return int(hip.load().sv_swin_attn_block_mx_launches())
+
+
+def swin_attn_block_mx_packs(wqkv: torch.Tensor, wproj: torch.Tensor, C: int) -> torch.Tensor:
+    """The MX rows of qkv.weight / proj.weight (quantize_weight_mx: the unfused sites' bytes, from the module's pack cache) in the fragment
+    order of sv_swin_attn_block_fwd_mx."""
+    (wqq, wqs), (wpq, wps) = quantize_weight_mx(wqkv), quantize_weight_mx(wproj)
+    packs = torch.empty(int(hip.load().sv_swin_attn_block_mx_pack_bytes(C)), dtype=torch.uint8, device=wqkv.device)
+    call("sv_swin_attn_block_mx_pack", ptr(wqq), ptr(wqs), ptr(wpq), ptr(wps), ptr(packs), C)
+    return packs
+
+
 def set_attention_fp8(on: bool, backward: bool = False) -> None:
     """BASELINE configuration 5: QK^T and PV of the Swin window attention FORWARD on fp8 (OCP e4m3) MFMA operands with per-(window, head)
     scales; everything else keeps bf16 operands.  With backward=True the window-attention backward differentiates that fp8 forward
@@ -672,7 +704,9 @@ def set_linear_fp8(on: bool, backward: bool = False, recipe: str = "row", backwa
     Blocks that run the fused stage-0 kernels keep their bf16 operands (set_fused_attn_block(False) / set_fused_mlp(False) unfuse them).
     Under recipe "mx" set_fused_mlp_mx(True) (off by default) gives the fused MLP an MXFP8 forward of its own (sv_swin_mlp_fwd_mx), and
     set_fused_mlp_mx(True, backward=True) under backward_recipe "mx" an MXFP8 data gradient as well (sv_swin_mlp_bwd_mx), wgrad=True its MXFP8
-    weight gradients (sv_swin_mlp_wgrad_mx).
+    weight gradients (sv_swin_mlp_wgrad_mx).  set_fused_attn_block_mx(True) (off by default) does the same for the FORWARD of the fused attention
+    branch (sv_swin_attn_block_fwd_mx, C = 96 with 3 heads: qkv and proj on MX operands, the attention core in bf16); its backward stays the
+    fused bf16 backward on the bf16 tape.  With both switches on no Swin linear of the forward is left on bf16 operands.
     The LayerNorms that feed qkv, fc1 and the reduction emit the quantised rows themselves (set_ln_quant_fused).
     recipe = "row" (default): one fp32 scale per operand row, divided out in the epilogue.  recipe = "mx": the FORWARD of the same call sites
     on MX operands - one E8M0 power-of-two scale per 32 consecutive elements of the contraction, applied by the MFMA (sv_linear_mxfp8).  A block
