@@ -400,6 +400,46 @@ int sv_bn_bwd2_signs(const void* dz, int lddz, const void* signs, const void* x3
                      const float* save_rstd3, const void* xd, int ldxd, const float* gammad, const float* save_meand, const float* save_rstdd,
                      long long M, int C, void* dx3, int lddx3, void* dxd, int lddxd, float* dgamma3, float* dbeta3, float* dgammad, float* dbetad,
                      double* sums_ws3, double* sums_wsd, int act_dtype, void* stream);
+/* Launch plans of the token LayerNorm and the per-layer BatchNorm apply / backward (timm norm1 / norm2 behind models/swin_transformer.py:78;
+ * nn.BatchNorm2d/3d of models/encoder.py:22-23 and the other call sites above): which kernel family, access width and grids a call gets.  The
+ * entry points launch what the same pure host functions plan, so a caller (tests: the path they mean to exercise) can name the path of a
+ * shape without running it; the queries make no GPU call and look at the pointers for NULL and for their alignment only. */
+enum { SV_NORM_LN_FWD = 0,               /* ln_fwd_kernel (plain, row-quantising or MX: one geometry) */
+       SV_NORM_LN_BWD = 1,               /* ln_bwd_kernel, then ln_bwd_fold_kernel */
+       SV_NORM_BN_SCALAR = 2,            /* one element per access: any C, row stride and alignment */
+       SV_NORM_BN_NARROW = 3,            /* padded rows: C <= 16, row strides multiples of 4 and >= roundup4(C), 4-element aligned tensors */
+       SV_NORM_BN_VECTOR = 4 };          /* C % 4 == 0, row strides multiples of 4, 4-element aligned tensors, 16-byte aligned fp32 vectors */
+enum { SV_MASK_PLAIN = 0,                /* the apply pass of sv_bn_bwd masks dz itself: from z, or from x and the forward scale / shift */
+       SV_MASK_PREMASK = 1,              /* the reduce pass stores the masked gradient in dres, the apply pass reads it back mask-free */
+       SV_MASK_SIGN_APPLY = 2 };         /* the reduce pass stores dres, the apply pass masks dz from the sign words */
+typedef struct sv_norm_plan {
+  int family;                /* SV_NORM_* */
+  int merge;                 /* LayerNorm: 1 = the rows are the PatchMerging gather */
+  int storage;               /* SV_F32 / SV_BF16: element type the kernels are instantiated for */
+  int vec;                   /* elements per access: 4, or 8 (16 bytes of bf16); 1 in SV_NORM_BN_SCALAR */
+  int lanes;                 /* LayerNorm: lanes per row (16 / 32 / 64); BatchNorm: lanes across a row (SV_NORM_BN_VECTOR: 4 channels each), else 0 */
+  int nv;                    /* LayerNorm: chunks of `vec` elements per lane (1, 2, 3, 4, 6, 12) */
+  int mask;                  /* sv_bn_bwd: SV_MASK_* */
+  int launches;              /* entries of `launch` in use, in dispatch order (backward: reduce, fold, apply; LayerNorm backward: rows, fold) */
+  struct { int grid_x, grid_y, block, lds_bytes; } launch[3];
+  long long rows[2];         /* rows per workgroup of launch 0 (SV_NORM_BN_NARROW backward: per thread) and of the SV_NORM_BN_VECTOR apply launch;
+                                0 where the workgroups stride over the rows */
+} sv_norm_plan;
+/* kind 0: the plan of sv_layernorm_fwd, 1: of sv_layernorm_quant_fwd, 2: of sv_layernorm_quant_mx_fwd (a = x, b = y, c ignored), 3: of
+ * sv_layernorm_bwd (a = dy, b = x, c = dx) (timm LayerNorm behind models/swin_transformer.py:78).  Returns 0, or SV_ERR_INVALID with the
+ * entry's message for what the entry refuses about these arguments (rows, C, the merge map, act_dtype, a NULL x / dy / dx). */
+int sv_layernorm_plan(int kind, const void* a, const void* b, const void* c, long long rows, int C, int merge_H, int merge_W, int act_dtype,
+                      sv_norm_plan* plan);
+/* The plan of sv_scale_shift_act (signs == NULL) / sv_scale_shift_act_signs for these arguments (nn.BatchNorm2d/3d apply of
+ * models/encoder.py:22-23 and the other call sites above).  Returns what the entry point returns up to its launch. */
+int sv_scale_shift_act_plan(const void* x, int ldx, const float* scale, const float* shift, const void* residual, int ldr, void* y, int ldy,
+                            long long M, int C, int act, float slope, void* signs, int act_dtype, sv_norm_plan* plan);
+/* The plan of sv_bn_bwd (signs == NULL) / sv_bn_bwd_signs (z, fwd_scale, fwd_shift NULL) for these arguments (autograd of nn.BatchNorm2d/3d,
+ * models/encoder.py:22-23 and the other call sites above).  Returns what the entry point returns up to its launch. */
+int sv_bn_bwd_plan(const void* dz, int lddz, const void* z, int ldz, const void* signs, const void* x, int ldx, const float* gamma,
+                   const float* save_mean, const float* save_rstd, long long M, int C, int act, float slope, int training, void* dx, int lddx,
+                   void* dres, int lddres, float* dgamma, float* dbeta, double* sums_ws, const float* fwd_scale, const float* fwd_shift,
+                   int act_dtype, sv_norm_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------
  * Attention cores.  Window attention = timm WindowAttention + SwinTransformerBlock roll/partition/mask

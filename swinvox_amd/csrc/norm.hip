@@ -2,6 +2,7 @@
 // LayerNorm([C,H,W]) of the Swin stage heads, BatchNorm statistics / apply / backward on channels-last data.
 #include "common.h"
 #include <atomic>
+#include <initializer_list>
 
 namespace sv {
 
@@ -1379,55 +1380,39 @@ __global__ __launch_bounds__(256) void bn_pool3d_bwd_kernel(const AT* __restrict
 
 using namespace sv;
 
-template <bool MERGE, typename AT, int VEC>
-static void ln_fwd_launch(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, long long rows, int C,
-                          float eps, MergeMap mm, hipStream_t s) {
-  int lpr, nv;
-  ln_shape(C / VEC, lpr, nv);
-  const int rpb = 4 * (64 / lpr);   // rows per workgroup
-  SV_LN_DISPATCH(lpr, nv, hipLaunchKernelGGL((ln_fwd_kernel<MERGE, AT, VEC, LPR, NV>), dim3(cdiv(rows, rpb)), dim3(256), 0, s,
-                                             static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm););
+// What a token-LayerNorm call launches, for valid arguments: pure host code behind the four entries and sv_layernorm_plan.  a, b, c = the
+// activation tensors of the call (forward: x, y; backward: dy, x, dx), looked at for their alignment only.
+static sv_norm_plan ln_plan(bool bwd, long long rows, int C, int merge_H, int act_dtype, const void* a, const void* b, const void* c = nullptr) {
+  sv_norm_plan p{};
+  p.family = bwd ? SV_NORM_LN_BWD : SV_NORM_LN_FWD; p.merge = merge_H > 0; p.storage = act_dtype;
+  // VEC = 8 needs bf16 storage, 8-element channel groups (also of the un-merged map) and 16-byte aligned tensors
+  const bool v8 = act_dtype == SV_BF16 && C % 8 == 0 && (merge_H == 0 || (C / 4) % 8 == 0) && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+  p.vec = v8 ? 8 : 4; ln_shape(C / p.vec, p.lanes, p.nv);
+  const int rpi = 4 * (64 / p.lanes);                   // rows per workgroup (backward: per workgroup iteration)
+  long long rpb = bwd ? rows / 1024 : rpi; if (rpb < rpi) rpb = rpi; if (rpb > 256) rpb = 256;   // backward: >= ~1024 workgroups where the row count allows
+  p.rows[0] = rpb = (rpb + rpi - 1) / rpi * rpi;
+  p.launch[0] = {cdiv(rows, rpb), 1, 256, bwd ? (int)sizeof(float) * 2 * C : 0};
+  p.launch[1] = {cdiv(2 * C, 256), 1, 256, 0}; p.launches = bwd ? 2 : 1;     // ln_bwd_fold_kernel
+  return p;
 }
-template <bool MERGE, typename AT, int VEC>
-static void ln_quant_fwd_launch(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* q, int Kp,
-                                float* scales, long long rows, int C, float eps, MergeMap mm, hipStream_t s) {
-  int lpr, nv;
-  ln_shape(C / VEC, lpr, nv);
-  const int rpb = 4 * (64 / lpr);   // rows per workgroup
-  const LnQuantOut qo{static_cast<uint8_t*>(q), scales, Kp};
-  SV_LN_DISPATCH(lpr, nv, hipLaunchKernelGGL((ln_fwd_kernel<MERGE, AT, VEC, LPR, NV, LnQuantOut>), dim3(cdiv(rows, rpb)), dim3(256), 0, s,
-                                             static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm, qo););
+// (merge, VEC, storage type) of a plan as MERGE, AT, VEC for the statement: the one selection of the LayerNorm entries
+#define SV_LN_SELECT_AT(P_, ...)                                                                       \
+  if (P_.vec == 8) { typedef __bf16 AT; constexpr int VEC = 8; __VA_ARGS__ }                           \
+  else if (P_.storage == SV_BF16) { typedef __bf16 AT; constexpr int VEC = 4; __VA_ARGS__ }            \
+  else { typedef float AT; constexpr int VEC = 4; __VA_ARGS__ }
+#define SV_LN_SELECT(P_, ...)                                                                          \
+  do {                                                                                                 \
+    if (P_.merge) { constexpr bool MERGE = true; SV_LN_SELECT_AT(P_, __VA_ARGS__) }                    \
+    else { constexpr bool MERGE = false; SV_LN_SELECT_AT(P_, __VA_ARGS__) }                            \
+  } while (0)
+// qo: nothing (the plain forward), or the LnQuantOut / LnQuantMxOut of the quantising forms
+template <bool MERGE, typename AT, int VEC, typename... QO>
+static void ln_fwd_launch(const sv_norm_plan& p, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, long long rows, int C,
+                          float eps, int merge_H, int merge_W, void* stream, QO... qo) {
+  const MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
+  SV_LN_DISPATCH(p.lanes, p.nv, hipLaunchKernelGGL((ln_fwd_kernel<MERGE, AT, VEC, LPR, NV, QO...>), dim3(p.launch[0].grid_x), dim3(256), 0, (hipStream_t)stream,
+                                                   static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm, qo...););
 }
-template <bool MERGE, typename AT, int VEC>
-static void ln_quant_mx_fwd_launch(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* q, int Kp,
-                                   void* scales, long long rows, int C, float eps, MergeMap mm, hipStream_t s) {
-  int lpr, nv;
-  ln_shape(C / VEC, lpr, nv);
-  const int rpb = 4 * (64 / lpr);   // rows per workgroup
-  const LnQuantMxOut qo{static_cast<uint8_t*>(q), static_cast<uint8_t*>(scales), Kp};
-  SV_LN_DISPATCH(lpr, nv, hipLaunchKernelGGL((ln_fwd_kernel<MERGE, AT, VEC, LPR, NV, LnQuantMxOut>), dim3(cdiv(rows, rpb)), dim3(256), 0, s,
-                                             static_cast<const AT*>(x), gamma, beta, static_cast<AT*>(y), mean, rstd, rows, C, eps, mm, qo););
-}
-template <bool MERGE, typename AT, int VEC>
-static void ln_bwd_launch(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
-                          float* dbeta, long long rows, int C, MergeMap mm, int accumulate_dx, float* ws, hipStream_t s) {
-  int lpr, nv;
-  ln_shape(C / VEC, lpr, nv);
-  const int rpi = 4 * (64 / lpr);                       // rows per workgroup iteration
-  long long rpb = rows / 1024; if (rpb < rpi) rpb = rpi; if (rpb > 256) rpb = 256;   // >= ~1024 workgroups where the row count allows
-  rpb = (rpb + rpi - 1) / rpi * rpi;
-  const size_t lds = sizeof(float) * 2 * C;
-  SV_LN_DISPATCH(lpr, nv, hipLaunchKernelGGL((ln_bwd_kernel<MERGE, AT, VEC, LPR, NV>), dim3(cdiv(rows, rpb)), dim3(256), lds, s,
-                                             static_cast<const AT*>(dy), static_cast<const AT*>(x), gamma, mean, rstd, static_cast<AT*>(dx),
-                                             dgamma, dbeta, rows, C, mm, accumulate_dx, (int)rpb, ws););
-  hipLaunchKernelGGL(ln_bwd_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, s, ws, C, dgamma, dbeta);
-}
-// VEC = 8 needs bf16 storage, 8-element channel groups (also of the un-merged map) and 16-byte aligned tensors
-static inline bool ln_vec8(int act_dtype, int C, int merge_H, const void* a, const void* b, const void* c = nullptr) {
-  return act_dtype == SV_BF16 && C % 8 == 0 && (merge_H == 0 || (C / 4) % 8 == 0) &&
-         (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
-
 // the refusals both forward entries share (everything but the null checks of their outputs); `who` names the entry in the message
 static int ln_fwd_check(const char* who, const void* x, const float* gamma, const float* beta, long long rows, int C, int merge_H, int merge_W,
                         int act_dtype) {
@@ -1443,102 +1428,69 @@ extern "C" int sv_layernorm_fwd(const void* x, const float* gamma, const float* 
                                 long long rows, int C, float eps, int merge_H, int merge_W, int act_dtype, void* stream) {
   SV_REQUIRE(y && mean && rstd, "layernorm_fwd: null/empty argument");
   if (const int rc = ln_fwd_check("layernorm_fwd", x, gamma, beta, rows, C, merge_H, merge_W, act_dtype)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
-  const bool v8 = ln_vec8(act_dtype, C, merge_H, x, y);
-  if (merge_H > 0) {
-    if (v8) ln_fwd_launch<true, __bf16, 8>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
-    else if (act_dtype == SV_BF16) ln_fwd_launch<true, __bf16, 4>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
-    else ln_fwd_launch<true, float, 4>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
-  } else {
-    if (v8) ln_fwd_launch<false, __bf16, 8>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
-    else if (act_dtype == SV_BF16) ln_fwd_launch<false, __bf16, 4>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
-    else ln_fwd_launch<false, float, 4>(x, gamma, beta, y, mean, rstd, rows, C, eps, mm, s);
-  }
+  const sv_norm_plan p = ln_plan(false, rows, C, merge_H, act_dtype, x, y);
+  SV_LN_SELECT(p, ln_fwd_launch<MERGE, AT, VEC>(p, x, gamma, beta, y, mean, rstd, rows, C, eps, merge_H, merge_W, stream););
   return check_launch("sv_layernorm_fwd");
 }
-
-static std::atomic<long long> layernorm_quant_launches{0};
-
-extern "C" long long sv_layernorm_quant_launches(void) { return layernorm_quant_launches.load(std::memory_order_relaxed); }
-
-extern "C" int sv_layernorm_quant_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                                      void* q, int Kp, float* scales, long long rows, int C, float eps, int merge_H, int merge_W,
-                                      int act_dtype, void* stream) {
-  SV_REQUIRE(q && scales, "sv_layernorm_quant_fwd: q and scales must not be null");
-  SV_REQUIRE((mean == nullptr) == (rstd == nullptr), "sv_layernorm_quant_fwd: mean and rstd must be null together");
-  if (const int rc = ln_fwd_check("sv_layernorm_quant_fwd", x, gamma, beta, rows, C, merge_H, merge_W, act_dtype)) return rc;
-  SV_REQUIRE(C > 0 && Kp == (C + 127) / 128 * 128, "sv_layernorm_quant_fwd: Kp (%d) must be C (%d) rounded up to a multiple of 128", Kp, C);
-  SV_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)scales & 3) == 0, "sv_layernorm_quant_fwd: q must be 16-byte aligned, scales 4-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
-  const bool v8 = ln_vec8(act_dtype, C, merge_H, x, y);
-  if (merge_H > 0) {
-    if (v8) ln_quant_fwd_launch<true, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
-    else if (act_dtype == SV_BF16) ln_quant_fwd_launch<true, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
-    else ln_quant_fwd_launch<true, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
-  } else {
-    if (v8) ln_quant_fwd_launch<false, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
-    else if (act_dtype == SV_BF16) ln_quant_fwd_launch<false, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
-    else ln_quant_fwd_launch<false, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales, rows, C, eps, mm, s);
-  }
-  const int rc = check_launch("sv_layernorm_quant_fwd");
-  if (rc == SV_OK) layernorm_quant_launches.fetch_add(1, std::memory_order_relaxed);
+// The body of both quantising entries: QO = LnQuantOut (ST = float) or LnQuantMxOut (uint8_t); who / sname name the entry and its scale argument in the messages
+template <typename QO, typename ST>
+static int ln_quant_fwd(const char* who, const char* sname, std::atomic<long long>& launches, const void* x, const float* gamma, const float* beta, void* y,
+                        float* mean, float* rstd, void* q, int Kp, void* scales, long long rows, int C, float eps, int merge_H, int merge_W, int act_dtype, void* stream) {
+  SV_REQUIRE(q && scales, "%s: q and %s must not be null", who, sname);
+  SV_REQUIRE((mean == nullptr) == (rstd == nullptr), "%s: mean and rstd must be null together", who);
+  if (const int rc = ln_fwd_check(who, x, gamma, beta, rows, C, merge_H, merge_W, act_dtype)) return rc;
+  SV_REQUIRE(C > 0 && Kp == (C + 127) / 128 * 128, "%s: Kp (%d) must be C (%d) rounded up to a multiple of 128", who, Kp, C);
+  SV_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)scales & 3) == 0, "%s: q must be 16-byte aligned, %s 4-byte aligned", who, sname);
+  const sv_norm_plan p = ln_plan(false, rows, C, merge_H, act_dtype, x, y);
+  const QO qo{static_cast<uint8_t*>(q), static_cast<ST*>(scales), Kp};
+  SV_LN_SELECT(p, ln_fwd_launch<MERGE, AT, VEC>(p, x, gamma, beta, y, mean, rstd, rows, C, eps, merge_H, merge_W, stream, qo););
+  const int rc = check_launch(who);
+  if (rc == SV_OK) launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }
-
-static std::atomic<long long> layernorm_quant_mx_launches{0};
-
+static std::atomic<long long> layernorm_quant_launches{0}, layernorm_quant_mx_launches{0};
+extern "C" long long sv_layernorm_quant_launches(void) { return layernorm_quant_launches.load(std::memory_order_relaxed); }
 extern "C" long long sv_layernorm_quant_mx_launches(void) { return layernorm_quant_mx_launches.load(std::memory_order_relaxed); }
-
-extern "C" int sv_layernorm_quant_mx_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                                         void* q, int Kp, void* scales_u8, long long rows, int C, float eps, int merge_H, int merge_W,
-                                         int act_dtype, void* stream) {
-  SV_REQUIRE(q && scales_u8, "sv_layernorm_quant_mx_fwd: q and scales_u8 must not be null");
-  SV_REQUIRE((mean == nullptr) == (rstd == nullptr), "sv_layernorm_quant_mx_fwd: mean and rstd must be null together");
-  if (const int rc = ln_fwd_check("sv_layernorm_quant_mx_fwd", x, gamma, beta, rows, C, merge_H, merge_W, act_dtype)) return rc;
-  SV_REQUIRE(C > 0 && Kp == (C + 127) / 128 * 128, "sv_layernorm_quant_mx_fwd: Kp (%d) must be C (%d) rounded up to a multiple of 128", Kp, C);
-  SV_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)scales_u8 & 3) == 0,
-             "sv_layernorm_quant_mx_fwd: q must be 16-byte aligned, scales_u8 4-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
-  const bool v8 = ln_vec8(act_dtype, C, merge_H, x, y);
-  if (merge_H > 0) {
-    if (v8) ln_quant_mx_fwd_launch<true, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
-    else if (act_dtype == SV_BF16) ln_quant_mx_fwd_launch<true, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
-    else ln_quant_mx_fwd_launch<true, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
-  } else {
-    if (v8) ln_quant_mx_fwd_launch<false, __bf16, 8>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
-    else if (act_dtype == SV_BF16) ln_quant_mx_fwd_launch<false, __bf16, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
-    else ln_quant_mx_fwd_launch<false, float, 4>(x, gamma, beta, y, mean, rstd, q, Kp, scales_u8, rows, C, eps, mm, s);
-  }
-  const int rc = check_launch("sv_layernorm_quant_mx_fwd");
-  if (rc == SV_OK) layernorm_quant_mx_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
+extern "C" int sv_layernorm_quant_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* q, int Kp, float* scales,
+                                      long long rows, int C, float eps, int merge_H, int merge_W, int act_dtype, void* stream) {
+  return ln_quant_fwd<LnQuantOut, float>("sv_layernorm_quant_fwd", "scales", layernorm_quant_launches, x, gamma, beta, y, mean, rstd, q, Kp, scales,
+                                         rows, C, eps, merge_H, merge_W, act_dtype, stream);
+}
+extern "C" int sv_layernorm_quant_mx_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* q, int Kp, void* scales_u8,
+                                         long long rows, int C, float eps, int merge_H, int merge_W, int act_dtype, void* stream) {
+  return ln_quant_fwd<LnQuantMxOut, uint8_t>("sv_layernorm_quant_mx_fwd", "scales_u8", layernorm_quant_mx_launches, x, gamma, beta, y, mean, rstd, q,
+                                             Kp, scales_u8, rows, C, eps, merge_H, merge_W, act_dtype, stream);
 }
 
 extern "C" size_t sv_layernorm_bwd_workspace_floats(int C) { return (size_t)LN_BWD_SLOTS * 2 * C + 2; }
-
-extern "C" int sv_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                void* dx, float* dgamma, float* dbeta, float* workspace, long long rows, int C, int merge_H, int merge_W,
-                                int accumulate_dx, int act_dtype, void* stream) {
-  SV_REQUIRE(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && workspace && rows > 0, "layernorm_bwd: null/empty argument");
+// the refusals of the backward; given = every pointer the caller has to pass is there
+static int ln_bwd_check(bool given, long long rows, int C, int act_dtype, const float* gamma) {
+  SV_REQUIRE(given && rows > 0, "layernorm_bwd: null/empty argument");
   SV_REQUIRE(C % 4 == 0 && C <= 3072, "layernorm_bwd: C=%d unsupported", C);
   SV_REQUIRE_ACT(act_dtype);
   SV_REQUIRE(((uintptr_t)gamma & 15) == 0, "layernorm_bwd: gamma must be 16-byte aligned");
+  return SV_OK;
+}
+extern "C" int sv_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma, float* dbeta,
+                                float* workspace, long long rows, int C, int merge_H, int merge_W, int accumulate_dx, int act_dtype, void* stream) {
+  if (const int rc = ln_bwd_check(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && workspace, rows, C, act_dtype, gamma)) return rc;
+  const sv_norm_plan p = ln_plan(true, rows, C, merge_H, act_dtype, dy, x, dx);
+  const MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
   hipStream_t s = (hipStream_t)stream;
-  MergeMap mm{merge_H, merge_W, merge_H > 0 ? C / 4 : 0};
-  const bool v8 = ln_vec8(act_dtype, C, merge_H, dy, x, dx);
-  if (merge_H > 0) {
-    if (v8) ln_bwd_launch<true, __bf16, 8>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, mm, accumulate_dx, workspace, s);
-    else if (act_dtype == SV_BF16) ln_bwd_launch<true, __bf16, 4>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, mm, accumulate_dx, workspace, s);
-    else ln_bwd_launch<true, float, 4>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, mm, accumulate_dx, workspace, s);
-  } else {
-    if (v8) ln_bwd_launch<false, __bf16, 8>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, mm, accumulate_dx, workspace, s);
-    else if (act_dtype == SV_BF16) ln_bwd_launch<false, __bf16, 4>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, mm, accumulate_dx, workspace, s);
-    else ln_bwd_launch<false, float, 4>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, mm, accumulate_dx, workspace, s);
-  }
+  SV_LN_SELECT(p, SV_LN_DISPATCH(p.lanes, p.nv, hipLaunchKernelGGL((ln_bwd_kernel<MERGE, AT, VEC, LPR, NV>), dim3(p.launch[0].grid_x), dim3(256), p.launch[0].lds_bytes, s,
+                                                static_cast<const AT*>(dy), static_cast<const AT*>(x), gamma, mean, rstd, static_cast<AT*>(dx), dgamma, dbeta, rows, C,
+                                                mm, accumulate_dx, (int)p.rows[0], workspace);););
+  hipLaunchKernelGGL(ln_bwd_fold_kernel, dim3(p.launch[1].grid_x), dim3(256), 0, s, workspace, C, dgamma, dbeta);
   return check_launch("sv_layernorm_bwd");
+}
+extern "C" int sv_layernorm_plan(int kind, const void* a, const void* b, const void* c, long long rows, int C, int merge_H, int merge_W,
+                                 int act_dtype, sv_norm_plan* plan) {
+  static const char* const who[3] = {"layernorm_fwd", "sv_layernorm_quant_fwd", "sv_layernorm_quant_mx_fwd"};
+  alignas(16) static const float params[4] = {};      // stands in for gamma / beta, which the plan does not depend on
+  SV_REQUIRE(plan && kind >= 0 && kind <= 3, "layernorm_plan: null plan or bad kind %d", kind);
+  if (const int rc = kind == 3 ? ln_bwd_check(a && b && c, rows, C, act_dtype, params) : ln_fwd_check(who[kind], a, params, params, rows, C, merge_H, merge_W, act_dtype)) return rc;
+  *plan = ln_plan(kind == 3, rows, C, merge_H, act_dtype, a, b, kind == 3 ? c : nullptr);
+  return SV_OK;
 }
 
 // image slices of lnl_bwd_apply_kernel: enough workgroups for ~8 per CU, at least 8 images per slice
@@ -1619,44 +1571,79 @@ static inline bool aligned4(int act_dtype, const void* a, const void* b = nullpt
 
 // sign words of sv_scale_shift_act_signs / sv_bn_bwd_signs need the wave-per-row mapping of the vector kernels: G == 64 column groups
 static inline bool bn_signs_ok(int C) { return C % 256 == 0; }
-
-static int scale_shift_act_impl(const void* x, int ldx, const float* scale, const float* shift, const void* residual, int ldr,
-                                void* y, int ldy, long long M, int C, int act, float slope, unsigned long long* signs, int act_dtype, void* stream) {
+// ---- launch plans of the per-layer apply and backward: pure host code behind sv_scale_shift_act(_signs), sv_bn_bwd(_signs) and their queries
+struct BnRows { const void* p; int ld; };     // an activation tensor of the call and its row stride; p == nullptr: not given
+// A plan with the kernel family for rows of C channels: t = the activation tensors of the call, params = the fp32 vectors the vector kernels read as float4, OR-ed.
+// Vector and narrow kernels need row strides that are multiples of 4 and 4-element aligned tensors; the narrow ones own the padded row (roundup4(C) columns).
+static sv_norm_plan bn_family(int act_dtype, int C, std::initializer_list<BnRows> t, uintptr_t params) {
+  const int c4 = (C + 3) & ~3; bool ld4 = true, room = true; uintptr_t ptrs = 0;
+  for (const BnRows& r : t) if (r.p) { ld4 = ld4 && r.ld % 4 == 0; room = room && r.ld >= c4; ptrs |= (uintptr_t)r.p; }
+  sv_norm_plan p{};
+  if (!ld4 || !aligned4(act_dtype, (const void*)ptrs)) p.family = SV_NORM_BN_SCALAR;
+  else if (C % 4 == 0 && (params & 15) == 0) p.family = SV_NORM_BN_VECTOR;
+  else p.family = C <= BN_NARROW_MAXC && room ? SV_NORM_BN_NARROW : SV_NORM_BN_SCALAR;
+  p.storage = act_dtype; p.vec = p.family == SV_NORM_BN_SCALAR ? 1 : 4;
+  return p;
+}
+// vector family: G lanes across a row (4 channels each), RL rows per step of a workgroup, cg column groups along grid x
+struct BnVecGeom { int G, RL, cg; };
+static inline BnVecGeom bn_vec_geom(int C) { const int G = C / 4 < 64 ? C / 4 : 64; return {G, 256 / G, cdiv(C / 4, G)}; }
+static inline dim3 bn_grid(const sv_norm_plan& p, int i) { return dim3(p.launch[i].grid_x, p.launch[i].grid_y); }
+// p with launch i, its last = the apply pass of its family, the same grid forward and backward
+static sv_norm_plan plan_bn_apply(sv_norm_plan p, int i, long long M, int C) {
+  if (p.family == SV_NORM_BN_VECTOR) {
+    const BnVecGeom v = bn_vec_geom(C);
+    p.lanes = v.G; p.rows[1] = bn_rows_per_block(M, v.cg, 4096, 4 * v.RL);
+    p.launch[i] = {v.cg, cdiv(M, p.rows[1]), 256, 0};
+  } else {
+    long long blocks = p.family == SV_NORM_BN_NARROW ? (M + 63) / 64 : (M * C + 255) / 256; if (blocks > 8192) blocks = 8192;
+    p.launch[i] = {(int)blocks, 1, 256, 0};
+  }
+  p.launches = i + 1;
+  return p;
+}
+static sv_norm_plan plan_scale_shift_act(std::initializer_list<BnRows> t, uintptr_t params, long long M, int C, int act_dtype) {
+  return plan_bn_apply(bn_family(act_dtype, C, t, params), 0, M, C);
+}
+// arguments -> plan -> (query: report it) -> launch; behind sv_scale_shift_act, sv_scale_shift_act_signs and sv_scale_shift_act_plan
+static int scale_shift_act_impl(const void* x, int ldx, const float* scale, const float* shift, const void* residual, int ldr, void* y, int ldy,
+                                long long M, int C, int act, float slope, void* signs, int act_dtype, hipStream_t s, sv_norm_plan* query) {
   SV_REQUIRE(x && scale && shift && y && M > 0 && C > 0 && ldx >= C && ldy >= C, "scale_shift_act: bad arguments");
   SV_REQUIRE_ACT(act_dtype);
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (!residual || ldr % 4 == 0) && aligned4(act_dtype, x, y, residual) &&
-                   (((uintptr_t)scale | (uintptr_t)shift) & 15) == 0;
-  const bool narrow = !vec && C <= BN_NARROW_MAXC && (ldx % 4 == 0) && (ldy % 4 == 0) && ldx >= ((C + 3) & ~3) && ldy >= ((C + 3) & ~3) &&
-                      (!residual || (ldr % 4 == 0 && ldr >= ((C + 3) & ~3))) && aligned4(act_dtype, x, y, residual);
-  SV_REQUIRE(!signs || (vec && bn_signs_ok(C) && ((uintptr_t)signs & 15) == 0), "scale_shift_act_signs: needs C %% 256 == 0 and 4-aligned rows (C=%d)", C);
-  if (narrow) {
-    long long blocks = (M + 63) / 64; if (blocks > 8192) blocks = 8192;
-    SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(scale_shift_act_narrow_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const AT*>(x), ldx, scale, shift,
-                                                  static_cast<const AT*>(residual), ldr, static_cast<AT*>(y), ldy, M, C, act, slope););
-  } else if (vec) {
-    const int G = C / 4 < 64 ? C / 4 : 64, RL = 256 / G;
-    const int cg = cdiv(C / 4, G);
-    const long long rpb = bn_rows_per_block(M, cg, 4096, 4 * RL);
-    SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(scale_shift_act_cg_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, static_cast<const AT*>(x), ldx, scale, shift,
-                                                  static_cast<const AT*>(residual), ldr, static_cast<AT*>(y), ldy, M, C, act, slope, rpb, G, signs););
-  } else {
-    long long blocks = (M * C + 255) / 256; if (blocks > 8192) blocks = 8192;
-    SV_DISPATCH_ACT(act_dtype, hipLaunchKernelGGL(scale_shift_act_scalar_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const AT*>(x), ldx, scale, shift,
-                                                  static_cast<const AT*>(residual), ldr, static_cast<AT*>(y), ldy, M, C, act, slope););
-  }
+  const sv_norm_plan p = plan_scale_shift_act({{x, ldx}, {y, ldy}, {residual, ldr}}, (uintptr_t)scale | (uintptr_t)shift, M, C, act_dtype);
+  SV_REQUIRE(!signs || (p.family == SV_NORM_BN_VECTOR && bn_signs_ok(C) && ((uintptr_t)signs & 15) == 0),
+             "scale_shift_act_signs: needs C %% 256 == 0 and 4-aligned rows (C=%d)", C);
+  if (query) { *query = p; return SV_OK; }
+  SV_DISPATCH_ACT(act_dtype,
+    const AT* x_ = static_cast<const AT*>(x); const AT* r_ = static_cast<const AT*>(residual); AT* y_ = static_cast<AT*>(y);
+    switch (p.family) {
+      case SV_NORM_BN_NARROW:
+        hipLaunchKernelGGL(scale_shift_act_narrow_kernel<AT>, bn_grid(p, 0), dim3(256), 0, s, x_, ldx, scale, shift, r_, ldr, y_, ldy, M, C, act, slope);
+        break;
+      case SV_NORM_BN_VECTOR:
+        hipLaunchKernelGGL(scale_shift_act_cg_kernel<AT>, bn_grid(p, 0), dim3(256), 0, s, x_, ldx, scale, shift, r_, ldr, y_, ldy, M, C, act, slope, p.rows[1],
+                           p.lanes, static_cast<unsigned long long*>(signs));
+        break;
+      default:
+        hipLaunchKernelGGL(scale_shift_act_scalar_kernel<AT>, bn_grid(p, 0), dim3(256), 0, s, x_, ldx, scale, shift, r_, ldr, y_, ldy, M, C, act, slope);
+    });
   return check_launch("sv_scale_shift_act");
 }
 
 extern "C" int sv_scale_shift_act(const void* x, int ldx, const float* scale, const float* shift, const void* residual, int ldr,
                                   void* y, int ldy, long long M, int C, int act, float slope, int act_dtype, void* stream) {
-  return scale_shift_act_impl(x, ldx, scale, shift, residual, ldr, y, ldy, M, C, act, slope, nullptr, act_dtype, stream);
+  return scale_shift_act_impl(x, ldx, scale, shift, residual, ldr, y, ldy, M, C, act, slope, nullptr, act_dtype, (hipStream_t)stream, nullptr);
 }
 extern "C" int sv_bn_signs_supported(int C) { return bn_signs_ok(C) ? 1 : 0; }
 extern "C" int sv_scale_shift_act_signs(const void* x, int ldx, const float* scale, const float* shift, const void* residual, int ldr,
                                         void* y, int ldy, long long M, int C, int act, float slope, void* signs, int act_dtype, void* stream) {
   SV_REQUIRE(signs, "scale_shift_act_signs: null sign buffer");
-  return scale_shift_act_impl(x, ldx, scale, shift, residual, ldr, y, ldy, M, C, act, slope, static_cast<unsigned long long*>(signs), act_dtype, stream);
+  return scale_shift_act_impl(x, ldx, scale, shift, residual, ldr, y, ldy, M, C, act, slope, signs, act_dtype, (hipStream_t)stream, nullptr);
+}
+extern "C" int sv_scale_shift_act_plan(const void* x, int ldx, const float* scale, const float* shift, const void* residual, int ldr, void* y, int ldy,
+                                       long long M, int C, int act, float slope, void* signs, int act_dtype, sv_norm_plan* plan) {
+  SV_REQUIRE(plan, "scale_shift_act_plan: null plan");
+  return scale_shift_act_impl(x, ldx, scale, shift, residual, ldr, y, ldy, M, C, act, slope, signs, act_dtype, nullptr, plan);
 }
 
 // ---- ResNet stem, fused with its max-pool (kernels above).  x = the convolution's output [N, H, W, C] (rows of exactly C elements, C % 4 == 0,
@@ -1767,87 +1754,98 @@ extern "C" int sv_bn_maxpool3d_bwd(const void* dpooled, const void* idx, const v
 }
 
 extern "C" size_t sv_bn_bwd_workspace_doubles(int C) { return (size_t)(BN_BWD_SLOTS + 1) * 2 * C + 2; }
-
-static int bn_bwd_impl(const void* dz, int lddz, const void* z, int ldz, const unsigned long long* signs, const void* x, int ldx, const float* gamma,
-                       const float* save_mean, const float* save_rstd, long long M, int C, int act, float slope, int training,
-                       void* dx, int lddx, void* dres, int lddres, float* dgamma, float* dbeta, double* sums_ws,
-                       const float* fwd_scale, const float* fwd_shift, int act_dtype, void* stream) {
-  SV_REQUIRE(dz && x && gamma && save_mean && save_rstd && dx && dgamma && dbeta && sums_ws && M > 0 && C > 0, "bn_bwd: null/empty argument");
-  SV_REQUIRE(act == SV_ACT_NONE || z || signs || (fwd_scale && fwd_shift), "bn_bwd: the activation mask needs the forward output z, its sign words or the forward scale/shift");
-  const float* fsc = fwd_scale; const float* fsh = fwd_shift;
-  SV_REQUIRE_ACT(act_dtype);
-  hipStream_t s = (hipStream_t)stream;   // sums_ws: sv_bn_bwd_workspace_doubles(C) doubles, ZERO on entry (e.g. a slice of one pre-zeroed arena)
-  const bool vec = (C % 4 == 0) && (lddz % 4 == 0) && (ldx % 4 == 0) && (lddx % 4 == 0) && (!z || ldz % 4 == 0) && (!dres || lddres % 4 == 0) &&
-                   aligned4(act_dtype, dz, z, x, dx, dres) &&
-                   (((uintptr_t)save_mean | (uintptr_t)save_rstd | (uintptr_t)fwd_scale | (uintptr_t)fwd_shift) & 15) == 0;   // all four are read as float4
-  // sign words: the reduce pass takes the mask from them and hands the masked gradient on through dres (premask) - both vector-path features
-  SV_REQUIRE(!signs || (vec && bn_signs_ok(C) && dres && act != SV_ACT_NONE && ((uintptr_t)signs & 15) == 0),
-             "bn_bwd_signs: needs C %% 256 == 0, 4-aligned rows, an activation and the residual-branch output dres (C=%d)", C);
-  SV_DISPATCH_ACT(act_dtype,
-    const AT* dz_ = static_cast<const AT*>(dz); const AT* z_ = static_cast<const AT*>(z); const AT* x_ = static_cast<const AT*>(x);
-    AT* dx_ = static_cast<AT*>(dx); AT* dres_ = static_cast<AT*>(dres);
-    const int c4 = (C + 3) & ~3;
-    const bool narrow = !vec && C <= BN_NARROW_MAXC && (lddz % 4 == 0) && (ldx % 4 == 0) && (lddx % 4 == 0) && lddz >= c4 && ldx >= c4 && lddx >= c4 &&
-                        (!z || (ldz % 4 == 0 && ldz >= c4)) && (!dres || (lddres % 4 == 0 && lddres >= c4)) && aligned4(act_dtype, dz, z, x, dx, dres);
-    if (narrow) {
-      const int rpt = 16;
-      const long long nb = (M + 64LL * rpt - 1) / (64LL * rpt);
-      hipLaunchKernelGGL(bn_bwd_reduce_narrow_kernel<AT>, dim3((unsigned)nb), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope,
-                         sums_ws, rpt, fsc, fsh);
-      bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
-      long long blocks = (M + 63) / 64; if (blocks > 8192) blocks = 8192;
-      hipLaunchKernelGGL(bn_bwd_apply_narrow_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
-                         act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh);
-    } else if (vec) {
-      const int G = C / 4 < 64 ? C / 4 : 64, RL = 256 / G;
-      const int cg = cdiv(C / 4, G);
-      const long long rpb = bn_rows_per_block(M, cg, 2048, 2 * RL), arpb = bn_rows_per_block(M, cg, 4096, 4 * RL);
+// t = dz, z, x, dx, dres with their row strides; params = save_mean | save_rstd | fwd_scale | fwd_shift, all four read as float4 by the vector kernels
+static sv_norm_plan plan_bn_bwd(std::initializer_list<BnRows> t, uintptr_t params, long long M, int C, int act, bool dres, bool signs, int act_dtype) {
+  sv_norm_plan p = bn_family(act_dtype, C, t, params);
+  if (p.family == SV_NORM_BN_NARROW) { p.rows[0] = 16; p.launch[0] = {cdiv(M, 64 * 16), 1, 256, 0}; }   // 16 rows per thread, 64 row lanes
+  else {
+    int cg, step;                                           // column groups along grid x, rows of one loop step of a workgroup
+    if (p.family == SV_NORM_BN_VECTOR) {
+      const BnVecGeom v = bn_vec_geom(C); cg = v.cg; step = 2 * v.RL;
       // with a residual-branch gradient to produce (dres) the reduce pass stores the masked gradient there and the apply pass reads IT,
       // mask-free, instead of (dz, z): 7 instead of 8 passes over the tensor.  The sums are of the fp32 values, the stored ones are
       // rounded to the storage type - as dres always was.  The hand-off needs the stored value to BE the masked gradient: true for ReLU
       // (dz or 0) and for fp32 storage, not for LeakyReLU in bf16, where slope * dz rounds and dx would inherit 2^-9 |gamma rstd dz'| -
       // there the apply pass masks dz itself (from z / x, or from the sign words) and dres only carries the residual branch's gradient.
-      const bool exact = !(act == SV_ACT_LRELU && act_dtype == SV_BF16);
-      const bool premask = dres_ && act != SV_ACT_NONE && exact;
-      const bool sign_apply = signs && !premask;       // the reduce pass still delivers dres, the apply pass reads (dz, words)
-      hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope,
-                         sums_ws, rpb, G, fsc, fsh, (premask || sign_apply) ? dres_ : (AT*)nullptr, lddres, signs);
-      bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
-      if (sign_apply)
-        hipLaunchKernelGGL((bn_bwd_apply_cg_kernel<AT, true>), dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, dz_, lddz, (const AT*)nullptr, 0, x_, ldx, gamma, save_mean,
-                           save_rstd, sums_ws, M, C, act, slope, training, dx_, lddx, (AT*)nullptr, 0, fsc, fsh, arpb, G, signs);
-      else if (premask)
-        hipLaunchKernelGGL(bn_bwd_apply_cg_kernel<AT>, dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, (const AT*)dres_, lddres, (const AT*)nullptr, 0, x_, ldx, gamma, save_mean,
-                           save_rstd, sums_ws, M, C, (int)SV_ACT_NONE, 0.f, training, dx_, lddx, (AT*)nullptr, 0, fsc, fsh, arpb, G);
-      else
-        hipLaunchKernelGGL(bn_bwd_apply_cg_kernel<AT>, dim3(cg, cdiv(M, arpb)), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
-                           act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh, arpb, G);
+      const bool premask = dres && act != SV_ACT_NONE && !(act == SV_ACT_LRELU && act_dtype == SV_BF16);
+      p.mask = premask ? SV_MASK_PREMASK : signs ? SV_MASK_SIGN_APPLY : SV_MASK_PLAIN;   // SIGN_APPLY: the reduce pass still delivers dres, the apply pass reads (dz, words)
     } else {
-      int CW = 1; while (CW < C && CW < 64) CW <<= 1;         // channel lanes: next power of two of C, at most 64
-      const int cg = cdiv(C, CW), RLg = 256 / CW;
-      const long long rpb = bn_rows_per_block(M, cg, 2048, 4 * RLg);
-      hipLaunchKernelGGL(bn_bwd_reduce_kernel<AT>, dim3(cg, cdiv(M, rpb)), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope, sums_ws, rpb, CW, fsc, fsh);
-      bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
-      long long blocks = (M * C + 255) / 256; if (blocks > 8192) blocks = 8192;
-      hipLaunchKernelGGL(bn_bwd_apply_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
-                         act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh);
+      int CW = 1; while (CW < C && CW < 64) CW <<= 1;       // channel lanes: next power of two of C, at most 64
+      p.lanes = CW; cg = cdiv(C, CW); step = 4 * (256 / CW);
+    }
+    p.rows[0] = bn_rows_per_block(M, cg, 2048, step);
+    p.launch[0] = {cg, cdiv(M, p.rows[0]), 256, 0};
+  }
+  p.launch[1] = {cdiv(2 * C, 256), 1, 256, 0};              // bn_bwd_fold
+  return plan_bn_apply(p, 2, M, C);
+}
+// arguments -> plan -> (query: report it) -> launch; behind sv_bn_bwd, sv_bn_bwd_signs and sv_bn_bwd_plan
+static int bn_bwd_impl(const void* dz, int lddz, const void* z, int ldz, const void* signs, const void* x, int ldx, const float* gamma, const float* save_mean,
+                       const float* save_rstd, long long M, int C, int act, float slope, int training, void* dx, int lddx, void* dres, int lddres, float* dgamma,
+                       float* dbeta, double* sums_ws, const float* fsc, const float* fsh, int act_dtype, hipStream_t s, sv_norm_plan* query) {
+  SV_REQUIRE(dz && x && gamma && save_mean && save_rstd && dx && dgamma && dbeta && sums_ws && M > 0 && C > 0, "bn_bwd: null/empty argument");
+  SV_REQUIRE(act == SV_ACT_NONE || z || signs || (fsc && fsh), "bn_bwd: the activation mask needs the forward output z, its sign words or the forward scale/shift");
+  SV_REQUIRE_ACT(act_dtype);             // sums_ws: sv_bn_bwd_workspace_doubles(C) doubles, ZERO on entry (e.g. a slice of one pre-zeroed arena)
+  const sv_norm_plan p = plan_bn_bwd({{dz, lddz}, {z, ldz}, {x, ldx}, {dx, lddx}, {dres, lddres}},
+                                     (uintptr_t)save_mean | (uintptr_t)save_rstd | (uintptr_t)fsc | (uintptr_t)fsh, M, C, act, dres, signs, act_dtype);
+  // sign words: the reduce pass takes the mask from them and hands the masked gradient on through dres (premask) - both vector-path features
+  SV_REQUIRE(!signs || (p.family == SV_NORM_BN_VECTOR && bn_signs_ok(C) && dres && act != SV_ACT_NONE && ((uintptr_t)signs & 15) == 0),
+             "bn_bwd_signs: needs C %% 256 == 0, 4-aligned rows, an activation and the residual-branch output dres (C=%d)", C);
+  if (query) { *query = p; return SV_OK; }
+  SV_DISPATCH_ACT(act_dtype,
+    const AT* dz_ = static_cast<const AT*>(dz); const AT* z_ = static_cast<const AT*>(z); const AT* x_ = static_cast<const AT*>(x);
+    AT* dx_ = static_cast<AT*>(dx); AT* dres_ = static_cast<AT*>(dres); const AT* none = nullptr; const unsigned long long* w = static_cast<const unsigned long long*>(signs);
+    const int G = p.lanes; const long long rpb = p.rows[0], arpb = p.rows[1];
+    switch (p.family) {
+      case SV_NORM_BN_NARROW:
+        hipLaunchKernelGGL(bn_bwd_reduce_narrow_kernel<AT>, bn_grid(p, 0), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope,
+                           sums_ws, (int)rpb, fsc, fsh);
+        bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
+        hipLaunchKernelGGL(bn_bwd_apply_narrow_kernel<AT>, bn_grid(p, 2), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
+                           act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh);
+        break;
+      case SV_NORM_BN_VECTOR:
+        hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel<AT>, bn_grid(p, 0), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope,
+                           sums_ws, rpb, G, fsc, fsh, p.mask != SV_MASK_PLAIN ? dres_ : (AT*)nullptr, lddres, w);
+        bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
+        if (p.mask == SV_MASK_SIGN_APPLY)
+          hipLaunchKernelGGL((bn_bwd_apply_cg_kernel<AT, true>), bn_grid(p, 2), dim3(256), 0, s, dz_, lddz, none, 0, x_, ldx, gamma, save_mean, save_rstd, sums_ws,
+                             M, C, act, slope, training, dx_, lddx, (AT*)nullptr, 0, fsc, fsh, arpb, G, w);
+        else if (p.mask == SV_MASK_PREMASK)
+          hipLaunchKernelGGL(bn_bwd_apply_cg_kernel<AT>, bn_grid(p, 2), dim3(256), 0, s, (const AT*)dres_, lddres, none, 0, x_, ldx, gamma, save_mean, save_rstd,
+                             sums_ws, M, C, (int)SV_ACT_NONE, 0.f, training, dx_, lddx, (AT*)nullptr, 0, fsc, fsh, arpb, G);
+        else
+          hipLaunchKernelGGL(bn_bwd_apply_cg_kernel<AT>, bn_grid(p, 2), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
+                             act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh, arpb, G);
+        break;
+      default:
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<AT>, bn_grid(p, 0), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, save_mean, save_rstd, M, C, act, slope, sums_ws, rpb, G, fsc, fsh);
+        bn_bwd_fold(s, C, sums_ws, dgamma, dbeta);
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<AT>, bn_grid(p, 2), dim3(256), 0, s, dz_, lddz, z_, ldz, x_, ldx, gamma, save_mean, save_rstd, sums_ws, M, C,
+                           act, slope, training, dx_, lddx, dres_, lddres, fsc, fsh);
     });
   return check_launch("sv_bn_bwd");
 }
 
-extern "C" int sv_bn_bwd(const void* dz, int lddz, const void* z, int ldz, const void* x, int ldx, const float* gamma,
-                         const float* save_mean, const float* save_rstd, long long M, int C, int act, float slope, int training,
-                         void* dx, int lddx, void* dres, int lddres, float* dgamma, float* dbeta, double* sums_ws,
-                         const float* fwd_scale, const float* fwd_shift, int act_dtype, void* stream) {
+extern "C" int sv_bn_bwd(const void* dz, int lddz, const void* z, int ldz, const void* x, int ldx, const float* gamma, const float* save_mean, const float* save_rstd,
+                         long long M, int C, int act, float slope, int training, void* dx, int lddx, void* dres, int lddres, float* dgamma, float* dbeta,
+                         double* sums_ws, const float* fwd_scale, const float* fwd_shift, int act_dtype, void* stream) {
   return bn_bwd_impl(dz, lddz, z, ldz, nullptr, x, ldx, gamma, save_mean, save_rstd, M, C, act, slope, training, dx, lddx, dres, lddres, dgamma, dbeta,
-                     sums_ws, fwd_scale, fwd_shift, act_dtype, stream);
+                     sums_ws, fwd_scale, fwd_shift, act_dtype, (hipStream_t)stream, nullptr);
 }
-extern "C" int sv_bn_bwd_signs(const void* dz, int lddz, const void* signs, const void* x, int ldx, const float* gamma,
-                               const float* save_mean, const float* save_rstd, long long M, int C, int act, float slope, int training,
-                               void* dx, int lddx, void* dres, int lddres, float* dgamma, float* dbeta, double* sums_ws, int act_dtype, void* stream) {
+extern "C" int sv_bn_bwd_signs(const void* dz, int lddz, const void* signs, const void* x, int ldx, const float* gamma, const float* save_mean, const float* save_rstd,
+                               long long M, int C, int act, float slope, int training, void* dx, int lddx, void* dres, int lddres, float* dgamma, float* dbeta,
+                               double* sums_ws, int act_dtype, void* stream) {
   SV_REQUIRE(signs, "bn_bwd_signs: null sign buffer");
-  return bn_bwd_impl(dz, lddz, nullptr, 0, static_cast<const unsigned long long*>(signs), x, ldx, gamma, save_mean, save_rstd, M, C, act, slope, training,
-                     dx, lddx, dres, lddres, dgamma, dbeta, sums_ws, nullptr, nullptr, act_dtype, stream);
+  return bn_bwd_impl(dz, lddz, nullptr, 0, signs, x, ldx, gamma, save_mean, save_rstd, M, C, act, slope, training, dx, lddx, dres, lddres, dgamma, dbeta,
+                     sums_ws, nullptr, nullptr, act_dtype, (hipStream_t)stream, nullptr);
+}
+extern "C" int sv_bn_bwd_plan(const void* dz, int lddz, const void* z, int ldz, const void* signs, const void* x, int ldx, const float* gamma, const float* save_mean,
+                              const float* save_rstd, long long M, int C, int act, float slope, int training, void* dx, int lddx, void* dres, int lddres, float* dgamma,
+                              float* dbeta, double* sums_ws, const float* fwd_scale, const float* fwd_shift, int act_dtype, sv_norm_plan* plan) {
+  SV_REQUIRE(plan, "bn_bwd_plan: null plan");
+  return bn_bwd_impl(dz, lddz, z, ldz, signs, x, ldx, gamma, save_mean, save_rstd, M, C, act, slope, training, dx, lddx, dres, lddres, dgamma, dbeta, sums_ws,
+                     fwd_scale, fwd_shift, act_dtype, nullptr, plan);
 }
 
 // ---- bn3 + the down-sampling BatchNorm of a ResNet layer's first bottleneck in the same passes (kernels above).  Vector geometry only:

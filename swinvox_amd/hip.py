@@ -43,6 +43,25 @@ class LaunchPlan(C.Structure):   # sv_launch_plan: what sv_conv_gather_plan / sv
 OPERANDS_F32, OPERANDS_BF16_F32, OPERANDS_BF16 = 0, 1, 2
 
 
+class NormLaunch(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("grid_x", "grid_y", "block", "lds_bytes")]
+
+
+class NormPlan(C.Structure):   # sv_norm_plan: what sv_layernorm_plan / sv_scale_shift_act_plan / sv_bn_bwd_plan report
+    _fields_ = ([(n, C.c_int) for n in ("family", "merge", "storage", "vec", "lanes", "nv", "mask", "launches")] +
+                [("launch", NormLaunch * 3), ("rows", C.c_longlong * 2)])
+
+    def grids(self):
+        """(grid_x, grid_y) of every launch, in dispatch order"""
+        return [(l.grid_x, l.grid_y) for l in self.launch[:self.launches]]
+
+
+# SV_NORM_* / SV_MASK_* of a NormPlan; kinds of sv_layernorm_plan
+NORM_LN_FWD, NORM_LN_BWD, NORM_BN_SCALAR, NORM_BN_NARROW, NORM_BN_VECTOR = range(5)
+MASK_PLAIN, MASK_PREMASK, MASK_SIGN_APPLY = 0, 1, 2
+LN_PLAIN, LN_QUANT, LN_QUANT_MX, LN_BWD = range(4)
+
+
 class PackDesc(C.Structure):   # sv_pack_desc
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("A", C.c_int), ("B", C.c_int), ("T", C.c_int), ("swap", C.c_int),
                 ("rows_out", C.c_int), ("inner_out", C.c_int), ("block0", C.c_int), ("reserved", C.c_int)]
@@ -117,6 +136,7 @@ _PROTOS = {
     "sv_layernorm_quant_mx_launches": (_L, None),
     "sv_layernorm_bwd_workspace_floats": (C.c_size_t, None, [_I]),
     "sv_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I]),
+    "sv_layernorm_plan": (_I, None, [_I, _P, _P, _P, _L, _I, _I, _I, _I, C.POINTER(NormPlan)]),
     "sv_bn_bwd_workspace_doubles": (C.c_size_t, None, [_I]),
     "sv_ln_image_workspace_floats": (C.c_size_t, None, [_I, _I]),
     "sv_ln_image_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _U, _P]),
@@ -125,6 +145,8 @@ _PROTOS = {
     "sv_bn_finalize": (_I, [_P, _L, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _I]),
     "sv_scale_shift_act": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _L, _I, _I, _F]),
     "sv_bn_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _L, _I, _I, _F, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "sv_scale_shift_act_plan": (_I, None, [_P, _I, _P, _P, _P, _I, _P, _I, _L, _I, _I, _F, _P, _I, C.POINTER(NormPlan)]),
+    "sv_bn_bwd_plan": (_I, None, [_P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _L, _I, _I, _F, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, C.POINTER(NormPlan)]),
     "sv_bn_signs_supported": (_I, None, [_I]),
     "sv_scale_shift_act_signs": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _L, _I, _I, _F, _P]),
     "sv_bn_bwd_signs": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _L, _I, _I, _F, _I, _P, _I, _P, _I, _P, _P, _P]),

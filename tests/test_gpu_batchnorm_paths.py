@@ -24,8 +24,12 @@ with the check switched to recording, rounded up to a power of two.  The measure
 The largest, 15.5, is dx of the scalar family with the mask from z and LeakyReLU (M = 65, C = 18), so K = 64.  The first recording run had nine
 cases between 4.6e3 and 4.7e4, all of them dx in bf16 storage with LeakyReLU and dres on the vector kernels (mask from z, recomputed, or sign
 words): the apply pass read back the bf16-rounded masked gradient that the reduce pass had stored for dres, so dx carried 2^-9 |gamma rstd dz'|.
-bn_bwd_impl now hands the masked gradient over through dres only where the stored value is exact (ReLU, or fp32 storage).
+plan_bn_bwd hands the masked gradient over through dres only where the stored value is exact (ReLU, or fp32 storage).
+
+Every apply and backward call first asks the plan query (sv_scale_shift_act_plan / sv_bn_bwd_plan) with the buffers it is about to pass: the
+family must be the one the case names, and in the backward the mask hand-off the one its mask source, activation and storage imply.
 """
+import ctypes
 import os
 import sys
 
@@ -44,6 +48,7 @@ pytestmark = pytest.mark.gpu
 SENT = -1234.5
 STORES = ("f32", "bf16")
 ACT_NAME = {ACT_NONE: "none", ACT_RELU: "relu", ACT_LRELU: "lrelu"}
+FAMILY = {"scalar": hip.NORM_BN_SCALAR, "narrow": hip.NORM_BN_NARROW, "vec": hip.NORM_BN_VECTOR}
 
 
 def _up4(c):
@@ -120,7 +125,7 @@ def _slack_intact(b, n, fill_nan=True):
 
 # ---- forward: statistics, finalize, apply ------------------------------------------------------------------------------------------------
 def _fwd_layout(fam, C):
-    """strides / offsets / alignment that select the family (see scale_shift_act_impl)"""
+    """strides / offsets / alignment that select the family (bn_family in csrc/norm.hip; _forward asserts it through the plan query)"""
     if fam == "scalar":
         return {1: dict(ldx=1, ldy=1, ldr=1), 9: dict(ldx=9, ldy=9, ldr=9), 18: dict(ldx=20, ldy=20, ldr=20),
                 8: dict(ldx=12, ldy=12, ldr=12, head=1)}[C]                    # C = 8 would be a vector shape: every view is off by one element
@@ -132,8 +137,9 @@ def _fwd_layout(fam, C):
     return dict(ldx=C, ldy=C, ldr=C)
 
 
-def _forward(dev, store, name, case, lay, wide, training=True, signs=False):
-    """sv_bn_stats -> sv_bn_finalize -> sv_scale_shift_act(_signs) on fresh buffers; checks every output and returns (y buffer, sign words)"""
+def _forward(dev, store, name, case, lay, wide, fam, training=True, signs=False):
+    """sv_bn_stats -> sv_bn_finalize -> sv_scale_shift_act(_signs) on fresh buffers, after the plan query has named the family `fam` for them;
+    checks every output and returns (y buffer, sign words)"""
     M, C, act, ref = case["M"], case["C"], case["act"], case["ref"]
     head = lay.get("head", 0)
     with _storage(store) as dt:
@@ -151,6 +157,10 @@ def _forward(dev, store, name, case, lay, wide, training=True, signs=False):
         call("sv_bn_finalize", ptr(sums) if training else None, M, ptr(gm), ptr(bt), ptr(rm), ptr(rv), MOMENTUM, EPS, 1 if training else 0,
              ptr(sc), ptr(sh), ptr(mu), ptr(rs), C)
         rptr, ldr = (res.ptr, lay["ldr"]) if res is not None else (None, 0)
+        plan = hip.NormPlan()
+        assert hip.load().sv_scale_shift_act_plan(x.ptr, lay["ldx"], ptr(sc), ptr(sh), rptr, ldr, y.ptr, lay["ldy"], M, C, act, SLOPE, ptr(words), hip.ACT,
+                                                  ctypes.byref(plan)) == 0, f"{name}: {hip.load().sv_last_error().decode()}"
+        assert plan.family == FAMILY[fam], f"{name}: the layout selects family {plan.family}, the case names {fam}"
         if signs:
             call("sv_scale_shift_act_signs", x.ptr, lay["ldx"], ptr(sc), ptr(sh), rptr, ldr, y.ptr, lay["ldy"], M, C, act, SLOPE, ptr(words))
         else:
@@ -181,7 +191,7 @@ FWD_PARAMS = [pytest.param(fam, C, M, training, id=f"{fam}-C{C}-M{M}-{ACT_NAME[R
 def test_forward(dev, fam, C, M, training, store):
     r = R.fwd_recipe(C, M)
     case = R.bn_case(M, C, r["act"], r["with_res"], r["offset"], store == "bf16", 0, training)
-    _forward(dev, store, f"fwd-{fam}-C{C}-M{M}-{store}", case, _fwd_layout(fam, C), wide=(fam == "narrow"), training=training)
+    _forward(dev, store, f"fwd-{fam}-C{C}-M{M}-{store}", case, _fwd_layout(fam, C), wide=(fam == "narrow"), fam=fam, training=training)
 
 
 @pytest.mark.parametrize("store", STORES)
@@ -189,7 +199,7 @@ def test_forward_constant_channel(dev, store):
     """variance 0: rstd = eps^-1/2, the channel's output is beta (+ res) whatever the constant; M == 1 is a shape of test_forward"""
     case = R.bn_case(*R.const_recipe(store == "bf16"))
     assert float(case["ref"]["var"][R.CONST_CHANNEL]) == 0.0
-    _forward(dev, store, f"fwd-const-{store}", case, dict(ldx=12, ldy=12, ldr=12), wide=False)
+    _forward(dev, store, f"fwd-const-{store}", case, dict(ldx=12, ldy=12, ldr=12), wide=False, fam="vec")
 
 
 @pytest.mark.parametrize("store", STORES)
@@ -200,8 +210,8 @@ def test_forward_sign_words(dev, C, M, act, store):
     case = R.bn_case(*R.sign_recipe(C, M, act, store == "bf16"))
     lay = dict(ldx=C, ldy=C + 4, ldr=C)
     name = f"signs-C{C}-M{M}-{store}"
-    y, words = _forward(dev, store, name, case, lay, wide=False, signs=True)
-    y0, _ = _forward(dev, store, name + "-plain", case, lay, wide=False, signs=False)
+    y, words = _forward(dev, store, name, case, lay, wide=False, fam="vec", signs=True)
+    y0, _ = _forward(dev, store, name + "-plain", case, lay, wide=False, fam="vec", signs=False)
     n = M * (C // 64)
     assert torch.equal(words[:n].cpu().view(M, C // 256, 4), R.sign_words(case["ref"]["p"])), f"{name}: sign words"
     assert bool((words[n:] == 0x5A5A5A5A).all()), f"{name}: written behind the sign words"
@@ -235,16 +245,24 @@ def test_finalize_sums_every_slot(dev, store):
 
 # ---- backward ----------------------------------------------------------------------------------------------------------------------------
 BWD_LAYOUTS = {
-    "scalar": dict(lddz=19, ldz=20, ldx=20, lddx=18, lddres=21),
-    "narrow": dict(lddz=12, ldz=16, ldx=12, lddx=12, lddres=16, wide=True),
-    "vec": dict(lddz=48, ldz=40, ldx=44, lddx=52, lddres=44),
-    "vec256": dict(lddz=256, ldz=256, ldx=256, lddx=256, lddres=260),
-    "narrow_wrap": dict(lddz=12, ldz=12, ldx=12, lddx=12, lddres=12, wide=True),
-    "merger12": dict(lddz=48, offdz=24, ldz=48, ldx=12, lddx=12, lddres=12, wide=True),     # backward(dzk, 48, None, 0, y, 12, dy, 12, ...)
-    "merger1": dict(lddz=1, ldz=1, ldx=1, lddx=4, lddres=1),                                 # backward(dwl, 1, None, 0, y6, 1, dy6, 4, ...)
-    "fsc8": dict(lddz=8, ldz=8, ldx=8, lddx=8, lddres=8, fsc_off=1),                         # fwd_scale / fwd_shift 4 bytes off a 16-byte boundary
-    "fsc24": dict(lddz=24, ldz=24, ldx=24, lddx=24, lddres=24, fsc_off=1),
+    "scalar": dict(fam="scalar", lddz=19, ldz=20, ldx=20, lddx=18, lddres=21),
+    "narrow": dict(fam="narrow", lddz=12, ldz=16, ldx=12, lddx=12, lddres=16, wide=True),
+    "vec": dict(fam="vec", lddz=48, ldz=40, ldx=44, lddx=52, lddres=44),
+    "vec256": dict(fam="vec", lddz=256, ldz=256, ldx=256, lddx=256, lddres=260),
+    "narrow_wrap": dict(fam="narrow", lddz=12, ldz=12, ldx=12, lddx=12, lddres=12, wide=True),
+    "merger12": dict(fam="narrow", lddz=48, offdz=24, ldz=48, ldx=12, lddx=12, lddres=12, wide=True),     # backward(dzk, 48, None, 0, y, 12, dy, 12, ...)
+    "merger1": dict(fam="scalar", lddz=1, ldz=1, ldx=1, lddx=4, lddres=1),                   # backward(dwl, 1, None, 0, y6, 1, dy6, 4, ...)
+    "fsc8": dict(fam="narrow", lddz=8, ldz=8, ldx=8, lddx=8, lddres=8, fsc_off=1),           # fwd_scale / fwd_shift 4 bytes off a 16-byte boundary
+    "fsc24": dict(fam="scalar", lddz=24, ldz=24, ldx=24, lddx=24, lddres=24, fsc_off=1),
 }
+
+
+def _hand_off(fam, act, store, with_dres, words):
+    """how the mask reaches the apply pass: through dres (premask) on the vector kernels wherever the stored masked gradient is exact (ReLU, or
+    fp32 storage), from the sign words where they are given and it is not, else from the case's own mask source (z, recomputed, none)"""
+    if fam == "vec" and with_dres and act != ACT_NONE and not (act == ACT_LRELU and store == "bf16"):
+        return hip.MASK_PREMASK
+    return hip.MASK_SIGN_APPLY if words is not None else hip.MASK_PLAIN
 
 
 def _backward(dev, store, name, case, lay, mask, with_dres, words=None, null_fwd=False):
@@ -266,8 +284,14 @@ def _backward(dev, store, name, case, lay, mask, with_dres, words=None, null_fwd
         dg, db = _f32(g0, dev), _f32(-g0, dev)
         ws = torch.zeros(int(hip.load().sv_bn_bwd_workspace_doubles(C)), dtype=torch.float64, device=dev)
         dresp, lddres = (dres.ptr, lay["lddres"]) if dres is not None else (None, 0)
+        wd = words.reshape(-1).to(dev) if words is not None else None
+        plan = hip.NormPlan()
+        assert hip.load().sv_bn_bwd_plan(dz.ptr, lay["lddz"], z.ptr if z is not None else None, lay["ldz"] if z is not None else 0, ptr(wd), x.ptr, lay["ldx"],
+                                         ptr(gm), ptr(mu), ptr(rs), M, C, act, SLOPE, 1 if training else 0, dx.ptr, lay["lddx"], dresp, lddres, ptr(dg),
+                                         ptr(db), ptr(ws), ptr(fsc), ptr(fsh), hip.ACT, ctypes.byref(plan)) == 0, f"{name}: {hip.load().sv_last_error().decode()}"
+        assert plan.family == FAMILY[lay["fam"]], f"{name}: the layout selects family {plan.family}, the case names {lay['fam']}"
+        assert plan.mask == _hand_off(lay["fam"], act, store, with_dres, words), f"{name}: mask hand-off {plan.mask}"
         if words is not None:
-            wd = words.reshape(-1).to(dev)
             call("sv_bn_bwd_signs", dz.ptr, lay["lddz"], ptr(wd), x.ptr, lay["ldx"], ptr(gm), ptr(mu), ptr(rs), M, C, act, SLOPE,
                  1 if training else 0, dx.ptr, lay["lddx"], dresp, lddres, ptr(dg), ptr(db), ptr(ws))
         else:
@@ -316,7 +340,7 @@ def test_backward(dev, fam, mask, act, with_dres, training, store):
 def test_backward_sign_words(dev, C, M, act, training, store):
     """mask from the sign words (built on the host from the reference's p in the header's layout), masked gradient through dres"""
     case = R.bn_case(*R.sign_recipe(C, M, act, store == "bf16", training))
-    lay = dict(lddz=C, ldz=C, ldx=C + 4, lddx=C, lddres=C + 8)
+    lay = dict(fam="vec", lddz=C, ldz=C, ldx=C + 4, lddx=C, lddres=C + 8)
     _backward(dev, store, f"bwd-signs-C{C}-M{M}-{ACT_NAME[act]}-{'train' if training else 'eval'}-{store}", case, lay, "signs", True, words=R.sign_words(case["ref"]["p"]))
 
 

@@ -17,8 +17,8 @@ from swinvox_amd.ops import call, ptr  # noqa: E402
 
 GUARD = 3                       # rows past `rows` in every output buffer; they must keep their fill
 ROWS = (1, 37, 130)             # one lane group; several waves with an idle tail; more than one workgroup at every LPR (16 rows each at most)
-# C: 64 / 96 -> LPR 16 (bf16, VEC 8) or 16 / 32 (VEC 4); 100 -> VEC 4 in both storages; 192, 384 -> LPR 32 / 64; 3072 -> NV = 12 (bf16) and the
-# widest VEC 4 kernel.  C = 64 in fp32: 16 chunks x 4 = 64 elements in the lane group against Kp = 128 (the padding loop runs past the registers)
+# C: 64 / 96 -> LPR 16 (bf16, VEC 8) or 16 / 32 (VEC 4); 100 -> VEC 4 in both storages; 192, 384 -> LPR 32 / 64; 3072 -> NV = 6 (bf16, VEC 8) and NV = 12,
+# the widest VEC 4 kernel (fp32 storage); tests/test_cpu_norm_plan.py pins these through sv_layernorm_plan.  C = 64 in fp32: 16 chunks x 4 = 64 elements in the lane group against Kp = 128 (the padding loop runs past the registers)
 CS = (64, 96, 100, 192, 384, 3072)
 MERGED = ((2, 4, 4, 24), (1, 6, 6, 96), (3, 2, 2, 384))      # (I, H, W, C0): C = 4 C0 = 96, 384, 1536
 
