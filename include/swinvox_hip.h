@@ -730,6 +730,22 @@ int sv_binvox_decode(const unsigned char* rle, const long long* pair_offsets, in
 int sv_augment_views(const unsigned char* src, int I, int V, int Hs, int Ws, int C, int crop_h, int crop_w, int out_h, int out_w,
                      const sv_aug_sample* params_dev, const unsigned char* flip_dev, double* grey_sum_ws, float* out, void* stream);
 
+/* sv_binvox_encode: the run-length writer of utils/binvox_rw.py:239-292 (write) for B volumes of equal dims, the inverse of
+ *    sv_binvox_decode.  File order is [d0][d1][d2]; `vol` is [B][d0][d2][d1] when fix_coords (xyz order, what the decoder
+ *    produces: file element (i, j, k) = vol[b][(i*d2 + k)*d1 + j]), [B][d0][d1][d2] otherwise.  For cubic volumes that is
+ *    the writer's axis_order == 'xyz' branch (:269-270); for non-cubic ones the contract is "inverse of the reader" (the
+ *    reference's own writer and reader are not inverses there).  dtype 0 = float32, 1 = uint8 (bool tensors pass as uint8).
+ *    threshold < 0: the input is occupancy, a voxel is set iff its value != 0; 0 < threshold < 1: float32 logits, set iff
+ *    1.f / (1.f + expf(-x)) >= threshold, the predicate of sv_iou_counts.  Values written are 0 and 1 only.
+ *    pairs + b * 2 * pair_capacity receives volume b's (value, count) bytes - the payload that follows the "data" header
+ *    line - and n_pairs[b] their number; pair_capacity >= d0*d1*d2 is required and always suffices.
+ *    Zero-count pairs: the reference dumps (state, 255) when its counter reaches 255 and restarts it at 0; when the very next
+ *    voxel switches value it dumps (state, 0).  So a run of n voxels that is not the last emits n / 255 pairs (v, 255) and
+ *    then (v, n % 255) EVEN WHEN n % 255 == 0; the last run emits (v, n % 255) only when that is non-zero.  These bytes are
+ *    reproduced exactly; readers (np.repeat, sv_binvox_decode) skip a zero count.                                          */
+int sv_binvox_encode(const void* vol, int dtype, int B, int d0, int d1, int d2, int fix_coords, float threshold,
+                     unsigned char* pairs, long long pair_capacity, int* n_pairs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,15 @@ for b in range(min(a.batch, 4)):
                                      noise_alpha=np.asarray(p.noise_alpha), flips=list(p.flips), perm=list(p.perm)))
     OD.read_binvox(files[b])
 t_cpu = (time.perf_counter() - t0) / min(a.batch, 4) * a.batch * 1e3
+vol_dev = torch.from_numpy(np.stack(vols)).to(dev)
+t_enc = timed(lambda: D.encode_binvox_batch(vol_dev))
+t0 = time.perf_counter()
+for b in range(a.batch):
+    OD.write_binvox(vols[b])
+t_wr = (time.perf_counter() - t0) * 1e3
 n = a.batch * a.views
 print(f"augment_views   {t_aug:7.3f} ms / batch of {n} views ({n / t_aug * 1e3:9.0f} views/s, host parameter packing included)")
 print(f"binvox decode   {t_vox:7.3f} ms / {a.batch} volumes (header parsing + H2D of the run-length bytes included)")
+print(f"binvox encode   {t_enc:7.3f} ms / {a.batch} volumes (pair counts + trimmed payload D2H and header formatting included); "
+      f"oracle.data.write_binvox on the host, one core: {t_wr:7.2f} ms")
 print(f"numpy restatement of the reference path, one core: {t_cpu:8.1f} ms / batch ({n / t_cpu * 1e3:7.0f} views/s)")

@@ -3,6 +3,7 @@
 // CPU path is the bottleneck, so the raw bytes (RLE voxel runs, 8-bit renderings) are shipped and expanded here.
 //
 //   sv_binvox_decode  run-length (value, count) byte pairs -> dense float occupancy, xzy -> xyz transposition
+//   sv_binvox_encode  the way back (utils/binvox_rw.py:239-292): dense occupancy or thresholded logits -> the writer's byte pairs
 //   sv_augment_views  crop -> bilinear resize -> background composite -> colour jitter -> PCA noise -> normalise ->
 //                     flip -> channel permutation -> CHW float, two launches (grey means for the contrast step, then the image)
 #include "common.h"
@@ -53,6 +54,124 @@ __global__ void __launch_bounds__(256) binvox_decode_kernel(const unsigned char*
     __syncthreads();
   }
   if (tid == 0) decoded[b] = running_s;
+}
+
+// ---- binvox writer (utils/binvox_rw.py:239-292): one workgroup per volume, file-order chunks of ENC_CHUNK voxels --------------
+// A chunk is first reduced to a bit mask in LDS, in file order: the input is read along its own fastest axis and the (0, 2, 1)
+// transposition happens in the scatter of the bits.  The reference's (state, ctr) loop is then restated per voxel, 256 voxels per pass:
+//   start  = the voxel differs from its predecessor in file order (or is the first voxel)
+//   t      = 1-based offset of the voxel in its run (max-scan of the start positions; a run open from earlier passes continues `run`)
+//   a start other than voxel 0 emits (previous value, previous t % 255) - the "switch state" dump, a zero count included, which is what
+//            the reference writes when the switch comes right after a dump at 255
+//   t % 255 == 0 emits (value, 255)
+//   the tail emits (value, run % 255) when that is non-zero
+// and a sum-scan of the 0 / 1 / 2 emissions per voxel gives the output slots.  Carried between passes: the run length so far, the pairs
+// written so far, and (between chunks) the last value.  A run of n >= 1 voxels emits at most n / 255 + 1 <= n pairs, so a volume never
+// emits more pairs than it has voxels; every store is bounded by `cap` regardless.
+constexpr int ENC_CHUNK = 1024;
+
+// occupancy of one input element; with 0 < th < 1 the same expression as iou_counts_kernel (elementwise.hip), so that an exported
+// file and the reported IoU agree voxel for voxel
+__device__ __forceinline__ bool voxel_set(const void* __restrict__ vol, int dtype, size_t idx, float th) {
+  if (dtype == 1) return static_cast<const unsigned char*>(vol)[idx] != 0;
+  const float xv = static_cast<const float*>(vol)[idx];
+  if (th < 0.f) return xv != 0.f;
+  const float pr = 1.f / (1.f + expf(-xv));
+  return pr >= th;
+}
+
+__global__ void __launch_bounds__(256) binvox_encode_kernel(const void* __restrict__ vol, int dtype, int d0, int d1, int d2, int fix_coords, float th,
+                                                            unsigned char* __restrict__ pairs, long long cap, int* __restrict__ n_pairs) {
+  __shared__ unsigned int bits[ENC_CHUNK / 32];
+  __shared__ int tl[256];
+  __shared__ int wmax[4], wsum[4];
+  __shared__ int run_s, np_s;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int total = d0 * d1 * d2, slab = d1 * d2;
+  const size_t vbase = (size_t)b * total;
+  unsigned char* o = pairs + (size_t)b * 2 * (size_t)cap;
+  auto getbit = [&](int p) -> int { return (bits[p >> 5] >> (p & 31)) & 1; };
+  auto put = [&](int slot, int v, int c) {
+    if (slot < cap) {
+      o[2 * (size_t)slot] = (unsigned char)v;
+      o[2 * (size_t)slot + 1] = (unsigned char)c;
+    }
+  };
+  if (tid == 0) { run_s = 0; np_s = 0; }
+  int pv = 0;                                    // value of the voxel before the chunk
+  for (int c0 = 0; c0 < total; c0 += ENC_CHUNK) {
+    const int n = min(ENC_CHUNK, total - c0);
+    __syncthreads();                             // the previous chunk's mask has been read
+    if (tid < ENC_CHUNK / 32) bits[tid] = 0u;
+    __syncthreads();
+    if (fix_coords) {                            // file (i, j, k) = vol[(i * d2 + k) * d1 + j]: per slab i, walk the rows j the chunk touches with j fastest
+      for (int i = c0 / slab; i <= (c0 + n - 1) / slab; ++i) {
+        const int s0 = max(c0 - i * slab, 0), s1 = min(c0 + n - i * slab, slab);   // the chunk's part of the slab, in file order
+        const int jlo = s0 / d2, nj = (s1 - 1) / d2 - jlo + 1;
+        const int klo = nj == 1 ? s0 % d2 : 0, nk = nj == 1 ? s1 - s0 : d2;
+        for (int q = tid; q < nj * nk; q += 256) {
+          const int k = klo + q / nj, j = jlo + q % nj, s = j * d2 + k;
+          if (s >= s0 && s < s1 && voxel_set(vol, dtype, vbase + ((size_t)i * d2 + k) * d1 + j, th)) {
+            const int p = i * slab + s - c0;
+            atomicOr(&bits[p >> 5], 1u << (p & 31));
+          }
+        }
+      }
+    } else {
+      for (int q = 0; q < n; q += 256) {         // wave-uniform trip count: every lane takes part in the ballot
+        const int p = q + tid;
+        const unsigned long long m = __ballot(p < n && voxel_set(vol, dtype, vbase + c0 + p, th));
+        if (lane == 0) {
+          bits[(q >> 5) + 2 * w] = (unsigned int)m;
+          bits[(q >> 5) + 2 * w + 1] = (unsigned int)(m >> 32);
+        }
+      }
+    }
+    __syncthreads();
+    for (int q = 0; q < n; q += 256) {
+      const int p = q + tid;
+      const bool valid = p < n;
+      const int bit = valid ? getbit(p) : 0;
+      const int prev = p > 0 ? getbit(p - 1) : pv;
+      const bool start = valid && (c0 + p == 0 || bit != prev);
+      int ms = start ? tid : -1;                 // inclusive max-scan: position of the latest run start at or before this voxel
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(ms, d, 64);
+        if (lane >= d) ms = max(ms, t);
+      }
+      if (lane == 63) wmax[w] = ms;
+      __syncthreads();
+      for (int i = 0; i < w; ++i) ms = max(ms, wmax[i]);
+      const int t = valid ? (ms >= 0 ? tid - ms + 1 : run_s + tid + 1) : 0;
+      tl[tid] = t;
+      const int ea = (start && c0 + p > 0) ? 1 : 0, eb = (valid && t % 255 == 0) ? 1 : 0;
+      int inc = ea + eb;                         // inclusive sum-scan of the emissions
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int u = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += u;
+      }
+      if (lane == 63) wsum[w] = inc;
+      __syncthreads();
+      int slot = np_s + inc - ea - eb;
+      for (int i = 0; i < w; ++i) slot += wsum[i];
+      if (ea) put(slot, prev, (tid > 0 ? tl[tid - 1] : run_s) % 255);
+      if (eb) put(slot + ea, bit, 255);
+      __syncthreads();
+      if (tid == 0) {
+        np_s += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        run_s = tl[min(256, n - q) - 1];
+      }
+      __syncthreads();
+    }
+    pv = getbit(n - 1);
+  }
+  if (tid == 0) {
+    int np = np_s;
+    if (run_s % 255 > 0) put(np++, pv, run_s % 255);   // "flush out remainders"
+    n_pairs[b] = np;
+  }
 }
 
 // ---- view augmentation -----------------------------------------------------------------------------------------------------
@@ -166,6 +285,19 @@ extern "C" int sv_binvox_decode(const unsigned char* rle, const long long* pair_
   SV_REQUIRE((long long)d0 * d1 * d2 < (1ll << 30), "binvox_decode: volume too large");
   hipLaunchKernelGGL(binvox_decode_kernel, dim3(B), dim3(256), 0, STREAM, rle, pair_offsets, d0, d1, d2, fix_coords, out, decoded);
   return check_launch("sv_binvox_decode");
+}
+
+extern "C" int sv_binvox_encode(const void* vol, int dtype, int B, int d0, int d1, int d2, int fix_coords, float threshold, unsigned char* pairs,
+                                long long pair_capacity, int* n_pairs, void* stream) {
+  SV_REQUIRE(vol && pairs && n_pairs && B > 0 && d0 > 0 && d1 > 0 && d2 > 0, "sv_binvox_encode: bad arguments");
+  SV_REQUIRE((long long)d0 * d1 * d2 < (1ll << 30), "sv_binvox_encode: volume too large");
+  SV_REQUIRE(dtype == 0 || dtype == 1, "sv_binvox_encode: dtype %d is neither 0 (float32) nor 1 (uint8)", dtype);
+  SV_REQUIRE(threshold < 0.f || (threshold > 0.f && threshold < 1.f), "sv_binvox_encode: threshold must be negative (occupancy input) or in (0, 1)");
+  SV_REQUIRE(threshold < 0.f || dtype == 0, "sv_binvox_encode: a sigmoid threshold needs float32 logits");
+  SV_REQUIRE(pair_capacity >= (long long)d0 * d1 * d2, "sv_binvox_encode: pair_capacity %lld is below the %lld voxels of a volume", pair_capacity,
+             (long long)d0 * d1 * d2);
+  hipLaunchKernelGGL(binvox_encode_kernel, dim3(B), dim3(256), 0, STREAM, vol, dtype, d0, d1, d2, fix_coords, threshold, pairs, pair_capacity, n_pairs);
+  return check_launch("sv_binvox_encode");
 }
 
 extern "C" int sv_augment_views(const unsigned char* src, int I, int V, int Hs, int Ws, int C, int crop_h, int crop_w, int out_h, int out_w,

@@ -75,6 +75,54 @@ def decode_binvox_batch(files: Sequence[bytes], device, fix_coords: bool = True,
     return out
 
 
+def binvox_header(dims, translate=(0.0, 0.0, 0.0), scale=1.0) -> bytes:
+    """The five header lines utils/binvox_rw.py:254-262 writes, formatted the same way (str() of every number)."""
+    return ("#binvox 1\ndim %s\ntranslate %s\nscale %s\ndata\n"
+            % (" ".join(map(str, dims)), " ".join(map(str, translate)), str(scale))).encode("latin-1")
+
+
+def _per_volume(value, B: int, is_single, what: str) -> list:
+    if is_single(value):
+        return [value] * B
+    value = list(value)
+    if len(value) != B:
+        raise ValueError(f"encode_binvox_batch: {what} must be one value or one per volume ({B}), got {len(value)}")
+    return value
+
+
+def encode_binvox_batch(volumes: torch.Tensor, threshold: Optional[float] = None, translate=(0.0, 0.0, 0.0), scale=1.0,
+                        fix_coords: bool = True) -> List[bytes]:
+    """[B, a, b, c] on the GPU -> B binvox files (whole file contents), the bytes utils/binvox_rw.py:239-292 (write) produces,
+    zero-count pairs included (see sv_binvox_encode in the header).  float32 / uint8 / bool volumes are occupancy (set iff != 0);
+    with `threshold` in (0, 1) the volumes are float32 logits and a voxel is set iff sigmoid(x) >= threshold, the predicate of
+    voxel_metrics.  The header dims are (a, c, b) with fix_coords (xyz input, as decode_binvox_batch returns it), (a, b, c)
+    without, so decode_binvox_batch(encode_binvox_batch(v)) == v.  translate (three numbers) and scale (a number) may also be
+    given per volume.  One kernel launch and two device-to-host copies whatever B is: the pair counts, then the payload
+    trimmed to the longest stream."""
+    hip.check_cuda(volumes)
+    if volumes.dim() != 4 or volumes.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise RuntimeError("encode_binvox_batch expects float32, uint8 or bool [B, a, b, c]")
+    if threshold is not None and (not 0.0 < float(threshold) < 1.0 or volumes.dtype != torch.float32):
+        raise ValueError("encode_binvox_batch: threshold must lie in (0, 1) and needs float32 logits")
+    B, a, b, c = volumes.shape
+    if B == 0:
+        raise ValueError("encode_binvox_batch: no volumes")
+    d0, d1, d2 = (a, c, b) if fix_coords else (a, b, c)
+    trs = _per_volume(translate, B, lambda t: not hasattr(t[0], "__len__"), "translate")
+    scs = _per_volume(scale, B, lambda s: not hasattr(s, "__len__"), "scale")
+    vol = volumes.contiguous()
+    if vol.dtype == torch.bool:
+        vol = vol.view(torch.uint8)
+    total = d0 * d1 * d2
+    pairs = torch.empty(B, total, 2, dtype=torch.uint8, device=vol.device)
+    n_pairs = torch.empty(B, dtype=torch.int32, device=vol.device)
+    call("sv_binvox_encode", ptr(vol), 0 if vol.dtype == torch.float32 else 1, B, d0, d1, d2, 1 if fix_coords else 0,
+         -1.0 if threshold is None else float(threshold), ptr(pairs), total, ptr(n_pairs))
+    counts = n_pairs.tolist()
+    payload = pairs[:, :max(counts)].cpu().numpy()
+    return [binvox_header((d0, d1, d2), trs[i], scs[i]) + payload[i, :counts[i]].tobytes() for i in range(B)]
+
+
 # ---- augmentation -----------------------------------------------------------------------------------------------------------
 @dataclass
 class AugParams:

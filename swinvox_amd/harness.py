@@ -18,6 +18,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import hip
+from .data import encode_binvox_batch
 from .hip import call, ptr
 from .losses import bce_with_logits as _bce      # torch.nn.BCEWithLogitsLoss() of core/train.py:165 on sv_bce_logits
 from .optim import FlatAdam, FlatSGD, _FlatSolver
@@ -139,6 +140,32 @@ def evaluate(nets, cfg, images, gt, epoch_idx: int = 0, with_fscore: bool = Fals
             n.train(t)
     iou, fs = voxel_metrics(volume, gt, cfg.TEST.VOXEL_THRESH)
     return (el * 10, rl * 10, iou, fs) if with_fscore else (el * 10, rl * 10, iou)
+
+
+@torch.no_grad()
+def reconstruct(nets, cfg, images, epoch_idx: int = 0, binvox_threshold: Optional[float] = None):
+    """The forward of core/test.py:120-130 without ground truth: the [B, 32, 32, 32] logits of the last active module, with the
+    merger / refiner gating of forward_losses and the nets in eval() for the pass, as in evaluate.  With binvox_threshold the
+    result is (volume, files): files[b] is the binvox file of sigmoid(volume[b]) >= binvox_threshold, the occupancy
+    voxel_metrics scores at that threshold (data.encode_binvox_batch)."""
+    enc, dec, mer, ref = nets
+    was_training = [n.training for n in nets]
+    for n in nets:
+        n.eval()
+    try:
+        raw, vol = dec(enc(images))
+        if cfg.NETWORK.USE_MERGER and epoch_idx >= cfg.TRAIN.EPOCH_START_USE_MERGER:
+            volume = mer(raw, vol)
+        else:
+            volume = _MeanViews.apply(vol)
+        if cfg.NETWORK.USE_REFINER and epoch_idx >= cfg.TRAIN.EPOCH_START_USE_REFINER:
+            volume = ref(volume)
+    finally:
+        for n, t in zip(nets, was_training):
+            n.train(t)
+    if binvox_threshold is None:
+        return volume
+    return volume, encode_binvox_batch(volume, threshold=binvox_threshold)
 
 
 def aggregate_by_taxonomy(taxonomy_ids: Sequence, per_sample):
