@@ -746,6 +746,33 @@ int sv_augment_views(const unsigned char* src, int I, int V, int Hs, int Ws, int
 int sv_binvox_encode(const void* vol, int dtype, int B, int d0, int d1, int d2, int fix_coords, float threshold,
                      unsigned char* pairs, long long pair_capacity, int* n_pairs, void* stream);
 
+/* sv_augment_images: the bounding-box branch of CenterCrop / RandomCrop (utils/data_transforms.py:93-136, :187-232), which the
+ *    Pascal3D and Pix3D loaders take for every sample (utils/data_loaders.py:176-180, :311-315), followed by the rest of the
+ *    transform list as sv_augment_views applies it.  I photographs of DIFFERING sizes, one view each, packed into one 8-bit
+ *    buffer `src` of src_bytes bytes; image i is [Hs][Ws][C] at byte offset images[i].offset (no alignment required).  All
+ *    images of a call share C (3 or 4).  The kept rectangle is img[y_top:y_bottom + 1, x_left:x_right + 1] (inclusive, as
+ *    the reference writes it) and the pads are those of its np.pad(..., mode='edge'): the padded crop is
+ *    cw = pad_l + (x_right - x_left + 1) + pad_r wide and ch = pad_t + (y_bottom - y_top + 1) + pad_b high and is resized
+ *    (cv2.resize INTER_LINEAR, separate scales cw / out_w and ch / out_h) to (out_h, out_w).  No padded copy is made:
+ *    padded coordinate s reads source column clamp(x_left - pad_l + s, x_left, x_right), likewise in y.  An image without a
+ *    box uses the same table with zero pads and the centre-crop rectangle of sv_augment_views (or the whole image).
+ *    How the reference gets the integers from a box in fractions of the image (Python doubles, int() truncating toward
+ *    zero) is restated in INTEGRATION.md and swinvox_amd/data.py (bbox_crop_rect); callers of the C ABI compute them so.
+ *    images_host (host memory) is validated BEFORE anything is launched - rectangle non-empty and inside the image, pads
+ *    >= 0, cw / ch / Hs / Ws at most 2^24, offset >= 0 and offset + Hs*Ws*C <= src_bytes - and then copied to
+ *    images_dev_ws (I descriptors of device scratch) on the stream; a bad table is an error code, never a read outside
+ *    `src`.  params_dev: one sv_aug_sample per image; flip_dev: one byte per image or NULL; grey_sum_ws: I doubles of
+ *    scratch; out [I][3][out_h][out_w] fp32.  I <= 65535.                                                                */
+typedef struct sv_aug_image {
+  long long offset;                        /* byte offset of the image's first pixel in src                                */
+  int Hs, Ws;                              /* its height and width                                                         */
+  int x_left, x_right, y_top, y_bottom;    /* kept rectangle, inclusive, inside the image                                  */
+  int pad_l, pad_r, pad_t, pad_b;          /* edge-replicated columns / rows around it                                     */
+} sv_aug_image;
+int sv_augment_images(const unsigned char* src, long long src_bytes, int I, int C, const sv_aug_image* images_host,
+                      sv_aug_image* images_dev_ws, int out_h, int out_w, const sv_aug_sample* params_dev,
+                      const unsigned char* flip_dev, double* grey_sum_ws, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,7 +53,22 @@ t0 = time.perf_counter()
 for b in range(a.batch):
     OD.write_binvox(vols[b])
 t_wr = (time.perf_counter() - t0) * 1e3
+# photographs with bounding boxes (the Pascal3D / Pix3D branch): 32 images of 640 x 480 x 3, each cropped to its jittered box
+photos = [rng.integers(0, 256, size=(480, 640, 3), dtype=np.uint8) for _ in range(32)]
+boxes = [(0.1 + 0.2 * rng.random(), 0.1 + 0.2 * rng.random(), 0.7 + 0.35 * rng.random(), 0.7 + 0.35 * rng.random()) for _ in photos]
+pparams = [D.draw_train_params(1, cfg, n_channels=3, bounding_box=b) for b in boxes]
+t_box = timed(lambda: D.augment_images(photos, boxes, pparams, cfg, device=dev))
+t0 = time.perf_counter()
+for im, box, p in list(zip(photos, boxes, pparams))[:4]:
+    xl, xr, yt, yb, pl, pr, pt, pb = D.bbox_crop_rect(480, 640, box, p.crop_draws)
+    crop = np.pad(im[yt:yb + 1, xl:xr + 1], ((pt, pb), (pl, pr), (0, 0)), mode="edge")
+    OD.transform_views(crop[None], dict(bg=np.asarray(p.bg), jitter_value=p.jitter_value, jitter_order=list(p.jitter_order),
+                                        noise_alpha=np.asarray(p.noise_alpha), flips=list(p.flips), perm=list(p.perm)),
+                       crop_size=(max(crop.shape[0], 224) + 1, max(crop.shape[1], 224) + 1))
+t_box_cpu = (time.perf_counter() - t0) / 4 * len(photos) * 1e3
 n = a.batch * a.views
+print(f"augment_images  {t_box:7.3f} ms / batch of {len(photos)} photographs 640x480x3 with boxes ({len(photos) / t_box * 1e3:9.0f} images/s, host packing and "
+      f"the H2D copy of {sum(im.size for im in photos) / 1e6:.1f} MB included); numpy restatement of the same path, one core: {t_box_cpu:7.1f} ms")
 print(f"augment_views   {t_aug:7.3f} ms / batch of {n} views ({n / t_aug * 1e3:9.0f} views/s, host parameter packing included)")
 print(f"binvox decode   {t_vox:7.3f} ms / {a.batch} volumes (header parsing + H2D of the run-length bytes included)")
 print(f"binvox encode   {t_enc:7.3f} ms / {a.batch} volumes (pair counts + trimmed payload D2H and header formatting included); "

@@ -6,6 +6,8 @@
 //   sv_binvox_encode  the way back (utils/binvox_rw.py:239-292): dense occupancy or thresholded logits -> the writer's byte pairs
 //   sv_augment_views  crop -> bilinear resize -> background composite -> colour jitter -> PCA noise -> normalise ->
 //                     flip -> channel permutation -> CHW float, two launches (grey means for the contrast step, then the image)
+//   sv_augment_images the same for a ragged batch of photographs, each cropped to its bounding box with edge padding
+//                     (utils/data_transforms.py:93-136, :187-232): one launch pair, a descriptor per image
 #include "common.h"
 
 namespace sv {
@@ -189,8 +191,21 @@ __device__ __forceinline__ void lin_coord(int d, double scale, int ssize, int& s
   f = fx;
 }
 
-// resized crop at (oy, ox): horizontal pass on the two source rows, then the vertical pass; products and sums are rounded
-// separately (no fused multiply-add) so that the CPU restatement reproduces them bit for bit
+// the four taps of one resized pixel (rows r0 / r1, pixel columns x0 / x1 in them): horizontal pass on the two source rows, then the
+// vertical pass; products and sums are rounded separately (no fused multiply-add) so that the CPU restatement reproduces them bit for bit
+__device__ __forceinline__ void blend_taps(const unsigned char* __restrict__ r0, const unsigned char* __restrict__ r1, int x0, int x1, int C, float fx,
+                                           float fy, float px[4]) {
+  const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
+  for (int c = 0; c < C; ++c) {
+    const float t00 = (float)r0[x0 * C + c] / 255.f, t01 = (float)r0[x1 * C + c] / 255.f;
+    const float t10 = (float)r1[x0 * C + c] / 255.f, t11 = (float)r1[x1 * C + c] / 255.f;
+    const float h0 = __fadd_rn(__fmul_rn(t00, a0), __fmul_rn(t01, a1));
+    const float h1 = __fadd_rn(__fmul_rn(t10, a0), __fmul_rn(t11, a1));
+    px[c] = __fadd_rn(__fmul_rn(h0, b0), __fmul_rn(h1, b1));
+  }
+}
+
+// resized crop at (oy, ox)
 __device__ __forceinline__ void sample_pixel(const unsigned char* __restrict__ img, const AugGeom& g, int oy, int ox, float px[4]) {
   int sx, sy;
   float fx, fy;
@@ -199,14 +214,7 @@ __device__ __forceinline__ void sample_pixel(const unsigned char* __restrict__ i
   const int sx1 = min(sx + 1, g.cw - 1), sy1 = min(sy + 1, g.ch - 1);
   const unsigned char* r0 = img + ((size_t)(g.y0 + sy) * g.Ws + g.x0) * g.C;
   const unsigned char* r1 = img + ((size_t)(g.y0 + sy1) * g.Ws + g.x0) * g.C;
-  const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
-  for (int c = 0; c < g.C; ++c) {
-    const float t00 = (float)r0[sx * g.C + c] / 255.f, t01 = (float)r0[sx1 * g.C + c] / 255.f;
-    const float t10 = (float)r1[sx * g.C + c] / 255.f, t11 = (float)r1[sx1 * g.C + c] / 255.f;
-    const float h0 = __fadd_rn(__fmul_rn(t00, a0), __fmul_rn(t01, a1));
-    const float h1 = __fadd_rn(__fmul_rn(t10, a0), __fmul_rn(t11, a1));
-    px[c] = __fadd_rn(__fmul_rn(h0, b0), __fmul_rn(h1, b1));
-  }
+  blend_taps(r0, r1, sx, sx1, g.C, fx, fy, px);
 }
 
 // RandomBackground: pixels whose (resized) alpha is exactly zero take the background colour
@@ -274,6 +282,97 @@ __global__ void __launch_bounds__(256) augment_apply_kernel(const unsigned char*
   }
 }
 
+// ---- ragged form of the two kernels above (sv_augment_images): grid (blocks, I), image blockIdx.y described by images[blockIdx.y], one
+// sv_aug_sample and one flip byte per image.  The two paths share lin_coord, blend_taps, composite and grey_of.  The kernel bodies mirror
+// the dense ones statement for statement instead of sharing a function: the jitter and normalise expressions are left to the compiler's
+// contraction, and moving them into a shared function changed which products it fuses in augment_apply_kernel (last-bit changes in
+// sv_augment_views).  Mirrored, the dense kernels compile to the instructions they had before, and an unboxed batch of equal sizes gives
+// the bits of sv_augment_views (tests/test_gpu_bbox_crop.py).
+struct BoxGeom {
+  int Ws, C, cw, ch, Ho, Wo;
+  int xo, yo;                   // source coordinate of padded coordinate 0 (x_left - pad_l, y_top - pad_t; negative inside the padding)
+  int xl, xr, yt, yb;           // kept rectangle, inclusive
+};
+__device__ __forceinline__ BoxGeom box_geom(const sv_aug_image& d, int C, int Ho, int Wo) {
+  BoxGeom g;
+  g.Ws = d.Ws; g.C = C; g.Ho = Ho; g.Wo = Wo;
+  g.cw = d.pad_l + (d.x_right - d.x_left + 1) + d.pad_r;
+  g.ch = d.pad_t + (d.y_bottom - d.y_top + 1) + d.pad_b;
+  g.xo = d.x_left - d.pad_l; g.yo = d.y_top - d.pad_t;
+  g.xl = d.x_left; g.xr = d.x_right; g.yt = d.y_top; g.yb = d.y_bottom;
+  return g;
+}
+
+// lin_coord runs in the coordinates of the padded crop (cw x ch); np.pad(..., mode='edge') is the clamp of a padded coordinate onto the
+// kept rectangle, so no padded copy exists.  Bytes only: an image starts wherever the one before it ended.
+__device__ __forceinline__ void sample_pixel(const unsigned char* __restrict__ img, const BoxGeom& g, int oy, int ox, float px[4]) {
+  int sx, sy;
+  float fx, fy;
+  lin_coord(ox, (double)g.cw / g.Wo, g.cw, sx, fx);
+  lin_coord(oy, (double)g.ch / g.Ho, g.ch, sy, fy);
+  const int sx1 = min(sx + 1, g.cw - 1), sy1 = min(sy + 1, g.ch - 1);
+  const int x0 = min(max(g.xo + sx, g.xl), g.xr), x1 = min(max(g.xo + sx1, g.xl), g.xr);
+  const int y0 = min(max(g.yo + sy, g.yt), g.yb), y1 = min(max(g.yo + sy1, g.yt), g.yb);
+  blend_taps(img + (size_t)y0 * g.Ws * g.C, img + (size_t)y1 * g.Ws * g.C, x0, x1, g.C, fx, fy, px);
+}
+
+__global__ void __launch_bounds__(256) augment_images_grey_mean_kernel(const unsigned char* __restrict__ src, const sv_aug_image* __restrict__ images,
+                                                                       int C, int Ho, int Wo, const sv_aug_sample* __restrict__ prm,
+                                                                       double* __restrict__ grey_sum) {
+  __shared__ float red[4];
+  const int img = blockIdx.y;
+  const sv_aug_sample& P = prm[img];
+  const BoxGeom g = box_geom(images[img], C, Ho, Wo);
+  const unsigned char* s = src + images[img].offset;
+  const int npix = g.Ho * g.Wo;
+  float acc = 0.f;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
+    float px[4];
+    sample_pixel(s, g, p / g.Wo, p % g.Wo, px);
+    composite(px, g.C, P.bg);
+    acc += grey_of(px);
+  }
+  const float r = block_sum<4>(acc, red);
+  if (threadIdx.x == 0) atomicAdd(&grey_sum[img], (double)r);
+}
+
+__global__ void __launch_bounds__(256) augment_images_apply_kernel(const unsigned char* __restrict__ src, const sv_aug_image* __restrict__ images, int C,
+                                                                   int Ho, int Wo, const sv_aug_sample* __restrict__ prm,
+                                                                   const unsigned char* __restrict__ flip, const double* __restrict__ grey_sum,
+                                                                   float* __restrict__ out) {
+  const int img = blockIdx.y;
+  const sv_aug_sample P = prm[img];
+  const BoxGeom g = box_geom(images[img], C, Ho, Wo);
+  const unsigned char* s = src + images[img].offset;
+  const int npix = g.Ho * g.Wo;
+  const bool fl = flip != nullptr && flip[img] != 0;
+  float mean_grey = (float)(grey_sum[img] / (double)npix);
+  float contrast_mean = mean_grey;                                 // as in augment_apply_kernel
+  for (int k = 0; k < 3; ++k) {
+    if (P.jitter_order[k] == 1) break;
+    if (P.jitter_order[k] == 0) contrast_mean *= P.jitter_value[0];
+  }
+  float* o = out + (size_t)img * 3 * npix;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
+    const int oy = p / g.Wo, ox = p % g.Wo;
+    float px[4];
+    sample_pixel(s, g, oy, fl ? g.Wo - 1 - ox : ox, px);
+    composite(px, g.C, P.bg);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int kind = P.jitter_order[k];
+      const float a = P.jitter_value[kind];
+      const float other = kind == 0 ? 0.f : (kind == 1 ? contrast_mean : grey_of(px));
+#pragma unroll
+      for (int c = 0; c < 3; ++c) px[c] = a * px[c] + (1.f - a) * other;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[c] = (px[c] + P.noise[c] - P.mean[c]) / P.std[c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[(size_t)c * npix + p] = px[P.perm[c]];
+  }
+}
+
 }  // namespace sv
 
 using namespace sv;
@@ -317,4 +416,41 @@ extern "C" int sv_augment_views(const unsigned char* src, int I, int V, int Hs, 
   hipLaunchKernelGGL(augment_grey_mean_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, g, params_dev, grey_sum_ws);
   hipLaunchKernelGGL(augment_apply_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, g, params_dev, flip_dev, grey_sum_ws, out);
   return check_launch("sv_augment_views");
+}
+
+// CenterCrop / RandomCrop with a bounding box (data_transforms.py:93-136 / :187-232) for a ragged batch, then the list of sv_augment_views
+extern "C" int sv_augment_images(const unsigned char* src, long long src_bytes, int I, int C, const sv_aug_image* images_host,
+                                 sv_aug_image* images_dev_ws, int out_h, int out_w, const sv_aug_sample* params_dev, const unsigned char* flip_dev,
+                                 double* grey_sum_ws, float* out, void* stream) {
+  SV_REQUIRE(src && images_host && images_dev_ws && params_dev && grey_sum_ws && out, "augment_images: bad arguments");
+  SV_REQUIRE(I > 0 && I <= 65535, "augment_images: %d images (1 ... 65535 per call)", I);
+  SV_REQUIRE(C == 3 || C == 4, "augment_images: %d channels (3 or 4)", C);
+  SV_REQUIRE(out_h > 0 && out_w > 0 && (long long)out_h * out_w < (1ll << 30), "augment_images: bad output size %d x %d", out_h, out_w);
+  SV_REQUIRE(src_bytes > 0, "augment_images: empty source buffer");
+  constexpr int LIM = 1 << 24;                                       // keeps every coordinate sum and Hs*Ws*C far from overflow
+  for (int i = 0; i < I; ++i) {                                      // the whole table, on the host, before anything is launched
+    const sv_aug_image& d = images_host[i];
+    SV_REQUIRE(d.Hs > 0 && d.Ws > 0 && d.Hs <= LIM && d.Ws <= LIM, "augment_images: image %d has size %d x %d", i, d.Hs, d.Ws);
+    SV_REQUIRE(d.offset >= 0 && d.offset <= src_bytes && (long long)d.Hs * d.Ws * C <= src_bytes - d.offset,
+               "augment_images: image %d (offset %lld, %d x %d x %d) does not lie inside the %lld bytes of the source buffer", i, d.offset, d.Hs, d.Ws,
+               C, src_bytes);
+    SV_REQUIRE(d.x_left >= 0 && d.x_left <= d.x_right && d.x_right < d.Ws && d.y_top >= 0 && d.y_top <= d.y_bottom && d.y_bottom < d.Hs,
+               "augment_images: image %d keeps columns [%d, %d] and rows [%d, %d]: empty or outside its %d x %d pixels", i, d.x_left, d.x_right,
+               d.y_top, d.y_bottom, d.Hs, d.Ws);
+    SV_REQUIRE(d.pad_l >= 0 && d.pad_r >= 0 && d.pad_t >= 0 && d.pad_b >= 0, "augment_images: image %d has a negative pad (%d, %d, %d, %d)", i,
+               d.pad_l, d.pad_r, d.pad_t, d.pad_b);
+    SV_REQUIRE(d.pad_l <= LIM && d.pad_r <= LIM && d.pad_t <= LIM && d.pad_b <= LIM &&
+                   (long long)d.pad_l + (d.x_right - d.x_left + 1) + d.pad_r <= LIM && (long long)d.pad_t + (d.y_bottom - d.y_top + 1) + d.pad_b <= LIM,
+               "augment_images: the padded crop of image %d is larger than %d", i, LIM);
+  }
+  // pageable host memory: the copy has read images_host when the call returns
+  hipError_t e = hipMemcpyAsync(images_dev_ws, images_host, sizeof(sv_aug_image) * (size_t)I, hipMemcpyHostToDevice, STREAM);
+  if (e != hipSuccess) { set_error("augment_images: descriptor copy failed: %s", hipGetErrorString(e)); return SV_ERR_LAUNCH; }
+  e = hipMemsetAsync(grey_sum_ws, 0, sizeof(double) * (size_t)I, STREAM);
+  if (e != hipSuccess) { set_error("augment_images: memset failed: %s", hipGetErrorString(e)); return SV_ERR_LAUNCH; }
+  const int bx = cdiv((long long)out_h * out_w, 256 * 4);
+  hipLaunchKernelGGL(augment_images_grey_mean_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, images_dev_ws, C, out_h, out_w, params_dev, grey_sum_ws);
+  hipLaunchKernelGGL(augment_images_apply_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, images_dev_ws, C, out_h, out_w, params_dev, flip_dev,
+                     grey_sum_ws, out);
+  return check_launch("sv_augment_images");
 }

@@ -5,6 +5,8 @@ The reference expands every sample on the CPU inside DataLoader workers (np.repe
 passes per rendering).  Here the workers only read bytes: run-length pairs and 8-bit renderings go to the GPU as they are and
 two entry points expand a whole batch - sv_binvox_decode and sv_augment_views.  Random augmentation parameters are drawn on
 the host in the reference's call order (draw_train_params), so a seeded run sees the same crops / colours / flips.
+Photographs with bounding boxes (the Pascal3D / Pix3D loaders, utils/data_loaders.py:176-203, :311-338) go through augment_images:
+images of differing sizes in one packed buffer, the reference's crop integers computed on the host (bbox_crop_rect), one launch pair.
 """
 from __future__ import annotations
 
@@ -133,17 +135,24 @@ class AugParams:
     noise_alpha: Sequence[float] = (0.0, 0.0, 0.0)        # PCA coefficients of RandomNoise
     flips: Sequence[bool] = field(default_factory=list)
     perm: Sequence[int] = (0, 1, 2)
+    crop_draws: Optional[Sequence[float]] = None          # RandomCrop with a bounding box: scale, then left / right / top / bottom (:203-208)
 
     def noise_rgb(self) -> np.ndarray:
         a = np.asarray(self.noise_alpha, dtype=np.float64)   # utils/data_transforms.py:373-383
         return np.sum(np.multiply(np.multiply(np.array(EIGVECS), np.tile(a, (3, 1))), np.tile(np.array(EIGVALS), (3, 1))), axis=1)
 
 
-def draw_train_params(n_views: int, cfg, rng_np=np.random, rng_py=random, n_channels: int = 4) -> AugParams:
+def draw_train_params(n_views: int, cfg, rng_np=np.random, rng_py=random, n_channels: int = 4, bounding_box=None) -> AugParams:
     """One __getitem__ worth of random draws in the reference's call order: RandomBackground (data_transforms.py:425-428, plus
     the per-image random.randint of :440), ColorJitter (:276-284), RandomNoise (:372), RandomFlip (:252-255),
     RandomPermuteRGB (:67).  RandomCrop draws nothing without a bounding box (:222-231).  RandomBackground returns before it draws
-    anything when the renderings have no alpha channel (:428-430): pass n_channels=3 for RGB inputs."""
+    anything when the renderings have no alpha channel (:428-430): pass n_channels=3 for RGB inputs.
+    With a bounding_box (any non-None value; its numbers are not used here) RandomCrop, the first transform of the list
+    (core/train.py:44-53), draws first: random.uniform(0.8, 1.2) and four random.uniform(.4, .6) (:203-208) -> crop_draws."""
+    crop_draws = None
+    if bounding_box is not None:
+        _refuse_box_with_views(n_views, "draw_train_params")
+        crop_draws = [rng_py.uniform(0.8, 1.2)] + [rng_py.uniform(.4, .6) for _ in range(4)]
     t = cfg.TRAIN
     rg = t.RANDOM_BG_COLOR_RANGE
     if n_channels == 4:
@@ -160,7 +169,7 @@ def draw_train_params(n_views: int, cfg, rng_np=np.random, rng_py=random, n_chan
     flips = [bool(rng_py.randint(0, 1)) for _ in range(n_views)]
     perm = rng_np.permutation(3)
     return AugParams(bg=bg.tolist(), jitter_value=jv, jitter_order=[int(i) for i in order], noise_alpha=alpha.tolist(), flips=flips,
-                     perm=[int(i) for i in perm])
+                     perm=[int(i) for i in perm], crop_draws=crop_draws)
 
 
 def val_params(n_views: int, cfg, n_channels: int = 4) -> AugParams:
@@ -168,6 +177,81 @@ def val_params(n_views: int, cfg, n_channels: int = 4) -> AugParams:
     rg = cfg.TEST.RANDOM_BG_COLOR_RANGE
     bg = np.array([np.random.randint(rg[i][0], rg[i][1] + 1) for i in range(3)]) / 255.0 if n_channels == 4 else np.ones(3)
     return AugParams(bg=bg.tolist(), flips=[False] * n_views)
+
+
+def _refuse_box_with_views(n_views: int, who: str) -> None:
+    if n_views != 1:
+        raise ValueError(f"{who}: a bounding box goes with one view per sample, got {n_views}: the reference multiplies the box by the image "
+                         "size again for every view (data_transforms.py:94-99 sits inside the per-image loop), which compounds for "
+                         "V > 1 and is not reproduced")
+
+
+def bbox_crop_rect(img_height: int, img_width: int, bounding_box=None, crop_draws=None, crop_size=None):
+    """Integers of the reference's crop: (x_left, x_right, y_top, y_bottom, pad_l, pad_r, pad_t, pad_b); the kept rectangle is
+    img[y_top:y_bottom + 1, x_left:x_right + 1] (inclusive) and np.pad(..., mode='edge') by the pads makes the crop that is resized.
+    With a bounding_box (x0, y0, x1, y1 in fractions of the image): utils/data_transforms.py:93-130 (CenterCrop; crop_draws None)
+    and :187-226 (RandomCrop; crop_draws = the five uniform draws of AugParams.crop_draws) in Python doubles and int(), so truncation
+    toward zero and rounding are the reference's.  Without one: the centre crop of :137-147 / :233-243 when the image is larger
+    than crop_size = (crop_h, crop_w) in both directions, else the whole image; pads 0.
+    ValueError when the clamped rectangle is empty (a box outside the image, or one of negative extent): the reference slices
+    nothing there and fails inside cv2.resize (for x_right or y_bottom below -1 its slice end wraps round instead; not reproduced)."""
+    H, W = int(img_height), int(img_width)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"bbox_crop_rect: bad image size {H} x {W}")
+    if bounding_box is None:
+        if crop_size is not None and H > crop_size[0] and W > crop_size[1] and crop_size[0] > 0 and crop_size[1] > 0:
+            x_left, y_top = int(W - crop_size[1]) // 2, int(H - crop_size[0]) // 2
+            return x_left, x_left + int(crop_size[1]) - 1, y_top, y_top + int(crop_size[0]) - 1, 0, 0, 0, 0
+        return 0, W - 1, 0, H - 1, 0, 0, 0, 0
+    if len(bounding_box) != 4:
+        raise ValueError("bbox_crop_rect: a bounding box is (x0, y0, x1, y1) in fractions of the image")
+    box = [float(bounding_box[0]) * W, float(bounding_box[1]) * H, float(bounding_box[2]) * W, float(bounding_box[3]) * H]
+    if not all(np.isfinite(box)):
+        raise ValueError(f"bbox_crop_rect: box {tuple(bounding_box)} is not finite")
+    bbox_width, bbox_height = box[2] - box[0], box[3] - box[1]
+    x_mid, y_mid = (box[2] + box[0]) * .5, (box[3] + box[1]) * .5
+    size = max(bbox_width, bbox_height)
+    if crop_draws is None:                                    # CenterCrop :108-112
+        left = right = top = bottom = .5
+    else:                                                     # RandomCrop :202-208
+        if len(crop_draws) != 5:
+            raise ValueError("bbox_crop_rect: crop_draws holds five numbers (scale, left, right, top, bottom)")
+        scale, left, right, top, bottom = (float(d) for d in crop_draws)
+        size = size * scale
+    x_left, x_right = int(x_mid - size * left), int(x_mid + size * right)
+    y_top, y_bottom = int(y_mid - size * top), int(y_mid + size * bottom)
+    pad_l = pad_r = pad_t = pad_b = 0
+    if x_left < 0:
+        pad_l, x_left = -x_left, 0
+    if x_right >= W:
+        pad_r, x_right = x_right - W + 1, W - 1
+    if y_top < 0:
+        pad_t, y_top = -y_top, 0
+    if y_bottom >= H:
+        pad_b, y_bottom = y_bottom - H + 1, H - 1
+    if x_left > x_right or y_top > y_bottom:
+        raise ValueError(f"bbox_crop_rect: box {tuple(bounding_box)} keeps columns [{x_left}, {x_right}] and rows [{y_top}, {y_bottom}] of a "
+                         f"{H} x {W} image: the rectangle is empty")
+    return x_left, x_right, y_top, y_bottom, pad_l, pad_r, pad_t, pad_b
+
+
+def _pack_aug_samples(params: Sequence[AugParams], V: int, cfg, who: str):
+    """host side of the sv_aug_sample table and the flip bytes: (ctypes array, uint8 [len(params) * V])"""
+    B = len(params)
+    arr = (hip.AugSample * B)()
+    flips = np.zeros(B * V, dtype=np.uint8)
+    mean, std = cfg.DATASET.MEAN, cfg.DATASET.STD
+    for b, p in enumerate(params):
+        if sorted(p.jitter_order) != [0, 1, 2] or sorted(p.perm) != [0, 1, 2] or len(p.flips) != V:
+            raise ValueError(f"{who}: malformed AugParams")
+        nz = p.noise_rgb()
+        s = arr[b]
+        for c in range(3):
+            s.bg[c], s.jitter_value[c], s.jitter_order[c] = float(p.bg[c]), float(p.jitter_value[c]), int(p.jitter_order[c])
+            s.noise[c] = float(nz[2 - c])                     # the reference adds noise_rgb[i] to channel 2 - i (:386-390)
+            s.perm[c], s.mean[c], s.std[c] = int(p.perm[c]), float(mean[c]), float(std[c])
+        flips[b * V:(b + 1) * V] = np.asarray(p.flips, dtype=np.uint8)
+    return arr, flips
 
 
 def augment_views(images_u8: torch.Tensor, params: Sequence[AugParams], cfg) -> torch.Tensor:
@@ -180,19 +264,7 @@ def augment_views(images_u8: torch.Tensor, params: Sequence[AugParams], cfg) -> 
     if len(params) != B:
         raise ValueError("augment_views: one AugParams per sample")
     images_u8 = images_u8.contiguous()
-    arr = (hip.AugSample * B)()
-    flips = np.zeros(B * V, dtype=np.uint8)
-    mean, std = cfg.DATASET.MEAN, cfg.DATASET.STD
-    for b, p in enumerate(params):
-        if sorted(p.jitter_order) != [0, 1, 2] or sorted(p.perm) != [0, 1, 2] or len(p.flips) != V:
-            raise ValueError("augment_views: malformed AugParams")
-        nz = p.noise_rgb()
-        s = arr[b]
-        for c in range(3):
-            s.bg[c], s.jitter_value[c], s.jitter_order[c] = float(p.bg[c]), float(p.jitter_value[c]), int(p.jitter_order[c])
-            s.noise[c] = float(nz[2 - c])                     # the reference adds noise_rgb[i] to channel 2 - i (:386-390)
-            s.perm[c], s.mean[c], s.std[c] = int(p.perm[c]), float(mean[c]), float(std[c])
-        flips[b * V:(b + 1) * V] = np.asarray(p.flips, dtype=np.uint8)
+    arr, flips = _pack_aug_samples(params, V, cfg, "augment_views")
     dev = images_u8.device
     prm = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
     fl = torch.from_numpy(flips).to(dev)
@@ -201,4 +273,78 @@ def augment_views(images_u8: torch.Tensor, params: Sequence[AugParams], cfg) -> 
     out = torch.empty(B, V, 3, H, W, dtype=torch.float32, device=dev)
     call("sv_augment_views", ptr(images_u8), B * V, V, Hs, Ws, Cc, cfg.CONST.CROP_IMG_H, cfg.CONST.CROP_IMG_W, H, W, ptr(prm), ptr(fl),
          ptr(ws), ptr(out))
+    return out
+
+
+def augment_images(images, boxes, params: Sequence[AugParams], cfg, sizes=None, device="cuda") -> torch.Tensor:
+    """A batch of photographs of differing sizes, one view per sample, each cropped to its bounding box: what the reference's
+    Pascal3D / Pix3D datasets hand to core/train.py:222 (utils/data_loaders.py:176-203, :311-338 with the transform lists of
+    core/train.py:44-59) -> float32 [B, 1, 3, IMG_H, IMG_W].
+    images: a list of B uint8 arrays (numpy or CPU tensors) [Hs_i, Ws_i, C] with one C (3, or 4 with alpha) for the whole batch; a 2-D
+    greyscale image is stacked to three channels (data_loaders.py:194-196).  They are packed end to end into one buffer that goes to
+    `device` in one copy.  Or: that packed buffer itself, a 1-D uint8 tensor already on the GPU, with sizes = [(Hs_i, Ws_i, C), ...]
+    in packing order.
+    boxes: None, or per image None / (x0, y0, x1, y1) in fractions of the image.  A boxed image is cropped by bbox_crop_rect with
+    its AugParams.crop_draws (None = CenterCrop, the validation list), an unboxed one by the centre-crop rule of augment_views."""
+    if isinstance(images, torch.Tensor) and sizes is None:
+        raise RuntimeError("augment_images: a packed buffer comes with sizes = [(Hs, Ws, C), ...]; separate images go in a list")
+    B = len(sizes) if isinstance(images, torch.Tensor) else len(images)
+    if B == 0:
+        raise ValueError("augment_images: no images")
+    if len(params) != B:
+        raise ValueError("augment_images: one AugParams per image")
+    boxes = [None] * B if boxes is None else list(boxes)
+    if len(boxes) != B:
+        raise ValueError("augment_images: one bounding box (or None) per image")
+    if isinstance(images, torch.Tensor):
+        hip.check_cuda(images)
+        if images.dtype != torch.uint8 or images.dim() != 1 or not images.is_contiguous():
+            raise RuntimeError("augment_images expects the packed buffer as contiguous 1-D uint8")
+        if any(len(s) != 3 for s in sizes):
+            raise RuntimeError("augment_images: sizes holds one (Hs, Ws, C) per packed image")
+        shapes, packed = [tuple(int(v) for v in s) for s in sizes], images
+    else:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("swinvox_amd: tensors must live on the GPU (no CPU path exists in the product)")
+        host = []
+        for im in images:
+            im = im.numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+            if im.dtype != np.uint8 or im.ndim not in (2, 3):
+                raise RuntimeError("augment_images expects uint8 images [Hs, Ws, C] (or [Hs, Ws] greyscale)")
+            if im.ndim == 2:
+                im = np.stack((im, ) * 3, -1)
+            host.append(im)
+        shapes = [im.shape for im in host]
+        packed = None
+    Cc = shapes[0][2]
+    if Cc not in (3, 4) or any(s[2] != Cc for s in shapes) or any(s[0] <= 0 or s[1] <= 0 for s in shapes):
+        raise RuntimeError(f"augment_images: every image of a call is [Hs, Ws, C] with the same C = 3 or 4, got {sorted(set(shapes))}")
+    crop = (cfg.CONST.CROP_IMG_H, cfg.CONST.CROP_IMG_W)
+    desc, off = (hip.AugImage * B)(), 0
+    for i, ((Hs, Ws, _), box, p) in enumerate(zip(shapes, boxes, params)):
+        rect = bbox_crop_rect(Hs, Ws, box, p.crop_draws if box is not None else None, crop)
+        if max(rect[4:]) > 1 << 24:                           # the entry's limit; checked here because a ctypes int field wraps silently
+            raise ValueError(f"augment_images: box {tuple(box)} pads image {i} by {rect[4:]} pixels (at most 2^24)")
+        d = desc[i]
+        d.offset, d.Hs, d.Ws = off, Hs, Ws
+        d.x_left, d.x_right, d.y_top, d.y_bottom, d.pad_l, d.pad_r, d.pad_t, d.pad_b = rect
+        off += Hs * Ws * Cc
+    arr, flips = _pack_aug_samples(params, 1, cfg, "augment_images")
+    if packed is None:
+        buf = np.empty(off, dtype=np.uint8)
+        for d, im in zip(desc, host):
+            buf[d.offset:d.offset + im.size] = im.reshape(-1)
+        packed = torch.from_numpy(buf).to(dev)
+        hip.check_cuda(packed)
+    elif packed.numel() < off:
+        raise RuntimeError(f"augment_images: the packed buffer holds {packed.numel()} bytes, sizes describe {off}")
+    dev = packed.device
+    prm = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    fl = torch.from_numpy(flips).to(dev)
+    ws = torch.empty(B, dtype=torch.float64, device=dev)
+    desc_dev = torch.empty(B * C.sizeof(hip.AugImage), dtype=torch.uint8, device=dev)
+    H, W = cfg.CONST.IMG_H, cfg.CONST.IMG_W
+    out = torch.empty(B, 1, 3, H, W, dtype=torch.float32, device=dev)
+    call("sv_augment_images", ptr(packed), packed.numel(), B, Cc, C.addressof(desc), ptr(desc_dev), H, W, ptr(prm), ptr(fl), ptr(ws), ptr(out))
     return out

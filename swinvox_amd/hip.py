@@ -72,6 +72,11 @@ class AugSample(C.Structure):   # sv_aug_sample
                 ("perm", C.c_int * 3), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
 
 
+class AugImage(C.Structure):   # sv_aug_image
+    _fields_ = [("offset", C.c_longlong), ("Hs", C.c_int), ("Ws", C.c_int), ("x_left", C.c_int), ("x_right", C.c_int), ("y_top", C.c_int),
+                ("y_bottom", C.c_int), ("pad_l", C.c_int), ("pad_r", C.c_int), ("pad_t", C.c_int), ("pad_b", C.c_int)]
+
+
 # name -> (restype, argtypes); p = device/host pointer, i = int, l = long long, f = float, u = uint32, z = size_t
 _P, _I, _L, _F, _U, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_uint32, C.c_double
 # Entry points whose activation tensors are void* + `int act_dtype` (inserted by call() right before the stream argument)
@@ -236,6 +241,7 @@ _PROTOS = {
     "sv_binvox_decode": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "sv_binvox_encode": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _L, _P]),
     "sv_augment_views": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "sv_augment_images": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "sv_grad_sumsq": (_I, [_P, _L, _F, _P]),
     "sv_adam_step": (_I, [_P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _L, _F, _P, _F, _P]),
     "sv_sgd_step": (_I, [_P, _P, _P, _L, _D, _D, _D, _L, _F, _P, _F, _P]),
