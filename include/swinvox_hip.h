@@ -746,6 +746,26 @@ int sv_augment_views(const unsigned char* src, int I, int V, int Hs, int Ws, int
 int sv_binvox_encode(const void* vol, int dtype, int B, int d0, int d1, int d2, int fix_coords, float threshold,
                      unsigned char* pairs, long long pair_capacity, int* n_pairs, void* stream);
 
+/* sv_voxel_surface: the exposed voxel faces of B volumes of equal dims as indexed quad meshes - the face set utils/helpers.py:50-88
+ *    (get_volume_views -> Axes3D.voxels, called from core/test.py:178-187) and utils/binvox_rw.py:306-343 draw.
+ *    `vol` is [B][d0][d1][d2] in its own axis order (no fix_coords transposition), every dim in 1 .. 64; dtype and threshold as
+ *    for sv_binvox_encode (0 = float32, 1 = uint8; threshold < 0: occupancy, set iff != 0; 0 < threshold < 1: float32 logits, set
+ *    iff 1.f / (1.f + expf(-x)) >= threshold), the same predicate, so mesh, .binvox file and reported IoU agree voxel for voxel.
+ *    Exposed face: voxel (x, y, z) is set and its neighbour in a direction is unset or outside the grid.
+ *    Face order: ascending voxel index (x*d1 + y)*d2 + z, then direction -x, +x, -y, +y, -z, +z.  Corners (offsets added to
+ *    (x, y, z)), counter-clockwise seen from outside:
+ *      -x (0,0,0) (0,0,1) (0,1,1) (0,1,0)     +x (1,0,0) (1,1,0) (1,1,1) (1,0,1)
+ *      -y (0,0,0) (1,0,0) (1,0,1) (0,0,1)     +y (0,1,0) (0,1,1) (1,1,1) (1,1,0)
+ *      -z (0,0,0) (0,1,0) (1,1,0) (1,0,0)     +z (0,0,1) (1,0,1) (1,1,1) (0,1,1)
+ *    Vertex order: the lattice points (i, j, k) of [0..d0] x [0..d1] x [0..d2] that are a corner of an exposed face, each once,
+ *    in ascending lattice index (i*(d1+1) + j)*(d2+1) + k.
+ *    verts + b * vert_capacity receives volume b's lattice indices, faces + b * 4 * face_capacity its quads as four indices
+ *    into that vertex list (`faces` 16-byte aligned), counts[2b] / counts[2b + 1] the number of vertices / faces.
+ *    vert_capacity >= (d0+1)(d1+1)(d2+1) and face_capacity >= 3*d0*d1*d2 + d0*d1 + d1*d2 + d0*d2 are required and always
+ *    suffice.  One workgroup per volume, no atomics: the output is deterministic.                                          */
+int sv_voxel_surface(const void* vol, int dtype, int B, int d0, int d1, int d2, float threshold, unsigned int* verts,
+                     long long vert_capacity, unsigned int* faces, long long face_capacity, int* counts, void* stream);
+
 /* sv_augment_images: the bounding-box branch of CenterCrop / RandomCrop (utils/data_transforms.py:93-136, :187-232), which the
  *    Pascal3D and Pix3D loaders take for every sample (utils/data_loaders.py:176-180, :311-315), followed by the rest of the
  *    transform list as sv_augment_views applies it.  I photographs of DIFFERING sizes, one view each, packed into one 8-bit

@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import swinvox_amd as S  # noqa: E402
 from oracle import data as OD  # noqa: E402
 from swinvox_amd import data as D  # noqa: E402
+from swinvox_amd.hip import call, ptr  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=32)
@@ -53,6 +54,42 @@ t0 = time.perf_counter()
 for b in range(a.batch):
     OD.write_binvox(vols[b])
 t_wr = (time.perf_counter() - t0) * 1e3
+# exposed voxel faces of the same 32 volumes as PLY files next to a plain per-voxel face loop on the host (what a mesh cost before:
+# a device-to-host copy of the volumes and this loop)
+SURF_DIRS = ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1))
+SURF_CORNERS = (((0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0)), ((1, 0, 0), (1, 1, 0), (1, 1, 1), (1, 0, 1)), ((0, 0, 0), (1, 0, 0), (1, 0, 1), (0, 0, 1)),
+                ((0, 1, 0), (0, 1, 1), (1, 1, 1), (1, 1, 0)), ((0, 0, 0), (0, 1, 0), (1, 1, 0), (1, 0, 0)), ((0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)))
+
+
+def host_face_loop(vol):
+    pad = np.pad(vol, 1)
+    quads = []
+    for x, y, z in np.argwhere(vol):
+        for (dx, dy, dz), corners in zip(SURF_DIRS, SURF_CORNERS):
+            if not pad[x + 1 + dx, y + 1 + dy, z + 1 + dz]:
+                quads.append([((x + a) * 33 + y + b) * 33 + z + c for a, b, c in corners])
+    lat = np.asarray(quads, np.int64).reshape(-1, 4)
+    used = np.unique(lat)
+    verts = np.stack([used // 1089, used // 33 % 33, used % 33], axis=1)
+    return D.mesh_file(verts, np.searchsorted(used, lat), "ply")
+
+
+t_mesh = timed(lambda: D.encode_mesh_batch(vol_dev), n=50)
+t_surf = timed(lambda: D.extract_surface_batch(vol_dev), n=50)
+sv, sf, sc = (torch.empty(s, dtype=torch.int32, device=dev) for s in ((a.batch, 33 ** 3), (a.batch, 3 * 32 ** 3 + 3 * 32 ** 2, 4), (a.batch, 2)))
+vol_u8 = vol_dev.view(torch.uint8)
+ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+surf_launch = lambda: call("sv_voxel_surface", ptr(vol_u8), 1, a.batch, 32, 32, 32, -1.0, ptr(sv), sv.shape[1], ptr(sf), sf.shape[1], ptr(sc))  # noqa: E731
+surf_launch(); torch.cuda.synchronize()
+ev0.record()
+for _ in range(50):
+    surf_launch()
+ev1.record(); torch.cuda.synchronize()
+t_surf_kernel = ev0.elapsed_time(ev1) / 50
+t0 = time.perf_counter()
+host_meshes = [host_face_loop(v) for v in vols]
+t_mesh_cpu = (time.perf_counter() - t0) * 1e3
+assert host_meshes == D.encode_mesh_batch(vol_dev)
 # photographs with bounding boxes (the Pascal3D / Pix3D branch): 32 images of 640 x 480 x 3, each cropped to its jittered box
 photos = [rng.integers(0, 256, size=(480, 640, 3), dtype=np.uint8) for _ in range(32)]
 boxes = [(0.1 + 0.2 * rng.random(), 0.1 + 0.2 * rng.random(), 0.7 + 0.35 * rng.random(), 0.7 + 0.35 * rng.random()) for _ in photos]
@@ -73,4 +110,7 @@ print(f"augment_views   {t_aug:7.3f} ms / batch of {n} views ({n / t_aug * 1e3:9
 print(f"binvox decode   {t_vox:7.3f} ms / {a.batch} volumes (header parsing + H2D of the run-length bytes included)")
 print(f"binvox encode   {t_enc:7.3f} ms / {a.batch} volumes (pair counts + trimmed payload D2H and header formatting included); "
       f"oracle.data.write_binvox on the host, one core: {t_wr:7.2f} ms")
+print(f"voxel surface   {t_mesh:7.3f} ms / {a.batch} volumes as PLY files (counts + trimmed payload D2H, lattice decode and PLY formatting included; "
+      f"{t_surf:7.3f} ms without the formatting, {t_surf_kernel:6.3f} ms the kernel alone by device events; {sum(len(m) for m in host_meshes) / 1e6:.2f} MB of files); per-voxel numpy face loop + the same formatting on "
+      f"the host, one core: {t_mesh_cpu:7.1f} ms")
 print(f"numpy restatement of the reference path, one core: {t_cpu:8.1f} ms / batch ({n / t_cpu * 1e3:7.0f} views/s)")

@@ -4,6 +4,7 @@
 //
 //   sv_binvox_decode  run-length (value, count) byte pairs -> dense float occupancy, xzy -> xyz transposition
 //   sv_binvox_encode  the way back (utils/binvox_rw.py:239-292): dense occupancy or thresholded logits -> the writer's byte pairs
+//   sv_voxel_surface  the exposed voxel faces the reference draws (utils/helpers.py:50-88, core/test.py:178-187) as an indexed quad mesh
 //   sv_augment_views  crop -> bilinear resize -> background composite -> colour jitter -> PCA noise -> normalise ->
 //                     flip -> channel permutation -> CHW float, two launches (grey means for the contrast step, then the image)
 //   sv_augment_images the same for a ragged batch of photographs, each cropped to its bounding box with edge padding
@@ -173,6 +174,167 @@ __global__ void __launch_bounds__(256) binvox_encode_kernel(const void* __restri
     int np = np_s;
     if (run_s % 255 > 0) put(np++, pv, run_s % 255);   // "flush out remainders"
     n_pairs[b] = np;
+  }
+}
+
+// ---- exposed voxel faces (utils/helpers.py:50-88 -> Axes3D.voxels; utils/binvox_rw.py:306-343): one workgroup per volume ---------
+// The quads that separate a filled voxel from an empty one or from the outside, as an indexed mesh in a fixed order (no atomics):
+//   (a) occupancy bit mask `occ` in LDS, bit p = voxel (x * d1 + y) * d2 + z, from a ballot over the input;
+//   (b) lattice "used" bit mask: point (i, j, k) of [0..d0] x [0..d1] x [0..d2] is a corner of an exposed face iff its 8 surrounding cells
+//       (outside = empty) are neither all filled nor all empty; `pre[w]` = used points in the words before w (workgroup sum-scan of the
+//       popcounts), so vertex id of lattice point l = pre[l >> 5] + popcount(used[l >> 5] & lower bits) - lattice rows are d2 + 1 points long,
+//       so a row's vertex run straddles words and nothing below assumes otherwise;
+//   (c) vertex list: the used lattice indices, ascending;
+//   (d) faces: every thread owns a contiguous run of voxels, counts their exposed faces (directions -x +x -y +y -z +z), one workgroup
+//       sum-scan gives its first slot, and each face is one 16-byte store of four vertex ids (corners counter-clockwise seen from outside).
+// LDS at MAXD = 64: 8192 + 2 * 8583 words = 101 432 B (one static block, as the fused kernels of attn.hip hold theirs); at MAXD = 32: 13 088 B.
+// Every global store is bounded by the capacities; every LDS word index by the word counts of the template's MAXD.
+constexpr int SURF_NT = 1024;
+
+template <int MAXD>
+struct SurfLds {
+  static constexpr int OCC_W = MAXD * MAXD * MAXD / 32;
+  static constexpr int LAT_W = ((MAXD + 1) * (MAXD + 1) * (MAXD + 1) + 31) / 32;
+};
+
+// exclusive sum-scan over the workgroup in thread order; `total` receives the workgroup's sum.  wsum is [SURF_NT / 64] in LDS.
+__device__ __forceinline__ int surf_scan(int v, int* wsum, int& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += u;
+  }
+  __syncthreads();                               // the previous scan's wsum has been read
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  int excl = inc - v, t = 0;
+  for (int i = 0; i < SURF_NT / 64; ++i) {
+    const int s = wsum[i];
+    if (i < w) excl += s;
+    t += s;
+  }
+  total = t;
+  return excl;
+}
+
+template <int MAXD>
+__global__ void __launch_bounds__(SURF_NT) voxel_surface_kernel(const void* __restrict__ vol, int dtype, int d0, int d1, int d2, float th,
+                                                                unsigned int* __restrict__ verts, long long vcap, unsigned int* __restrict__ faces,
+                                                                long long fcap, int* __restrict__ counts) {
+  constexpr int OCC_W = SurfLds<MAXD>::OCC_W, LAT_W = SurfLds<MAXD>::LAT_W;
+  __shared__ __attribute__((aligned(16))) unsigned int surf_smem[OCC_W + 2 * LAT_W];
+  __shared__ int wsum[SURF_NT / 64];
+  unsigned int* occ = surf_smem;                 // [OCC_W]
+  unsigned int* used = occ + OCC_W;              // [LAT_W]
+  unsigned int* pre = used + LAT_W;              // [LAT_W]
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int total = d0 * d1 * d2, slab = d1 * d2;
+  const int e1 = d1 + 1, e2 = d2 + 1, lslab = e1 * e2, ltotal = (d0 + 1) * lslab, lwords = (ltotal + 31) >> 5;
+  const size_t vbase = (size_t)b * total;
+  unsigned int* vo = verts + (size_t)b * (size_t)vcap;
+  uint4* fo = reinterpret_cast<uint4*>(faces) + (size_t)b * (size_t)fcap;
+  auto filled = [&](int p) -> bool { return (occ[p >> 5] >> (p & 31)) & 1u; };
+  // corners of the six directions, counter-clockwise seen from outside; a corner is (dx << 2) | (dy << 1) | dz
+  constexpr int CORNER[6][4] = {{0, 1, 3, 2}, {4, 6, 7, 5}, {0, 4, 5, 1}, {2, 3, 7, 6}, {0, 2, 6, 4}, {1, 5, 7, 3}};
+
+  // (a) occupancy mask; the trip count is wave-uniform, so every lane takes part in the ballot
+  for (int q = 0; q < total; q += SURF_NT) {
+    const int p = q + tid;
+    const unsigned long long m = __ballot(p < total && voxel_set(vol, dtype, vbase + p, th));
+    const int wi = (q >> 5) + 2 * w;
+    if (lane == 0 && wi + 1 < OCC_W) {           // always true for total <= MAXD^3 (a multiple of SURF_NT); the LDS bound all the same
+      occ[wi] = (unsigned int)m;
+      occ[wi + 1] = (unsigned int)(m >> 32);
+    }
+  }
+  __syncthreads();
+
+  // (b) used mask from the 8-cell rule
+  for (int q = 0; q < ltotal; q += SURF_NT) {
+    const int l = q + tid;
+    bool u = false;
+    if (l < ltotal) {
+      const int i = l / lslab, r = l - i * lslab, j = r / e2, k = r - j * e2;
+      int n = 0;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int x = i - 1 + (c >> 2), y = j - 1 + ((c >> 1) & 1), z = k - 1 + (c & 1);
+        if (x >= 0 && x < d0 && y >= 0 && y < d1 && z >= 0 && z < d2) n += filled(x * slab + y * d2 + z) ? 1 : 0;
+      }
+      u = n > 0 && n < 8;
+    }
+    const unsigned long long m = __ballot(u);
+    const int wi = (q >> 5) + 2 * w;
+    if (lane == 0) {
+      if (wi < lwords) used[wi] = (unsigned int)m;
+      if (wi + 1 < lwords) used[wi + 1] = (unsigned int)(m >> 32);
+    }
+  }
+  __syncthreads();
+  int n_verts;
+  {
+    const int per = (lwords + SURF_NT - 1) / SURF_NT, w0 = min(tid * per, lwords), w1 = min(w0 + per, lwords);
+    int s = 0;
+    for (int i = w0; i < w1; ++i) s += __popc(used[i]);
+    int run = surf_scan(s, wsum, n_verts);
+    for (int i = w0; i < w1; ++i) {
+      pre[i] = (unsigned int)run;
+      run += __popc(used[i]);
+    }
+  }
+  __syncthreads();
+  auto vid = [&](int l) -> unsigned int { return pre[l >> 5] + __popc(used[l >> 5] & ((1u << (l & 31)) - 1u)); };
+
+  // (c) vertex list
+  for (int l = tid; l < ltotal; l += SURF_NT) {
+    if ((used[l >> 5] >> (l & 31)) & 1u) {
+      const unsigned int id = vid(l);
+      if ((long long)id < vcap) vo[id] = (unsigned int)l;
+    }
+  }
+
+  // (d) faces
+  const int per = (total + SURF_NT - 1) / SURF_NT, p0 = min(tid * per, total), p1 = min(p0 + per, total);
+  auto exposure = [&](int p, int x, int y, int z) -> unsigned int {
+    if (!filled(p)) return 0u;
+    unsigned int e = 0u;
+    if (x == 0 || !filled(p - slab)) e |= 1u;
+    if (x == d0 - 1 || !filled(p + slab)) e |= 2u;
+    if (y == 0 || !filled(p - d2)) e |= 4u;
+    if (y == d1 - 1 || !filled(p + d2)) e |= 8u;
+    if (z == 0 || !filled(p - 1)) e |= 16u;
+    if (z == d2 - 1 || !filled(p + 1)) e |= 32u;
+    return e;
+  };
+  const int x0 = p0 / slab, r0 = p0 - x0 * slab, y0 = r0 / d2, z0 = r0 - y0 * d2;
+  int nf = 0;
+  for (int p = p0, x = x0, y = y0, z = z0; p < p1; ++p) {
+    nf += __popc(exposure(p, x, y, z));
+    if (++z == d2) { z = 0; if (++y == d1) { y = 0; ++x; } }
+  }
+  int n_faces;
+  long long slot = surf_scan(nf, wsum, n_faces);
+  for (int p = p0, x = x0, y = y0, z = z0; p < p1; ++p) {
+    const unsigned int e = exposure(p, x, y, z);
+    if (e) {
+      const int l = (x * e1 + y) * e2 + z;
+      unsigned int c[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) c[q] = vid(l + (q >> 2) * lslab + ((q >> 1) & 1) * e2 + (q & 1));
+#pragma unroll
+      for (int d = 0; d < 6; ++d)
+        if ((e >> d) & 1u) {
+          if (slot < fcap) fo[slot] = make_uint4(c[CORNER[d][0]], c[CORNER[d][1]], c[CORNER[d][2]], c[CORNER[d][3]]);
+          ++slot;
+        }
+    }
+    if (++z == d2) { z = 0; if (++y == d1) { y = 0; ++x; } }
+  }
+  if (tid == 0) {
+    counts[2 * b] = n_verts;
+    counts[2 * b + 1] = n_faces;
   }
 }
 
@@ -397,6 +559,27 @@ extern "C" int sv_binvox_encode(const void* vol, int dtype, int B, int d0, int d
              (long long)d0 * d1 * d2);
   hipLaunchKernelGGL(binvox_encode_kernel, dim3(B), dim3(256), 0, STREAM, vol, dtype, d0, d1, d2, fix_coords, threshold, pairs, pair_capacity, n_pairs);
   return check_launch("sv_binvox_encode");
+}
+
+extern "C" int sv_voxel_surface(const void* vol, int dtype, int B, int d0, int d1, int d2, float threshold, unsigned int* verts, long long vert_capacity,
+                                unsigned int* faces, long long face_capacity, int* counts, void* stream) {
+  SV_REQUIRE(vol && verts && faces && counts && B > 0, "sv_voxel_surface: bad arguments");
+  SV_REQUIRE(d0 >= 1 && d0 <= 64 && d1 >= 1 && d1 <= 64 && d2 >= 1 && d2 <= 64, "sv_voxel_surface: dims %d x %d x %d, every dim must lie in 1 .. 64", d0,
+             d1, d2);
+  SV_REQUIRE(dtype == 0 || dtype == 1, "sv_voxel_surface: dtype %d is neither 0 (float32) nor 1 (uint8)", dtype);
+  SV_REQUIRE(threshold < 0.f || (threshold > 0.f && threshold < 1.f), "sv_voxel_surface: threshold must be negative (occupancy input) or in (0, 1)");
+  SV_REQUIRE(threshold < 0.f || dtype == 0, "sv_voxel_surface: a sigmoid threshold needs float32 logits");
+  const long long vmax = (long long)(d0 + 1) * (d1 + 1) * (d2 + 1), fmax = 3ll * d0 * d1 * d2 + (long long)d0 * d1 + (long long)d1 * d2 + (long long)d0 * d2;
+  SV_REQUIRE(vert_capacity >= vmax, "sv_voxel_surface: vert_capacity %lld is below the %lld lattice points of a volume", vert_capacity, vmax);
+  SV_REQUIRE(face_capacity >= fmax, "sv_voxel_surface: face_capacity %lld is below the %lld lattice faces of a volume", face_capacity, fmax);
+  SV_REQUIRE((reinterpret_cast<uintptr_t>(faces) & 15) == 0, "sv_voxel_surface: faces must be 16-byte aligned");
+  if (d0 <= 32 && d1 <= 32 && d2 <= 32)
+    hipLaunchKernelGGL(voxel_surface_kernel<32>, dim3(B), dim3(SURF_NT), 0, STREAM, vol, dtype, d0, d1, d2, threshold, verts, vert_capacity, faces,
+                       face_capacity, counts);
+  else
+    hipLaunchKernelGGL(voxel_surface_kernel<64>, dim3(B), dim3(SURF_NT), 0, STREAM, vol, dtype, d0, d1, d2, threshold, verts, vert_capacity, faces,
+                       face_capacity, counts);
+  return check_launch("sv_voxel_surface");
 }
 
 extern "C" int sv_augment_views(const unsigned char* src, int I, int V, int Hs, int Ws, int C, int crop_h, int crop_w, int out_h, int out_w,

@@ -83,12 +83,12 @@ def binvox_header(dims, translate=(0.0, 0.0, 0.0), scale=1.0) -> bytes:
             % (" ".join(map(str, dims)), " ".join(map(str, translate)), str(scale))).encode("latin-1")
 
 
-def _per_volume(value, B: int, is_single, what: str) -> list:
+def _per_volume(value, B: int, is_single, what: str, who: str = "encode_binvox_batch") -> list:
     if is_single(value):
         return [value] * B
     value = list(value)
     if len(value) != B:
-        raise ValueError(f"encode_binvox_batch: {what} must be one value or one per volume ({B}), got {len(value)}")
+        raise ValueError(f"{who}: {what} must be one value or one per volume ({B}), got {len(value)}")
     return value
 
 
@@ -123,6 +123,101 @@ def encode_binvox_batch(volumes: torch.Tensor, threshold: Optional[float] = None
     counts = n_pairs.tolist()
     payload = pairs[:, :max(counts)].cpu().numpy()
     return [binvox_header((d0, d1, d2), trs[i], scs[i]) + payload[i, :counts[i]].tobytes() for i in range(B)]
+
+
+# ---- exposed voxel faces ---------------------------------------------------------------------------------------------------
+SURFACE_MAX_DIM = 64                                                       # sv_voxel_surface keeps a volume's bit masks in LDS
+
+
+def extract_surface_batch(volumes: torch.Tensor, threshold: Optional[float] = None) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """[B, a, b, c] on the GPU -> per volume (verts int32 [n, 3], faces int32 [m, 4]) on the host: the quads that separate a set
+    voxel from an unset one or from the outside, the face set utils/helpers.py:50-88 hands to Axes3D.voxels (core/test.py:178-187).
+    Axes are the array's own (no fix_coords transposition); vertices are lattice points (i, j, k) in ascending lattice order, faces
+    follow ascending voxel index and then the directions -x +x -y +y -z +z, corners counter-clockwise seen from outside (see
+    sv_voxel_surface in the header).  float32 / uint8 / bool volumes are occupancy (set iff != 0); with `threshold` in (0, 1) the
+    volumes are float32 logits and a voxel is set iff sigmoid(x) >= threshold, the predicate of voxel_metrics and
+    encode_binvox_batch.  One kernel launch and two device-to-host copies whatever B is: the counts, then both payloads trimmed
+    to the longest in the batch."""
+    hip.check_cuda(volumes)
+    if volumes.dim() != 4 or volumes.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise RuntimeError("extract_surface_batch expects float32, uint8 or bool [B, a, b, c]")
+    if threshold is not None and (not 0.0 < float(threshold) < 1.0 or volumes.dtype != torch.float32):
+        raise ValueError("extract_surface_batch: threshold must lie in (0, 1) and needs float32 logits")
+    B, d0, d1, d2 = volumes.shape
+    if B == 0:
+        raise ValueError("extract_surface_batch: no volumes")
+    if min(d0, d1, d2) < 1 or max(d0, d1, d2) > SURFACE_MAX_DIM:
+        raise ValueError(f"extract_surface_batch: dims {(d0, d1, d2)}, every dim must lie in 1 .. {SURFACE_MAX_DIM}")
+    vol = volumes.contiguous()
+    if vol.dtype == torch.bool:
+        vol = vol.view(torch.uint8)
+    vcap = (d0 + 1) * (d1 + 1) * (d2 + 1)
+    fcap = 3 * d0 * d1 * d2 + d0 * d1 + d1 * d2 + d0 * d2
+    verts = torch.empty(B, vcap, dtype=torch.int32, device=vol.device)
+    faces = torch.empty(B, fcap, 4, dtype=torch.int32, device=vol.device)
+    counts = torch.empty(B, 2, dtype=torch.int32, device=vol.device)
+    call("sv_voxel_surface", ptr(vol), 0 if vol.dtype == torch.float32 else 1, B, d0, d1, d2,
+         -1.0 if threshold is None else float(threshold), ptr(verts), vcap, ptr(faces), fcap, ptr(counts))
+    cnt = counts.tolist()
+    nv, nf = max(c[0] for c in cnt), max(c[1] for c in cnt)
+    both = torch.cat([verts[:, :nv], faces[:, :nf].reshape(B, 4 * nf)], dim=1).cpu().numpy()
+    out = []
+    for i, (n, m) in enumerate(cnt):
+        lat = both[i, :n]
+        ijk = np.stack([lat // ((d1 + 1) * (d2 + 1)), lat // (d2 + 1) % (d1 + 1), lat % (d2 + 1)], axis=1).astype(np.int32)
+        out.append((ijk, both[i, nv:nv + 4 * m].reshape(m, 4).copy()))
+    return out
+
+
+_PLY_HEADER = ("ply\nformat binary_little_endian 1.0\ncomment swinvox_amd exposed voxel faces\nelement vertex %d\n"
+               "property float x\nproperty float y\nproperty float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n")
+
+
+def mesh_file(verts, faces, fmt: str = "ply", dims=None, translate=(0.0, 0.0, 0.0), scale=None) -> bytes:
+    """A quad mesh (verts [n, 3] lattice points, faces [m, 4] indices into them) as the contents of a .ply (binary little endian),
+    .off or .obj file; pure host code.  Coordinates are lattice units when `scale` is None, otherwise
+    translate + scale * idx / max(dims) in float64 - the binvox header convention: voxel corner idx of a model normalised to its
+    largest dimension.  An empty mesh is a valid file in every format."""
+    verts = np.asarray(verts).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 4).astype(np.int64)
+    n, m = len(verts), len(faces)
+    if m and (faces.min() < 0 or faces.max() >= n):
+        raise ValueError("mesh_file: a face index lies outside the vertex list")
+    if scale is None:
+        if any(float(t) != 0.0 for t in translate):
+            raise ValueError("mesh_file: translate needs a scale (coordinates are lattice units without one)")
+        xyz = verts.astype(np.float64)
+    else:
+        if dims is None:
+            raise ValueError("mesh_file: scale needs the volume's dims")
+        xyz = np.asarray(translate, np.float64)[None, :] + float(scale) * verts.astype(np.float64) / float(max(dims))
+    if fmt == "ply":
+        rec = np.empty(m, dtype=np.dtype([("n", "u1"), ("v", "<i4", (4,))]))
+        rec["n"], rec["v"] = 4, faces
+        return (_PLY_HEADER % (n, m)).encode("ascii") + xyz.astype("<f4").tobytes() + rec.tobytes()
+    if fmt == "off":
+        lines = ["OFF", "%d %d 0" % (n, m)]
+        lines += ["%.9g %.9g %.9g" % tuple(p) for p in xyz.tolist()]
+        lines += ["4 %d %d %d %d" % tuple(f) for f in faces.tolist()]
+    elif fmt == "obj":
+        lines = ["v %.9g %.9g %.9g" % tuple(p) for p in xyz.tolist()]
+        lines += ["f %d %d %d %d" % tuple(f) for f in (faces + 1).tolist()]
+    else:
+        raise ValueError(f"mesh_file: format {fmt!r} is none of 'ply', 'off', 'obj'")
+    return ("\n".join(lines) + "\n").encode("ascii") if lines else b""
+
+
+def encode_mesh_batch(volumes: torch.Tensor, threshold: Optional[float] = None, fmt: str = "ply", translate=(0.0, 0.0, 0.0),
+                      scale=None) -> List[bytes]:
+    """[B, a, b, c] on the GPU -> B mesh files (extract_surface_batch + mesh_file with dims = (a, b, c)).  translate (three
+    numbers) and scale (a number or None) may also be given per volume."""
+    if fmt not in ("ply", "off", "obj"):
+        raise ValueError(f"encode_mesh_batch: format {fmt!r} is none of 'ply', 'off', 'obj'")
+    meshes = extract_surface_batch(volumes, threshold)
+    B, dims = len(meshes), tuple(volumes.shape[1:])
+    trs = _per_volume(translate, B, lambda t: not hasattr(t[0], "__len__"), "translate", "encode_mesh_batch")
+    scs = _per_volume(scale, B, lambda s: not hasattr(s, "__len__"), "scale", "encode_mesh_batch")
+    return [mesh_file(v, f, fmt, dims, trs[i], scs[i]) for i, (v, f) in enumerate(meshes)]
 
 
 # ---- augmentation -----------------------------------------------------------------------------------------------------------

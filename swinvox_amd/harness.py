@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import hip
-from .data import encode_binvox_batch
+from .data import encode_binvox_batch, encode_mesh_batch
 from .hip import call, ptr
 from .losses import bce_with_logits as _bce      # torch.nn.BCEWithLogitsLoss() of core/train.py:165 on sv_bce_logits
 from .optim import FlatAdam, FlatSGD, _FlatSolver
@@ -143,11 +143,14 @@ def evaluate(nets, cfg, images, gt, epoch_idx: int = 0, with_fscore: bool = Fals
 
 
 @torch.no_grad()
-def reconstruct(nets, cfg, images, epoch_idx: int = 0, binvox_threshold: Optional[float] = None):
+def reconstruct(nets, cfg, images, epoch_idx: int = 0, binvox_threshold: Optional[float] = None, mesh_threshold: Optional[float] = None,
+                mesh_format: str = "ply"):
     """The forward of core/test.py:120-130 without ground truth: the [B, 32, 32, 32] logits of the last active module, with the
     merger / refiner gating of forward_losses and the nets in eval() for the pass, as in evaluate.  With binvox_threshold the
     result is (volume, files): files[b] is the binvox file of sigmoid(volume[b]) >= binvox_threshold, the occupancy
-    voxel_metrics scores at that threshold (data.encode_binvox_batch)."""
+    voxel_metrics scores at that threshold (data.encode_binvox_batch).  With mesh_threshold the result gains a trailing list of
+    mesh files, (volume, meshes) or (volume, files, meshes): meshes[b] is the exposed voxel faces of sigmoid(volume[b]) >=
+    mesh_threshold in mesh_format ("ply", "off" or "obj"), the face set core/test.py:178-187 draws (data.encode_mesh_batch)."""
     enc, dec, mer, ref = nets
     was_training = [n.training for n in nets]
     for n in nets:
@@ -163,9 +166,12 @@ def reconstruct(nets, cfg, images, epoch_idx: int = 0, binvox_threshold: Optiona
     finally:
         for n, t in zip(nets, was_training):
             n.train(t)
-    if binvox_threshold is None:
-        return volume
-    return volume, encode_binvox_batch(volume, threshold=binvox_threshold)
+    out = (volume,)
+    if binvox_threshold is not None:
+        out += (encode_binvox_batch(volume, threshold=binvox_threshold),)
+    if mesh_threshold is not None:
+        out += (encode_mesh_batch(volume, threshold=mesh_threshold, fmt=mesh_format),)
+    return out if len(out) > 1 else volume
 
 
 def aggregate_by_taxonomy(taxonomy_ids: Sequence, per_sample):

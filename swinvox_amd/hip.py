@@ -240,6 +240,7 @@ _PROTOS = {
     "sv_iou_counts": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "sv_binvox_decode": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "sv_binvox_encode": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _L, _P]),
+    "sv_voxel_surface": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _L, _P, _L, _P]),
     "sv_augment_views": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "sv_augment_images": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "sv_grad_sumsq": (_I, [_P, _L, _F, _P]),
