@@ -793,6 +793,39 @@ int sv_augment_images(const unsigned char* src, long long src_bytes, int I, int 
                       sv_aug_image* images_dev_ws, int out_h, int out_w, const sv_aug_sample* params_dev,
                       const unsigned char* flip_dev, double* grey_sum_ws, float* out, void* stream);
 
+/* sv_render_volumes: pictures of B volumes of equal dims from n_cams viewpoints - what utils/helpers.py:50-88 (get_volume_views ->
+ *    Axes3D.voxels(edgecolor="k") at elev 30 / azim 45, called from core/test.py:178-187) and utils/binvox_rw.py:306-343 draw, as a
+ *    ray-cast.  `vol` is [B][d0][d1][d2] in its own axis order (no fix_coords transposition), every dim in 1 .. 64; dtype and
+ *    threshold as for sv_voxel_surface (0 = float32, 1 = uint8; threshold < 0: occupancy, set iff != 0; 0 < threshold < 1: float32
+ *    logits, set iff 1.f / (1.f + expf(-x)) >= threshold), the same predicate, so picture, mesh, .binvox file and IoU agree voxel for
+ *    voxel.  Voxel (i, j, k) fills [i, i+1] x [j, j+1] x [k, k+1].
+ *    Camera: one ray per pixel, affine in the pixel centre; row 0 is the top of the image:
+ *      origin = o0 + (col+0.5) ox + (row+0.5) oy        dir = d0 + (col+0.5) dx + (row+0.5) dy
+ *    (perspective: ox = oy = 0, o0 is the eye; orthographic: dx = dy = 0).  data.view_camera gives the reference's camera.
+ *    Ray-cast, every step one fp32 operation (no fma contraction, IEEE division), per axis a with extent D:
+ *      1. slab: dir != 0: t0 = (0 - origin) / dir, t1 = (D - origin) / dir, tnear = min, tfar = max; dir == 0: tnear = -inf and
+ *         tfar = +inf when 0 <= origin < D, else a miss.
+ *      2. tin = max tnear, tout = min tfar; hit iff tin < tout and tin > 0.  Entry axis = first arg-max of tnear (x before y before z).
+ *      3. entry cell = clamp(floor(origin + dir * tin), 0, D - 1); along the entry axis 0 when dir > 0, else D - 1.
+ *      4. Amanatides-Woo: tmax = ((cell + (dir > 0)) - origin) / dir, tdelta = |1 / dir| (both +inf for dir == 0); while the cell is
+ *         unset, advance the axis with the smallest tmax (first arg-min): cell += sign(dir), tmax += tdelta; leaving the grid is a miss.
+ *    ids[b][cam][row][col] = ((i*d1 + j)*d2 + k)*6 + face of the first set voxel on the ray, face = the one the ray entered it
+ *    through, numbered -x, +x, -y, +y, -z, +z (the order of sv_voxel_surface); -1 = background.
+ *    Shading (skipped when rgb is NULL), an integer rule on the ids: a pixel is an edge pixel iff its id differs from the id of its
+ *    right or of its lower neighbour (the pixel itself at the last column / row); edge pixels take edge_rgb, other hit pixels
+ *    face_rgb[3*face ..], other pixels plate_dev[ch][row][col] when plate_dev is given, else background_rgb.
+ *    rgb is [B][n_cams][3][H][W].  face_rgb (18), edge_rgb (3), background_rgb (3) and cams_host are host memory; cams_host is
+ *    validated BEFORE anything is launched and then copied to cams_dev_ws (n_cams cameras of device scratch) on the stream.
+ *    mask_ws: B*d0*d1 words of device scratch for d2 <= 32, twice that above (bit k of a row's word(s) = voxel (i, j, k)).
+ *    Refused with an error code, before any launch: null pointers (plate_dev and rgb may be NULL), dims outside 1 .. 64, B or n_cams
+ *    outside 1 .. 65535, H or W < 1, H*W > 2^24, a camera number that is not finite, a threshold outside the two ranges, a
+ *    perspective eye inside or on the box [0, d0] x [0, d1] x [0, d2].  At most three launches, no atomics: deterministic.         */
+typedef struct sv_view_camera { float o0[3], ox[3], oy[3], d0[3], dx[3], dy[3]; } sv_view_camera;
+int sv_render_volumes(const void* vol, int dtype, int B, int d0, int d1, int d2, float threshold,
+                      const sv_view_camera* cams_host, int n_cams, sv_view_camera* cams_dev_ws, int H, int W,
+                      const unsigned char* face_rgb, const unsigned char* edge_rgb, const unsigned char* background_rgb,
+                      const unsigned char* plate_dev, unsigned int* mask_ws, int* ids, unsigned char* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """Device-side input preparation for one training batch (B x V renderings + B volumes) next to the CPU restatement of the
 reference's per-sample numpy path.  python scripts/bench_data.py [--batch 32]"""
 import argparse
+import ctypes
 import os
 import random
 import sys
@@ -90,6 +91,32 @@ t0 = time.perf_counter()
 host_meshes = [host_face_loop(v) for v in vols]
 t_mesh_cpu = (time.perf_counter() - t0) * 1e3
 assert host_meshes == D.encode_mesh_batch(vol_dev)
+# the picture of each of the same 32 volumes at the reference's 640 x 480 from its camera (sv_render_volumes) next to the numpy
+# restatement of the same rule on the host (tests/volume_view_ref.py: ray-cast + shading); matplotlib, which the reference calls, takes
+# seconds per volume
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import volume_view_ref as VR  # noqa: E402
+
+t_view = timed(lambda: D.render_views_batch(vol_dev), n=50)
+view_cam = D.view_camera((32, 32, 32))
+cam_arr = (S.hip.ViewCamera * 1).from_buffer_copy(view_cam.astype(np.float32).tobytes())
+colours = [(ctypes.c_ubyte * len(v))(*v) for v in ([c for rgb in D.VIEW_FACE_RGB for c in rgb], (0, 0, 0), (255, 255, 255))]
+cam_ws = torch.empty(72, dtype=torch.uint8, device=dev)
+mask_ws = torch.empty(a.batch * 1024, dtype=torch.int32, device=dev)
+view_ids = torch.empty(a.batch, 1, 480, 640, dtype=torch.int32, device=dev)
+view_rgb = torch.empty(a.batch, 1, 3, 480, 640, dtype=torch.uint8, device=dev)
+view_launch = lambda: call("sv_render_volumes", ptr(vol_u8), 1, a.batch, 32, 32, 32, -1.0, ctypes.addressof(cam_arr), 1, ptr(cam_ws), 480, 640,  # noqa: E731
+                           *(ctypes.addressof(c) for c in colours), None, ptr(mask_ws), ptr(view_ids), ptr(view_rgb))
+view_launch(); torch.cuda.synchronize()
+ev0.record()
+for _ in range(50):
+    view_launch()
+ev1.record(); torch.cuda.synchronize()
+t_view_kernel = ev0.elapsed_time(ev1) / 50
+t0 = time.perf_counter()
+host_views = np.stack([VR.shade(VR.render_ids(v, view_cam, (480, 640)), D.VIEW_FACE_RGB) for v in vols])
+t_view_cpu = (time.perf_counter() - t0) * 1e3
+view_diff = int((host_views != D.render_views_batch(vol_dev)[:, 0].cpu().numpy()).any(axis=1).sum())
 # photographs with bounding boxes (the Pascal3D / Pix3D branch): 32 images of 640 x 480 x 3, each cropped to its jittered box
 photos = [rng.integers(0, 256, size=(480, 640, 3), dtype=np.uint8) for _ in range(32)]
 boxes = [(0.1 + 0.2 * rng.random(), 0.1 + 0.2 * rng.random(), 0.7 + 0.35 * rng.random(), 0.7 + 0.35 * rng.random()) for _ in photos]
@@ -113,4 +140,7 @@ print(f"binvox encode   {t_enc:7.3f} ms / {a.batch} volumes (pair counts + trimm
 print(f"voxel surface   {t_mesh:7.3f} ms / {a.batch} volumes as PLY files (counts + trimmed payload D2H, lattice decode and PLY formatting included; "
       f"{t_surf:7.3f} ms without the formatting, {t_surf_kernel:6.3f} ms the kernel alone by device events; {sum(len(m) for m in host_meshes) / 1e6:.2f} MB of files); per-voxel numpy face loop + the same formatting on "
       f"the host, one core: {t_mesh_cpu:7.1f} ms")
+print(f"volume views    {t_view:7.3f} ms / {a.batch} volumes as {a.batch} pictures of 640x480 on the device (allocation of the outputs and the camera copy "
+      f"included; {t_view_kernel:6.3f} ms the three launches alone by device events); numpy restatement of the same ray-cast and shading on the host, "
+      f"one core: {t_view_cpu:7.1f} ms; pixels that differ between the two: {view_diff}")
 print(f"numpy restatement of the reference path, one core: {t_cpu:8.1f} ms / batch ({n / t_cpu * 1e3:7.0f} views/s)")

@@ -278,4 +278,14 @@ __device__ __forceinline__ float uniform01(uint32_t seed, uint64_t idx) {
   return (hash_u32(seed, (uint32_t)idx, (uint32_t)(idx >> 32)) >> 8) * (1.0f / 16777216.0f);
 }
 
+// occupancy of one input element of the voxel exports (dataprep.hip: binvox writer, exposed faces; render.hip: views); with 0 < th < 1 the
+// same expression as iou_counts_kernel (elementwise.hip), so that an exported file, a picture and the reported IoU agree voxel for voxel
+__device__ __forceinline__ bool voxel_set(const void* __restrict__ vol, int dtype, size_t idx, float th) {
+  if (dtype == 1) return static_cast<const unsigned char*>(vol)[idx] != 0;
+  const float xv = static_cast<const float*>(vol)[idx];
+  if (th < 0.f) return xv != 0.f;
+  const float pr = 1.f / (1.f + expf(-xv));
+  return pr >= th;
+}
+
 }  // namespace sv

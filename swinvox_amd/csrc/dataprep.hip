@@ -73,16 +73,6 @@ __global__ void __launch_bounds__(256) binvox_decode_kernel(const unsigned char*
 // emits more pairs than it has voxels; every store is bounded by `cap` regardless.
 constexpr int ENC_CHUNK = 1024;
 
-// occupancy of one input element; with 0 < th < 1 the same expression as iou_counts_kernel (elementwise.hip), so that an exported
-// file and the reported IoU agree voxel for voxel
-__device__ __forceinline__ bool voxel_set(const void* __restrict__ vol, int dtype, size_t idx, float th) {
-  if (dtype == 1) return static_cast<const unsigned char*>(vol)[idx] != 0;
-  const float xv = static_cast<const float*>(vol)[idx];
-  if (th < 0.f) return xv != 0.f;
-  const float pr = 1.f / (1.f + expf(-xv));
-  return pr >= th;
-}
-
 __global__ void __launch_bounds__(256) binvox_encode_kernel(const void* __restrict__ vol, int dtype, int d0, int d1, int d2, int fix_coords, float th,
                                                             unsigned char* __restrict__ pairs, long long cap, int* __restrict__ n_pairs) {
   __shared__ unsigned int bits[ENC_CHUNK / 32];

@@ -12,6 +12,8 @@ from __future__ import annotations
 
 import ctypes as C
 import random
+import struct
+import zlib
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
@@ -218,6 +220,141 @@ def encode_mesh_batch(volumes: torch.Tensor, threshold: Optional[float] = None, 
     trs = _per_volume(translate, B, lambda t: not hasattr(t[0], "__len__"), "translate", "encode_mesh_batch")
     scs = _per_volume(scale, B, lambda s: not hasattr(s, "__len__"), "scale", "encode_mesh_batch")
     return [mesh_file(v, f, fmt, dims, trs[i], scs[i]) for i, (v, f) in enumerate(meshes)]
+
+
+# ---- volume views -----------------------------------------------------------------------------------------------------------
+# the colours matplotlib shades the faces of Axes3D.voxels with (default light source, default face colour), in the face order
+# -x +x -y +y -z +z, as 8-bit RGB; from the camera of get_volume_views +x, +y and +z are the visible ones
+VIEW_FACE_RGB = ((27, 105, 159), (13, 50, 75), (27, 105, 159), (13, 50, 75), (17, 63, 96), (24, 91, 138))
+
+
+def view_camera(dims, elev: float = 30, azim: float = 45, size=(480, 640), proj_type: str = "persp") -> np.ndarray:
+    """The camera of the reference's get_volume_views (utils/helpers.py:50-88) for a volume of these dims, as the 18 numbers of
+    sv_view_camera, float64 [6, 3] = o0, ox, oy, d0, dx, dy: the ray of pixel (row, col) starts at o0 + (col+0.5) ox + (row+0.5) oy
+    and runs along d0 + (col+0.5) dx + (row+0.5) dy in the array's own coordinates, row 0 at the top.  It is what matplotlib's Axes3D
+    arrives at in subplot(111) of a figure of size = (H, W) pixels (the default 6.4 x 4.8 in at 100 dpi for (480, 640)) with
+    set_box_aspect([1, 1, 1]), limits 0 .. dims, view_init(elev, azim), focal length 1 and distance 10; other sizes scale that figure.
+    proj_type "ortho" is the orthographic projection utils/binvox_rw.py:306-343 asks for (rays parallel, dx = dy = 0)."""
+    if proj_type not in ("persp", "ortho"):
+        raise ValueError(f"view_camera: proj_type {proj_type!r} is neither 'persp' nor 'ortho'")
+    H, W = int(size[0]), int(size[1])
+    d = np.asarray(dims, np.float64)
+    if d.shape != (3,) or (d < 1).any() or H < 1 or W < 1:
+        raise ValueError("view_camera: dims are three positive numbers, size is (H, W)")
+    dist = 10.0                                                              # Axes3D._dist; the focal length is 1
+    aspect = np.ones(3)
+    aspect *= 1.8294640721620434 * 25 / 24 * 1 / np.linalg.norm(aspect)       # axes3d.py set_box_aspect
+    scale = aspect / d                                                       # proj3d.world_transformation for limits 0 .. dims
+    centre = 0.5 * aspect
+    er, ar = np.deg2rad(elev), np.deg2rad(azim)
+    eye = centre + dist * np.array([np.cos(er) * np.cos(ar), np.cos(er) * np.sin(ar), np.sin(er)])   # get_proj
+    flipped = abs(np.deg2rad((elev + 180.0) % 360.0 - 180.0)) > np.pi / 2     # _calc_view_axes: the vertical axis turns over
+    w = (eye - centre) / np.linalg.norm(eye - centre)                        # proj3d._view_axes: out of the screen, right, up
+    u = np.cross(np.array([0.0, 0.0, -1.0 if flipped else 1.0]), w)
+    u = u / np.linalg.norm(u)
+    v = np.cross(w, u)
+    # the axes rectangle: subplot(111) spans 0.125 .. 0.9 by 0.11 .. 0.88 of the figure and apply_aspect shrinks it to a square about
+    # its centre; set_top_view maps the view interval (-0.95 / dist, 0.9 / dist) onto it.  Display y runs upwards.
+    side = min(0.775 * W, 0.77 * H)
+    left, bottom = 0.125 * W + 0.5 * (0.775 * W - side), 0.11 * H + 0.5 * (0.77 * H - side)
+    lo, span = -0.95 / dist, (0.9 + 0.95) / dist
+    xa, xb = lo - left * span / side, span / side                            # view x = xa + xb (col + 0.5)
+    ya, yb = lo + (H - bottom) * span / side, -span / side                   # view y = ya + yb (row + 0.5)
+    cam = np.zeros((6, 3))
+    if proj_type == "persp":                                                 # _persp_transformation: view x = e.x / -e.z
+        cam[0], cam[3], cam[4], cam[5] = eye / scale, (xa * u + ya * v - w) / scale, xb * u / scale, yb * v / scale
+    else:                                                                    # _ortho_transformation: view x = e.x / dist
+        cam[0], cam[1], cam[2], cam[3] = (eye + dist * (xa * u + ya * v)) / scale, dist * xb * u / scale, dist * yb * v / scale, -w / scale
+    return cam
+
+
+def _rgb_bytes(value, n: int, what: str):
+    arr = np.asarray(value)
+    if arr.size != n or arr.dtype.kind not in "iu" or arr.min() < 0 or arr.max() > 255:
+        raise ValueError(f"render_views_batch: {what} holds {n} integers in 0 .. 255")
+    return (C.c_ubyte * n)(*[int(x) for x in arr.reshape(-1)])
+
+
+def render_views_batch(volumes: torch.Tensor, threshold: Optional[float] = None, cameras=None, size=(480, 640), face_colors=None,
+                       edge_color=(0, 0, 0), background=(255, 255, 255), return_ids: bool = False):
+    """[B, a, b, c] on the GPU -> uint8 [B, n_cams, 3, H, W] on the GPU: the pictures the reference's evaluation loop draws of its
+    reconstructions (utils/helpers.py:50-88 from core/test.py:178-187), for every volume of the batch and every camera, in the layout
+    SummaryWriter.add_image takes.  With return_ids also the int32 [B, n_cams, H, W] id buffer (voxel index * 6 + face, -1 background).
+    The rule - ray-cast, ids, edge pixels - is written out at sv_render_volumes in the header.  Axes are the array's own, as for
+    extract_surface_batch, and so are the dtype and threshold rules: float32 / uint8 / bool volumes are occupancy (set iff != 0); with
+    `threshold` in (0, 1) the volumes are float32 logits and a voxel is set iff sigmoid(x) >= threshold.
+    cameras: None = the reference's single view, view_camera(dims, size=size); or a sequence of cameras ([6, 3] or 18 numbers each, a
+    turntable for instance).  face_colors: six RGB triples for -x +x -y +y -z +z, None = VIEW_FACE_RGB, one table for all cameras.
+    background: a colour, or a uint8 [3, H, W] tensor on the GPU (a plate with panes and ticks, say).  Left out: axis panes, grid, ticks
+    and labels, anti-aliasing (edge lines are one pixel wide), translucent faces.  One call of the entry, no host synchronisation."""
+    hip.check_cuda(volumes)
+    if volumes.dim() != 4 or volumes.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise RuntimeError("render_views_batch expects float32, uint8 or bool [B, a, b, c]")
+    if threshold is not None and (not 0.0 < float(threshold) < 1.0 or volumes.dtype != torch.float32):
+        raise ValueError("render_views_batch: threshold must lie in (0, 1) and needs float32 logits")
+    B, d0, d1, d2 = volumes.shape
+    if B == 0:
+        raise ValueError("render_views_batch: no volumes")
+    if min(d0, d1, d2) < 1 or max(d0, d1, d2) > SURFACE_MAX_DIM:
+        raise ValueError(f"render_views_batch: dims {(d0, d1, d2)}, every dim must lie in 1 .. {SURFACE_MAX_DIM}")
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1 or H * W > 1 << 24:
+        raise ValueError(f"render_views_batch: size {(H, W)}: at least 1 x 1 and at most 2^24 pixels")
+    cams = [view_camera((d0, d1, d2), size=(H, W))] if cameras is None else [np.asarray(c, np.float64) for c in cameras]
+    if not cams or any(c.size != 18 for c in cams):
+        raise ValueError("render_views_batch: cameras is a non-empty sequence of 18 numbers each (o0, ox, oy, d0, dx, dy)")
+    cam32 = np.ascontiguousarray(np.stack([c.reshape(18) for c in cams]).astype(np.float32))
+    if not np.isfinite(cam32).all():
+        raise ValueError("render_views_batch: a camera holds a number that is not finite in float32")
+    for n, c in enumerate(cam32):
+        if not c[3:9].any() and all(0.0 <= c[a] <= d for a, d in enumerate((d0, d1, d2))):
+            raise ValueError(f"render_views_batch: the eye of camera {n} lies inside or on the volume's box")
+    face = _rgb_bytes(VIEW_FACE_RGB if face_colors is None else face_colors, 18, "face_colors")
+    edge = _rgb_bytes(edge_color, 3, "edge_color")
+    plate = None
+    if isinstance(background, torch.Tensor):
+        hip.check_cuda(background)
+        if background.dtype != torch.uint8 or tuple(background.shape) != (3, H, W):
+            raise ValueError(f"render_views_batch: a background plate is uint8 [3, {H}, {W}]")
+        plate, bg = background.contiguous(), _rgb_bytes((0, 0, 0), 3, "background")
+    else:
+        bg = _rgb_bytes(background, 3, "background")
+    vol = volumes.contiguous()
+    if vol.dtype == torch.bool:
+        vol = vol.view(torch.uint8)
+    dev, n_cams = vol.device, len(cams)
+    cam_arr = (hip.ViewCamera * n_cams).from_buffer_copy(cam32.tobytes())
+    cam_ws = torch.empty(n_cams * C.sizeof(hip.ViewCamera), dtype=torch.uint8, device=dev)
+    mask_ws = torch.empty(B * d0 * d1 * (1 if d2 <= 32 else 2), dtype=torch.int32, device=dev)
+    ids = torch.empty(B, n_cams, H, W, dtype=torch.int32, device=dev)
+    rgb = torch.empty(B, n_cams, 3, H, W, dtype=torch.uint8, device=dev)
+    call("sv_render_volumes", ptr(vol), 0 if vol.dtype == torch.float32 else 1, B, d0, d1, d2, -1.0 if threshold is None else float(threshold),
+         C.addressof(cam_arr), n_cams, ptr(cam_ws), H, W, C.addressof(face), C.addressof(edge), C.addressof(bg), ptr(plate), ptr(mask_ws),
+         ptr(ids), ptr(rgb))
+    return (rgb, ids) if return_ids else rgb
+
+
+def _png_chunk(kind: bytes, body: bytes) -> bytes:
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+
+def image_file(img, fmt: str = "png") -> bytes:
+    """A uint8 [3, H, W] picture (an array, or a tensor on any device) as the contents of a .png (8-bit RGB, no interlace, every scanline
+    with filter 0) or a binary .ppm (P6) file; pure host code, standard library only."""
+    if isinstance(img, torch.Tensor):
+        img = img.detach().cpu().numpy()
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[0] != 3 or img.shape[1] < 1 or img.shape[2] < 1:
+        raise ValueError("image_file expects uint8 [3, H, W]")
+    H, W = img.shape[1:]
+    rows = np.ascontiguousarray(img.transpose(1, 2, 0)).reshape(H, 3 * W)
+    if fmt == "ppm":
+        return b"P6\n%d %d\n255\n" % (W, H) + rows.tobytes()
+    if fmt != "png":
+        raise ValueError(f"image_file: format {fmt!r} is neither 'png' nor 'ppm'")
+    raw = np.concatenate([np.zeros((H, 1), np.uint8), rows], axis=1).tobytes()   # filter type 0 in front of every scanline
+    return (b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) + _png_chunk(b"IDAT", zlib.compress(raw, 6))
+            + _png_chunk(b"IEND", b""))
 
 
 # ---- augmentation -----------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import hip
-from .data import encode_binvox_batch, encode_mesh_batch
+from .data import encode_binvox_batch, encode_mesh_batch, render_views_batch
 from .hip import call, ptr
 from .losses import bce_with_logits as _bce      # torch.nn.BCEWithLogitsLoss() of core/train.py:165 on sv_bce_logits
 from .optim import FlatAdam, FlatSGD, _FlatSolver
@@ -144,13 +144,16 @@ def evaluate(nets, cfg, images, gt, epoch_idx: int = 0, with_fscore: bool = Fals
 
 @torch.no_grad()
 def reconstruct(nets, cfg, images, epoch_idx: int = 0, binvox_threshold: Optional[float] = None, mesh_threshold: Optional[float] = None,
-                mesh_format: str = "ply"):
+                mesh_format: str = "ply", view_threshold: Optional[float] = None, view_size=(480, 640), view_cameras=None):
     """The forward of core/test.py:120-130 without ground truth: the [B, 32, 32, 32] logits of the last active module, with the
     merger / refiner gating of forward_losses and the nets in eval() for the pass, as in evaluate.  With binvox_threshold the
     result is (volume, files): files[b] is the binvox file of sigmoid(volume[b]) >= binvox_threshold, the occupancy
     voxel_metrics scores at that threshold (data.encode_binvox_batch).  With mesh_threshold the result gains a trailing list of
     mesh files, (volume, meshes) or (volume, files, meshes): meshes[b] is the exposed voxel faces of sigmoid(volume[b]) >=
-    mesh_threshold in mesh_format ("ply", "off" or "obj"), the face set core/test.py:178-187 draws (data.encode_mesh_batch)."""
+    mesh_threshold in mesh_format ("ply", "off" or "obj"), the face set core/test.py:178-187 draws (data.encode_mesh_batch).  With view_threshold it gains, after those, a
+    uint8 [B, n_cams, 3, H, W] tensor on the device: the picture core/test.py:178-187 makes of sigmoid(volume[b]) >= view_threshold
+    (utils/helpers.py:50-88), for every sample, at view_size = (H, W) from view_cameras (None: the reference's view;
+    data.render_views_batch)."""
     enc, dec, mer, ref = nets
     was_training = [n.training for n in nets]
     for n in nets:
@@ -171,6 +174,8 @@ def reconstruct(nets, cfg, images, epoch_idx: int = 0, binvox_threshold: Optiona
         out += (encode_binvox_batch(volume, threshold=binvox_threshold),)
     if mesh_threshold is not None:
         out += (encode_mesh_batch(volume, threshold=mesh_threshold, fmt=mesh_format),)
+    if view_threshold is not None:
+        out += (render_views_batch(volume, threshold=view_threshold, cameras=view_cameras, size=view_size),)
     return out if len(out) > 1 else volume
 
 

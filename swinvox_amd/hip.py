@@ -77,6 +77,10 @@ class AugImage(C.Structure):   # sv_aug_image
                 ("y_bottom", C.c_int), ("pad_l", C.c_int), ("pad_r", C.c_int), ("pad_t", C.c_int), ("pad_b", C.c_int)]
 
 
+class ViewCamera(C.Structure):   # sv_view_camera
+    _fields_ = [(n, C.c_float * 3) for n in ("o0", "ox", "oy", "d0", "dx", "dy")]
+
+
 # name -> (restype, argtypes); p = device/host pointer, i = int, l = long long, f = float, u = uint32, z = size_t
 _P, _I, _L, _F, _U, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_uint32, C.c_double
 # Entry points whose activation tensors are void* + `int act_dtype` (inserted by call() right before the stream argument)
@@ -241,6 +245,7 @@ _PROTOS = {
     "sv_binvox_decode": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "sv_binvox_encode": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _L, _P]),
     "sv_voxel_surface": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _L, _P, _L, _P]),
+    "sv_render_volumes": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sv_augment_views": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "sv_augment_images": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "sv_grad_sumsq": (_I, [_P, _L, _F, _P]),
