@@ -793,6 +793,25 @@ int sv_augment_images(const unsigned char* src, long long src_bytes, int I, int 
                       sv_aug_image* images_dev_ws, int out_h, int out_w, const sv_aug_sample* params_dev,
                       const unsigned char* flip_dev, double* grey_sum_ws, float* out, void* stream);
 
+/* sv_augment_views_bg: sv_augment_views with the folder of RandomBackground(color_range, random_bg_folder_path)
+ *    (utils/data_transforms.py:415-452), which the reference's real-photograph experiments paste their renderings over.  The
+ *    reference picks one photograph per sample (random.choice, :439) and then, per view, either that photograph or the flat
+ *    colour (random.randint(0, 1), :447); its blend alpha * bg + (1 - alpha) * img has alpha in {0, 1}, so it is a select.
+ *    All arguments of sv_augment_views keep their meaning.  bank: n_bank photographs as 8-bit [n_bank][out_h][out_w][3] on the
+ *    device, channel order of the stored renderings (cv2.imread gives both); a photograph has exactly the output size - the
+ *    reference fails on any other (its multiply cannot broadcast) - and nothing is resized or cropped.  bg_index_host (host
+ *    memory, I ints): entry i is the photograph of image i, or -1 for the flat colour params_dev[i / V].bg.
+ *    Rule: a pixel whose resized alpha is exactly 0 becomes (float)bank[idx][oy][sx][c] / 255.f when idx >= 0, else bg[c];
+ *    sx is the column the source is sampled at, out_w - 1 - ox for a flipped image: RandomFlip mirrors the finished image,
+ *    photograph included.  The grey mean of the contrast step is taken over the same composite.  C = 3 composites nothing.
+ *    The table is validated BEFORE anything is launched: -1 <= idx < n_bank for every image, and bank non-NULL when any idx is
+ *    >= 0; it is then copied to bg_index_dev_ws (I ints of device scratch) on the stream.  A bad table is an error code and
+ *    nothing is written, never a read outside the bank.  With every index -1 the output has the bits of sv_augment_views.
+ *    I <= 65535; two launches, no second pass over the output.                                                           */
+int sv_augment_views_bg(const unsigned char* src, int I, int V, int Hs, int Ws, int C, int crop_h, int crop_w, int out_h, int out_w,
+                        const sv_aug_sample* params_dev, const unsigned char* flip_dev, const unsigned char* bank, int n_bank,
+                        const int* bg_index_host, int* bg_index_dev_ws, double* grey_sum_ws, float* out, void* stream);
+
 /* sv_render_volumes: pictures of B volumes of equal dims from n_cams viewpoints - what utils/helpers.py:50-88 (get_volume_views ->
  *    Axes3D.voxels(edgecolor="k") at elev 30 / azim 45, called from core/test.py:178-187) and utils/binvox_rw.py:306-343 draw, as a
  *    ray-cast.  `vol` is [B][d0][d1][d2] in its own axis order (no fix_coords transposition), every dim in 1 .. 64; dtype and

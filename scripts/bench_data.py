@@ -41,6 +41,34 @@ def timed(fn, n=20):
 
 
 t_aug = timed(lambda: D.augment_views(x, params, cfg))
+# the same renderings over photographs (RandomBackground with a folder): a bank of 64, every second view takes its sample's photograph
+bank = D.background_bank(np.random.default_rng(1).integers(0, 256, size=(64, 224, 224, 3), dtype=np.uint8), cfg, device=dev)
+bparams = [D.AugParams(**{**vars(p), "bg_index": b % 64, "bg_photo": [v % 2 == 0 for v in range(a.views)]}) for b, p in enumerate(params)]
+t_aug_bg = timed(lambda: D.augment_views(x, bparams, cfg, backgrounds=bank))
+# ... and the launch pairs alone, by device events, on buffers prepared once
+aug_arr, aug_flips = D._pack_aug_samples(params, a.views, cfg, "bench_data")
+aug_prm = torch.frombuffer(bytearray(bytes(aug_arr)), dtype=torch.uint8).to(dev)
+aug_fl = torch.from_numpy(aug_flips).to(dev)
+aug_ws = torch.empty(a.batch * a.views, dtype=torch.float64, device=dev)
+aug_out = torch.empty(a.batch, a.views, 3, 224, 224, dtype=torch.float32, device=dev)
+aug_tab = D._bg_index_table(bparams, a.views, cfg, bank)
+aug_tab_dev = torch.empty(a.batch * a.views, dtype=torch.int32, device=dev)
+aug_head = (ptr(x), a.batch * a.views, a.views, 137, 137, 4, cfg.CONST.CROP_IMG_H, cfg.CONST.CROP_IMG_W, 224, 224, ptr(aug_prm), ptr(aug_fl))
+
+
+def timed_events(fn, n=50):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn(); torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+t_aug_kernel = timed_events(lambda: call("sv_augment_views", *aug_head, ptr(aug_ws), ptr(aug_out)))
+t_aug_bg_kernel = timed_events(lambda: call("sv_augment_views_bg", *aug_head, ptr(bank), 64, aug_tab.ctypes.data, ptr(aug_tab_dev), ptr(aug_ws),
+                                            ptr(aug_out)))
 t_vox = timed(lambda: D.decode_binvox_batch(files, dev, check=False))
 t0 = time.perf_counter()
 for b in range(min(a.batch, 4)):
@@ -134,6 +162,9 @@ n = a.batch * a.views
 print(f"augment_images  {t_box:7.3f} ms / batch of {len(photos)} photographs 640x480x3 with boxes ({len(photos) / t_box * 1e3:9.0f} images/s, host packing and "
       f"the H2D copy of {sum(im.size for im in photos) / 1e6:.1f} MB included); numpy restatement of the same path, one core: {t_box_cpu:7.1f} ms")
 print(f"augment_views   {t_aug:7.3f} ms / batch of {n} views ({n / t_aug * 1e3:9.0f} views/s, host parameter packing included)")
+print(f"augment_views   {t_aug_bg:7.3f} ms / batch of {n} views over a bank of 64 photographs 224x224x3, every second view taking one "
+      f"({n / t_aug_bg * 1e3:9.0f} views/s, host parameter and table packing included; {t_aug_bg / t_aug:.2f} x the line above); the launch pairs alone "
+      f"by device events: {t_aug_bg_kernel:6.3f} ms with the bank, {t_aug_kernel:6.3f} ms without ({t_aug_bg_kernel / t_aug_kernel:.2f} x)")
 print(f"binvox decode   {t_vox:7.3f} ms / {a.batch} volumes (header parsing + H2D of the run-length bytes included)")
 print(f"binvox encode   {t_enc:7.3f} ms / {a.batch} volumes (pair counts + trimmed payload D2H and header formatting included); "
       f"oracle.data.write_binvox on the host, one core: {t_wr:7.2f} ms")

@@ -9,6 +9,7 @@
 //                     flip -> channel permutation -> CHW float, two launches (grey means for the contrast step, then the image)
 //   sv_augment_images the same for a ragged batch of photographs, each cropped to its bounding box with edge padding
 //                     (utils/data_transforms.py:93-136, :187-232): one launch pair, a descriptor per image
+//   sv_augment_views_bg  sv_augment_views with RandomBackground's folder (:415-452): per image a photograph of a bank, or the flat colour
 #include "common.h"
 
 namespace sv {
@@ -525,6 +526,87 @@ __global__ void __launch_bounds__(256) augment_images_apply_kernel(const unsigne
   }
 }
 
+// ---- photograph backgrounds (sv_augment_views_bg): the dense pair once more, mirrored for the reason given above, with the composite
+// that RandomBackground makes when it has a folder (utils/data_transforms.py:437-448): image blockIdx.y takes photograph bg_index[img] of
+// the bank ([n_bank][Ho][Wo][3] bytes) where its resized alpha is exactly zero, or the flat colour when the index is -1.  The reference's
+// alpha * bg + (1 - alpha) * img with alpha in {0, 1} is a select.  The photograph has the size of the output, so its pixel is read at the
+// output row and at the column the source is sampled at: RandomFlip mirrors the finished image, photograph included.  One byte-triple per
+// transparent pixel, consecutive lanes on consecutive triples (mirrored: descending).  The entry has checked every index against n_bank.
+__device__ __forceinline__ void composite_photo(float px[4], int C, const float bg[3], const unsigned char* __restrict__ photo, int pix) {
+  if (C == 4 && px[3] == 0.f) {
+    if (photo != nullptr) {
+      const unsigned char* t = photo + (size_t)pix * 3;
+      px[0] = (float)t[0] / 255.f;               // cv2.imread(...).astype(np.float32) / 255.
+      px[1] = (float)t[1] / 255.f;
+      px[2] = (float)t[2] / 255.f;
+    } else {
+      px[0] = bg[0];
+      px[1] = bg[1];
+      px[2] = bg[2];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) augment_bg_grey_mean_kernel(const unsigned char* __restrict__ src, AugGeom g, const sv_aug_sample* __restrict__ prm,
+                                                                   const unsigned char* __restrict__ bank, const int* __restrict__ bg_index,
+                                                                   double* __restrict__ grey_sum) {
+  __shared__ float red[4];
+  const int img = blockIdx.y;
+  const sv_aug_sample& P = prm[img / g.V];
+  const unsigned char* s = src + (size_t)img * g.Hs * g.Ws * g.C;
+  const int npix = g.Ho * g.Wo;
+  const int bi = bg_index[img];
+  const unsigned char* photo = bi >= 0 ? bank + (size_t)bi * npix * 3 : nullptr;
+  float acc = 0.f;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
+    float px[4];
+    sample_pixel(s, g, p / g.Wo, p % g.Wo, px);
+    composite_photo(px, g.C, P.bg, photo, p);
+    acc += grey_of(px);
+  }
+  const float r = block_sum<4>(acc, red);
+  if (threadIdx.x == 0) atomicAdd(&grey_sum[img], (double)r);
+}
+
+__global__ void __launch_bounds__(256) augment_bg_apply_kernel(const unsigned char* __restrict__ src, AugGeom g, const sv_aug_sample* __restrict__ prm,
+                                                               const unsigned char* __restrict__ flip, const unsigned char* __restrict__ bank,
+                                                               const int* __restrict__ bg_index, const double* __restrict__ grey_sum,
+                                                               float* __restrict__ out) {
+  const int img = blockIdx.y;
+  const sv_aug_sample P = prm[img / g.V];
+  const unsigned char* s = src + (size_t)img * g.Hs * g.Ws * g.C;
+  const int npix = g.Ho * g.Wo;
+  const bool fl = flip != nullptr && flip[img] != 0;
+  const int bi = bg_index[img];
+  const unsigned char* photo = bi >= 0 ? bank + (size_t)bi * npix * 3 : nullptr;
+  float mean_grey = (float)(grey_sum[img] / (double)npix);
+  float contrast_mean = mean_grey;                                 // as in augment_apply_kernel
+  for (int k = 0; k < 3; ++k) {
+    if (P.jitter_order[k] == 1) break;
+    if (P.jitter_order[k] == 0) contrast_mean *= P.jitter_value[0];
+  }
+  float* o = out + (size_t)img * 3 * npix;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
+    const int oy = p / g.Wo, ox = p % g.Wo;
+    const int sx = fl ? g.Wo - 1 - ox : ox;
+    float px[4];
+    sample_pixel(s, g, oy, sx, px);
+    composite_photo(px, g.C, P.bg, photo, oy * g.Wo + sx);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int kind = P.jitter_order[k];
+      const float a = P.jitter_value[kind];
+      const float other = kind == 0 ? 0.f : (kind == 1 ? contrast_mean : grey_of(px));
+#pragma unroll
+      for (int c = 0; c < 3; ++c) px[c] = a * px[c] + (1.f - a) * other;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[c] = (px[c] + P.noise[c] - P.mean[c]) / P.std[c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[(size_t)c * npix + p] = px[P.perm[c]];
+  }
+}
+
 }  // namespace sv
 
 using namespace sv;
@@ -589,6 +671,38 @@ extern "C" int sv_augment_views(const unsigned char* src, int I, int V, int Hs, 
   hipLaunchKernelGGL(augment_grey_mean_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, g, params_dev, grey_sum_ws);
   hipLaunchKernelGGL(augment_apply_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, g, params_dev, flip_dev, grey_sum_ws, out);
   return check_launch("sv_augment_views");
+}
+
+// sv_augment_views with RandomBackground's folder (data_transforms.py:437-448): a photograph of the bank, or the flat colour, per image
+extern "C" int sv_augment_views_bg(const unsigned char* src, int I, int V, int Hs, int Ws, int C, int crop_h, int crop_w, int out_h, int out_w,
+                                   const sv_aug_sample* params_dev, const unsigned char* flip_dev, const unsigned char* bank, int n_bank,
+                                   const int* bg_index_host, int* bg_index_dev_ws, double* grey_sum_ws, float* out, void* stream) {
+  SV_REQUIRE(src && params_dev && grey_sum_ws && out && bg_index_host && bg_index_dev_ws, "augment_views_bg: bad arguments");
+  SV_REQUIRE(I > 0 && V > 0 && I % V == 0 && (C == 3 || C == 4) && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0, "augment_views_bg: bad shapes");
+  SV_REQUIRE(I <= 65535, "augment_views_bg: %d images (1 ... 65535 per call)", I);
+  SV_REQUIRE((long long)out_h * out_w < (1ll << 30), "augment_views_bg: bad output size %d x %d", out_h, out_w);
+  SV_REQUIRE(n_bank >= 0, "augment_views_bg: a bank of %d photographs", n_bank);
+  for (int i = 0; i < I; ++i) {                                      // the whole table, on the host, before anything is launched
+    const int idx = bg_index_host[i];
+    SV_REQUIRE(idx >= -1 && idx < n_bank, "augment_views_bg: image %d asks for photograph %d of a bank of %d (-1 = the flat colour)", i, idx, n_bank);
+    SV_REQUIRE(idx < 0 || bank != nullptr, "augment_views_bg: image %d asks for photograph %d and the bank is NULL", i, idx);
+  }
+  AugGeom g;
+  g.I = I; g.V = V; g.Hs = Hs; g.Ws = Ws; g.C = C; g.Ho = out_h; g.Wo = out_w;
+  if (Hs > crop_h && Ws > crop_w && crop_h > 0 && crop_w > 0) {      // as in sv_augment_views
+    g.x0 = (Ws - crop_w) / 2; g.y0 = (Hs - crop_h) / 2; g.cw = crop_w; g.ch = crop_h;
+  } else {
+    g.x0 = 0; g.y0 = 0; g.cw = Ws; g.ch = Hs;
+  }
+  // pageable host memory: the copy has read bg_index_host when the call returns
+  hipError_t e = hipMemcpyAsync(bg_index_dev_ws, bg_index_host, sizeof(int) * (size_t)I, hipMemcpyHostToDevice, STREAM);
+  if (e != hipSuccess) { set_error("augment_views_bg: index copy failed: %s", hipGetErrorString(e)); return SV_ERR_LAUNCH; }
+  e = hipMemsetAsync(grey_sum_ws, 0, sizeof(double) * (size_t)I, STREAM);
+  if (e != hipSuccess) { set_error("augment_views_bg: memset failed: %s", hipGetErrorString(e)); return SV_ERR_LAUNCH; }
+  const int bx = cdiv((long long)out_h * out_w, 256 * 4);
+  hipLaunchKernelGGL(augment_bg_grey_mean_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, g, params_dev, bank, bg_index_dev_ws, grey_sum_ws);
+  hipLaunchKernelGGL(augment_bg_apply_kernel, dim3(bx, I), dim3(256), 0, STREAM, src, g, params_dev, flip_dev, bank, bg_index_dev_ws, grey_sum_ws, out);
+  return check_launch("sv_augment_views_bg");
 }
 
 // CenterCrop / RandomCrop with a bounding box (data_transforms.py:93-136 / :187-232) for a ragged batch, then the list of sv_augment_views

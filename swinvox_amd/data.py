@@ -5,6 +5,8 @@ The reference expands every sample on the CPU inside DataLoader workers (np.repe
 passes per rendering).  Here the workers only read bytes: run-length pairs and 8-bit renderings go to the GPU as they are and
 two entry points expand a whole batch - sv_binvox_decode and sv_augment_views.  Random augmentation parameters are drawn on
 the host in the reference's call order (draw_train_params), so a seeded run sees the same crops / colours / flips.
+Renderings pasted over photographs (RandomBackground with a folder, utils/data_transforms.py:415-452): augment_views(..., backgrounds=
+background_bank(...)) -> sv_augment_views_bg, the photograph and the per-view choice drawn by draw_train_params(n_backgrounds=N).
 Photographs with bounding boxes (the Pascal3D / Pix3D loaders, utils/data_loaders.py:176-203, :311-338) go through augment_images:
 images of differing sizes in one packed buffer, the reference's crop integers computed on the host (bbox_crop_rect), one launch pair.
 """
@@ -368,20 +370,28 @@ class AugParams:
     flips: Sequence[bool] = field(default_factory=list)
     perm: Sequence[int] = (0, 1, 2)
     crop_draws: Optional[Sequence[float]] = None          # RandomCrop with a bounding box: scale, then left / right / top / bottom (:203-208)
+    bg_index: Optional[int] = None                        # RandomBackground with a folder: the sample's photograph (random.choice, :439)
+    bg_photo: Sequence[bool] = ()                         # ... and per view whether it takes it or the flat colour (random.randint, :447)
 
     def noise_rgb(self) -> np.ndarray:
         a = np.asarray(self.noise_alpha, dtype=np.float64)   # utils/data_transforms.py:373-383
         return np.sum(np.multiply(np.multiply(np.array(EIGVECS), np.tile(a, (3, 1))), np.tile(np.array(EIGVALS), (3, 1))), axis=1)
 
 
-def draw_train_params(n_views: int, cfg, rng_np=np.random, rng_py=random, n_channels: int = 4, bounding_box=None) -> AugParams:
+def draw_train_params(n_views: int, cfg, rng_np=np.random, rng_py=random, n_channels: int = 4, bounding_box=None,
+                      n_backgrounds: int = 0) -> AugParams:
     """One __getitem__ worth of random draws in the reference's call order: RandomBackground (data_transforms.py:425-428, plus
     the per-image random.randint of :440), ColorJitter (:276-284), RandomNoise (:372), RandomFlip (:252-255),
     RandomPermuteRGB (:67).  RandomCrop draws nothing without a bounding box (:222-231).  RandomBackground returns before it draws
     anything when the renderings have no alpha channel (:428-430): pass n_channels=3 for RGB inputs.
     With a bounding_box (any non-None value; its numbers are not used here) RandomCrop, the first transform of the list
-    (core/train.py:44-53), draws first: random.uniform(0.8, 1.2) and four random.uniform(.4, .6) (:203-208) -> crop_draws."""
-    crop_draws = None
+    (core/train.py:44-53), draws first: random.uniform(0.8, 1.2) and four random.uniform(.4, .6) (:203-208) -> crop_draws.
+    With n_backgrounds > 0 (RandomBackground given a folder of that many files, :416-421) and four channels the sample's photograph is
+    drawn after the colour - random.choice over the files (:439), here over range(n_backgrounds) - and the per-view coin flips that
+    follow are kept as bg_photo instead of thrown away.  With n_backgrounds == 0 every draw is what it was without the argument."""
+    if n_backgrounds < 0:
+        raise ValueError(f"draw_train_params: n_backgrounds = {n_backgrounds}")
+    crop_draws, bg_index, bg_photo = None, None, ()
     if bounding_box is not None:
         _refuse_box_with_views(n_views, "draw_train_params")
         crop_draws = [rng_py.uniform(0.8, 1.2)] + [rng_py.uniform(.4, .6) for _ in range(4)]
@@ -389,8 +399,10 @@ def draw_train_params(n_views: int, cfg, rng_np=np.random, rng_py=random, n_chan
     rg = t.RANDOM_BG_COLOR_RANGE
     if n_channels == 4:
         bg = np.array([rng_np.randint(rg[i][0], rg[i][1] + 1) for i in range(3)]) / 255.0
-        for _ in range(n_views):
-            rng_py.randint(0, 1)
+        if n_backgrounds > 0:
+            bg_index = int(rng_py.choice(range(n_backgrounds)))
+        coins = [bool(rng_py.randint(0, 1)) for _ in range(n_views)]       # drawn with or without a folder
+        bg_photo = coins if n_backgrounds > 0 else ()
     else:
         bg = np.ones(3)                       # unused: the composite step is skipped for 3-channel images
     jv = [1 + rng_np.uniform(low=-t.BRIGHTNESS, high=t.BRIGHTNESS), 1 + rng_np.uniform(low=-t.CONTRAST, high=t.CONTRAST),
@@ -401,7 +413,7 @@ def draw_train_params(n_views: int, cfg, rng_np=np.random, rng_py=random, n_chan
     flips = [bool(rng_py.randint(0, 1)) for _ in range(n_views)]
     perm = rng_np.permutation(3)
     return AugParams(bg=bg.tolist(), jitter_value=jv, jitter_order=[int(i) for i in order], noise_alpha=alpha.tolist(), flips=flips,
-                     perm=[int(i) for i in perm], crop_draws=crop_draws)
+                     perm=[int(i) for i in perm], crop_draws=crop_draws, bg_index=bg_index, bg_photo=bg_photo)
 
 
 def val_params(n_views: int, cfg, n_channels: int = 4) -> AugParams:
@@ -486,9 +498,80 @@ def _pack_aug_samples(params: Sequence[AugParams], V: int, cfg, who: str):
     return arr, flips
 
 
-def augment_views(images_u8: torch.Tensor, params: Sequence[AugParams], cfg) -> torch.Tensor:
+def background_bank(photos, cfg, device="cuda") -> torch.Tensor:
+    """The photographs of RandomBackground's folder (utils/data_transforms.py:416-421) as one uint8 [N, IMG_H, IMG_W, 3] tensor on the
+    GPU, contiguous: what augment_views(..., backgrounds=) reads.  photos: a list of uint8 [IMG_H, IMG_W, 3] arrays (numpy or tensors)
+    as cv2.imread returns them - the channel order of the stored renderings -, or an already stacked array or tensor.  Nothing is
+    resized or cropped: any other size, rank or dtype is a ValueError, because the reference fails on it too (its
+    alpha * bg_color at :448 cannot broadcast a photograph that is not the size of the resized rendering)."""
+    H, W = cfg.CONST.IMG_H, cfg.CONST.IMG_W
+    why = (f"background_bank: a photograph is uint8 [{H}, {W}, 3] (cfg.CONST.IMG_H x IMG_W, three channels), got %s; the reference fails on it "
+           "too: its blend cannot broadcast a photograph of another size onto the resized rendering (utils/data_transforms.py:448)")
+    if isinstance(photos, (list, tuple)):
+        if not photos:
+            raise ValueError("background_bank: no photographs")
+        host = []
+        for ph in photos:
+            if isinstance(ph, torch.Tensor):
+                if ph.dtype != torch.uint8 or tuple(ph.shape) != (H, W, 3):
+                    raise ValueError(why % f"{ph.dtype} {list(ph.shape)}")
+                host.append(ph)
+            else:
+                ph = np.asarray(ph)
+                if ph.dtype != np.uint8 or ph.shape != (H, W, 3):
+                    raise ValueError(why % f"{ph.dtype} {list(ph.shape)}")
+                host.append(torch.from_numpy(np.ascontiguousarray(ph)))
+        bank = torch.stack(host)
+    else:
+        bank = photos if isinstance(photos, torch.Tensor) else None
+        if bank is None:
+            arr = np.asarray(photos)
+            if arr.dtype != np.uint8:
+                raise ValueError(why % f"{arr.dtype} {list(arr.shape)}")
+            bank = torch.from_numpy(np.ascontiguousarray(arr))
+        if bank.dtype != torch.uint8 or bank.dim() != 4 or bank.shape[0] < 1 or tuple(bank.shape[1:]) != (H, W, 3):
+            raise ValueError(why % f"a stack {bank.dtype} {list(bank.shape)}")
+    dev = bank.device if bank.is_cuda else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("swinvox_amd: tensors must live on the GPU (no CPU path exists in the product)")
+    return bank.to(dev).contiguous()
+
+
+def _bg_index_table(params: Sequence[AugParams], V: int, cfg, backgrounds) -> np.ndarray:
+    """host side of sv_augment_views_bg's table, int32 [len(params) * V]: the sample's photograph for a view whose coin says so, else -1"""
+    H, W = cfg.CONST.IMG_H, cfg.CONST.IMG_W
+    if not isinstance(backgrounds, torch.Tensor) or backgrounds.dtype != torch.uint8 or backgrounds.dim() != 4 or \
+            backgrounds.shape[0] < 1 or tuple(backgrounds.shape[1:]) != (H, W, 3):
+        got = f"{backgrounds.dtype} {list(backgrounds.shape)}" if isinstance(backgrounds, torch.Tensor) else type(backgrounds).__name__
+        raise ValueError(f"augment_views: backgrounds is a uint8 [N, {H}, {W}, 3] tensor (data.background_bank; cfg.CONST.IMG_H x IMG_W), got {got}")
+    n_bank = backgrounds.shape[0]
+    table = np.full(len(params) * V, -1, dtype=np.int32)
+    for b, p in enumerate(params):
+        if len(p.bg_photo) not in (0, V):
+            raise ValueError(f"augment_views: sample {b} has {len(p.bg_photo)} bg_photo flags for {V} views (none, or one per view)")
+        if p.bg_index is None:
+            continue
+        if not 0 <= int(p.bg_index) < n_bank:
+            raise ValueError(f"augment_views: sample {b} asks for photograph {p.bg_index} of a bank of {n_bank}")
+        for v, take in enumerate(p.bg_photo):
+            if take:
+                table[b * V + v] = int(p.bg_index)
+    return table
+
+
+def augment_views(images_u8: torch.Tensor, params: Sequence[AugParams], cfg, backgrounds: Optional[torch.Tensor] = None) -> torch.Tensor:
     """images_u8 [B, V, Hs, Ws, C] uint8 on the GPU (C = 4 with alpha or 3, channel order as stored) -> float32
-    [B, V, 3, IMG_H, IMG_W]: the tensor the reference's DataLoader hands to core/train.py:222."""
+    [B, V, 3, IMG_H, IMG_W]: the tensor the reference's DataLoader hands to core/train.py:222.
+    backgrounds: None, or a bank of photographs (background_bank) - RandomBackground with a folder (utils/data_transforms.py:437-448).
+    View v of sample b then shows photograph params[b].bg_index where the rendering is transparent if params[b].bg_photo[v] is set,
+    and the flat colour params[b].bg otherwise (always, for a sample whose bg_index is None); draw_train_params(n_backgrounds=N) draws
+    both.  The bank and the parameters are checked (ValueError) before anything else happens."""
+    table = None
+    if backgrounds is not None:
+        if images_u8.dim() != 5:
+            raise RuntimeError("augment_views expects uint8 [B, V, Hs, Ws, C]")
+        table = _bg_index_table(params, images_u8.shape[1], cfg, backgrounds)
+        hip.check_cuda(backgrounds)
     hip.check_cuda(images_u8)
     if images_u8.dtype != torch.uint8 or images_u8.dim() != 5:
         raise RuntimeError("augment_views expects uint8 [B, V, Hs, Ws, C]")
@@ -503,8 +586,16 @@ def augment_views(images_u8: torch.Tensor, params: Sequence[AugParams], cfg) -> 
     ws = torch.empty(B * V, dtype=torch.float64, device=dev)
     H, W = cfg.CONST.IMG_H, cfg.CONST.IMG_W
     out = torch.empty(B, V, 3, H, W, dtype=torch.float32, device=dev)
-    call("sv_augment_views", ptr(images_u8), B * V, V, Hs, Ws, Cc, cfg.CONST.CROP_IMG_H, cfg.CONST.CROP_IMG_W, H, W, ptr(prm), ptr(fl),
-         ptr(ws), ptr(out))
+    if table is None:
+        call("sv_augment_views", ptr(images_u8), B * V, V, Hs, Ws, Cc, cfg.CONST.CROP_IMG_H, cfg.CONST.CROP_IMG_W, H, W, ptr(prm), ptr(fl),
+             ptr(ws), ptr(out))
+        return out
+    if backgrounds.device != dev:
+        raise RuntimeError(f"augment_views: the bank lives on {backgrounds.device}, the renderings on {dev}")
+    bank = backgrounds.contiguous()
+    table_dev = torch.empty(B * V, dtype=torch.int32, device=dev)
+    call("sv_augment_views_bg", ptr(images_u8), B * V, V, Hs, Ws, Cc, cfg.CONST.CROP_IMG_H, cfg.CONST.CROP_IMG_W, H, W, ptr(prm), ptr(fl),
+         ptr(bank), bank.shape[0], table.ctypes.data, ptr(table_dev), ptr(ws), ptr(out))
     return out
 
 

@@ -247,6 +247,7 @@ _PROTOS = {
     "sv_voxel_surface": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _L, _P, _L, _P]),
     "sv_render_volumes": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sv_augment_views": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "sv_augment_views_bg": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_augment_images": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "sv_grad_sumsq": (_I, [_P, _L, _F, _P]),
     "sv_adam_step": (_I, [_P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _L, _F, _P, _F, _P]),
