@@ -845,6 +845,43 @@ int sv_render_volumes(const void* vol, int dtype, int B, int d0, int d1, int d2,
                       const unsigned char* face_rgb, const unsigned char* edge_rgb, const unsigned char* background_rgb,
                       const unsigned char* plate_dev, unsigned int* mask_ws, int* ids, unsigned char* rgb, void* stream);
 
+/* sv_voxelise_meshes: B triangle meshes -> B occupancy volumes of equal dims, the step the reference leaves to the external `binvox`
+ *    program (utils/binvox_converter.py and its notebook's convert_obj_to_binvox shell out to it).  That program is part of neither
+ *    tree and was never run next to this code: NO PARITY WITH IT IS CLAIMED.  What is computed is the rule below, in exact integer
+ *    arithmetic, so that a restatement (tests/mesh_voxel_ref.py) agrees bit for bit.
+ *    Grid and fixed point.  S = 1024 units per voxel.  verts: int32 [total_verts][3] in grid units, tris: int32 [total_tris][3], both
+ *    on the device; mesh b owns vertices mesh_table[4b] .. + mesh_table[4b+1] and triangles mesh_table[4b+2] .. + mesh_table[4b+3], its
+ *    triangle indices counting from its own first vertex.  Dims d0, d1, d2 in 1 .. 64 each (the range of sv_voxel_surface).  Voxel
+ *    (i, j, k) is the closed cube [iS, (i+1)S] x [jS, (j+1)S] x [kS, (k+1)S]; its centre ((2i+1)S/2, (2j+1)S/2, (2k+1)S/2) is a lattice
+ *    point of the units.  Every coordinate must lie in [-d S, 2 d S] of its axis - the CALLER guarantees it (data.voxelise_mesh_batch
+ *    refuses a mesh outside with the reason); inside it every quantity fits int64: differences < 2^18, edge functions and normal
+ *    components < 2^37, plane values < 2^57.  A triangle with a zero normal is skipped in both modes.
+ *    SV_VOXELISE_SOLID: parity along z.  For a triangle a, b, c: A2 = (b.x-a.x)(c.y-a.y) - (b.y-a.y)(c.x-a.x); A2 == 0: skipped; A2 < 0:
+ *    b and c change places for the edge tests only.  The column through the centre P = (Px, Py) is covered when for each directed edge
+ *    u -> v, d = v - u, the edge function E = d.x (Py - u.y) - d.y (Px - u.x) is > 0, or is 0 and the edge owns its ties: d.y < 0, or
+ *    d.y == 0 and d.x < 0.  With n = (b-a) x (c-a) of the original triangle, voxel k of a covered column is toggled iff
+ *    sgn(n.z) (n.x (Px-a.x) + n.y (Py-a.y) + n.z (zk - a.z)) > 0, zk = (2k+1)S/2: the crossing lies strictly below the centre; the
+ *    toggled voxels are a suffix of the column.  A voxel is set iff it was toggled an odd number of times.
+ *    SV_VOXELISE_SURFACE: voxel (i, j, k) is set iff its closed cube and the closed triangle intersect, decided by the 13 separating
+ *    axes (3 cube normals, the triangle's normal, 9 cross products of a cube axis with a triangle edge) with the vertices taken
+ *    relative to the cube's centre: the sets are disjoint iff on one axis the triangle's projections lie strictly beyond the cube's
+ *    radius S/2 (|x| + |y| + |z| of the axis).  Touching counts: a triangle lying in a lattice plane sets the voxels on BOTH sides of it.
+ *    SV_VOXELISE_BOTH: surface | solid, what `binvox -e` is documented to produce (exact surface voxels, interior filled).
+ *    XOR and OR commute: the result depends neither on the order of the triangles nor on how they are split over workgroups.
+ *    out: [B][d0][d1][d2], 0 / 1 as float32 (out_dtype 0) or uint8 (1).  workspace: sv_voxelise_meshes_workspace_bytes(B, d0, d1, d2)
+ *    bytes of device scratch, 8-byte aligned, cleared on the stream by the call (no host synchronisation): the table's device copy
+ *    (4 B long longs), then B ints at byte offset 32 B - entry b counts the triangles of mesh b that name a vertex outside 0 ..
+ *    n_verts - 1; such a triangle is skipped, never dereferenced, and data.voxelise_mesh_batch raises on a non-zero count -, then
+ *    (8-byte aligned) per mesh the solid and the surface mask, d0*d1 rows of one (d2 <= 32) or two 32-bit words, bit k = voxel (i, j, k).
+ *    mesh_table (host memory) is validated BEFORE anything is launched: offsets and counts >= 0 and inside total_verts / total_tris,
+ *    counts < 2^31; also refused: null out / workspace / table (verts and tris may be NULL when their total is 0), B outside 1 .. 65535,
+ *    dims outside 1 .. 64, an unknown mode or out_dtype, a misaligned workspace.  A refused call is an error code; out and the
+ *    workspace are untouched.  A mesh without triangles gives an empty volume.  The workspace query returns 0 for what is refused. */
+enum { SV_VOXELISE_SOLID = 0, SV_VOXELISE_SURFACE = 1, SV_VOXELISE_BOTH = 2 };
+size_t sv_voxelise_meshes_workspace_bytes(int B, int d0, int d1, int d2);
+int sv_voxelise_meshes(const int* verts, long long total_verts, const int* tris, long long total_tris, const long long* mesh_table,
+                       int B, int d0, int d1, int d2, int mode, int out_dtype, void* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,37 @@ t0 = time.perf_counter()
 host_views = np.stack([VR.shade(VR.render_ids(v, view_cam, (480, 640)), D.VIEW_FACE_RGB) for v in vols])
 t_view_cpu = (time.perf_counter() - t0) * 1e3
 view_diff = int((host_views != D.render_views_batch(vol_dev)[:, 0].cpu().numpy()).any(axis=1).sum())
+# mesh voxelisation (sv_voxelise_meshes): the voxel surfaces of the same volumes as triangle meshes, the last one replaced by the surface of a
+# half-filled volume (about 100 k triangles), back to 32^3 in mode "both"; next to the numpy restatement of the rule (tests/mesh_voxel_ref.py,
+# clipped to bounding boxes) on the host, timed on the first VOX_SAMPLE triangles of a small and of the large mesh and scaled by the counts
+import mesh_voxel_ref as MR  # noqa: E402
+
+VOX_SAMPLE = 2000
+vox_meshes = D.extract_surface_batch(vol_dev)
+vox_meshes[-1] = D.extract_surface_batch(torch.from_numpy(np.random.default_rng(2).random((1, 32, 32, 32)) < 0.5).to(dev))[0]
+t_voxelise = timed(lambda: D.voxelise_mesh_batch(vox_meshes, 32, fit=None, device=dev), n=10)
+vox_packed, vox_table, vox_nv, vox_nt, _, _ = D.pack_meshes(vox_meshes, 32, fit=None)
+vox_buf = torch.from_numpy(vox_packed).to(dev)
+vox_out = torch.empty(a.batch, 32, 32, 32, dtype=torch.float32, device=dev)
+vox_ws = torch.empty(S.hip.load().sv_voxelise_meshes_workspace_bytes(a.batch, 32, 32, 32), dtype=torch.uint8, device=dev)
+vox_launch = lambda: call("sv_voxelise_meshes", ptr(vox_buf), vox_nv, ptr(vox_buf) + 12 * vox_nv, vox_nt, vox_table.ctypes.data, a.batch,  # noqa: E731
+                          32, 32, 32, 2, 0, ptr(vox_out), ptr(vox_ws))
+t_voxelise_kernel = [timed_events(vox_launch, n=20) for _ in range(2)]
+t_voxelise_cpu, vox_diff = [], 0
+for run in range(2):
+    t_run = 0.0
+    for b in (0, a.batch - 1):
+        v, nv_b, t0_b, nt_b = (int(x) for x in vox_table[b])
+        verts_b = vox_packed[3 * v:3 * (v + nv_b)].reshape(-1, 3)
+        tris_b = vox_packed[3 * vox_nv + 3 * t0_b:3 * vox_nv + 3 * (t0_b + nt_b)].reshape(-1, 3)[:VOX_SAMPLE]
+        t0 = time.perf_counter()
+        want = MR.voxelise(verts_b, tris_b, (32, 32, 32), "both", clip=True)
+        per_tri = (time.perf_counter() - t0) / len(tris_b)
+        t_run += per_tri * (vox_nt - int(vox_table[-1, 3]) if b == 0 else int(vox_table[-1, 3])) * 1e3
+        if run == 0:
+            got = D.voxelise_mesh_batch([(verts_b / 1024.0, tris_b)], 32, fit=None, device=dev)[0][0].cpu().numpy() != 0
+            vox_diff += int((got != want).sum())
+    t_voxelise_cpu.append(t_run)
 # photographs with bounding boxes (the Pascal3D / Pix3D branch): 32 images of 640 x 480 x 3, each cropped to its jittered box
 photos = [rng.integers(0, 256, size=(480, 640, 3), dtype=np.uint8) for _ in range(32)]
 boxes = [(0.1 + 0.2 * rng.random(), 0.1 + 0.2 * rng.random(), 0.7 + 0.35 * rng.random(), 0.7 + 0.35 * rng.random()) for _ in photos]
@@ -174,4 +205,9 @@ print(f"voxel surface   {t_mesh:7.3f} ms / {a.batch} volumes as PLY files (count
 print(f"volume views    {t_view:7.3f} ms / {a.batch} volumes as {a.batch} pictures of 640x480 on the device (allocation of the outputs and the camera copy "
       f"included; {t_view_kernel:6.3f} ms the three launches alone by device events); numpy restatement of the same ray-cast and shading on the host, "
       f"one core: {t_view_cpu:7.1f} ms; pixels that differ between the two: {view_diff}")
+print(f"mesh voxelise    {t_voxelise:7.3f} ms / {a.batch} meshes of {vox_nt} triangles in all (the largest {int(vox_table[-1, 3])}) -> 32^3, mode both (fan "
+      f"triangulation, snapping, packing, the H2D copy of {vox_packed.nbytes / 1e6:.1f} MB and the counter read-back included); the launches alone by "
+      f"device events, two runs: {t_voxelise_kernel[0]:6.3f} / {t_voxelise_kernel[1]:6.3f} ms; numpy restatement of the same rule on the host, one core, "
+      f"scaled from {VOX_SAMPLE} triangles of a small and of the large mesh, two runs: {t_voxelise_cpu[0]:8.0f} / {t_voxelise_cpu[1]:8.0f} ms; voxels that "
+      f"differ between the two on those triangles: {vox_diff}")
 print(f"numpy restatement of the reference path, one core: {t_cpu:8.1f} ms / batch ({n / t_cpu * 1e3:7.0f} views/s)")

@@ -9,6 +9,8 @@ Renderings pasted over photographs (RandomBackground with a folder, utils/data_t
 background_bank(...)) -> sv_augment_views_bg, the photograph and the per-view choice drawn by draw_train_params(n_backgrounds=N).
 Photographs with bounding boxes (the Pascal3D / Pix3D loaders, utils/data_loaders.py:176-203, :311-338) go through augment_images:
 images of differing sizes in one packed buffer, the reference's crop integers computed on the host (bbox_crop_rect), one launch pair.
+Ground truth from model files (utils/binvox_converter.py, which shells out to the external binvox program): parse_mesh reads OFF / OBJ / PLY,
+voxelise_mesh_batch -> sv_voxelise_meshes voxelises a ragged batch in exact integer arithmetic, meshes_to_binvox writes the files.
 """
 from __future__ import annotations
 
@@ -222,6 +224,303 @@ def encode_mesh_batch(volumes: torch.Tensor, threshold: Optional[float] = None, 
     trs = _per_volume(translate, B, lambda t: not hasattr(t[0], "__len__"), "translate", "encode_mesh_batch")
     scs = _per_volume(scale, B, lambda s: not hasattr(s, "__len__"), "scale", "encode_mesh_batch")
     return [mesh_file(v, f, fmt, dims, trs[i], scs[i]) for i, (v, f) in enumerate(meshes)]
+
+
+# ---- mesh voxelisation -----------------------------------------------------------------------------------------------------
+VOXEL_UNITS = 1024                                                         # S of sv_voxelise_meshes: snapped units per voxel
+_VOXELISE_MODES = {"solid": 0, "surface": 1, "both": 2}                    # SV_VOXELISE_*
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2", "int": "i4",
+              "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _fan(polys) -> np.ndarray:
+    """polygons (index lists, or an [m, k] array) -> int64 [t, 3]: polygon (p0 .. pk-1) becomes (p0, pi, pi+1), i = 1 .. k - 2, in order"""
+    if isinstance(polys, np.ndarray):
+        if polys.size == 0:
+            return np.zeros((0, 3), np.int64)
+        if polys.ndim != 2 or polys.shape[1] < 3:
+            raise ValueError(f"faces are [m, k] with k >= 3 corners, got {list(polys.shape)}")
+        f = polys.astype(np.int64)
+        return np.stack([np.stack([f[:, 0], f[:, i], f[:, i + 1]], axis=1) for i in range(1, f.shape[1] - 1)], axis=1).reshape(-1, 3)
+    tris = [(p[0], p[i], p[i + 1]) for p in polys for i in range(1, len(p) - 1)]
+    return np.asarray(tris, np.int64).reshape(-1, 3)
+
+
+def _parse_off(text: str):
+    lines = [ln.split("#", 1)[0].split() for ln in text.splitlines()]
+    lines = [ln for ln in lines if ln]
+    head = lines[0]
+    if head[0] not in ("OFF", "COFF"):
+        raise ValueError(f"parse_mesh: an OFF file starts with OFF or COFF, got {head[0]!r}")
+    if len(head) >= 3:                                                     # "OFF n m e" on one line
+        counts, row = head[1:], 1
+    else:
+        counts, row = lines[1], 2
+    n, m = int(counts[0]), int(counts[1])
+    if len(lines) < row + n + m:
+        raise ValueError(f"parse_mesh: the OFF header promises {n} vertices and {m} faces, the file holds {len(lines) - row} lines")
+    verts = np.asarray([[float(x) for x in ln[:3]] for ln in lines[row:row + n]], np.float64).reshape(-1, 3)
+    polys = []
+    for ln in lines[row + n:row + n + m]:
+        k = int(ln[0])
+        if k < 3 or len(ln) < 1 + k:
+            raise ValueError(f"parse_mesh: OFF face {' '.join(ln)!r} has fewer than 3 corners or misses indices")
+        polys.append([int(x) for x in ln[1:1 + k]])                        # colours after the indices are ignored
+    return verts, _fan(polys)
+
+
+def _parse_obj(text: str):
+    verts, polys = [], []
+    for ln in text.splitlines():
+        tok = ln.split("#", 1)[0].split()
+        if not tok:
+            continue
+        if tok[0] == "v":
+            verts.append([float(x) for x in tok[1:4]])
+        elif tok[0] == "f":
+            idx = [int(t.split("/")[0]) for t in tok[1:]]                  # i, i/t, i/t/n, i//n
+            if len(idx) < 3 or 0 in idx:
+                raise ValueError(f"parse_mesh: OBJ face {ln.strip()!r} has fewer than 3 corners or an index 0")
+            polys.append([i - 1 if i > 0 else len(verts) + i for i in idx])   # negative: counted back from the vertices read so far
+    return np.asarray(verts, np.float64).reshape(-1, 3), _fan(polys)
+
+
+def _parse_ply(raw: bytes):
+    end = raw.find(b"end_header")
+    nl = raw.find(b"\n", end)
+    if end < 0 or nl < 0:
+        raise ValueError("parse_mesh: a PLY file without end_header")
+    fmt, elements = None, []                                               # elements: [name, count, [(kind, ...), ...]]
+    for ln in raw[:end].decode("latin-1").splitlines()[1:]:
+        tok = ln.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1][2].append(("list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]], tok[4]))
+            else:
+                elements[-1][2].append(("scalar", _PLY_TYPES[tok[1]], tok[2]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"parse_mesh: PLY format {fmt!r} is neither ascii nor binary_little_endian")
+    body, pos = raw[nl + 1:], 0
+    words = body.split() if fmt == "ascii" else None
+    verts, polys = np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64)
+    for name, count, props in elements:
+        if name not in ("vertex", "face"):
+            if fmt == "ascii" or any(p[0] == "list" for p in props):
+                raise ValueError(f"parse_mesh: PLY element {name!r} is not supported")
+            pos += count * sum(np.dtype(p[1]).itemsize for p in props)
+            continue
+        if name == "vertex":
+            if any(p[0] == "list" for p in props) or not {"x", "y", "z"} <= {p[2] for p in props}:
+                raise ValueError("parse_mesh: PLY vertices need scalar properties x, y, z")
+            if fmt == "ascii":
+                tab = np.asarray(words[pos:pos + count * len(props)], np.float64).reshape(count, len(props))
+                pos += count * len(props)
+                col = {p[2]: i for i, p in enumerate(props)}
+                verts = np.stack([tab[:, col[c]] for c in "xyz"], axis=1).reshape(-1, 3)
+            else:
+                dt = np.dtype([(p[2], "<" + p[1]) for p in props])
+                tab = np.frombuffer(body, dt, count, pos)
+                pos += count * dt.itemsize
+                verts = np.stack([tab[c].astype(np.float64) for c in "xyz"], axis=1).reshape(-1, 3)
+        else:
+            if len(props) != 1 or props[0][0] != "list":
+                raise ValueError("parse_mesh: PLY faces need exactly one list property (vertex_indices)")
+            _, ct, it, _ = props[0]
+            faces = []
+            if fmt == "ascii":
+                for _ in range(count):
+                    k = int(words[pos])
+                    faces.append([int(w) for w in words[pos + 1:pos + 1 + k]])
+                    pos += 1 + k
+            elif count:
+                k0 = int(np.frombuffer(body, "<" + ct, 1, pos)[0])
+                dt = np.dtype([("n", "<" + ct), ("v", "<" + it, (k0, ))])
+                if len(body) - pos >= count * dt.itemsize and (np.frombuffer(body, dt, count, pos)["n"] == k0).all():   # every face alike
+                    faces = np.frombuffer(body, dt, count, pos)["v"].astype(np.int64).reshape(count, k0)
+                    pos += count * dt.itemsize
+                else:
+                    cs, isz = np.dtype(ct).itemsize, np.dtype(it).itemsize
+                    for _ in range(count):
+                        k = int(np.frombuffer(body, "<" + ct, 1, pos)[0])
+                        faces.append(np.frombuffer(body, "<" + it, k, pos + cs).astype(np.int64).tolist())
+                        pos += cs + k * isz
+            if not isinstance(faces, np.ndarray) and any(len(f) < 3 for f in faces):
+                raise ValueError("parse_mesh: a PLY face has fewer than 3 corners")
+            polys = _fan(faces)
+    return verts, polys
+
+
+def parse_mesh(raw: bytes) -> Tuple[np.ndarray, np.ndarray]:
+    """The contents of an OFF, OBJ or PLY file -> (verts float64 [n, 3], tris int64 [m, 3]); pure host code.  OFF: `COFF`, comment lines and
+    colours behind the indices are tolerated; OBJ: `v` and `f` lines, corners written i, i/t, i/t/n or i//n, negative indices counted back
+    from the vertices read so far, every other line ignored; PLY: ASCII, and binary little endian as mesh_file writes it (scalar vertex
+    properties with x, y, z among them, one list property per face).  Polygons are fan-triangulated: (p0 .. pk-1) gives (p0, pi, pi+1) for
+    i = 1 .. k - 2, so parse_mesh(mesh_file(v, f, fmt)) returns the lattice vertices and each quad as its two triangles.  An index outside
+    the vertex list is a ValueError."""
+    raw = bytes(raw)
+    if raw[:3] == b"ply":
+        verts, tris = _parse_ply(raw)
+    else:
+        text = raw.decode("latin-1")
+        first = next((ln.split("#", 1)[0].split() for ln in text.splitlines() if ln.split("#", 1)[0].split()), None)
+        if first is None:
+            return np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64)       # mesh_file's empty OBJ
+        verts, tris = _parse_off(text) if first[0] in ("OFF", "COFF") else _parse_obj(text)
+    if len(tris) and (tris.min() < 0 or tris.max() >= len(verts)):
+        raise ValueError(f"parse_mesh: a face names vertex {int(tris.min() if tris.min() < 0 else tris.max())} of {len(verts)}")
+    return verts, tris
+
+
+def _dims3(dims, who: str) -> Tuple[int, int, int]:
+    d = (int(dims), ) * 3 if np.ndim(dims) == 0 else tuple(int(x) for x in dims)
+    if len(d) != 3 or min(d) < 1 or max(d) > SURFACE_MAX_DIM:
+        raise ValueError(f"{who}: dims {d}, three numbers in 1 .. {SURFACE_MAX_DIM}")
+    return d
+
+
+def mesh_grid_fit(verts, dims, margin: float = 0.0) -> Tuple[List[float], float]:
+    """(translate, scale) of the .binvox header convention, grid coordinate = (p - translate) * max(dims) / scale, that maps the longest
+    side of the vertices' bounding box onto the grid and centres the box in it - the documented meaning of `binvox -cb`.  For dims that are
+    not a cube the side that fills its axis first decides.  margin: the fraction of every axis left free on each side (0 <= margin < 0.5).
+    A bounding box without extent (one point) keeps one model unit per voxel."""
+    d = np.asarray(_dims3(dims, "mesh_grid_fit"), np.float64)
+    v = np.asarray(verts, np.float64).reshape(-1, 3)
+    if not len(v) or not np.isfinite(v).all():
+        raise ValueError("mesh_grid_fit: needs at least one vertex, and finite ones")
+    if not 0.0 <= margin < 0.5:
+        raise ValueError(f"mesh_grid_fit: margin {margin} must lie in [0, 0.5)")
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    side = hi - lo
+    per_unit = float(np.min(d[side > 0] * (1.0 - 2.0 * margin) / side[side > 0])) if (side > 0).any() else 1.0   # voxels per model unit
+    translate = 0.5 * (lo + hi) - 0.5 * d / per_unit
+    return [float(t) for t in translate], float(d.max() / per_unit)
+
+
+def snap_vertices(grid_verts, dims, who: str = "snap_vertices") -> np.ndarray:
+    """Vertices in voxel units (float64 [n, 3]) -> int32 [n, 3] in units of 1 / VOXEL_UNITS voxel: floor(p * VOXEL_UNITS + 0.5) in
+    float64.  ValueError for a coordinate that is not finite or lies outside [-d, 2 d] voxels of its axis: sv_voxelise_meshes keeps its
+    products inside int64 only for such coordinates."""
+    d = np.asarray(_dims3(dims, who), np.float64)
+    g = np.asarray(grid_verts, np.float64).reshape(-1, 3)
+    if not np.isfinite(g).all():
+        raise ValueError(f"{who}: a vertex is not finite")
+    s = np.floor(g * VOXEL_UNITS + 0.5)
+    bad = np.argwhere((s < -d * VOXEL_UNITS) | (s > 2 * d * VOXEL_UNITS))
+    if len(bad):
+        n, a = (int(x) for x in bad[0])
+        raise ValueError(f"{who}: vertex {n} has coordinate {g[n, a]:.6g} on axis {a}, outside [{-d[a]:g}, {2 * d[a]:g}] voxels (one grid beside a "
+                         f"grid of {int(d[a])}): the exact integer arithmetic is sized for that range; fit the mesh to the grid first")
+    return s.astype(np.int32)
+
+
+def _mesh_arrays(mesh, who: str) -> Tuple[np.ndarray, np.ndarray]:
+    if isinstance(mesh, (bytes, bytearray, memoryview)):
+        return parse_mesh(bytes(mesh))
+    if len(mesh) != 2:
+        raise ValueError(f"{who}: a mesh is (verts, faces) or the contents of a mesh file")
+    verts = np.asarray(mesh[0], np.float64).reshape(-1, 3)
+    try:
+        tris = _fan(np.asarray(mesh[1]))
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
+    return verts, tris
+
+
+def pack_meshes(meshes, dims=32, fit="bbox", transform=None, who: str = "pack_meshes"):
+    """Host side of voxelise_mesh_batch: (packed int32 buffer - all snapped vertices, then all triangles -, mesh table int64 [B, 4] of
+    sv_voxelise_meshes, total vertices, total triangles, translates, scales).  Nothing here touches the GPU."""
+    d = _dims3(dims, who)
+    D = float(max(d))
+    if not len(meshes):
+        raise ValueError(f"{who}: no meshes")
+    M = None
+    if transform is not None:
+        M = np.asarray(transform, np.float64)
+        if M.shape not in ((3, 3), (3, 4)) or not np.isfinite(M).all():
+            raise ValueError(f"{who}: transform is a finite 3 x 3 or 3 x 4 matrix")
+    fits = None
+    if fit is not None and not (isinstance(fit, str) and fit == "bbox"):
+        fit = list(fit)
+        fits = [fit] * len(meshes) if len(fit) == 2 and not hasattr(fit[1], "__len__") else fit
+        if len(fits) != len(meshes) or any(len(f) != 2 or len(f[0]) != 3 or not float(f[1]) > 0 for f in fits):
+            raise ValueError(f"{who}: fit is 'bbox', None, (translate, scale) or one such pair per mesh, with scale > 0")
+    vs, ts, table, translates, scales, nv, nt = [], [], [], [], [], 0, 0
+    for i, mesh in enumerate(meshes):
+        verts, tris = _mesh_arrays(mesh, who)
+        if M is not None:
+            verts = verts @ M[:, :3].T + (M[:, 3] if M.shape[1] == 4 else 0.0)
+        if fit is None:
+            tr, sc = [0.0, 0.0, 0.0], D                                   # vertices are voxel units already
+        elif fits is not None:
+            tr, sc = [float(x) for x in fits[i][0]], float(fits[i][1])
+        elif len(verts):
+            tr, sc = mesh_grid_fit(verts, d)
+        else:
+            tr, sc = [0.0, 0.0, 0.0], 1.0
+        snapped = snap_vertices((verts - np.asarray(tr)[None, :]) * D / sc, d, f"{who}: mesh {i}")
+        tris = np.where((tris < 0) | (tris > 0x7fffffff), -1, tris).astype(np.int32)   # what int32 cannot hold is out of range anyway
+        vs.append(snapped.reshape(-1))
+        ts.append(tris.reshape(-1))
+        table.append([nv, len(snapped), nt, len(tris)])
+        nv, nt = nv + len(snapped), nt + len(tris)
+        translates.append(tr)
+        scales.append(sc)
+    packed = np.concatenate(vs + ts + [np.zeros(1, np.int32)])             # never empty
+    return packed, np.asarray(table, np.int64).reshape(-1, 4), nv, nt, translates, scales
+
+
+def voxelise_mesh_batch(meshes, dims=32, mode: str = "both", fit="bbox", transform=None, dtype=torch.float32, device="cuda"):
+    """B triangle meshes -> (volumes [B, d0, d1, d2] on the GPU, translates, scales): what the reference's utils/binvox_converter.py asks
+    the external `binvox` program for.  That program was never run next to this code and NO PARITY WITH IT IS CLAIMED; the rule - exact
+    integer arithmetic on coordinates snapped to 1 / 1024 voxel - is written out at sv_voxelise_meshes in the header.
+    meshes: a sequence of (verts [n, 3], faces [m, k >= 3], polygons fan-triangulated) or of file contents (parse_mesh).
+    dims: one number or three, each in 1 .. 64.  mode: "solid" (parity along z: the inside of a closed surface), "surface" (every voxel
+    whose closed cube a triangle touches) or "both" (their union, what `binvox -e` is documented to give).
+    transform: a 3 x 3 or 3 x 4 matrix applied to the vertices first - the reference's -rotx / -rotz turns and its (2, 0, 1)
+    transposition are such permutations of the axes.  fit: "bbox" = mesh_grid_fit per mesh; (translate, scale), or one pair per mesh, =
+    the .binvox header convention grid = (p - translate) * max(dims) / scale; None = the vertices are voxel units already (translate 0,
+    scale max(dims)).  The volumes are in xyz order, as decode_binvox_batch returns them, so they serve as `gt` directly; translates and
+    scales are what the .binvox header of each volume says (meshes_to_binvox).  dtype: float32, uint8 or bool.
+    A mesh without triangles gives an empty volume.  A vertex outside [-d, 2 d] voxels after the fit is a ValueError (snap_vertices), and
+    so is a face that names a vertex its mesh does not have - counted on the device, never dereferenced.  One host-to-device copy of the
+    packed vertices and triangles, one call of the entry, and one device-to-host copy: those counters."""
+    if mode not in _VOXELISE_MODES:
+        raise ValueError(f"voxelise_mesh_batch: mode {mode!r} is none of 'solid', 'surface', 'both'")
+    if dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise ValueError("voxelise_mesh_batch: dtype is float32, uint8 or bool")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("swinvox_amd: tensors must live on the GPU (no CPU path exists in the product)")
+    d0, d1, d2 = _dims3(dims, "voxelise_mesh_batch")
+    packed, table, nv, nt, translates, scales = pack_meshes(meshes, (d0, d1, d2), fit, transform, "voxelise_mesh_batch")
+    B = len(table)
+    buf = torch.from_numpy(packed).to(dev)
+    hip.check_cuda(buf)
+    out = torch.empty(B, d0, d1, d2, dtype=torch.float32 if dtype == torch.float32 else torch.uint8, device=buf.device)
+    ws = torch.empty(hip.load().sv_voxelise_meshes_workspace_bytes(B, d0, d1, d2), dtype=torch.uint8, device=buf.device)
+    table = np.ascontiguousarray(table)
+    call("sv_voxelise_meshes", ptr(buf), nv, ptr(buf) + 12 * nv, nt, table.ctypes.data, B, d0, d1, d2, _VOXELISE_MODES[mode],
+         0 if dtype == torch.float32 else 1, ptr(out), ptr(ws))
+    bad = ws[32 * B:36 * B].view(torch.int32).tolist()
+    if any(bad):
+        raise ValueError("voxelise_mesh_batch: " + ", ".join(f"mesh {i}: {n} face(s)" for i, n in enumerate(bad) if n) +
+                         " name a vertex outside the mesh's vertex list")
+    return (out.view(torch.bool) if dtype == torch.bool else out), translates, scales
+
+
+def meshes_to_binvox(meshes, dims=32, **kw) -> List[bytes]:
+    """B meshes -> B .binvox files (whole file contents), the job of the reference's utils/binvox_converter.py: voxelise_mesh_batch (its
+    keywords pass through), then encode_binvox_batch with each mesh's translate and scale in the header, so that
+    decode_binvox_batch(meshes_to_binvox(m)) is voxelise_mesh_batch(m)[0]."""
+    kw.pop("dtype", None)
+    volumes, translates, scales = voxelise_mesh_batch(meshes, dims, dtype=torch.uint8, **kw)
+    return encode_binvox_batch(volumes, translate=translates, scale=scales)
 
 
 # ---- volume views -----------------------------------------------------------------------------------------------------------

@@ -246,6 +246,8 @@ _PROTOS = {
     "sv_binvox_encode": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _L, _P]),
     "sv_voxel_surface": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _L, _P, _L, _P]),
     "sv_render_volumes": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_voxelise_meshes_workspace_bytes": (C.c_size_t, None, [_I, _I, _I, _I]),
+    "sv_voxelise_meshes": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sv_augment_views": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "sv_augment_views_bg": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_augment_images": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
